@@ -14,9 +14,11 @@ projected `wv` rows + all-gather of the [G,15] Bipartite output over RCCL/xGMI) 
 `python bench.py --gpus N` launches its own N ranks (torch.distributed.run on 127.0.0.1) when it is not already
 running under one (WORLD_SIZE unset); under `torchrun` it reads RANK / LOCAL_RANK / WORLD_SIZE as usual.
 
-Prints ONE JSON line (rank 0). Extra objects: `roofline` (path-level algorithmic bytes B_alg x windows/s
-against the 8 TB/s HBM peak; per-kernel HIP-event times and counter traffic as extras) and `cpu_baseline` (the oracle's
-reference-formulation forward on the host cores, rank 0, N=1).
+Prints ONE JSON line (rank 0) with `roofline` (path-level algorithmic bytes B_alg x windows/s against the 8 TB/s
+HBM peak). A plain run sets up, warms up, times the steps and prints it (`--dump-outputs DIR` also writes what the last timed step
+returned). `--full` adds everything else, each from runs of its own: the cold-GPU figure, per-kernel HIP-event times and counter
+traffic, the window pipeline, the training / streaming / day-loop / config-4 legs, per-phase times and `cpu_baseline` (the oracle's
+reference-formulation forward on the host cores, rank 0, N=1) with its parity checks.
 """
 import argparse
 import json
@@ -50,13 +52,38 @@ F_NODE = {"k_stage1": 2.0 * (240 + 3840 + 3600 + 2820) + 690.0, "k_stage2": 2.0 
 F16_EXEC_FLOP_NODE = 120 * 32768.0 / 32.0
 F16_MFMA_PEAK_TF = 2500.0   # MI355X_MICROARCH.md: dense bf16 / fp16
 FLOP_NODE = 22980.0 + 1380.0   # reference dense + gather adds per product node
+DUMP_MAX_BYTES = 64 << 20      # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write {name: tensor} as out_dir/<name>.npy, float32 (float64 stays float64), in the order given. An array
+    larger than what is left of DUMP_MAX_BYTES is replaced by a fixed sample of its rows (seed 0, ascending row order), so that two
+    builds given the same arguments write the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_MAX_BYTES
+    for name, t in arrays.items():
+        v = np.atleast_1d(t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t))
+        v = np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32)
+        if v.nbytes > left:
+            keep = left // max(1, v.nbytes // max(1, v.shape[0]))
+            v = v[np.sort(np.random.default_rng(0).choice(v.shape[0], min(keep, v.shape[0]), replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+        left -= v.nbytes
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=300)
-    ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 300; --mode train: 50)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed warm-up steps before them (default 30; --mode train: 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the line measures besides its headline: the cold-GPU figure, the window pipeline, per-kernel and "
+                         "counter roofline figures, the training / streaming / day-loop / config-4 legs, the CPU baselines with their "
+                         "parity checks, per-phase times (the --no-* switches below trim it). Off: set up, warm up, time the steps, "
+                         "print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32, "
+                         "float64 kept; %d MB at most, a larger array as a fixed seeded sample of its rows)" % (DUMP_MAX_BYTES >> 20))
     ap.add_argument("--settle", type=int, default=1500,
                     help="untimed windows run during set-up, before the W warm-up steps: the GPU clocks need ~0.5 s of sustained "
                          "load to settle (a cold start reads 5-10 %% slow for the first few hundred windows; DESIGN.md section 5)")
@@ -85,18 +112,18 @@ def parse():
                          "host memory (dist.Transport); its timings mean nothing and the line says so")
     ap.add_argument("--cpu-windows", type=int, default=3, help="cpu_baseline: timed windows after one warm-up (median)")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="N = 1 default run: skip the two rocprofv3 --pmc passes that measure roofline.traffic in this run (the line "
+                    help="N = 1 with --full: skip the two rocprofv3 --pmc passes that measure roofline.traffic in this run (the line "
                          "then carries the constants of the committed profile)")
-    ap.add_argument("--no-train-step", action="store_true", help="skip the live config-3 training-step figure of the default line")
-    ap.add_argument("--no-stream", action="store_true", help="skip the live config-5 streaming figure of the default line")
-    ap.add_argument("--no-day-loops", action="store_true", help="skip the refine / association loop figures of the default line")
+    ap.add_argument("--no-train-step", action="store_true", help="skip the live config-3 training-step figure of the N = 1 --full line")
+    ap.add_argument("--no-stream", action="store_true", help="skip the live config-5 streaming figure of the N = 1 --full line")
+    ap.add_argument("--no-day-loops", action="store_true", help="skip the refine / association loop figures of the N = 1 --full line")
     ap.add_argument("--emulate-world", type=int, default=None,
                     help="N = 1: time every rank of the W-rank shard plan of the sharded workload alone on this GPU (collectives replaced by "
                          "device copies of the same size) and report per-rank ms, imbalance, halo MB and the projected speed-up over the "
-                         "one-GPU time -- labelled projected, no xGMI. With --mode sharded: only that. The default N = 1 line carries it "
+                         "one-GPU time -- labelled projected, no xGMI. With --mode sharded: only that. The N = 1 --full line carries it "
                          "for W = 8 as `projected_scaling_8` (skip with --no-cfg4-one-gpu)")
     ap.add_argument("--no-cfg4-one-gpu", action="store_true",
-                    help="N = 1 default run: skip the short measurement of the N > 1 workload (config 4, one window sharded over source "
+                    help="N = 1 with --full: skip the short measurement of the N > 1 workload (config 4, one window sharded over source "
                          "nodes) on this one GPU that the line carries as `sharded_workload_on_one_gpu`")
     return ap.parse_args()
 
@@ -402,6 +429,9 @@ def main_stream(a, geom, nq, rank, world, dev, dist, emit=True):
         drain(a.warmup + a.steps)
         barrier()
         dtm = time.perf_counter() - t0
+    if rank == 0 and a.dump_outputs:
+        # what the caller keeps: the columns of Out_2 the windows of this run were stacked into
+        dump_outputs(a.dump_outputs, {"Out_2": Out_2[:, int(t_all[0]):int(t_all[-1]) + 9].T})
     if dist is not None:
         t = torch.tensor([dtm], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -546,11 +576,13 @@ def main_sharded(a, geom, n_picks, nq, rank, world, dev, dist, emit=True, one_ra
             y, x = step()
         barrier()
         dt = time.perf_counter() - t0
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"y": y, "x": x})
     if dist is not None:
         t = torch.tensor([dt], device=dev if dist.get_backend() == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    phases = sharded_phases(net, Slice, Mask, xg, xq, tq, barrier, min(a.steps, 5))
+    phases = sharded_phases(net, Slice, Mask, xg, xq, tq, barrier, min(a.steps, 5)) if a.full else None
     ranks = world if dist is None else int(dist.get_world_size())
     wps = a.steps / dt
     b_alg = 1532.0 * S * G + 816.0 * G
@@ -781,8 +813,9 @@ def main_train(a, geom, n_picks, nq, rank, world, dev, dist, emit=True):
     net.train()
     opt = torch.optim.Adam(net.parameters(), lr=1e-3)
     losses = []
+    last = {}
 
-    def step(i):
+    def step(i, keep=False):
         k = i % len(dS)
         opt.zero_grad(set_to_none=True)
         y, x = net.forward_fixed_source(dS[k], dM[k], None, None, None, locs, xg, xq, tq)
@@ -790,6 +823,8 @@ def main_train(a, geom, n_picks, nq, rank, world, dev, dist, emit=True):
         loss.backward()
         opt.step()
         losses.append(loss.detach())
+        if keep:
+            last.update(loss=loss.detach(), y=y.detach(), x=x.detach())
 
     def barrier():
         if dist is not None:
@@ -802,9 +837,11 @@ def main_train(a, geom, n_picks, nq, rank, world, dev, dist, emit=True):
     losses.clear()
     t0 = time.perf_counter()
     for i in range(a.steps):
-        step(i)
+        step(i, keep=i == a.steps - 1 and bool(a.dump_outputs))
     barrier()
     dt = time.perf_counter() - t0
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, last)
     if dist is not None:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -812,59 +849,62 @@ def main_train(a, geom, n_picks, nq, rank, world, dev, dist, emit=True):
     ms = dt / a.steps * 1e3
     loss_vals = [float(v) for v in losses]
     # ---- phases with HIP events on the launch stream (the same entry points, called directly)
-    hp = net._hip
-    knn = net.SpatialAttention.query_table(xq, xg, 10)
-    ph = {k: [] for k in ("fwd_front", "fwd_total", "bwd_tail", "bwd_front")}
-    for i in range(min(a.steps, 10)):
-        e = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
-        e[0].record()
-        r_, xl_, save = hp.train_fwd(dS[0], dM[0], net._edge_attr, want_x_latent=False)
-        e[1].record()
-        del r_, xl_, save
-        e[2].record()
-        y, x, xs, _, _, save, tsave = hp.path_train_fwd(dS[0], dM[0], net._edge_attr, xg, xq, knn, tq)
-        e[3].record()
-        d_r, blob = hp.tail_train_bwd(xg, xq, knn, tq, tsave, y[:, :, 0].contiguous(), x[:, :, 0].contiguous())
-        e[4].record()
-        hp.train_bwd(dS[0], dM[0], net._edge_attr, save, d_r[:, :30])
-        e[5].record()
-        torch.cuda.synchronize()
-        ph["fwd_front"].append(e[0].elapsed_time(e[1])); ph["fwd_total"].append(e[2].elapsed_time(e[3]))
-        ph["bwd_tail"].append(e[3].elapsed_time(e[4])); ph["bwd_front"].append(e[4].elapsed_time(e[5]))
-        del y, x, xs, save, tsave, d_r, blob
-    pms = {k: round(float(np.median(v)), 4) for k, v in ph.items()}
-    pms["fwd_tail"] = round(pms["fwd_total"] - pms["fwd_front"], 4)
-    pms["adam_loss_and_host"] = round(ms - pms["fwd_total"] - pms["bwd_tail"] - pms["bwd_front"], 4)
+    pms = None
+    if a.full:
+        hp = net._hip
+        knn = net.SpatialAttention.query_table(xq, xg, 10)
+        ph = {k: [] for k in ("fwd_front", "fwd_total", "bwd_tail", "bwd_front")}
+        for i in range(min(a.steps, 10)):
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+            e[0].record()
+            r_, xl_, save = hp.train_fwd(dS[0], dM[0], net._edge_attr, want_x_latent=False)
+            e[1].record()
+            del r_, xl_, save
+            e[2].record()
+            y, x, xs, _, _, save, tsave = hp.path_train_fwd(dS[0], dM[0], net._edge_attr, xg, xq, knn, tq)
+            e[3].record()
+            d_r, blob = hp.tail_train_bwd(xg, xq, knn, tq, tsave, y[:, :, 0].contiguous(), x[:, :, 0].contiguous())
+            e[4].record()
+            hp.train_bwd(dS[0], dM[0], net._edge_attr, save, d_r[:, :30])
+            e[5].record()
+            torch.cuda.synchronize()
+            ph["fwd_front"].append(e[0].elapsed_time(e[1])); ph["fwd_total"].append(e[2].elapsed_time(e[3]))
+            ph["bwd_tail"].append(e[3].elapsed_time(e[4])); ph["bwd_front"].append(e[4].elapsed_time(e[5]))
+            del y, x, xs, save, tsave, d_r, blob
+        pms = {k: round(float(np.median(v)), 4) for k, v in ph.items()}
+        pms["fwd_tail"] = round(pms["fwd_total"] - pms["fwd_front"], 4)
+        pms["adam_loss_and_host"] = round(ms - pms["fwd_total"] - pms["bwd_tail"] - pms["bwd_front"], 4)
     # ---- the reference's 4-output step (association heads included), a few steps
     four = None
-    try:
-        smp = synthetic.training_sample(geom, min(n_picks, 4000), n_src=4, seed=3, window=0)
-        # (the time-pointer tables of this sample; the graphs were set by set_adjacencies_base above)
-        net.A_edges_p, net.A_edges_s = t(smp["A_edges_p"]).long(), t(smp["A_edges_s"]).long()
-        net.dt_partition, net.tlatent = t(smp["dt_partition"]), t(smp["tlatent"])
-        from genie_amd import train as gtrain
-        args4 = (t(smp["Slice"]), t(smp["Mask"]), t(smp["tpick"]), t(smp["ipick"]).long(), t(smp["phase_label"]), locs, xg, xq,
-                 t(smp["x_query_src"]), tq, t(smp["tq_sample"]), t(smp["trv_out_q"]))
-        lab4 = (t(smp["Lbls"]), t(smp["Lbls_query"]), t(smp["pick_lbls"]))
+    if a.full:
+        try:
+            smp = synthetic.training_sample(geom, min(n_picks, 4000), n_src=4, seed=3, window=0)
+            # (the time-pointer tables of this sample; the graphs were set by set_adjacencies_base above)
+            net.A_edges_p, net.A_edges_s = t(smp["A_edges_p"]).long(), t(smp["A_edges_s"]).long()
+            net.dt_partition, net.tlatent = t(smp["dt_partition"]), t(smp["tlatent"])
+            from genie_amd import train as gtrain
+            args4 = (t(smp["Slice"]), t(smp["Mask"]), t(smp["tpick"]), t(smp["ipick"]).long(), t(smp["phase_label"]), locs, xg, xq,
+                     t(smp["x_query_src"]), tq, t(smp["tq_sample"]), t(smp["trv_out_q"]))
+            lab4 = (t(smp["Lbls"]), t(smp["Lbls_query"]), t(smp["pick_lbls"]))
 
-        def step4():
-            opt.zero_grad(set_to_none=True)
-            loss = gtrain.reference_loss(net.forward_fixed(*args4), lab4, 1)
-            loss.backward()
-            opt.step()
-        for _ in range(2):
-            step4()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        for _ in range(5):
-            step4()
-        torch.cuda.synchronize()
-        four = {"ms_per_step": round((time.perf_counter() - t1) / 5 * 1e3, 3), "n_picks": int(len(smp["tpick"])), "n_src": 4,
-                "note": "mz(*input_tensors) + 4-term loss + backward + Adam; every module in HIP in both directions: shared path (source "
-                        "queries riding along), BipartiteGraphReadOutOperator + DataAggregationAssociationPhase, LocalSliceLgCollapse P / S, "
-                        "StationSourceAttentionMergedPhases; PyTorch: the loss, Adam, index plumbing"}
-    except Exception as e:
-        four = {"error": repr(e)[:200]}
+            def step4():
+                opt.zero_grad(set_to_none=True)
+                loss = gtrain.reference_loss(net.forward_fixed(*args4), lab4, 1)
+                loss.backward()
+                opt.step()
+            for _ in range(2):
+                step4()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            for _ in range(5):
+                step4()
+            torch.cuda.synchronize()
+            four = {"ms_per_step": round((time.perf_counter() - t1) / 5 * 1e3, 3), "n_picks": int(len(smp["tpick"])), "n_src": 4,
+                    "note": "mz(*input_tensors) + 4-term loss + backward + Adam; every module in HIP in both directions: shared path (source "
+                            "queries riding along), BipartiteGraphReadOutOperator + DataAggregationAssociationPhase, LocalSliceLgCollapse P / S, "
+                            "StationSourceAttentionMergedPhases; PyTorch: the loss, Adam, index plumbing"}
+        except Exception as e:
+            four = {"error": repr(e)[:200]}
     # ---- the reference's call convention: `mz(*input_tensors)` with NEW graphs per sample (train_GENIE_model.py:1722-1786: another
     # station subset, grid and product edge lists every sample), so `forward` verifies the lists and rebuilds the HIP context per step
     rebuild = None
@@ -897,7 +937,7 @@ def main_train(a, geom, n_picks, nq, rank, world, dev, dist, emit=True):
                              "size (200 x 10 000: the oracle's autograd needs minutes per step) the tests assert finite, decreasing, "
                              "bitwise-reproducible steps only",
     }
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and emit:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and emit:
         c_full, gs, c_s = cpu_train_baseline(geom, wins[0], lbl, lbl_q)
         out["cpu_baseline"] = {"value": round(n_picks / c_full, 1), "unit": "picks/s", "cores": int(torch.get_num_threads()), "kind": "port",
                                "physical_cores": physical_cores(),
@@ -1002,6 +1042,10 @@ def main():
         a.mode = "sharded" if world > 1 else "replicas"
     if a.config is None:
         a.config = "cfg4_2000x50k" if (a.mode == "sharded" and world > 1) else "cfg2_200x10k"
+    if a.steps is None:                 # the window defaults are too many for a training step
+        a.steps = 50 if a.mode == "train" else 300
+    if a.warmup is None:
+        a.warmup = 5 if a.mode == "train" else 30
     dist = None
     if world > 1:
         import torch.distributed as dist
@@ -1029,11 +1073,11 @@ def main():
         if world == 1:
             return main_sharded(a, geom, n_picks, nq, rank, world, dev, dist)
         out = main_sharded(a, geom, n_picks, nq, rank, world, dev, dist, emit=False)       # (destroys the process group)
-        if rank == 0:
+        if rank == 0 and a.full:
             # the one-GPU figure of the SAME workload, measured live on this rank after the sharded run (not a constant)
             import copy
             a1 = copy.copy(a)
-            a1.steps, a1.warmup, a1.no_overlap = 5, 2, False
+            a1.steps, a1.warmup, a1.no_overlap, a1.dump_outputs = 5, 2, False, None
             torch.cuda.empty_cache()
             try:
                 o1 = main_sharded(a1, geom, n_picks, nq, 0, 1, dev, None, emit=False, one_rank_group=False)
@@ -1046,13 +1090,12 @@ def main():
                                               "source": "measured live on rank 0 after the sharded run, same code path with one rank"}
             except Exception as e:
                 out["one_gpu_same_config"] = {"error": repr(e)[:200]}
+        if rank == 0:
             emit_line(json.dumps(out))
         return out
     if a.mode == "stream":
         return main_stream(a, geom, nq, rank, world, dev, dist)
     if a.mode == "train":
-        if a.steps == 300 and a.warmup == 30:       # the window defaults are too many for a training step
-            a.steps, a.warmup = 50, 5
         return main_train(a, geom, n_picks, nq, rank, world, dev, dist)
     net = build_model(geom, dev)
     # synthetic pick windows of the fixed shape, resident in HBM (each rank its own windows)
@@ -1098,41 +1141,96 @@ def main():
         return net.forward_fixed_source(dS[k], dM[k], None, None, None, locs, xg, xq, tq)
 
     def timed(n):
+        """n literal calls between two barriers: (seconds, what the last call returned)."""
         barrier()
         t0 = time.perf_counter()
-        for i in range(n):
+        for i in range(n - 1):
             literal(i)
+        last = literal(n - 1)
         barrier()
-        return time.perf_counter() - t0
+        return time.perf_counter() - t0, last
 
+    dt_cold = dt_long = n_long = None
     with torch.no_grad():
-        # (1) the command as given: W warm-up calls, K timed calls on a GPU that has done nothing else yet -> `cold_ms_per_step`
-        for i in range(a.warmup):
-            literal(i)
-        dt_cold = timed(a.steps)
+        if a.full:
+            # (1) the command as given: W warm-up calls, K timed calls on a GPU that has done nothing else yet -> `cold_ms_per_step`
+            for i in range(a.warmup):
+                literal(i)
+            dt_cold, _ = timed(a.steps)
         # (2) clock settle: untimed windows (their own key `settle_windows`; the GPU clocks need ~0.5 s of sustained load, a cold
-        # start reads 5-10 % slow), then W warm-up calls and K timed calls again -> `value` / `ms_per_step` (the steady state an apply
-        # loop over a day runs in), and a longer timed region next to it when K calls last under 0.1 s
+        # start reads 5-10 % slow), then W warm-up calls and K timed calls -> `value` / `ms_per_step` (the steady state an apply
+        # loop over a day runs in); with --full a longer timed region next to it when K calls last under 0.1 s
         for i in range(a.settle):
             literal(i)
         for i in range(a.warmup):
             literal(i)
-        dt = timed(a.steps)
-        n_long = max(a.steps, 1000) if dt < 0.1 else None
-        dt_long = timed(n_long) if n_long else None
+        dt, (y_last, x_last) = timed(a.steps)
+        if rank == 0 and a.dump_outputs:
+            dump_outputs(a.dump_outputs, {"y": y_last, "x": x_last})
+        del y_last, x_last
+        if a.full:
+            n_long = max(a.steps, 1000) if dt < 0.1 else None
+            dt_long = timed(n_long)[0] if n_long else None
     if dist is not None:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-        tc = torch.tensor([dt_cold], device=dev, dtype=torch.float64)
-        dist.all_reduce(tc, op=dist.ReduceOp.MAX)
-        dt_cold = float(tc.item())
+        if dt_cold is not None:
+            tc = torch.tensor([dt_cold], device=dev, dtype=torch.float64)
+            dist.all_reduce(tc, op=dist.ReduceOp.MAX)
+            dt_cold = float(tc.item())
     ms_per_step = dt / a.steps * 1e3
     windows_per_s = world * a.steps / dt
     value = windows_per_s * n_picks
 
-    # ---- the apply loop's window pipeline over independent windows (push_window / flush_windows: P-sized kernels per window on the
-    # main stream, G-sized tails of `tail_batch` windows per set of launches on side streams): an extra, not the headline
+    hp = net._hip
+    info = hp.stage_precision()
+    prec_detail = ("fp32 in / out, fp32 accumulation; P-sized stages %s (fp16 range guard of the committed weights: largest hidden-state bound "
+                   "%.4g, largest weight %.4g, limit 60000; mode %s)"
+                   % ("multiply on the 16-bit matrix pipe with every fp32 operand as two fp16 pieces (three partial products per product)"
+                      if info["f16x2_active"] else "on fp32 MFMA", info["act_bound"], info["weight_bound"], info["mode"]))
+    P = S * G
+    b_alg = 1532.0 * P + 816.0 * G
+    path_gbs = b_alg * (windows_per_s / world) / 1e9
+    fused_bytes = (B_NODE["k_stage1"] + B_NODE["k_stage2"]) * P + 816.0 * G
+    # SURVEY.md 8d: the path is priced against the HBM roofline on its ALGORITHMIC bytes (reference dataflow at layer
+    # granularity, B_alg per window); the fused kernels move fewer real bytes, so with --full the per-kernel figures (algorithmic bytes
+    # of what each kernel has to touch, HIP-event time on the launch stream, counter traffic measured in the run) are reported next
+    # to it. Stage 1 additionally reports the fp16 FLOPs it executes against the 16-bit matrix peak: it is the one compute-bound
+    # kernel of the path.
+    roofline = {"bound": "hbm", "kernel": "path (B_alg = 1532 P + 816 G bytes per window, SURVEY.md 8d)",
+                "achieved": round(path_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(path_gbs / HBM_PEAK_GBS, 4),
+                # the same window time against the bytes the FUSED design itself has to move (616 B per product node: h0 / h1 / u / v never
+                # leave the registers) -- the design's own HBM floor, far below `frac`, which prices the reference dataflow's bytes
+                "fused_bytes_per_window": fused_bytes,
+                "fused_bytes_frac": round(fused_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                "alg_bytes_per_window": b_alg, "fp32_tflops": round(FLOP_NODE * P * (windows_per_s / world) / 1e12, 2)}
+    workload = ("%s: %d stations / %d grid nodes / %d picks per window; one step = ONE literal call forward_fixed_source(Slice, Mask, tpick, "
+                "ipick, phase_label, locs, x_grid, x_query, t_query) of the reference's signature on one stream, both read-outs included, "
+                "graphs preset, inputs resident in HBM. " % (a.config, S, G, n_picks))
+    out = {
+        "metric": "picks/sec through GCN_Detection_Network_extended.forward_fixed_source (GCS_Network.forward)",
+        "value": round(value, 1), "unit": "picks/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "dtype_detail": prec_detail,
+        "settle_windows": a.settle,
+        "config": {"workload": workload + "`value` / `ms_per_step` = %d warm-up + %d timed calls after %d untimed clock-settle windows "
+                                          "(`settle_windows`)" % (a.warmup, a.steps, a.settle),
+                   "n_stations": S, "n_grid": G, "n_picks": n_picks, "n_query": nq,
+                   "parallelism": "window-parallel replicas x%d" % world if world > 1 else "single GPU"},
+        "windows_per_s": round(windows_per_s, 2),
+        "roofline": roofline,
+    }
+    if not a.full:
+        if rank == 0:
+            emit_line(json.dumps(out))
+        if dist is not None:
+            dist.destroy_process_group()
+        return out
+
+    # ---- --full: the apply loop's window pipeline over independent windows (push_window / flush_windows: P-sized kernels per window
+    # on the main stream, G-sized tails of `tail_batch` windows per set of launches on side streams): an extra, not the headline
     pipe_ms = None
     if not a.no_pipeline:
         npipe = max(a.steps, 160)
@@ -1150,13 +1248,6 @@ def main():
     drop_in_ms = ms_per_step
 
     # ---- dominant-kernel timing with HIP events on the launch stream (staged API = same kernels) ----
-    hp = net._hip
-    info = hp.stage_precision()
-    prec_detail = ("fp32 in / out, fp32 accumulation; P-sized stages %s (fp16 range guard of the committed weights: largest hidden-state bound "
-                   "%.4g, largest weight %.4g, limit 60000; mode %s)"
-                   % ("multiply on the 16-bit matrix pipe with every fp32 operand as two fp16 pieces (three partial products per product)"
-                      if info["f16x2_active"] else "on fp32 MFMA", info["act_bound"], info["weight_bound"], info["mode"]))
-    P = S * G
     ev = {k: [] for k in ("k_stage1", "k_stage2", "path")}
     torch.cuda.synchronize()
     with torch.no_grad():
@@ -1177,13 +1268,6 @@ def main():
             ev["k_stage2"].append(e[1].elapsed_time(e[2]))
             ev["path"].append(e[0].elapsed_time(e[3]))
     kms = {k: float(np.median(v)) for k, v in ev.items()}
-    b_alg = 1532.0 * P + 816.0 * G
-    path_gbs = b_alg * (windows_per_s / world) / 1e9
-    # the path is priced against the HBM roofline on its ALGORITHMIC bytes (reference dataflow at layer
-    # granularity, B_alg per window); the fused kernels move fewer real bytes, so the per-kernel figures (algorithmic bytes of
-    # what each kernel has to touch, HIP-event time on the launch stream, counter traffic from the committed PMC profile) are
-    # reported next to it. Stage 1 additionally reports the fp16 FLOPs it executes against the 16-bit matrix peak: it is the
-    # one compute-bound kernel of the path.
     kern = {}
     for k in ("k_stage1", "k_stage2"):
         gbs = B_NODE[k] * P / (kms[k] * 1e-3) / 1e9
@@ -1195,47 +1279,25 @@ def main():
     kern["k_stage1"]["executed_f16"] = {"tflops": round(exec_tf, 1), "peak": F16_MFMA_PEAK_TF, "frac": round(exec_tf / F16_MFMA_PEAK_TF, 4),
                                          "note": "fp32 operands as two fp16 pieces, three partial products per product, fp32 accumulation"}
     kern["k_stage2"]["kernels"] = "k_stage2_h2u"
-    fused_bytes = (B_NODE["k_stage1"] + B_NODE["k_stage2"]) * P + 816.0 * G
-    roofline = {"bound": "hbm", "kernel": "path (B_alg = 1532 P + 816 G bytes per window, SURVEY.md 8d)",
-                "achieved": round(path_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(path_gbs / HBM_PEAK_GBS, 4),
-                "traffic": None, "hbm_real_frac": None,
-                # the same window time against the bytes the FUSED design itself has to move (616 B per product node: h0 / h1 / u / v never
-                # leave the registers) -- the design's own HBM floor, far below `frac`, which prices the reference dataflow's bytes
-                "fused_bytes_per_window": fused_bytes,
-                "fused_bytes_frac": round(fused_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                "pipelined_frac": round(b_alg / (pipe_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if pipe_ms else None,
-                "traffic_source": "not measured in this run (rocprofv3 unavailable, --no-live-traffic, or the bench is itself being profiled)",
-                "alg_bytes_per_window": b_alg, "kernels": kern, "single_stream_path_ms": round(kms["path"], 4),
-                "fp32_tflops": round(FLOP_NODE * P * (windows_per_s / world) / 1e12, 2)}
-
-    out = {
-        "metric": "picks/sec through GCN_Detection_Network_extended.forward_fixed_source (GCS_Network.forward)",
-        "value": round(value, 1), "unit": "picks/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "dtype_detail": prec_detail,
-        "settle_windows": a.settle,
+    roofline.update({"traffic": None, "hbm_real_frac": None,
+                     "pipelined_frac": round(b_alg / (pipe_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if pipe_ms else None,
+                     "traffic_source": "not measured in this run (rocprofv3 unavailable, --no-live-traffic, or the bench is itself being profiled)",
+                     "kernels": kern, "single_stream_path_ms": round(kms["path"], 4)})
+    out["config"]["workload"] = (workload + "`cold_ms_per_step` = the command as given (%d warm-up calls, then %d timed calls on an idle GPU); "
+                                 "`value` / `ms_per_step` / `settled_ms_per_step` = %d warm-up + %d timed calls again after %d untimed "
+                                 "clock-settle windows (`settle_windows`; --settle 0 makes the two the same measurement)%s"
+                                 % (a.warmup, a.steps, a.warmup, a.steps, a.settle,
+                                    "; `settled_long_run` = %d more timed calls (the %d requested ones last under 0.1 s)" % (n_long, a.steps) if n_long else ""))
+    out.update({
         "cold_ms_per_step": round(dt_cold / a.steps * 1e3, 4),
         "settled_ms_per_step": round(ms_per_step, 4),
         "settled_long_run": {"steps": n_long, "ms_per_step": round(dt_long / n_long * 1e3, 4)} if n_long else None,
-        "config": {"workload": "%s: %d stations / %d grid nodes / %d picks per window; one step = ONE literal call forward_fixed_source(Slice, "
-                               "Mask, tpick, ipick, phase_label, locs, x_grid, x_query, t_query) of the reference's signature on one stream, both "
-                               "read-outs included, graphs preset, inputs resident in HBM. `cold_ms_per_step` = the command as given (%d warm-up "
-                               "calls, then %d timed calls on an idle GPU); `value` / `ms_per_step` / `settled_ms_per_step` = %d warm-up + %d timed "
-                               "calls again after %d untimed clock-settle windows (`settle_windows`; --settle 0 makes the two the same "
-                               "measurement)%s"
-                               % (a.config, S, G, n_picks, a.warmup, a.steps, a.warmup, a.steps, a.settle,
-                                  "; `settled_long_run` = %d more timed calls (the %d requested ones last under 0.1 s)" % (n_long, a.steps) if n_long else ""),
-                   "n_stations": S, "n_grid": G, "n_picks": n_picks, "n_query": nq,
-                   "parallelism": "window-parallel replicas x%d" % world if world > 1 else "single GPU"},
-        "windows_per_s": round(windows_per_s, 2),
         "pipelined_windows_ms": round(pipe_ms, 4) if pipe_ms else None, "tail_batch": 1 if a.no_pipeline else tail_batch,
         "pipelined_windows_note": "the apply loop's form over independent windows (push_window / flush_windows: P-sized kernels per window, G-sized "
                                   "tails and read-outs of %d windows per set of launches on side streams; bit-identical results): an extra, `value` "
                                   "is the literal call" % tail_batch,
         "drop_in_call_ms": round(drop_in_ms, 4),
-        "roofline": roofline,
-    }
+    })
     if rank == 0 and world == 1 and a.config == "cfg2_200x10k" and not a.no_pipeline and not a.no_live_traffic:
         tr = measure_traffic()
         if tr is not None:
@@ -1255,7 +1317,7 @@ def main():
         # same code path (a few windows), so that a scaling curve over N = 1, 2, 4, 8 has its own N = 1 point.
         import copy
         a4 = copy.copy(a)
-        a4.config, a4.steps, a4.warmup, a4.no_overlap = "cfg4_2000x50k", 5, 2, False
+        a4.config, a4.steps, a4.warmup, a4.no_overlap, a4.dump_outputs = "cfg4_2000x50k", 5, 2, False, None
         S4, G4, np4, L4, nq4 = synthetic.CONFIGS[a4.config]
         try:
             o4 = main_sharded(a4, synthetic.Geometry(S4, G4, L=L4, n_query=nq4, seed=1), np4, nq4, 0, 1, dev, None, emit=False)
@@ -1285,7 +1347,7 @@ def main():
         # BASELINE config 3 (the training step on this same shape), measured live through `--mode train`'s code path
         import copy
         a3 = copy.copy(a)
-        a3.steps, a3.warmup, a3.no_cpu_baseline = 10, 3, True
+        a3.steps, a3.warmup, a3.no_cpu_baseline, a3.dump_outputs = 10, 3, True, None
         try:
             o3 = main_train(a3, geom, n_picks, nq, 0, 1, dev, None, emit=False)
             out["training_step_config3"] = {"config": o3["config"]["workload"], "steps": a3.steps, "ms_per_step": o3["ms_per_step"],
@@ -1301,7 +1363,7 @@ def main():
         # live through `--mode stream`'s code path
         import copy
         a5 = copy.copy(a)
-        a5.steps, a5.warmup = 320, 64
+        a5.steps, a5.warmup, a5.dump_outputs = 320, 64, None
         try:
             o5 = main_stream(a5, geom, nq, 0, 1, dev, None, emit=False)
             out["streaming_config5"] = {"config": o5["config"]["workload"], "steps": a5.steps, "ms_per_step": o5["ms_per_step"],

@@ -73,3 +73,26 @@ def test_bench_dry_run_halo_bytes_at_the_config4_shape_with_eight_ranks():
     assert len(h["MB_in_per_rank"]) == 8 and 30.0 < min(h["MB_in_per_rank"]) and h["MB_in_max"] < 160.0
     assert 20.0 < h["largest_pair_MB"] < 80.0 and h["largest_pair_ms_at_153_GBs"] < 0.55
     assert all(1 <= n <= 7 for n in h["peers_per_rank"])
+
+
+def test_dump_outputs_writes_float32_and_samples_rows_past_the_budget(tmp_path, monkeypatch):
+    """`--dump-outputs`: one float32 .npy per array (float64 kept), and an array past the byte budget becomes the same seeded sample of
+    its rows on every call, so that two builds given the same arguments can be compared element for element."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import importlib
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4096)
+    big = torch.arange(1000 * 8, dtype=torch.float64).view(1000, 8).float()          # 32 000 B > 4096 - 40
+    small = torch.tensor([1.5, 2.5], dtype=torch.float64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"loss": small, "x": big, "n": torch.tensor(3)})
+    s, x = np.load(tmp_path / "a" / "loss.npy"), np.load(tmp_path / "a" / "x.npy")
+    assert s.dtype == np.float64 and s.tolist() == [1.5, 2.5]
+    assert x.dtype == np.float32 and x.shape[1] == 8 and 0 < x.shape[0] < 1000 and x.nbytes <= 4096 - s.nbytes
+    rows = x[:, 0] / 8
+    assert np.array_equal(rows, np.round(rows)) and np.all(np.diff(rows) > 0)        # whole rows, ascending
+    assert np.array_equal(x, np.load(tmp_path / "b" / "x.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) < 4096 + 3 * 128                # + the .npy headers
+    assert np.load(tmp_path / "a" / "n.npy").dtype == np.float32

@@ -2254,14 +2254,14 @@ def test_arrivals_head_hip_matches_module(S, n_src, n_picks):
 
 
 def test_bench_line_contract_on_the_gpu():
-    """`python bench.py` (short run, the optional extras off): ONE JSON line with the fields the driver reads, the headline
+    """`python bench.py --full` (short run, the optional extras off): ONE JSON line with the fields the driver reads, the headline
     workload named, a roofline object priced on algorithmic bytes against the HBM peak and per-kernel HIP-event times."""
     import json
     import os
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--steps", "16", "--warmup", "8", "--settle", "16", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--full", "--steps", "16", "--warmup", "8", "--settle", "16", "--no-cpu-baseline",
                         "--no-cfg4-one-gpu", "--no-live-traffic", "--no-train-step", "--no-stream", "--no-day-loops"], cwd=repo,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -2287,6 +2287,47 @@ def test_bench_line_contract_on_the_gpu():
     assert abs(d["value"] - 50000.0 * 1e3 / d["ms_per_step"]) <= 1e-3 * d["value"]
     assert abs(rf["achieved"] - 3.07216 / d["ms_per_step"] * 1e3) <= 2e-3 * rf["achieved"]          # B_alg = 3.072 GB per window
     assert 0.1 < d["ms_per_step"] < 5.0 and set(rf["kernels"]) == {"k_stage1", "k_stage2"}
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """`python bench.py --dump-outputs DIR` without --full: the headline only (no extra legs in the line), and DIR holds the (y, x) the
+    last timed literal call returned -- the same as the model gives for that window when called here."""
+    import json
+    import os
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, out_dir = 7, str(tmp_path / "out")
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2", "--settle", "4",
+                        "--dump-outputs", out_dir], cwd=repo, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert d["steps"] == steps and d["warmup"] == 2 and d["settle_windows"] == 4 and d["unit"] == "picks/s" and d["dtype"] == "f32"
+    assert abs(d["value"] - 50000.0 * 1e3 / d["ms_per_step"]) <= 1e-3 * d["value"]
+    for k in ("cold_ms_per_step", "pipelined_windows_ms", "cpu_baseline", "training_step_config3", "streaming_config5", "day_loops_config2",
+              "sharded_workload_on_one_gpu"):
+        assert k not in d, k
+    assert "kernels" not in d["roofline"]
+    assert sorted(os.listdir(out_dir)) == ["x.npy", "y.npy"]
+    y, x = np.load(os.path.join(out_dir, "y.npy")), np.load(os.path.join(out_dir, "x.npy"))
+    assert y.dtype == np.float32 and x.dtype == np.float32 and y.nbytes + x.nbytes <= 64 << 20
+    sys.path.insert(0, repo)
+    import bench
+    S, G, n_picks, L, nq = synthetic.CONFIGS["cfg2_200x10k"]
+    geom = synthetic.Geometry(S, G, L=L, n_query=nq, seed=1)
+    net = bench.build_model(geom, DEV)
+    win = synthetic.make_window(geom, n_picks, seed=2, window=(steps - 1) % 4)        # the bench cycles 4 windows
+    t = lambda v: torch.from_numpy(v).float().to(DEV)
+    with torch.no_grad():
+        y_ref, x_ref = net.forward_fixed_source(t(win["Slice"]), t(win["Mask"]), None, None, None, t(geom.locs), t(geom.x_grid),
+                                                t(geom.x_query), t(geom.t_query))
+    assert y.shape == tuple(y_ref.shape) and x.shape == tuple(x_ref.shape) and y.shape[0] == G and x.shape[0] == nq
+    assert np.isfinite(y).all() and np.isfinite(x).all()
+    assert max_abs(torch.from_numpy(y), y_ref.cpu()) <= 1e-5 and max_abs(torch.from_numpy(x), x_ref.cpu()) <= 1e-5
 
 
 def test_drop_in_accepts_the_tensor_forms_pytorch_callers_pass():

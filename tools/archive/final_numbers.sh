@@ -6,8 +6,4 @@ import json
 for l in open("gpurun_out/r04_p_variants.json"):
     d = json.loads(l); print(d["variant"], d["ms_per_window"], d["ms_per_window_batched_tails"], d["batched_equals_single_stream_bitwise"], d["max_abs_y_vs_cpu"], d["max_abs_x_vs_cpu"])
 PY
-timeout 600 python bench.py --mode train > gpurun_out/r04_p_bench_train.json 2>/dev/null
-python - <<'PY'
-import json
-d = json.loads(open("gpurun_out/r04_p_bench_train.json").read().strip().splitlines()[-1]); print(d["ms_per_step"], d["roofline"]["phase_ms"], d["four_output_step"]["ms_per_step"])
-PY
+timeout 600 python bench.py --full --mode train 2>/dev/null | tail -1 | python -c "import sys, json; d = json.loads(sys.stdin.read()); print(d['ms_per_step'], d['roofline']['phase_ms'], d['four_output_step']['ms_per_step'])"

@@ -12,15 +12,15 @@ python $R/tools/kernel_resources.py $GENIE_LIB_PATH k_train_b1s k_train_b1ILb0EL
 for rep in 1 2; do
 for v in 0 1; do
   echo "== GENIE_B1_SPLIT=$v (run $rep): ms_per_step, phases, four-output step"
-  GENIE_B1_SPLIT=$v timeout 300 python $R/bench.py --mode train --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['roofline']['phase_ms'], d['four_output_step']['ms_per_step'])"
+  GENIE_B1_SPLIT=$v timeout 300 python $R/bench.py --full --mode train --steps 30 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['roofline']['phase_ms'], d['four_output_step']['ms_per_step'])"
 done
 done
 for v in 0 1; do
   rm -rf /tmp/rt_$v /tmp/pmc_$v
-  GENIE_B1_SPLIT=$v timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/rt_$v -o rt -- python $R/bench.py --mode train --steps 10 --warmup 3 --no-cpu-baseline > /tmp/rt.log 2>&1
+  GENIE_B1_SPLIT=$v timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/rt_$v -o rt -- python $R/bench.py --full --mode train --steps 10 --warmup 3 --no-cpu-baseline > /tmp/rt.log 2>&1
   echo "== GENIE_B1_SPLIT=$v kernel trace"
   python $R/tools/prof_summary.py $(find /tmp/rt_$v -name "*.db" | head -1) 40 | grep "k_train_b1" | cut -c1-170
-  GENIE_B1_SPLIT=$v timeout 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_LDS --output-format csv -d /tmp/pmc_$v -- python $R/bench.py --mode train --steps 4 --warmup 2 --no-cpu-baseline > /tmp/pmc.log 2>&1 || echo "pmc pass failed"
+  GENIE_B1_SPLIT=$v timeout 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_LDS --output-format csv -d /tmp/pmc_$v -- python $R/bench.py --full --mode train --steps 4 --warmup 2 --no-cpu-baseline > /tmp/pmc.log 2>&1 || echo "pmc pass failed"
   echo "== GENIE_B1_SPLIT=$v counters (quad-cycles except SQ_VALU_MFMA_BUSY_CYCLES, per launch, summed over the chip)"
   python $R/tools/pmc_summary.py /tmp/pmc_$v k_train_b1
 done
