@@ -1041,9 +1041,9 @@ struct DaArgs {
     int rev;                   // k_stage2_fast: sweep every XCD's chunk backwards (the rows stage 1 wrote last are read first)
     int wgmap;                 // k_stage2_ord: blocks of 4 source nodes per workgroup, one node per wave (see the kernel)
     const int32_t* ptile;      // irregular product graph: processing order of the kernel's tiles (16 or 32 consecutive product nodes), or null
-    int np;                    // c / wv rows are NODE-PLANAR (k_stage1_h2 writes, k_stage2_h2 reads): inside the block of a source node,
+    int np;                    // c / wv rows are NODE-PLANAR (k_stage1_h2 writes, k_stage2_h2u reads): inside the block of a source node,
                                // chunk q (16 B) of all S stations is contiguous: c [g][8][S] x 16 B, wv [g][4][S] x 16 B
-    const unsigned* ea_frag;   // k_stage2_h2: edge_attr as B fragments (k_ea_frag), node-planar [g][2][S] x 16 B, processing order
+    const unsigned* ea_frag;   // k_stage2_h2u: edge_attr as B fragments (k_ea_frag), node-planar [g][2][S] x 16 B, processing order
 };
 
 // wave-uniform work item iterator. XCD x (blockIdx % 8, observed dispatch placement: used for speed only) sweeps
@@ -1252,6 +1252,8 @@ __device__ __forceinline__ void gather_sum16(const float* __restrict__ base, lon
 // ================================================================================================
 // context + C ABI
 // ================================================================================================
+enum class RowLayout { Rows, NodePlanar };   // the c / wv rows of stage 1 in the workspace: rows or node-planar (DaArgs.np)
+
 struct genie_ctx {
     int S, G, G_ext, T;
     float scale_rel, scale_t;
@@ -1268,9 +1270,6 @@ struct genie_ctx {
     float* packed[NPLAN];
     AccDesc* d_acc[NTM]; VecDesc* d_vec[NTM]; int32_t* d_sc[NTM];   // gradient maps of the backward passes (k_train_reduce)
     int n_acc[NTM], n_vec[NTM], n_sc[NTM];
-    float* train_save;         // ... and where those kernels keep the pre-activations (DaArgs.save)
-    int force_generic;         // set for the duration of a training call: the generic fp32 stage kernels (caller's station order,
-                               // pre-activations saved) run whatever the context would normally select
     float* as_pg;              // [G][AS_PG] per-source-node terms of the association stages (allocated on first use)
     float* as_ps;              // [S][AS_PS] per-station terms of the two model variants (allocated on first use)
     int32_t* d_h2tbl;          // k_pack_h2 source table
@@ -1313,10 +1312,9 @@ struct genie_ctx {
     int ks_uni, kp_uni;        // uniform in-degree of the station / source graph, -1 when ragged
     int use_fast;              // the reference's kNN graphs (ks_uni == 8 && kp_uni == 15): the pipelined kernels k_stage1_h2 / k_stage2_ord apply
     int bpc2o;                 // workgroups of k_stage2_ord per CU (its occupancy: three per CU)
-    int bpc2h;                 // workgroups of k_stage2_h2 per CU
     int s2_wgmap;              // k_stage2_ord: blocks of 4 source nodes per workgroup (large station counts)
     int bpc1b;                 // workgroups of k_stage1_h2 per CU in the grid (one is resident; more = dynamic balancing by the dispatcher)
-    int use_h2;                // the SHAPE admits the f16x2 kernels (k_stage1_h2 / k_stage2_h2): uniform 8 / 15-degree graphs, 24-bit
+    int use_h2;                // the SHAPE admits the f16x2 kernels (k_stage1_h2 / k_stage2_h2u): uniform 8 / 15-degree graphs, 24-bit
                                // multiplicands; whether they run is h2_on(): precision mode + the fp16 range guard below
     int prec_mode;             // genie_set_stage_precision: 0 = auto (f16x2 while the range guard holds, else fp32 MFMA), 1 = f16x2, 2 = fp32
     bool range_ok;             // fp16 range guard (k_h2_range, evaluated at every weight commit): every hidden state the f16x2 kernels
@@ -1330,19 +1328,17 @@ struct genie_ctx {
     struct S2uTables { void* blocks; int32_t* xcd0; int nblk; };
     std::map<std::pair<int, int>, S2uTables> s2u;
     std::vector<int32_t> tab_host;
-    int s2u_off;               // tuning: k_stage2_h2 (every source row through the texture path) where k_stage2_h2u applies
-    int32_t* d_s2htbl;         // k_pack_h2 source table of k_stage2_h2's image
-    float* packed_s2h;         // f16x2 weight image of k_stage2_h2 (Bipartite_ReadIn.fc1)
-    unsigned *ea_frag, *ea_frag_tmp;    // edge_attr as B fragments of k_stage2_h2 (k_ea_frag): of the registered static edge_attr / of any other one
+    int32_t* d_s2htbl;         // k_pack_h2 source table of k_stage2_h2u's image
+    float* packed_s2h;         // f16x2 weight image of k_stage2_h2u (Bipartite_ReadIn.fc1)
+    unsigned *ea_frag, *ea_frag_tmp;    // edge_attr as B fragments of k_stage2_h2u (k_ea_frag): of the registered static edge_attr / of any other one
     bool tables_shared = false;   // the graph-independent tables below belong to the device's template context (model_tables): not freed here
-    bool ws_np;                // layout of the c / wv rows the last stage 1 left in the workspace: node-planar (DaArgs.np) or rows
+    RowLayout s1_layout;       // layout of the c / wv rows the last stage 1 left in the workspace (stage 2 checks it against its route)
     std::vector<const void*> lds_attr_done;   // kernels whose MaxDynamicSharedMemorySize was raised for THIS context's device (the attribute
                                // is per device: a process-wide flag would skip the second GPU of a multi-GPU process)
     int xs_sta_order;          // genie_embed_window_split: the station-order state its split rows were written under
     int sign_input;            // genie_set_sign_input(1): the embedding tags every feature with the sign of the series' negative slope
     int no_phase;              // genie_set_phase_types(0): the embedding zeroes the phase-informed columns of Slice / Mask
     int tail_f32;              // genie_set_tail_precision(0): the G-sized tail on fp32 MFMA chains (default: fp64 chains, tail_kernels.hpp)
-    int tail_train;            // set for the duration of a training forward: its tail keeps the fp32 chains (the backward recomputes with them)
     // workspace offsets (floats)
     size_t o_xs, o_mm, o_c, o_wu, o_wv, o_part, o_sa0, o_sa1, o_bip, o_gpart, o_pj0, o_pj1, o_cv, ws_floats;
     size_t slot_stride;        // the G-sized buffers (o_part ... o_cv) exist GENIE_NSLOT times; `slot` selects the copy
@@ -1361,11 +1357,6 @@ int raise_lds_limit(genie_ctx* c, const void* kern, int bytes) {
     return GENIE_OK;
 }
 
-// The station processing order is honoured by k_split_rows / the embedding's split rows, k_stage1_h2 (through the relabelled
-// station graph) and k_stage2_ord: active only while those are the kernels that run (use_absolute_pos together with the
-// edge-feature variant takes the generic stage-1 kernel).
-// The f16x2 kernels run when the shape admits them AND the precision mode says so: auto = while the fp16 range guard holds for the
-// committed weights (k_h2_range), else the fp32-MFMA kernels take over -- no environment variable, no non-finite output.
 // rows of the static edge-feature tables (DataAggregationEdges): per station / per source node, per product node on an irregular graph
 long long edge_rows_sta(const genie_ctx* c) { return c->pcsr ? c->P : c->S; }
 long long edge_rows_src(const genie_ctx* c) { return c->pcsr ? c->P : c->G; }
@@ -1379,34 +1370,79 @@ const char* tune_env(const char* name) {
     return nullptr;
 #endif
 }
-// stage 2 of an irregular product graph with the station sum folded in (k_stage2_pseg); tuning builds can switch back for A/B runs
-bool pseg_on() {
-    static const char* e = tune_env("GENIE_S2_PSEG");
-    return !e || atoi(e) != 0;
-}
+// The f16x2 kernels run when the shape admits them AND the precision mode says so: auto = while the fp16 range guard holds for the
+// committed weights (k_h2_range), else the fp32-MFMA kernels take over -- no environment variable, no non-finite output.
 bool h2_on(const genie_ctx* c) { return c->use_h2 && (c->prec_mode == 1 || (c->prec_mode == 0 && c->range_ok)); }
 bool pcsr_h2_on(const genie_ctx* c) { return c->pcsr_h2 && (c->prec_mode == 1 || (c->prec_mode == 0 && c->range_ok)); }
 int part_T(const genie_ctx* c) { return c->pcsr ? 1 : c->T; }      // rows of station-sum partials per source node in `part`
+// use_absolute_pos together with the edge-feature variant, or on the fp32 kernels: the generic stage-1 kernel
 bool abs_generic(const genie_ctx* c) { return c->abs_sta != nullptr && (c->has_edges || !h2_on(c)); }
-bool sta_order_on(const genie_ctx* c) {
-    return c->sta_perm != nullptr && !c->pcsr && h2_on(c) && !abs_generic(c) && !c->force_generic;
-}
 
-// k_stage2_h2 is the stage 2 of the production configuration (the reference's kNN graphs in station processing order); the stage 1
-// that feeds it writes c / wv node-planar (DaArgs.np). Both launch sites ask this.
-// the G-sized tail of inference calls runs its Linears as fp64 MFMA chains (WIDE kernels) unless told otherwise
-bool tail_wide(const genie_ctx* c) { return !c->tail_f32 && !c->tail_train; }
-// training forward on the reference's kNN graphs with the f16x2 kernels in range: stage 2 is the production kernel (k_stage2_h2u,
-// SAVE) in the CALLER's station order, so the stage 1 of a training call writes c / wv node-planar too
-bool train_h2u_on(const genie_ctx* c) {
-    return c->force_generic && !c->pcsr && c->train_save != nullptr && c->use_fast && h2_on(c) && c->src_tab != nullptr && !c->tab_host.empty() &&
-           !c->s2u_off && !abs_generic(c);
+// The mode of one call into the stage kernels or the G-sized tail, passed down from the entry point (nothing of it is kept on the
+// context). A training forward runs in the CALLER's station order, keeps the pre-activations of its stage kernels in `save`
+// (DaArgs.save), and runs its tail on fp32 chains (the backward recomputes every pre-activation of the tail with them).
+struct StageCall {
+    float* save;
+    bool train;
+};
+constexpr StageCall kInference{nullptr, false};
+
+// The station processing order is honoured by k_split_rows / the embedding's split rows, k_stage1_h2 (through the relabelled
+// station graph) and the stage 2 after it: inference through the f16x2 kernels on a Cartesian product graph.
+bool sta_order_on(const genie_ctx* c, const StageCall& call) {
+    return c->sta_perm != nullptr && !c->pcsr && h2_on(c) && !abs_generic(c) && !call.train;
 }
-bool s2h_on(const genie_ctx* c) {
-#if GENIE_TUNING
-    { static const bool old_pair = getenv("GENIE_S2_OLD") != nullptr; if (old_pair) return false; }   // A/B: row layout + k_stage2_ord
-#endif
-    return c->use_fast && sta_order_on(c);
+// the G-sized tail of inference calls runs its Linears as fp64 MFMA chains (WIDE kernels) unless told otherwise
+bool tail_wide(const genie_ctx* c, const StageCall& call) { return !c->tail_f32 && !call.train; }
+
+// The DataAggregation stage kernels a call runs. stage_routes() is the one place that chooses them; run_stage1 / run_stage2 issue
+// the launches of the route they are given.
+enum class S1Route {
+    Generic,     // k_stage1: fp32 MFMA, any graph (64-bit safe); use_absolute_pos with edge features or outside the fp16 range
+    PcsrH2,      // irregular product graph, f16x2: k_split_rows + k_stage1_h2<.., PCSR>
+    PcsrF32,     // irregular product graph, fp32 MFMA: k_stage1_pcsr
+    H2,          // k_split_rows(_g) + k_stage1_h2: c / wv node-planar when stage 2 is k_stage2_h2u, else rows
+};
+enum class S2Route {
+    TrainAssoc,  // training forward, last pass of the association heads: k_stage2_ord SAVE in the caller's station order
+    TrainH2u,    // training forward on the reference's kNN graphs, f16x2: k_stage2_h2u SAVE in the caller's station order
+    TrainOrd,    // ... the same on a sub-range of the source nodes (k_stage2_h2u SAVE covers the whole grid only): k_stage2_ord SAVE
+    Generic,     // k_stage2: fp32 MFMA, any graph
+    PcsrPseg,    // irregular product graph, inference: k_stage2_pseg (station sum folded in, straight into the window's slot)
+    PcsrSeg,     // irregular product graph otherwise: k_stage2_pcsr (+ k_seg_sum32 of the station sums into the window's slot)
+    AssocLast,   // last pass of the association heads in station processing order: k_stage2_ord NB on the rows k_assoc_b wrote
+    H2u,         // the production stage 2 (kNN graphs, station processing order): k_stage2_h2u
+};
+struct StageRoutes {
+    S1Route s1;
+    S2Route s2;
+    RowLayout layout;    // of the c / wv rows between the two: stage 1 writes it, stage 2 checks it
+};
+// range: positions [gi_begin, gi_end) of the processing order; no_bip: the association heads' last pass (no Bipartite half);
+// want_xl: x_latent is written. Stage 1 asks with no_bip = want_xl = false.
+// use_fast (kNN graphs: ks_uni == 8 && kp_uni == 15) implies that the constructor filled src_tab / tab_host, which k_stage1_h2 and
+// k_stage2_h2u read; use_h2 implies use_fast.
+StageRoutes stage_routes(const genie_ctx* c, const StageCall& call, int gi_begin, int gi_end, bool no_bip, bool want_xl) {
+    StageRoutes r;
+    if (c->pcsr) {
+        r.s1 = pcsr_h2_on(c) && !(c->abs_sta && c->has_edges) ? S1Route::PcsrH2 : S1Route::PcsrF32;
+        r.s2 = !no_bip && !want_xl && !call.save ? S2Route::PcsrPseg : S2Route::PcsrSeg;
+    } else {
+        r.s1 = h2_on(c) && !abs_generic(c) ? S1Route::H2 : S1Route::Generic;
+        const bool whole = gi_begin == 0 && gi_end == c->G;
+        const bool fast = c->use_fast && !abs_generic(c);
+        if (call.train) {
+            if (fast && no_bip && want_xl && whole) r.s2 = S2Route::TrainAssoc;
+            else if (fast && !no_bip && h2_on(c)) r.s2 = whole ? S2Route::TrainH2u : S2Route::TrainOrd;
+            else r.s2 = S2Route::Generic;
+        } else if (c->use_fast && sta_order_on(c, call) && (!no_bip || want_xl)) {
+            r.s2 = no_bip ? S2Route::AssocLast : S2Route::H2u;
+        } else {
+            r.s2 = S2Route::Generic;
+        }
+    }
+    r.layout = r.s1 == S1Route::H2 && (r.s2 == S2Route::H2u || r.s2 == S2Route::TrainH2u) ? RowLayout::NodePlanar : RowLayout::Rows;
+    return r;
 }
 
 // largest |Slice| / |Mask| entry for which the committed weights keep every hidden state of the f16x2 kernels below the fp16 range: the
@@ -1539,7 +1575,7 @@ int da_grid(const genie_ctx* c, long long nitems_waves, int blocks_per_cu) {
     return (int)g;
 }
 
-DaArgs make_da_args(const genie_ctx* c, float* ws) {
+DaArgs make_da_args(const genie_ctx* c, const StageCall& call, float* ws) {
     DaArgs a;
     memset(&a, 0, sizeof(a));
     a.S = c->S; a.G = c->G; a.T = c->T;
@@ -1547,13 +1583,14 @@ DaArgs make_da_args(const genie_ctx* c, float* ws) {
     a.order = c->order;
     a.src_tab = c->src_tab;
     a.Pn = c->P;
-    a.save = c->force_generic ? c->train_save : nullptr;
+    a.save = call.save;
     if (c->pcsr) {
         a.sta_rowptr = c->p_sta_rowptr; a.sta_col = c->p_sta_col; a.src_rowptr = c->p_src_rowptr; a.src_col = c->p_src_col;
     }
-    if (sta_order_on(c)) { a.sta_rowptr = c->sta_rowptr_p; a.sta_col = c->sta_col_p; a.sta_user = c->sta_perm; }
+    const bool so = sta_order_on(c, call);
+    if (so) { a.sta_rowptr = c->sta_rowptr_p; a.sta_col = c->sta_col_p; a.sta_user = c->sta_perm; }
     a.abs_sta = c->abs_sta; a.abs_src = c->abs_src; a.abs_ts = c->abs_ts; a.abs_tg = c->abs_tg;
-    a.eb_sta = c->has_edges ? (sta_order_on(c) ? c->ebias_sta_p : c->ebias_sta) : nullptr;
+    a.eb_sta = c->has_edges ? (so ? c->ebias_sta_p : c->ebias_sta) : nullptr;
     a.eb_src = c->has_edges ? c->ebias_src : nullptr;
     a.seg = std::max(1, c->seg);
 #if GENIE_TUNING
@@ -2166,21 +2203,20 @@ int genie_ctx_create(genie_ctx** out, int n_sta, int n_grid, int n_grid_ext, con
         c->tail_cu_ro = c->num_cu * 2;          // genie_set_tail_grid
         c->tail_cu_sa = c->num_cu * 2;
         // persistent grids: exactly as many workgroups as are co-resident (a larger grid runs in two uneven rounds)
-        int occ1 = 0, occ2 = 0, occo = 0, occh = 0;
-        {   // (four driver queries: once per device and process)
-            static std::map<int, std::array<int, 4>> occ;
+        int occ1 = 0, occ2 = 0, occo = 0;
+        {   // (three driver queries: once per device and process)
+            static std::map<int, std::array<int, 3>> occ;
             static std::mutex mu;
             std::lock_guard<std::mutex> lk(mu);
             auto it = occ.find(dev);
             if (it == occ.end()) {
-                std::array<int, 4> o{};
+                std::array<int, 3> o{};
                 HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o[0], k_stage1, 256, 0));
                 HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o[1], k_stage2, 256, 0));
                 HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o[2], k_stage2_ord<8, 15, false>, 256, 0));
-                HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o[3], k_stage2_h2<false, false>, 256, 0));
                 it = occ.emplace(dev, o).first;
             }
-            occ1 = it->second[0]; occ2 = it->second[1]; occo = it->second[2]; occh = it->second[3];
+            occ1 = it->second[0]; occ2 = it->second[1]; occo = it->second[2];
         }
         c->bpc1 = std::max(1, occ1);
         c->bpc2 = (e = tune_env("GENIE_BPC2")) ? atoi(e) : std::max(1, occ2);
@@ -2190,11 +2226,6 @@ int genie_ctx_create(genie_ctx** out, int n_sta, int n_grid, int n_grid_ext, con
         // GPU: stage 2 16.1 -> 11.8 ms (three workgroups, interleaved items: 16.1; two: 14.8; block map alone: 13.1). At 200
         // stations the same settings lose (0.266 -> 0.268 ms), hence by size.
         c->s2_wgmap = (e = tune_env("GENIE_S2_WGMAP")) ? (atoi(e) != 0) : (n_sta >= 1024);
-        {
-            // two workgroups per CU: as fast as three (0.2367 / 0.2370 ms) with 8 % less fabric traffic (FETCH_SIZE 5.18e5 vs 5.62e5 KB)
-            c->bpc2h = (e = tune_env("GENIE_BPC2")) ? atoi(e) : std::min(2, std::max(1, occh));
-            c->s2u_off = tune_env("GENIE_S2_NOUNION") != nullptr;
-        }
         c->bpc2o = (e = tune_env("GENIE_BPC2")) ? atoi(e) : std::min(2, std::max(1, occo));     // round 3, after the f16x2 stage 1: 2 beat 3 at 200 stations too (window 0.593 -> 0.588 ms)
         // the reference's kNN graphs (8 station / 15 source neighbours everywhere): pipelined kernels k_stage1_h2 / k_stage2_ord
         c->use_fast = c->ks_uni == 8 && c->kp_uni == 15;
@@ -2389,8 +2420,8 @@ int genie_set_static_edge_attr(genie_ctx* c, const float* edge_attr, void* strea
     if (!c) return fail(GENIE_ERR_ARG, "genie_set_static_edge_attr: null context");
     c->ea_user = nullptr;
     if (!edge_attr || !c->sta_perm || c->pcsr) return GENIE_OK;       // nothing to prepare without a station processing order
-    if (!c->use_h2) return GENIE_OK;      // only k_stage2_h2 honours the station processing order in stage 2
-    // k_stage2_h2 reads the static edge_attr as ready-made B fragments (32 B per product node, processing order)
+    if (!c->use_h2) return GENIE_OK;      // only k_stage2_h2u honours the station processing order in stage 2
+    // k_stage2_h2u reads the static edge_attr as ready-made B fragments (32 B per product node, processing order)
     if (!c->ea_frag) HIP_TRY(gmalloc((void**)&c->ea_frag, 32 * (size_t)c->P));
     k_ea_frag<<<(unsigned)((c->P + 255) / 256), 256, 0, (hipStream_t)stream>>>(edge_attr, c->P, c->S, c->sta_perm, c->ea_frag);
     HIP_TRY(hipGetLastError());
@@ -2476,10 +2507,26 @@ int genie_weights_commit(genie_ctx* c, void* stream) {
 size_t genie_workspace_bytes(const genie_ctx* c) { return c ? c->ws_floats * sizeof(float) : 0; }
 
 namespace {
+// k_stage1_h2's variants: absolute positions or edge terms (never both: stage_routes sends that model to the generic kernel), 64-bit
+// row offsets (big)
+extern "C++" template <bool PCSR>
+void launch_stage1_h2(const DaArgs& a, bool abs, bool edges, bool big, int grid, hipStream_t st) {
+    if (abs) {
+        if (big) k_stage1_h2<8, 15, false, true, true, PCSR><<<grid, H2_THREADS, 0, st>>>(a);
+        else k_stage1_h2<8, 15, false, false, true, PCSR><<<grid, H2_THREADS, 0, st>>>(a);
+    } else if (edges) {
+        if (big) k_stage1_h2<8, 15, true, true, false, PCSR><<<grid, H2_THREADS, 0, st>>>(a);
+        else k_stage1_h2<8, 15, true, false, false, PCSR><<<grid, H2_THREADS, 0, st>>>(a);
+    } else {
+        if (big) k_stage1_h2<8, 15, false, true, false, PCSR><<<grid, H2_THREADS, 0, st>>>(a);
+        else k_stage1_h2<8, 15, false, false, false, PCSR><<<grid, H2_THREADS, 0, st>>>(a);
+    }
+}
+
 // gi_begin / gi_end: positions of the processing order this call covers (the whole grid: 0, G); do_split: run the input
 // split pass over ALL rows (owned + halo) first -- the first range call of a window does, later ones reuse its rows
-int run_stage1(genie_ctx* c, const float* slice, const float* mask, float* dbg_h0, float* dbg_h1, void* ws, void* stream,
-               int gi_begin, int gi_end, bool do_split) {
+int run_stage1(genie_ctx* c, const StageCall& call, const float* slice, const float* mask, float* dbg_h0, float* dbg_h1, void* ws,
+               void* stream, int gi_begin, int gi_end, bool do_split) {
     int rc = check_ws(c, ws);
     if (rc) return rc;
     if (!slice || !mask) return fail(GENIE_ERR_ARG, "genie_da_stage1: null input");
@@ -2488,27 +2535,30 @@ int run_stage1(genie_ctx* c, const float* slice, const float* mask, float* dbg_h
     if (!whole && c->pcsr) return fail(GENIE_ERR_STATE, "genie_da_stage1_range: not available on an irregular product graph");
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_packed(c, st))) return rc;
-    DaArgs a = make_da_args(c, (float*)ws);
+    const StageRoutes r = stage_routes(c, call, gi_begin, gi_end, false, false);
+    const bool so = sta_order_on(c, call);
+    DaArgs a = make_da_args(c, call, (float*)ws);
     a.gi0 = gi_begin; a.G = gi_end - gi_begin;
     const long long n_tiles = (long long)a.G * c->T;
     a.slice = slice; a.mask = mask; a.packed = c->packed[0];
     a.dbg_h0 = dbg_h0; a.dbg_h1 = dbg_h1;
-    c->ws_np = false;
+    c->s1_layout = r.layout;
     float* dbg_tmp = nullptr;
-    if ((dbg_h0 || dbg_h1) && sta_order_on(c)) {
+    if ((dbg_h0 || dbg_h1) && so) {
         HIP_TRY(gmalloc((void**)&dbg_tmp, sizeof(float) * 90 * (size_t)c->P));
         if (dbg_h0) a.dbg_h0 = dbg_tmp;
         if (dbg_h1) a.dbg_h1 = dbg_tmp + c->P * 30;
     }
-    if (((c->force_generic && !h2_on(c)) || abs_generic(c)) && !c->pcsr) {   // use_absolute_pos, training on other graph shapes: generic kernel (64-bit safe, any graph)
+    switch (r.s1) {
+    case S1Route::Generic:
         if (n_tiles) k_stage1<<<da_grid(c, n_tiles, c->bpc1), 256, 0, st>>>(a);
-    } else if (c->pcsr && pcsr_h2_on(c) && !(c->abs_sta && c->has_edges)) {      // (both options at once: the generic fp32-MFMA kernel below)
+        break;
+    case S1Route::PcsrH2: {
         unsigned* xs = (unsigned*)((float*)ws + c->o_xs);
         k_split_rows<<<(unsigned)((c->P + 255) / 256), 256, 0, st>>>(slice, mask, c->P, xs, nullptr, c->S, nullptr, input_limit(c), c->h_inflag);
         a.xs = xs; a.packed = c->packed_h2; a.xs_plane = c->P * (long long)XPC;
         const long long nitems = (c->P + 31) / 32;
         const int grid = (int)std::max<long long>(8, std::min<long long>((nitems + H2_THREADS / 64 - 1) / (H2_THREADS / 64), (long long)c->num_cu * c->bpc1b) / 8 * 8);
-        const bool bigp = c->P * XROW >= (1ll << 32);
         a.ptile = c->ptile32;
         if (c->abs_sta) {      // position pieces per product node (genie_set_absolute_pos on a subgraph context)
             if (c->abs_dirty || !c->abs_ts) {
@@ -2521,28 +2571,25 @@ int run_stage1(genie_ctx* c, const float* slice, const float* mask, float* dbg_h
                 c->abs_dirty = false; c->abs_ts_order = 0;
             }
             a.abs_ts = c->abs_ts; a.abs_tg = c->abs_tg;
-            if (bigp) k_stage1_h2<8, 15, false, true, true, true><<<grid, H2_THREADS, 0, st>>>(a);
-            else k_stage1_h2<8, 15, false, false, true, true><<<grid, H2_THREADS, 0, st>>>(a);
-        } else if (c->has_edges) {
-            if (bigp) k_stage1_h2<8, 15, true, true, false, true><<<grid, H2_THREADS, 0, st>>>(a);
-            else k_stage1_h2<8, 15, true, false, false, true><<<grid, H2_THREADS, 0, st>>>(a);
-        } else {
-            if (bigp) k_stage1_h2<8, 15, false, true, false, true><<<grid, H2_THREADS, 0, st>>>(a);
-            else k_stage1_h2<8, 15, false, false, false, true><<<grid, H2_THREADS, 0, st>>>(a);
         }
-    } else if (c->pcsr) {
+        launch_stage1_h2<true>(a, c->abs_sta != nullptr, c->has_edges, c->P * XROW >= (1ll << 32), grid, st);
+        break;
+    }
+    case S1Route::PcsrF32: {
         const long long ntiles = (c->P + 15) / 16;
         a.ptile = c->ptile16;
         const long long gw = std::min<long long>((ntiles + 3) / 4, (long long)c->num_cu * c->bpc1);
         k_stage1_pcsr<<<(int)std::max<long long>(8, gw / 8 * 8), 256, 0, st>>>(a);
-    } else if (h2_on(c)) {
+        break;
+    }
+    case S1Route::H2: {
         unsigned* xs = (unsigned*)((float*)ws + c->o_xs);
         // genie_embed_window_split, one-shot; its rows count only if they were written under the station-order state of THIS call
         // (a training forward, or other weights whose range guard flipped the kernels, re-split in their own order)
-        const bool presplit = (c->xs_slice == slice && c->xs_mask == mask && c->xs_ws == ws && c->xs_sta_order == (sta_order_on(c) ? 1 : 0)) || !do_split;
+        const bool presplit = (c->xs_slice == slice && c->xs_mask == mask && c->xs_ws == ws && c->xs_sta_order == (so ? 1 : 0)) || !do_split;
         if (do_split) { c->xs_slice = c->xs_mask = nullptr; c->xs_ws = nullptr; }
         float* mmw = (float*)ws + c->o_mm + (c->slot % GENIE_NBIG) * c->big_stride;
-        if (presplit && do_split && sta_order_on(c) && c->xs_mm_copy != c->slot % GENIE_NBIG) {
+        if (presplit && do_split && so && c->xs_mm_copy != c->slot % GENIE_NBIG) {
             // the embedding ran under another slot: its message-mask row sits in a different copy than the one stage 2 of THIS
             // window reads (the split rows `xs` exist once). Bring it over (P_ext floats, same stream); callers avoid the copy by
             // selecting the window's slot before they embed (engine.embed_window does).
@@ -2550,44 +2597,33 @@ int run_stage1(genie_ctx* c, const float* slice, const float* mask, float* dbg_h
                                    hipMemcpyDeviceToDevice, st));
         }
         if (!presplit) {
-            if (sta_order_on(c) && c->S <= SPLIT_G_MAXS) {
+            if (so && c->S <= SPLIT_G_MAXS) {
                 HIP_TRY(hipFuncSetAttribute((const void*)k_split_rows_g, hipFuncAttributeMaxDynamicSharedMemorySize, SPLIT_G_MAXS * 32));
                 k_split_rows_g<<<(unsigned)(c->P_ext / c->S), 256, (size_t)c->S * 32, st>>>(slice, mask, c->S, xs, c->sta_perm, mmw, c->P_ext,
                                                                                             input_limit(c), c->h_inflag);
             } else
-                k_split_rows<<<(unsigned)((c->P_ext + 255) / 256), 256, 0, st>>>(slice, mask, c->P_ext, xs,
-                                                                                sta_order_on(c) ? c->sta_perm : nullptr, c->S, mmw,
-                                                                                input_limit(c), c->h_inflag);
+                k_split_rows<<<(unsigned)((c->P_ext + 255) / 256), 256, 0, st>>>(slice, mask, c->P_ext, xs, so ? c->sta_perm : nullptr, c->S,
+                                                                                mmw, input_limit(c), c->h_inflag);
         }
         a.xs = xs; a.packed = c->packed_h2; a.xs_plane = c->P_ext * (long long)XPC;
-        a.np = (s2h_on(c) || train_h2u_on(c)) ? 1 : 0;
-        c->ws_np = a.np != 0;
+        a.np = r.layout == RowLayout::NodePlanar ? 1 : 0;
         const int grid = da_grid_w(c, (n_tiles + 1) / 2, c->bpc1b, H2_THREADS / 64);
-        const bool big = c->P_ext * XROW >= (1ll << 32);
-        if (!n_tiles) {
-        } else if (c->abs_sta) {
-            const int so = sta_order_on(c) ? 1 : 0;      // a training forward runs in the caller's station order, inference in processing order
-            if (c->abs_dirty || !c->abs_ts || c->abs_ts_order != so) {
-                if (!c->abs_ts) {
-                    HIP_TRY(gmalloc((void**)&c->abs_ts, 16 * (size_t)c->S));
-                    HIP_TRY(gmalloc((void**)&c->abs_tg, 16 * (size_t)c->G_ext));
-                }
-                k_abs_pieces<<<(c->S + 255) / 256, 256, 0, st>>>(c->abs_sta, sta_order_on(c) ? c->sta_perm : nullptr, c->S, c->abs_ts);
-                k_abs_pieces<<<(c->G_ext + 255) / 256, 256, 0, st>>>(c->abs_src, nullptr, c->G_ext, c->abs_tg);
-                c->abs_dirty = false; c->abs_ts_order = so;
-                a.abs_ts = c->abs_ts; a.abs_tg = c->abs_tg;
+        if (!n_tiles) break;
+        if (c->abs_sta && (c->abs_dirty || !c->abs_ts || c->abs_ts_order != (so ? 1 : 0))) {
+            // (a training forward runs in the caller's station order, inference in processing order)
+            if (!c->abs_ts) {
+                HIP_TRY(gmalloc((void**)&c->abs_ts, 16 * (size_t)c->S));
+                HIP_TRY(gmalloc((void**)&c->abs_tg, 16 * (size_t)c->G_ext));
             }
-            if (big) k_stage1_h2<8, 15, false, true, true><<<grid, H2_THREADS, 0, st>>>(a);
-            else k_stage1_h2<8, 15, false, false, true><<<grid, H2_THREADS, 0, st>>>(a);
-        } else if (c->has_edges) {
-            if (big) k_stage1_h2<8, 15, true, true><<<grid, H2_THREADS, 0, st>>>(a);
-            else k_stage1_h2<8, 15, true, false><<<grid, H2_THREADS, 0, st>>>(a);
-        } else {
-            if (big) k_stage1_h2<8, 15, false, true><<<grid, H2_THREADS, 0, st>>>(a);
-            else k_stage1_h2<8, 15, false, false><<<grid, H2_THREADS, 0, st>>>(a);
+            k_abs_pieces<<<(c->S + 255) / 256, 256, 0, st>>>(c->abs_sta, so ? c->sta_perm : nullptr, c->S, c->abs_ts);
+            k_abs_pieces<<<(c->G_ext + 255) / 256, 256, 0, st>>>(c->abs_src, nullptr, c->G_ext, c->abs_tg);
+            c->abs_dirty = false; c->abs_ts_order = so ? 1 : 0;
+            a.abs_ts = c->abs_ts; a.abs_tg = c->abs_tg;
         }
-    } else if (n_tiles)
-        k_stage1<<<da_grid(c, n_tiles, c->bpc1), 256, 0, st>>>(a);
+        launch_stage1_h2<false>(a, c->abs_sta != nullptr, c->has_edges, c->P_ext * XROW >= (1ll << 32), grid, st);
+        break;
+    }
+    }
     HIP_TRY(hipGetLastError());
     if (dbg_tmp) {     // parity outputs were written in station processing order: back to the caller's order
         if (dbg_h0) k_permute_sta_rows<<<(unsigned)((c->P * 30 + 255) / 256), 256, 0, st>>>(dbg_tmp, c->P, 30, c->sta_perm, c->S, dbg_h0);
@@ -2601,30 +2637,25 @@ int run_stage1(genie_ctx* c, const float* slice, const float* mask, float* dbg_h
 
 int genie_da_stage1(genie_ctx* c, const float* slice, const float* mask, void* ws, void* stream) {
     if (!c) return fail(GENIE_ERR_ARG, "null context");
-    return run_stage1(c, slice, mask, nullptr, nullptr, ws, stream, 0, c->G, true);
+    return run_stage1(c, kInference, slice, mask, nullptr, nullptr, ws, stream, 0, c->G, true);
 }
 
 int genie_da_stage1_range(genie_ctx* c, const float* slice, const float* mask, int gi_begin, int gi_end, int first, void* ws,
                           void* stream) {
     if (!c) return fail(GENIE_ERR_ARG, "null context");
-    return run_stage1(c, slice, mask, nullptr, nullptr, ws, stream, gi_begin, gi_end, first != 0);
+    return run_stage1(c, kInference, slice, mask, nullptr, nullptr, ws, stream, gi_begin, gi_end, first != 0);
 }
 
 int genie_da_stage1_debug(genie_ctx* c, const float* slice, const float* mask, float* h0_out, float* h1_out, void* ws,
                           void* stream) {
     if (!c || !h0_out || !h1_out) return fail(GENIE_ERR_ARG, "genie_da_stage1_debug: null argument");
-    return run_stage1(c, slice, mask, h0_out, h1_out, ws, stream, 0, c->G, true);
+    return run_stage1(c, kInference, slice, mask, h0_out, h1_out, ws, stream, 0, c->G, true);
 }
 
 float* genie_ws_v_ptr(const genie_ctx* c, void* ws) {
     return (c && ws) ? (float*)ws + c->o_wv + (c->slot % GENIE_NBIG) * c->big_stride : nullptr;
 }
 int genie_ws_v_pitch(const genie_ctx* c) { (void)c; return ROWW; }
-
-namespace {
-int run_stage2(genie_ctx* c, const float* mask, const float* edge_attr, float* x_latent_out, void* ws, void* stream,
-               int gi_begin, int gi_end, const float* slope2 = nullptr, int no_bip = 0);
-}
 
 namespace {
 // k_stage2_h2u's tables for the range [gb0, ge0) of the processing order: per XCD chunk (the chunks of ItemIter), blocks of up to
@@ -2687,23 +2718,29 @@ int get_s2u_tables(genie_ctx* c, int gb0, int ge0, const genie_ctx::S2uTables** 
     *out = &(c->s2u[key] = t);
     return GENIE_OK;
 }
-}  // namespace
 
-int genie_da_stage2_partials(genie_ctx* c, const float* mask, const float* edge_attr, float* x_latent_out, void* ws,
-                             void* stream) {
-    if (!c) return fail(GENIE_ERR_ARG, "null context");
-    return run_stage2(c, mask, edge_attr, x_latent_out, ws, stream, 0, c->G);
+// k_stage2_h2u over the range [gi_begin, gi_end): the source-neighbour rows of blocks of adjacent source nodes staged once in LDS
+// (the 70-KB dynamic LDS needs the attribute once per kernel and device)
+extern "C++" template <bool SAVE>
+int launch_stage2_h2u(genie_ctx* c, const DaArgs& a, int gi_begin, int gi_end, bool xl, hipStream_t st) {
+    const genie_ctx::S2uTables* tb = nullptr;
+    if (int rc = get_s2u_tables(c, gi_begin, gi_end, &tb)) return rc;
+    const size_t lds = sizeof(float) * S2H_IMG_FLOATS + (size_t)S2U_UCAP * 1024;
+    const long long items = (long long)tb->nblk * c->T;
+    const int grid = (int)std::max<long long>(8, std::min<long long>((long long)c->num_cu * GENIE_S2U_BPC, (items + 7) / 8 * 8) / 8 * 8);
+    const bool big = c->P_ext * 128 >= (1ll << 32);
+    auto launch = [&](auto kern) -> int {
+        if (int r = raise_lds_limit(c, (const void*)kern, 160 * 1024)) return r;
+        kern<<<grid, S2U_WPB * 64, lds, st>>>(a, (const S2uBlock*)tb->blocks, tb->xcd0);
+        return GENIE_OK;
+    };
+    if (xl) return big ? launch(k_stage2_h2u<true, true, SAVE>) : launch(k_stage2_h2u<true, false, SAVE>);
+    return big ? launch(k_stage2_h2u<false, true, SAVE>) : launch(k_stage2_h2u<false, false, SAVE>);
 }
 
-int genie_da_stage2_partials_range(genie_ctx* c, const float* mask, const float* edge_attr, float* x_latent_out, int gi_begin,
-                                   int gi_end, void* ws, void* stream) {
-    if (!c) return fail(GENIE_ERR_ARG, "null context");
-    return run_stage2(c, mask, edge_attr, x_latent_out, ws, stream, gi_begin, gi_end);
-}
-
-namespace {
-int run_stage2(genie_ctx* c, const float* mask, const float* edge_attr, float* x_latent_out, void* ws, void* stream,
-               int gi_begin, int gi_end, const float* slope2, int no_bip) {
+// slope2 / no_bip: the association heads' last pass (their PReLU2 slope, no Bipartite half)
+int run_stage2(genie_ctx* c, const StageCall& call, const float* mask, const float* edge_attr, float* x_latent_out, void* ws,
+               void* stream, int gi_begin, int gi_end, const float* slope2 = nullptr, int no_bip = 0) {
     int rc = check_ws(c, ws);
     if (rc) return rc;
     if (!mask || !edge_attr) return fail(GENIE_ERR_ARG, "genie_da_stage2_partials: null argument");
@@ -2712,14 +2749,22 @@ int run_stage2(genie_ctx* c, const float* mask, const float* edge_attr, float* x
         return fail(GENIE_ERR_STATE, "genie_da_stage2_partials_range: not available on an irregular product graph");
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_packed(c, st))) return rc;
-    DaArgs a = make_da_args(c, (float*)ws);
+    DaArgs a = make_da_args(c, call, (float*)ws);
     a.gi0 = gi_begin; a.G = gi_end - gi_begin;
     a.slope2 = slope2; a.no_bip = no_bip;
     const long long n_tiles = (long long)a.G * c->T;
     if (n_tiles == 0) return GENIE_OK;
+    const StageRoutes r = stage_routes(c, call, gi_begin, gi_end, no_bip != 0, x_latent_out != nullptr);
+    // (no_bip: the association heads' last pass reads the rows k_assoc_b wrote, whatever stage 1 left)
+    if (!no_bip && c->s1_layout != r.layout)
+        return fail(GENIE_ERR_STATE, r.layout == RowLayout::NodePlanar
+                                         ? "stage 2: this call's stage 2 reads c / wv node-planar, but the last stage 1 wrote them as rows"
+                                         : "stage 2: this call's stage 2 reads c / wv as rows, but the last stage 1 wrote them node-planar");
     a.mask = mask; a.edge_attr = edge_attr; a.x_latent = x_latent_out; a.packed = c->packed[1];
     a.ea_int = nullptr;
     a.mm_int = (const float*)ws + c->o_mm + (c->slot % GENIE_NBIG) * c->big_stride;
+    // training forward: the caller's station order through an identity processing order (the saved pre-activations of 1.8 GB stay
+    // contiguous stores)
     auto identity_order = [&]() -> int {
         if (!c->sta_ident) {
             std::vector<int32_t> id((size_t)c->S);
@@ -2727,63 +2772,46 @@ int run_stage2(genie_ctx* c, const float* mask, const float* edge_attr, float* x
             HIP_TRY(gmalloc((void**)&c->sta_ident, sizeof(int32_t) * id.size()));
             HIP_TRY(hipMemcpy(c->sta_ident, id.data(), sizeof(int32_t) * id.size(), hipMemcpyHostToDevice));
         }
+        a.sta_user = c->sta_ident; a.wgmap = 0;
         return GENIE_OK;
     };
-    if (c->force_generic && !c->pcsr && a.save != nullptr && c->use_fast && !abs_generic(c) && no_bip && x_latent_out != nullptr &&
-        gi_begin == 0 && gi_end == c->G) {
-        // training forward of the association phase (its last pass): the pipelined fp32 stage 2 in the caller's station order with the
-        // output layer's pre-activations kept, instead of the generic kernel (427 -> ~300 us at config 3)
+    switch (r.s2) {
+    case S2Route::TrainAssoc:
+        // the pipelined fp32 stage 2 with the output layer's pre-activations kept, instead of the generic kernel (427 -> ~300 us
+        // at config 3)
         if ((rc = identity_order())) return rc;
-        a.sta_user = c->sta_ident; a.wgmap = 0;
         k_stage2_ord<8, 15, true, true, true><<<da_grid(c, n_tiles, c->bpc2o), 256, 0, st>>>(a);
-        HIP_TRY(hipGetLastError());
-        return GENIE_OK;
-    }
-    if (c->force_generic && !c->pcsr && a.save != nullptr && c->use_fast && h2_on(c) && !abs_generic(c) && c->src_tab != nullptr && !no_bip) {
-        // training forward on the reference's kNN graphs: the production stage 2 in the CALLER's station order (identity
-        // processing order: the saved pre-activations of 1.8 GB stay contiguous stores), message mask from the split pass of
-        // k_stage1_h2's launch (both model options at once run the generic stage 1, which has no split pass: generic stage 2 below)
+        break;
+    case S2Route::TrainH2u:
+        // the production stage 2 with the pre-activations kept; message mask from the split pass of k_stage1_h2's launch, edge_attr
+        // fragments built per call (identity station order)
         if ((rc = identity_order())) return rc;
-        a.sta_user = c->sta_ident; a.ea_int = edge_attr; a.wgmap = 0;
-        if (train_h2u_on(c) && c->ws_np && gi_begin == 0 && gi_end == c->G) {
-            // k_stage2_h2u with the pre-activations kept (identity station order: edge_attr fragments built per call)
-            a.np = 1; a.packed = c->packed_s2h;
-            if (!c->ea_frag_tmp) HIP_TRY(gmalloc((void**)&c->ea_frag_tmp, 32 * (size_t)c->P));
-            k_ea_frag<<<(unsigned)((c->P + 255) / 256), 256, 0, st>>>(edge_attr, c->P, c->S, nullptr, c->ea_frag_tmp);
-            a.ea_frag = c->ea_frag_tmp;
-            const genie_ctx::S2uTables* tb = nullptr;
-            if ((rc = get_s2u_tables(c, gi_begin, gi_end, &tb))) return rc;
-            const size_t lds = sizeof(float) * S2H_IMG_FLOATS + (size_t)S2U_UCAP * 1024;
-            const long long items = (long long)tb->nblk * c->T;
-            const int grid = (int)std::max<long long>(8, std::min<long long>((long long)c->num_cu * GENIE_S2U_BPC, (items + 7) / 8 * 8) / 8 * 8);
-            const bool big = c->P_ext * 128 >= (1ll << 32);
-            auto launch = [&](auto kern) -> int {
-                if (int r = raise_lds_limit(c, (const void*)kern, 160 * 1024)) return r;
-                kern<<<grid, S2U_WPB * 64, lds, st>>>(a, (const S2uBlock*)tb->blocks, tb->xcd0);
-                return GENIE_OK;
-            };
-            if (x_latent_out) rc = big ? launch(k_stage2_h2u<true, true, true>) : launch(k_stage2_h2u<true, false, true>);
-            else rc = big ? launch(k_stage2_h2u<false, true, true>) : launch(k_stage2_h2u<false, false, true>);
-            if (rc) return rc;
-        } else {
-            const int grid = da_grid(c, n_tiles, c->bpc2o);
-            if (x_latent_out) k_stage2_ord<8, 15, true, false, true><<<grid, 256, 0, st>>>(a);
-            else k_stage2_ord<8, 15, false, false, true><<<grid, 256, 0, st>>>(a);
-        }
-    } else if (c->force_generic && !c->pcsr) {
+        a.ea_int = edge_attr; a.np = 1; a.packed = c->packed_s2h;
+        if (!c->ea_frag_tmp) HIP_TRY(gmalloc((void**)&c->ea_frag_tmp, 32 * (size_t)c->P));
+        k_ea_frag<<<(unsigned)((c->P + 255) / 256), 256, 0, st>>>(edge_attr, c->P, c->S, nullptr, c->ea_frag_tmp);
+        a.ea_frag = c->ea_frag_tmp;
+        if ((rc = launch_stage2_h2u<true>(c, a, gi_begin, gi_end, x_latent_out != nullptr, st))) return rc;
+        break;
+    case S2Route::TrainOrd:
+        if ((rc = identity_order())) return rc;
+        a.ea_int = edge_attr;
+        if (x_latent_out) k_stage2_ord<8, 15, true, false, true><<<da_grid(c, n_tiles, c->bpc2o), 256, 0, st>>>(a);
+        else k_stage2_ord<8, 15, false, false, true><<<da_grid(c, n_tiles, c->bpc2o), 256, 0, st>>>(a);
+        break;
+    case S2Route::Generic:
         k_stage2<<<da_grid(c, n_tiles, c->bpc2), 256, 0, st>>>(a);
-    } else if (c->pcsr) {
+        break;
+    case S2Route::PcsrPseg: {
+        // a wave per source node, the station sum folded into the pass, straight into the window's slot (a.part)
+        a.ptile = c->ptile16;
+        const long long gs = std::min<long long>((c->G + 3) / 4, (long long)c->num_cu * c->bpc2);
+        k_stage2_pseg<<<(int)std::max<long long>(8, gs / 8 * 8), 256, 0, st>>>(a, c->seg_rowptr, c->G);
+        break;
+    }
+    case S2Route::PcsrSeg: {
         const long long ntiles = (c->P + 15) / 16;
         a.ptile = c->ptile16;
         const long long gw = std::min<long long>((ntiles + 3) / 4, (long long)c->num_cu * c->bpc2);      // 2 .. 12 workgroups per CU: +-1 %
-        if (!no_bip && !x_latent_out && !a.save && pseg_on()) {
-            // inference: a wave per source node, the station sum folded into the pass (k_stage2_pseg), straight into the window's slot
-            a.part = (float*)ws + c->o_part + c->slot * c->slot_stride;
-            const long long gs = std::min<long long>((c->G + 3) / 4, (long long)c->num_cu * c->bpc2);
-            k_stage2_pseg<<<(int)std::max<long long>(8, gs / 8 * 8), 256, 0, st>>>(a, c->seg_rowptr, c->G);
-            HIP_TRY(hipGetLastError());
-            return GENIE_OK;
-        }
         k_stage2_pcsr<<<(int)std::max<long long>(8, gw / 8 * 8), 256, 0, st>>>(a);                       // (a multiple of the 8 XCDs)
         // the gated messages sit in the c rows, which exist GENIE_NBIG times only: their station sums (row order) go to the window's
         // own slot right away, one partial row per source node, so that every tail form (per window, side streams, batched) reads
@@ -2791,64 +2819,41 @@ int run_stage2(genie_ctx* c, const float* mask, const float* edge_attr, float* x
         if (!no_bip)
             k_seg_sum32<<<(c->G * 32 + 255) / 256, 256, 0, st>>>((const float*)ws + c->o_c + (c->slot % GENIE_NBIG) * c->big_stride, c->seg_rowptr,
                                                                  c->G, (float*)ws + c->o_part + c->slot * c->slot_stride);
-    } else if (c->use_fast && a.sta_user != nullptr && (!no_bip || x_latent_out != nullptr)) {
-        // the production configuration: uniform 8 / 15-degree graphs, station processing order; the static edge_attr is registered
-        // (genie_set_static_edge_attr), any other one is brought into processing order here (one extra pass over [P, 3])
-        a.wgmap = no_bip ? 0 : c->s2_wgmap;
-        if (no_bip) {      // last pass of the association heads: row-layout c / wu / wv written by k_assoc_b
-            k_stage2_ord<8, 15, true, true><<<da_grid(c, n_tiles, c->bpc2o), 256, 0, st>>>(a);       // (3 / 4 / 6 workgroups per CU: 291-298 us against 286)
-#if GENIE_TUNING
-        } else if (!s2h_on(c)) {     // A/B reference (GENIE_S2_OLD): the round-3 stage 2 on row-layout c / wv
-            if (!c->ea_tmp) HIP_TRY(gmalloc((void**)&c->ea_tmp, sizeof(float) * 3 * (size_t)c->P));
-            k_permute_sta_rows<<<(unsigned)((c->P * 3 + 255) / 256), 256, 0, st>>>(edge_attr, c->P, 3, c->sta_inv, c->S, c->ea_tmp);
-            a.ea_int = c->ea_tmp;
-            k_stage2_ord<8, 15, false><<<da_grid(c, n_tiles, c->bpc2o), 256, 0, st>>>(a);
-#endif
-        } else {           // s2h_on(c): stage 1 of this window wrote c / wv node-planar
-            if (!c->ws_np)     // (genie_set_stage_precision between a window's two stages would get here)
-                return fail(GENIE_ERR_STATE, "stage 2: the last stage 1 left row-layout c / wv but the f16x2 stage 2 reads them node-planar "
-                                             "(stage precision changed between the two stages of a window?)");
-            a.np = 1; a.packed = c->packed_s2h;
-            if (c->ea_frag && c->ea_user == edge_attr) a.ea_frag = c->ea_frag;
-            else {
-                if (!c->ea_frag_tmp) HIP_TRY(gmalloc((void**)&c->ea_frag_tmp, 32 * (size_t)c->P));
-                k_ea_frag<<<(unsigned)((c->P + 255) / 256), 256, 0, st>>>(edge_attr, c->P, c->S, c->sta_perm, c->ea_frag_tmp);
-                a.ea_frag = c->ea_frag_tmp;
-            }
-            const bool big = c->P_ext * 128 >= (1ll << 32);
-            if (!c->tab_host.empty() && !c->s2u_off) {
-                // source-neighbour rows of blocks of adjacent source nodes staged once in LDS (k_stage2_h2u), for this range of the order
-                const genie_ctx::S2uTables* tb = nullptr;
-                if ((rc = get_s2u_tables(c, gi_begin, gi_end, &tb))) return rc;
-                const size_t lds = sizeof(float) * S2H_IMG_FLOATS + (size_t)S2U_UCAP * 1024;
-                const long long items = (long long)tb->nblk * c->T;
-                const long long gsz = std::min<long long>((long long)c->num_cu * GENIE_S2U_BPC, (items + 7) / 8 * 8);
-                const int grid = (int)std::max<long long>(8, gsz / 8 * 8);
-                auto launch = [&](auto kern) -> int {      // (the 70-KB dynamic LDS needs the attribute once per kernel and device)
-                    if (int r = raise_lds_limit(c, (const void*)kern, 160 * 1024)) return r;
-                    kern<<<grid, S2U_WPB * 64, lds, st>>>(a, (const S2uBlock*)tb->blocks, tb->xcd0);
-                    return GENIE_OK;
-                };
-                if (x_latent_out) rc = big ? launch(k_stage2_h2u<true, true>) : launch(k_stage2_h2u<true, false>);
-                else rc = big ? launch(k_stage2_h2u<false, true>) : launch(k_stage2_h2u<false, false>);
-                if (rc) return rc;
-            } else {
-                const int grid = da_grid(c, n_tiles, c->bpc2h);
-                if (x_latent_out) { if (big) k_stage2_h2<true, true><<<grid, 256, 0, st>>>(a); else k_stage2_h2<true, false><<<grid, 256, 0, st>>>(a); }
-                else { if (big) k_stage2_h2<false, true><<<grid, 256, 0, st>>>(a); else k_stage2_h2<false, false><<<grid, 256, 0, st>>>(a); }
-            }
-        }
+        break;
     }
-    else {
-        if (c->ws_np && !no_bip)       // (no_bip: the association heads' last pass reads the rows k_assoc_b wrote, whatever stage 1 left)
-            return fail(GENIE_ERR_STATE, "stage 2: the last stage 1 left node-planar c / wv but the fp32 stage 2 reads rows (stage precision "
-                                         "changed between the two stages of a window?)");
-        k_stage2<<<da_grid(c, n_tiles, c->bpc2), 256, 0, st>>>(a);
+    case S2Route::AssocLast:      // row-layout c / wu / wv written by k_assoc_b
+        a.wgmap = 0;
+        k_stage2_ord<8, 15, true, true><<<da_grid(c, n_tiles, c->bpc2o), 256, 0, st>>>(a);       // (3 / 4 / 6 workgroups per CU: 291-298 us against 286)
+        break;
+    case S2Route::H2u:
+        // the static edge_attr is registered (genie_set_static_edge_attr), any other one is brought into processing order here
+        // (one extra pass over [P, 3])
+        a.wgmap = c->s2_wgmap; a.np = 1; a.packed = c->packed_s2h;
+        if (c->ea_frag && c->ea_user == edge_attr) a.ea_frag = c->ea_frag;
+        else {
+            if (!c->ea_frag_tmp) HIP_TRY(gmalloc((void**)&c->ea_frag_tmp, 32 * (size_t)c->P));
+            k_ea_frag<<<(unsigned)((c->P + 255) / 256), 256, 0, st>>>(edge_attr, c->P, c->S, c->sta_perm, c->ea_frag_tmp);
+            a.ea_frag = c->ea_frag_tmp;
+        }
+        if ((rc = launch_stage2_h2u<false>(c, a, gi_begin, gi_end, x_latent_out != nullptr, st))) return rc;
+        break;
     }
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }
 }  // namespace
+
+int genie_da_stage2_partials(genie_ctx* c, const float* mask, const float* edge_attr, float* x_latent_out, void* ws,
+                             void* stream) {
+    if (!c) return fail(GENIE_ERR_ARG, "null context");
+    return run_stage2(c, kInference, mask, edge_attr, x_latent_out, ws, stream, 0, c->G);
+}
+
+int genie_da_stage2_partials_range(genie_ctx* c, const float* mask, const float* edge_attr, float* x_latent_out, int gi_begin,
+                                   int gi_end, void* ws, void* stream) {
+    if (!c) return fail(GENIE_ERR_ARG, "null context");
+    return run_stage2(c, kInference, mask, edge_attr, x_latent_out, ws, stream, gi_begin, gi_end);
+}
 
 int genie_bipartite_readout(genie_ctx* c, float* bip_out, void* ws, void* stream) {
     int rc = check_ws(c, ws);
@@ -2856,7 +2861,7 @@ int genie_bipartite_readout(genie_ctx* c, float* bip_out, void* ws, void* stream
     if (!bip_out) return fail(GENIE_ERR_ARG, "genie_bipartite_readout: null output");
     const float* part = (const float*)ws + c->o_part + c->slot * c->slot_stride;
     { int rcp = ensure_packed(c, (hipStream_t)stream); if (rcp) return rcp; }
-    if (tail_wide(c)) k_bip_out_m<true><<<tl_blocks(c->G, c->num_cu * 2), 256, 0, (hipStream_t)stream>>>(part, c->G, part_T(c), c->packed[PL_BIP], bip_out, 0, 0);
+    if (tail_wide(c, kInference)) k_bip_out_m<true><<<tl_blocks(c->G, c->num_cu * 2), 256, 0, (hipStream_t)stream>>>(part, c->G, part_T(c), c->packed[PL_BIP], bip_out, 0, 0);
     else k_bip_out_m<false><<<tl_blocks(c->G, c->num_cu * 2), 256, 0, (hipStream_t)stream>>>(part, c->G, part_T(c), c->packed[PL_BIP], bip_out, 0, 0);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
@@ -2893,7 +2898,7 @@ int sa_blocks(const genie_ctx* c) { return tl_blocks(c->G, std::min(1024, c->tai
 
 // The pre-pass of `layer` was already produced (by k_sa_pre_m or by the previous layer's NEXT tail) in pj / gpart buffer `cur`;
 // with_next emits the next layer's pre-pass into the other buffer.
-int sa_launch_layer(genie_ctx* c, int layer, const float* x_in, const float* pos, float* out, float* ws, int cur,
+int sa_launch_layer(genie_ctx* c, const StageCall& call, int layer, const float* x_in, const float* pos, float* out, float* ws, int cur,
                     bool with_next, hipStream_t st) {
     SaArgs a;
     memset(&a, 0, sizeof(a));
@@ -2907,7 +2912,7 @@ int sa_launch_layer(genie_ctx* c, int layer, const float* x_in, const float* pos
     const int nb = sa_blocks(c);
     { int rcp = ensure_packed(c, st); if (rcp) return rcp; }
     a.img = c->packed[PL_SA1 + layer - 1];
-    if (tail_wide(c)) {
+    if (tail_wide(c, call)) {
         if (layer == 1) { if (with_next) k_sa_layer_m<15, true, true><<<nb, 256, 0, st>>>(a); else k_sa_layer_m<15, false, true><<<nb, 256, 0, st>>>(a); }
         else { if (with_next) k_sa_layer_m<30, true, true><<<nb, 256, 0, st>>>(a); else k_sa_layer_m<30, false, true><<<nb, 256, 0, st>>>(a); }
     } else if (layer == 1) {
@@ -2918,7 +2923,7 @@ int sa_launch_layer(genie_ctx* c, int layer, const float* x_in, const float* pos
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }
-int sa_launch_pre(genie_ctx* c, int layer, const float* x_in, float* ws, int cur, hipStream_t st) {
+int sa_launch_pre(genie_ctx* c, const StageCall& call, int layer, const float* x_in, float* ws, int cur, hipStream_t st) {
     SaArgs a;
     memset(&a, 0, sizeof(a));
     sa_fill_layer(c, layer, a);
@@ -2928,7 +2933,7 @@ int sa_launch_pre(genie_ctx* c, int layer, const float* x_in, float* ws, int cur
     const int nb = sa_blocks(c);
     { int rcp = ensure_packed(c, st); if (rcp) return rcp; }
     a.img = c->packed[PL_SA1 + layer - 1];
-    if (tail_wide(c)) { if (layer == 1) k_sa_pre_m<15, true><<<nb, 256, 0, st>>>(a); else k_sa_pre_m<30, true><<<nb, 256, 0, st>>>(a); }
+    if (tail_wide(c, call)) { if (layer == 1) k_sa_pre_m<15, true><<<nb, 256, 0, st>>>(a); else k_sa_pre_m<30, true><<<nb, 256, 0, st>>>(a); }
     else { if (layer == 1) k_sa_pre_m<15, false><<<nb, 256, 0, st>>>(a); else k_sa_pre_m<30, false><<<nb, 256, 0, st>>>(a); }
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
@@ -2943,8 +2948,8 @@ int genie_spatial_agg_fwd(genie_ctx* c, int layer, const float* x_in, const floa
     if (!x_in || !pos || !out) return fail(GENIE_ERR_ARG, "genie_spatial_agg_fwd: null argument");
     if (c->G_ext != c->G) return fail(GENIE_ERR_STATE, "genie_spatial_agg_fwd needs an unsharded source graph");
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = sa_launch_pre(c, layer, x_in, (float*)ws, 0, st))) return rc;
-    return sa_launch_layer(c, layer, x_in, pos, out, (float*)ws, 0, false, st);
+    if ((rc = sa_launch_pre(c, kInference, layer, x_in, (float*)ws, 0, st))) return rc;
+    return sa_launch_layer(c, kInference, layer, x_in, pos, out, (float*)ws, 0, false, st);
 }
 
 int genie_spatial_agg3_fwd(genie_ctx* c, const float* x_in15, const float* pos, float* out, void* ws, void* stream) {
@@ -2954,11 +2959,11 @@ int genie_spatial_agg3_fwd(genie_ctx* c, const float* x_in15, const float* pos, 
     if (c->G_ext != c->G) return fail(GENIE_ERR_STATE, "genie_spatial_agg3_fwd needs an unsharded source graph");
     hipStream_t st = (hipStream_t)stream;
     float* w = (float*)ws;
-    if ((rc = sa_launch_pre(c, 1, x_in15, w, 0, st))) return rc;
+    if ((rc = sa_launch_pre(c, kInference, 1, x_in15, w, 0, st))) return rc;
     const size_t so = c->slot * c->slot_stride;
-    if ((rc = sa_launch_layer(c, 1, x_in15, pos, w + c->o_sa0 + so, w, 0, true, st))) return rc;
-    if ((rc = sa_launch_layer(c, 2, w + c->o_sa0 + so, pos, w + c->o_sa1 + so, w, 1, true, st))) return rc;
-    return sa_launch_layer(c, 3, w + c->o_sa1 + so, pos, out, w, 0, false, st);
+    if ((rc = sa_launch_layer(c, kInference, 1, x_in15, pos, w + c->o_sa0 + so, w, 0, true, st))) return rc;
+    if ((rc = sa_launch_layer(c, kInference, 2, w + c->o_sa0 + so, pos, w + c->o_sa1 + so, w, 1, true, st))) return rc;
+    return sa_launch_layer(c, kInference, 3, w + c->o_sa1 + so, pos, out, w, 0, false, st);
 }
 
 int genie_path_fwd(genie_ctx* c, const float* slice, const float* mask, const float* edge_attr, const float* pos,
@@ -2987,13 +2992,13 @@ int genie_path_fwd(genie_ctx* c, const float* slice, const float* mask, const fl
         a.pj_out = w + c->o_pj0 + so; a.gpart_out = w + c->o_gpart + so;
         a.img = c->packed[PL_SA1];
         const int nb = sa_blocks(c);
-        if (tail_wide(c)) k_bip_pre_m<true><<<nb, 256, 0, st>>>(w + c->o_part + so, part_T(c), c->packed[PL_BIP], 0, a);
+        if (tail_wide(c, kInference)) k_bip_pre_m<true><<<nb, 256, 0, st>>>(w + c->o_part + so, part_T(c), c->packed[PL_BIP], 0, a);
         else k_bip_pre_m<false><<<nb, 256, 0, st>>>(w + c->o_part + so, part_T(c), c->packed[PL_BIP], 0, a);
         HIP_TRY(hipGetLastError());
     }
-    if ((rc = sa_launch_layer(c, 1, bip, pos, w + c->o_sa0 + so, w, 0, true, st))) return rc;
-    if ((rc = sa_launch_layer(c, 2, w + c->o_sa0 + so, pos, w + c->o_sa1 + so, w, 1, true, st))) return rc;
-    return sa_launch_layer(c, 3, w + c->o_sa1 + so, pos, x_spatial_out, w, 0, false, st);
+    if ((rc = sa_launch_layer(c, kInference, 1, bip, pos, w + c->o_sa0 + so, w, 0, true, st))) return rc;
+    if ((rc = sa_launch_layer(c, kInference, 2, w + c->o_sa0 + so, pos, w + c->o_sa1 + so, w, 1, true, st))) return rc;
+    return sa_launch_layer(c, kInference, 3, w + c->o_sa1 + so, pos, x_spatial_out, w, 0, false, st);
 }
 
 namespace {
@@ -3017,8 +3022,8 @@ RoArgs make_ro_args(const genie_ctx* c) {
 
 namespace {
 // grid read-out (k_readout_m<0>): fp64 chains for inference calls (their score scratch holds doubles), fp32 for the training forward
-int launch_readout_grid(genie_ctx* c, const RoArgs& a, bool with_cv, hipStream_t st) {
-    const bool wide = tail_wide(c);
+int launch_readout_grid(genie_ctx* c, const StageCall& call, const RoArgs& a, bool with_cv, hipStream_t st) {
+    const bool wide = tail_wide(c, call);
     const size_t lds = sizeof(float) * (ROM_LDS_FLOATS + (wide ? 4 * 16 * RO_SCS : 0) + (with_cv ? GP_IMG_FLOATS : 0));
     const int lds_max = (int)(sizeof(float) * (ROM_LDS_FLOATS + 4 * 16 * RO_SCS + GP_IMG_FLOATS));
     if (wide) {
@@ -3039,7 +3044,7 @@ int genie_readout_grid(genie_ctx* c, const float* x_spatial, const float* t_quer
     { int rcp = ensure_packed(c, (hipStream_t)stream); if (rcp) return rcp; }
     a.N = a.Nw = c->G; a.T = n_t; a.x_spatial = x_spatial; a.t_query = t_query; a.out = y_out;
     a.img = c->packed[PL_RO0];
-    { int rl = launch_readout_grid(c, a, false, (hipStream_t)stream); if (rl) return rl; }
+    { int rl = launch_readout_grid(c, kInference, a, false, (hipStream_t)stream); if (rl) return rl; }
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }
@@ -3059,7 +3064,7 @@ int readout_query_impl(genie_ctx* c, const float* x_spatial, const float* x_grid
     { int rcp = ensure_packed(c, (hipStream_t)stream); if (rcp) return rcp; }
     float* cvbuf = (float*)ws + c->o_cv + c->slot * c->slot_stride;
     a.cv = cvbuf;
-    if (tail_wide(c)) k_ro_pre_m<true><<<tl_blocks(c->G, c->tail_cu_ro), 256, 0, (hipStream_t)stream>>>(x_spatial, c->G, c->packed[PL_ROP], cvbuf, c->G, 0);
+    if (tail_wide(c, kInference)) k_ro_pre_m<true><<<tl_blocks(c->G, c->tail_cu_ro), 256, 0, (hipStream_t)stream>>>(x_spatial, c->G, c->packed[PL_ROP], cvbuf, c->G, 0);
     else k_ro_pre_m<false><<<tl_blocks(c->G, c->tail_cu_ro), 256, 0, (hipStream_t)stream>>>(x_spatial, c->G, c->packed[PL_ROP], cvbuf, c->G, 0);
     a.img = c->packed[PL_RO1];
     if (n_query <= 16384) {      // about one 16-query tile per wave of the launch: nothing else hides a wave's round trips (PF)
@@ -3089,7 +3094,7 @@ int genie_readout_grid_latent(genie_ctx* c, const float* x_spatial, const float*
     { int rcp = ensure_packed(c, (hipStream_t)stream); if (rcp) return rcp; }
     a.N = a.Nw = c->G; a.T = n_t; a.x_spatial = x_spatial; a.t_query = t_query; a.out = y_out; a.lat_out = y_latent_out;
     a.img = c->packed[PL_RO0];
-    { int rl = launch_readout_grid(c, a, false, (hipStream_t)stream); if (rl) return rl; }
+    { int rl = launch_readout_grid(c, kInference, a, false, (hipStream_t)stream); if (rl) return rl; }
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }
@@ -3132,7 +3137,7 @@ int genie_tail_batched(genie_ctx* c, int slot0, int nwin, const float* pos, cons
         a.out = w + c->o_bip + so; a.ws_out = ss; a.ws_slot = ss;
         a.pj_out = pj[0]; a.gpart_out = gp[0];
         a.img = c->packed[PL_SA1];
-        if (tail_wide(c)) k_bip_pre_m<true><<<grid, 256, 0, st>>>(w + c->o_part + so, part_T(c), c->packed[PL_BIP], ss, a);
+        if (tail_wide(c, kInference)) k_bip_pre_m<true><<<grid, 256, 0, st>>>(w + c->o_part + so, part_T(c), c->packed[PL_BIP], ss, a);
         else k_bip_pre_m<false><<<grid, 256, 0, st>>>(w + c->o_part + so, part_T(c), c->packed[PL_BIP], ss, a);
     }
     // SpatialAggregation x3: bip -> sa0 -> sa1 -> x_spatial_out [nwin, G, 30]
@@ -3149,7 +3154,7 @@ int genie_tail_batched(genie_ctx* c, int slot0, int nwin, const float* pos, cons
         a.pj_in = pj[cur]; a.gpart_in = gp[cur]; a.n_gpart_in = sa_vg(c);
         a.pj_out = pj[cur ^ 1]; a.gpart_out = gp[cur ^ 1];
         a.img = c->packed[PL_SA1 + layer - 1];
-        if (tail_wide(c)) {
+        if (tail_wide(c, kInference)) {
             if (layer == 1) k_sa_layer_m<15, true, true><<<grid, 256, 0, st>>>(a);
             else if (layer == 2) k_sa_layer_m<30, true, true><<<grid, 256, 0, st>>>(a);
             else k_sa_layer_m<30, false, true><<<grid, 256, 0, st>>>(a);
@@ -3166,7 +3171,7 @@ int genie_tail_batched(genie_ctx* c, int slot0, int nwin, const float* pos, cons
         RoArgs g = a;
         g.N = nwin * c->G; g.Nw = c->G; g.out = y_out; g.img = c->packed[PL_RO0];
         if (x_out) { g.cv_out = w + c->o_cv + so; g.cv_ws = ss; g.pimg = c->packed[PL_ROP]; }
-        { int rl = launch_readout_grid(c, g, x_out != nullptr, st); if (rl) return rl; }
+        { int rl = launch_readout_grid(c, kInference, g, x_out != nullptr, st); if (rl) return rl; }
     }
     if (x_out) {
         RoArgs q = a;
@@ -3209,7 +3214,7 @@ int genie_embed_window_split(genie_ctx* c, const double* pick_t, const int32_t* 
                            stream);
     if (rc == GENIE_OK && xs) {
         c->xs_slice = slice_out; c->xs_mask = mask_out; c->xs_ws = ws; c->xs_mm_copy = c->slot % GENIE_NBIG;
-        c->xs_sta_order = sta_order_on(c) ? 1 : 0;
+        c->xs_sta_order = sta_order_on(c, kInference) ? 1 : 0;
     }
     return rc;
 }
@@ -3233,7 +3238,7 @@ int embed_window_impl(genie_ctx* c, const double* pick_t, const int32_t* pick_st
     a.n_extra = (int)ceil(3.0 * kernel_sig_t / dt);                                       // process_utils.py:518
     a.emb = emb_ws; a.trv = trv; a.rows = c->P_ext; a.slice = slice_out; a.mask = mask_out; a.xs = xs;
     a.no_phase = c->no_phase; a.sign_input = c->sign_input;
-    a.sta_inv = (xs && sta_order_on(c)) ? c->sta_inv : nullptr;
+    a.sta_inv = (xs && sta_order_on(c, kInference)) ? c->sta_inv : nullptr;
     a.mm = xs ? (float*)xs - c->o_xs + c->o_mm + (c->slot % GENIE_NBIG) * c->big_stride : nullptr;   // xs = workspace + o_xs
     HIP_TRY(hipMemsetAsync(emb_ws, 0, sizeof(float) * 2 * (size_t)a.S * a.n_time, st));
     if (n_picks > 0) {
@@ -3462,11 +3467,9 @@ int genie_da_train_fwd(genie_ctx* c, const float* slice, const float* mask, cons
     if (rc) return rc;
     if (!slice || !mask || !edge_attr || !save || !r_out) return fail(GENIE_ERR_ARG, "genie_da_train_fwd: null argument");
     if ((rc = train_check(c, "genie_da_train_fwd", true, true))) return rc;
-    c->force_generic = 1; c->train_save = save;
-    rc = run_stage1(c, slice, mask, nullptr, nullptr, ws, stream, 0, c->G, true);
-    if (!rc) rc = run_stage2(c, mask, edge_attr, x_latent_out, ws, stream, 0, c->G);
-    c->force_generic = 0; c->train_save = nullptr;
-    if (rc) return rc;
+    const StageCall call{save, true};
+    if ((rc = run_stage1(c, call, slice, mask, nullptr, nullptr, ws, stream, 0, c->G, true))) return rc;
+    if ((rc = run_stage2(c, call, mask, edge_attr, x_latent_out, ws, stream, 0, c->G))) return rc;
     float* part = (float*)ws + c->o_part + c->slot * c->slot_stride;
     k_part_sum<<<(c->G * 30 + 255) / 256, 256, 0, (hipStream_t)stream>>>(part, c->G, part_T(c), r_out);
     HIP_TRY(hipGetLastError());
@@ -3637,22 +3640,19 @@ int genie_tail_train_fwd(genie_ctx* c, const float* pos, const float* x_query, c
     // inputs land in `tsave` instead of the workspace slot
     k_part_sum32<<<(c->G * 32 + 255) / 256, 256, 0, st>>>(w + c->o_part + so, c->G, part_T(c), r);
     k_bip_out_m<false><<<tl_blocks(c->G, c->tail_cu_sa), 256, 0, st>>>(w + c->o_part + so, c->G, part_T(c), c->packed[PL_BIP], bip, 0, 0);
-    if ((rc = raise_lds_limit(c, (const void*)k_readout_m<1>, (int)(sizeof(float) * ROM_LDS_FLOATS)))) return rc;   // (before tail_train is set: no
-                                                                                                                     // early return may leave it on)
-    c->tail_train = 1;           // fp32 chains: the backward recomputes every pre-activation of the tail with them
-    rc = sa_launch_pre(c, 1, bip, w, 0, st);
-    if (!rc) rc = sa_launch_layer(c, 1, bip, pos, sa1, w, 0, true, st);
-    if (!rc) rc = sa_launch_layer(c, 2, sa1, pos, sa2, w, 1, true, st);
-    if (!rc) rc = sa_launch_layer(c, 3, sa2, pos, xs, w, 0, false, st);
+    if ((rc = raise_lds_limit(c, (const void*)k_readout_m<1>, (int)(sizeof(float) * ROM_LDS_FLOATS)))) return rc;
+    const StageCall call{nullptr, true};     // fp32 chains (the tail's pre-activations go to `tsave`)
+    if ((rc = sa_launch_pre(c, call, 1, bip, w, 0, st))) return rc;
+    if ((rc = sa_launch_layer(c, call, 1, bip, pos, sa1, w, 0, true, st))) return rc;
+    if ((rc = sa_launch_layer(c, call, 2, sa1, pos, sa2, w, 1, true, st))) return rc;
+    if ((rc = sa_launch_layer(c, call, 3, sa2, pos, xs, w, 0, false, st))) return rc;
     RoArgs a = make_ro_args(c);
     a.T = n_t; a.x_spatial = xs; a.t_query = t_query;
-    if (!rc) {
+    {
         RoArgs g = a;
         g.N = g.Nw = c->G; g.out = y_out; g.lat_out = y_latent_out; g.img = c->packed[PL_RO0];
-        rc = launch_readout_grid(c, g, false, st);
+        if ((rc = launch_readout_grid(c, call, g, false, st))) return rc;
     }
-    c->tail_train = 0;
-    if (rc) return rc;
     float* cvbuf = w + c->o_cv + so;
     k_ro_pre_m<false><<<tl_blocks(c->G, c->tail_cu_ro), 256, 0, st>>>(xs, c->G, c->packed[PL_ROP], cvbuf, c->G, 0);
     {
@@ -3856,8 +3856,8 @@ int assoc_fwd_impl(genie_ctx* c, const float* y_latent, const float* mask_src, c
     const bool variant = c->has_edges || c->abs_sta != nullptr;
     if (variant && !c->as_ps) HIP_TRY(gmalloc((void**)&c->as_ps, sizeof(float) * AS_PS * (size_t)edge_rows_sta(c)));
     assoc_pre_launch(c, y_latent, mask_src, st);
-    if (save) { c->force_generic = 1; c->train_save = save; }      // training forward: caller's station order, pre-activations kept
-    DaArgs d = make_da_args(c, (float*)ws);
+    const StageCall call{save, save != nullptr};      // save: training forward (caller's station order, pre-activations kept)
+    DaArgs d = make_da_args(c, call, (float*)ws);
     AsArgs a;
     memset(&a, 0, sizeof(a));
     a.S = c->S; a.G = c->G; a.T = c->T; a.seg = d.seg; a.nxcd = d.nxcd;
@@ -3890,9 +3890,7 @@ int assoc_fwd_impl(genie_ctx* c, const float* y_latent, const float* mask_src, c
         k_assoc_b<false, 16><<<std::max(8, c->num_cu / 8 * 8), 1024, 0, st>>>(a);
     }
     // second pair of neighbour means + PReLU2 = the stage-2 kernel of this context without its Bipartite half
-    rc = run_stage2(c, mask, edge_attr, out, ws, stream, 0, c->G, c->raw + g_params[W_AS_ACT2].off, 1);
-    if (save) { c->force_generic = 0; c->train_save = nullptr; }
-    if (rc) return rc;
+    if ((rc = run_stage2(c, call, mask, edge_attr, out, ws, stream, 0, c->G, c->raw + g_params[W_AS_ACT2].off, 1))) return rc;
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }
@@ -4353,8 +4351,8 @@ int genie_ws_export(genie_ctx* c, int which, void* ws, float* out, void* stream)
         default: return fail(GENIE_ERR_ARG, "genie_ws_export: which must be 0..2");
     }
     const long long n = rows * ncol;
-    k_export<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(src, rows, pitch, ncol, out, sta_order_on(c) ? c->sta_perm : nullptr, c->S,
-                                                                         (c->ws_np && which != 1) ? 1 : 0);
+    k_export<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(src, rows, pitch, ncol, out, sta_order_on(c, kInference) ? c->sta_perm : nullptr, c->S,
+                                                                         (c->s1_layout == RowLayout::NodePlanar && which != 1) ? 1 : 0);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }
