@@ -232,6 +232,10 @@ def apply_windows_device(net, geom, P, trv_times, tsteps_abs=None, t_win=6.0, st
                 flush(first)
                 first = w + 1
         hp.wait_tails()
+    # the verdicts of the day's last windows, on every context of the model (a shard's local one included): one wait per day
+    torch.cuda.current_stream(dev).synchronize()
+    for h in net._contexts():
+        h.check_input_range()
     return Out_2, times
 
 
@@ -336,8 +340,7 @@ class GridLeg(object):
     def check(self):
         """Raise what the device-side checks of the calls COMPLETED so far found (`HipPath.check_input_range` / `check_index_flags`);
         the per-day loops call it after their final copy to the host, which has waited for every window."""
-        net = self.net
-        for hp in ((net._hip,) if getattr(net, "_shard", None) is None else (net._shard.local, net._shard.full)):
+        for hp in self.net._contexts():
             hp.check_input_range()
 
     def embed(self, picks, t0, max_t, kernel_sig_t, dt):

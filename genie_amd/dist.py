@@ -26,6 +26,8 @@ sharded here is its product-node numbering `p = g * n_sta + s` (`process_utils.p
 import numpy as np
 import torch
 
+from . import engine
+
 
 class ShardRows(object):
     """Rows of a per-product-node tensor in a rank's LOCAL order: the S-row blocks of its owned source nodes (space-filling-curve
@@ -300,7 +302,6 @@ class ShardedPath(object):
 
     def __init__(self, n_sta, n_grid, sta_csr, A_src_src, pos_global, world, rank, device, group=None, scale_rel=30000.0,
                  pos_sta=None, overlap=True, halo="a2a", emulate=False):
-        from . import engine
         self.group = group
         self.n_sta, self.n_grid = int(n_sta), int(n_grid)
         order = engine.sfc_order(np.asarray(pos_global))
@@ -331,6 +332,11 @@ class ShardedPath(object):
         self.tail_stream = torch.cuda.Stream(device=dev) if self.local.device.type == "cuda" else None
         self._tail_done = None
 
+    @property
+    def contexts(self):
+        """Both HIP contexts of the shard: the P-sized local one and the replicated G-sized one."""
+        return (self.local, self.full)
+
     def set_weights(self, named):
         self.local.set_weights(named)
         self.full.set_weights(named)
@@ -358,9 +364,9 @@ class ShardedPath(object):
         if isinstance(t, ShardRows):
             if t.own_only != own_only and self.plan.n_halo:
                 if own_only and not t.own_only:           # owned blocks come first in the local order
-                    return lp_f32(t.t, name)[:n_loc]
+                    return engine._f32(t.t, name, (self.plan.n_ext * self.n_sta, cols))[:n_loc]
                 raise ValueError("%s: rows of the owned source nodes only, the halo rows are needed too" % name)
-            return lp_f32(t.t, name, (n_loc, cols))
+            return engine._f32(t.t, name, (n_loc, cols))
         t = torch.as_tensor(t)
         if tuple(t.shape) != (self.n_grid * self.n_sta, cols):
             raise ValueError("%s: expected shape (%d, %d) (all product nodes) or a ShardRows of %d local rows, got %s"
@@ -417,9 +423,9 @@ class ShardedPath(object):
         lp = self.local
         lp.check_input_range()         # (verdicts of the windows that have completed: engine.HipPath.check_input_range)
         P_ext = p.n_ext * S
-        Slice_ext = lp_f32(Slice_ext, "Slice", (P_ext, 4))
-        Mask_ext = lp_f32(Mask_ext, "Mask", (P_ext, 4))
-        edge_attr_own = lp_f32(edge_attr_own, "edge_attr", (p.n_own * S, 3))
+        Slice_ext = engine._f32(Slice_ext, "Slice", (P_ext, 4))
+        Mask_ext = engine._f32(Mask_ext, "Mask", (P_ext, 4))
+        edge_attr_own = engine._f32(edge_attr_own, "edge_attr", (p.n_own * S, 3))
         ea = getattr(lp, "_static_ea", None)
         if ea is None or ea.data_ptr() != edge_attr_own.data_ptr() or edge_attr_own._version != lp._static_ea_version:
             # the static edge_attr of the owned rows: registered once, so that stage 2 reads its processing-order copy and runs
@@ -487,7 +493,3 @@ class ShardedPath(object):
         if self._tail_done is not None:
             torch.cuda.current_stream(self.device).wait_event(self._tail_done)
 
-
-def lp_f32(t, name, shape):
-    from . import engine
-    return engine._f32(t, name, shape)

@@ -285,6 +285,23 @@ def time_partition(dt_partition):
     return (float(dt_partition[0]), float(dt_partition[1] - dt_partition[0]), None, n)
 
 
+def _verdict_error(flags, magnitude, limit, live=False):
+    """The exception for the device-side verdicts of a context: IndexError when an index flag is set, GenieHipError otherwise. `live`:
+    the context stays in use (and runs the fp32 kernels from now on when the magnitude is set); otherwise it is replaced or dropped."""
+    what = []
+    if flags & 1:
+        what.append("lslc_fwd: a pick outside the time-pointer table (tpick outside dt_partition, or ipick outside the stations of A_edges)")
+    if flags & 2:
+        what.append("arrivals: a station index `ipick` outside [0, n_sta)")
+    if magnitude:
+        what.append("Slice / Mask entries of magnitude %.6g in the f16x2 stage kernels (the committed weights keep their hidden states inside "
+                    "the fp16 range only up to |input| <= %.6g; the reference's embedding produces [-1, 1])" % (magnitude, limit))
+    tail = ("The results of the last calls on this replaced context are invalid and must be recomputed" if not live else
+            "The results of the calls issued since the last check are invalid; this context now runs the fp32 kernels (stage_precision "
+            "'f32'): repeat those calls" if magnitude else "Its results were computed from clamped indices and are invalid")
+    return (IndexError if flags else _lib.GenieHipError)("an earlier call on this context met " + "; ".join(what) + ". " + tail)
+
+
 class HipPath(object):
     """One libgenie_hip context bound to the current CUDA(HIP) device.
 
@@ -409,14 +426,11 @@ class HipPath(object):
     def __del__(self):
         try:
             if getattr(self, "ctx", None) and self.ctx.value:
-                fl, mx = ctypes.c_uint(0), ctypes.c_float(0.0)
-                self.lib.genie_index_flags(self.ctx, ctypes.byref(fl), 0)
-                self.lib.genie_input_range(self.ctx, ctypes.byref(mx), None, 0)
-                if fl.value or mx.value != 0.0:
+                verdicts = self._read_verdicts()
+                if verdicts[0] or verdicts[1]:
                     import warnings
-                    warnings.warn("genie_amd: a HIP context is destroyed with unread device-side verdicts (index flags %#x, input magnitude "
-                                  "%.6g): results of its last calls were computed from clamped indices / outside the verified fp16 range"
-                                  % (fl.value, mx.value), RuntimeWarning)
+                    warnings.warn("genie_amd: a HIP context is destroyed with unread device-side verdicts: %s" % _verdict_error(*verdicts),
+                                  RuntimeWarning)
                 self.lib.genie_ctx_destroy(self.ctx)
                 self.ctx = ctypes.c_void_p(0)
         except Exception:
@@ -490,19 +504,13 @@ class HipPath(object):
         word of host-mapped memory, read without synchronising -- it reflects the calls that have completed; `synchronize=True` waits for
         the device's current stream first, so that every call issued so far is covered). The context is switched to the fp32 kernels,
         which take any input the reference's fp32 arithmetic takes, before the error is raised: the results of the calls issued since the
-        last check are invalid and must be recomputed. Called at the top of every entry point that runs stage 1, by `wait_tails`, and
-        wherever the host has just waited for the device anyway (module.forward's deferred verdicts, the per-day loops' final copies)."""
+        last check are invalid and must be recomputed. Index flags are raised first, the magnitude word then stays for the next check.
+        Called at the top of every entry point that runs stage 1, by `wait_tails`, and where the host has just waited for the device."""
         self.check_index_flags(synchronize)
-        mx, lim = ctypes.c_float(0.0), ctypes.c_float(0.0)
-        _lib.check(self.lib.genie_input_range(self.ctx, ctypes.byref(mx), ctypes.byref(lim), 0), "genie_input_range")
-        if mx.value != 0.0:
-            _lib.check(self.lib.genie_input_range(self.ctx, ctypes.byref(mx), None, 1), "genie_input_range")   # atomic fetch-and-clear
+        _, mx, lim = self._read_verdicts(flags=False)
+        if mx:
             self.set_stage_precision("f32")
-            raise _lib.GenieHipError(
-                "an earlier call handed the f16x2 stage kernels Slice / Mask entries of magnitude %.6g; the committed weights keep their "
-                "hidden states inside the fp16 range only up to |input| <= %.6g (the reference's embedding produces [-1, 1]). The results "
-                "of the calls issued since the last check are invalid; this context now runs the fp32 kernels (stage_precision 'f32'): "
-                "repeat those calls." % (mx.value, lim.value))
+            raise _verdict_error(0, mx, lim, live=True)
 
     def check_index_flags(self, synchronize=False):
         """Raise IndexError when a pick of an earlier `lslc_fwd` / arrivals call indexed outside its table (genie_index_flags: host-mapped
@@ -512,35 +520,41 @@ class HipPath(object):
         for the device's current stream first, so that the calls issued so far are covered."""
         if synchronize:
             torch.cuda.current_stream(self.device).synchronize()
-        fl = ctypes.c_uint(0)
-        _lib.check(self.lib.genie_index_flags(self.ctx, ctypes.byref(fl), 0), "genie_index_flags")
-        if fl.value:
-            _lib.check(self.lib.genie_index_flags(self.ctx, ctypes.byref(fl), 1), "genie_index_flags")          # atomic fetch-and-clear
-            what = []
-            if fl.value & 1:
-                what.append("lslc_fwd: a pick lies outside the time-pointer table (tpick outside dt_partition, or ipick outside the stations "
-                            "of A_edges)")
-            if fl.value & 2:
-                what.append("arrivals: a station index `ipick` outside [0, n_sta)")
-            raise IndexError("an earlier call on this context met " + "; ".join(what) + ". Its results were computed from clamped indices "
-                             "and are invalid")
+        fl, _, _ = self._read_verdicts(magnitude=False)
+        if fl:
+            raise _verdict_error(fl, 0.0, 0.0, live=True)
 
     def retire(self, synchronize=True):
-        """Last look at the device-side verdicts of a context that is being replaced or dropped (`module.forward` builds a new context
-        per training sample; nothing reads the flag word once the context is gone): raises what `check_input_range` would.
-        `synchronize=False` when the caller has just waited for the device (the constructor of the replacing context does).
+        """Last look at the device-side verdicts of a context that is being replaced or dropped (nothing reads them once it is gone):
+        ONE error for both words, IndexError when an index flag is set; the precision of a context about to be destroyed is left as it
+        is. `synchronize=False` when the caller has just waited for the device (the constructor of the replacing context does).
         `__del__` cannot raise; it warns instead."""
         if getattr(self, "ctx", None) and self.ctx.value:
             if synchronize:
                 with torch.cuda.device(self.device):
                     torch.cuda.synchronize()
-            self.check_input_range()
+            fl, mx, lim = self._read_verdicts()
+            if fl or mx:
+                raise _verdict_error(fl, mx, lim)
 
     def discard_flags(self):
         """Forget the device-side verdicts (calls whose results the caller throws away anyway, e.g. a context built on graphs that the
         deferred structure checks then rejected)."""
-        _lib.check(self.lib.genie_index_flags(self.ctx, None, 1), "genie_index_flags")
-        _lib.check(self.lib.genie_input_range(self.ctx, None, None, 1), "genie_input_range")
+        self._read_verdicts()
+
+    def _read_verdicts(self, flags=True, magnitude=True):
+        """The one reader of the two device-side verdict words (host-mapped, no synchronisation: they reflect the calls that have
+        completed) -> (index flags, input magnitude, its limit). Reads the words asked for only; one found set is fetched and cleared."""
+        fl, mx, lim = ctypes.c_uint(0), ctypes.c_float(0.0), ctypes.c_float(0.0)
+        if flags:
+            _lib.check(self.lib.genie_index_flags(self.ctx, ctypes.byref(fl), 0), "genie_index_flags")
+            if fl.value:                                                                                    # atomic fetch-and-clear
+                _lib.check(self.lib.genie_index_flags(self.ctx, ctypes.byref(fl), 1), "genie_index_flags")
+        if magnitude:
+            _lib.check(self.lib.genie_input_range(self.ctx, ctypes.byref(mx), ctypes.byref(lim), 0), "genie_input_range")
+            if mx.value != 0.0:
+                _lib.check(self.lib.genie_input_range(self.ctx, ctypes.byref(mx), None, 1), "genie_input_range")
+        return fl.value, mx.value, lim.value
 
     # ---- stages --------------------------------------------------------------------------------
     def da_stage1(self, Slice, Mask, debug=False):

@@ -481,6 +481,21 @@ class StationSourceAttentionMergedPhases(nn.Module):
         self.n_heads, self.n_latent, self.eps = n_heads, n_latent, eps
 
 
+def _retire(contexts):
+    """Last look at the device-side verdicts of replaced HIP contexts (`HipPath.retire`; no synchronisation: the constructor of the
+    replacing context has waited for the device). Every context is retired, even when an earlier one raises; then ONE error names every
+    verdict found (IndexError when any index flag was set)."""
+    errors = []
+    for hp in contexts:
+        try:
+            hp.retire(synchronize=False)
+        except Exception as e:
+            errors.append(e)
+    if errors:
+        raise (IndexError if any(isinstance(e, IndexError) for e in errors) else _engine._lib.GenieHipError)(
+            " | ".join(str(e) for e in errors))
+
+
 class GCN_Detection_Network_extended(nn.Module):
     """Drop-in for the reference class of the same name (module.py:882-1020).
 
@@ -541,6 +556,7 @@ class GCN_Detection_Network_extended(nn.Module):
         self._hip = None
         self._path_params = None
         self._edge_attr = None
+        self._retire_later = None          # `forward`'s build: the contexts it replaced, retired after its fallback (`_install`)
 
     def _weight_split(self):
         """state_dict view -> the library's registry view (static-term columns of the two other model definitions under their own names)."""
@@ -549,90 +565,84 @@ class GCN_Detection_Network_extended(nn.Module):
         return _split_edge_columns if self.use_updated_model_definition else (_split_abs_columns if self.use_absolute_pos else None)
 
     # ---- graphs --------------------------------------------------------------------------------
-    def _configure_engine(self):
-        """The model-level options every new HIP context gets, whichever builder made it (Cartesian or `use_subgraph`): the weight
-        registry view, TemporalAttention's time scale, and the two flags of the device pick embedding (config.yaml:91, :93)."""
-        self._path_params = _path_param_dict(self)
-        for hp in ((self._hip,) if self._shard is None else (self._shard.local, self._shard.full)):
-            hp.set_scale_t(self.TemporalAttention.scale_t)
-            hp.set_phase_types(self.use_phase_types)
-            hp.set_sign_input(self.use_sign_input)
+    def _contexts(self):
+        """The model's live HIP contexts: (the context,) unsharded, the shard's (local, full) sharded, () before `set_adjacencies*`."""
+        if self._shard is not None:
+            return self._shard.contexts
+        return (self._hip,) if self._hip is not None else ()
 
-    def _build_engine(self, sta_csr, src_csr, n_sta, n_grid, pos_src, pos_loc=None):
-        # (positions on the GPU are ordered there: no host round trip per context, which the training call convention builds per sample)
+    def _new_cartesian(self, sta_csr, src_csr, n_sta, n_grid, pos_loc, pos_src):
+        """A context for the Cartesian product of two base graphs (CSR); on a sharded model this rank's part (genie_amd/dist.py): the
+        shard plan from the base source graph and the space-filling-curve order of the source nodes (no collective), the local context
+        over the owned + halo source nodes, the replicated G-sized one. (GPU positions are ordered there: no host round trip per sample.)"""
         dev = next(self.parameters()).device
-        if self._shard_cfg is not None:
-            return self._build_engine_sharded(sta_csr, src_csr, n_sta, n_grid, pos_src, pos_loc, dev)
-        order = _engine.sfc_order(pos_src) if pos_src is not None else None
-        sta_order = _engine.sfc_order(pos_loc) if pos_loc is not None else None
-        new = _engine.HipPath(n_sta, n_grid, sta_csr, src_csr, grid_order=order, scale_rel=self.scale_rel,
-                              device=dev, sta_order=sta_order)
-        self._retire_engine()
-        self._hip = new
-        self._configure_engine()
-        if self.use_updated_model_definition:
-            if pos_loc is None or pos_src is None:
-                raise ValueError("use_updated_model_definition=True needs station and source positions")
-            self._hip.set_edge_features(pos_loc.to(dev), pos_src.to(dev))                 # module.py:1102-1111
-        if self.use_absolute_pos:
-            if pos_loc is None or pos_src is None:
-                raise ValueError("use_absolute_pos=True needs station and source positions")
-            self._hip.set_absolute_pos(pos_loc.to(dev), pos_src.to(dev))                  # module.py:1007
-
-    def _build_engine_sharded(self, sta_csr, src_csr, n_sta, n_grid, pos_src, pos_loc, dev):
-        """This rank's part of the product graph (genie_amd/dist.py): the shard plan from the base source graph and the space-filling-
-        curve order of the source nodes (the same arithmetic on every rank, no collective), the local context over the owned + halo
-        source nodes, the replicated G-sized context. `self._hip` is the replicated one: the read-out heads run on it unchanged."""
-        if pos_src is None or pos_loc is None:
-            raise ValueError("a sharded model needs station and source positions (the shard plan follows the source nodes' order)")
+        if self._shard_cfg is None:
+            return _engine.HipPath(n_sta, n_grid, sta_csr, src_csr, grid_order=_engine.sfc_order(pos_src), scale_rel=self.scale_rel,
+                                   device=dev, sta_order=_engine.sfc_order(pos_loc))
         rank, world, group = self._shard_cfg
         rp, col = [torch.as_tensor(t).cpu().long().numpy() for t in src_csr]
         A_src = np.stack((col, np.repeat(np.arange(n_grid, dtype=np.int64), np.diff(rp))))
         to_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
-        new = _dist.ShardedPath(n_sta, n_grid, sta_csr, A_src, to_np(pos_src), world, rank, dev, group=group,
-                                scale_rel=self.scale_rel, pos_sta=to_np(pos_loc), **self._shard_opts)
-        self._retire_engine()
-        self._shard = new
-        self._hip = self._shard.full
-        self._hip.side_stream = self._shard.tail_stream                    # where the pipelined windows' (y, x) are produced
-        self._hip.side_streams = [self._shard.tail_stream, self._shard.comm_stream]
-        self._configure_engine()
-        if self.use_updated_model_definition:
-            self._shard.set_edge_features(pos_loc, pos_src)
-        if self.use_absolute_pos:
-            self._shard.set_absolute_pos(pos_loc, pos_src)
+        return _dist.ShardedPath(n_sta, n_grid, sta_csr, A_src, to_np(pos_src), world, rank, dev, group=group,
+                                 scale_rel=self.scale_rel, pos_sta=to_np(pos_loc), **self._shard_opts)
 
-    def _set_edge_attr(self, edge_attr, n_sta, n_grid):
-        """`A_src_in_edges.x` [P, 3] registered with the context(s); a sharded model keeps the rows of its owned source nodes only (a full
-        tensor is cut down once, a `ShardRows` of the owned rows is taken as it is: config 4's 1.2 GB need not exist on any rank).
-        A callable `edge_attr(source_node_ids) -> [len(ids) * S, 3]` is evaluated for the source nodes this model holds, in blocks."""
+    def _install(self, new, edge_attr, pos_loc, pos_src, pairs=None):
+        """Every `set_adjacencies*` ends here. `new` (a HipPath, or a ShardedPath on a sharded model) is configured completely while the
+        old contexts stand: model options (config.yaml:91, :93), the positions of the static terms (one row per product node of an
+        irregular graph through `pairs` = A_src_in_sta; a shard maps them to its extended node list) and the static `A_src_in_edges.x`
+        (a shard keeps its owned rows only; a callable `edge_attr(source_node_ids)` is evaluated for the nodes `new` holds). Then it is
+        swapped in and the replaced contexts are retired -- by `forward` after its fallback, inside its build: past the swap only their
+        verdicts raise, and the model stands on `new`."""
+        sharded = isinstance(new, _dist.ShardedPath)
+        if pairs is not None:
+            new.set_subgraph_stations(pairs[0])
+        if sharded:            # `self._hip` is the replicated context: the read-out heads run on it unchanged
+            new.full.side_stream = new.tail_stream                    # where the pipelined windows' (y, x) are produced
+            new.full.side_streams = [new.tail_stream, new.comm_stream]
+        for hp in new.contexts if sharded else (new,):
+            hp.set_scale_t(self.TemporalAttention.scale_t)
+            hp.set_phase_types(self.use_phase_types)
+            hp.set_sign_input(self.use_sign_input)
+        if self.use_updated_model_definition or self.use_absolute_pos:
+            if not sharded:
+                pos_loc, pos_src = pos_loc.to(new.device), pos_src.to(new.device)
+            if pairs is not None:
+                idx = pairs.to(new.device).long()
+                pos_loc, pos_src = pos_loc[idx[0]].contiguous(), pos_src[idx[1]].contiguous()
+            if self.use_updated_model_definition:
+                new.set_edge_features(pos_loc, pos_src)           # module.py:1102-1111 (irregular edge lists: :1059-1072)
+            if self.use_absolute_pos:
+                new.set_absolute_pos(pos_loc, pos_src)            # module.py:1007 / :1056
         if callable(edge_attr):
-            edge_attr = self._rows_from_callable(edge_attr, n_grid, own_only=True)
-        if self._shard is not None:
-            self._edge_attr = self._shard.local_rows(edge_attr, "A_src_in_edges.x", 3, own_only=True).contiguous()
-            self._edge_attr_version = self._edge_attr._version
-            self._shard.local.set_static_edge_attr(self._edge_attr)
-            return
-        self._edge_attr = _engine._f32(edge_attr, "A_src_in_edges.x", (n_sta * n_grid, 3))
-        self._edge_attr_version = self._edge_attr._version
-        self._hip.set_static_edge_attr(self._edge_attr)
-
-    def _rows_from_callable(self, fn, n_grid, own_only=False, block=2048):
-        """`fn(ids)` -> rows of the source nodes `ids` ([len, S, C] or [len * S, C]), evaluated block by block for every source node of
-        an unsharded model, or for the owned (+ halo) source nodes of this rank; returned on the device (a `ShardRows` when sharded)."""
-        dev = self._hip.device
-        if self._shard is not None:
-            p = self._shard.plan
-            ids = p.own_global if own_only else p.ext_global
+            edge_attr = self._rows_from_callable(edge_attr, new, own_only=True)
+        if sharded:
+            ea = new.local_rows(edge_attr, "A_src_in_edges.x", 3, own_only=True).contiguous()
+            new.local.set_static_edge_attr(ea)
         else:
-            ids = np.arange(n_grid, dtype=np.int64)
+            ea = _engine._f32(edge_attr, "A_src_in_edges.x", (new.n_prod, 3))
+            new.set_static_edge_attr(ea)                          # (a no-op on an irregular product graph)
+        replaced = self._contexts()
+        self._shard, self._hip = (new, new.full) if sharded else (None, new)
+        self._edge_attr, self._edge_attr_version = ea, ea._version
+        self._path_params = _path_param_dict(self)
+        if self._retire_later is not None:
+            self._retire_later.extend(replaced)
+        else:
+            _retire(replaced)
+
+    def _rows_from_callable(self, fn, path, own_only=False, block=2048):
+        """`fn(ids)` -> rows of the source nodes `ids` ([len, S, C] or [len * S, C]), evaluated block by block for every source node of
+        the HipPath `path`, or for the owned (+ halo) source nodes of the ShardedPath `path`; returned on the device (a `ShardRows` when
+        sharded)."""
+        sharded = isinstance(path, _dist.ShardedPath)
+        ids = (path.plan.own_global if own_only else path.plan.ext_global) if sharded else np.arange(path.n_grid, dtype=np.int64)
         parts = []
         for i in range(0, len(ids), block):
             r = fn(ids[i:i + block])
             r = r if torch.is_tensor(r) else torch.from_numpy(np.ascontiguousarray(r))
-            parts.append(r.reshape(-1, r.shape[-1]).to(dev, torch.float32))
+            parts.append(r.reshape(-1, r.shape[-1]).to(path.device, torch.float32))
         t = torch.cat(parts, 0) if len(parts) != 1 else parts[0]
-        return _dist.ShardRows(t, own_only=own_only) if self._shard is not None else t
+        return _dist.ShardRows(t, own_only=own_only) if sharded else t
 
     @property
     def is_sharded(self):
@@ -704,8 +714,8 @@ class GCN_Detection_Network_extended(nn.Module):
             a, b = [t.cpu() for t in src_from_A], [t.cpu() for t in src_csr]
             if a[0].shape != b[0].shape or a[1].shape != b[1].shape or not (torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])):
                 raise ValueError("A_src is not the base graph of A_in_src")
-        self._build_engine(_engine.csr_from_table(sta_nbr), src_csr, n_sta, n_grid, pos_src, pos_loc)
-        self._set_edge_attr(A_src_in_edges.x, n_sta, n_grid)
+        self._install(self._new_cartesian(_engine.csr_from_table(sta_nbr), src_csr, n_sta, n_grid, pos_loc, pos_src), A_src_in_edges.x,
+                      pos_loc, pos_src)
         self._pending_checks = verdict
 
     def _resolve_pending_checks(self):
@@ -725,14 +735,6 @@ class GCN_Detection_Network_extended(nn.Module):
             self._hip.discard_flags()
         return ok
 
-    def _retire_engine(self):
-        """The context(s) about to be replaced: called right AFTER the replacing context was constructed (its constructor waits for the
-        device), so the verdicts of every call issued on the old one are in; raises what they hold."""
-        old = [h for h in ((self._hip,) if self._shard is None else (self._shard.local, self._shard.full)) if h is not None]
-        self._hip = self._shard = None
-        for h in old:
-            h.retire(synchronize=False)
-
     def _set_adjacencies_subgraph(self, A_in_sta, A_in_src, A_src_in_edges, A_src_in_sta, A_src, n_sta, n_grid, pos_loc, pos_src):
         """`use_subgraph: True` (config.yaml:86, process_utils.py:744-849): the product nodes are the pairs listed in
         A_src_in_sta (grouped by source node) and the edge lists are irregular: product-level CSRs, generic HIP kernels."""
@@ -746,25 +748,9 @@ class GCN_Detection_Network_extended(nn.Module):
         sub = {"n_prod": n_prod, "sta_csr": _engine.csr_from_edges(A_in_sta, n_prod),
                "src_csr": _engine.csr_from_edges(A_in_src, n_prod), "seg_rowptr": seg}
         order = _engine.sfc_order(pos_src.detach().cpu().numpy())
-        dev = next(self.parameters()).device
         new = _engine.HipPath(n_sta, n_grid, None, _engine.csr_from_edges(A_src, n_grid), grid_order=order,
-                              scale_rel=self.scale_rel, device=dev, subgraph=sub)
-        self._retire_engine()
-        self._hip = new
-        self._hip.set_subgraph_stations(pairs[0])
-        self._configure_engine()
-        if self.use_updated_model_definition:       # module.py:1059-1072 on the irregular edge lists: positions per product node
-            if pos_loc is None or pos_src is None:
-                raise ValueError("use_updated_model_definition=True needs station and source positions")
-            pl, ps = _engine._f32(pos_loc.to(dev), "pos_loc"), _engine._f32(pos_src.to(dev), "pos_src")
-            self._hip.set_edge_features(pl[pairs[0].to(dev)].contiguous(), ps[pairs[1].to(dev)].contiguous())
-        if self.use_absolute_pos:                   # module.py:1007 / :1056: the positions of a product node's station and source node
-            if pos_loc is None or pos_src is None:
-                raise ValueError("use_absolute_pos=True needs station and source positions")
-            pl, ps = _engine._f32(pos_loc.to(dev), "pos_loc"), _engine._f32(pos_src.to(dev), "pos_src")
-            self._hip.set_absolute_pos(pl[pairs[0].to(dev)].contiguous(), ps[pairs[1].to(dev)].contiguous())
-        self._edge_attr = _engine._f32(A_src_in_edges.x, "A_src_in_edges.x", (n_prod, 3))
-        self._edge_attr_version = self._edge_attr._version
+                              scale_rel=self.scale_rel, device=next(self.parameters()).device, subgraph=sub)
+        self._install(new, A_src_in_edges.x, pos_loc, pos_src, pairs=pairs)
 
     def set_adjacencies_subgraph_from_positions(self, pos_loc, pos_src, edge_attr=None, k_sta_edges=10, k_spc_edges=15,
                                                 max_deg_offset=5.0, k_nearest_pairs=30, scale_deg=110e3,
@@ -786,21 +772,13 @@ class GCN_Detection_Network_extended(nn.Module):
         pairs = _engine.subgraph_pairs_device(pos_loc, pos_src, max_deg_offset, k_nearest_pairs, scale_deg)
         src_csr = _engine.csr_from_table(src_tab)
         sub = _engine.subgraph_csr_device(pairs, n_grid, _engine.csr_from_table(sta_tab), src_csr)
-        order = _engine.sfc_order(pos_src.detach().cpu().numpy())
-        new = _engine.HipPath(n_sta, n_grid, None, src_csr, grid_order=order, scale_rel=self.scale_rel, device=dev, subgraph=sub)
-        self._retire_engine()
-        self._hip = new
-        self._hip.set_subgraph_stations(pairs[0])
-        self._configure_engine()
-        if self.use_updated_model_definition:
-            self._hip.set_edge_features(pos_loc[pairs[0].long()].contiguous(), pos_src[pairs[1].long()].contiguous())
-        if self.use_absolute_pos:
-            self._hip.set_absolute_pos(pos_loc[pairs[0].long()].contiguous(), pos_src[pairs[1].long()].contiguous())
         if edge_attr is None:
             edge_attr = (pos_src[pairs[1]] - pos_loc[pairs[0]]) / float(scale_pairwise_sta_in_src_distances)
         elif callable(edge_attr):
             edge_attr = edge_attr(pairs)
-        self._edge_attr = _engine._f32(edge_attr, "edge_attr", (sub["n_prod"], 3))
+        order = _engine.sfc_order(pos_src.detach().cpu().numpy())
+        new = _engine.HipPath(n_sta, n_grid, None, src_csr, grid_order=order, scale_rel=self.scale_rel, device=dev, subgraph=sub)
+        self._install(new, edge_attr, pos_loc, pos_src, pairs=pairs)
         self.A_src = A_src
         return A_sta, A_src, pairs
 
@@ -815,9 +793,9 @@ class GCN_Detection_Network_extended(nn.Module):
         n_sta, n_grid = int(pos_loc.shape[0]), int(pos_src.shape[0])
         sta_tab, A_sta = _engine.knn_graph_device(pos_loc, _graph.k_sta_effective(k_sta_edges, n_sta))
         src_tab, A_src = _engine.knn_graph_device(pos_src, min(k_spc_edges, n_grid - 1))
+        new = self._new_cartesian(_engine.csr_from_table(sta_tab), _engine.csr_from_table(src_tab), n_sta, n_grid, pos_loc, pos_src)
         self.A_src = A_src
-        self._build_engine(_engine.csr_from_table(sta_tab), _engine.csr_from_table(src_tab), n_sta, n_grid, pos_src, pos_loc)
-        self._set_edge_attr(edge_attr, n_sta, n_grid)
+        self._install(new, edge_attr, pos_loc, pos_src)
         return A_sta, A_src
 
     def set_adjacencies_base(self, A_sta_sta, A_src_src, edge_attr, pos_loc, pos_src, A_edges_p=None, A_edges_s=None,
@@ -828,9 +806,8 @@ class GCN_Detection_Network_extended(nn.Module):
         n_sta, n_grid = int(pos_loc.shape[0]), int(pos_src.shape[0])
         self.A_edges_p, self.A_edges_s, self.dt_partition, self.tlatent = A_edges_p, A_edges_s, dt_partition, tlatent
         self.A_src = torch.as_tensor(A_src_src)
-        self._build_engine(_engine.csr_from_edges(A_sta_sta, n_sta), _engine.csr_from_edges(A_src_src, n_grid),
-                           n_sta, n_grid, pos_src, pos_loc)
-        self._set_edge_attr(edge_attr, n_sta, n_grid)
+        self._install(self._new_cartesian(_engine.csr_from_edges(A_sta_sta, n_sta), _engine.csr_from_edges(A_src_src, n_grid),
+                                          n_sta, n_grid, pos_loc, pos_src), edge_attr, pos_loc, pos_src)
 
     # ---- hot path ------------------------------------------------------------------------------
     def _path(self, Slice, Mask, x_temp_cuda_cart, want_x_latent=False, want_bip=False):
@@ -917,8 +894,7 @@ class GCN_Detection_Network_extended(nn.Module):
         if isinstance(table, _dist.ShardRows):
             return table
         if callable(table):          # table(source_node_ids) -> their rows: evaluated for the source nodes this model / rank holds
-            n_grid = self._shard.n_grid if self._shard is not None else self._hip.n_grid
-            return self._rows_from_callable(table, n_grid)
+            return self._rows_from_callable(table, self._shard if self._shard is not None else self._hip)
         t = table if torch.is_tensor(table) else torch.from_numpy(np.ascontiguousarray(table))
         if t.dim() == 3:
             t = t.reshape(t.shape[0] * t.shape[1], t.shape[2])
@@ -1070,16 +1046,24 @@ class GCN_Detection_Network_extended(nn.Module):
             # deferral pays only while the callers' lists are written in the literal form the device checks recognise: once a sample
             # failed them (valid graphs in another edge order, base graphs of non-uniform degree, ...) every later sample would pay a
             # discarded forward + a second build, so the model remembers and builds with the checks up front from then on
-            if getattr(self, "_defer_failed", False):
-                self.set_adjacencies(*adj)
-            else:
-                try:
-                    self.set_adjacencies(*adj, _defer_checks=True)
-                except Exception:
-                    # building on unverified (clamped) tables can fail in ways the checked path reports properly or does not hit at all
-                    self._defer_failed = True
+            self._retire_later = []
+            try:
+                if getattr(self, "_defer_failed", False):
                     self.set_adjacencies(*adj)
+                else:
+                    try:
+                        self.set_adjacencies(*adj, _defer_checks=True)
+                    except (ValueError, RuntimeError):
+                        # building on unverified (clamped) tables can fail in ways the checked path reports properly or does not hit
+                        # at all (shape checks, torch / library errors); the verdicts of the replaced context are not read in here
+                        self._defer_failed = True
+                        self.set_adjacencies(*adj)
+            finally:
+                replaced, self._retire_later = self._retire_later, None
             self._fwd_key, self._fwd_refs = key, graph_tensors
+            # what the previous sample's calls left on the replaced context propagates as it is; the new context stands, and the
+            # next call with these graphs runs on it
+            _retire(replaced)
         else:
             self.A_src_in_edges, self.A_Lg_in_src = A_src_in_edges, A_Lg_in_src
             self.A_edges_p, self.A_edges_s, self.dt_partition, self.tlatent = A_edges_p, A_edges_s, dt_partition, tlatent

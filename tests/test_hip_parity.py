@@ -2175,9 +2175,18 @@ def test_device_side_verdicts_of_a_contexts_last_call_are_not_lost():
         net._hip.check_index_flags(synchronize=True)
     net._hip.check_index_flags(synchronize=True)                     # reported once
     bad_call()                                                       # (2) the context is replaced right after its last call
-    with pytest.raises(IndexError, match="outside the time-pointer table"):
+    old = net._hip
+    with pytest.raises(IndexError, match="outside the time-pointer table") as err:
         net.set_adjacencies_base(*adj)
-    net.set_adjacencies_base(*adj)                                   # the model is usable again
+    assert "recomputed" in str(err.value)
+    assert net._hip is not None and net._hip is not old              # the model stands on the new context ...
+    del old, err                                                     # (the traceback holds the contexts: step 4 drops the last reference)
+    tp_ok = tp_bad.clone()
+    tp_ok[4] = tp_bad[3]
+    net._hip.sync_weights(net._path_params)                          # ... and runs on it, no second set_adjacencies_base
+    out = net._hip.lslc_fwd(0, s, tab, dtp_t, tp_ok, ip, phase, tlatent, 0, net.LocalSliceLgCollapseP.eps)
+    net._hip.check_index_flags(synchronize=True)
+    assert torch.isfinite(out).all()
     leg = apply.GridLeg(net, geom.x_grid, trv)                       # (3) the per-day loops' final check
     bad_call()
     torch.cuda.synchronize()
@@ -2196,6 +2205,113 @@ def test_device_side_verdicts_of_a_contexts_last_call_are_not_lost():
         del hp, leg, leg2
         gc.collect()
     assert any("unread device-side verdicts" in str(w.message) for w in rec)
+
+
+def test_replacing_a_sharded_models_contexts_reports_the_verdicts_of_both():
+    """A sharded model has two contexts (the shard's local one, the replicated full one), and replacing them retires both: a verdict on
+    each (inputs beyond the verified fp16 range on the local one, an Arrivals station index outside the table on the full one) comes out
+    of `set_adjacencies_base` as ONE error naming both, and the model then runs on the new contexts (one rank, no process group)."""
+    c = Case("odd_33x257")
+    net = module.GCN_Detection_Network_extended(lambda x: x, lambda x: x, device=DEV, shard=(0, 1))
+    net.load_state_dict({k: v.clone() for k, v in c.weights.items()})
+    net.eval()
+    locs, xg = c.locs.float().to(DEV), c.x_grid.float().to(DEV)
+    adj = (c.A_sta_sta, c.A_src_src, c.edge_attr.to(DEV), locs, xg)
+    net.set_adjacencies_base(*adj)
+    Slice, Mask = c.Slice.to(DEV), c.Mask.to(DEV)
+    args = (None, None, None, locs, xg, c.x_query.float().to(DEV), c.t_query.float().to(DEV))
+    n, S = 6, c.S
+    ok_ip = torch.arange(n, device=DEV) % S
+    bad_ip = ok_ip.clone()
+    bad_ip[2] = S
+    emb, trv = torch.zeros((1, 30), device=DEV), torch.ones((1, S, 2), device=DEV)
+    rows, tp, phase = torch.zeros((n, 15), device=DEV), torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)
+    with torch.no_grad():
+        ref = net.forward_fixed_source(Slice, Mask, *args)
+        lim = net._shard.local.input_limit()
+        assert lim > 0.0
+        net.forward_fixed_source(Slice * (4.0 * lim), Mask, *args)                  # local context: beyond the verified range
+        net._shard.full.arrivals_fwd(torch.zeros(1, device=DEV), emb, trv, rows, rows, tp, bad_ip, phase, net.Arrivals.eps)   # full one
+        torch.cuda.synchronize()
+        old = net._shard.contexts
+        with pytest.raises(IndexError) as err:
+            net.set_adjacencies_base(*adj)
+        assert "magnitude" in str(err.value) and "station index" in str(err.value)
+        assert net._shard is not None and not set(map(id, net._shard.contexts)) & set(map(id, old))
+        del old, err
+        got = net.forward_fixed_source(Slice, Mask, *args)                           # no second set_adjacencies_base
+        net._shard.full.arrivals_fwd(torch.zeros(1, device=DEV), emb, trv, rows, rows, tp, ok_ip, phase, net.Arrivals.eps)
+        for hp in net._shard.contexts:
+            hp.check_input_range(synchronize=True)
+    assert all(torch.equal(a, b) for a, b in zip(ref, got))
+
+
+def test_owned_rows_of_an_owned_plus_halo_shard_rows():
+    """`ShardedPath.local_rows(..., own_only=True)` given the owned + halo rows (`node_rows`): the owned blocks, after the row count is
+    checked; `set_adjacencies_base` takes such rows as its edge_attr (rank 0 of a two-rank plan: no collective is involved)."""
+    from genie_amd import dist as gdist
+    c = Case("odd_33x257")
+    net = module.GCN_Detection_Network_extended(lambda x: x, lambda x: x, device=DEV, shard=(0, 2))
+    net.load_state_dict({k: v.clone() for k, v in c.weights.items()})
+    locs, xg, ea = c.locs.float().to(DEV), c.x_grid.float().to(DEV), c.edge_attr.to(DEV)
+    net.set_adjacencies_base(c.A_sta_sta, c.A_src_src, ea, locs, xg)
+    sp = net._shard
+    assert sp.plan.n_halo > 0
+    own = sp.local_rows(ea, "edge_attr", 3, own_only=True)
+    ext = net.node_rows(ea, 3)
+    assert isinstance(ext, gdist.ShardRows) and not ext.own_only and ext.shape[0] == sp.plan.n_ext * c.S
+    assert torch.equal(sp.local_rows(ext, "edge_attr", 3, own_only=True), own)
+    with pytest.raises(ValueError, match="expected shape"):
+        sp.local_rows(gdist.ShardRows(ext.t[: -c.S]), "edge_attr", 3, own_only=True)
+    net.set_adjacencies_base(c.A_sta_sta, c.A_src_src, ext, locs, xg)
+    assert torch.equal(net._edge_attr, own)
+
+
+def test_forward_raises_the_verdict_of_the_replaced_context_as_it_is():
+    """`forward` builds a new context when the graphs change and retires the old one after its deferred build: a verdict the previous
+    sample's calls left there (here a bad Arrivals station index issued directly on the context) propagates out of `forward` unchanged,
+    does not count as a failed deferral, and leaves the model on the new context; repeating the call does not rebuild and returns what a
+    fresh model returns."""
+    import os
+    from tests.util import GOLDEN_DIR
+    from oracle import genie_oracle as O
+    z = np.load(os.path.join(GOLDEN_DIR, "assoc_7x45.npz"))
+    S, G = int(z["n_sta"]), int(z["n_grid"])
+    t = lambda k, dt=torch.float32: torch.from_numpy(np.asarray(z[k])).to(dt).to(DEV)
+
+    def fresh():
+        net = module.GCN_Detection_Network_extended(lambda x: x, lambda x: x, device=DEV)
+        net.load_state_dict({k: v.clone() for k, v in O.weights_from_npz(z).items()}, strict=True)
+        return net.eval()
+
+    A1, A2, A3, A4 = graph.cartesian_product_edges(z["A_sta_sta"], z["A_src_src"], S, G)
+    ea = graph.GraphEdges(x=t("edge_attr"), edge_index=A3.to(DEV))
+    rest = (t("A_edges_p", torch.long), t("A_edges_s", torch.long), t("dt_partition"), t("tlatent"), t("tpick"), t("ipick", torch.long),
+            t("phase_label"), t("locs"), t("x_grid"), t("x_query"), t("x_query_src"), t("t_query"), t("tq_sample"), t("trv_out_q"))
+    graphs = lambda: (A1.to(DEV), A2.to(DEV), ea, ea, A4.to(DEV), t("A_src_src", torch.long))     # new tensors: new graphs for `forward`
+    first, second = graphs(), graphs()
+    net = fresh()
+    calls = []
+    plain = net.set_adjacencies
+    net.set_adjacencies = lambda *a, **k: (calls.append(bool(k.get("_defer_checks"))), plain(*a, **k))[1]
+    n = 5
+    ip = torch.arange(n, device=DEV) % S
+    ip[1] = S + 2
+    rows, zn = torch.zeros((n, 15), device=DEV), torch.zeros(n, device=DEV)
+    with torch.no_grad():
+        net(t("Slice"), t("Mask"), *first, *rest)
+        old = net._hip
+        old.arrivals_fwd(torch.zeros(1, device=DEV), torch.zeros((1, 30), device=DEV), torch.ones((1, S, 2), device=DEV), rows, rows, zn,
+                         ip, zn, net.Arrivals.eps)
+        with pytest.raises(IndexError, match="station index"):
+            net(t("Slice"), t("Mask"), *second, *rest)
+        assert calls == [True, True] and not getattr(net, "_defer_failed", False)
+        assert net._hip is not None and net._hip is not old
+        del old
+        got = net(t("Slice"), t("Mask"), *second, *rest)
+        assert calls == [True, True]                                  # the same graphs: no rebuild
+        exp = fresh()(t("Slice"), t("Mask"), *second, *rest)
+    assert all(torch.equal(a, b) for a, b in zip(got, exp))
 
 
 @pytest.mark.parametrize("S,n_src,n_picks", [(7, 4, 23), (40, 9, 1500), (12, 1, 1), (30, 3, 600), (3, 2, 1300)])

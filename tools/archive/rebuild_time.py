@@ -89,10 +89,7 @@ for rep in range(3):
         del old
         hp = timed("HipPath.__init__", lambda: engine.HipPath(n_sta, n_grid, engine.csr_from_table(tabs[0]), src_csr, grid_order=order[0],
                                                               scale_rel=net.scale_rel, device=dev, sta_order=order[1]), acc)
-        net._hip = hp
-        net._configure_engine()
-        net._edge_attr = ea.x
-        timed("set_static_edge_attr", lambda: hp.set_static_edge_attr(ea.x), acc)
+        timed("_install (options, set_static_edge_attr)", lambda: net._install(hp, ea.x, locs, xg), acc)
         timed("sync_weights (upload, pack, range guard)", lambda: hp.sync_weights(net._path_params, None), acc)
         timed("first path_train_fwd (tables on first use)", lambda: net._path_train(s[0], s[1], xg, s[17], s[19]), acc)
         timed("second path_train_fwd", lambda: net._path_train(s[0], s[1], xg, s[17], s[19]), acc)
