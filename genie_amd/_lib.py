@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(_HERE)
 SRC = os.path.join(_HERE, "csrc", "genie_hip.hip")
 LIB_DIR = os.path.join(_HERE, "lib")
-LIB_PATH = os.environ.get("GENIE_LIB_PATH", os.path.join(LIB_DIR, "libgenie_hip.so"))  # override: tuning builds (tools/tune.py) only
+LIB_PATH = os.environ.get("GENIE_LIB_PATH", os.path.join(LIB_DIR, "libgenie_hip.so"))  # override: variant builds for same-box A/B runs
 INCLUDE = os.path.join(REPO, "include")
 
 # every symbol include/genie_hip.h declares: (name, restype, argtypes)

@@ -33,23 +33,11 @@
 
 #include "genie_hip.h"
 
-// GENIE_TUNING=1 builds (tools/tune.py only) add run-time ablation switches (env GENIE_ABLATE) that SKIP parts of
-// a kernel to attribute its time; they break the results and are compiled out of the product library.
-#ifndef GENIE_TUNING
-#define GENIE_TUNING 0
-#endif
-#if GENIE_TUNING
-#define ABL(a, bit) (((a).abl >> (bit)) & 1)
-#else
-#define ABL(a, bit) 0
-#endif
-
 // read-once rows (c, Mask, edge_attr of stage 2): plain loads (non-temporal ones measured slower, 0.354 vs 0.326 ms)
 #define GENIE_LD_STREAM(ptr) (*(ptr))
-// Register budgets and depths settled by measurement (profiles/EXPERIMENTS.md): k_stage2_ord / k_stage2_h2 are held to two waves per
+// Register budgets and depths settled by measurement (profiles/EXPERIMENTS.md): k_stage2_ord is held to two waves per
 // SIMD (three: spills, +50 % fabric reads, 0.313 vs 0.302 ms); k_stage1_h2 keeps 6 row loads in flight ahead of their use (3..8 equal)
 #define GENIE_S2_WAVES 2
-#define GENIE_S2H_WAVES 2
 #define GENIE_H2_DEPTH 6
 
 namespace {
@@ -413,7 +401,7 @@ constexpr int H2_NBIAS = 6;     // init_trns, l1_t1_2, l1_t2_2, l2_t1_1, l2_t2_1
 constexpr int H2_IMG_FLOATS = H2_FRAGS * 256 + H2_NBIAS * 32 + 16;
 constexpr int H2_TBL = H2_FRAGS * 512 + H2_NBIAS * 32 + 16;
 
-// STAGE 2 on the 16-bit matrix pipe (k_stage2_h2): 1-KB A fragments of v_mfma_f32_16x16x32_f16 for Bipartite_ReadIn.fc1, lane
+// STAGE 2 on the 16-bit matrix pipe (k_stage2_h2u): 1-KB A fragments of v_mfma_f32_16x16x32_f16 for Bipartite_ReadIn.fc1, lane
 // (i = lane & 15, kg = lane >> 4) holds the 8 K slots (kg, e) of output row 16 t + i. K slots of the x_latent step: e < 4 = channel
 // 4 kg + e of the first half (o1, 15 channels + 1 zero), e >= 4 = channel 4 kg + e - 4 of the second half; of the edge_attr step:
 // group 0 = {e0, e1, e2, - | e0, e1, e2, -} (first | second pieces), group 1 = {e0, e1, e2 (/ 16), - | -}; see k_ea_frag.
@@ -499,7 +487,7 @@ void build_h2_table(std::vector<int32_t>& tbl) {
     for (int k = 0; k < 6; ++k) scal[k] = g_params[sv[k]].off;
 }
 
-// k_stage2_h2's image: same entry format as build_h2_table (k_pack_h2 writes both)
+// k_stage2_h2u's image: same entry format as build_h2_table (k_pack_h2 writes both)
 void build_s2h_table(std::vector<int32_t>& tbl) {
     tbl.assign(S2H_TBL, -1);
     auto put = [&](int f, int i, int kg, int e, int piece, int off) {
@@ -941,17 +929,7 @@ __global__ void k_pack_all(const float* __restrict__ raw, const PackPlan* __rest
 // ------------------------------------------------------------------------------------------------
 // device helpers
 // ------------------------------------------------------------------------------------------------
-#ifndef GENIE_ABL_MFMA
-#define GENIE_ABL_MFMA GENIE_TUNING      // the run-time MFMA switch costs every fp32 MFMA a branch: -DGENIE_ABL_MFMA=0 for timing other hooks
-#endif
-#if GENIE_TUNING
-__device__ int g_abl_mfma;  // set from the host in tuning builds
-#endif
-#if GENIE_ABL_MFMA
-#define MFMA16(a, b, c) (g_abl_mfma ? ((c) + (a) * (b)) : __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0))
-#else
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-#endif
 
 // wave-level ordering point for data the lanes of ONE wave exchange through LDS. The DS instructions of a wave execute in issue
 // order, so a wavefront-scope fence (compiler ordering only, no s_waitcnt) is enough; the workgroup-scope fence used until round 4
@@ -1010,7 +988,6 @@ struct DaArgs {
     int S, G, T;               // stations, source nodes this launch processes, tiles per source node = ceil(S/16)
     int gi0;                   // ... = positions [gi0, gi0 + G) of the processing order (sub-range launches of the sharded path; else 0)
     int seg;                   // source nodes per scheduling segment
-    int abl;                   // GENIE_TUNING only: ablation bits
     int nxcd;                  // XCD-chunked sweep (8) or flat (1)
     const int32_t* sta_rowptr; const int32_t* sta_col;
     const int32_t* src_rowptr; const int32_t* src_col;
@@ -1308,7 +1285,7 @@ struct genie_ctx {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int device = 0;            // the HIP device the context was created on (genie_ctx_destroy drains THAT device)
     int num_cu;
-    int seg, bpc1, bpc2;       // sweep segments (env GENIE_SEG), workgroups per CU of the generic stage kernels
+    int seg, bpc1, bpc2;       // sweep segments, workgroups per CU of the generic stage kernels
     int ks_uni, kp_uni;        // uniform in-degree of the station / source graph, -1 when ragged
     int use_fast;              // the reference's kNN graphs (ks_uni == 8 && kp_uni == 15): the pipelined kernels k_stage1_h2 / k_stage2_ord apply
     int bpc2o;                 // workgroups of k_stage2_ord per CU (its occupancy: three per CU)
@@ -1360,16 +1337,6 @@ int raise_lds_limit(genie_ctx* c, const void* kern, int bytes) {
 // rows of the static edge-feature tables (DataAggregationEdges): per station / per source node, per product node on an irregular graph
 long long edge_rows_sta(const genie_ctx* c) { return c->pcsr ? c->P : c->S; }
 long long edge_rows_src(const genie_ctx* c) { return c->pcsr ? c->P : c->G; }
-// scheduling overrides of the tuning builds (-DGENIE_TUNING=1: tools/tune.py, tools/*_sweep.sh); the product library reads no
-// environment variable
-const char* tune_env(const char* name) {
-#if GENIE_TUNING
-    return getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
 // The f16x2 kernels run when the shape admits them AND the precision mode says so: auto = while the fp16 range guard holds for the
 // committed weights (k_h2_range), else the fp32-MFMA kernels take over -- no environment variable, no non-finite output.
 bool h2_on(const genie_ctx* c) { return c->use_h2 && (c->prec_mode == 1 || (c->prec_mode == 0 && c->range_ok)); }
@@ -1593,9 +1560,6 @@ DaArgs make_da_args(const genie_ctx* c, const StageCall& call, float* ws) {
     a.eb_sta = c->has_edges ? (so ? c->ebias_sta_p : c->ebias_sta) : nullptr;
     a.eb_src = c->has_edges ? c->ebias_src : nullptr;
     a.seg = std::max(1, c->seg);
-#if GENIE_TUNING
-    { const char* e = getenv("GENIE_ABLATE"); a.abl = e ? atoi(e) : 0; }
-#endif
     a.nxcd = 8;
     const size_t bo = (c->slot % GENIE_NBIG) * c->big_stride;
     a.c = ws + c->o_c + bo; a.wu = ws + c->o_wu + bo; a.wv = ws + c->o_wv + bo;
@@ -2192,10 +2156,9 @@ int genie_ctx_create(genie_ctx** out, int n_sta, int n_grid, int n_grid_ext, con
         c->num_cu = it->second;
     }
     {
-        const char* e;
         // scheduling segments: node-major sweeps (1) at config 2; at 2000 stations station-tile-major sweeps over segments of 16
         // source nodes keep the source-neighbour rows of stage 1 in L2 (config 4 on one GPU: stage 1 25.8 -> 24.8 ms)
-        c->seg = (e = tune_env("GENIE_SEG")) ? atoi(e) : (n_sta >= 1024 ? 16 : 1);
+        c->seg = n_sta >= 1024 ? 16 : 1;
         // G-sized tail: few, long-lived workgroups. Next to the persistent P-sized kernels a tail workgroup only runs when one
         // of theirs retires and keeps that CU until it ends, so what the tail costs the main stream is its CU-time = workgroups x
         // duration, and most of a short tail workgroup is fixed cost (its LDS weight image). Two 62-KB read-out workgroups per CU
@@ -2219,14 +2182,14 @@ int genie_ctx_create(genie_ctx** out, int n_sta, int n_grid, int n_grid_ext, con
             occ1 = it->second[0]; occ2 = it->second[1]; occo = it->second[2];
         }
         c->bpc1 = std::max(1, occ1);
-        c->bpc2 = (e = tune_env("GENIE_BPC2")) ? atoi(e) : std::max(1, occ2);
+        c->bpc2 = std::max(1, occ2);
         // Large station counts (config 4: 2000 stations, 128 KB of wu / wv rows per source node): the gathers leave L2, and what
         // pays is locality, not concurrency: blocks of 4 adjacent source nodes per workgroup (one node per wave: the four waves
         // share half of their source rows, every wu block is gathered on one CU) and two workgroups per CU. Config 4 on one
         // GPU: stage 2 16.1 -> 11.8 ms (three workgroups, interleaved items: 16.1; two: 14.8; block map alone: 13.1). At 200
         // stations the same settings lose (0.266 -> 0.268 ms), hence by size.
-        c->s2_wgmap = (e = tune_env("GENIE_S2_WGMAP")) ? (atoi(e) != 0) : (n_sta >= 1024);
-        c->bpc2o = (e = tune_env("GENIE_BPC2")) ? atoi(e) : std::min(2, std::max(1, occo));     // round 3, after the f16x2 stage 1: 2 beat 3 at 200 stations too (window 0.593 -> 0.588 ms)
+        c->s2_wgmap = n_sta >= 1024;
+        c->bpc2o = std::min(2, std::max(1, occo));     // round 3, after the f16x2 stage 1: 2 beat 3 at 200 stations too (window 0.593 -> 0.588 ms)
         // the reference's kNN graphs (8 station / 15 source neighbours everywhere): pipelined kernels k_stage1_h2 / k_stage2_ord
         c->use_fast = c->ks_uni == 8 && c->kp_uni == 15;
         // f16x2 kernels: 24-bit multiplicands (64-bit row offsets are a template variant). Whether they run: h2_on()
@@ -2236,13 +2199,6 @@ int genie_ctx_create(genie_ctx** out, int n_sta, int n_grid, int n_grid_ext, con
         // 8: 0.579; the weight image is staged once per CU instead of four times)
         c->bpc1b = 1;
     }
-#if GENIE_TUNING
-    {
-        const char* e = getenv("GENIE_ABLATE");
-        int v = (e && (atoi(e) & 4)) ? 1 : 0;
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_abl_mfma), &v, sizeof(int)));
-    }
-#endif
     layout_ws(c);
     HIP_TRY(hipDeviceSynchronize());
     guard.c = nullptr;
@@ -3380,20 +3336,12 @@ namespace {
 // association phase's light passes did not pay: k_as_b3 174 -> 167 us, k_as_b0 (88 registers, 12 tiles) 301 -> 334 us: they keep 4.
 // Every wave still writes its own partial slot; the scratch is sized by the heaviest pass (30 tiles x 4 waves).
 constexpr int TR_WPB_LIGHT = 8;
-// pass 1' as two waves per tile (k_train_b1s); the tuning builds can switch back to the one-wave kernel for A/B runs
+// pass 1' as two waves per tile (k_train_b1s)
 #ifndef GENIE_B1_SPLIT_DEFAULT
 #define GENIE_B1_SPLIT_DEFAULT 1          // (a build with 0 = the one-wave kernel, for same-box A/B runs of production code generation)
 #endif
-bool b1_split_on() {
-    static const char* e = tune_env("GENIE_B1_SPLIT");
-    return e ? atoi(e) != 0 : GENIE_B1_SPLIT_DEFAULT != 0;
-}
-int train_grid(const genie_ctx* c) {
-#if GENIE_TUNING
-    { static const char* e = getenv("GENIE_TRAIN_WG"); if (e) return std::max(8, c->num_cu * atoi(e) / 8 * 8); }
-#endif
-    return std::max(8, c->num_cu * 2 / 8 * 8);
-}      // 2 workgroups per CU (1: +10 %, 3: +6 %, 4: +1 % step time)
+bool b1_split_on() { return GENIE_B1_SPLIT_DEFAULT != 0; }
+int train_grid(const genie_ctx* c) { return std::max(8, c->num_cu * 2 / 8 * 8); }      // 2 workgroups per CU (1: +10 %, 3: +6 %, 4: +1 % step time)
 size_t train_part_floats(const genie_ctx* c) { return (size_t)train_grid(c) * 4 * (30 * 256 + 12 * 16 + 16); }
 // `variants`: the call also serves DataAggregationEdges / use_absolute_pos (the forward_fixed_source step does; the association heads'
 // training step is the default model definition only)
@@ -3545,9 +3493,6 @@ int da_train_bwd_impl(genie_ctx* c, const float* slice, const float* mask, const
         a.r_sta_rowptr = c->rp_sta_rowptr; a.r_sta_cw = c->rp_sta_cw; a.r_src_rowptr = c->rp_src_rowptr; a.r_src_cw = c->rp_src_cw;
         a.r_sta_col = a.r_src_col = nullptr; a.r_sta_w = a.r_src_w = nullptr;       // (the PCSR passes read the pair arrays only)
     }
-#if GENIE_TUNING
-    { static const char* e = getenv("GENIE_TRABL"); a.abl = e ? atoi(e) : 0; }
-#endif
     const int grid = train_grid(c);
     // 32-bit row offsets on scalar bases (ldo / sto) while every block of the kept rows lies below 4 GiB
     const bool o32 = !c->pcsr && (unsigned long long)SV_BLOCKS * (unsigned long long)c->P * 64ull < (1ull << 32);

@@ -124,7 +124,7 @@ __device__ __forceinline__ void stage1_dense(const DaArgs& a, const f32x4* lw, c
             wuv[1] = MFMA16(w2[1][r], o6[2 + b][r], wuv[1]);
         }
     }
-    if (valid && !ABL(a, 3)) {
+    if (valid) {
         *(f32x4*)(a.c + p * ROWC + 4 * q) = o6[4];
         *(f32x4*)(a.c + p * ROWC + 16 + 4 * q) = o6[5];
         *(f32x4*)(a.wu + p * ROWW + 4 * q) = wuv[0];
@@ -181,14 +181,12 @@ __global__ __launch_bounds__(256) void k_stage1(DaArgs a) {
         f32x4 n1a = {0.f, 0.f, 0.f, 0.f}, n1b = {0.f, 0.f, 0.f, 0.f};
         {
             const int eb = a.sta_rowptr[sc], ee = a.sta_rowptr[sc + 1];
-            if (!ABL(a, 0)) {
-                if (s11 <= 1.f)
-                    gather_recompute<false, true>(a.slice, a.mask, (long long)g * S, 1, q, a.sta_col, eb, ee, wi0, wi1, bi0,
-                                                  bi1, s11, n1a, n1b, AbsNbr{a.abs_sta, true, gq});
-                else
-                    gather_recompute<false, false>(a.slice, a.mask, (long long)g * S, 1, q, a.sta_col, eb, ee, wi0, wi1, bi0,
-                                                   bi1, s11, n1a, n1b, AbsNbr{a.abs_sta, true, gq});
-            }
+            if (s11 <= 1.f)
+                gather_recompute<false, true>(a.slice, a.mask, (long long)g * S, 1, q, a.sta_col, eb, ee, wi0, wi1, bi0, bi1,
+                                              s11, n1a, n1b, AbsNbr{a.abs_sta, true, gq});
+            else
+                gather_recompute<false, false>(a.slice, a.mask, (long long)g * S, 1, q, a.sta_col, eb, ee, wi0, wi1, bi0, bi1,
+                                               s11, n1a, n1b, AbsNbr{a.abs_sta, true, gq});
             const float inv = 1.f / (float)max(ee - eb, 1);
             n1a *= inv; n1b *= inv;
         }
@@ -197,14 +195,12 @@ __global__ __launch_bounds__(256) void k_stage1(DaArgs a) {
         {
             const int eb = __builtin_amdgcn_readfirstlane(a.src_rowptr[g]);
             const int ee = __builtin_amdgcn_readfirstlane(a.src_rowptr[g + 1]);
-            if (!ABL(a, 1)) {
-                if (s12 <= 1.f)
-                    gather_recompute<true, true>(a.slice, a.mask, (long long)sc, (long long)S, q, a.src_col, eb, ee, wi0, wi1,
-                                                 bi0, bi1, s12, n2a, n2b, AbsNbr{a.abs_src, false, lq});
-                else
-                    gather_recompute<true, false>(a.slice, a.mask, (long long)sc, (long long)S, q, a.src_col, eb, ee, wi0, wi1,
-                                                  bi0, bi1, s12, n2a, n2b, AbsNbr{a.abs_src, false, lq});
-            }
+            if (s12 <= 1.f)
+                gather_recompute<true, true>(a.slice, a.mask, (long long)sc, (long long)S, q, a.src_col, eb, ee, wi0, wi1, bi0,
+                                             bi1, s12, n2a, n2b, AbsNbr{a.abs_src, false, lq});
+            else
+                gather_recompute<true, false>(a.slice, a.mask, (long long)sc, (long long)S, q, a.src_col, eb, ee, wi0, wi1, bi0,
+                                              bi1, s12, n2a, n2b, AbsNbr{a.abs_src, false, lq});
             const float inv = 1.f / (float)max(ee - eb, 1);
             n2a *= inv; n2b *= inv;
         }
@@ -312,7 +308,7 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int XROW = 32;                 // bytes per split input row: two 16-B pieces
 constexpr int XPC = 16;                  // bytes per piece
 #ifndef GENIE_H2_THREADS
-#define GENIE_H2_THREADS 512             // waves x 64 of one k_stage1_h2 workgroup (tuning builds: 1024 = 16 waves sharing the weight image)
+#define GENIE_H2_THREADS 512             // waves x 64 of one k_stage1_h2 workgroup (a variant build with 1024: 16 waves sharing the weight image)
 #endif
 constexpr int H2_THREADS = GENIE_H2_THREADS;
 
@@ -652,8 +648,6 @@ __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
                 else if (PCSR) tp[u] = *(const u32x2*)((const char*)a.abs_tg + (tp_h + (unsigned)src_id[(u - KS - 1) % KPP] * 16u));
                 else tp[u] = *(const u32x2*)((const char*)a.abs_tg + (tp_h + (unsigned)row_bcast_dyn(srcv, u - KS) * 16u));
             }
-            if (ABL(a, 12) && u > 0) { buf[u] = buf[0]; return; }     // tuning: no neighbour-row loads
-            if (ABL(a, 13) && u >= 1 && u <= KS) { buf[u] = buf[0]; return; }     // tuning bit 13: the station-neighbour units cost nothing (upper bound of ANY caching of them)
             buf[u] = *(const u32x4*)(xs + off);
         };
         const u32x4 own0 = *(const u32x4*)(xs + (gbase0 + sbase0));         // x0 of the own row (lanes h = 1: Mask pads)
@@ -680,17 +674,11 @@ __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
                 z0 = MFMA32H(fa1, buf[u], z0); z1 = MFMA32H(fa1, buf[u + 1], z1);
                 z0 = MFMA32H(fp0, p0, z0); z1 = MFMA32H(fp0, p1, z1);
             } else {
-                const bool skip0 = ABL(a, 13) && u >= 1 && u <= KS, skip1 = ABL(a, 13) && u + 1 >= 1 && u + 1 <= KS;
-                z0 = biasA; z1 = biasA;
-                if (!skip0) z0 = MFMA32H(fa1, buf[u], biasA);
-                if (!skip1) z1 = MFMA32H(fa1, buf[u + 1], biasA);
-                if (!skip0) z0 = MFMA32H(fa0, buf[u], z0);
-                if (!skip1) z1 = MFMA32H(fa0, buf[u + 1], z1);
+                z0 = MFMA32H(fa1, buf[u], biasA);
+                z1 = MFMA32H(fa1, buf[u + 1], biasA);
             }
-            if (ABS) {
             z0 = MFMA32H(fa0, buf[u], z0);
             z1 = MFMA32H(fa0, buf[u + 1], z1);
-            }
 #pragma unroll
             for (int d = 0; d < 2; ++d) {
                 f32x16 z = d == 0 ? z0 : z1;
@@ -714,23 +702,7 @@ __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
                         al = present ? (uu <= KS ? alS : alP) : 0.f;
                         be = present ? (uu <= KS ? beS : beP) : 0.f;
                     }
-                    if (ABL(a, 13) && uu <= KS) {
-                        // tuning bit 14 (with 13): what a cache of the station neighbours' rows in LDS would cost instead: address, four
-                        // ds_read_b128 of a 136-B-pitch row picked by the neighbour's station id, sixteen adds (stand-in data: the weight image)
-                        if (uu == 1) {
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) sn[r] = 0.f;
-                        }
-                        if (ABL(a, 14)) {
-                            const unsigned x = ((unsigned)sta_id[uu - 1] * 136u + (unsigned)h * 64u) % 49152u;
-                            const char* lb = (const char*)lw + (x & ~15u);
-#pragma unroll
-                            for (int k4 = 0; k4 < 4; ++k4) {
-                                const f32x4 t = *(const f32x4*)(lb + 16 * k4);
-                                sn[4 * k4] += t.x; sn[4 * k4 + 1] += t.y; sn[4 * k4 + 2] += t.z; sn[4 * k4 + 3] += t.w;
-                            }
-                        }
-                    } else if (uu == 1 || uu == KS + 1) {
+                    if (uu == 1 || uu == KS + 1) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r) sn[r] = fmaf(be, __builtin_fabsf(z[r]), al * z[r]);
                     } else {
@@ -838,7 +810,7 @@ __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
                 mma3<3>(o3, lw, f0, lane, hp[kb]);
             }
         }
-        // node-planar rows (a.np, read by k_stage2_h2): chunk q = 2 b + h of station sc at [g][q][sc] x 16 B inside the node's block
+        // node-planar rows (a.np, read by k_stage2_h2u): chunk q = 2 b + h of station sc at [g][q][sc] x 16 B inside the node's block
         const long long npb = PCSR ? 0 : (long long)g * S;
         const long long npl = (long long)S * 4;
         if (valid) {
@@ -927,14 +899,14 @@ __global__ __launch_bounds__(256) void k_stage2(DaArgs a) {
         {
             const int eb = a.sta_rowptr[sc], ee = a.sta_rowptr[sc + 1];
             const float* base = a.wu + (long long)g * S * ROWW + 4 * q;
-            if (!ABL(a, 0)) gather_sum16<false>(base, ROWW, a.sta_col, eb, ee, n1);
+            gather_sum16<false>(base, ROWW, a.sta_col, eb, ee, n1);
             o[0] = fma4(n1, 1.f / (float)max(ee - eb, 1), o[0]);
         }
         {
             const int eb = __builtin_amdgcn_readfirstlane(a.src_rowptr[g]);
             const int ee = __builtin_amdgcn_readfirstlane(a.src_rowptr[g + 1]);
             const float* base = a.wv + (long long)sc * ROWW + 4 * q;
-            if (!ABL(a, 1)) gather_sum16<true>(base, (long long)S * ROWW, a.src_col, eb, ee, n2);
+            gather_sum16<true>(base, (long long)S * ROWW, a.src_col, eb, ee, n2);
             o[1] = fma4(n2, 1.f / (float)max(ee - eb, 1), o[1]);
         }
         if (a.save != nullptr && valid) {
@@ -1251,15 +1223,14 @@ __global__ __launch_bounds__(256, GENIE_S2_WAVES) void k_stage2_ord(DaArgs a) {
     auto issue0 = [&](Stream& st, int idv, int tb) {
         const int g = __builtin_amdgcn_readlane(idv, 0);
         const int s = tb * 16 + jl, sc = s < S ? s : S - 1;
-        long long p = (long long)g * S + sc;
-        if (ABL(a, 9)) p &= 4095;          // tuning: streamed rows from a cache-resident region
+        const long long p = (long long)g * S + sc;
         st.o[0] = *(const f32x4*)(a.c + p * ROWC + 4 * ql);
         st.o[1] = *(const f32x4*)(a.c + p * ROWC + 16 + 4 * ql);
         st.mq = NB ? 0.f : a.mm_int[p];
         st.eq = (!NB && ql < 3) ? a.ea_int[p * 3 + ql] : 0.f;
-        const char* wug = wub + (ABL(a, 11) ? (size_t)0 : (size_t)g * gpitch);     // tuning bit 11: gathers hit one resident block
+        const char* wug = wub + (size_t)g * gpitch;
 #pragma unroll
-        for (int k = 0; k < KS; ++k) rows.ru[k] = ABL(a, 0) ? st.o[0] : *(const f32x4*)(wug + ((unsigned)sta[k] * 64u + q16));
+        for (int k = 0; k < KS; ++k) rows.ru[k] = *(const f32x4*)(wug + ((unsigned)sta[k] * 64u + q16));
     };
     auto issue_v = [&](int idv, int tb, int k0, int k1) {
         const int s = tb * 16 + jl, sc = s < S ? s : S - 1;
@@ -1270,11 +1241,11 @@ __global__ __launch_bounds__(256, GENIE_S2_WAVES) void k_stage2_ord(DaArgs a) {
                 // the row base of a source neighbour is wave-uniform: kept opaque in an SGPR pair, so that the load is
                 // `global_load v, voffset, s[base]` (left to itself hipcc hoists wvb + so into a VGPR pair and adds the
                 // scalar part with a 64-bit vector multiply-add per neighbour: 3 vector instructions each)
-                unsigned long long wvk = (unsigned long long)wvb + (ABL(a, 11) ? (size_t)k : (size_t)__builtin_amdgcn_readlane(idv, 1 + k)) * gpitch;
+                unsigned long long wvk = (unsigned long long)wvb + (size_t)__builtin_amdgcn_readlane(idv, 1 + k) * gpitch;
                 asm volatile("" : "+s"(wvk));
                 typedef const __attribute__((address_space(1))) char* gbytes;
                 typedef const __attribute__((address_space(1))) f32x4* grow;
-                rows.rv[k] = ABL(a, 1) ? rows.ru[0] : *(grow)((gbytes)wvk + so);
+                rows.rv[k] = *(grow)((gbytes)wvk + so);
             }
     };
     constexpr int KH = (KP + 1) / 2;
@@ -1344,11 +1315,9 @@ __global__ __launch_bounds__(256, GENIE_S2_WAVES) void k_stage2_ord(DaArgs a) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             if (NB) break;
-            if (!ABL(a, 6)) {      // (tuning bit 6: no fc1 MFMAs)
-                bp[t] = mma_block(bp[t], lw[G2_BP(t, 0) * 64 + lane], o[0]);
-                bp[t] = mma_block(bp[t], lw[G2_BP(t, 1) * 64 + lane], o[1]);
-                bp[t] = MFMA16(lw[G2_BP(t, 2) * 64 + lane].x, eq, bp[t]);
-            } else bp[t] += o[0] + o[1] + eq;
+            bp[t] = mma_block(bp[t], lw[G2_BP(t, 0) * 64 + lane], o[0]);
+            bp[t] = mma_block(bp[t], lw[G2_BP(t, 1) * 64 + lane], o[1]);
+            bp[t] = MFMA16(lw[G2_BP(t, 2) * 64 + lane].x, eq, bp[t]);
             if (SAVE && tb_c * 16 + j < S)
                 *(f32x4*)(a.save + ((size_t)(SV_ZB + t) * a.Pn + (size_t)g_c * S + a.sta_user[tb_c * 16 + j]) * 16 + 4 * q) = bp[t];
             bp[t] = prelu4u(bp[t], ab1);
@@ -1374,222 +1343,7 @@ __global__ __launch_bounds__(256, GENIE_S2_WAVES) void k_stage2_ord(DaArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// STAGE 2 on the 16-bit matrix pipe (k_stage2_h2, round 4): the production stage 2 of the reference's kNN graphs.
-//
-// What k_stage2_ord spent its time on (profiles/r03_zz_pmc_stage_kernels.txt, r03_y_s2_ablations.txt): 18 fp32 MFMAs of 32 cycles
-// per 16 nodes that do not overlap with vector work, a round trip through LDS per tile (row layout -> MFMA layout) in the middle
-// of the dependency chain, 64-bit scalar address arithmetic per gathered row (as many scalar as vector instructions), and 47 % of
-// all wave cycles waiting. Here
-//  * Bipartite fc1 (33 -> 30) runs as v_mfma_f32_16x16x32_f16 with fp32 operands as two fp16 pieces (the f16x2 form of stage 1:
-//    W0 x1 + W1' (x0 / 16) + W0 x0): D[channel, node] for 16 channels x 16 nodes, K = 32 = [o1 chunk | o2 chunk] x 4 lane groups:
-//    ONE K-step for all of x_latent, so a tile takes 2 x 3 MFMAs of 16 cycles + 2 for edge_attr instead of 18 x 32 cycles;
-//  * lane (m = lane & 15, kg = lane >> 4) holds channels 4 kg .. 4 kg + 3 of BOTH halves of node m's x_latent, which is the
-//    MFMA's B operand as it stands: no LDS transpose. For that the rows stage 1 writes are NODE-PLANAR: inside the block of a
-//    source node, chunk q (16 B) of all S stations is contiguous (c: [g][8][S] x 16 B, wv: [g][4][S] x 16 B; DaArgs.np), so the 16
-//    lanes of a lane group read 256 contiguous bytes and the block of a source node stays contiguous (the halo exchange of the
-//    sharded path moves whole blocks, genie_amd/dist.py);
-//  * the station-neighbour rows (wu, row layout [p][16]) are still gathered four lanes to a 64-B row (the texture path's fast
-//    pattern), summed there, and the SUM crosses into the operand layout with four ds_bpermute_b32;
-//  * the static edge_attr arrives as a ready-made B fragment (k_ea_frag, written once per registered edge_attr): its K-step is one
-//    MFMA per channel block;
-//  * row bases are 32-bit scalar products on top of a 64-bit pointer (BIG: 64-bit products, config 4 on one GPU).
-// Same arithmetic up to x_latent as k_stage2_ord (bitwise equal x_latent); the Bipartite message is fp32-class like stage 1
-// (products exact in the fp32 accumulator, operands within one fp32 ulp), tests compare it with the oracle and the fp32 kernels.
-// ------------------------------------------------------------------------------------------------
-#define MFMA16H(a, b, c) \
-    __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, (a)), __builtin_bit_cast(f16x8, (b)), (c), 0, 0, 0)
-
-// edge_attr [P, 3] (caller's station order) -> B fragments of the edge_attr K-step, node-planar [g][2][S] x 16 B in station
-// processing order: lane group 0 = {e0, e1, e2, 0 (first pieces) | e0, e1, e2, 0 (second pieces)}, group 1 = {e / 16 (3), 0 | 0}
-__global__ void k_ea_frag(const float* __restrict__ ea, long long rows, int S, const int32_t* __restrict__ sta_user,
-                          unsigned* __restrict__ out) {
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= rows) return;
-    const long long g = p / S;
-    const int s = (int)(p - g * S);
-    const long long pu = g * S + (sta_user != nullptr ? sta_user[s] : s);
-    const float e0 = ea[pu * 3], e1 = ea[pu * 3 + 1], e2 = ea[pu * 3 + 2];
-    const unsigned a0 = cvt_pk_f16(e0, e1), b0 = cvt_pk_f16(e2, 0.f);
-    const unsigned a1 = cvt_pk_f16(sub_f16_lo(e0, a0), sub_f16_hi(e1, a0)), b1 = cvt_pk_f16(sub_f16_lo(e2, b0), 0.f);
-    *(u32x4*)(out + ((g * 2) * S + s) * 4) = u32x4{a0, b0, a1, b1};
-    *(u32x4*)(out + ((g * 2 + 1) * S + s) * 4) = u32x4{pk_mul_f16(a0, H2_SIXTEENTH), pk_mul_f16(b0, H2_SIXTEENTH), 0u, 0u};
-}
-
-template <bool BIG>
-__device__ __forceinline__ unsigned long long s2h_base(const void* b, int id, unsigned pitch) {
-    const unsigned long long off = BIG ? (unsigned long long)(unsigned)id * (unsigned long long)pitch
-                                       : (unsigned long long)((unsigned)id * pitch);
-    unsigned long long r = (unsigned long long)b + off;
-    asm volatile("" : "+s"(r));      // stays an SGPR pair: the load is `global_load v, voffset, s[base]`
-    return r;
-}
-
-template <bool XL, bool BIG>
-__global__ __launch_bounds__(256, GENIE_S2H_WAVES) void k_stage2_h2(DaArgs a) {
-    constexpr int KS = 8, KP = 15;
-    constexpr int NF4 = S2H_IMG_FLOATS / 4;
-    __shared__ f32x4 lw[NF4];
-    for (int i = threadIdx.x; i < NF4; i += blockDim.x) lw[i] = ((const f32x4*)a.packed)[i];
-    __syncthreads();
-    const float* lbias = (const float*)(lw + S2H_FRAGS * 64);
-    const float a2 = a.slope2 != nullptr ? *a.slope2 : lbias[32], ab1 = lbias[33];
-    int lane = threadIdx.x & 63;
-    const int m = lane & 15, kg = lane >> 4;      // operand layout: node m of the tile, K-slot group kg
-    const int jl = lane >> 2, ql = lane & 3;      // row layout of the station-neighbour gathers: node jl, 16-B chunk ql
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int S = a.S;
-    ItemIter w(a.G, a.T, a.seg, a.nxcd, wave, a.gi0);
-    if (a.wgmap) {     // blocks of 4 adjacent source nodes per workgroup, one node per wave (see k_stage2_ord)
-        const int nx = (a.nxcd > 1 && gridDim.x >= (unsigned)a.nxcd && (gridDim.x % a.nxcd) == 0) ? a.nxcd : 1;
-        const int lb = blockIdx.x / nx, nbx = gridDim.x / nx, n = w.gend - w.gbeg, n_blk = (n + 3) / 4;
-        int n_my = lb < n_blk ? (n_blk - lb + nbx - 1) / nbx : 0;
-        if (n_my > 0 && 4 * (lb + (n_my - 1) * nbx) + wave >= n) --n_my;
-        w.it = 0; w.stride = 1; w.nitems = (long long)n_my * a.T;
-        w.lead_ = lb; w.chunk_ = nbx;
-    }
-    if (w.it >= w.nitems) return;
-    const unsigned m_T = ItemIter::recip((unsigned)a.T);
-    auto item_of = [&](long long it, int& gi, int& tb) {      // every XCD's chunk is swept backwards (the rows stage 1 wrote last first)
-        const long long itr = w.nitems - 1 - it;
-        if (a.wgmap) {
-            unsigned rem;
-            const unsigned kb = a.T <= 1 ? (rem = 0u, (unsigned)itr) : ItemIter::fdiv((unsigned)itr, (unsigned)a.T, m_T, rem);
-            tb = (int)rem;
-            gi = w.gbeg + 4 * (w.lead_ + (int)kb * w.chunk_) + wave;
-        } else {
-            w.decode(itr, gi, tb);
-        }
-        gi = __builtin_amdgcn_readfirstlane(gi);
-        tb = __builtin_amdgcn_readfirstlane(tb);
-    };
-    typedef const __attribute__((address_space(1))) char* gbytes;
-    typedef const __attribute__((address_space(1))) f32x4* grow;
-    typedef const __attribute__((address_space(1))) u32x4* gfrag;
-    typedef const __attribute__((address_space(1))) float* gflt;
-    const unsigned plane = (unsigned)S * 16u;          // bytes of one chunk plane inside a source node's block
-    const unsigned pc = (unsigned)S * 128u, pw = (unsigned)S * 64u, pe = (unsigned)S * 32u, pm = (unsigned)S * 4u;
-    const unsigned kgp = (unsigned)kg * plane, kge = (unsigned)min(kg, 1) * plane;
-    const unsigned q16 = 16u * (unsigned)ql;
-    const int bperm = (4 * m + kg) * 4;                // this lane's operand = the row-layout lane of (node m, chunk kg)
-
-    struct Tile { f32x4 ru[KS], rv[KP], c1, c2; u32x4 ea; float mq; } R;
-    int sta[KS];
-    auto load_ids = [&](int gi, int tb, int& idv) {
-        idv = a.src_tab[gi * 16 + m];
-        const int s = tb * 16 + jl;
-        load_sta_ids<KS>(a.sta_col, s < S ? s : S - 1, sta);
-    };
-    auto issue = [&](int idv, int tb) {
-        const int g = __builtin_amdgcn_readlane(idv, 0);
-        const int s = tb * 16 + m, sc = s < S ? s : S - 1;
-        const unsigned so = (unsigned)sc * 16u;
-        const unsigned lo = kgp + so;
-        const int gs = ABL(a, 9) ? (g & 7) : g;        // tuning bit 9: streamed rows (c, mask, edge_attr) from a cache-resident region
-        const unsigned long long cb = s2h_base<BIG>(a.c, gs, pc);
-        R.c1 = *(grow)((gbytes)cb + lo);
-        R.c2 = *(grow)((gbytes)cb + (lo + 4u * plane));
-        const unsigned long long mb = s2h_base<BIG>(a.mm_int, gs, pm);
-        R.mq = *(gflt)((gbytes)mb + (unsigned)sc * 4u);
-        if (s >= S) R.mq = 0.f;
-        const unsigned long long eb = s2h_base<BIG>(a.ea_frag, gs, pe);
-        R.ea = *(gfrag)((gbytes)eb + (kge + so));
-        const unsigned long long ub = s2h_base<BIG>(a.wu, ABL(a, 11) ? (g & 7) : g, pw);
-#pragma unroll
-        for (int k = 0; k < KS; ++k) R.ru[k] = ABL(a, 0) ? R.c1 : *(grow)((gbytes)ub + ((unsigned)sta[k] * 64u + q16));
-#pragma unroll
-        for (int k = 0; k < KP; ++k) {
-            // tuning bit 11: every gather from a cache-resident block (same instruction stream); bit 12: the 15 source rows of a tile
-            // are ONE row (the L1 misses of the source gathers collapse to those of one row); bit 1: no source gathers
-            const int idk = ABL(a, 11) ? k : __builtin_amdgcn_readlane(idv, ABL(a, 12) ? 1 : 1 + k);
-            const unsigned long long vb = s2h_base<BIG>(a.wv, idk, pw);
-            R.rv[k] = ABL(a, 1) ? R.c2 : *(grow)((gbytes)vb + lo);
-        }
-    };
-
-    long long it = w.it;
-    int gi_c, tb_c, gi_n, tb_n, idv_c, idv_n;
-    item_of(it, gi_c, tb_c);
-    load_ids(gi_c, tb_c, idv_c);
-    issue(idv_c, tb_c);
-    {
-        const long long itn = it + w.stride < w.nitems ? it + w.stride : it;
-        item_of(itn, gi_n, tb_n);
-        load_ids(gi_n, tb_n, idv_n);
-    }
-    for (;;) {
-        asm volatile("" : "+v"(lane));
-        const int g_c = __builtin_amdgcn_readlane(idv_c, 0);
-        const bool has_next = it + w.stride < w.nitems;
-        const long long it2 = it + 2 * w.stride < w.nitems ? it + 2 * w.stride : (has_next ? it + w.stride : it);
-        int gi_2, tb_2, idv_2;
-        item_of(it2, gi_2, tb_2);
-        // (1) neighbour means of the projected operands in edge order (as k_stage2_ord), PReLU2 -> x_latent
-        f32x4 n1 = {0.f, 0.f, 0.f, 0.f}, n2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int k = 0; k < KS; ++k) n1 += R.ru[k];
-#pragma unroll
-        for (int k = 0; k < KP; ++k) n2 += R.rv[k];
-        f32x4 n1t;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {     // (through a scalar temporary: __builtin_bit_cast applied to a vector ELEMENT reads element 0, hipcc 7.0)
-            const float v = n1[r];
-            n1t[r] = __int_as_float(__builtin_amdgcn_ds_bpermute(bperm, __float_as_int(v)));
-        }
-        f32x4 o1 = fma4(n1t, 1.f / (float)KS, R.c1), o2 = fma4(n2, 1.f / (float)KP, R.c2);
-        const float mq = R.mq;
-        const u32x4 eab = R.ea;
-        o1 = prelu4u(o1, a2);
-        o2 = prelu4u(o2, a2);
-        asm volatile("" : "+v"(o1), "+v"(o2), "+v"(idv_n));
-        // (2) every row of the next tile (the item after the last repeats the last one: its rows are never consumed)
-        issue(idv_n, tb_n);
-        if (XL && tb_c * 16 + m < S) {
-            const int su = a.sta_user[tb_c * 16 + m];
-            float* xl = a.x_latent + ((long long)g_c * S + su) * 30;
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-                if (4 * kg + r < 15) { xl[4 * kg + r] = o1[r]; xl[15 + 4 * kg + r] = o2[r]; }
-        }
-        // (3) B operand: K slots (kg, e) = o1 channels 4 kg + e (e < 4), o2 channels 4 kg + e - 4; pieces {x0, x1, x0 / 16}
-        u32x4 p0, p1, p2;
-        p0[0] = cvt_pk_f16(o1[0], o1[1]); p0[1] = cvt_pk_f16(o1[2], o1[3]);
-        p0[2] = cvt_pk_f16(o2[0], o2[1]); p0[3] = cvt_pk_f16(o2[2], o2[3]);
-        p1[0] = cvt_pk_f16(sub_f16_lo(o1[0], p0[0]), sub_f16_hi(o1[1], p0[0]));
-        p1[1] = cvt_pk_f16(sub_f16_lo(o1[2], p0[1]), sub_f16_hi(o1[3], p0[1]));
-        p1[2] = cvt_pk_f16(sub_f16_lo(o2[0], p0[2]), sub_f16_hi(o2[1], p0[2]));
-        p1[3] = cvt_pk_f16(sub_f16_lo(o2[2], p0[3]), sub_f16_hi(o2[3], p0[3]));
-#pragma unroll
-        for (int d = 0; d < 4; ++d) p2[d] = pk_mul_f16(p0[d], H2_SIXTEENTH);
-        // (4) Bipartite fc1: D[channel 16 t + 4 kg + r, node m], smallest products first
-        f32x4 bp[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            bp[t] = *(const f32x4*)(lbias + 16 * t + 4 * kg);
-            const f32x4 w0 = lw[(S2H_FW + 2 * t) * 64 + lane], w1 = lw[(S2H_FW + 2 * t + 1) * 64 + lane];
-            const f32x4 we = lw[(S2H_FE + t) * 64 + lane];
-            bp[t] = MFMA16H(w0, p1, bp[t]);
-            bp[t] = MFMA16H(w1, p2, bp[t]);
-            bp[t] = MFMA16H(we, eab, bp[t]);
-            bp[t] = MFMA16H(w0, p0, bp[t]);
-        }
-        // (5) ids of the tile after next
-        load_ids(gi_2, tb_2, idv_2);
-        // (6) PReLU, mask gate, station sum of this tile (DPP row reduction in the butterfly's order), one partial row per tile
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            f32x4 v = prelu4u(bp[t], ab1) * mq;
-            v.x = row_sum16_tree(v.x); v.y = row_sum16_tree(v.y); v.z = row_sum16_tree(v.z); v.w = row_sum16_tree(v.w);
-            if (m == 0) *(f32x4*)(a.part + ((long long)g_c * a.T + tb_c) * 32 + 16 * t + 4 * kg) = v;
-        }
-        if (!has_next) break;
-        it += w.stride;
-        idv_c = idv_n; tb_c = tb_n;
-        idv_n = idv_2; tb_n = tb_2;
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// fp16 range guard of the f16x2 kernels (k_stage1_h2, k_stage2_h2). They split every hidden state into fp16 pieces, so a value
+// fp16 range guard of the f16x2 kernels (k_stage1_h2, k_stage2_h2u). They split every hidden state into fp16 pieces, so a value
 // above 65 504 would turn into inf where the reference's fp32 arithmetic is still fine. This kernel computes, from the weights
 // alone, a RIGOROUS bound of every such value (interval arithmetic per channel: |W x + b| <= sum_j |W_ij| X_j + |b_i|,
 // |PReLU_a(z)| <= max(1, |a|) |z|, |mean| <= max) for inputs Slice, Mask in [-1, 1] (process_utils.py:262-275: exp(-r^2 / 2 s^2) in
@@ -1702,7 +1456,7 @@ __global__ __launch_bounds__(256) void k_h2_range(RangeArgs a) {
         amax = fmaxf(amax, g1(s) * z);
     }
     __syncthreads();
-    if (t < 30) {       // x_latent = PReLU2(c + mean of the projected u / v), the B operand of k_stage2_h2
+    if (t < 30) {       // x_latent = PReLU2(c + mean of the projected u / v), the B operand of k_stage2_h2u
         const int i = t % 15, hf = t / 15;
         const float* w = W(hf ? RG_L2T22_W : RG_L2T12_W) + i * 94;
         const float* uv = hf ? V : U;
@@ -1722,19 +1476,66 @@ __global__ __launch_bounds__(256) void k_h2_range(RangeArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// k_stage2_h2u: k_stage2_h2 with the source-neighbour rows of BLOCKS of adjacent source nodes staged once in LDS (round 4).
+// STAGE 2 on the 16-bit matrix pipe (k_stage2_h2u, round 4): the production stage 2 of the reference's kNN graphs.
 //
-// What bounds k_stage2_h2 is the vector-memory path: 27 KB per tile through the texture addresser and
-// 170 L1 misses per tile, 120 of them the 15 source-neighbour rows, which are never L1 hits: the ~15 users of a row (g', tile) are
-// the tiles (g, same station tile) of the source nodes g that list g', and they run on other CUs. Adjacent source nodes of the
-// space-filling-curve order share about half of their neighbours, so a workgroup takes a BLOCK of up to 8 consecutive source nodes
-// for ONE station tile: the union of their neighbour rows (<= S2U_UCAP, ~45 of 120) is copied into LDS once (each wave fetches a
-// quarter of the rows into registers while the previous block-tile computes), and every node of the block sums its 15 rows from
-// LDS (lane-contiguous 16-B reads, no bank conflicts). Texture traffic of the source rows 15 -> ~5.6 KB per tile, L1 misses 120 -> ~45.
-// Blocks and their union lists are static (genie_ctx_create: build_union_blocks); two workgroup barriers per block-tile (8 tiles).
-// Everything per node (streamed rows, station-neighbour gathers, f16x2 fc1, station sum) is k_stage2_h2's code: same results bit for
-// bit (the row sums keep the edge order).
+// What k_stage2_ord spent its time on (profiles/r03_zz_pmc_stage_kernels.txt, r03_y_s2_ablations.txt): 18 fp32 MFMAs of 32 cycles
+// per 16 nodes that do not overlap with vector work, a round trip through LDS per tile (row layout -> MFMA layout) in the middle
+// of the dependency chain, 64-bit scalar address arithmetic per gathered row (as many scalar as vector instructions), and 47 % of
+// all wave cycles waiting. Here
+//  * Bipartite fc1 (33 -> 30) runs as v_mfma_f32_16x16x32_f16 with fp32 operands as two fp16 pieces (the f16x2 form of stage 1:
+//    W0 x1 + W1' (x0 / 16) + W0 x0): D[channel, node] for 16 channels x 16 nodes, K = 32 = [o1 chunk | o2 chunk] x 4 lane groups:
+//    ONE K-step for all of x_latent, so a tile takes 2 x 3 MFMAs of 16 cycles + 2 for edge_attr instead of 18 x 32 cycles;
+//  * lane (m = lane & 15, kg = lane >> 4) holds channels 4 kg .. 4 kg + 3 of BOTH halves of node m's x_latent, which is the
+//    MFMA's B operand as it stands: no LDS transpose. For that the rows stage 1 writes are NODE-PLANAR: inside the block of a
+//    source node, chunk q (16 B) of all S stations is contiguous (c: [g][8][S] x 16 B, wv: [g][4][S] x 16 B; DaArgs.np), so the 16
+//    lanes of a lane group read 256 contiguous bytes and the block of a source node stays contiguous (the halo exchange of the
+//    sharded path moves whole blocks, genie_amd/dist.py);
+//  * the station-neighbour rows (wu, row layout [p][16]) are gathered four lanes to a 64-B row (the texture path's fast pattern,
+//    DESIGN.md section 5), summed there, and the SUM crosses into the operand layout with four ds_bpermute_b32;
+//  * the source-neighbour rows (wv) are staged in LDS per BLOCK of adjacent source nodes. Gathered per node, they were 120 of the
+//    170 L1 misses of a tile (27 KB per tile through the texture addresser) and never L1 hits: the
+//    ~15 users of a row (g', tile) are the tiles (g, same station tile) of the source nodes g that list g', and they run on other
+//    CUs. Adjacent source nodes of the space-filling-curve order share about half of their neighbours, so a workgroup takes a
+//    block of up to 8 consecutive source nodes for ONE station tile: the union of their neighbour rows (<= S2U_UCAP, ~45 of 120)
+//    is copied into LDS once (each wave fetches a quarter of the rows into registers while the previous block-tile computes), and
+//    every node of the block sums its 15 rows from LDS (lane-contiguous 16-B reads, no bank conflicts). Texture traffic of the
+//    source rows 15 -> ~5.6 KB per tile, L1 misses 120 -> ~45. Blocks and their union lists are static (genie_ctx_create:
+//    build_union_blocks); two workgroup barriers per block-tile (8 tiles);
+//  * the static edge_attr arrives as a ready-made B fragment (k_ea_frag, written once per registered edge_attr): its K-step is one
+//    MFMA per channel block;
+//  * row bases are 32-bit scalar products on top of a 64-bit pointer (BIG: 64-bit products, config 4 on one GPU).
+// Same arithmetic up to x_latent as k_stage2_ord: the neighbour sums keep the edge order, so x_latent is bitwise equal. The
+// Bipartite message is fp32-class like stage 1 (products exact in the fp32 accumulator, operands within one fp32 ulp); tests
+// compare it with the oracle and the fp32 kernels.
 // ------------------------------------------------------------------------------------------------
+#define MFMA16H(a, b, c) \
+    __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, (a)), __builtin_bit_cast(f16x8, (b)), (c), 0, 0, 0)
+
+// edge_attr [P, 3] (caller's station order) -> B fragments of the edge_attr K-step, node-planar [g][2][S] x 16 B in station
+// processing order: lane group 0 = {e0, e1, e2, 0 (first pieces) | e0, e1, e2, 0 (second pieces)}, group 1 = {e / 16 (3), 0 | 0}
+__global__ void k_ea_frag(const float* __restrict__ ea, long long rows, int S, const int32_t* __restrict__ sta_user,
+                          unsigned* __restrict__ out) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= rows) return;
+    const long long g = p / S;
+    const int s = (int)(p - g * S);
+    const long long pu = g * S + (sta_user != nullptr ? sta_user[s] : s);
+    const float e0 = ea[pu * 3], e1 = ea[pu * 3 + 1], e2 = ea[pu * 3 + 2];
+    const unsigned a0 = cvt_pk_f16(e0, e1), b0 = cvt_pk_f16(e2, 0.f);
+    const unsigned a1 = cvt_pk_f16(sub_f16_lo(e0, a0), sub_f16_hi(e1, a0)), b1 = cvt_pk_f16(sub_f16_lo(e2, b0), 0.f);
+    *(u32x4*)(out + ((g * 2) * S + s) * 4) = u32x4{a0, b0, a1, b1};
+    *(u32x4*)(out + ((g * 2 + 1) * S + s) * 4) = u32x4{pk_mul_f16(a0, H2_SIXTEENTH), pk_mul_f16(b0, H2_SIXTEENTH), 0u, 0u};
+}
+
+template <bool BIG>
+__device__ __forceinline__ unsigned long long s2h_base(const void* b, int id, unsigned pitch) {
+    const unsigned long long off = BIG ? (unsigned long long)(unsigned)id * (unsigned long long)pitch
+                                       : (unsigned long long)((unsigned)id * pitch);
+    unsigned long long r = (unsigned long long)b + off;
+    asm volatile("" : "+s"(r));      // stays an SGPR pair: the load is `global_load v, voffset, s[base]`
+    return r;
+}
+
 constexpr int S2U_WPB = 4;           // waves per workgroup (round 5: 8 waves = blocks of 16 source nodes on the same 64-row union, twice the resident
                                      // waves: 0.264 against 0.198 ms -- the 64-row cap cuts such blocks at 11-13 nodes and leaves a quarter of the slots empty)
 constexpr int S2U_NB = 2 * S2U_WPB;  // source nodes per block (two per wave)
@@ -1814,7 +1615,7 @@ __global__ __launch_bounds__(S2U_WPB * 64, GENIE_S2U_BPC) void k_stage2_h2u(DaAr
             if (u < U) *(f32x4*)(lrows + (unsigned)u * 1024u + (unsigned)lane * 16u) = stg[i];
         }
     };
-    // ---- per-node rows: streamed rows + station-neighbour gathers (one node-tile ahead), as in k_stage2_h2
+    // ---- per-node rows: streamed rows + station-neighbour gathers (one node-tile ahead)
     struct Node { f32x4 ru[KS], c1, c2; u32x4 ea; float mq; } R;
     int sta[KS];
     auto load_sta = [&](int tb) {

@@ -39,7 +39,6 @@ struct TrArgs {
                                  // association phase's AV_T, AV_UV, AV_UV + 2)
     const float* pg;             // association phase (k_train_b1<true>, k_as_*): [G][AS_PG] per-source-node terms, pg[31] = mask1[g]
     const float* x_latent;       // association phase: [P, 30] DataAggregation output (an input of init_trns there)
-    int abl;                     // GENIE_TUNING builds: ablation bits of k_train_b1 (tools/train_abl.sh)
     int store_dz0;               // k_train_b0: keep dz0 in the GR_DH0 blocks (read by the static-term gradients of use_absolute_pos)
     float* zsum;                 // k_as_b0: [G * T][32] per-tile station sums of d z1 (-> d y_latent, fc1's y_latent columns)
 };
@@ -335,15 +334,6 @@ __global__ __launch_bounds__(WPB * 64, 1) void k_train_b2(TrArgs a) {
 // vec: b(l2_t1_2), b(l2_t2_2), b(l2_t1_1) x2, b(l2_t2_1) x2 = 6; scal: a1, a21, a22
 // AS: the same pass for DataAggregationAssociationPhase (module.py:397-401; 95-wide l2_t?_2 with mask width 5): the column of mask1
 // (one value per source node) gets its gradient as two extra vectors.
-#if GENIE_TUNING
-#define TPH_DECL long long tph[6] = {0, 0, 0, 0, 0, 0}; long long tph_t0 = 0
-#define TPH_START() do { if (a.abl & 16) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); tph_t0 = __builtin_amdgcn_s_memtime(); } } while (0)
-#define TPH_MARK(k) do { if (a.abl & 16) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const long long t_ = __builtin_amdgcn_s_memtime(); tph[k] += t_ - tph_t0; tph_t0 = t_; } } while (0)
-#else
-#define TPH_DECL
-#define TPH_START()
-#define TPH_MARK(k)
-#endif
 template <bool AS, bool O32 = false>      // O32: rows addressed by 32-bit offsets on scalar bases (ldo / sto; P < 4.79 M)
 __global__ __launch_bounds__(256, 1) void k_train_b1(TrArgs a) {
     constexpr int NF4 = (GT1_GROUPS * 256 + 16) / 4;
@@ -368,7 +358,6 @@ __global__ __launch_bounds__(256, 1) void k_train_b1(TrArgs a) {
     for (int k = 0; k < NV; ++k) vec[k] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int SVT = a.sv_t, SVU = a.sv_up, SVV = a.sv_vp;
     ItemIter w(a.G, a.T, a.seg, a.nxcd, wave);
-    TPH_DECL;
     constexpr int EBS = 8, EBG = 16;            // prefetched out-edges per station (per lane) / per source node (uniform)
     struct Tile { int g, scn; bool valid; };
     struct Rp { int s0, s1, g0, g1; };
@@ -466,7 +455,6 @@ __global__ __launch_bounds__(256, 1) void k_train_b1(TrArgs a) {
         rp_n = rp_of(nxt);
     }
     for (; w.it < w.nitems; w.it += w.stride) {
-        TPH_START();
         asm volatile("" : "+v"(lane));
         const int g = cur.g, scn = cur.scn;
         const bool valid = cur.valid;
@@ -482,12 +470,10 @@ __global__ __launch_bounds__(256, 1) void k_train_b1(TrArgs a) {
         own_load(nxt, own_n);
         const f32x4 mb = own.mb;
         const f32x4 do1 = own.do1 * vm, do2 = own.do2 * vm;
-        TPH_MARK(0);
         if (AS) {
             const float m1 = a.pg[(long long)g * AS_PG + 31];
             vec[6] += do1 * m1; vec[7] += do2 * m1;
         }
-        TPH_MARK(1);
         f32x4 t[4], h1[4], up[2], vp[2], u[2], v[2];
 #pragma unroll
         for (int k = 0; k < 4; ++k) { t[k] = own.t[k]; h1[k] = prelu4u(t[k], a1); }
@@ -507,7 +493,6 @@ __global__ __launch_bounds__(256, 1) void k_train_b1(TrArgs a) {
             du[b] = gu * dprelu4(up[b], a21);
             dv[b] = gv * dprelu4(vp[b], a22);
         }
-        TPH_MARK(2);
         // dh1 and dt
         f32x4 dt[4];
 #pragma unroll
@@ -521,9 +506,6 @@ __global__ __launch_bounds__(256, 1) void k_train_b1(TrArgs a) {
             d = mma_block(d, lw[GT_H(hb, 5) * 64 + lane], do2);
             scal[0] += negsum4(d, t[hb]);
             dt[hb] = d * dprelu4(t[hb], a1);
-#if GENIE_TUNING
-            if (a.abl & 8) { if (dt[hb].x == 1.2345f) stb(a.gr, GR_DT + hb, P, p, q, dt[hb]); continue; }
-#endif
             if (valid) { if (O32) sto(grb, (unsigned)(GR_DT + hb) * P64 + (unsigned)p * 64u + q16, dt[hb]); else stb(a.gr, GR_DT + hb, P, p, q, dt[hb]); }
         }
 #pragma unroll
@@ -535,7 +517,6 @@ __global__ __launch_bounds__(256, 1) void k_train_b1(TrArgs a) {
         }
         vec[0] += do1; vec[1] += do2;
         vec[2] += du[0]; vec[3] += du[1]; vec[4] += dv[0]; vec[5] += dv[1];
-        TPH_MARK(3);
         // the next tile's gathered rows: in flight under the weight gradients
         f32x4 rs[EBS], rg[EBG];
         rows_issue(nxt, xs_n, xg_n, rs, rg);
@@ -566,15 +547,9 @@ __global__ __launch_bounds__(256, 1) void k_train_b1(TrArgs a) {
                 acc[22 + b * 4 + k] = outer16(acc[22 + b * 4 + k], dvt, h1t[k]);
             }
         }
-        TPH_MARK(4);
         rows_sum(nxt, xs_n, xg_n, rs, rg, tm1, tm2);
         cur = nxt; nxt = nn; rp_n = rp_nn; own = own_n;
     }
-#if GENIE_TUNING
-    if ((a.abl & 16) && (threadIdx.x & 63) == 0 && wave == 1 && (blockIdx.x == 3 || blockIdx.x == 200))
-        printf("b1 blk %d: own loads %lld, gathers %lld, save loads + du/dv %lld, dh1/dt/dh0 + stores %lld, weight grads %lld\n", blockIdx.x,
-               tph[0], tph[1], tph[2], tph[3], tph[4]);
-#endif
     write_partials(a, blockIdx.x * 4 + wave, acc, 30, vec, NV, scal, 3, threadIdx.x & 63, j, q);
 }
 

@@ -115,7 +115,7 @@ int genie_set_stage2_workmap(genie_ctx* ctx, int blocks_of_four);
  * The fp32 chains are where almost all of the distance between (y, x) and the reference's fp64 run is made. */
 int genie_set_tail_precision(genie_ctx* ctx, int fp64_chains);
 /* Arithmetic of the P-sized stages on the reference's kNN graphs. mode 0 (default) = automatic: two-piece fp16 operands on the
- * 16-bit matrix pipe (k_stage1_h2 / k_stage2_h2) while the fp16 range guard of the committed weights holds, the fp32-MFMA kernels
+ * 16-bit matrix pipe (k_stage1_h2 / k_stage2_h2u) while the fp16 range guard of the committed weights holds, the fp32-MFMA kernels
  * otherwise; 1 = two-piece fp16 operands regardless of the guard (A/B runs; hidden states above 65504 become non-finite);
  * 2 = fp32 MFMA always. No environment variable takes part. */
 int genie_set_stage_precision(genie_ctx* ctx, int mode);

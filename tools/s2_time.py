@@ -1,7 +1,6 @@
 #!/usr/bin/env python
-"""Stage-2 kernel alone (HIP events over repeated launches after one stage 1), for A/B runs of kernel variants selected by
-environment variables (GENIE_BPC2 = workgroups per CU, GENIE_S2_WGMAP = work map; read by -DGENIE_TUNING=1 builds only:
-GENIE_LIB_PATH=genie_amd/lib/libgenie_tune.so).
+"""Stage-2 kernel alone (HIP events over repeated launches after one stage 1), for A/B runs of kernel variants: variant builds
+of the library through GENIE_LIB_PATH, the work map of the row-layout stage 2 through HipPath.set_stage2_workmap.
 Usage: python tools/s2_time.py [config] [iters]"""
 import os
 import sys
