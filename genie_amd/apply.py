@@ -518,17 +518,21 @@ def associate_sources(legs, picks, srcs_refined, locs_cart, tq, max_t, trv_out_s
     return Out_p, Out_s, Save_picks, lp_meta
 
 
-def retained_after_marching(srcs_refined, ftrns1, tc_win, sp_win, scale_depth_clustering=0.2, scale_time_ref=3500.0):
+def retained_after_marching(srcs_refined, ftrns1, tc_win, sp_win, scale_depth_clustering=0.2, scale_time_ref=3500.0, device=None):
     """The second LocalMarching of the caller and the match back to the refined list (process_continuous_days.py:1072-1085): the
     refined sources that survive it (`n_steps_max = 2, use_directed = False`), found as the nearest refined source of each survivor in
-    (Cartesian position, `scale_time_ref` * origin time), `np.unique`d. Returns the retained row indices (ascending)."""
+    (Cartesian position, `scale_time_ref` * origin time), `np.unique`d. Returns the retained row indices (ascending). `device`: run
+    the marching there (`postproc.local_marching_device`, same survivors); the match back stays on the host either way."""
     from scipy.spatial import cKDTree
     from . import postproc
     srcs_refined = np.asarray(srcs_refined, dtype=np.float64)
     if len(srcs_refined) == 0:
         return np.zeros(0, dtype=np.int64)
-    kept = postproc.local_marching(srcs_refined, ftrns1, tc_win=tc_win, sp_win=sp_win, scale_depth=scale_depth_clustering, n_steps_max=2,
-                                   use_directed=False)
+    kw = dict(tc_win=tc_win, sp_win=sp_win, scale_depth=scale_depth_clustering, n_steps_max=2, use_directed=False)
+    if device is None:
+        kept = postproc.local_marching(srcs_refined, ftrns1, **kw)
+    else:
+        kept = postproc.local_marching_device(srcs_refined, ftrns1, device=device, **kw)
     tree = cKDTree(np.concatenate((ftrns1(srcs_refined), scale_time_ref * srcs_refined[:, [3]]), axis=1))
     return np.unique(tree.query(np.concatenate((ftrns1(kept), scale_time_ref * kept[:, [3]]), axis=1))[1])
 
@@ -536,7 +540,7 @@ def retained_after_marching(srcs_refined, ftrns1, tc_win, sp_win, scale_depth_cl
 def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, tq, max_t, ftrns1, ftrns2, lat_range, lon_range,
                             depth_range, X_offset_min, X_offset_range, n_rand_query, thresh, src_t_kernel, dt_win, break_win, tc_win,
                             sp_win, scale_depth_clustering=0.2, kernel_sig_t=synthetic.KERNEL_SIG_T, dt_embed=None, t_win_assoc=10.0,
-                            rand=None, ftrns2_device=None):
+                            rand=None, ftrns2_device=None, detect_on_device=False):
     """Everything the caller does between the apply loop and the competitive assignment, with the network calls on the device
     (process_continuous_days.py:811-1105): peaks of the device-resident `Out_2` -> time groups -> LocalMarching (`postproc.
     detect_sources`, :811-891), the refine pass (`refine_sources`, :926-982), travel times of the refined sources (`trv(locs, srcs)`
@@ -545,13 +549,15 @@ def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, 
     sources (:1092) and the final sort by origin time (:1097-1105). `locs` [S, 3] (lat, lon, depth) of the stations in use; `trv`: the
     travel-time callable of the reference, (float tensor [S, 3], float tensor [n, 3]) -> [n, S, 2]. Returns a dict: `srcs` (after the
     first marching), `srcs_refined` [m, 5], `trv_out_srcs` (device [m, S, 2]), `Out_p_save`, `Out_s_save` (lists of device tensors),
-    `Save_picks`, `lp_meta` (lists of host arrays) -- the inputs of `competitive_assignment`, which is out of scope."""
+    `Save_picks`, `lp_meta` (lists of host arrays) -- the inputs of `competitive_assignment`, which is out of scope.
+    `detect_on_device`: both LocalMarchings, the distance rule and the grouping run on the GPU (`postproc.detect_sources_device`,
+    `retained_after_marching(device=...)`) instead of on the host; the sources are the same."""
     from . import postproc
     dev = legs[0].device
     empty = {"srcs": np.zeros((0, 5)), "srcs_refined": np.zeros((0, 5)), "trv_out_srcs": None, "Out_p_save": [], "Out_s_save": [],
              "Save_picks": [], "lp_meta": []}
-    srcs = postproc.detect_sources(Out_2, X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_win, break_win, tc_win, sp_win,
-                                   scale_depth_clustering)
+    detect = postproc.detect_sources_device if detect_on_device else postproc.detect_sources
+    srcs = detect(Out_2, X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_win, break_win, tc_win, sp_win, scale_depth_clustering)
     if len(srcs) == 0:
         return empty                                                                                                    # :886-888
     locs = np.asarray(locs, dtype=np.float64)
@@ -564,7 +570,8 @@ def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, 
     x_save = np.array([lat_range[0], lon_range[0], 0.0])                              # xx[0] of the meshgrid of :1008-1014
     Out_p, Out_s, Save_picks, lp_meta = associate_sources(legs, picks, srcs_refined, locs_cart, tq, max_t, trv_out, ftrns1, x_save,
                                                           kernel_sig_t, dt_embed, t_win_assoc)
-    keep = retained_after_marching(srcs_refined, ftrns1, tc_win, sp_win, scale_depth_clustering)
+    keep = retained_after_marching(srcs_refined, ftrns1, tc_win, sp_win, scale_depth_clustering,
+                                   device=dev if detect_on_device else None)
     srcs_kept = srcs_refined[keep]
     with torch.no_grad():
         trv_kept = trv(locs_d, torch.as_tensor(srcs_kept[:, 0:3]).float().to(dev)).detach()                             # :1092

@@ -1223,6 +1223,7 @@ __device__ __forceinline__ void gather_sum16(const float* __restrict__ base, lon
 #include "train_tail_kernels.hpp"
 #include "train_assoc_kernels.hpp"
 #include "train_arrival_kernels.hpp"
+#include "detect_kernels.hpp"
 
 }  // namespace
 
@@ -3996,6 +3997,81 @@ int genie_row_select_fill(const float* x, int rows, int64_t cols, float threshol
     const long long* off = (const long long*)offsets;
     if (mode == 0) k_row_select<0, false><<<rows, 256, 0, st>>>(x, cols, threshold, nullptr, off, out_row, out_col, out_val);
     else k_row_select<1, false><<<rows, 256, 0, st>>>(x, cols, threshold, nullptr, off, out_row, out_col, out_val);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+namespace {
+// the library is built with -fno-honor-nans, which folds `x != x`, `!(x >= 0)` and any other test for a NaN alone: an all-ones
+// exponent (NaN or infinity) is what can be tested
+bool dbl_finite(double x) {
+    uint64_t u;
+    memcpy(&u, &x, sizeof u);
+    return ((u >> 52) & 0x7ffu) != 0x7ffu;
+}
+}  // namespace
+
+int genie_peak_distance(const int64_t* offsets, int rows, int64_t n, const int32_t* col, const float* val, int d, uint8_t* keep,
+                        void* stream) {
+    if (rows < 0 || n < 0 || d < 1) return fail(GENIE_ERR_ARG, "genie_peak_distance: rows, n >= 0 and d >= 1 required");
+    if ((rows > 0 && !offsets) || (n > 0 && (!col || !val || !keep))) return fail(GENIE_ERR_ARG, "genie_peak_distance: null argument");
+    if (rows == 0 || n == 0) return GENIE_OK;
+    const int nb = (rows + PD_ROWS_PER_BLOCK - 1) / PD_ROWS_PER_BLOCK;
+    k_peak_distance<<<nb, 256, 0, (hipStream_t)stream>>>((const long long*)offsets, rows, (long long)n, col, val, d, keep);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+int64_t genie_time_groups_scratch_ints(int64_t n) { return n > 0 ? (n + TG_BLOCK - 1) / TG_BLOCK : 0; }
+
+int genie_time_groups(const double* t, int64_t n, double break_win, int32_t* scratch, int32_t* group, void* stream) {
+    if (n < 0 || n >= (1ll << 31)) return fail(GENIE_ERR_ARG, "genie_time_groups: 0 <= n < 2^31 required");
+    if (!dbl_finite(break_win)) return fail(GENIE_ERR_ARG, "genie_time_groups: break_win must be finite");
+    if (n > 0 && (!t || !scratch || !group)) return fail(GENIE_ERR_ARG, "genie_time_groups: null argument");
+    if (n == 0) return GENIE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const int nb = (int)genie_time_groups_scratch_ints(n);
+    k_time_groups<false><<<nb, 256, 0, st>>>(t, (long long)n, break_win, scratch, nullptr);
+    k_time_groups<true><<<nb, 256, 0, st>>>(t, (long long)n, break_win, scratch, group);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+namespace {
+size_t lm_pad(size_t b) { return (b + 255) & ~(size_t)255; }
+}  // namespace
+
+size_t genie_local_marching_scratch_bytes(int64_t n) {
+    return n > 0 ? 256 + 2 * lm_pad(4 * (size_t)n) + lm_pad((size_t)n) : 0;
+}
+
+int genie_local_marching(const double* xs, const double* t, const float* val, const int32_t* group, int64_t n, double tc_win,
+                         double sp_win, int n_steps_max, double tol, int use_directed, void* scratch, uint8_t* keep, void* stream) {
+    if (n < 0 || n >= (1ll << 31)) return fail(GENIE_ERR_ARG, "genie_local_marching: 0 <= n < 2^31 required");
+    if (!dbl_finite(tc_win) || !dbl_finite(sp_win) || tc_win < 0.0 || sp_win < 0.0)
+        return fail(GENIE_ERR_ARG, "genie_local_marching: tc_win and sp_win must be finite and >= 0");
+    if (n > 0 && (!xs || !t || !val || !scratch || !keep)) return fail(GENIE_ERR_ARG, "genie_local_marching: null argument");
+    if (((uintptr_t)scratch & 15) != 0) return fail(GENIE_ERR_ARG, "genie_local_marching: scratch must be 16-byte aligned");
+    if (n == 0) return GENIE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)scratch;
+    unsigned* diff = (unsigned*)base;
+    float* buf[2] = {(float*)(base + 256), (float*)(base + 256 + lm_pad(4 * (size_t)n))};
+    unsigned char* active = (unsigned char*)(base + 256 + 2 * lm_pad(4 * (size_t)n));
+    const int nb = (int)((n + 255) / 256);
+    const double tc2 = tc_win * tc_win, sp2 = sp_win * sp_win;
+    HIP_TRY(hipMemsetAsync(diff, 0, 256, st));
+    HIP_TRY(hipMemsetAsync(active, 0, (size_t)n, st));                     // n_steps_max < 1: nothing marches, every node is kept
+    const float* cur = val;
+    for (int s = 0; s < n_steps_max; ++s) {
+        float* out = buf[s & 1];
+        if (use_directed)
+            k_local_marching_step<true><<<nb, 256, 0, st>>>(xs, t, val, group, cur, out, active, (long long)n, tc_win, tc2, sp2, tol, s, diff);
+        else
+            k_local_marching_step<false><<<nb, 256, 0, st>>>(xs, t, val, group, cur, out, active, (long long)n, tc_win, tc2, sp2, tol, s, diff);
+        cur = out;
+    }
+    k_local_marching_keep<<<nb, 256, 0, st>>>(val, cur, active, (long long)n, (float)tol, keep);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }

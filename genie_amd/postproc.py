@@ -8,6 +8,13 @@ What runs where:
 * The remaining steps work on those few triplets on the host, restated from the libraries the reference calls: the distance
   rule of `find_peaks` (scipy `_select_by_peak_distance`), the grouping by `break_win` (:856-870) and `LocalMarching` (max
   propagation over a space-time radius graph, `process_utils.py:40-100`; pinned to the reference by tests/golden/localmarching.npz).
+  `detect_sources` takes this path. A day with a thousand events has ~5 * 10^5 triplets and the host LocalMarching then takes about a
+  minute (profiles/EXPERIMENTS.md, "Source detection on the device"), so:
+* `find_peaks_rows_device`, `local_marching_device` and `detect_sources_device` run the same three steps as HIP kernels
+  (`genie_peak_distance`, `genie_time_groups`, `genie_local_marching`, csrc/detect_kernels.hpp): triplets, the sort by time, groups and
+  the march stay on the GPU, `ftrns1` is applied once to the query positions on the host, and only the surviving [n, 5] rows come
+  back. The host functions are their oracle (equal index sets and rows); they differ only where scipy itself is unspecified: of two
+  equal peak heights closer than the distance, the device keeps the later column.
 """
 import ctypes
 
@@ -24,10 +31,8 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
-def row_select(x, threshold, mode):
-    """Device selection over the rows of a contiguous fp32 GPU matrix `x [rows, cols]`; mode 0: entries > threshold; mode 1:
-    local maxima (flat tops -> midpoint, never the first / last column) with value >= threshold. Returns (row int32, col int32,
-    value fp32) GPU tensors in row-major order. The only host round trip is the total count (one integer)."""
+def _row_select_offsets(x, threshold, mode):
+    """`row_select` plus the exclusive int64 row offsets of its triplets (what `genie_peak_distance` walks rows by)."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
         raise ValueError("row_select: x must be a 2-D fp32 GPU tensor")
     if not x.is_contiguous():
@@ -55,7 +60,14 @@ def row_select(x, threshold, mode):
         if n:
             _lib.check(lib.genie_row_select_fill(_ptr(x), rows, cols, ctypes.c_float(float(th)), int(mode), _ptr(offsets),
                                                  _ptr(out_row), _ptr(out_col), _ptr(out_val), st), "genie_row_select_fill")
-    return out_row, out_col, out_val
+    return out_row, out_col, out_val, offsets
+
+
+def row_select(x, threshold, mode):
+    """Device selection over the rows of a contiguous fp32 GPU matrix `x [rows, cols]`; mode 0: entries > threshold; mode 1:
+    local maxima (flat tops -> midpoint, never the first / last column) with value >= threshold. Returns (row int32, col int32,
+    value fp32) GPU tensors in row-major order. The only host round trip is the total count (one integer)."""
+    return _row_select_offsets(x, threshold, mode)[:3]
 
 
 def sparse_above(Out_2, thresh=0.01):
@@ -190,3 +202,115 @@ def detect_sources(Out_2, X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_
         return np.zeros((0, 5))
     srcs = np.vstack(out)
     return srcs[np.argsort(srcs[:, 3])]
+
+
+# ------------------------------------------------------------------------------------------------
+# The same three stages on the device (genie_peak_distance / genie_time_groups / genie_local_marching, csrc/detect_kernels.hpp).
+# The host functions above stay as they are and are the oracle of these: index sets and surviving rows are equal, not close.
+# ------------------------------------------------------------------------------------------------
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def find_peaks_rows_device(Out_2, height, distance):
+    """`find_peaks_rows` without the host: candidates and the distance rule both on the device. Returns GPU tensors (row int32,
+    col int32, peak height fp32), rows ascending, columns ascending within a row. Equal to `find_peaks_rows` wherever the distance
+    rule is decided by heights; of two EQUAL heights closer than ceil(distance) the later column is kept (scipy decides that case
+    by an unstable sort, so its own answer is not specified)."""
+    if distance is not None and distance < 1:
+        raise ValueError("`distance` must be greater or equal to 1")
+    if not height > 0.01:
+        raise ValueError("find_peaks_rows_device: height must be > 0.01 (the reference's sparsification threshold)")
+    r, c, v, offsets = _row_select_offsets(Out_2, height, 1)
+    if distance is None or r.numel() == 0:
+        return r, c, v
+    keep = _peak_distance_keep(offsets, c, v, distance)
+    return r[keep], c[keep], v[keep]
+
+
+def _peak_distance_keep(offsets, c, v, distance):
+    """Keep flags (bool GPU tensor) of the distance rule on row-major peak triplets: `offsets` [rows] int64 exclusive row offsets,
+    `c` int32 columns (ascending within a row), `v` fp32 heights."""
+    keep = torch.empty(c.numel(), dtype=torch.uint8, device=c.device)
+    with torch.cuda.device(c.device):
+        _lib.check(_lib.load().genie_peak_distance(_ptr(offsets), int(offsets.numel()), int(c.numel()), _ptr(c), _ptr(v),
+                                                   int(np.ceil(distance)), _ptr(keep), _stream(c.device)), "genie_peak_distance")
+    return keep.bool()
+
+
+def time_groups_device(t, break_win):
+    """Group number (int32 GPU tensor) of every entry of the ascending fp64 GPU tensor `t`: a new group starts where the gap to the
+    predecessor is >= break_win (`group_sources`)."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 1 and t.is_contiguous()):
+        raise ValueError("time_groups_device: t must be a contiguous 1-D fp64 GPU tensor")
+    lib = _lib.load()
+    n = int(t.numel())
+    group = torch.empty(n, dtype=torch.int32, device=t.device)
+    scratch = torch.empty(int(lib.genie_time_groups_scratch_ints(n)), dtype=torch.int32, device=t.device)
+    with torch.cuda.device(t.device):
+        _lib.check(lib.genie_time_groups(_ptr(t), n, ctypes.c_double(float(break_win)), _ptr(scratch), _ptr(group), _stream(t.device)),
+                   "genie_time_groups")
+    return group
+
+
+def _marching_keep(xs, t, val, group, tc_win, sp_win, n_steps_max, tol, use_directed):
+    """Keep flags (bool GPU tensor) of LocalMarching on device tensors already sorted by time: xs [n, 3] fp64, t [n] fp64,
+    val [n] fp32, group [n] int32 or None."""
+    lib = _lib.load()
+    n = int(t.numel())
+    xs, t, val = xs.contiguous(), t.contiguous(), val.contiguous()
+    group = group.contiguous() if group is not None else None
+    keep = torch.empty(n, dtype=torch.uint8, device=t.device)
+    scratch = torch.empty(int(lib.genie_local_marching_scratch_bytes(n)), dtype=torch.uint8, device=t.device)
+    with torch.cuda.device(t.device):
+        _lib.check(lib.genie_local_marching(_ptr(xs), _ptr(t), _ptr(val), _ptr(group), n,
+                                            ctypes.c_double(float(tc_win)), ctypes.c_double(float(sp_win)), int(n_steps_max),
+                                            ctypes.c_double(float(tol)), int(bool(use_directed)), _ptr(scratch), _ptr(keep),
+                                            _stream(t.device)), "genie_local_marching")
+    return keep.bool()
+
+
+def local_marching_device(srcs, ftrns1, tc_win=5, sp_win=35e3, n_steps_max=100, tol=1e-12, scale_depth=1.0, use_directed=True,
+                          device=None):
+    """`local_marching` with the graph and the march on the device: same arguments, same surviving rows of `srcs` in index order.
+    `ftrns1` and the depth scale are applied on the host (one call); nodes are sorted by time on the device and the flags mapped back."""
+    srcs = np.asarray(srcs, dtype=np.float64)
+    n = srcs.shape[0]
+    if n == 0:
+        return srcs
+    dev = torch.device("cuda" if device is None else device)
+    xs = np.asarray(ftrns1(srcs[:, 0:3]), dtype=np.float64) * np.array([1.0, 1.0, scale_depth]).reshape(1, -1)
+    xs_d = torch.from_numpy(np.ascontiguousarray(xs)).to(dev)
+    t_d, order = torch.sort(torch.from_numpy(np.ascontiguousarray(srcs[:, 3])).to(dev), stable=True)
+    val_d = torch.from_numpy(srcs[:, 4].astype(np.float32)).to(dev)
+    keep_sorted = _marching_keep(xs_d[order], t_d, val_d[order], None, tc_win, sp_win, n_steps_max, tol, use_directed)
+    keep = torch.empty_like(keep_sorted)
+    keep[order] = keep_sorted
+    return srcs[keep.cpu().numpy()]
+
+
+def detect_sources_device(Out_2, X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_win, break_win, tc_win, sp_win,
+                          scale_depth_clustering=0.2):
+    """`detect_sources` with every stage on the device: peaks and distance rule (`find_peaks_rows_device`), a stable sort by time,
+    the time groups, LocalMarching within the groups (`n_steps_max = 2, use_directed = False`). `ftrns1` is applied once to the
+    query positions on the host (every candidate sits on a query row). Only the surviving rows cross to the host: [n, 5], sorted by
+    time, equal to the rows `detect_sources` returns (sources of equal time may come in another order)."""
+    r, c, v = find_peaks_rows_device(Out_2, thresh, int(1.5 * src_t_kernel / dt_win))
+    return _sources_from_peaks(r, c, v, X_query, tsteps_abs, ftrns1, break_win, tc_win, sp_win, scale_depth_clustering)
+
+
+def _sources_from_peaks(r, c, v, X_query, tsteps_abs, ftrns1, break_win, tc_win, sp_win, scale_depth_clustering):
+    """The part of `detect_sources_device` after the peaks: GPU triplets (row, col, height) -> surviving sources [n, 5] on the host."""
+    if r.numel() == 0:
+        return np.zeros((0, 5))
+    dev = r.device
+    xq = np.asarray(X_query, dtype=np.float64)
+    xs_q = np.asarray(ftrns1(xq[:, 0:3]), dtype=np.float64) * np.array([1.0, 1.0, scale_depth_clustering]).reshape(1, -1)
+    ts_d = torch.from_numpy(np.ascontiguousarray(np.asarray(tsteps_abs, dtype=np.float64))).to(dev)
+    t, order = torch.sort(ts_d[c.long()], stable=True)
+    r, v = r[order].long(), v[order]
+    group = time_groups_device(t, break_win)
+    keep = _marching_keep(torch.from_numpy(np.ascontiguousarray(xs_q)).to(dev)[r], t, v, group, tc_win, sp_win, 2, 1e-12, False)
+    xq_d = torch.from_numpy(np.ascontiguousarray(xq[:, 0:3])).to(dev)
+    srcs = torch.cat((xq_d[r[keep]], t[keep].reshape(-1, 1), v[keep].double().reshape(-1, 1)), dim=1)
+    return srcs.cpu().numpy()

@@ -540,6 +540,30 @@ int genie_row_select_count(const float* x, int rows, int64_t cols, float thresho
 int genie_row_select_fill(const float* x, int rows, int64_t cols, float threshold, int mode, const int64_t* offsets,
                           int32_t* out_row, int32_t* out_col, float* out_val, void* stream);
 
+/* Source detection after the peaks, on the device (process_continuous_days.py:846-891; LocalMarching, process_utils.py:40-100).
+ * The host functions of genie_amd/postproc.py are the oracle of all three; flags are uint8 (1 = kept).
+ *
+ * genie_peak_distance: the distance rule of scipy.signal.find_peaks on the triplets genie_row_select_fill (mode 1) wrote.
+ *   offsets [rows] are the exclusive row offsets handed to it, n the number of triplets, d = ceil(distance) >= 1. Walking from the
+ *   highest peak of a row down, a kept peak removes every peak of the row closer than d columns; of two EQUAL heights within d the later
+ *   column wins (scipy leaves that case to an unstable sort). keep [n].
+ * genie_time_groups: t [n] ascending (fp64); node i starts a new group when t[i] - t[i - 1] >= break_win; group [n] = number of starts
+ *   up to and including i (0 for the first group); break_win finite. scratch: genie_time_groups_scratch_ints(n) int32.
+ * genie_local_marching: n nodes SORTED BY TIME (the caller's contract, not checked): xs [n, 3] fp64 positions already mapped and
+ *   depth-scaled, t [n] fp64, val [n] fp32, group [n] or NULL (one group). j is an in-neighbour of i when both are in the same group,
+ *   (t_i - t_j)^2 <= tc_win^2 and ((dx0^2 + dx1^2) + dx2^2) <= sp_win^2 (fp64, inclusive, unfused); a node with no neighbour but itself
+ *   is kept as it is; the others take the maximum over their in-neighbours (use_directed: only those with val[i] <= val[j]) for
+ *   n_steps_max steps or until a step changes nothing by more than tol, and survive when |val - marched| <= 1e-8 + tol |marched| (fp32).
+ *   scratch: genie_local_marching_scratch_bytes(n) bytes, 16-byte aligned. keep [n]. Values must not be NaN.
+ * Bad arguments (n < 0, a null pointer with n > 0, d < 1, tc_win / sp_win negative or not finite) return GENIE_ERR_ARG before any launch. */
+int genie_peak_distance(const int64_t* offsets, int rows, int64_t n, const int32_t* col, const float* val, int d, uint8_t* keep,
+                        void* stream);
+int64_t genie_time_groups_scratch_ints(int64_t n);
+int genie_time_groups(const double* t, int64_t n, double break_win, int32_t* scratch, int32_t* group, void* stream);
+size_t genie_local_marching_scratch_bytes(int64_t n);
+int genie_local_marching(const double* xs, const double* t, const float* val, const int32_t* group, int64_t n, double tc_win,
+                         double sp_win, int n_steps_max, double tol, int use_directed, void* scratch, uint8_t* keep, void* stream);
+
 /* Debug/parity access to intermediates kept in the workspace (which: 0 = c [P,30], 1 = wu [P,15], 2 = wv [P,15]);
  * copies de-padded rows into `out` (async). */
 int genie_ws_export(genie_ctx* ctx, int which, void* ws, float* out, void* stream);
