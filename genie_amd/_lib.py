@@ -24,6 +24,7 @@ SYMBOLS = [
     ("genie_ctx_create", _c.c_int, [_c.POINTER(_P), _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P, _P, _c.c_float]),
     ("genie_ctx_create_subgraph", _c.c_int, [_c.POINTER(_P), _c.c_int, _c.c_int, _c.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _c.c_float]),
     ("genie_ctx_destroy", _c.c_int, [_P]),
+    ("genie_pool_stats", _c.c_int, [_c.c_int, _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64), _c.POINTER(_c.c_int64)]),
     ("genie_set_scale_t", _c.c_int, [_P, _c.c_float]),
     ("genie_set_edge_features", _c.c_int, [_P, _P, _P, _P]),
     ("genie_set_absolute_pos", _c.c_int, [_P, _P, _P, _P]),

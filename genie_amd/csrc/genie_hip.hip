@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <array>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <utility>
 #include <type_traits>
@@ -57,6 +58,10 @@ int fail(int code, const std::string& msg) {
         if (e_ != hipSuccess)                                                                      \
             return fail(GENIE_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));         \
     } while (0)
+#define GENIE_TRY(expr)                                                                            \
+    do {                                                                                           \
+        if (int rc_ = (expr)) return rc_;                                                          \
+    } while (0)
 
 // ------------------------------------------------------------------------------------------------
 // Device-memory pool of the library's own allocations (graph tables, weight images, plan tables).
@@ -64,8 +69,8 @@ int fail(int code, const std::string& msg) {
 // and created per sample: ~100 hipMalloc / hipFree pairs through the driver (each hipFree also drains the device) were most of
 // that cost. Freed blocks are kept per device and size class (sizes rounded up to 1/8-octave steps, so a context of 199 stations
 // reuses the blocks of one of 200) and handed out again; above POOL_CAP cached bytes a freed block goes back to the driver.
-// Blocks are reused without an implicit device synchronisation: gfree_sync() (one hipDeviceSynchronize, then gfree) where work
-// that may still read the block can be in flight; genie_ctx_destroy synchronises once for all of its blocks.
+// Blocks are reused without an implicit device synchronisation: whoever returns one drains the device first where work that may
+// still read it can be in flight; genie_ctx_destroy synchronises once for all of its blocks. Every block has one owner, a DevBuf.
 // ------------------------------------------------------------------------------------------------
 struct DevPool {
     std::multimap<size_t, void*> free_;
@@ -129,11 +134,24 @@ hipError_t gfree(void* p) {         // the caller guarantees that no launched wo
     return hipSuccess;
 }
 
-hipError_t gfree_sync(void* p) {
-    if (!p) return hipSuccess;
-    (void)hipDeviceSynchronize();
-    return gfree(p);
-}
+// Owner of one pool block: move-only, the destructor and reset() hand the block back with gfree. It never synchronises, so the
+// rule of gfree holds for whoever lets a DevBuf go: no launched work still uses the block (genie_ctx_destroy drains the device once
+// for all buffers of a context; the replace-in-place paths drain before they reset). Converts to T*, so launches and argument
+// structs read it like the pointer it holds.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { reset(); p = o.p; o.p = nullptr; }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset() { (void)gfree(p); p = nullptr; }
+    hipError_t alloc(size_t n) { reset(); return gmalloc(&p, sizeof(T) * std::max<size_t>(n, 1)); }      // n elements, uninitialised
+    operator T*() const { return p; }
+};
 
 // ------------------------------------------------------------------------------------------------
 // Weight registry: the path's parameters under the reference's state_dict names.
@@ -701,8 +719,12 @@ void build_train_plans(StagePlan& p2, StagePlan& p1, StagePlan& p0) {
 // lane (j = lane&15, q = lane>>4) holds channels 16t + 4q + {0..3} of node j exactly as in the stage kernels, every per-node
 // Linear is a chain of v_mfma_f32_16x16x4_f32 whose A fragments come from a k_pack_all image in LDS (one ds_read_b128 per 16 x 16
 // weight block and wave instead of two LDS reads per scalar FMA) and whose result is the B operand of the next Linear.
-// Plans (genie_ctx::plan[PL_*]) and their group index maps:
-enum { PL_RO0 = 7, PL_RO1, PL_ROP, PL_SA1, PL_SA2, PL_SA3, PL_BIP, PL_LSP, PL_LSS, PL_ARR,
+// Plans (ModelTables::plan[PL_*], genie_ctx::packed[PL_*]) and their group index maps:
+enum { PL_S1, PL_S2,               // DataAggregation stage 1 / 2
+       PL_ASA, PL_ASB,             // association stages A / B
+       PL_B2, PL_B1, PL_B0,        // backward passes 2', 1', 0' (consecutive: PL_B2 + pass)
+       // the MFMA kernels of the G- / Q-sized tail
+       PL_RO0, PL_RO1, PL_ROP, PL_SA1, PL_SA2, PL_SA3, PL_BIP, PL_LSP, PL_LSS, PL_ARR,
        // transposed weights of the tail's backward passes (train_tail_kernels.hpp)
        PL_TRO0, PL_TRO1, PL_TSN, PL_TSA1, PL_TSA2, PL_TSA3, PL_TBIP,
        // ... and of the association heads' backward passes (train_assoc_kernels.hpp)
@@ -1232,58 +1254,72 @@ __device__ __forceinline__ void gather_sum16(const float* __restrict__ base, lon
 // ================================================================================================
 enum class RowLayout { Rows, NodePlanar };   // the c / wv rows of stage 1 in the workspace: rows or node-planar (DaArgs.np)
 
+// The tables that depend on neither a graph nor the weights: the stage plans (host), their step / bias / scalar descriptors, the gradient
+// maps of the backward passes and the source tables of the f16x2 weight images (device). Built ONCE per device and process
+// (model_tables) and never destroyed; every context of the device reads them through genie_ctx::tb. Building them per context was ~45
+// blocking host-to-device copies = most of the 2.4 ms genie_ctx_create cost per training sample (train_GENIE_model.py:1722-1786).
+// Their blocks come from the pool like every other one and stay handed out for the life of the process.
+struct ModelTables {
+    StagePlan plan[NPLAN];
+    DevBuf<StepDesc> d_steps[NPLAN];
+    DevBuf<BiasDesc> d_bias[NPLAN];
+    DevBuf<int32_t> d_scal[NPLAN];
+    DevBuf<AccDesc> d_acc[NTM]; DevBuf<VecDesc> d_vec[NTM]; DevBuf<int32_t> d_sc[NTM];   // gradient maps of the backward passes (k_train_reduce)
+    int n_acc[NTM] = {}, n_vec[NTM] = {}, n_sc[NTM] = {};
+    DevBuf<int32_t> d_h2tbl;   // k_pack_h2 source table of k_stage1_h2's image
+    DevBuf<int32_t> d_s2htbl;  // ... of k_stage2_h2u's image
+};
+
+// out-edge CSR of a graph given as in-edge CSR, weights 1 / in-degree of the target (build_reversed)
+struct RevGraph {
+    DevBuf<int32_t> rowptr, col;
+    DevBuf<float> w;
+    DevBuf<int2> cw;           // the same edges as (column, weight bits) pairs: one 8-byte load per edge (training passes); optional
+};
+
+// Every DevBuf below is owned by the context and goes with it; a raw pointer is borrowed and says so.
 struct genie_ctx {
     int S, G, G_ext, T;
     float scale_rel, scale_t;
     long long P, P_ext, E_src;
-    int32_t *sta_rowptr, *sta_col, *src_rowptr, *src_col, *order, *outdeg;
-    float* raw;
+    DevBuf<int32_t> sta_rowptr, sta_col, src_rowptr, src_col, order, outdeg;
+    DevBuf<float> raw;
     bool dirty;
-    StagePlan plan[NPLAN];     // 0, 1: DataAggregation stage 1 / 2; 2, 3: association stages A / B; 4, 5, 6: backward passes 2', 1', 0';
-                               // PL_RO0 ...: the MFMA kernels of the G- / Q-sized tail
-    void* d_packplans; int pack_blocks;     // k_pack_all's plan table (PackPlan[NPLAN]) and its grid
-    StepDesc* d_steps[NPLAN];
-    BiasDesc* d_bias[NPLAN];
-    int32_t* d_scal[NPLAN];
-    float* packed[NPLAN];
-    AccDesc* d_acc[NTM]; VecDesc* d_vec[NTM]; int32_t* d_sc[NTM];   // gradient maps of the backward passes (k_train_reduce)
-    int n_acc[NTM], n_vec[NTM], n_sc[NTM];
-    float* as_pg;              // [G][AS_PG] per-source-node terms of the association stages (allocated on first use)
-    float* as_ps;              // [S][AS_PS] per-station terms of the two model variants (allocated on first use)
-    int32_t* d_h2tbl;          // k_pack_h2 source table
-    // reversed base graphs (out-edges, weights 1 / in-degree of the target): built on the first genie_nbr_mean_bwd
-    int32_t *r_sta_rowptr, *r_sta_col, *r_src_rowptr, *r_src_col;
-    float *r_sta_w, *r_src_w;
-    int2 *r_sta_cw, *r_src_cw;   // the same edges as (column, weight bits) pairs: one 8-byte load per edge (training passes)
-    int32_t *rp_sta_rowptr, *rp_src_rowptr; int2 *rp_sta_cw, *rp_src_cw;   // irregular product graph: the reversed PRODUCT-level graphs
-    int32_t *ptile16, *ptile32;  // irregular product graph: the tiles of 16 / 32 consecutive product nodes in the ORDER they are processed in
+    const ModelTables* tb;     // the device's graph-independent tables (borrowed: they outlive every context)
+    DevBuf<PackPlan> d_packplans; int pack_blocks;     // k_pack_all's plan table (PackPlan[NPLAN]) and its grid
+    DevBuf<float> packed[NPLAN];   // weight images of the plans tb->plan[PL_*]
+    DevBuf<float> as_pg;       // [G][AS_PG] per-source-node terms of the association stages (allocated on first use)
+    DevBuf<float> as_ps;       // [S][AS_PS] per-station terms of the two model variants (allocated on first use)
+    // reversed base graphs: built on the first genie_nbr_mean_bwd (without cw) or training backward (ensure_reversed)
+    RevGraph r_sta, r_src;
+    RevGraph rp_sta, rp_src;   // irregular product graph: the reversed PRODUCT-level graphs (rowptr and cw only)
+    DevBuf<int32_t> ptile16, ptile32;  // irregular product graph: the tiles of 16 / 32 consecutive product nodes in the ORDER they are processed in
                                  // (by the space-filling-curve rank of their source node): neighbouring source nodes run together on one XCD
-    const float *xs_slice, *xs_mask;   // genie_embed_window_split: the (Slice, Mask) buffers whose split rows already sit in the workspace (one-shot)
-    const void* xs_ws;
+    const float *xs_slice, *xs_mask;   // genie_embed_window_split: the caller's (Slice, Mask) buffers whose split rows already sit in the
+    const void* xs_ws;                 // workspace (one-shot); borrowed, compared only
     int xs_mm_copy;            // ... and the copy (slot % GENIE_NBIG at embed time) its message-mask row `mm` was written to
-    float *abs_sta, *abs_src;  // use_absolute_pos: [S][4], [G_ext][4] scaled positions; null = off
-    unsigned *abs_ts, *abs_tg; // ... their fp16 pieces for k_stage1_h2 (stations in processing order), rebuilt when abs_dirty
+    DevBuf<float> abs_sta, abs_src;  // use_absolute_pos: [S][4], [G_ext][4] scaled positions; null = off
+    DevBuf<unsigned> abs_ts, abs_tg; // ... their fp16 pieces for k_stage1_h2 (stations in processing order), rebuilt when abs_dirty
     bool abs_dirty;
     int abs_ts_order;          // station order the pieces were built in (1 = processing order)
     // irregular product graph (`use_subgraph`): product-level CSRs, row range of every source node
     bool pcsr;
     bool pcsr_h2;              // ... with at most 8 / 15 neighbours per product node: k_stage1_h2<.., PCSR> applies
-    int32_t *p_sta_rowptr, *p_sta_col, *p_src_rowptr, *p_src_col, *seg_rowptr;
-    int32_t* p_src_of;         // ... source node of every product node (built on the first genie_assoc_fwd)
-    int32_t* p_sta_of = nullptr;   // ... station of every product node (genie_set_subgraph_stations: the device embedding needs it)
-    float *mpos_sta, *mpos_src, *ebias_sta, *ebias_src;   // DataAggregationEdges: mean edge features [n,4] and their Linear [n,48]
+    DevBuf<int32_t> p_sta_rowptr, p_sta_col, p_src_rowptr, p_src_col, seg_rowptr;
+    DevBuf<int32_t> p_src_of;  // ... source node of every product node (built on the first genie_assoc_fwd)
+    DevBuf<int32_t> p_sta_of;  // ... station of every product node (genie_set_subgraph_stations: the device embedding needs it)
+    DevBuf<float> mpos_sta, mpos_src, ebias_sta, ebias_src;   // DataAggregationEdges: mean edge features [n,4] and their Linear [n,48]
     bool has_edges;
     // station processing order (genie_set_station_order): internal -> caller's station, its inverse, the station graph in
     // internal labels, the per-station edge terms in internal order; null = the caller's order
-    int32_t *sta_perm, *sta_inv, *sta_rowptr_p, *sta_col_p;
-    int32_t* sta_ident;        // 0 .. S-1: the station order of the training forward (pre-activations are stored in the caller's order)
-    float* ebias_sta_p;
-    float* ea_int; const float* ea_user;   // genie_set_static_edge_attr: processing-order copy of the caller's static edge_attr
-    float* ea_tmp;             // ... of an edge_attr that is not the registered one (permuted per call)
-    int32_t* src_tab;          // [G][16] processing-order table of k_stage1_h2 (null unless kp_uni == 15)
-    float* packed_h2;          // f16x2 weight image of k_stage1_h2
-    hipStream_t side_stream = nullptr;      // fork / join inside one call (genie_tail_train_bwd: the grid branch beside the query branch); the device's, not owned
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    DevBuf<int32_t> sta_perm, sta_inv, sta_rowptr_p, sta_col_p;     // (installed together: sta_perm != null = an order is installed)
+    DevBuf<int32_t> sta_ident; // 0 .. S-1: the station order of the training forward (pre-activations are stored in the caller's order)
+    DevBuf<float> ebias_sta_p;
+    const float* ea_user;      // genie_set_static_edge_attr: the caller's static edge_attr that ea_frag was built from (borrowed, compared only)
+    DevBuf<int32_t> src_tab;   // [G][16] processing-order table of k_stage1_h2 (null unless kp_uni == 15)
+    DevBuf<float> packed_h2;   // f16x2 weight image of k_stage1_h2
+    hipStream_t side_stream;   // fork / join inside one call (genie_tail_train_bwd: the grid branch beside the query branch); the device's, borrowed
+    hipEvent_t ev_fork, ev_join;            // ... its two events: owned (~genie_ctx)
     int device = 0;            // the HIP device the context was created on (genie_ctx_destroy drains THAT device)
     int num_cu;
     int seg, bpc1, bpc2;       // sweep segments, workgroups per CU of the generic stage kernels
@@ -1298,18 +1334,16 @@ struct genie_ctx {
     bool range_ok;             // fp16 range guard (k_h2_range, evaluated at every weight commit): every hidden state the f16x2 kernels
                                // split into fp16 pieces is bounded below 60 000 for inputs in [-1, 1], and so is every weight
     float range_act, range_w;  // ... the two bounds it found (largest hidden-state bound, largest weight magnitude incl. the 16 x forms)
-    float* d_range; float* h_range;     // device result / pinned host copy of k_h2_range
-    unsigned* h_inflag = nullptr;       // host-mapped word: bits of the largest |input| a split pass saw BEYOND what the range guard verified
-                                        // (flag_input_range), 0 = none; read by genie_input_range without synchronising
+    DevBuf<float> d_range; float* h_range;     // device result / pinned host copy (owned: ~genie_ctx) of k_h2_range
+    unsigned* h_inflag;                 // host-mapped word: bits of the largest |input| a split pass saw BEYOND what the range guard verified
+                                        // (flag_input_range), 0 = none; read by genie_input_range without synchronising. Pinned, owned
     // k_stage2_h2u: blocks of adjacent source nodes with the union of their neighbour rows, per launched range [gi_begin, gi_end) of the
     // processing order (the whole grid; the sharded path's four static sub-ranges): built on first use from the host copy of src_tab
-    struct S2uTables { void* blocks; int32_t* xcd0; int nblk; };
+    struct S2uTables { DevBuf<S2uBlock> blocks; DevBuf<int32_t> xcd0; int nblk; };
     std::map<std::pair<int, int>, S2uTables> s2u;
     std::vector<int32_t> tab_host;
-    int32_t* d_s2htbl;         // k_pack_h2 source table of k_stage2_h2u's image
-    float* packed_s2h;         // f16x2 weight image of k_stage2_h2u (Bipartite_ReadIn.fc1)
-    unsigned *ea_frag, *ea_frag_tmp;    // edge_attr as B fragments of k_stage2_h2u (k_ea_frag): of the registered static edge_attr / of any other one
-    bool tables_shared = false;   // the graph-independent tables below belong to the device's template context (model_tables): not freed here
+    DevBuf<float> packed_s2h;  // f16x2 weight image of k_stage2_h2u (Bipartite_ReadIn.fc1)
+    DevBuf<unsigned> ea_frag, ea_frag_tmp;    // edge_attr as B fragments of k_stage2_h2u (k_ea_frag): of the registered static edge_attr / of any other one
     RowLayout s1_layout;       // layout of the c / wv rows the last stage 1 left in the workspace (stage 2 checks it against its route)
     std::vector<const void*> lds_attr_done;   // kernels whose MaxDynamicSharedMemorySize was raised for THIS context's device (the attribute
                                // is per device: a process-wide flag would skip the second GPU of a multi-GPU process)
@@ -1323,6 +1357,14 @@ struct genie_ctx {
     size_t big_stride;         // so do the P-sized stage-1 -> stage-2 buffers (c, wu, wv)
     int tail_cu_ro, tail_cu_sa; // grid caps (workgroups) of the read-out / SpatialAggregation kernels of the G-sized tail
     int slot;                  // lets window i+1's stage 1/2 overlap window i's G-sized kernels on another stream
+
+    // what is not a DevBuf; the caller (genie_ctx_destroy) has selected and drained the device
+    ~genie_ctx() {
+        if (h_range) (void)hipHostFree(h_range);
+        if (h_inflag) (void)hipHostFree(h_inflag);
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+        if (ev_join) (void)hipEventDestroy(ev_join);
+    }
 };
 
 namespace {
@@ -1451,14 +1493,21 @@ void layout_ws(genie_ctx* c) {
     c->ws_floats = o;
 }
 
+// a new block of n elements filled from device / host memory (blocking copies)
 template <typename T>
-int dev_copy(T** dst, const T* src_dev, size_t n) {
-    *dst = nullptr;
-    if (n == 0) n = 1;
-    HIP_TRY(gmalloc((void**)dst, n * sizeof(T)));
-    if (src_dev) HIP_TRY(hipMemcpy(*dst, src_dev, n * sizeof(T), hipMemcpyDeviceToDevice));
+int dev_copy(DevBuf<T>& dst, const T* src_dev, size_t n) {
+    HIP_TRY(dst.alloc(n));
+    if (src_dev && n) HIP_TRY(hipMemcpy(dst, src_dev, n * sizeof(T), hipMemcpyDeviceToDevice));
     return GENIE_OK;
 }
+template <typename T>
+int dev_upload(DevBuf<T>& dst, const T* src_host, size_t n) {
+    HIP_TRY(dst.alloc(n));
+    if (n) HIP_TRY(hipMemcpy(dst, src_host, n * sizeof(T), hipMemcpyHostToDevice));
+    return GENIE_OK;
+}
+template <typename T>
+int dev_upload(DevBuf<T>& dst, const std::vector<T>& v) { return dev_upload(dst, v.data(), v.size()); }
 
 int ensure_packed(genie_ctx* c, hipStream_t st) {
     if (!c->dirty) return GENIE_OK;
@@ -1466,19 +1515,18 @@ int ensure_packed(genie_ctx* c, hipStream_t st) {
         std::vector<PackPlan> pl(NPLAN);
         int blocks = 0;
         for (int s = 0; s < NPLAN; ++s) {
-            const StagePlan& p = c->plan[s];
-            pl[s].steps = c->d_steps[s]; pl[s].bias = c->d_bias[s]; pl[s].scal = c->d_scal[s]; pl[s].out = c->packed[s];
+            const StagePlan& p = c->tb->plan[s];
+            pl[s].steps = c->tb->d_steps[s]; pl[s].bias = c->tb->d_bias[s]; pl[s].scal = c->tb->d_scal[s]; pl[s].out = c->packed[s];
             pl[s].n_groups = p.n_groups(); pl[s].n_bias = (int)p.bias.size(); pl[s].n_scal = (int)p.scal.size(); pl[s].block0 = blocks;
             blocks += (p.packed_floats() + 255) / 256;
         }
-        HIP_TRY(gmalloc(&c->d_packplans, sizeof(PackPlan) * NPLAN));
-        HIP_TRY(hipMemcpy(c->d_packplans, pl.data(), sizeof(PackPlan) * NPLAN, hipMemcpyHostToDevice));
+        GENIE_TRY(dev_upload(c->d_packplans, pl));
         c->pack_blocks = blocks;
     }
-    k_pack_all<<<c->pack_blocks, 256, 0, st>>>(c->raw, (const PackPlan*)c->d_packplans, NPLAN);
-    k_pack_h2<<<(H2_FRAGS * 64 + H2_NBIAS * 32 + 16 + 255) / 256, 256, 0, st>>>(c->raw, c->d_h2tbl, c->packed_h2, H2_FRAGS,
+    k_pack_all<<<c->pack_blocks, 256, 0, st>>>(c->raw, c->d_packplans, NPLAN);
+    k_pack_h2<<<(H2_FRAGS * 64 + H2_NBIAS * 32 + 16 + 255) / 256, 256, 0, st>>>(c->raw, c->tb->d_h2tbl, c->packed_h2, H2_FRAGS,
                                                                                H2_NBIAS * 32 + 16);
-    k_pack_h2<<<(S2H_FRAGS * 64 + 32 + 16 + 255) / 256, 256, 0, st>>>(c->raw, c->d_s2htbl, c->packed_s2h, S2H_FRAGS, 32 + 16);
+    k_pack_h2<<<(S2H_FRAGS * 64 + 32 + 16 + 255) / 256, 256, 0, st>>>(c->raw, c->tb->d_s2htbl, c->packed_s2h, S2H_FRAGS, 32 + 16);
     if (c->has_edges) {
         const long long ns = edge_rows_sta(c), ng = edge_rows_src(c);
         k_edge_bias<<<(unsigned)((ns * 48 + 255) / 256), 256, 0, st>>>(c->raw, g_params[W_DA_L1T12_P].off, g_params[W_DA_L2T12_P].off,
@@ -1486,7 +1534,7 @@ int ensure_packed(genie_ctx* c, hipStream_t st) {
         k_edge_bias<<<(unsigned)((ng * 48 + 255) / 256), 256, 0, st>>>(c->raw, g_params[W_DA_L1T22_P].off, g_params[W_DA_L2T22_P].off,
                                                                       c->mpos_src, (int)ng, c->ebias_src);
         if (c->sta_perm) {
-            if (!c->ebias_sta_p) HIP_TRY(gmalloc((void**)&c->ebias_sta_p, sizeof(float) * 48 * (size_t)c->S));
+            if (!c->ebias_sta_p) HIP_TRY(c->ebias_sta_p.alloc(48 * (size_t)c->S));
             k_permute_sta_rows<<<(c->S * 48 + 255) / 256, 256, 0, st>>>(c->ebias_sta, c->S, 48, c->sta_inv, c->S, c->ebias_sta_p);
         }
     }
@@ -1569,7 +1617,7 @@ DaArgs make_da_args(const genie_ctx* c, const StageCall& call, float* ws) {
 }
 
 // gradient maps of the three backward passes: accumulator / vector / scalar k of pass s -> entries of the gradient blob
-int build_grad_maps(genie_ctx* c) {
+int build_grad_maps(ModelTables* tb) {
     std::vector<AccDesc> acc[3];
     std::vector<VecDesc> vec[3];
     std::vector<int32_t> sc[3];
@@ -1626,13 +1674,10 @@ int build_grad_maps(genie_ctx* c) {
     for (int s = 0; s < 3; ++s) {
         if ((int)acc[s].size() != want_acc[s] || (int)vec[s].size() != want_vec[s])
             return fail(GENIE_ERR_STATE, "internal: gradient maps do not match the backward kernels");
-        c->n_acc[s] = (int)acc[s].size(); c->n_vec[s] = (int)vec[s].size(); c->n_sc[s] = (int)sc[s].size();
-        HIP_TRY(gmalloc((void**)&c->d_acc[s], sizeof(AccDesc) * acc[s].size()));
-        HIP_TRY(hipMemcpy(c->d_acc[s], acc[s].data(), sizeof(AccDesc) * acc[s].size(), hipMemcpyHostToDevice));
-        HIP_TRY(gmalloc((void**)&c->d_vec[s], sizeof(VecDesc) * vec[s].size()));
-        HIP_TRY(hipMemcpy(c->d_vec[s], vec[s].data(), sizeof(VecDesc) * vec[s].size(), hipMemcpyHostToDevice));
-        HIP_TRY(gmalloc((void**)&c->d_sc[s], sizeof(int32_t) * sc[s].size()));
-        HIP_TRY(hipMemcpy(c->d_sc[s], sc[s].data(), sizeof(int32_t) * sc[s].size(), hipMemcpyHostToDevice));
+        tb->n_acc[s] = (int)acc[s].size(); tb->n_vec[s] = (int)vec[s].size(); tb->n_sc[s] = (int)sc[s].size();
+        GENIE_TRY(dev_upload(tb->d_acc[s], acc[s]));
+        GENIE_TRY(dev_upload(tb->d_vec[s], vec[s]));
+        GENIE_TRY(dev_upload(tb->d_sc[s], sc[s]));
     }
     return GENIE_OK;
 }
@@ -1759,7 +1804,7 @@ void build_tail_train_plans(StagePlan* plan) {
 
 // gradient maps of the tail's backward kernels (accumulator / vector / scalar k of kernel TM_* -> entries of the gradient blob;
 // the d(temporal query) blocks land behind the blob, at g_raw_total)
-int build_tail_grad_maps(genie_ctx* c) {
+int build_tail_grad_maps(ModelTables* tb) {
     std::vector<AccDesc> acc[NTM];
     std::vector<VecDesc> vec[NTM];
     std::vector<int32_t> sc[NTM];
@@ -1933,21 +1978,16 @@ int build_tail_grad_maps(genie_ctx* c) {
     for (int s = TM_RO0; s < NTM; ++s) {
         if ((int)acc[s].size() != want_acc[s] || (int)vec[s].size() != want_vec[s] || sc[s].size() > 16)
             return fail(GENIE_ERR_STATE, "internal: tail gradient maps do not match the backward kernels");
-        c->n_acc[s] = (int)acc[s].size(); c->n_vec[s] = (int)vec[s].size(); c->n_sc[s] = (int)sc[s].size();
-        HIP_TRY(gmalloc((void**)&c->d_acc[s], sizeof(AccDesc) * std::max<size_t>(1, acc[s].size())));
-        if (!acc[s].empty()) HIP_TRY(hipMemcpy(c->d_acc[s], acc[s].data(), sizeof(AccDesc) * acc[s].size(), hipMemcpyHostToDevice));
-        HIP_TRY(gmalloc((void**)&c->d_vec[s], sizeof(VecDesc) * std::max<size_t>(1, vec[s].size())));
-        if (!vec[s].empty()) HIP_TRY(hipMemcpy(c->d_vec[s], vec[s].data(), sizeof(VecDesc) * vec[s].size(), hipMemcpyHostToDevice));
-        HIP_TRY(gmalloc((void**)&c->d_sc[s], sizeof(int32_t) * std::max<size_t>(1, sc[s].size())));
-        if (!sc[s].empty()) HIP_TRY(hipMemcpy(c->d_sc[s], sc[s].data(), sizeof(int32_t) * sc[s].size(), hipMemcpyHostToDevice));
+        tb->n_acc[s] = (int)acc[s].size(); tb->n_vec[s] = (int)vec[s].size(); tb->n_sc[s] = (int)sc[s].size();
+        GENIE_TRY(dev_upload(tb->d_acc[s], acc[s]));
+        GENIE_TRY(dev_upload(tb->d_vec[s], vec[s]));
+        GENIE_TRY(dev_upload(tb->d_sc[s], sc[s]));
     }
     return GENIE_OK;
 }
 
-struct CtxGuard {            // destroys a partially built context on every early return of the create calls
-    genie_ctx* c;
-    ~CtxGuard() { if (c) genie_ctx_destroy(c); }
-};
+struct CtxDeleter { void operator()(genie_ctx* c) const { (void)genie_ctx_destroy(c); } };
+using CtxGuard = std::unique_ptr<genie_ctx, CtxDeleter>;      // destroys a partially built context on every early return of the create calls
 
 // workgroups (4 waves x 16 nodes) of an MFMA tail kernel over n nodes, at most `cap`
 int tl_blocks(long long n, int cap) { return (int)std::max<long long>(1, std::min<long long>((n + 63) / 64, cap)); }
@@ -1963,68 +2003,57 @@ int check_ws(const genie_ctx* c, const void* ws) {
 
 
 namespace {
-// The tables of a context that do not depend on its graph or its weights -- the stage plans (host), their step / bias / scalar descriptors,
-// the gradient maps of the backward passes and the source tables of the f16x2 weight images (device) -- are built ONCE per device and
-// process on a template context that is never destroyed; every context points at them (`tables_shared`). Building them per context was
-// ~45 blocking host-to-device copies = most of the 2.4 ms genie_ctx_create cost per training sample (train_GENIE_model.py:1722-1786).
-int init_model_tables(genie_ctx* c) {
-    build_plans(c->plan[0], c->plan[1]);
-    build_assoc_plans(c->plan[2], c->plan[3]);
-    build_train_plans(c->plan[4], c->plan[5], c->plan[6]);
-    build_tail_plans(c->plan);
-    build_tail_train_plans(c->plan);
-    if (c->plan[PL_TRO0].n_groups() != GTR_GROUPS || c->plan[PL_TRO1].n_groups() != GTR_GROUPS || c->plan[PL_TSN].n_groups() != GTN_GROUPS ||
-        c->plan[PL_TSA1].n_groups() != GTS_GROUPS || c->plan[PL_TSA3].n_groups() != GTS_GROUPS || c->plan[PL_TBIP].n_groups() != GTB_GROUPS ||
-        c->plan[PL_TAB2].n_groups() != GT1_GROUPS || c->plan[PL_TAB1].n_groups() != GA1_GROUPS || c->plan[PL_TAB0].n_groups() != GA0_GROUPS ||
-        c->plan[PL_TAG].n_groups() != GAG_GROUPS || c->plan[PL_TLSP].n_groups() != GLT_GROUPS || c->plan[PL_TLSS].n_groups() != GLT_GROUPS ||
-        c->plan[PL_TARR].n_groups() != GTA_GROUPS)
+// fills the ModelTables of the current device
+int init_model_tables(ModelTables* tb) {
+    build_plans(tb->plan[PL_S1], tb->plan[PL_S2]);
+    build_assoc_plans(tb->plan[PL_ASA], tb->plan[PL_ASB]);
+    build_train_plans(tb->plan[PL_B2], tb->plan[PL_B1], tb->plan[PL_B0]);
+    build_tail_plans(tb->plan);
+    build_tail_train_plans(tb->plan);
+    if (tb->plan[PL_TRO0].n_groups() != GTR_GROUPS || tb->plan[PL_TRO1].n_groups() != GTR_GROUPS || tb->plan[PL_TSN].n_groups() != GTN_GROUPS ||
+        tb->plan[PL_TSA1].n_groups() != GTS_GROUPS || tb->plan[PL_TSA3].n_groups() != GTS_GROUPS || tb->plan[PL_TBIP].n_groups() != GTB_GROUPS ||
+        tb->plan[PL_TAB2].n_groups() != GT1_GROUPS || tb->plan[PL_TAB1].n_groups() != GA1_GROUPS || tb->plan[PL_TAB0].n_groups() != GA0_GROUPS ||
+        tb->plan[PL_TAG].n_groups() != GAG_GROUPS || tb->plan[PL_TLSP].n_groups() != GLT_GROUPS || tb->plan[PL_TLSS].n_groups() != GLT_GROUPS ||
+        tb->plan[PL_TARR].n_groups() != GTA_GROUPS)
         return fail(GENIE_ERR_STATE, "internal: transposed tail plan does not match kernel group maps");
-    if (c->plan[PL_RO0].n_groups() != GR_GROUPS || c->plan[PL_RO1].n_groups() != GR_GROUPS || (int)c->plan[PL_RO0].bias.size() != GR_BIAS ||
-        (int)c->plan[PL_RO1].bias.size() != GR_BIAS || c->plan[PL_ROP].n_groups() != GP_GROUPS || (int)c->plan[PL_ROP].bias.size() != GP_BIAS ||
-        c->plan[PL_SA1].n_groups() != GS_GROUPS || c->plan[PL_SA2].n_groups() != GS_GROUPS || c->plan[PL_SA3].n_groups() != GS_GROUPS ||
-        (int)c->plan[PL_SA1].bias.size() != GS_BIAS || (int)c->plan[PL_SA3].bias.size() != GS_BIAS || c->plan[PL_BIP].n_groups() != GB_GROUPS2)
+    if (tb->plan[PL_RO0].n_groups() != GR_GROUPS || tb->plan[PL_RO1].n_groups() != GR_GROUPS || (int)tb->plan[PL_RO0].bias.size() != GR_BIAS ||
+        (int)tb->plan[PL_RO1].bias.size() != GR_BIAS || tb->plan[PL_ROP].n_groups() != GP_GROUPS || (int)tb->plan[PL_ROP].bias.size() != GP_BIAS ||
+        tb->plan[PL_SA1].n_groups() != GS_GROUPS || tb->plan[PL_SA2].n_groups() != GS_GROUPS || tb->plan[PL_SA3].n_groups() != GS_GROUPS ||
+        (int)tb->plan[PL_SA1].bias.size() != GS_BIAS || (int)tb->plan[PL_SA3].bias.size() != GS_BIAS || tb->plan[PL_BIP].n_groups() != GB_GROUPS2)
         return fail(GENIE_ERR_STATE, "internal: tail plan does not match kernel group maps");
-    if (c->plan[4].n_groups() != GT2_GROUPS || c->plan[5].n_groups() != GT1_GROUPS || c->plan[6].n_groups() != GT0_GROUPS)
+    if (tb->plan[PL_B2].n_groups() != GT2_GROUPS || tb->plan[PL_B1].n_groups() != GT1_GROUPS || tb->plan[PL_B0].n_groups() != GT0_GROUPS)
         return fail(GENIE_ERR_STATE, "internal: backward plan does not match kernel group maps");
-    { int rc_tr; if ((rc_tr = build_grad_maps(c))) return rc_tr; if ((rc_tr = build_tail_grad_maps(c))) return rc_tr; }
-    if (c->plan[0].n_groups() != G1_GROUPS || c->plan[1].n_groups() != G2_GROUPS ||
-        (int)c->plan[0].bias.size() != G1_BIAS || (int)c->plan[1].bias.size() != G2_BIAS ||
-        c->plan[2].n_groups() != GA_GROUPS || c->plan[3].n_groups() != GB_GROUPS ||
-        (int)c->plan[2].bias.size() != GA_BIAS || (int)c->plan[3].bias.size() != GB_BIAS)
+    GENIE_TRY(build_grad_maps(tb));
+    GENIE_TRY(build_tail_grad_maps(tb));
+    if (tb->plan[PL_S1].n_groups() != G1_GROUPS || tb->plan[PL_S2].n_groups() != G2_GROUPS ||
+        (int)tb->plan[PL_S1].bias.size() != G1_BIAS || (int)tb->plan[PL_S2].bias.size() != G2_BIAS ||
+        tb->plan[PL_ASA].n_groups() != GA_GROUPS || tb->plan[PL_ASB].n_groups() != GB_GROUPS ||
+        (int)tb->plan[PL_ASA].bias.size() != GA_BIAS || (int)tb->plan[PL_ASB].bias.size() != GB_BIAS)
         return fail(GENIE_ERR_STATE, "internal: stage plan does not match kernel group maps");
     for (int s = 0; s < NPLAN; ++s) {
-        const StagePlan& p = c->plan[s];
-        HIP_TRY(hipMalloc((void**)&c->d_steps[s], sizeof(StepDesc) * p.steps.size()));
-        HIP_TRY(hipMemcpy(c->d_steps[s], p.steps.data(), sizeof(StepDesc) * p.steps.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc((void**)&c->d_bias[s], sizeof(BiasDesc) * std::max<size_t>(1, p.bias.size())));
-        if (!p.bias.empty()) HIP_TRY(hipMemcpy(c->d_bias[s], p.bias.data(), sizeof(BiasDesc) * p.bias.size(), hipMemcpyHostToDevice));
-        HIP_TRY(hipMalloc((void**)&c->d_scal[s], sizeof(int32_t) * 16));
-        HIP_TRY(hipMemcpy(c->d_scal[s], p.scal.data(), sizeof(int32_t) * p.scal.size(), hipMemcpyHostToDevice));
+        const StagePlan& p = tb->plan[s];
+        GENIE_TRY(dev_upload(tb->d_steps[s], p.steps));
+        GENIE_TRY(dev_upload(tb->d_bias[s], p.bias));
+        GENIE_TRY(dev_upload(tb->d_scal[s], p.scal));
     }
-    {
-        std::vector<int32_t> tbl;
-        build_h2_table(tbl);
-        HIP_TRY(hipMalloc((void**)&c->d_h2tbl, sizeof(int32_t) * tbl.size()));
-        HIP_TRY(hipMemcpy(c->d_h2tbl, tbl.data(), sizeof(int32_t) * tbl.size(), hipMemcpyHostToDevice));
-        build_s2h_table(tbl);
-        HIP_TRY(hipMalloc((void**)&c->d_s2htbl, sizeof(int32_t) * tbl.size()));
-        HIP_TRY(hipMemcpy(c->d_s2htbl, tbl.data(), sizeof(int32_t) * tbl.size(), hipMemcpyHostToDevice));
-    }
-    return GENIE_OK;
+    std::vector<int32_t> tbl;
+    build_h2_table(tbl);
+    GENIE_TRY(dev_upload(tb->d_h2tbl, tbl));
+    build_s2h_table(tbl);
+    return dev_upload(tb->d_s2htbl, tbl);
 }
 
-int model_tables(genie_ctx** out) {
-    static std::map<int, genie_ctx*> tmpl;
+int model_tables(const ModelTables** out) {
+    static std::map<int, const ModelTables*> tables;      // never destroyed (the pool's own maps may go first at process exit)
     static std::mutex mu;
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(mu);
-    auto it = tmpl.find(dev);
-    if (it == tmpl.end()) {
-        genie_ctx* t = new genie_ctx();
-        int rc = init_model_tables(t);
-        if (rc) return rc;              // (the half-built template leaks a few KB; the process cannot create contexts anyway)
-        it = tmpl.emplace(dev, t).first;
+    auto it = tables.find(dev);
+    if (it == tables.end()) {
+        std::unique_ptr<ModelTables> t(new ModelTables());
+        GENIE_TRY(init_model_tables(t.get()));
+        it = tables.emplace(dev, t.release()).first;
     }
     *out = it->second;
     return GENIE_OK;
@@ -2048,9 +2077,8 @@ int genie_ctx_create(genie_ctx** out, int n_sta, int n_grid, int n_grid_ext, con
     *out = nullptr;
     if (n_sta < 1 || n_grid < 1 || n_grid_ext < n_grid) return fail(GENIE_ERR_ARG, "bad n_sta / n_grid / n_grid_ext");
     if (!sta_rowptr || !src_rowptr) return fail(GENIE_ERR_ARG, "null rowptr");
-    genie_ctx* c = new genie_ctx();      // value-initialised: every pointer member starts null
-    CtxGuard guard{c};                   // every early return below destroys the partially built context
-    memset((void*)&c->S, 0, sizeof(int) * 4);
+    CtxGuard guard(new genie_ctx());     // value-initialised: every member starts null / zero / false, every DevBuf empty;
+    genie_ctx* c = guard.get();          // every early return below destroys the partially built context
     c->S = n_sta; c->G = n_grid; c->G_ext = n_grid_ext; c->T = (n_sta + 15) / 16;
     c->scale_rel = scale_rel;
     c->scale_t = 9.0f;  // 3 * kernel_sig_t (module.py:40, train_config.yaml:17); override with genie_set_scale_t
@@ -2073,59 +2101,32 @@ int genie_ctx_create(genie_ctx** out, int n_sta, int n_grid, int n_grid_ext, con
         c->ks_uni = uniform(sta_rowptr, n_sta);
         c->kp_uni = uniform(src_rowptr, n_grid);
     }
-    int rc;
-    if ((rc = dev_copy(&c->sta_rowptr, sta_rowptr, (size_t)n_sta + 1))) return rc;
-    if ((rc = dev_copy(&c->sta_col, sta_col, (size_t)e_sta))) return rc;
-    if ((rc = dev_copy(&c->src_rowptr, src_rowptr, (size_t)n_grid + 1))) return rc;
-    if ((rc = dev_copy(&c->src_col, src_col, (size_t)e_src))) return rc;
+    GENIE_TRY(dev_copy(c->sta_rowptr, sta_rowptr, (size_t)n_sta + 1));
+    GENIE_TRY(dev_copy(c->sta_col, sta_col, (size_t)e_sta));
+    GENIE_TRY(dev_copy(c->src_rowptr, src_rowptr, (size_t)n_grid + 1));
+    GENIE_TRY(dev_copy(c->src_col, src_col, (size_t)e_src));
     if (grid_order) {
-        if ((rc = dev_copy(&c->order, grid_order, (size_t)n_grid))) return rc;
+        GENIE_TRY(dev_copy(c->order, grid_order, (size_t)n_grid));
     } else {
         std::vector<int32_t> id(n_grid);
         for (int i = 0; i < n_grid; ++i) id[i] = i;
-        HIP_TRY(gmalloc((void**)&c->order, sizeof(int32_t) * n_grid));
-        HIP_TRY(hipMemcpy(c->order, id.data(), sizeof(int32_t) * n_grid, hipMemcpyHostToDevice));
+        GENIE_TRY(dev_upload(c->order, id));
     }
-    HIP_TRY(gmalloc((void**)&c->outdeg, sizeof(int32_t) * (size_t)n_grid_ext));
+    HIP_TRY(c->outdeg.alloc((size_t)n_grid_ext));
     HIP_TRY(hipMemset(c->outdeg, 0, sizeof(int32_t) * (size_t)n_grid_ext));
     if (e_src > 0) k_outdeg<<<(e_src + 255) / 256, 256>>>(c->src_col, e_src, c->outdeg);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(gmalloc((void**)&c->raw, sizeof(float) * g_raw_total));
+    HIP_TRY(c->raw.alloc(g_raw_total));
     HIP_TRY(hipMemset(c->raw, 0, sizeof(float) * g_raw_total));
-    {   // graph- and weight-independent tables: shared with the device's template context (model_tables)
-        genie_ctx* tm = nullptr;
-        if ((rc = model_tables(&tm))) return rc;
-        for (int s = 0; s < NPLAN; ++s) {
-            c->plan[s] = tm->plan[s];
-            c->d_steps[s] = tm->d_steps[s]; c->d_bias[s] = tm->d_bias[s]; c->d_scal[s] = tm->d_scal[s];
-            HIP_TRY(gmalloc((void**)&c->packed[s], sizeof(float) * c->plan[s].packed_floats()));
-        }
-        for (int s = 0; s < NTM; ++s) {
-            c->d_acc[s] = tm->d_acc[s]; c->d_vec[s] = tm->d_vec[s]; c->d_sc[s] = tm->d_sc[s];
-            c->n_acc[s] = tm->n_acc[s]; c->n_vec[s] = tm->n_vec[s]; c->n_sc[s] = tm->n_sc[s];
-        }
-        c->d_h2tbl = tm->d_h2tbl; c->d_s2htbl = tm->d_s2htbl;
-        c->tables_shared = true;
-        HIP_TRY(gmalloc((void**)&c->packed_h2, sizeof(float) * H2_IMG_FLOATS));
-        HIP_TRY(gmalloc((void**)&c->packed_s2h, sizeof(float) * S2H_IMG_FLOATS));
-        HIP_TRY(gmalloc((void**)&c->d_range, sizeof(float) * (4 + 4 * RG_PART)));
-        HIP_TRY(hipHostMalloc((void**)&c->h_range, sizeof(float) * 4));
-        HIP_TRY(hipHostMalloc((void**)&c->h_inflag, 64, hipHostMallocMapped));
-        c->h_inflag[0] = 0u; c->h_inflag[1] = 0u;
-        c->range_ok = true; c->prec_mode = 0;
-    }
-    c->mpos_sta = c->mpos_src = c->ebias_sta = c->ebias_src = nullptr;
-    c->has_edges = false;
-    c->xs_slice = c->xs_mask = nullptr; c->xs_ws = nullptr; c->xs_mm_copy = 0;
-    c->abs_sta = c->abs_src = nullptr; c->abs_ts = c->abs_tg = nullptr; c->abs_dirty = false; c->abs_ts_order = 0;
-    c->r_sta_rowptr = c->r_sta_col = c->r_src_rowptr = c->r_src_col = nullptr;
-    c->sta_perm = c->sta_inv = c->sta_rowptr_p = c->sta_col_p = nullptr; c->ebias_sta_p = nullptr; c->sta_ident = nullptr;
-    c->ea_int = c->ea_tmp = nullptr; c->ea_user = nullptr;
-    c->r_sta_w = c->r_src_w = nullptr; c->r_sta_cw = c->r_src_cw = nullptr;
-    c->rp_sta_rowptr = c->rp_src_rowptr = nullptr; c->rp_sta_cw = c->rp_src_cw = nullptr; c->ptile16 = c->ptile32 = nullptr;
-    c->pcsr = false; c->pcsr_h2 = false;
-    c->p_sta_rowptr = c->p_sta_col = c->p_src_rowptr = c->p_src_col = c->seg_rowptr = nullptr;
-    c->src_tab = nullptr;
+    GENIE_TRY(model_tables(&c->tb));     // graph- and weight-independent tables: the device's, shared
+    for (int s = 0; s < NPLAN; ++s) HIP_TRY(c->packed[s].alloc(c->tb->plan[s].packed_floats()));
+    HIP_TRY(c->packed_h2.alloc(H2_IMG_FLOATS));
+    HIP_TRY(c->packed_s2h.alloc(S2H_IMG_FLOATS));
+    HIP_TRY(c->d_range.alloc(4 + 4 * RG_PART));
+    HIP_TRY(hipHostMalloc((void**)&c->h_range, sizeof(float) * 4));
+    HIP_TRY(hipHostMalloc((void**)&c->h_inflag, 64, hipHostMallocMapped));
+    c->h_inflag[0] = 0u; c->h_inflag[1] = 0u;
+    c->range_ok = true;
     if (c->kp_uni == 15) {
         std::vector<int32_t> ord(n_grid), col((size_t)e_src), tab((size_t)n_grid * 16);
         HIP_TRY(hipMemcpy(ord.data(), c->order, sizeof(int32_t) * n_grid, hipMemcpyDeviceToHost));
@@ -2136,9 +2137,8 @@ int genie_ctx_create(genie_ctx** out, int n_sta, int n_grid, int n_grid_ext, con
             tab[(size_t)gi * 16] = gg;
             for (int k = 0; k < 15; ++k) tab[(size_t)gi * 16 + 1 + k] = col[(size_t)gg * 15 + k];
         }
-        HIP_TRY(gmalloc((void**)&c->src_tab, sizeof(int32_t) * tab.size()));
-        HIP_TRY(hipMemcpy(c->src_tab, tab.data(), sizeof(int32_t) * tab.size(), hipMemcpyHostToDevice));
-        c->tab_host = tab;
+        GENIE_TRY(dev_upload(c->src_tab, tab));
+        c->tab_host = std::move(tab);
     }
     c->dirty = true;
     int dev = 0;
@@ -2202,8 +2202,7 @@ int genie_ctx_create(genie_ctx** out, int n_sta, int n_grid, int n_grid_ext, con
     }
     layout_ws(c);
     HIP_TRY(hipDeviceSynchronize());
-    guard.c = nullptr;
-    *out = c;
+    *out = guard.release();
     return GENIE_OK;
 }
 
@@ -2215,15 +2214,14 @@ int genie_ctx_create_subgraph(genie_ctx** out, int n_sta, int n_grid, int64_t n_
     *out = nullptr;
     if (n_prod < 1 || n_prod >= (1ll << 31)) return fail(GENIE_ERR_ARG, "genie_ctx_create_subgraph: bad n_prod");
     if (!p_sta_rowptr || !p_src_rowptr || !seg_rowptr) return fail(GENIE_ERR_ARG, "genie_ctx_create_subgraph: null rowptr");
-    int32_t* zeros = nullptr;       // empty base station graph: the station edges live in the product-level CSR
-    HIP_TRY(gmalloc((void**)&zeros, sizeof(int32_t) * ((size_t)n_sta + 1)));
     genie_ctx* c = nullptr;
-    int rc = hipMemset(zeros, 0, sizeof(int32_t) * ((size_t)n_sta + 1)) == hipSuccess
-                 ? genie_ctx_create(&c, n_sta, n_grid, n_grid, zeros, nullptr, src_rowptr, src_col, grid_order, scale_rel)
-                 : fail(GENIE_ERR_HIP, "genie_ctx_create_subgraph: hipMemset failed");
-    (void)gfree(zeros);
-    if (rc) return rc;
-    CtxGuard guard{c};
+    {   // empty base station graph: the station edges live in the product-level CSR (genie_ctx_create copies it and drains the device)
+        DevBuf<int32_t> zeros;
+        HIP_TRY(zeros.alloc((size_t)n_sta + 1));
+        HIP_TRY(hipMemset(zeros, 0, sizeof(int32_t) * ((size_t)n_sta + 1)));
+        GENIE_TRY(genie_ctx_create(&c, n_sta, n_grid, n_grid, zeros, nullptr, src_rowptr, src_col, grid_order, scale_rel));
+    }
+    CtxGuard guard(c);
     int32_t e1 = 0, e2 = 0, last = 0;
     HIP_TRY(hipMemcpy(&e1, p_sta_rowptr + n_prod, sizeof(int32_t), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(&e2, p_src_rowptr + n_prod, sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -2231,11 +2229,11 @@ int genie_ctx_create_subgraph(genie_ctx** out, int n_sta, int n_grid, int64_t n_
     if (e1 < 0 || e2 < 0 || last != (int32_t)n_prod || (e1 > 0 && !p_sta_col) || (e2 > 0 && !p_src_col)) {
         return fail(GENIE_ERR_ARG, "genie_ctx_create_subgraph: inconsistent CSR arrays (seg_rowptr[n_grid] must equal n_prod)");
     }
-    if ((rc = dev_copy(&c->p_sta_rowptr, p_sta_rowptr, (size_t)n_prod + 1)) || (rc = dev_copy(&c->p_sta_col, p_sta_col, (size_t)e1)) ||
-        (rc = dev_copy(&c->p_src_rowptr, p_src_rowptr, (size_t)n_prod + 1)) || (rc = dev_copy(&c->p_src_col, p_src_col, (size_t)e2)) ||
-        (rc = dev_copy(&c->seg_rowptr, seg_rowptr, (size_t)n_grid + 1))) {
-        return rc;
-    }
+    GENIE_TRY(dev_copy(c->p_sta_rowptr, p_sta_rowptr, (size_t)n_prod + 1));
+    GENIE_TRY(dev_copy(c->p_sta_col, p_sta_col, (size_t)e1));
+    GENIE_TRY(dev_copy(c->p_src_rowptr, p_src_rowptr, (size_t)n_prod + 1));
+    GENIE_TRY(dev_copy(c->p_src_col, p_src_col, (size_t)e2));
+    GENIE_TRY(dev_copy(c->seg_rowptr, seg_rowptr, (size_t)n_grid + 1));
     c->pcsr = true;
     c->P = c->P_ext = n_prod;
     {   // the f16x2 stage-1 kernel unrolls 8 station + 15 source neighbour slots per node: enough for every induced subgraph of
@@ -2261,16 +2259,13 @@ int genie_ctx_create_subgraph(genie_ctx** out, int n_sta, int n_grid, int64_t n_
             std::vector<int32_t> t((size_t)nt);
             for (int i = 0; i < nt; ++i) t[i] = i;
             std::stable_sort(t.begin(), t.end(), [&](int32_t x, int32_t y) { return rank[src_of[(size_t)x * w]] < rank[src_of[(size_t)y * w]]; });
-            int32_t** dst = w == 16 ? &c->ptile16 : &c->ptile32;
-            HIP_TRY(gmalloc((void**)dst, sizeof(int32_t) * (size_t)std::max(nt, 1)));
-            HIP_TRY(hipMemcpy(*dst, t.data(), sizeof(int32_t) * (size_t)nt, hipMemcpyHostToDevice));
+            GENIE_TRY(dev_upload(w == 16 ? c->ptile16 : c->ptile32, t));
         }
     }
     c->use_fast = c->use_h2 = 0;
     c->ks_uni = c->kp_uni = -1;
     layout_ws(c);
-    guard.c = nullptr;
-    *out = c;
+    *out = guard.release();
     return GENIE_OK;
 }
 
@@ -2278,16 +2273,17 @@ int genie_set_absolute_pos(genie_ctx* c, const float* pos_sta, const float* pos_
     if (!c) return fail(GENIE_ERR_ARG, "genie_set_absolute_pos: null context");
     if (!pos_sta || !pos_src) {
         (void)hipDeviceSynchronize();        // pooled blocks are reused without the driver's implicit drain
-        (void)gfree(c->abs_sta); (void)gfree(c->abs_src); (void)gfree(c->abs_ts); (void)gfree(c->abs_tg);
-        c->abs_sta = c->abs_src = nullptr; c->abs_ts = c->abs_tg = nullptr;
+        c->abs_sta.reset(); c->abs_src.reset(); c->abs_ts.reset(); c->abs_tg.reset();
         return GENIE_OK;
     }
     // irregular product graph: both arguments are [n_prod, 3] (the station's / the source node's position of every product node) and the
     // tables are per product node: a neighbour (a product-node id) is looked up like the node itself
     const long long ns = c->pcsr ? c->P : c->S, ng = c->pcsr ? c->P : c->G_ext;
-    if (!c->abs_sta) {
-        HIP_TRY(gmalloc((void**)&c->abs_sta, sizeof(float) * 4 * (size_t)ns));
-        HIP_TRY(gmalloc((void**)&c->abs_src, sizeof(float) * 4 * (size_t)ng));
+    if (!c->abs_sta) {      // both tables or neither: abs_sta != null means "on"
+        DevBuf<float> sta, src;
+        HIP_TRY(sta.alloc(4 * (size_t)ns));
+        HIP_TRY(src.alloc(4 * (size_t)ng));
+        c->abs_sta = std::move(sta); c->abs_src = std::move(src);
     }
     const float inv = 1.f / (3.f * c->scale_rel);
     hipStream_t st = (hipStream_t)stream;
@@ -2309,11 +2305,13 @@ int genie_set_edge_features(genie_ctx* c, const float* pos_sta, const float* pos
     // irregular product graph: the mean runs over the PRESENT neighbours of a product node, so both tables are per product node and the
     // positions arrive per product node too ([n_prod, 3]: the station's, the source node's)
     const long long ns = edge_rows_sta(c), ng = edge_rows_src(c);
-    if (!c->mpos_sta) {
-        HIP_TRY(gmalloc((void**)&c->mpos_sta, sizeof(float) * 4 * (size_t)ns));
-        HIP_TRY(gmalloc((void**)&c->mpos_src, sizeof(float) * 4 * (size_t)ng));
-        HIP_TRY(gmalloc((void**)&c->ebias_sta, sizeof(float) * 48 * (size_t)ns));
-        HIP_TRY(gmalloc((void**)&c->ebias_src, sizeof(float) * 48 * (size_t)ng));
+    if (!c->mpos_sta) {     // all four tables or none
+        DevBuf<float> ms, mg, es, eg;
+        HIP_TRY(ms.alloc(4 * (size_t)ns));
+        HIP_TRY(mg.alloc(4 * (size_t)ng));
+        HIP_TRY(es.alloc(48 * (size_t)ns));
+        HIP_TRY(eg.alloc(48 * (size_t)ng));
+        c->mpos_sta = std::move(ms); c->mpos_src = std::move(mg); c->ebias_sta = std::move(es); c->ebias_src = std::move(eg);
     }
     if (c->pcsr) {
         k_edge_feat<<<(unsigned)((ns + 255) / 256), 256, 0, st>>>(c->p_sta_rowptr, c->p_sta_col, (int)ns, pos_sta, c->scale_rel, c->mpos_sta);
@@ -2336,13 +2334,11 @@ int genie_set_scale_t(genie_ctx* c, float scale_t) {
 
 int genie_set_station_order(genie_ctx* c, const int32_t* order_host) {
     if (!c) return fail(GENIE_ERR_ARG, "genie_set_station_order: null context");
-    void* old[] = {c->sta_perm, c->sta_inv, c->sta_rowptr_p, c->sta_col_p, c->ea_int, c->ea_tmp, c->ea_frag, c->ea_frag_tmp};
-    bool any_old = false;
-    for (void* q : old) any_old = any_old || q != nullptr;
-    if (any_old) (void)hipDeviceSynchronize();      // (a first call on a fresh context has nothing in flight and nothing to free)
-    for (void* q : old) (void)gfree(q);
-    c->sta_perm = c->sta_inv = c->sta_rowptr_p = c->sta_col_p = nullptr;
-    c->ea_int = c->ea_tmp = nullptr; c->ea_user = nullptr; c->ea_frag = c->ea_frag_tmp = nullptr;
+    // the old order and what was derived from it go first, whatever follows: a failure below leaves "no order installed". The four
+    // order buffers are installed together, so sta_perm stands for all of them in the drain condition
+    if (c->sta_perm || c->ea_frag || c->ea_frag_tmp) (void)hipDeviceSynchronize();      // (a first call on a fresh context has nothing in flight and nothing to free)
+    c->sta_perm.reset(); c->sta_inv.reset(); c->sta_rowptr_p.reset(); c->sta_col_p.reset();
+    c->ea_frag.reset(); c->ea_frag_tmp.reset(); c->ea_user = nullptr;
     c->xs_slice = c->xs_mask = nullptr; c->xs_ws = nullptr;      // split rows of an embedding made under the previous order are void
     c->dirty = true; c->abs_dirty = true;
     if (!order_host || c->pcsr) return GENIE_OK;
@@ -2362,14 +2358,12 @@ int genie_set_station_order(genie_ctx* c, const int32_t* order_host) {
         rpp[(size_t)i + 1] = rpp[i] + (rp[u + 1] - rp[u]);
         for (int e = rp[u]; e < rp[u + 1]; ++e) colp[(size_t)rpp[i] + (e - rp[u])] = inv[col[e]];
     }
-    HIP_TRY(gmalloc((void**)&c->sta_perm, sizeof(int32_t) * S));
-    HIP_TRY(gmalloc((void**)&c->sta_inv, sizeof(int32_t) * S));
-    HIP_TRY(gmalloc((void**)&c->sta_rowptr_p, sizeof(int32_t) * ((size_t)S + 1)));
-    HIP_TRY(gmalloc((void**)&c->sta_col_p, sizeof(int32_t) * std::max<size_t>(E, 1)));
-    HIP_TRY(hipMemcpy(c->sta_perm, perm.data(), sizeof(int32_t) * S, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->sta_inv, inv.data(), sizeof(int32_t) * S, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->sta_rowptr_p, rpp.data(), sizeof(int32_t) * rpp.size(), hipMemcpyHostToDevice));
-    if (E) HIP_TRY(hipMemcpy(c->sta_col_p, colp.data(), sizeof(int32_t) * E, hipMemcpyHostToDevice));
+    DevBuf<int32_t> d_perm, d_inv, d_rpp, d_colp;      // installed only when all four exist and are filled
+    GENIE_TRY(dev_upload(d_perm, perm));
+    GENIE_TRY(dev_upload(d_inv, inv));
+    GENIE_TRY(dev_upload(d_rpp, rpp));
+    GENIE_TRY(dev_upload(d_colp, colp));
+    c->sta_perm = std::move(d_perm); c->sta_inv = std::move(d_inv); c->sta_rowptr_p = std::move(d_rpp); c->sta_col_p = std::move(d_colp);
     return GENIE_OK;
 }
 
@@ -2379,7 +2373,7 @@ int genie_set_static_edge_attr(genie_ctx* c, const float* edge_attr, void* strea
     if (!edge_attr || !c->sta_perm || c->pcsr) return GENIE_OK;       // nothing to prepare without a station processing order
     if (!c->use_h2) return GENIE_OK;      // only k_stage2_h2u honours the station processing order in stage 2
     // k_stage2_h2u reads the static edge_attr as ready-made B fragments (32 B per product node, processing order)
-    if (!c->ea_frag) HIP_TRY(gmalloc((void**)&c->ea_frag, 32 * (size_t)c->P));
+    if (!c->ea_frag) HIP_TRY(c->ea_frag.alloc(8 * (size_t)c->P));
     k_ea_frag<<<(unsigned)((c->P + 255) / 256), 256, 0, (hipStream_t)stream>>>(edge_attr, c->P, c->S, c->sta_perm, c->ea_frag);
     HIP_TRY(hipGetLastError());
     c->ea_user = edge_attr;
@@ -2396,37 +2390,24 @@ int genie_ctx_destroy(genie_ctx* c) {
     if (!c) return GENIE_OK;
     int cur = 0;
     (void)hipGetDevice(&cur);
-    if (cur != c->device) (void)hipSetDevice(c->device);      // (a Python finaliser may run with another device current)
-    (void)hipDeviceSynchronize();        // one drain for every block below: the pool hands them out again without one
-    (void)gfree(c->d_packplans);
-    if (c->tables_shared) {
-        for (int s = 0; s < NPLAN; ++s) c->d_steps[s] = nullptr, c->d_bias[s] = nullptr, c->d_scal[s] = nullptr;
-        for (int s = 0; s < NTM; ++s) c->d_acc[s] = nullptr, c->d_vec[s] = nullptr, c->d_sc[s] = nullptr;
-        c->d_h2tbl = c->d_s2htbl = nullptr;
-    }
-    for (int s = 7; s < NPLAN; ++s) { (void)gfree(c->d_steps[s]); (void)gfree(c->d_bias[s]); (void)gfree(c->d_scal[s]); (void)gfree(c->packed[s]); }
-    for (int s = 3; s < NTM; ++s) { (void)gfree(c->d_acc[s]); (void)gfree(c->d_vec[s]); (void)gfree(c->d_sc[s]); }
-    void* ptrs[] = {c->sta_rowptr, c->sta_col, c->src_rowptr, c->src_col, c->order, c->outdeg, c->raw,
-                    c->d_steps[0], c->d_steps[1], c->d_bias[0], c->d_bias[1],
-                    c->d_scal[0], c->d_scal[1], c->packed[0], c->packed[1],
-                    c->d_steps[2], c->d_steps[3], c->d_bias[2], c->d_bias[3], c->d_scal[2], c->d_scal[3], c->packed[2], c->packed[3],
-                    c->d_steps[4], c->d_steps[5], c->d_steps[6], c->d_bias[4], c->d_bias[5], c->d_bias[6], c->d_scal[4], c->d_scal[5],
-                    c->d_scal[6], c->packed[4], c->packed[5], c->packed[6], c->d_acc[0], c->d_acc[1], c->d_acc[2], c->d_vec[0],
-                    c->d_vec[1], c->d_vec[2], c->d_sc[0], c->d_sc[1], c->d_sc[2],
-                    c->as_pg, c->as_ps, c->d_h2tbl, c->packed_h2, c->src_tab,
-                    c->mpos_sta, c->mpos_src, c->ebias_sta, c->ebias_src,
-                    c->p_sta_rowptr, c->p_sta_col, c->p_src_rowptr, c->p_src_col, c->seg_rowptr, c->abs_sta, c->abs_src,
-                    c->r_sta_rowptr, c->r_sta_col, c->r_src_rowptr, c->r_src_col, c->r_sta_w, c->r_src_w, c->r_sta_cw, c->r_src_cw, c->rp_sta_rowptr, c->rp_src_rowptr, c->rp_sta_cw, c->rp_src_cw, c->ptile16, c->ptile32,
-                    c->sta_perm, c->sta_inv, c->sta_rowptr_p, c->sta_col_p, c->ebias_sta_p, c->ea_int, c->ea_tmp, c->sta_ident,
-                    c->d_s2htbl, c->packed_s2h, c->ea_frag, c->ea_frag_tmp, c->d_range, c->abs_ts, c->abs_tg, c->p_src_of, c->p_sta_of};
-    for (void* p : ptrs) (void)gfree(p);
-    if (c->h_range) (void)hipHostFree(c->h_range);
-    if (c->h_inflag) (void)hipHostFree(c->h_inflag);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    for (auto& kv : c->s2u) { (void)gfree(kv.second.blocks); (void)gfree(kv.second.xcd0); }
-    if (cur != c->device) (void)hipSetDevice(cur);
+    const int dev = c->device;
+    if (cur != dev) (void)hipSetDevice(dev);      // (a Python finaliser may run with another device current)
+    (void)hipDeviceSynchronize();        // one drain for every block of the context: the pool hands them out again without one
     delete c;
+    if (cur != dev) (void)hipSetDevice(cur);
+    return GENIE_OK;
+}
+
+int genie_pool_stats(int device, int64_t* live_blocks, int64_t* live_bytes, int64_t* cached_bytes) {
+    std::lock_guard<std::mutex> lk(g_pool_mutex);
+    int64_t blocks = 0, bytes = 0, cached_blocks = 0, cached = 0;
+    for (const auto& kv : g_pool_blocks)
+        if (kv.second.first == device) { ++blocks; bytes += (int64_t)kv.second.second; }
+    auto it = g_pools.find(device);
+    if (it != g_pools.end()) { cached_blocks = (int64_t)it->second.free_.size(); cached = (int64_t)it->second.cached; }
+    if (live_blocks) *live_blocks = blocks - cached_blocks;
+    if (live_bytes) *live_bytes = bytes - cached;
+    if (cached_bytes) *cached_bytes = cached;
     return GENIE_OK;
 }
 
@@ -2480,6 +2461,15 @@ void launch_stage1_h2(const DaArgs& a, bool abs, bool edges, bool big, int grid,
     }
 }
 
+// the fp16 pieces of the absolute-position tables (16 B per row): both or neither
+int alloc_abs_pieces(genie_ctx* c, size_t n_sta_rows, size_t n_src_rows) {
+    DevBuf<unsigned> ts, tg;
+    HIP_TRY(ts.alloc(4 * n_sta_rows));
+    HIP_TRY(tg.alloc(4 * n_src_rows));
+    c->abs_ts = std::move(ts); c->abs_tg = std::move(tg);
+    return GENIE_OK;
+}
+
 // gi_begin / gi_end: positions of the processing order this call covers (the whole grid: 0, G); do_split: run the input
 // split pass over ALL rows (owned + halo) first -- the first range call of a window does, later ones reuse its rows
 int run_stage1(genie_ctx* c, const StageCall& call, const float* slice, const float* mask, float* dbg_h0, float* dbg_h1, void* ws,
@@ -2497,12 +2487,13 @@ int run_stage1(genie_ctx* c, const StageCall& call, const float* slice, const fl
     DaArgs a = make_da_args(c, call, (float*)ws);
     a.gi0 = gi_begin; a.G = gi_end - gi_begin;
     const long long n_tiles = (long long)a.G * c->T;
-    a.slice = slice; a.mask = mask; a.packed = c->packed[0];
+    a.slice = slice; a.mask = mask; a.packed = c->packed[PL_S1];
     a.dbg_h0 = dbg_h0; a.dbg_h1 = dbg_h1;
     c->s1_layout = r.layout;
-    float* dbg_tmp = nullptr;
+    DevBuf<float> dbg_tmp;     // kernels write it: released behind the stream synchronisation below, or on an error return, where the
+                               // failed launch means that nothing was queued on it
     if ((dbg_h0 || dbg_h1) && so) {
-        HIP_TRY(gmalloc((void**)&dbg_tmp, sizeof(float) * 90 * (size_t)c->P));
+        HIP_TRY(dbg_tmp.alloc(90 * (size_t)c->P));
         if (dbg_h0) a.dbg_h0 = dbg_tmp;
         if (dbg_h1) a.dbg_h1 = dbg_tmp + c->P * 30;
     }
@@ -2519,10 +2510,7 @@ int run_stage1(genie_ctx* c, const StageCall& call, const float* slice, const fl
         a.ptile = c->ptile32;
         if (c->abs_sta) {      // position pieces per product node (genie_set_absolute_pos on a subgraph context)
             if (c->abs_dirty || !c->abs_ts) {
-                if (!c->abs_ts) {
-                    HIP_TRY(gmalloc((void**)&c->abs_ts, 16 * (size_t)c->P));
-                    HIP_TRY(gmalloc((void**)&c->abs_tg, 16 * (size_t)c->P));
-                }
+                if (!c->abs_ts) GENIE_TRY(alloc_abs_pieces(c, (size_t)c->P, (size_t)c->P));
                 k_abs_pieces<<<(unsigned)((c->P + 255) / 256), 256, 0, st>>>(c->abs_sta, nullptr, (int)c->P, c->abs_ts);
                 k_abs_pieces<<<(unsigned)((c->P + 255) / 256), 256, 0, st>>>(c->abs_src, nullptr, (int)c->P, c->abs_tg);
                 c->abs_dirty = false; c->abs_ts_order = 0;
@@ -2568,10 +2556,7 @@ int run_stage1(genie_ctx* c, const StageCall& call, const float* slice, const fl
         if (!n_tiles) break;
         if (c->abs_sta && (c->abs_dirty || !c->abs_ts || c->abs_ts_order != (so ? 1 : 0))) {
             // (a training forward runs in the caller's station order, inference in processing order)
-            if (!c->abs_ts) {
-                HIP_TRY(gmalloc((void**)&c->abs_ts, 16 * (size_t)c->S));
-                HIP_TRY(gmalloc((void**)&c->abs_tg, 16 * (size_t)c->G_ext));
-            }
+            if (!c->abs_ts) GENIE_TRY(alloc_abs_pieces(c, (size_t)c->S, (size_t)c->G_ext));
             k_abs_pieces<<<(c->S + 255) / 256, 256, 0, st>>>(c->abs_sta, so ? c->sta_perm : nullptr, c->S, c->abs_ts);
             k_abs_pieces<<<(c->G_ext + 255) / 256, 256, 0, st>>>(c->abs_src, nullptr, c->G_ext, c->abs_tg);
             c->abs_dirty = false; c->abs_ts_order = so ? 1 : 0;
@@ -2585,8 +2570,7 @@ int run_stage1(genie_ctx* c, const StageCall& call, const float* slice, const fl
     if (dbg_tmp) {     // parity outputs were written in station processing order: back to the caller's order
         if (dbg_h0) k_permute_sta_rows<<<(unsigned)((c->P * 30 + 255) / 256), 256, 0, st>>>(dbg_tmp, c->P, 30, c->sta_perm, c->S, dbg_h0);
         if (dbg_h1) k_permute_sta_rows<<<(unsigned)((c->P * 60 + 255) / 256), 256, 0, st>>>(dbg_tmp + c->P * 30, c->P, 60, c->sta_perm, c->S, dbg_h1);
-        HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(gfree(dbg_tmp));
+        HIP_TRY(hipStreamSynchronize(st));     // ahead of dbg_tmp's scope exit: the pool hands the block out again without a drain
     }
     return GENIE_OK;
 }
@@ -2667,12 +2651,10 @@ int get_s2u_tables(genie_ctx* c, int gb0, int ge0, const genie_ctx::S2uTables** 
     }
     x0[nxc] = (int32_t)blks.size();
     genie_ctx::S2uTables t;
-    t.blocks = nullptr; t.xcd0 = nullptr; t.nblk = (int)blks.size();
-    HIP_TRY(gmalloc(&t.blocks, sizeof(S2uBlock) * std::max<size_t>(1, blks.size())));
-    HIP_TRY(hipMemcpy(t.blocks, blks.data(), sizeof(S2uBlock) * blks.size(), hipMemcpyHostToDevice));
-    HIP_TRY(gmalloc((void**)&t.xcd0, sizeof(x0)));
-    HIP_TRY(hipMemcpy(t.xcd0, x0, sizeof(x0), hipMemcpyHostToDevice));
-    *out = &(c->s2u[key] = t);
+    t.nblk = (int)blks.size();
+    GENIE_TRY(dev_upload(t.blocks, blks));
+    GENIE_TRY(dev_upload(t.xcd0, x0, (size_t)nxc + 1));
+    *out = &(c->s2u[key] = std::move(t));
     return GENIE_OK;
 }
 
@@ -2688,7 +2670,7 @@ int launch_stage2_h2u(genie_ctx* c, const DaArgs& a, int gi_begin, int gi_end, b
     const bool big = c->P_ext * 128 >= (1ll << 32);
     auto launch = [&](auto kern) -> int {
         if (int r = raise_lds_limit(c, (const void*)kern, 160 * 1024)) return r;
-        kern<<<grid, S2U_WPB * 64, lds, st>>>(a, (const S2uBlock*)tb->blocks, tb->xcd0);
+        kern<<<grid, S2U_WPB * 64, lds, st>>>(a, tb->blocks, tb->xcd0);
         return GENIE_OK;
     };
     if (xl) return big ? launch(k_stage2_h2u<true, true, SAVE>) : launch(k_stage2_h2u<true, false, SAVE>);
@@ -2717,7 +2699,7 @@ int run_stage2(genie_ctx* c, const StageCall& call, const float* mask, const flo
         return fail(GENIE_ERR_STATE, r.layout == RowLayout::NodePlanar
                                          ? "stage 2: this call's stage 2 reads c / wv node-planar, but the last stage 1 wrote them as rows"
                                          : "stage 2: this call's stage 2 reads c / wv as rows, but the last stage 1 wrote them node-planar");
-    a.mask = mask; a.edge_attr = edge_attr; a.x_latent = x_latent_out; a.packed = c->packed[1];
+    a.mask = mask; a.edge_attr = edge_attr; a.x_latent = x_latent_out; a.packed = c->packed[PL_S2];
     a.ea_int = nullptr;
     a.mm_int = (const float*)ws + c->o_mm + (c->slot % GENIE_NBIG) * c->big_stride;
     // training forward: the caller's station order through an identity processing order (the saved pre-activations of 1.8 GB stay
@@ -2726,8 +2708,7 @@ int run_stage2(genie_ctx* c, const StageCall& call, const float* mask, const flo
         if (!c->sta_ident) {
             std::vector<int32_t> id((size_t)c->S);
             for (int i = 0; i < c->S; ++i) id[i] = i;
-            HIP_TRY(gmalloc((void**)&c->sta_ident, sizeof(int32_t) * id.size()));
-            HIP_TRY(hipMemcpy(c->sta_ident, id.data(), sizeof(int32_t) * id.size(), hipMemcpyHostToDevice));
+            GENIE_TRY(dev_upload(c->sta_ident, id));
         }
         a.sta_user = c->sta_ident; a.wgmap = 0;
         return GENIE_OK;
@@ -2744,7 +2725,7 @@ int run_stage2(genie_ctx* c, const StageCall& call, const float* mask, const flo
         // fragments built per call (identity station order)
         if ((rc = identity_order())) return rc;
         a.ea_int = edge_attr; a.np = 1; a.packed = c->packed_s2h;
-        if (!c->ea_frag_tmp) HIP_TRY(gmalloc((void**)&c->ea_frag_tmp, 32 * (size_t)c->P));
+        if (!c->ea_frag_tmp) HIP_TRY(c->ea_frag_tmp.alloc(8 * (size_t)c->P));
         k_ea_frag<<<(unsigned)((c->P + 255) / 256), 256, 0, st>>>(edge_attr, c->P, c->S, nullptr, c->ea_frag_tmp);
         a.ea_frag = c->ea_frag_tmp;
         if ((rc = launch_stage2_h2u<true>(c, a, gi_begin, gi_end, x_latent_out != nullptr, st))) return rc;
@@ -2788,7 +2769,7 @@ int run_stage2(genie_ctx* c, const StageCall& call, const float* mask, const flo
         a.wgmap = c->s2_wgmap; a.np = 1; a.packed = c->packed_s2h;
         if (c->ea_frag && c->ea_user == edge_attr) a.ea_frag = c->ea_frag;
         else {
-            if (!c->ea_frag_tmp) HIP_TRY(gmalloc((void**)&c->ea_frag_tmp, 32 * (size_t)c->P));
+            if (!c->ea_frag_tmp) HIP_TRY(c->ea_frag_tmp.alloc(8 * (size_t)c->P));
             k_ea_frag<<<(unsigned)((c->P + 255) / 256), 256, 0, st>>>(edge_attr, c->P, c->S, c->sta_perm, c->ea_frag_tmp);
             a.ea_frag = c->ea_frag_tmp;
         }
@@ -3232,9 +3213,8 @@ int genie_nbr_mean(genie_ctx* c, const float* x_sta, const float* x_src, float* 
 
 namespace {
 // out-edge CSR of a graph given as in-edge CSR (rowptr by target i, col = source j): for every j the targets i in increasing
-// order, with weight 1 / in-degree(i)
-int build_reversed(const int32_t* d_rowptr, const int32_t* d_col, int n_tgt, int n_src, int32_t** r_rowptr, int32_t** r_col, float** r_w,
-                   int2** r_cw = nullptr) {
+// order, with weight 1 / in-degree(i). `out` is replaced only when the whole graph was built.
+int build_reversed(const int32_t* d_rowptr, const int32_t* d_col, int n_tgt, int n_src, RevGraph& out, bool with_cw) {
     std::vector<int32_t> rp((size_t)n_tgt + 1);
     HIP_TRY(hipMemcpy(rp.data(), d_rowptr, sizeof(int32_t) * rp.size(), hipMemcpyDeviceToHost));
     const size_t E = (size_t)rp[n_tgt];
@@ -3256,20 +3236,16 @@ int build_reversed(const int32_t* d_rowptr, const int32_t* d_col, int n_tgt, int
             rw[pos] = w;
         }
     }
-    HIP_TRY(gmalloc((void**)r_rowptr, sizeof(int32_t) * rrp.size()));
-    HIP_TRY(hipMemcpy(*r_rowptr, rrp.data(), sizeof(int32_t) * rrp.size(), hipMemcpyHostToDevice));
-    HIP_TRY(gmalloc((void**)r_col, sizeof(int32_t) * std::max<size_t>(E, 1)));
-    HIP_TRY(gmalloc((void**)r_w, sizeof(float) * std::max<size_t>(E, 1)));
-    if (E) {
-        HIP_TRY(hipMemcpy(*r_col, rcol.data(), sizeof(int32_t) * E, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(*r_w, rw.data(), sizeof(float) * E, hipMemcpyHostToDevice));
-    }
-    if (r_cw) {
+    RevGraph g;
+    GENIE_TRY(dev_upload(g.rowptr, rrp));
+    GENIE_TRY(dev_upload(g.col, rcol));
+    GENIE_TRY(dev_upload(g.w, rw));
+    if (with_cw) {
         std::vector<int2> cw(std::max<size_t>(E, 1), int2{0, 0});
         for (size_t e = 0; e < E; ++e) { cw[e].x = rcol[e]; memcpy(&cw[e].y, &rw[e], 4); }
-        HIP_TRY(gmalloc((void**)r_cw, sizeof(int2) * cw.size()));
-        HIP_TRY(hipMemcpy(*r_cw, cw.data(), sizeof(int2) * cw.size(), hipMemcpyHostToDevice));
+        GENIE_TRY(dev_upload(g.cw, cw));
     }
+    out = std::move(g);
     return GENIE_OK;
 }
 }  // namespace
@@ -3280,15 +3256,16 @@ int genie_nbr_mean_bwd(genie_ctx* c, const float* g_sta, const float* g_src, flo
     if ((g_sta && !dx_sta) || (g_src && !dx_src)) return fail(GENIE_ERR_ARG, "genie_nbr_mean_bwd: input without output");
     if (c->pcsr || c->G_ext != c->G) return fail(GENIE_ERR_STATE, "genie_nbr_mean_bwd: needs an unsharded Cartesian product graph");
     if (!g_sta && !g_src) return GENIE_OK;
-    if (!c->r_sta_rowptr) {
-        int rc;
-        if ((rc = build_reversed(c->sta_rowptr, c->sta_col, c->S, c->S, &c->r_sta_rowptr, &c->r_sta_col, &c->r_sta_w))) return rc;
-        if ((rc = build_reversed(c->src_rowptr, c->src_col, c->G, c->G, &c->r_src_rowptr, &c->r_src_col, &c->r_src_w))) return rc;
+    if (!c->r_sta.rowptr) {     // (the training backward builds them with the pair arrays: ensure_reversed)
+        RevGraph sta, src;
+        GENIE_TRY(build_reversed(c->sta_rowptr, c->sta_col, c->S, c->S, sta, false));
+        GENIE_TRY(build_reversed(c->src_rowptr, c->src_col, c->G, c->G, src, false));
+        c->r_sta = std::move(sta); c->r_src = std::move(src);
     }
     const int nb = std::min<long long>((c->P + 31) / 32, (long long)c->num_cu * 16);
     hipStream_t st = (hipStream_t)stream;
-#define GENIE_NMB(CL_, VW_) k_nbr_mean<CL_, VW_><<<nb, 256, 0, st>>>(c->S, c->G, c->r_sta_rowptr, c->r_sta_col, c->r_src_rowptr, c->r_src_col, \
-                                                            g_sta, g_src, dx_sta, dx_src, c->r_sta_w, c->r_src_w)
+#define GENIE_NMB(CL_, VW_) k_nbr_mean<CL_, VW_><<<nb, 256, 0, st>>>(c->S, c->G, c->r_sta.rowptr, c->r_sta.col, c->r_src.rowptr, c->r_src.col, \
+                                                            g_sta, g_src, dx_sta, dx_src, c->r_sta.w, c->r_src.w)
     switch (row_floats) {
         case 16: GENIE_NMB(4, 4); break;
         case 32: GENIE_NMB(8, 4); break;
@@ -3354,9 +3331,11 @@ int train_check(const genie_ctx* c, const char* who, bool variants = false, bool
 // station sums live as [G][T][32] partial rows; on an irregular product graph the training calls keep ONE row per source node there
 int ensure_src_of(genie_ctx* c, hipStream_t st) {
     if (c->p_src_of || !c->pcsr) return GENIE_OK;
-    HIP_TRY(gmalloc((void**)&c->p_src_of, sizeof(int32_t) * (size_t)c->P));
-    k_seg_owner<<<(c->G + 255) / 256, 256, 0, st>>>(c->seg_rowptr, c->G, c->p_src_of);
+    DevBuf<int32_t> src_of;
+    HIP_TRY(src_of.alloc((size_t)c->P));
+    k_seg_owner<<<(c->G + 255) / 256, 256, 0, st>>>(c->seg_rowptr, c->G, src_of);
     HIP_TRY(hipGetLastError());
+    c->p_src_of = std::move(src_of);
     return GENIE_OK;
 }
 // scratch of static_term_grads: per-source-node sums [G][16], per-station partial sums [SG_CHUNKS][S][16], slices of one dW block
@@ -3426,35 +3405,28 @@ int genie_da_train_fwd(genie_ctx* c, const float* slice, const float* mask, cons
 }
 
 namespace {
+// The reversed graphs of the training backward, with the pair arrays. Built in locals and installed together: r_sta.cw != null means
+// that every graph below exists.
 int ensure_reversed(genie_ctx* c) {
-    if (c->r_sta_rowptr && c->r_sta_cw) return GENIE_OK;
-    int rc;
-    if (c->r_sta_rowptr) {      // built by genie_nbr_mean_bwd without the pair arrays: rebuild whole
-        void* old[] = {c->r_sta_rowptr, c->r_sta_col, c->r_sta_w, c->r_src_rowptr, c->r_src_col, c->r_src_w};
-        (void)hipDeviceSynchronize();
-        for (void* q : old) (void)gfree(q);
-        c->r_sta_rowptr = c->r_sta_col = c->r_src_rowptr = c->r_src_col = nullptr; c->r_sta_w = c->r_src_w = nullptr;
-    }
+    if (c->r_sta.cw) return GENIE_OK;
+    RevGraph sta, src, psta, psrc;
     if (c->pcsr) {      // irregular product graph: the P-sized passes gather by product-node id over the reversed PRODUCT-level graphs
         const int np = (int)c->P;    // (the G-sized tail keeps the reversed base source graph below)
-        int32_t* col_unused = nullptr;
-        float* w_unused = nullptr;
-        if ((rc = build_reversed(c->p_sta_rowptr, c->p_sta_col, np, np, &c->rp_sta_rowptr, &col_unused, &w_unused, &c->rp_sta_cw))) return rc;
-        (void)gfree(col_unused); (void)gfree(w_unused);
-        col_unused = nullptr; w_unused = nullptr;
-        if ((rc = build_reversed(c->p_src_rowptr, c->p_src_col, np, np, &c->rp_src_rowptr, &col_unused, &w_unused, &c->rp_src_cw))) return rc;
-        (void)gfree(col_unused); (void)gfree(w_unused);
+        GENIE_TRY(build_reversed(c->p_sta_rowptr, c->p_sta_col, np, np, psta, true));
+        GENIE_TRY(build_reversed(c->p_src_rowptr, c->p_src_col, np, np, psrc, true));
+        psta.col.reset(); psta.w.reset(); psrc.col.reset(); psrc.w.reset();      // only rowptr and cw are read (never launched on: no drain)
         // base station graph: not part of a subgraph context; an empty reversed graph keeps the non-null contract of the callers
-        std::vector<int32_t> zero((size_t)c->S + 1, 0);
-        HIP_TRY(gmalloc((void**)&c->r_sta_rowptr, sizeof(int32_t) * zero.size()));
-        HIP_TRY(hipMemcpy(c->r_sta_rowptr, zero.data(), sizeof(int32_t) * zero.size(), hipMemcpyHostToDevice));
-        HIP_TRY(gmalloc((void**)&c->r_sta_col, sizeof(int32_t)));
-        HIP_TRY(gmalloc((void**)&c->r_sta_w, sizeof(float)));
-        HIP_TRY(gmalloc((void**)&c->r_sta_cw, sizeof(int2)));
-        return build_reversed(c->src_rowptr, c->src_col, c->G, c->G, &c->r_src_rowptr, &c->r_src_col, &c->r_src_w, &c->r_src_cw);
+        GENIE_TRY(dev_upload(sta.rowptr, std::vector<int32_t>((size_t)c->S + 1, 0)));
+        HIP_TRY(sta.col.alloc(1));
+        HIP_TRY(sta.w.alloc(1));
+        HIP_TRY(sta.cw.alloc(1));
+    } else {
+        GENIE_TRY(build_reversed(c->sta_rowptr, c->sta_col, c->S, c->S, sta, true));
     }
-    if ((rc = build_reversed(c->sta_rowptr, c->sta_col, c->S, c->S, &c->r_sta_rowptr, &c->r_sta_col, &c->r_sta_w, &c->r_sta_cw))) return rc;
-    return build_reversed(c->src_rowptr, c->src_col, c->G, c->G, &c->r_src_rowptr, &c->r_src_col, &c->r_src_w, &c->r_src_cw);
+    GENIE_TRY(build_reversed(c->src_rowptr, c->src_col, c->G, c->G, src, true));
+    if (c->r_sta.rowptr) (void)hipDeviceSynchronize();      // built by genie_nbr_mean_bwd without the pair arrays: replaced whole
+    c->r_sta = std::move(sta); c->r_src = std::move(src); c->rp_sta = std::move(psta); c->rp_src = std::move(psrc);
+    return GENIE_OK;
 }
 int da_train_bwd_impl(genie_ctx* c, const float* slice, const float* mask, const float* edge_attr, const float* save,
                       const float* d_r, float* scratch, float* grad_blob, void* stream, bool zero_blob);
@@ -3481,9 +3453,9 @@ int da_train_bwd_impl(genie_ctx* c, const float* slice, const float* mask, const
     a.S = c->S; a.G = c->G; a.T = c->T; a.seg = std::max(1, c->seg);
     a.nxcd = 8;
     a.P = c->P; a.order = c->order;
-    a.r_sta_rowptr = c->r_sta_rowptr; a.r_sta_col = c->r_sta_col; a.r_sta_w = c->r_sta_w;
-    a.r_src_rowptr = c->r_src_rowptr; a.r_src_col = c->r_src_col; a.r_src_w = c->r_src_w;
-    a.r_sta_cw = c->r_sta_cw; a.r_src_cw = c->r_src_cw;
+    a.r_sta_rowptr = c->r_sta.rowptr; a.r_sta_col = c->r_sta.col; a.r_sta_w = c->r_sta.w;
+    a.r_src_rowptr = c->r_src.rowptr; a.r_src_col = c->r_src.col; a.r_src_w = c->r_src.w;
+    a.r_sta_cw = c->r_sta.cw; a.r_src_cw = c->r_src.cw;
     a.slice = slice; a.mask = mask; a.edge_attr = edge_attr; a.save = save; a.dr = d_r;
     a.gr = scratch; a.part = scratch + (size_t)GR_BLOCKS * 16 * (size_t)c->P;
     a.sv_t = SV_T; a.sv_up = SV_UP; a.sv_vp = SV_VP;
@@ -3491,14 +3463,14 @@ int da_train_bwd_impl(genie_ctx* c, const float* slice, const float* mask, const
     if (c->pcsr) {
         if ((rc = ensure_src_of(c, st))) return rc;
         a.src_of = c->p_src_of; a.ptile = c->ptile16;
-        a.r_sta_rowptr = c->rp_sta_rowptr; a.r_sta_cw = c->rp_sta_cw; a.r_src_rowptr = c->rp_src_rowptr; a.r_src_cw = c->rp_src_cw;
+        a.r_sta_rowptr = c->rp_sta.rowptr; a.r_sta_cw = c->rp_sta.cw; a.r_src_rowptr = c->rp_src.rowptr; a.r_src_cw = c->rp_src.cw;
         a.r_sta_col = a.r_src_col = nullptr; a.r_sta_w = a.r_src_w = nullptr;       // (the PCSR passes read the pair arrays only)
     }
     const int grid = train_grid(c);
     // 32-bit row offsets on scalar bases (ldo / sto) while every block of the kept rows lies below 4 GiB
     const bool o32 = !c->pcsr && (unsigned long long)SV_BLOCKS * (unsigned long long)c->P * 64ull < (1ull << 32);
     for (int s = 0; s < 3; ++s) {
-        a.packed = c->packed[4 + s]; a.n_acc = c->n_acc[s]; a.n_vec = c->n_vec[s];
+        a.packed = c->packed[PL_B2 + s]; a.n_acc = c->tb->n_acc[s]; a.n_vec = c->tb->n_vec[s];
         // k_train_b1 holds one wave per SIMD (442 registers): one workgroup per CU is all that is ever resident. Its pair-split form
         // k_train_b1s (two waves per tile, <= 256 registers) runs two workgroups per CU and writes one partial per PAIR
         const bool split1 = s == 1 && o32 && b1_split_on();
@@ -3519,8 +3491,8 @@ int da_train_bwd_impl(genie_ctx* c, const float* slice, const float* mask, const
         }
         const int stride = a.n_acc * 256 + a.n_vec * 16 + 16;
         const int wpb_s = (s == 0 && !c->pcsr) ? TR_WPB_LIGHT : (split1 ? 2 : 4);
-        k_train_reduce<<<(stride + 31) / 32, 256, 0, st>>>(a.part, grid_w * wpb_s, a.n_acc, a.n_vec, c->n_sc[s], c->d_acc[s], c->d_vec[s],
-                                                            c->d_sc[s], grad_blob, 0);
+        k_train_reduce<<<(stride + 31) / 32, 256, 0, st>>>(a.part, grid_w * wpb_s, a.n_acc, a.n_vec, c->tb->n_sc[s], c->tb->d_acc[s], c->tb->d_vec[s],
+                                                            c->tb->d_sc[s], grad_blob, 0);
     }
     if (c->has_edges || c->abs_sta) {
         if ((rc = static_term_grads(c, a.gr, a.part + train_part_floats(c), grad_blob, st))) return rc;
@@ -3556,9 +3528,9 @@ TtScratch tt_layout(const genie_ctx* c, int n_query) {
     return t;
 }
 int tt_reduce(genie_ctx* c, int tm, const float* part, int n_waves, float* blob, hipStream_t st) {
-    const int stride = c->n_acc[tm] * 256 + c->n_vec[tm] * 16 + 16;
-    k_train_reduce<<<(stride + 31) / 32, 256, 0, st>>>(part, n_waves, c->n_acc[tm], c->n_vec[tm], c->n_sc[tm], c->d_acc[tm], c->d_vec[tm],
-                                                        c->d_sc[tm], blob, 1);
+    const int stride = c->tb->n_acc[tm] * 256 + c->tb->n_vec[tm] * 16 + 16;
+    k_train_reduce<<<(stride + 31) / 32, 256, 0, st>>>(part, n_waves, c->tb->n_acc[tm], c->tb->n_vec[tm], c->tb->n_sc[tm], c->tb->d_acc[tm], c->tb->d_vec[tm],
+                                                        c->tb->d_sc[tm], blob, 1);
     return GENIE_OK;
 }
 }  // namespace
@@ -3643,8 +3615,8 @@ int genie_tail_train_bwd(genie_ctx* c, const float* pos, const float* x_query, c
         std::lock_guard<std::mutex> lk(mu);
         hipStream_t& s = side[c->device];
         if (!s) HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+        if (!c->ev_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+        if (!c->ev_join) HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
         c->side_stream = s;
     }
     const int grid_y = tt_grid(c->G);
@@ -3655,7 +3627,7 @@ int genie_tail_train_bwd(genie_ctx* c, const float* pos, const float* x_query, c
         memset(&b, 0, sizeof(b));
         b.ro = ro; b.ro.N = b.ro.Nw = c->G; b.ro.img = c->packed[PL_RO0];
         b.timg = c->packed[PL_TRO0]; b.d_out = d_y; b.d_lat = d_ylat_extra; b.dxs = S + L.dxs_a;
-        b.part = S + L.part_ro0; b.n_acc = c->n_acc[TM_RO0]; b.n_vec = c->n_vec[TM_RO0];
+        b.part = S + L.part_ro0; b.n_acc = c->tb->n_acc[TM_RO0]; b.n_vec = c->tb->n_vec[TM_RO0];
         k_ro_bwd<0><<<grid_y, 256, sizeof(float) * RB_LDS_FLOATS, c->side_stream>>>(b);
         HIP_TRY(hipEventRecord(c->ev_join, c->side_stream));
     }
@@ -3666,7 +3638,7 @@ int genie_tail_train_bwd(genie_ctx* c, const float* pos, const float* x_query, c
         b.ro = ro; b.ro.N = b.ro.Nw = n_query; b.ro.x_grid = pos; b.ro.x_query = x_query; b.ro.knn = knn; b.ro.cv = S + L.cv;
         b.ro.img = c->packed[PL_RO1];
         b.timg = c->packed[PL_TRO1]; b.d_out = d_x; b.d_lat = d_qlat_extra; b.eb = S + L.eb; b.dxm = S + L.dxm;
-        b.part = S + L.part_ro; b.n_acc = c->n_acc[TM_RO1]; b.n_vec = c->n_vec[TM_RO1];
+        b.part = S + L.part_ro; b.n_acc = c->tb->n_acc[TM_RO1]; b.n_vec = c->tb->n_vec[TM_RO1];
         const int grid = tt_grid(n_query);
         k_ro_bwd<1><<<grid, 256, sizeof(float) * RB_LDS_FLOATS, st>>>(b);
         tt_reduce(c, TM_RO1, b.part, grid * 4, grad_blob, st);
@@ -3675,7 +3647,7 @@ int genie_tail_train_bwd(genie_ctx* c, const float* pos, const float* x_query, c
         n.G = c->G; n.nq = n_query; n.x_spatial = xs; n.x_grid = pos; n.x_query = x_query; n.r_rowptr = rknn_rowptr; n.r_edge = rknn_edge;
         n.eb = S + L.eb; n.dxm = S + L.dxm; n.raw = c->raw; n.o_sq_w = g_params[W_SAT_Q_W].off; n.o_sq_b = g_params[W_SAT_Q_B].off;
         n.scale_rel = c->scale_rel; n.timg = c->packed[PL_TSN]; n.dxs = S + L.dxs_b;
-        n.part = S + L.part_a; n.n_acc = c->n_acc[TM_SN]; n.n_vec = c->n_vec[TM_SN];
+        n.part = S + L.part_a; n.n_acc = c->tb->n_acc[TM_SN]; n.n_vec = c->tb->n_vec[TM_SN];
         const int gn = tt_grid(c->G);
         k_sat_node_bwd<<<gn, 256, 0, st>>>(n);
         tt_reduce(c, TM_SN, n.part, gn * 4, grad_blob, st);
@@ -3698,7 +3670,7 @@ int genie_tail_train_bwd(genie_ctx* c, const float* pos, const float* x_query, c
         SbArgs a;
         memset(&a, 0, sizeof(a));
         a.G = c->G; a.C = layer == 1 ? 15 : 30; a.E = c->E_src; a.x_in = x_in[layer - 1]; a.pos = pos;
-        a.rowptr = c->src_rowptr; a.col = c->src_col; a.outdeg = c->outdeg; a.r_rowptr = c->r_src_rowptr; a.r_col = c->r_src_col;
+        a.rowptr = c->src_rowptr; a.col = c->src_col; a.outdeg = c->outdeg; a.r_rowptr = c->r_src.rowptr; a.r_col = c->r_src.col;
         a.raw = c->raw; a.fc1_w = g_params[(layer == 1 ? W_SA1_FC1_W : (layer == 2 ? W_SA2_FC1_W : W_SA3_FC1_W))].off;
         a.scale_rel = c->scale_rel; a.pj = S + L.pj; a.gpart = S + L.gpart; a.n_gpart = sa_vg(c);
         a.img = c->packed[PL_SA1 + layer - 1]; a.timg = c->packed[PL_TSA1 + layer - 1];
@@ -3706,11 +3678,11 @@ int genie_tail_train_bwd(genie_ctx* c, const float* pos, const float* x_query, c
         else a.dout_a = dxl[layer & 1];
         a.dxd = S + L.dxd; a.dan = S + L.dan; a.dx = dxl[(layer - 1) & 1];
         const int tma = TM_SAA1 + layer - 1, tmb = TM_SAB1 + layer - 1;
-        a.part = S + L.part_b; a.n_acc = c->n_acc[tma]; a.n_vec = c->n_vec[tma];
+        a.part = S + L.part_b; a.n_acc = c->tb->n_acc[tma]; a.n_vec = c->tb->n_vec[tma];
         if (layer == 1) k_sa_bwd_a<15><<<gs, 256, 0, st>>>(a); else k_sa_bwd_a<30><<<gs, 256, 0, st>>>(a);
         tt_reduce(c, tma, a.part, gs * 4, grad_blob, st);
-        a.part_a = S + L.part_b; a.n_waves_a = gs * 4; a.n_acc_a = c->n_acc[tma]; a.n_vec_a = c->n_vec[tma];
-        a.part = S + L.part_a; a.n_acc = c->n_acc[tmb]; a.n_vec = c->n_vec[tmb]; a.blob = grad_blob;
+        a.part_a = S + L.part_b; a.n_waves_a = gs * 4; a.n_acc_a = c->tb->n_acc[tma]; a.n_vec_a = c->tb->n_vec[tma];
+        a.part = S + L.part_a; a.n_acc = c->tb->n_acc[tmb]; a.n_vec = c->tb->n_vec[tmb]; a.blob = grad_blob;
         if (layer == 1) k_sa_bwd_b<15><<<gs, 256, 0, st>>>(a); else k_sa_bwd_b<30><<<gs, 256, 0, st>>>(a);
         tt_reduce(c, tmb, a.part, gs * 4, grad_blob, st);
     }
@@ -3718,7 +3690,7 @@ int genie_tail_train_bwd(genie_ctx* c, const float* pos, const float* x_query, c
         BbArgs b;
         memset(&b, 0, sizeof(b));
         b.G = c->G; b.r = r; b.dbip = dxl[0]; b.img = c->packed[PL_BIP]; b.timg = c->packed[PL_TBIP]; b.dr = d_r_out;
-        b.part = S + L.part_a; b.n_acc = c->n_acc[TM_BIP]; b.n_vec = c->n_vec[TM_BIP];
+        b.part = S + L.part_a; b.n_acc = c->tb->n_acc[TM_BIP]; b.n_vec = c->tb->n_vec[TM_BIP];
         k_bip_bwd<<<gs, 256, 0, st>>>(b);
         tt_reduce(c, TM_BIP, b.part, gs * 4, grad_blob, st);
     }
@@ -3798,9 +3770,9 @@ int assoc_fwd_impl(genie_ctx* c, const float* y_latent, const float* mask_src, c
     if (((uintptr_t)assoc_ws & 15) != 0) return fail(GENIE_ERR_ARG, "genie_assoc_fwd: assoc_ws must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_packed(c, st))) return rc;
-    if (!c->as_pg) HIP_TRY(gmalloc((void**)&c->as_pg, sizeof(float) * AS_PG * (size_t)c->G));
+    if (!c->as_pg) HIP_TRY(c->as_pg.alloc(AS_PG * (size_t)c->G));
     const bool variant = c->has_edges || c->abs_sta != nullptr;
-    if (variant && !c->as_ps) HIP_TRY(gmalloc((void**)&c->as_ps, sizeof(float) * AS_PS * (size_t)edge_rows_sta(c)));
+    if (variant && !c->as_ps) HIP_TRY(c->as_ps.alloc(AS_PS * (size_t)edge_rows_sta(c)));
     assoc_pre_launch(c, y_latent, mask_src, st);
     const StageCall call{save, save != nullptr};      // save: training forward (caller's station order, pre-activations kept)
     DaArgs d = make_da_args(c, call, (float*)ws);
@@ -3820,16 +3792,16 @@ int assoc_fwd_impl(genie_ctx* c, const float* y_latent, const float* mask_src, c
         a.sta_user = nullptr; a.src_of = c->p_src_of; a.ptile = c->ptile16;
         const long long ntiles = (c->P + 15) / 16;
         const int grid = (int)std::max<long long>(8, std::min<long long>((ntiles + 3) / 4, (long long)c->num_cu * std::max(1, c->bpc1)) / 8 * 8);
-        a.packed = c->packed[2];
+        a.packed = c->packed[PL_ASA];
         k_assoc_a<true><<<grid, 256, 0, st>>>(a);
-        a.packed = c->packed[3];
+        a.packed = c->packed[PL_ASB];
         k_assoc_b<true><<<grid, 256, 0, st>>>(a);
     } else {
         const int grid = da_grid(c, (long long)c->G * c->T, std::max(1, c->bpc1));
-        a.packed = c->packed[2];
+        a.packed = c->packed[PL_ASA];
         // (40 registers, 21 KB of LDS: four workgroups per CU where stage 1's occupancy gave two -- 369 -> 322 us, six: 330; tools/assoc_ab.sh)
         k_assoc_a<false><<<da_grid(c, (long long)c->G * c->T, 4), 256, 0, st>>>(a);
-        a.packed = c->packed[3];
+        a.packed = c->packed[PL_ASB];
         // k_assoc_b is bound by its 23 gathered 128-B rows per node and, at 4 waves per workgroup, by LDS to 8 waves per CU (every
         // workgroup holds its own 52-KB copy of the weight image): ONE workgroup of 16 waves per CU shares one copy -- 969 -> 824 us at
         // config 2 (12 waves: 882; 8 waves in one workgroup: 987; `tools/assoc_ab.sh`)
@@ -3866,7 +3838,7 @@ int genie_assoc_train_bwd(genie_ctx* c, const float* y_latent, const float* mask
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_packed(c, st))) return rc;
     if ((rc = ensure_reversed(c))) return rc;
-    if (!c->as_pg) HIP_TRY(gmalloc((void**)&c->as_pg, sizeof(float) * AS_PG * (size_t)c->G));
+    if (!c->as_pg) HIP_TRY(c->as_pg.alloc(AS_PG * (size_t)c->G));
     assoc_pre_launch(c, y_latent, mask_src, st);          // pg[31] = mask1[g] (another forward may have overwritten the table)
     HIP_TRY(hipMemsetAsync(grad_blob, 0, sizeof(float) * g_raw_total, st));
     TrArgs a;
@@ -3874,9 +3846,9 @@ int genie_assoc_train_bwd(genie_ctx* c, const float* y_latent, const float* mask
     a.S = c->S; a.G = c->G; a.T = c->T; a.seg = std::max(1, c->seg);
     a.nxcd = 8;
     a.P = c->P; a.order = c->order;
-    a.r_sta_rowptr = c->r_sta_rowptr; a.r_sta_col = c->r_sta_col; a.r_sta_w = c->r_sta_w;
-    a.r_src_rowptr = c->r_src_rowptr; a.r_src_col = c->r_src_col; a.r_src_w = c->r_src_w;
-    a.r_sta_cw = c->r_sta_cw; a.r_src_cw = c->r_src_cw;
+    a.r_sta_rowptr = c->r_sta.rowptr; a.r_sta_col = c->r_sta.col; a.r_sta_w = c->r_sta.w;
+    a.r_src_rowptr = c->r_src.rowptr; a.r_src_col = c->r_src.col; a.r_src_w = c->r_src.w;
+    a.r_sta_cw = c->r_sta.cw; a.r_src_cw = c->r_src.cw;
     a.mask = mask; a.edge_attr = edge_attr; a.save = asave; a.x_latent = x_latent; a.pg = c->as_pg;
     a.gr = scratch; a.part = scratch + (size_t)GR_BLOCKS * 16 * (size_t)c->P;
     a.zsum = a.part + train_part_floats(c);
@@ -3885,7 +3857,7 @@ int genie_assoc_train_bwd(genie_ctx* c, const float* y_latent, const float* mask
     if (c->pcsr) {
         if ((rc = ensure_src_of(c, st))) return rc;
         a.src_of = c->p_src_of; a.ptile = c->ptile16;
-        a.r_sta_rowptr = c->rp_sta_rowptr; a.r_sta_cw = c->rp_sta_cw; a.r_src_rowptr = c->rp_src_rowptr; a.r_src_cw = c->rp_src_cw;
+        a.r_sta_rowptr = c->rp_sta.rowptr; a.r_sta_cw = c->rp_sta.cw; a.r_src_rowptr = c->rp_src.rowptr; a.r_src_cw = c->rp_src.cw;
         a.r_sta_col = a.r_src_col = nullptr; a.r_sta_w = a.r_src_w = nullptr;
     }
     a.sv_t = AV_T; a.sv_up = AV_UV; a.sv_vp = AV_UV + 2;
@@ -3895,7 +3867,7 @@ int genie_assoc_train_bwd(genie_ctx* c, const float* y_latent, const float* mask
     const int pls[4] = {-1, PL_TAB2, PL_TAB1, PL_TAB0};
     for (int s = 0; s < 4; ++s) {
         const int tm = tms[s];
-        a.packed = pls[s] >= 0 ? c->packed[pls[s]] : nullptr; a.n_acc = c->n_acc[tm]; a.n_vec = c->n_vec[tm];
+        a.packed = pls[s] >= 0 ? c->packed[pls[s]] : nullptr; a.n_acc = c->tb->n_acc[tm]; a.n_vec = c->tb->n_vec[tm];
         const bool split1 = s == 1 && !c->pcsr && o32a && b1_split_on();      // k_train_b1s: two waves per tile, one partial per pair
         const int grid_s = (s == 1 && !c->pcsr && !split1) ? std::max(8, grid / 2 / 8 * 8) : grid;      // k_train_b1: one workgroup per CU (see da_train_bwd_impl)
         if (c->pcsr) {
@@ -3913,8 +3885,8 @@ int genie_assoc_train_bwd(genie_ctx* c, const float* y_latent, const float* mask
             else k_as_b0<false><<<grid, 256, 0, st>>>(a);
         }
         const int stride = a.n_acc * 256 + a.n_vec * 16 + 16;
-        k_train_reduce<<<(stride + 31) / 32, 256, 0, st>>>(a.part, grid_s * (split1 ? 2 : 4), a.n_acc, a.n_vec, c->n_sc[tm], c->d_acc[tm], c->d_vec[tm],
-                                                            c->d_sc[tm], grad_blob, 0);
+        k_train_reduce<<<(stride + 31) / 32, 256, 0, st>>>(a.part, grid_s * (split1 ? 2 : 4), a.n_acc, a.n_vec, c->tb->n_sc[tm], c->tb->d_acc[tm], c->tb->d_vec[tm],
+                                                            c->tb->d_sc[tm], grad_blob, 0);
         // static terms of the two other model definitions: the layer-2 ones now (the next pass writes dtrp over do), the rest at the end;
         // on an irregular product graph the layer-1 ones after k_as_b1 already (k_as_b0<PCSR> leaves its d z1 rows in the dt blocks)
         if (variant && c->pcsr) {
@@ -3927,7 +3899,7 @@ int genie_assoc_train_bwd(genie_ctx* c, const float* y_latent, const float* mask
         AgArgs g;
         memset(&g, 0, sizeof(g));
         g.G = c->G; g.T = part_T(c); g.zsum = a.zsum; g.y_latent = y_latent; g.timg = c->packed[PL_TAG]; g.d_ylat = d_ylat_out;
-        g.part = a.part; g.n_acc = c->n_acc[TM_AG]; g.n_vec = c->n_vec[TM_AG];
+        g.part = a.part; g.n_acc = c->tb->n_acc[TM_AG]; g.n_vec = c->tb->n_vec[TM_AG];
         const int gg = tt_grid(c->G);
         k_as_g<<<gg, 256, 0, st>>>(g);
         tt_reduce(c, TM_AG, g.part, gg * 4, grad_blob, st);
@@ -4122,7 +4094,7 @@ int genie_lslc_bwd(genie_ctx* c, int phase_head, const float* s_rows, const int3
     b.timg = c->packed[phase_head == 0 ? PL_TLSP : PL_TLSS];
     b.d_out = d_out; b.erow = erow; b.etgt = etgt;
     const int tm = phase_head == 0 ? TM_LSP : TM_LSS;
-    b.part = part_scratch; b.n_acc = c->n_acc[tm]; b.n_vec = c->n_vec[tm];
+    b.part = part_scratch; b.n_acc = c->tb->n_acc[tm]; b.n_vec = c->tb->n_vec[tm];
     const int grid = tt_grid(n_picks);
     k_lslc_bwd<<<grid, 256, 0, st>>>(b);
     tt_reduce(c, tm, b.part, grid * 4, grad_blob, st);
@@ -4220,7 +4192,7 @@ int genie_arrivals_bwd(genie_ctx* c, int n_src, const float* stime, const float*
         AtArgs b;
         memset(&b, 0, sizeof(b));
         b.n_tgt = (int)n_tgt; b.img = c->packed[PL_ARR]; b.timg = c->packed[PL_TARR]; b.tstat = save; b.d_out = d_out; b.tg = tg;
-        b.part = part; b.n_acc = c->n_acc[TM_ART]; b.n_vec = c->n_vec[TM_ART];
+        b.part = part; b.n_acc = c->tb->n_acc[TM_ART]; b.n_vec = c->tb->n_vec[TM_ART];
         const int grid = (int)std::min<long long>(ARRT_GRID, (n_tgt + 63) / 64);
         const size_t lds = sizeof(float) * (GA2_IMG_FLOATS + GTA_IMG_FLOATS + 4 * 16 * 17);
         HIP_TRY(hipFuncSetAttribute((const void*)k_arrt_tgt_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -4232,7 +4204,7 @@ int genie_arrivals_bwd(genie_ctx* c, int n_src, const float* stime, const float*
         AeArgs b;
         memset(&b, 0, sizeof(b));
         b.f = a; b.timg = c->packed[PL_TARR]; b.tg = tg; b.darv = darv; b.cpair = cpair;
-        b.part = part; b.n_acc = c->n_acc[TM_ARE]; b.n_vec = c->n_vec[TM_ARE];
+        b.part = part; b.n_acc = c->tb->n_acc[TM_ARE]; b.n_vec = c->tb->n_vec[TM_ARE];
         const int grid = (int)std::min<long long>(ARRT_GRID, (long long)n_src * n_useg);
         const size_t lds = sizeof(float) * (GA2_IMG_FLOATS + GTA_IMG_FLOATS + 4 * 16 * 17 + 192 + AE_TCH * AT_TG + AE_TCH + 4 * 3 * 256);
         HIP_TRY(hipFuncSetAttribute((const void*)k_arrt_ent_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -4285,7 +4257,7 @@ int genie_set_phase_types(genie_ctx* c, int use_phase_types) {
 int genie_set_subgraph_stations(genie_ctx* c, const int32_t* sta_of_prod, void* stream) {
     if (!c || !sta_of_prod) return fail(GENIE_ERR_ARG, "genie_set_subgraph_stations: null argument");
     if (!c->pcsr) return fail(GENIE_ERR_STATE, "genie_set_subgraph_stations: the context is a Cartesian product graph (station = p % n_sta)");
-    if (!c->p_sta_of) HIP_TRY(gmalloc((void**)&c->p_sta_of, sizeof(int32_t) * (size_t)c->P));
+    if (!c->p_sta_of) HIP_TRY(c->p_sta_of.alloc((size_t)c->P));
     HIP_TRY(hipMemcpyAsync(c->p_sta_of, sta_of_prod, sizeof(int32_t) * (size_t)c->P, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return GENIE_OK;
 }

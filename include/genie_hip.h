@@ -87,6 +87,11 @@ int genie_ctx_create_subgraph(genie_ctx** out, int n_sta, int n_grid, int64_t n_
  * (`trv_times[src, ind_use[sta], :]`, process_utils.py:605). */
 int genie_set_subgraph_stations(genie_ctx* ctx, const int32_t* sta_of_prod, void* stream);
 int genie_ctx_destroy(genie_ctx* ctx);
+/* Accounting of the library's device-memory pool on `device` (every buffer a context owns comes from it; freed blocks are cached and
+ * handed out again): blocks / bytes handed out and not returned (`live`), bytes sitting in the free lists (`cached`). Any output
+ * pointer may be NULL. Host-only and read-only: no driver call, no synchronisation. After genie_ctx_destroy the `live` figures are
+ * back where they were before the matching create (the per-device model tables of the first context stay live). */
+int genie_pool_stats(int device, int64_t* live_blocks, int64_t* live_bytes, int64_t* cached_bytes);
 /* Optional station processing order: `order` (HOST pointer, n_sta int32, a permutation; typically the stations sorted along a
  * space-filling curve) = the caller's station id of the i-th station processed. A tile of the P-sized kernels is 16 consecutive
  * stations of one source node, and a station's neighbours are its nearest stations: with spatially sorted stations the rows a

@@ -2609,6 +2609,153 @@ def test_contexts_rebuilt_per_sample_reuse_pooled_memory_and_stay_correct():
         del fresh
 
 
+def test_every_pooled_block_of_a_context_returns_with_it():
+    """Ownership of the device buffers of a context (genie_pool_stats): after a first context has built the per-device model tables
+    (pool blocks that stay handed out for the life of the process), create -> use -> destroy brings the number of live blocks and
+    live bytes of the library's pool back to where it was, whatever the context allocated lazily on the way: edge-feature and
+    absolute-position tables, two station orders, the registered edge_attr fragments, an irregular product graph, the reversed
+    graphs of the backward passes (built whole, and rebuilt after genie_nbr_mean_bwd built them without the pair arrays), the
+    association heads' tables, the stage-2 block tables of the whole grid and of two sub-ranges (the sharded path's range calls run
+    on one GPU). The same holds for argument errors that are found after allocations were made, and a rejected station order leaves
+    "no order installed": the next forward equals the one of a context without a station order."""
+    import ctypes
+    import gc
+    import os
+    from genie_amd import _lib
+    from oracle import genie_oracle as O
+    from tests.util import GOLDEN_DIR
+    lib = _lib.load()
+    dev_index = torch.device(DEV).index
+
+    def live():
+        b, n = ctypes.c_int64(-1), ctypes.c_int64(-1)
+        _lib.check(lib.genie_pool_stats(dev_index, ctypes.byref(b), ctypes.byref(n), None), "genie_pool_stats")
+        return b.value, n.value
+
+    S, G = 24, 120
+    geom = synthetic.Geometry(S, G, L=150e3, n_query=10, seed=77)
+    win = synthetic.make_window(geom, 600, seed=78)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).float().to(DEV)
+    wd = {k: v.to(DEV) for k, v in O.weights_from_npz(np.load(os.path.join(GOLDEN_DIR, "assoc_7x45.npz"))).items()}
+    Slice, Mask, ea, pos, locs = t(win["Slice"]), t(win["Mask"]), t(geom.edge_attr()), t(geom.x_grid), t(geom.locs)
+    sta = engine.csr_from_edges(torch.from_numpy(geom.A_sta_sta), S)
+    src = engine.csr_from_edges(torch.from_numpy(geom.A_src_src), G)
+    go = engine.morton_order(geom.x_grid)
+    rng = np.random.default_rng(5)
+    y_latent, mask_src = t(rng.normal(0, 1, (G, 30))), t(rng.random((G, 1)) < 0.6)
+
+    def cartesian(**kw):
+        hp = engine.HipPath(S, G, sta, src, grid_order=go, device=DEV, **kw)
+        hp.set_weights(wd)
+        return hp
+
+    def destroy(hp):
+        torch.cuda.synchronize()
+        hp.__del__()
+        assert not hp.ctx.value
+
+    def set_order(hp, order):
+        so = np.ascontiguousarray(order, dtype=np.int32)
+        return lib.genie_set_station_order(hp.ctx, ctypes.c_void_p(so.ctypes.data))
+
+    def train_step_and_assoc(hp, Slice_, Mask_, ea_):
+        r, x_latent, save = hp.train_fwd(Slice_, Mask_, ea_)
+        grads = hp.train_bwd(Slice_, Mask_, ea_, save, torch.ones_like(r))
+        assert all(bool(torch.isfinite(g).all()) for g in grads.values())
+        assert bool(torch.isfinite(hp.assoc_fwd(y_latent, mask_src, x_latent, Mask_, ea_)).all())
+
+    hp = cartesian()                    # the first context of the process builds the device's model tables
+    base_out = hp.path_fwd(Slice, Mask, ea, pos)[0].clone()
+    destroy(hp)
+    gc.collect()                        # contexts of earlier tests that are garbage go now, not in the middle of the comparison
+    torch.cuda.synchronize()
+    base = live()                       # (the model tables, and whatever live contexts other tests of the session still hold)
+
+    def plain(hp):
+        assert torch.equal(hp.path_fwd(Slice, Mask, ea, pos)[0], base_out)
+
+    def options(hp):
+        hp.set_edge_features(locs, pos)
+        hp.set_absolute_pos(locs, pos)
+        hp.path_fwd(Slice, Mask, ea, pos)
+        hp.set_absolute_pos(None, None)
+        hp.path_fwd(Slice, Mask, ea, pos)
+        for order in (engine.morton_order(geom.locs), np.arange(S)[::-1]):
+            assert set_order(hp, order) == 0
+            hp.set_static_edge_attr(ea)
+            hp.set_weights(wd)
+            hp.path_fwd(Slice, Mask, ea, pos)
+            hp.path_fwd(Slice, Mask, ea.clone(), pos)          # an unregistered edge_attr: the per-call fragments
+        hp.da_stage1(Slice, Mask, debug=True)                  # the debug outputs' temporary, un-permuted
+
+    def training(hp):
+        hp.set_edge_features(locs, pos)                        # (the per-station terms of the association heads exist with them)
+        hp.set_weights(wd)
+        train_step_and_assoc(hp, Slice, Mask, ea)
+
+    def nbr_mean_bwd_first(hp):
+        g = torch.ones((S * G, 30), device=DEV)
+        hp.nbr_mean_bwd(g, g)                                  # the reversed graphs without the pair arrays ...
+        train_step_and_assoc(hp, Slice, Mask, ea)              # ... rebuilt whole by the training backward
+
+    def windows(hp):
+        knn = engine.knn_device(pos, t(geom.x_query), 10)
+        hp.set_window_batch(2)
+        for _ in range(2):
+            hp.window_push(Slice, Mask, ea)
+        hp.windows_flush(pos, t(geom.x_query), knn, t(geom.t_query))
+        hp.wait_tails()
+        for k, (b, e) in enumerate(((0, G // 2), (G // 2, G))):           # the sharded path's sub-ranges: block tables per range
+            hp.da_stage1_range(Slice, Mask, b, e, k == 0)
+        for b, e in ((0, G // 2), (G // 2, G)):
+            hp.da_stage2_partials_range(Mask, ea, b, e)
+        assert hp.stage_precision()["f16x2_active"]            # (k_stage2_h2u ran: the tables were built)
+
+    for use in (plain, options, training, nbr_mean_bwd_first, windows):
+        hp = cartesian()
+        use(hp)
+        destroy(hp)
+        assert live() == base, use.__name__
+
+    # irregular product graph: one forward; one training step + assoc_fwd
+    pairs = engine.subgraph_pairs_device(torch.from_numpy(geom.locs).to(DEV), torch.from_numpy(geom.x_grid).to(DEV), max_deg_offset=0.3,
+                                         k_nearest_pairs=12)
+    sub = engine.subgraph_csr_device(pairs, G, sta, src)
+    N = sub["n_prod"]
+    assert S * 12 <= N < S * G
+    Slice_p, Mask_p, ea_p = t(rng.random((N, 4))), t(rng.random((N, 4)) < 0.4), t(rng.normal(0, 1, (N, 3)))
+    for train in (False, True):
+        hp = engine.HipPath(S, G, sta, src, grid_order=go, device=DEV, subgraph=sub)
+        hp.set_weights(wd)
+        if train:
+            train_step_and_assoc(hp, Slice_p, Mask_p, ea_p)
+        else:
+            assert bool(torch.isfinite(hp.path_fwd(Slice_p, Mask_p, ea_p, pos)[0]).all())
+        destroy(hp)
+        assert live() == base, ("subgraph", train)
+
+    # argument errors found after allocations were made
+    with pytest.raises(_lib.GenieHipError):
+        engine.HipPath(S, G, sta, src, grid_order=np.full(G, G), device=DEV)           # 15-neighbour graph: the order is read for src_tab
+    assert live() == base
+    bad = dict(sub, seg_rowptr=sub["seg_rowptr"].clone())
+    bad["seg_rowptr"][-1] += 1
+    with pytest.raises(_lib.GenieHipError):
+        engine.HipPath(S, G, sta, src, grid_order=go, device=DEV, subgraph=bad)
+    assert live() == base
+    hp = cartesian(sta_order=engine.morton_order(geom.locs))
+    hp.path_fwd(Slice, Mask, ea, pos)
+    torch.cuda.synchronize()
+    assert set_order(hp, np.zeros(S)) != 0                     # not a permutation: the installed order is gone, none is installed
+    none = engine.HipPath(S, G, sta, src, grid_order=go, device=DEV)
+    assert lib.genie_set_station_order(none.ctx, None) == 0    # (HipPath installs the identity order by default)
+    none.set_weights(wd)
+    assert torch.equal(hp.path_fwd(Slice, Mask, ea, pos)[0], none.path_fwd(Slice, Mask, ea, pos)[0])
+    destroy(hp)
+    destroy(none)
+    assert live() == base
+
+
 def test_edge_attr_and_node_tables_as_callables_equal_the_tensor_forms():
     """`set_adjacencies_base(..., edge_attr=callable)` and `node_rows(callable)` evaluate the caller's function for the source nodes the
     model holds, block by block (what keeps config 4's 1.2 GB `edge_attr` and 0.8 GB travel-time table off every rank of a sharded job);
