@@ -21,7 +21,7 @@ travel-time table stay resident on the device and every window's `Slice/Mask` is
 import numpy as np
 import torch
 
-from . import synthetic
+from . import engine, synthetic
 
 
 def window_schedule(pick_times, max_t, day_len=86400.0, t_win=6.0, n_resolution=9, step_size="half"):
@@ -94,6 +94,57 @@ def window_columns(tsteps_abs, t0, offsets, drop_last, ascending=None):
     return ip[keep].astype(np.int64), keep
 
 
+def window_cols_table(tsteps_abs, times, offsets, drop_last, ascending=None):
+    """The `cols` table of `genie_stack_windows` for a list of window starts: int32 [len(times), len(offsets)], entry [w, j] = the
+    column of `Out_2` offset j of window w adds to (`window_columns`), or -1 where the offset adds nothing: the last offset of
+    step_size 'half' (`drop_last`) and every occurrence but the last of a column one window lists twice."""
+    tsteps_abs = np.asarray(tsteps_abs, dtype=np.float64)
+    if ascending is None:
+        ascending = is_ascending(tsteps_abs)
+    table = np.full((len(times), len(offsets)), -1, dtype=np.int32)
+    for w, t0 in enumerate(times):
+        cols, keep = window_columns(tsteps_abs, t0, offsets, drop_last, ascending)
+        table[w, keep] = cols
+    return table
+
+
+def window_blocks(n, world):
+    """[(lo, hi)] * world: `range(n)` cut into `world` contiguous blocks whose lengths differ by at most one (the longer ones
+    first; blocks are empty only when n < world). Rank r of a window-parallel apply loop takes windows [lo_r, hi_r)."""
+    n, world = int(n), int(world)
+    if n < 0 or world < 1:
+        raise ValueError("window_blocks needs n >= 0 and world >= 1")
+    base, extra = divmod(n, world)
+    blocks, lo = [], 0
+    for r in range(world):
+        hi = lo + base + (1 if r < extra else 0)
+        blocks.append((lo, hi))
+        lo = hi
+    return blocks
+
+
+def window_parallel_info(cols, n_cols, world):
+    """What a window-parallel run over `world` ranks does with the windows of a `cols` table (`window_cols_table`, [n, T], -1 = no
+    column), on the host: a dict with `world`; `windows` [(lo, hi)] per rank (`window_blocks`); `columns` [(c_min, c_max) or None for a rank
+    without windows] per rank; `ranks_per_column` int32 [n_cols] = how many ranks add to each column of `Out_2`; and `exact_merge` = no
+    column is fed by more than two ranks. Then every element's sum over the ranks has at most two non-zero terms; adding zeros is exact and
+    fp32 addition commutes, so the merged `Out_2` does not depend on the order in which the collective adds the ranks' partials.
+    False for tiny days (fewer windows per rank than windows per column) or a `times` list that does not ascend: the merge is then still
+    the right sum, up to rounding that depends on the collective. (A `tsteps_abs` that does not ascend only relabels the columns: the
+    flag is the one of the sorted axis, while a rank's column RANGE can then span the whole axis.)"""
+    cols = np.asarray(cols)
+    blocks = window_blocks(cols.shape[0], world)
+    per_col = np.zeros(int(n_cols), dtype=np.int32)
+    ranges = []
+    for lo, hi in blocks:
+        c = np.unique(cols[lo:hi])
+        c = c[c >= 0]
+        per_col[c] += 1
+        ranges.append((int(c[0]), int(c[-1])) if c.size else None)
+    return {"world": int(world), "windows": blocks, "columns": ranges, "ranks_per_column": per_col,
+            "exact_merge": bool(per_col.max(initial=0) <= 2)}
+
+
 def picks_in_embed_range(pick_times_sorted, t0, max_t, kernel_sig_t):
     """[lo, hi) of the picks with t0 - 2 sigma < t < t0 + max_t + 2 sigma (process_utils.py:476); the reference skips a window
     whose range is empty (process_continuous_days.py:792-793)."""
@@ -144,14 +195,45 @@ def apply_windows(net, geom, P, tsteps_abs=None, t_win=6.0, step_size="half", mi
 
 def apply_windows_device(net, geom, P, trv_times, tsteps_abs=None, t_win=6.0, step_size="half", min_required_picks=1,
                          n_grids=1.0, day_len=86400.0, kernel_sig_t=synthetic.KERNEL_SIG_T, dt_embed=None, max_t=None,
-                         times=None, tail_batch=16, pairs=None):
+                         times=None, tail_batch=16, pairs=None, stack_on_device=False, window_parallel=None, return_info=False,
+                         merge_timeout=60.0):
     """GPU-only apply loop: `P` [n,5] (t, station index in the model's station order, amp, prob, phase) sorted by time,
     `trv_times` [G, S, 2] theoretical travel times; `pairs` [2, N] (station, source) = the product nodes of a `use_subgraph` model
     (`A_src_in_sta`), whose Slice / Mask rows follow that list. Returns (Out_2 on device, window start times used). `tail_batch`: windows
     per G-sized tail (1..16; 16 is the default of the bench and measured best with the device embedding in the loop, bench.py --mode
-    stream: the tail kernels are latency-bound, their fixed costs are paid once per batch)."""
+    stream: the tail kernels are latency-bound, their fixed costs are paid once per batch).
+
+    `stack_on_device`: accumulate into `Out_2` with ONE `genie_stack_windows` launch per flush (per window when `window_batch == 1`)
+    instead of a slice, a scaling and an `index_add_` per window; same side stream, same event chain, same summation order, bit-equal
+    `Out_2`.
+
+    `window_parallel`: split the day's windows over GPUs. `(rank, world)`, or a `torch.distributed`
+    process group (True: the default group). After all filters, rank r takes the contiguous block `window_blocks(len(times), world)[r]`
+    of the final `times` and stacks it (on the device: `stack_on_device` is implied) into a zero-initialised full-size `Out_2`.
+    * tuple form: no collective; returns (this rank's partial `Out_2`, this rank's `times`) -- for a caller with its own transport.
+    * group form: one `all_reduce(SUM)` of the partials (in place on the device over "nccl"; staged through the host over gloo, where
+      the wait ends after `merge_timeout` seconds; an RCCL group carries the finite timeout it was initialised with); every rank returns
+      the full `Out_2` and the full `times`.
+    Against one GPU the merged `Out_2` is bit-equal in every column fed by one rank's windows only; in a column at a block boundary it is
+    `fl(prefix) + fl(suffix)` of that column's window contributions instead of one running sum, a difference of rounding only. With
+    step_size 'half' or 'full' on the default schedule a column has at most two contributions, so the whole `Out_2` is bit-equal.
+    `return_info`: a third return value, `window_parallel_info` of this run plus `rank` (its `exact_merge` tells whether the merged
+    bits are independent of the collective's reduction order). A source-sharded model cannot be combined with `window_parallel`.
+    No multi-GPU speed-up has been measured: ranks sharing one GPU say nothing about it, and the first run on N > 1 GPUs is still ahead
+    (DESIGN.md section 9.1)."""
     hp = net._hip
     sharded = getattr(net, "is_sharded", False)       # source-node-sharded model: this rank embeds and runs its owned + halo rows only;
+    wp = None
+    if window_parallel is not None and window_parallel is not False:
+        if sharded:
+            raise NotImplementedError("window_parallel on a source-node-sharded model: the hybrid of window-parallel replicas and "
+                                      "source-node shards is not built; use an unsharded model per GPU")
+        from . import dist as _dist
+        if isinstance(window_parallel, (tuple, list)):
+            wp = _dist.resolve_shard(shard=window_parallel) + (False,)
+        else:
+            wp = _dist.resolve_shard(process_group=window_parallel) + (True,)
+        stack_on_device = True
     net.window_batch = 1 if sharded else tail_batch   # the tail follows the shard's all-gather, one per window (module.py docstring)
     dev = hp.device
     max_t = float(max_t if max_t is not None else np.ceil(trv_times.max() + 1.0))
@@ -187,15 +269,35 @@ def apply_windows_device(net, geom, P, trv_times, tsteps_abs=None, t_win=6.0, st
     nonempty = hi > lo                                                                             # process_continuous_days.py:792-793
     times, lo, hi = times[nonempty], lo[nonempty], hi[nonempty]
     asc = is_ascending(tsteps_abs)
-    wc = [window_columns(tsteps_abs, t0, offsets, drop_last, asc) for t0 in times]
-    n_off = len(offsets) - (1 if drop_last else 0)
-    if all(len(k) == n_off for _, k in wc):            # the usual case: no duplicate column inside a window
-        cols = torch.from_numpy(np.stack([c_ for c_, _ in wc]) if wc else np.zeros((0, n_off), dtype=np.int64)).to(dev)
-        keeps = None
+    all_times, info = times, None
+    if return_info:                                     # (the table of ALL windows: a rank's loop needs its own block's rows only)
+        rank, world = wp[:2] if wp is not None else (0, 1)
+        info = dict(window_parallel_info(window_cols_table(tsteps_abs, times, offsets, drop_last, asc), len(tsteps_abs), world), rank=rank)
+    if wp is not None:                                  # this rank's contiguous block of the final window list
+        b_lo, b_hi = window_blocks(len(times), wp[1])[wp[0]]
+        times, lo, hi = times[b_lo:b_hi], lo[b_lo:b_hi], hi[b_lo:b_hi]
+    if stack_on_device:
+        # the whole loop's [n, T] column table once (-1: an offset that adds nothing); a flush hands the kernel its rows of it
+        h_cols = window_cols_table(tsteps_abs, times, offsets, drop_last, asc)
+        d_cols = torch.from_numpy(h_cols).to(dev)
+        scale = float(np.float32(1.0) / np.float32(n_overlap * n_grids))   # `tensor / host scalar` in torch: times the fp32 reciprocal
     else:
-        cols = [torch.from_numpy(c_).to(dev) for c_, _ in wc]
-        keeps = [torch.from_numpy(k_).to(dev) for _, k_ in wc]
+        wc = [window_columns(tsteps_abs, t0, offsets, drop_last, asc) for t0 in times]
+        n_off = len(offsets) - (1 if drop_last else 0)
+        if all(len(k) == n_off for _, k in wc):            # the usual case: no duplicate column inside a window
+            cols = torch.from_numpy(np.stack([c_ for c_, _ in wc]) if wc else np.zeros((0, n_off), dtype=np.int64)).to(dev)
+            keeps = None
+        else:
+            cols = [torch.from_numpy(c_).to(dev) for c_, _ in wc]
+            keeps = [torch.from_numpy(k_).to(dev) for _, k_ in wc]
     acc_done = [None]
+
+    def stack(x, first):                # x [n, Q, T, 1] (or one window's [Q, T, 1]) -> Out_2, windows first.. in order, one launch
+        n = x.shape[0] if x.dim() == 4 else 1
+        used = h_cols[first:first + n]
+        used = used[used >= 0]
+        if used.size:
+            engine.stack_windows(Out_2, x, d_cols[first:first + n], scale, int(used.min()), int(used.max()))
 
     def window_vals(xw, w):             # xw [Q, T, 1] of window w -> the kept offsets
         if keeps is not None:
@@ -209,8 +311,11 @@ def apply_windows_device(net, geom, P, trv_times, tsteps_abs=None, t_win=6.0, st
         with torch.cuda.stream(hp.side_stream):
             if acc_done[0] is not None:
                 hp.side_stream.wait_event(acc_done[0])
-            for k in range(x.shape[0]):
-                Out_2.index_add_(1, cols[first + k], window_vals(x[k], first + k) / (n_overlap * n_grids))
+            if stack_on_device:
+                stack(x, first)
+            else:
+                for k in range(x.shape[0]):
+                    Out_2.index_add_(1, cols[first + k], window_vals(x[k], first + k) / (n_overlap * n_grids))
             acc_done[0] = torch.cuda.Event()
             acc_done[0].record(hp.side_stream)
 
@@ -225,7 +330,10 @@ def apply_windows_device(net, geom, P, trv_times, tsteps_abs=None, t_win=6.0, st
                 with torch.cuda.stream(hp.side_stream):
                     if acc_done[0] is not None:
                         hp.side_stream.wait_event(acc_done[0])
-                    Out_2.index_add_(1, cols[w], window_vals(x, w) / (n_overlap * n_grids))
+                    if stack_on_device:
+                        stack(x, w)
+                    else:
+                        Out_2.index_add_(1, cols[w], window_vals(x, w) / (n_overlap * n_grids))
                     acc_done[0] = torch.cuda.Event()
                     acc_done[0].record(hp.side_stream)
             elif net.push_window(Slice, Mask) == net.window_batch or w == len(times) - 1:
@@ -236,7 +344,24 @@ def apply_windows_device(net, geom, P, trv_times, tsteps_abs=None, t_win=6.0, st
     torch.cuda.current_stream(dev).synchronize()
     for h in net._contexts():
         h.check_input_range()
-    return Out_2, times
+    if wp is not None and wp[3]:        # group form: one all-reduce of the ranks' partials; every rank gets the day
+        _merge_partials(Out_2, wp[2], merge_timeout)
+        times = all_times
+    return (Out_2, times, info) if return_info else (Out_2, times)
+
+
+def _merge_partials(Out_2, group, timeout):
+    """`Out_2` <- sum over the ranks of `group` of their `Out_2`: in place on the device over RCCL ("nccl"), through host memory for a
+    group without device collectives (gloo), as `dist.Transport` stages its collectives; that wait ends after `timeout` seconds."""
+    import datetime
+    import torch.distributed as dist
+    if dist.get_backend(group) == "nccl":
+        dist.all_reduce(Out_2, op=dist.ReduceOp.SUM, group=group)
+        return
+    h = Out_2.cpu()
+    work = dist.all_reduce(h, op=dist.ReduceOp.SUM, group=group, async_op=True)
+    work.wait(datetime.timedelta(seconds=float(timeout)))
+    Out_2.copy_(h)
 
 
 # ---- per-window pick lists (process_utils.py:644-699) and the two other per-day loops of the caller ------------------------------------

@@ -1246,6 +1246,7 @@ __device__ __forceinline__ void gather_sum16(const float* __restrict__ base, lon
 #include "train_assoc_kernels.hpp"
 #include "train_arrival_kernels.hpp"
 #include "detect_kernels.hpp"
+#include "stack_kernels.hpp"
 
 }  // namespace
 
@@ -4044,6 +4045,23 @@ int genie_local_marching(const double* xs, const double* t, const float* val, co
         cur = out;
     }
     k_local_marching_keep<<<nb, 256, 0, st>>>(val, cur, active, (long long)n, (float)tol, keep);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+int genie_stack_windows(const float* x, const int32_t* cols, int n_windows, int64_t n_query, int n_offsets, float scale, float* out,
+                        int64_t n_cols, int64_t c_min, int64_t c_max, void* stream) {
+    if (n_windows < 1 || n_windows > SW_MAX_B || n_offsets < 1 || n_offsets > SW_MAX_T)
+        return fail(GENIE_ERR_ARG, "genie_stack_windows: 1 <= n_windows <= 16 and 1 <= n_offsets <= 64 required");
+    if (n_query < 0 || n_cols < 1 || n_cols >= (1ll << 31) || c_min < 0 || c_max < c_min || c_max >= n_cols)
+        return fail(GENIE_ERR_ARG, "genie_stack_windows: n_query >= 0, 1 <= n_cols < 2^31 and 0 <= c_min <= c_max < n_cols required");
+    if (!cols || (n_query > 0 && (!x || !out))) return fail(GENIE_ERR_ARG, "genie_stack_windows: null argument");
+    if (n_query == 0) return GENIE_OK;
+    const int64_t width = c_max - c_min + 1;
+    const int64_t nb = (n_query * width + 255) / 256;                      // (n_query * width < 2^63: width < 2^31, n_query checked below)
+    if (n_query >= (1ll << 31) || nb >= (1ll << 31)) return fail(GENIE_ERR_ARG, "genie_stack_windows: n_query x (c_max - c_min + 1) too large for one launch");
+    k_stack_windows<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(x, cols, n_windows, (long long)n_query, n_offsets, scale, out, (long long)n_cols,
+                                                                  (int)c_min, (int)width);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }

@@ -51,6 +51,27 @@ def knn_device(x_context, x_query, k, exclude_self=False):
     return out
 
 
+def stack_windows(out, x, cols, scale, c_min, c_max):
+    """`out[q, cols[k, j]] += x[k, q, j] * scale` for k, then j, in order, entries `cols < 0` skipped (genie_stack_windows: one launch
+    on the current stream, no atomics, the bits of the per-window `index_add_` loop). out fp32 [Q, n_cols]; x fp32 [B, Q, T] or
+    [B, Q, T, 1] (B <= 16; a single window's [Q, T(, 1)] is B = 1); cols int32 [B, T] on the device; `[c_min, c_max]` contains every
+    column listed."""
+    lib = _lib.load()
+    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.is_contiguous()):
+        raise ValueError("stack_windows: out must be a contiguous fp32 GPU tensor [n_query, n_cols]")
+    if not (torch.is_tensor(cols) and cols.is_cuda and cols.dtype == torch.int32 and cols.dim() == 2 and cols.is_contiguous()):
+        raise ValueError("stack_windows: cols must be a contiguous int32 GPU tensor [n_windows, n_offsets]")
+    B, T = int(cols.shape[0]), int(cols.shape[1])
+    Q = int(out.shape[0])
+    x = _f32(x, "x")
+    if x.numel() != B * Q * T or tuple(x.shape[:3]) not in ((B, Q, T), (Q, T, 1), (Q, T)):
+        raise ValueError("stack_windows: x %s does not match cols %s and out %s" % (tuple(x.shape), tuple(cols.shape), tuple(out.shape)))
+    with torch.cuda.device(out.device):
+        _lib.check(lib.genie_stack_windows(_ptr(x), _ptr(cols), B, Q, T, float(scale), _ptr(out), int(out.shape[1]), int(c_min), int(c_max),
+                                           _stream()), "genie_stack_windows")
+    return out
+
+
 def knn_graph_device(points, k):
     """Base kNN graph of a point set on the device: the layout of `remove_self_loops(knn(x, x, k + 1).flip(0))`
     (process_utils.py:718-719) as (table int32 [n, k], edge list int64 [2, n * k] with row 0 = neighbour, row 1 = centre)."""

@@ -569,6 +569,20 @@ size_t genie_local_marching_scratch_bytes(int64_t n);
 int genie_local_marching(const double* xs, const double* t, const float* val, const int32_t* group, int64_t n, double tc_win,
                          double sp_win, int n_steps_max, double tol, int use_directed, void* scratch, uint8_t* keep, void* stream);
 
+/* Stacking of window read-outs into Out_2 (the apply loop's accumulation, process_continuous_days.py:797-805), one launch per flush:
+ *   for k in 0..n_windows-1 (window order), for j in 0..n_offsets-1 (offset order):
+ *       c = cols[k][j];  if c < 0: skip;   out[q, c] += x[k, q, j] * scale   for every query q
+ * x [n_windows, n_query, n_offsets] fp32 (the read-out of genie_tail_batched, or of one window: n_windows = 1); cols [n_windows, n_offsets]
+ * int32 ON THE DEVICE (-1 drops an offset: the last offset of step_size 'half', or all but the last occurrence of a column one window
+ * lists twice); out [n_query, n_cols] fp32, addressed with 64-bit element offsets; [c_min, c_max] = a column range that contains every
+ * entry >= 0 of cols: an entry outside it is ignored, nothing outside out[:, c_min..c_max] is read or written. 1 <= n_windows <= 16,
+ * 1 <= n_offsets <= 64, 1 <= n_cols < 2^31. No atomics: one thread owns one (q, c) and adds its contributions in (k, j) order, the product
+ * rounded to fp32 before the add, so the result is reproducible and carries the bits of `out.index_add_(1, cols_k, x_k * scale)` issued
+ * window by window. `scale`: the caller's fp32 factor (torch divides a tensor by a host scalar d as `x * (1.0f / (float)d)`; pass that
+ * reciprocal to match it). Bad arguments return GENIE_ERR_ARG before any launch. */
+int genie_stack_windows(const float* x, const int32_t* cols, int n_windows, int64_t n_query, int n_offsets, float scale, float* out,
+                        int64_t n_cols, int64_t c_min, int64_t c_max, void* stream);
+
 /* Debug/parity access to intermediates kept in the workspace (which: 0 = c [P,30], 1 = wu [P,15], 2 = wv [P,15]);
  * copies de-padded rows into `out` (async). */
 int genie_ws_export(genie_ctx* ctx, int which, void* ws, float* out, void* stream);
