@@ -189,7 +189,8 @@ __global__ __launch_bounds__(256) void k_nbr_mean(int S, int G, const int32_t* _
     }
 }
 
-// PReLU backward for the training path (one slope per call): dx = dy * (x >= 0 ? 1 : a), da = sum_{x < 0} dy * x. PyTorch's
+// PReLU backward for the training path (one slope per call): dx = x > 0 ? dy : a * dy (PyTorch's convention, and the one of the
+// fused training kernels: the slope applies AT zero, of either sign), da = sum_{x <= 0} dy * x (the terms at zero are 0). PyTorch's
 // own backward materialises a full-size slope gradient and reduces it in a second pass (0.9 ms per [2M, 30] tensor); this
 // is one pass plus a fixed-order two-level sum (deterministic).
 constexpr int PRELU_BLOCKS = 2048;
@@ -203,17 +204,17 @@ __global__ __launch_bounds__(256) void k_prelu_bwd(const float* __restrict__ x, 
         f32x4 o;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const bool neg = xv[k] < 0.f;
-            o[k] = neg ? gv[k] * a : gv[k];
-            acc += neg ? gv[k] * xv[k] : 0.f;
+            const bool pos = xv[k] > 0.f;
+            o[k] = pos ? gv[k] : gv[k] * a;
+            acc += pos ? 0.f : gv[k] * xv[k];
         }
         ((f32x4*)dx)[i] = o;
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {      // tail elements
         const long long i = (n4 << 2) + threadIdx.x;
-        const bool neg = x[i] < 0.f;
-        dx[i] = neg ? dy[i] * a : dy[i];
-        acc += neg ? dy[i] * x[i] : 0.f;
+        const bool pos = x[i] > 0.f;
+        dx[i] = pos ? dy[i] : dy[i] * a;
+        acc += pos ? 0.f : dy[i] * x[i];
     }
     __shared__ float red[256];
     red[threadIdx.x] = acc;

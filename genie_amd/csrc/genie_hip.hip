@@ -3256,6 +3256,8 @@ int genie_nbr_mean_bwd(genie_ctx* c, const float* g_sta, const float* g_src, flo
     if (!c) return fail(GENIE_ERR_ARG, "genie_nbr_mean_bwd: null context");
     if ((g_sta && !dx_sta) || (g_src && !dx_src)) return fail(GENIE_ERR_ARG, "genie_nbr_mean_bwd: input without output");
     if (c->pcsr || c->G_ext != c->G) return fail(GENIE_ERR_STATE, "genie_nbr_mean_bwd: needs an unsharded Cartesian product graph");
+    if (row_floats != 16 && row_floats != 30 && row_floats != 32)      // (before the reversed graphs are built: a refused call changes nothing)
+        return fail(GENIE_ERR_ARG, "genie_nbr_mean_bwd: row_floats must be 16, 30 or 32");
     if (!g_sta && !g_src) return GENIE_OK;
     if (!c->r_sta.rowptr) {     // (the training backward builds them with the pair arrays: ensure_reversed)
         RevGraph sta, src;

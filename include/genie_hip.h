@@ -327,12 +327,14 @@ int genie_embed_window_split(genie_ctx* ctx, const double* pick_t, const int32_t
 /* Neighbour means on the implicit product graph for [P, row_floats] fp32 rows (row_floats = 16 or 32, 16-byte aligned, or 30 = unpadded [P, 30] rows, 8-byte aligned):
  *   out_sta[(g,s)] = mean_k x_sta[(g, sta_nbr_k(s))]      (MessagePassing('mean') over A_in_sta)
  *   out_src[(g,s)] = mean_k x_src[(src_nbr_k(g), s)]      (... over A_in_src; x_src has n_grid_ext * n_sta rows)
- * Either pair may be null. Used by the association heads (DataAggregationAssociationPhase, module.py:395-400), whose
- * per-node Linears run on PyTorch-ROCm; an empty neighbourhood gives 0. */
+ * Either pair may be null; an empty neighbourhood gives 0. A stand-alone building block (the means of
+ * DataAggregationAssociationPhase, module.py:395-400, for a caller who keeps the per-node Linears in PyTorch): the fused
+ * association kernels of this library do not call it. */
 int genie_nbr_mean(genie_ctx* ctx, const float* x_sta, const float* x_src, float* out_sta, float* out_src, int row_floats,
                    void* stream);
-/* Backward of a single-slope PReLU over n contiguous fp32 values (training path): dx = dy * (x >= 0 ? 1 : slope),
- * dslope[0] = sum over x < 0 of dy * x, summed in a fixed order. `scratch` = 2048 floats; pointers 16-byte aligned. */
+/* Backward of a single-slope PReLU over n contiguous fp32 values (training path): dx = x > 0 ? dy : slope * dy
+ * (torch.nn.functional.prelu's backward: the slope applies at x == 0, of either sign), dslope[0] = sum over x <= 0 of dy * x (the
+ * terms at zero add nothing), summed in a fixed order. `scratch` = 2048 floats; pointers 16-byte aligned. */
 int genie_prelu_bwd(const float* x, const float* dy, const float* slope, int64_t n, float* dx, float* dslope, float* scratch,
                     void* stream);
 

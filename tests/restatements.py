@@ -204,3 +204,148 @@ def attach(net):
     for mod, fn in pairs:
         mod.forward = types.MethodType(fn, mod)
     return net
+
+
+# ---- references of the stand-alone training primitives of the C ABI (tests/test_train_primitives_cpu.py pins them, ----------------
+# ---- tests/test_train_primitives_gpu.py compares genie_nbr_mean_bwd / genie_seg_rows with them) ----------------------------------
+U32 = 2.0 ** -24          # unit round-off of fp32
+
+
+def handmade_graph(n, degrees, hub, lonely, self_loop, twice, seed):
+    """Edge list int64 [2, E] (row 0 = neighbour j, row 1 = target i) of a graph with PRESCRIBED in-degrees: target i lists `hub`
+    first (so the hub's out-degree is the number of other targets with a neighbour), then other nodes walking round the ring from i + 1;
+    `lonely` is never listed (nobody's neighbour: its row of the adjoint is exactly 0). Target `self_loop` lists itself and target
+    `twice` lists its second neighbour a second time, both in place of their last neighbour. The edges are shuffled, so grouping
+    them by target is the CSR builder's work."""
+    assert len(degrees) == n and max(degrees) <= n - 1 and hub != lonely
+    edges = []
+    for i, d in enumerate(degrees):
+        nbrs, k = ([hub] if d and i != hub else []), i
+        while len(nbrs) < d:
+            k = (k + 1) % n
+            if k not in (hub, lonely, i):
+                nbrs.append(k)
+        if i == self_loop:
+            assert d >= 2
+            nbrs[-1] = i
+        if i == twice:
+            assert d >= 3
+            nbrs[-1] = nbrs[1]
+        edges += [(j, i) for j in nbrs]
+    g = torch.Generator().manual_seed(seed)
+    return torch.tensor(edges, dtype=torch.long)[torch.randperm(len(edges), generator=g)].t().contiguous()
+
+
+# In-degrees on both sides of the 8-edge chunk of k_nbr_mean (0, 1, 7, 8, 9, 15, 16, 17) in both base graphs. Station 19 / source node
+# 23 are nobody's neighbour; station 8 / source node 10 are the hubs: neighbours of every other target that has one (reversed out-degree
+# 18 / 22); station 3 / source node 3 (in-degree 8) list themselves, station 4 / source node 4 (in-degree 9) one neighbour twice.
+HANDMADE_S, HANDMADE_G = 20, 24
+HANDMADE_STA_DEG = [0, 1, 7, 8, 9, 15, 16, 17, 2, 3, 4, 5, 6, 1, 2, 8, 16, 4, 1, 3]
+HANDMADE_SRC_DEG = [17, 16, 15, 8, 9, 7, 1, 0, 2, 3, 4, 5, 6, 8, 9, 16, 17, 1, 2, 3, 7, 15, 4, 5]
+
+
+def handmade_graphs():
+    """(A_sta [2, E_sta], A_src [2, E_src]) of the 20-station / 24-source-node graphs described above."""
+    return (handmade_graph(HANDMADE_S, HANDMADE_STA_DEG, hub=8, lonely=19, self_loop=3, twice=4, seed=11),
+            handmade_graph(HANDMADE_G, HANDMADE_SRC_DEG, hub=10, lonely=23, self_loop=3, twice=4, seed=12))
+
+
+def power_of_two_ring(n):
+    """Edge list of a ring in which target i has the 1, 2, 4 or 8 (= 2^(i % 4)) following nodes as neighbours: every weight
+    1 / in-degree is a power of two."""
+    return torch.tensor([((i + 1 + k) % n, i) for i in range(n) for k in range(1 << (i % 4))], dtype=torch.long).t().contiguous()
+
+
+def mean_adjacency(edge_index, n, sparse=False):
+    """fp64 matrix of the mean aggregation over a base graph: A[i, j] = (number of edges j -> i) / max(1, in-degree(i)), dense or
+    (large graphs) sparse COO, with the in-degree and the out-degree of every node (edges counted: a neighbour listed twice
+    counts twice)."""
+    j, i = torch.as_tensor(edge_index).long()
+    indeg, outdeg = torch.bincount(i, minlength=n), torch.bincount(j, minlength=n)
+    w = 1.0 / indeg.clamp(min=1).double()
+    if sparse:
+        A = torch.sparse_coo_tensor(torch.stack((i, j)), w[i], (n, n), dtype=torch.float64).coalesce()
+    else:
+        A = torch.zeros((n, n), dtype=torch.float64).index_put_((i, j), w[i], accumulate=True)
+    return A, indeg, outdeg
+
+
+def _apply_along(A, x3, dim, transpose):
+    """y = A x (or A^T x) along dimension `dim` (0: source nodes, 1: stations) of x3 [G, S, C], fp64."""
+    A = A.t() if transpose else A
+    x3 = x3.double()
+    G_, S_, C_ = x3.shape
+    mm = torch.sparse.mm if A.is_sparse else torch.matmul
+    if dim == 0:
+        return mm(A, x3.reshape(G_, S_ * C_)).reshape(G_, S_, C_)
+    return mm(A, x3.permute(1, 0, 2).reshape(S_, G_ * C_)).reshape(S_, G_, C_).permute(1, 0, 2).contiguous()
+
+
+def nbr_mean_ref(A_sta, A_src, x_sta, x_src, S, G):
+    """The neighbour means themselves as fp64 matrix products (rows p = g * S + s): out_sta[g, i] = sum_j A_sta[i, j] x_sta[g, j],
+    out_src[i, s] = sum_j A_src[i, j] x_src[j, s]; either input may be None."""
+    o1 = None if x_sta is None else _apply_along(A_sta, x_sta.view(G, S, -1), 1, False).reshape(G * S, -1)
+    o2 = None if x_src is None else _apply_along(A_src, x_src.view(G, S, -1), 0, False).reshape(G * S, -1)
+    return o1, o2
+
+
+def nbr_mean_adjoint_ref(A_sta, A_src, g_sta, g_src, S, G):
+    """Adjoint of the neighbour means as fp64 matrix products: dx_sta[g, j] = sum_i A_sta[i, j] g_sta[g, i], dx_src[j, s] =
+    sum_i A_src[i, j] g_src[i, s]; either gradient may be None."""
+    d1 = None if g_sta is None else _apply_along(A_sta, g_sta.view(G, S, -1), 1, True).reshape(G * S, -1)
+    d2 = None if g_src is None else _apply_along(A_src, g_src.view(G, S, -1), 0, True).reshape(G * S, -1)
+    return d1, d2
+
+
+def _scale_rows(b, terms_sta, terms_src, S, G):
+    b1, b2 = b
+    if b1 is not None:
+        b1 = (b1.view(G, S, -1) * ((terms_sta.double() + 2) * U32).view(1, S, 1)).reshape(G * S, -1)
+    if b2 is not None:
+        b2 = (b2.view(G, S, -1) * ((terms_src.double() + 2) * U32).view(G, 1, 1)).reshape(G * S, -1)
+    return b1, b2
+
+
+def nbr_mean_adjoint_bound(A_sta, A_src, out_sta, out_src, g_sta, g_src, S, G):
+    """Per-element fp32 error bound of an adjoint row, evaluated in fp64: (n_terms + 2) 2^-24 sum_i |A[i, j] g[i]| with n_terms the
+    node's out-degree. A sum of n products, each with one fp32-rounded weight, carries at most one rounding of the weight, one of
+    the product and n - 1 of the additions per term, whatever the order of the additions: (n + 1) 2^-24 to first order; the + 2
+    covers the second-order terms (n < 2^10 here)."""
+    absol = lambda t: None if t is None else t.abs()
+    return _scale_rows(nbr_mean_adjoint_ref(A_sta, A_src, absol(g_sta), absol(g_src), S, G), out_sta, out_src, S, G)
+
+
+def nbr_mean_bound(A_sta, A_src, in_sta, in_src, x_sta, x_src, S, G):
+    """The same bound for the means themselves, n_terms = the node's in-degree: n - 1 additions, one rounding of 1 / n and one of the
+    product with it, or a rounded weight and product per term."""
+    absol = lambda t: None if t is None else t.abs()
+    return _scale_rows(nbr_mean_ref(A_sta, A_src, absol(x_sta), absol(x_src), S, G), in_sta, in_src, S, G)
+
+
+def gather_mean_rows(x, edge_index, n, dim):
+    """Index-gather formulation of the mean over a (ragged) base graph along dimension `dim` of x [G, S, C]: messages x[j] summed
+    into their targets i by index_add_, divided by max(1, in-degree). Differentiable: its autograd is what the dense adjoint restates."""
+    j, i = torch.as_tensor(edge_index).long()
+    out = torch.zeros_like(x).index_add_(dim, i, x.index_select(dim, j))
+    shape = [1, 1, 1]
+    shape[dim] = n
+    return out / torch.bincount(i, minlength=n).clamp(min=1).to(x.dtype).view(shape)
+
+
+def seg_rows_sequential(erow, etgt, order, ds):
+    """genie_seg_rows in its own summation order, in fp32 on the host (numpy): for every run of equal targets along `order` a row sum
+    s = 0, s += erow[order[k], :30] edge by edge, then ONE addition d_s[target] += s; targets < 0 are dropped. Returns the new d_s."""
+    import numpy as np
+    erow, etgt, order = (np.asarray(a) for a in (erow, etgt, order))
+    ds = np.array(ds, dtype=np.float32, copy=True)
+    assert erow.dtype == np.float32
+    k, n = 0, int(order.shape[0])
+    while k < n:
+        tgt = int(etgt[order[k]])
+        s = np.zeros(30, dtype=np.float32)
+        while k < n and int(etgt[order[k]]) == tgt:
+            s += erow[order[k], :30]
+            k += 1
+        if tgt >= 0:
+            ds[tgt] += s
+    return ds

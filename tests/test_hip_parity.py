@@ -585,8 +585,8 @@ def test_prelu_bwd_matches_autograd(n):
 
 @pytest.mark.parametrize("S,G,C", [(12, 60, 30), (21, 40, 15), (50, 300, 32)])
 def test_nbr_mean_matches_torch_gathers(S, G, C):
-    """genie_nbr_mean (neighbour means of arbitrary [P, C] rows on the product graph, used by the association heads) against the
-    index-gather formulation; (21, 40) uses ragged graphs with an empty neighbourhood."""
+    """genie_nbr_mean (neighbour means of arbitrary [P, C] rows on the product graph; a stand-alone entry point, reached only through
+    `HipPath.nbr_mean` since the association heads run in the fused kernels) against the index-gather formulation; (21, 40) uses ragged graphs with an empty neighbourhood."""
     from tests.restatements import _mean_over_src, _mean_over_sta
     geom = synthetic.Geometry(S, G, L=100e3, n_query=5, seed=S + G)
     A_sta, A_src = geom.A_sta_sta, geom.A_src_src
@@ -615,13 +615,19 @@ def test_nbr_mean_matches_torch_gathers(S, G, C):
         t1 = _mean_over_sta(x1, graph.neighbour_table(A_sta, S).long().to(DEV), S, G)
         t2 = _mean_over_src(x2, graph.neighbour_table(A_src, G).long().to(DEV), S, G)
         assert max_abs(o1, t1) <= 1e-6 and max_abs(o2, t2) <= 1e-6
+    # either pair alone: the same rows, bit for bit
+    only1, none = hp.nbr_mean(x1, None)
+    assert none is None and torch.equal(only1, o1)
+    none, only2 = hp.nbr_mean(None, x2)
+    assert none is None and torch.equal(only2, o2)
 
 
 @pytest.mark.parametrize("name", ["tiny_6x40", "cfg1_20x500"])
 def test_training_mode_forward_and_gradients_match_oracle_autograd(name):
-    """a-8 (first pass): in train() mode with gradients enabled forward_fixed_source takes the differentiable formulation
-    (neighbour means through genie_nbr_mean / genie_nbr_mean_bwd, dense algebra under autograd). Its outputs equal the fused
-    HIP path and the gradient of a random linear functional of (y, x) w.r.t. every parameter of the path equals the oracle's
+    """a-8: in train() mode with gradients enabled forward_fixed_source runs as one autograd node over the fused HIP training
+    passes (module._PathTrain: genie_da_train_fwd + genie_tail_train_fwd forward, genie_train_bwd backward; the stand-alone
+    genie_nbr_mean / genie_nbr_mean_bwd of the first training path are no longer called here, tests/test_train_primitives_gpu.py
+    covers them). Its outputs equal the fused inference path and the gradient of a random linear functional of (y, x) w.r.t. every parameter of the path equals the oracle's
     autograd gradient (fp32 CPU) to 1e-5 of the gradient scale."""
     from oracle import genie_oracle as O
     c = Case(name)
