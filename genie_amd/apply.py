@@ -494,8 +494,60 @@ def _pinned_pair(n, device):
     return _PINNED[key]
 
 
+def _source_parallel(source_parallel, legs):
+    """(rank, world, group, is_group) of a `source_parallel` argument -- `(rank, world)`, a `torch.distributed` process group or True
+    for the default group: the three forms of `window_parallel` -- or None. Checked before anything touches a device."""
+    if source_parallel is None or source_parallel is False:
+        return None
+    if any(getattr(leg.net, "is_sharded", False) for leg in legs):
+        raise NotImplementedError("source_parallel on a source-node-sharded model: the hybrid of source-parallel replicas and "
+                                  "source-node shards is not built; use an unsharded model per GPU")
+    from . import dist as _dist
+    if isinstance(source_parallel, (tuple, list)):
+        return _dist.resolve_shard(shard=source_parallel) + (False,)
+    return _dist.resolve_shard(process_group=source_parallel) + (True,)
+
+
+def _gather_blocks(rows, blocks, group, timeout):
+    """The ranks' row blocks `rows` (device tensor [hi_r - lo_r, C] on rank r, `blocks` = every rank's (lo, hi)) put together on every
+    rank: host float64 [n, C]. One all-gather of blocks padded to the longest (they differ by at most one row): on the device over RCCL
+    ("nccl"), staged through the host over gloo, where the wait ends after `timeout` seconds -- as `_merge_partials` chooses."""
+    import datetime
+    import torch.distributed as dist
+    b_max = max(hi - lo for lo, hi in blocks)
+    on_device = dist.get_backend(group) == "nccl"
+    mine = rows if on_device else rows.cpu()
+    send = torch.zeros((b_max, rows.shape[1]), dtype=rows.dtype, device=mine.device)
+    send[: mine.shape[0]] = mine
+    parts = [torch.empty_like(send) for _ in blocks]
+    if on_device:
+        dist.all_gather(parts, send, group=group)
+    else:
+        dist.all_gather(parts, send, group=group, async_op=True).wait(datetime.timedelta(seconds=float(timeout)))
+    return torch.cat([p[: hi - lo] for p, (lo, hi) in zip(parts, blocks)]).cpu().numpy()
+
+
+def refined_from_found(found, srcs, tq, ftrns2):
+    """The end of the refine pass on the host: `found` float64 [n, 7] = per source (query row, offset index, value, any query inside the
+    region, the refined query's Cartesian position) as the device branch of `refine_sources` leaves them (the rows of all ranks of a
+    source-parallel pass laid side by side in source order) -> (srcs_refined [n, 5] sorted by origin time, `order`)."""
+    srcs = np.asarray(srcs, dtype=np.float64)
+    found = np.asarray(found, dtype=np.float64).reshape(-1, 7)
+    tq_host = np.asarray(tq.detach().cpu() if torch.is_tensor(tq) else tq, dtype=np.float64).reshape(-1)
+    out = np.zeros((srcs.shape[0], 5))
+    for i in range(srcs.shape[0]):
+        if found[i, 3] == 0.0:
+            raise ValueError("refine_sources: no query of source %d lies inside the region (the reference's argmax raises here too)" % i)
+        out[i, 0:3] = ftrns2(found[i, 4:7].reshape(1, 3))[0]
+        out[i, 3] = srcs[i, 3] + tq_host[int(found[i, 1])]
+        out[i, 4] = found[i, 2]
+    order = np.argsort(out[:, 3])
+    return out[order], order
+
+
 def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offset_range, n_rand_query, ftrns1, ftrns2,
-                   lat_range, lon_range, depth_range, kernel_sig_t=synthetic.KERNEL_SIG_T, dt_embed=None, rand=None, ftrns2_device=None):
+                   lat_range, lon_range, depth_range, kernel_sig_t=synthetic.KERNEL_SIG_T, dt_embed=None, rand=None, ftrns2_device=None,
+                   source_parallel=None, merge_timeout=60.0):
     """The refine pass of the caller (process_continuous_days.py:926-980) on the device: for every candidate source `srcs[i]` = (lat, lon,
     depth, origin time, value) a cloud of `n_rand_query` random queries around it (`ftrns1(src) + rand(n, 3) * X_offset_range +
     X_offset_min`, kept where `ftrns2` of it lies strictly inside the three ranges, :929-936), one `forward_fixed_source` per grid
@@ -508,9 +560,31 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
     GPU tensor [n, 3] (the reference also carries torch forms of its transforms, `ftrns2_diff`): the cloud's arithmetic, the region
     filter and the float32 rounding then run on the device in float64 -- the same values as the numpy path, whose 112 000 x 3 float64
     temporaries per source otherwise make the pass host-bound (37 ms per source at config 2 against ~6 ms of GPU work) -- and only the
-    refined source's own query is transformed back on the host."""
+    refined source's own query is transformed back on the host. In that branch the refined source is picked by ONE kernel per source
+    (`postproc.refine_select_device`: the sum over the legs, the region mask and the nested argmax in one read of the read-outs)
+    instead of ten torch passes over [n_rand_query, n_t]; the host-cloud branch keeps the torch statements, which are its reference.
+
+    `source_parallel`: split the sources over GPUs (needs `ftrns2_device`). `(rank, world)`, or a
+    `torch.distributed` process group (True: the default group) -- the forms of `window_parallel`. Rank r refines the contiguous block
+    `window_blocks(len(srcs), world)[r]` of `srcs`. Every source has its own window, cloud and picks, so the split is exact: a source's
+    row carries the same bits whichever rank computes it. The draws stay those of one GPU because every rank calls `rand` once per
+    source, in source order, and discards the draws of the sources it does not own -- host time only; a
+    caller who wants to save it passes a `rand` that is itself indexed by source.
+    * tuple form: no collective; returns (this rank's rows float64 [hi - lo, 7], (lo, hi)): `refined_from_found` turns the rows of
+      all ranks, concatenated in rank order, into (srcs_refined, order).
+    * group form: one all-gather of the fixed-size rows (`_gather_blocks`; the gloo wait ends after `merge_timeout` seconds), after which
+      every rank finishes identically and returns the same (srcs_refined, order) as one GPU.
+    A rank whose block is empty runs no window and still takes part in the collective; every rank checks the verdicts of its own
+    contexts. A source-sharded model is refused."""
+    sp = _source_parallel(source_parallel, legs)
     rand = rand or np.random.rand
     srcs = np.asarray(srcs, dtype=np.float64)
+    b_lo, b_hi = 0, srcs.shape[0]
+    if sp is not None:
+        if ftrns2_device is None:
+            raise ValueError("refine_sources: source_parallel needs ftrns2_device (the ranks exchange the device branch's fixed-size rows)")
+        blocks = window_blocks(srcs.shape[0], sp[1])
+        b_lo, b_hi = blocks[sp[0]]
     tq_host = np.asarray(tq.detach().cpu() if torch.is_tensor(tq) else tq, dtype=np.float64).reshape(-1)
     dev = legs[0].device
     tq_d = torch.as_tensor(tq_host.reshape(-1, 1)).float().to(dev)
@@ -523,10 +597,18 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
         off_rng_d = torch.as_tensor(np.asarray(X_offset_range, dtype=np.float64).reshape(1, 3), device=dev)
         off_min_d = torch.as_tensor(np.asarray(X_offset_min, dtype=np.float64).reshape(1, 3), device=dev)
         src_cart_d = torch.from_numpy(np.ascontiguousarray(ftrns1(srcs[:, 0:3]), dtype=np.float64)).to(dev) if srcs.shape[0] else None
-        ninf = torch.full((), float("-inf"), dtype=torch.float32, device=dev)
         stage, stage_ev = _pinned_pair(n_rand_query, dev), [None, None]
+        from . import postproc
+        if int(n_rand_query) < 1:
+            raise ValueError("refine_sources: n_rand_query must be >= 1")
+        if len(legs) > postproc.REFINE_SELECT_MAX_LEGS:
+            raise ValueError("refine_sources: at most %d grid legs with ftrns2_device" % postproc.REFINE_SELECT_MAX_LEGS)
+        sel_scratch = postproc.refine_select_scratch(dev)
     with torch.no_grad():
         for i in range(srcs.shape[0]):
+            if not b_lo <= i < b_hi:           # another rank's source: consume its draw, so that the stream is the one of one GPU
+                rand(n_rand_query, 3)
+                continue
             if on_device:
                 # Nothing in this branch waits for the device (round 5, tools/sync_probe_day.py: eight waits per source before -- pageable
                 # copies, the boolean-mask compaction, three tensor-indexed reads): the draw goes through pinned memory, the queries outside
@@ -545,14 +627,23 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
                 keep = ((X1_d[:, 0] > lat_range[0]) & (X1_d[:, 0] < lat_range[1]) & (X1_d[:, 1] > lon_range[0]) & (X1_d[:, 1] < lon_range[1])
                         & (X1_d[:, 2] > depth_range[0]) & (X1_d[:, 2] < depth_range[1]))
                 xq = Xc_d.float()
-            else:
-                Xc = ftrns1(srcs[i, 0:3].reshape(1, -1)) + (rand(n_rand_query, 3) * X_offset_range + X_offset_min)      # :929
-                X1 = ftrns2(Xc)
-                inside = np.where((X1[:, 0] > lat_range[0]) * (X1[:, 0] < lat_range[1]) * (X1[:, 1] > lon_range[0]) * (X1[:, 1] < lon_range[1])
-                                  * (X1[:, 2] > depth_range[0]) * (X1[:, 2] < depth_range[1]))[0]
-                X1, Xc = X1[inside], Xc[inside]
-                clouds.append(X1)
-                xq = torch.from_numpy(np.ascontiguousarray(Xc)).to(dev).float()                                       # torch.Tensor(...) :934 (rounded on the device)
+                # the legs' read-outs stay where the read-out kernel wrote them; one launch pair sums them, masks and selects
+                xs = []
+                for leg in legs:
+                    em = leg.embed(picks, srcs[i, 3], max_t, kernel_sig_t, dt)
+                    if em is None:
+                        continue                                                                                        # :966-967
+                    xs.append(leg.net.forward_fixed_source(em[0], em[1], None, None, None, locs_d, leg.x_grid_cart, xq, tq_d)[1].contiguous())
+                sel = postproc.refine_select_device(xs, (xq.shape[0], tq_host.shape[0]), keep, n_scale, scratch=sel_scratch)  # :972-978
+                found.append(torch.cat((sel, Xc_d.index_select(0, sel[0:1].long()).view(3))))
+                continue
+            Xc = ftrns1(srcs[i, 0:3].reshape(1, -1)) + (rand(n_rand_query, 3) * X_offset_range + X_offset_min)      # :929
+            X1 = ftrns2(Xc)
+            inside = np.where((X1[:, 0] > lat_range[0]) * (X1[:, 0] < lat_range[1]) * (X1[:, 1] > lon_range[0]) * (X1[:, 1] < lon_range[1])
+                              * (X1[:, 2] > depth_range[0]) * (X1[:, 2] < depth_range[1]))[0]
+            X1, Xc = X1[inside], Xc[inside]
+            clouds.append(X1)
+            xq = torch.from_numpy(np.ascontiguousarray(Xc)).to(dev).float()                                       # torch.Tensor(...) :934 (rounded on the device)
             acc = torch.zeros((xq.shape[0], tq_host.shape[0]), dtype=torch.float32, device=dev)
             if xq.shape[0]:
                 for leg in legs:
@@ -561,28 +652,31 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
                         continue                                                                                        # :966-967
                     _, x = leg.net.forward_fixed_source(em[0], em[1], None, None, None, locs_d, leg.x_grid_cart, xq, tq_d)
                     acc += x[:, :, 0] / n_scale                                                                         # :972
-            if on_device:
-                accm = torch.where(keep.view(-1, 1), acc, ninf)
-                ip = torch.argmax(accm.max(1)[0]).view(1)                                                               # :976 (first maximum)
-                row = accm.index_select(0, ip)[0]
-                it = torch.argmax(row).view(1)                                                                          # :977
-                found.append(torch.cat((ip.double(), it.double(), row.index_select(0, it).double(), keep.any().double().view(1),
-                                        Xc_d.index_select(0, ip).view(3))))
-            elif xq.shape[0]:
-                ip = torch.argmax(acc.max(1)[0])
-                it = torch.argmax(acc[ip])
+                ip = torch.argmax(acc.max(1)[0])                                                                        # :976 (first maximum)
+                it = torch.argmax(acc[ip])                                                                              # :977
                 found.append(torch.stack((ip.double(), it.double(), acc[ip, it].double())))
             else:
                 found.append(torch.full((3,), float("nan"), dtype=torch.float64, device=dev))
-    found = torch.stack(found).cpu().numpy() if found else np.zeros((0, 7 if on_device else 3))
+    if on_device:
+        rows = torch.stack(found) if found else torch.zeros((0, 7), dtype=torch.float64, device=dev)
+        if sp is not None and sp[3]:
+            found = _gather_blocks(rows, blocks, sp[2], merge_timeout)
+        else:
+            found = rows.cpu().numpy()
+        for leg in legs:       # a copy to the host has waited for the device (after the collective, so that a rank that raises here
+            leg.check()        # leaves no other rank waiting): the verdicts of every window of this rank's pass are in
+        if sp is not None and not sp[3]:
+            return found, (b_lo, b_hi)
+        return refined_from_found(found, srcs, tq_host, ftrns2)
+    found = torch.stack(found).cpu().numpy() if found else np.zeros((0, 3))
     for leg in legs:       # the copy above waited for the device: the verdicts of every window of this pass are in
         leg.check()
     out = np.zeros((srcs.shape[0], 5))
     for i in range(srcs.shape[0]):
-        if (found[i, 3] == 0.0) if on_device else (clouds[i].shape[0] == 0):
+        if clouds[i].shape[0] == 0:
             raise ValueError("refine_sources: no query of source %d lies inside the region (the reference's argmax raises here too)" % i)
         ip, it = int(found[i, 0]), int(found[i, 1])
-        out[i, 0:3] = ftrns2(found[i, 4:7].reshape(1, 3))[0] if on_device else clouds[i][ip]
+        out[i, 0:3] = clouds[i][ip]
         out[i, 3] = srcs[i, 3] + tq_host[it]
         out[i, 4] = found[i, 2]
     order = np.argsort(out[:, 3])
@@ -590,15 +684,23 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
 
 
 def associate_sources(legs, picks, srcs_refined, locs_cart, tq, max_t, trv_out_srcs, ftrns1, x_save, kernel_sig_t=synthetic.KERNEL_SIG_T,
-                      dt_embed=None, t_win=10.0):
+                      dt_embed=None, t_win=10.0, source_parallel=None):
     """The association pass of the caller (process_continuous_days.py:1020-1065) on the device: for every refined source one 4-output
     `forward_fixed` per grid leg on the window that starts at its origin time, with the window's pick lists (`ResidentPicks.pick_inputs`
     = extract_pick_inputs_from_data), ONE spatial query `x_save` (lat, lon of the first node of the reference's coarse map; its depth
     replaced by the source's, :1046) and the source itself as the only candidate (`x_query_src = ftrns1(src)`, `tq_sample = 0`,
     `trv_out_q = trv_out_srcs[[i]]` [1, S, 2], :1052). Returns (Out_p_save, Out_s_save: lists of float32 device tensors [m_i] = the
     P / S association likelihood of every pick of the window, averaged over the legs (:1054-1055); Save_picks: list of host [m_i, 2]
-    (relative time, station, :1042); lp_meta: list of host [m_i, 5]). A window without picks yields empty entries (:1049-1050)."""
+    (relative time, station, :1042); lp_meta: list of host [m_i, 5]). A window without picks yields empty entries (:1049-1050).
+
+    `source_parallel`: as in `refine_sources`; rank r runs the network for the block `window_blocks(len(srcs_refined), world)[r]`.
+    `Save_picks` and `lp_meta` depend on the picks alone, so every rank makes them for ALL sources itself, without a collective.
+    * tuple form: returns (Out_p, Out_s of this rank's block only, Save_picks, lp_meta of all sources, (lo, hi)).
+    * group form: one `all_gather_object` of the blocks' ragged likelihoods through the host (a few thousand floats per source; an
+      RCCL group carries them as byte tensors on the current device); every rank returns the four full lists of one GPU."""
+    sp = _source_parallel(source_parallel, legs)
     srcs = np.asarray(srcs_refined, dtype=np.float64)
+    b_lo, b_hi = window_blocks(srcs.shape[0], sp[1])[sp[0]] if sp is not None else (0, srcs.shape[0])
     dev = legs[0].device
     tq_d = torch.as_tensor(np.asarray(tq.detach().cpu() if torch.is_tensor(tq) else tq, dtype=np.float32).reshape(-1, 1)).to(dev)
     locs_d = torch.as_tensor(locs_cart).float().to(dev)
@@ -618,6 +720,8 @@ def associate_sources(legs, picks, srcs_refined, locs_cart, tq, max_t, trv_out_s
             tp, ip, ph, idx = picks.pick_inputs(srcs[i, 3], max_t, kernel_sig_t, t_win)
             Save_picks.append((tp, ip))
             lp_meta.append(idx)
+            if not b_lo <= i < b_hi:           # another rank's source: its pick lists only
+                continue
             acc_p = torch.zeros(tp.shape[0], dtype=torch.float32, device=dev)
             acc_s = torch.zeros(tp.shape[0], dtype=torch.float32, device=dev)
             Out_p.append(acc_p)
@@ -640,6 +744,15 @@ def associate_sources(legs, picks, srcs_refined, locs_cart, tq, max_t, trv_out_s
         torch.cuda.current_stream(dev).synchronize()      # (windows without picks copy nothing back)
     for leg in legs:       # device-side verdicts (a pick outside the time-pointer table, a station index outside the model) of every call above
         leg.check()
+    if sp is not None and not sp[3]:
+        return Out_p, Out_s, Save_picks, lp_meta, (b_lo, b_hi)
+    if sp is not None:
+        import torch.distributed as dist
+        parts = [None] * sp[1]
+        with torch.cuda.device(dev):
+            dist.all_gather_object(parts, ([o.cpu().numpy() for o in Out_p], [o.cpu().numpy() for o in Out_s]), group=sp[2])
+        Out_p = [torch.from_numpy(o).to(dev) for part in parts for o in part[0]]
+        Out_s = [torch.from_numpy(o).to(dev) for part in parts for o in part[1]]
     return Out_p, Out_s, Save_picks, lp_meta
 
 
@@ -665,7 +778,7 @@ def retained_after_marching(srcs_refined, ftrns1, tc_win, sp_win, scale_depth_cl
 def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, tq, max_t, ftrns1, ftrns2, lat_range, lon_range,
                             depth_range, X_offset_min, X_offset_range, n_rand_query, thresh, src_t_kernel, dt_win, break_win, tc_win,
                             sp_win, scale_depth_clustering=0.2, kernel_sig_t=synthetic.KERNEL_SIG_T, dt_embed=None, t_win_assoc=10.0,
-                            rand=None, ftrns2_device=None, detect_on_device=False):
+                            rand=None, ftrns2_device=None, detect_on_device=False, source_parallel=None):
     """Everything the caller does between the apply loop and the competitive assignment, with the network calls on the device
     (process_continuous_days.py:811-1105): peaks of the device-resident `Out_2` -> time groups -> LocalMarching (`postproc.
     detect_sources`, :811-891), the refine pass (`refine_sources`, :926-982), travel times of the refined sources (`trv(locs, srcs)`
@@ -676,8 +789,17 @@ def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, 
     first marching), `srcs_refined` [m, 5], `trv_out_srcs` (device [m, S, 2]), `Out_p_save`, `Out_s_save` (lists of device tensors),
     `Save_picks`, `lp_meta` (lists of host arrays) -- the inputs of `competitive_assignment`, which is out of scope.
     `detect_on_device`: both LocalMarchings, the distance rule and the grouping run on the GPU (`postproc.detect_sources_device`,
-    `retained_after_marching(device=...)`) instead of on the host; the sources are the same."""
+    `retained_after_marching(device=...)`) instead of on the host; the sources are the same.
+    `source_parallel`: the two per-source passes split over GPUs (`refine_sources`, `associate_sources`: a process group, True for
+    the default one, or `(rank, world)` -- which, having no transport, must have world 1 here). Detection, both LocalMarchings and the
+    `trv` calls are cheap and deterministic and run replicated on every rank; the returned dict equals the one-GPU dict on every rank."""
     from . import postproc
+    sp = _source_parallel(source_parallel, legs)
+    if sp is not None and not sp[3]:
+        if sp[1] != 1:
+            raise ValueError("detect_refine_associate: source_parallel = (rank, world) with world > 1 needs a process group (the "
+                             "association pass reads every rank's refined sources)")
+        source_parallel = None
     dev = legs[0].device
     empty = {"srcs": np.zeros((0, 5)), "srcs_refined": np.zeros((0, 5)), "trv_out_srcs": None, "Out_p_save": [], "Out_s_save": [],
              "Save_picks": [], "lp_meta": []}
@@ -689,12 +811,13 @@ def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, 
     locs_cart = ftrns1(locs)
     locs_d = torch.as_tensor(locs).float().to(dev)
     srcs_refined, _ = refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offset_range, n_rand_query, ftrns1, ftrns2,
-                                     lat_range, lon_range, depth_range, kernel_sig_t, dt_embed, rand, ftrns2_device)
+                                     lat_range, lon_range, depth_range, kernel_sig_t, dt_embed, rand, ftrns2_device,
+                                     source_parallel=source_parallel)
     with torch.no_grad():
         trv_out = trv(locs_d, torch.as_tensor(srcs_refined[:, 0:3]).float().to(dev)).detach()                           # :1004
     x_save = np.array([lat_range[0], lon_range[0], 0.0])                              # xx[0] of the meshgrid of :1008-1014
     Out_p, Out_s, Save_picks, lp_meta = associate_sources(legs, picks, srcs_refined, locs_cart, tq, max_t, trv_out, ftrns1, x_save,
-                                                          kernel_sig_t, dt_embed, t_win_assoc)
+                                                          kernel_sig_t, dt_embed, t_win_assoc, source_parallel=source_parallel)
     keep = retained_after_marching(srcs_refined, ftrns1, tc_win, sp_win, scale_depth_clustering,
                                    device=dev if detect_on_device else None)
     srcs_kept = srcs_refined[keep]

@@ -1247,6 +1247,7 @@ __device__ __forceinline__ void gather_sum16(const float* __restrict__ base, lon
 #include "train_arrival_kernels.hpp"
 #include "detect_kernels.hpp"
 #include "stack_kernels.hpp"
+#include "select_kernels.hpp"
 
 }  // namespace
 
@@ -4064,6 +4065,32 @@ int genie_stack_windows(const float* x, const int32_t* cols, int n_windows, int6
     if (n_query >= (1ll << 31) || nb >= (1ll << 31)) return fail(GENIE_ERR_ARG, "genie_stack_windows: n_query x (c_max - c_min + 1) too large for one launch");
     k_stack_windows<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(x, cols, n_windows, (long long)n_query, n_offsets, scale, out, (long long)n_cols,
                                                                   (int)c_min, (int)width);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+size_t genie_refine_select_scratch_bytes(void) { return (size_t)RS_MAX_WG * sizeof(RsPartial); }
+
+int genie_refine_select(const float* const* x, int n_used, int64_t n_query, int n_t, const uint8_t* keep, float n_scale, void* scratch,
+                        double* out, void* stream) {
+    if (n_used < 0 || n_used > RS_MAX_LEGS) return fail(GENIE_ERR_ARG, "genie_refine_select: 0 <= n_used <= 32 required");
+    if (n_query < 0 || n_t < 1) return fail(GENIE_ERR_ARG, "genie_refine_select: n_query >= 0 and n_t >= 1 required");
+    if (!(n_scale > 0.f) || !dbl_finite((double)n_scale)) return fail(GENIE_ERR_ARG, "genie_refine_select: n_scale must be finite and > 0");
+    if (!out || !scratch || (n_used > 0 && !x)) return fail(GENIE_ERR_ARG, "genie_refine_select: null argument");
+    if ((((uintptr_t)scratch) & 15) != 0 || (((uintptr_t)out) & 7) != 0) return fail(GENIE_ERR_ARG, "genie_refine_select: scratch must be 16-byte and out 8-byte aligned");
+    if (n_query > (int64_t)0x7fffffffffffffffLL / n_t / 2) return fail(GENIE_ERR_ARG, "genie_refine_select: n_query x n_t too large");
+    RsLegs legs;
+    memset(&legs, 0, sizeof(legs));
+    for (int l = 0; l < n_used; ++l) {
+        if (n_query > 0 && !x[l]) return fail(GENIE_ERR_ARG, "genie_refine_select: null read-out pointer");
+        legs.x[l] = x[l];
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const long long n_elem = (long long)n_query * n_t;
+    const int nb = (int)std::min<long long>((n_elem + RS_SPAN - 1) / RS_SPAN, (long long)RS_MAX_WG);
+    RsPartial* part = (RsPartial*)scratch;
+    if (nb > 0) k_refine_select_partial<<<nb, RS_BLOCK, 0, st>>>(legs, n_used, n_elem, n_t, keep, 1.0f / n_scale, part);
+    k_refine_select_final<<<1, RS_BLOCK, 0, st>>>(part, nb, n_t, out);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }

@@ -15,6 +15,9 @@ What runs where:
   the march stay on the GPU, `ftrns1` is applied once to the query positions on the host, and only the surviving [n, 5] rows come
   back. The host functions are their oracle (equal index sets and rows); they differ only where scipy itself is unspecified: of two
   equal peak heights closer than the distance, the device keeps the later column.
+* `refine_select_device` is the end of the refine pass per candidate source (process_continuous_days.py:972-978): the sum of the grid
+  legs' query read-outs, the region mask and the nested first-maximum argmax in one launch pair (`genie_refine_select`,
+  csrc/select_kernels.hpp); the torch statements of `apply.refine_sources` it replaces are its oracle (exact, ties included).
 """
 import ctypes
 
@@ -314,3 +317,45 @@ def _sources_from_peaks(r, c, v, X_query, tsteps_abs, ftrns1, break_win, tc_win,
     xq_d = torch.from_numpy(np.ascontiguousarray(xq[:, 0:3])).to(dev)
     srcs = torch.cat((xq_d[r[keep]], t[keep].reshape(-1, 1), v[keep].double().reshape(-1, 1)), dim=1)
     return srcs.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------------
+# The refine pass's selection of the refined source (genie_refine_select, csrc/select_kernels.hpp).
+# ------------------------------------------------------------------------------------------------
+REFINE_SELECT_MAX_LEGS = 32
+
+
+def refine_select_scratch(device):
+    """The scratch buffer of `refine_select_device` (uint8 GPU tensor, a few KB): a loop over sources allocates it once."""
+    return torch.empty(int(_lib.load().genie_refine_select_scratch_bytes()), dtype=torch.uint8, device=device)
+
+
+def refine_select_device(xs, shape, keep, n_scale, device=None, scratch=None):
+    """The refined source of one query cloud in one launch pair: with `acc = sum over xs, in order, of x / n_scale` (fp32, from zero; the
+    statements `acc += x[:, :, 0] / n_scale` of `apply.refine_sources`) and rows where `keep` is False counted as -inf, returns the fp64 GPU
+    tensor (ip, it, acc[ip, it], any_kept): `ip = argmax(acc.max(1)[0])`, `it = argmax(acc[ip])`, first maximum in both, bit for bit.
+    `xs`: the read-outs of the legs that produced a window, fp32 GPU tensors [Q, n_t] or [Q, n_t, 1], contiguous (their storage is
+    read in place); an empty list is an all-zero `acc`. `shape` = (Q, n_t); `keep`: bool / uint8 GPU tensor [Q] or None (all kept);
+    `n_scale`: the number of legs of the average. Nothing here waits for the device."""
+    Q, n_t = int(shape[0]), int(shape[1])
+    xs = list(xs)
+    if len(xs) > REFINE_SELECT_MAX_LEGS:
+        raise ValueError("refine_select_device: at most %d read-outs per call" % REFINE_SELECT_MAX_LEGS)
+    for x in xs:
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() == Q * n_t
+                and tuple(x.shape[:2]) == (Q, n_t)):
+            raise ValueError("refine_select_device: every read-out must be a contiguous fp32 GPU tensor [%d, %d] or [%d, %d, 1]" % (Q, n_t, Q, n_t))
+    if keep is not None:
+        if not (torch.is_tensor(keep) and keep.is_cuda and keep.dtype in (torch.bool, torch.uint8) and tuple(keep.shape) == (Q,)):
+            raise ValueError("refine_select_device: keep must be a bool or uint8 GPU tensor [%d]" % Q)
+        keep = keep.contiguous()
+    dev = xs[0].device if xs else (keep.device if keep is not None else torch.device("cuda" if device is None else device))
+    lib = _lib.load()
+    if scratch is None:
+        scratch = refine_select_scratch(dev)
+    out = torch.empty(4, dtype=torch.float64, device=dev)
+    ptrs = (ctypes.c_void_p * max(len(xs), 1))(*[x.data_ptr() for x in xs])
+    with torch.cuda.device(dev):
+        _lib.check(lib.genie_refine_select(ptrs, len(xs), Q, n_t, _ptr(keep), float(n_scale), _ptr(scratch), _ptr(out), _stream(dev)),
+                   "genie_refine_select")
+    return out

@@ -585,6 +585,24 @@ int genie_local_marching(const double* xs, const double* t, const float* val, co
 int genie_stack_windows(const float* x, const int32_t* cols, int n_windows, int64_t n_query, int n_offsets, float scale, float* out,
                         int64_t n_cols, int64_t c_min, int64_t c_max, void* stream);
 
+/* Selection of the refined source out of the grid legs' query read-outs (the refine pass, process_continuous_days.py:972-978), one call
+ * per candidate source instead of a chain of full passes over [n_query, n_t]:
+ *   acc[q, t] = fp32 sum over l = 0..n_used-1, in that order and starting from 0.0f, of x[l][q, t] / n_scale, computed as torch computes
+ *               `acc += x_l / n_scale` for a host scalar n_scale: x * (1.0f / n_scale), the product rounded before the add;
+ *   rows with keep[q] == 0 count as -inf (keep NULL: every row is kept);
+ *   ip = the first row whose row maximum equals the global maximum, it = the first column of that row holding its maximum,
+ *   out[0..3] = (ip, it, acc[ip, it], any_kept) as fp64; any_kept = 1 when a kept row exists, else 0 and out = (0, 0, -inf, 0).
+ * x: HOST array of n_used device pointers, each to fp32 [n_query, n_t] (row-major, 64-bit element offsets); the pointers travel in the
+ * kernel arguments, so the call copies nothing and never waits. n_used = the legs that produced a window, 0 <= n_used <= 32 (0: acc is
+ * all zero, the first kept row and column 0 win); n_scale = the number of legs of the average, finite and > 0. keep [n_query] uint8 on
+ * the device. scratch: genie_refine_select_scratch_bytes() bytes on the device, 16-byte aligned, contents irrelevant before and after.
+ * Equal to the nested argmax bit for bit, ties included; no atomics, the result does not depend on scheduling. NaN inputs are out of
+ * scope (the read-outs are finite sigmoid outputs; the library is built without NaN semantics). n_query >= 0, n_t >= 1. Bad arguments
+ * (a null pointer, a negative count, n_t < 1, n_used > 32, n_scale <= 0) return GENIE_ERR_ARG before any launch. */
+size_t genie_refine_select_scratch_bytes(void);
+int genie_refine_select(const float* const* x, int n_used, int64_t n_query, int n_t, const uint8_t* keep, float n_scale, void* scratch,
+                        double* out, void* stream);
+
 /* Debug/parity access to intermediates kept in the workspace (which: 0 = c [P,30], 1 = wu [P,15], 2 = wv [P,15]);
  * copies de-padded rows into `out` (async). */
 int genie_ws_export(genie_ctx* ctx, int which, void* ws, float* out, void* stream);
