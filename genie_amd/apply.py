@@ -18,6 +18,9 @@ nearest-pick semantics of `process_utils.py:262-275`). `apply_windows_device` is
 travel-time table stay resident on the device and every window's `Slice/Mask` is produced by `genie_embed_window`
 (`extract_input_from_data`, `process_utils.py:460-642`), so a window costs no host->device copy at all.
 """
+import collections
+import threading
+
 import numpy as np
 import torch
 
@@ -153,6 +156,40 @@ def picks_in_embed_range(pick_times_sorted, t0, max_t, kernel_sig_t):
     return lo, hi
 
 
+_RankSplit = collections.namedtuple("_RankSplit", "rank world group collective")
+
+
+def _rank_split(parallel, name, sharded):
+    """`_RankSplit(rank, world, group, collective)` of a `window_parallel` / `source_parallel` argument (`name` in messages) -- `(rank,
+    world)`: no collective; a `torch.distributed` process group or True for the default group: collective -- or None. `sharded`: a model
+    involved is source-node-sharded, which is refused. Checked before anything touches a device."""
+    if parallel is None or parallel is False:
+        return None
+    if sharded:
+        raise NotImplementedError("%s on a source-node-sharded model: the hybrid of %s replicas and source-node shards is not built; "
+                                  "use an unsharded model per GPU" % (name, name.replace("_", "-")))
+    from . import dist as _dist
+    if isinstance(parallel, (tuple, list)):
+        return _RankSplit(*_dist.resolve_shard(shard=parallel), collective=False)
+    return _RankSplit(*_dist.resolve_shard(process_group=parallel), collective=True)
+
+
+def _day_schedule(P, max_t, day_len, t_win, step_size, min_required_picks, tsteps_abs, times=None):
+    """(tsteps_abs, times, offsets, n_overlap) of a day's apply loop: the reference's axis and kept window starts, or the caller's own."""
+    tsteps, offsets, step, n_overlap, dt_win = window_schedule(P[:, 0], max_t, day_len, t_win, 9, step_size)
+    if tsteps_abs is None:
+        tsteps_abs = np.arange(tsteps.min() - t_win / 2.0, tsteps.max() + t_win / 2.0 + dt_win, dt_win)
+    if times is None:
+        times = windows_with_enough_picks(P[:, 0], tsteps, max_t, t_win, min_required_picks)
+    return tsteps_abs, np.asarray(times, dtype=np.float64), offsets, n_overlap
+
+
+def _check_verdicts(net):
+    """Raise what the device-side checks of the completed calls found, on every context of the model (a shard's local one included)."""
+    for hp in net._contexts():
+        hp.check_input_range()
+
+
 def apply_windows(net, geom, P, tsteps_abs=None, t_win=6.0, step_size="half", min_required_picks=1, n_grids=1.0,
                   day_len=86400.0, device=None, embed=None):
     """Run `net.forward_fixed_source` over every kept window and stack the query read-out into `Out_2[Q, len(tsteps_abs)]`.
@@ -162,10 +199,7 @@ def apply_windows(net, geom, P, tsteps_abs=None, t_win=6.0, step_size="half", mi
     """
     dev = device or next(net.parameters()).device
     max_t = geom.max_t
-    tsteps, offsets, step, n_overlap, dt_win = window_schedule(P[:, 0], max_t, day_len, t_win, 9, step_size)
-    if tsteps_abs is None:
-        tsteps_abs = np.arange(tsteps.min() - t_win / 2.0, tsteps.max() + t_win / 2.0 + dt_win, dt_win)
-    times = windows_with_enough_picks(P[:, 0], tsteps, max_t, t_win, min_required_picks)
+    tsteps_abs, times, offsets, n_overlap = _day_schedule(P, max_t, day_len, t_win, step_size, min_required_picks, tsteps_abs)
     Out_2 = torch.zeros((geom.x_query.shape[0], len(tsteps_abs)), dtype=torch.float32, device=dev)
     locs = torch.from_numpy(geom.locs).float().to(dev)
     xg = torch.from_numpy(geom.x_grid).float().to(dev)
@@ -223,27 +257,13 @@ def apply_windows_device(net, geom, P, trv_times, tsteps_abs=None, t_win=6.0, st
     (DESIGN.md section 9.1)."""
     hp = net._hip
     sharded = getattr(net, "is_sharded", False)       # source-node-sharded model: this rank embeds and runs its owned + halo rows only;
-    wp = None
-    if window_parallel is not None and window_parallel is not False:
-        if sharded:
-            raise NotImplementedError("window_parallel on a source-node-sharded model: the hybrid of window-parallel replicas and "
-                                      "source-node shards is not built; use an unsharded model per GPU")
-        from . import dist as _dist
-        if isinstance(window_parallel, (tuple, list)):
-            wp = _dist.resolve_shard(shard=window_parallel) + (False,)
-        else:
-            wp = _dist.resolve_shard(process_group=window_parallel) + (True,)
-        stack_on_device = True
+    wp = _rank_split(window_parallel, "window_parallel", sharded)
+    stack_on_device = stack_on_device or wp is not None
     net.window_batch = 1 if sharded else tail_batch   # the tail follows the shard's all-gather, one per window (module.py docstring)
     dev = hp.device
     max_t = float(max_t if max_t is not None else np.ceil(trv_times.max() + 1.0))
-    dt_embed = float(dt_embed if dt_embed is not None else np.round(kernel_sig_t / 10.0, 2))      # process_continuous_days.py:608
-    tsteps, offsets, step, n_overlap, dt_win = window_schedule(P[:, 0], max_t, day_len, t_win, 9, step_size)
-    if tsteps_abs is None:
-        tsteps_abs = np.arange(tsteps.min() - t_win / 2.0, tsteps.max() + t_win / 2.0 + dt_win, dt_win)
-    if times is None:
-        times = windows_with_enough_picks(P[:, 0], tsteps, max_t, t_win, min_required_picks)
-    times = np.asarray(times, dtype=np.float64)
+    dt_embed = _dt_embed(kernel_sig_t, dt_embed)
+    tsteps_abs, times, offsets, n_overlap = _day_schedule(P, max_t, day_len, t_win, step_size, min_required_picks, tsteps_abs, times)
     order = np.argsort(P[:, 0], kind="stable")
     Ps = P[order]
     d_t = torch.from_numpy(Ps[:, 0].copy()).to(dev)
@@ -271,10 +291,10 @@ def apply_windows_device(net, geom, P, trv_times, tsteps_abs=None, t_win=6.0, st
     asc = is_ascending(tsteps_abs)
     all_times, info = times, None
     if return_info:                                     # (the table of ALL windows: a rank's loop needs its own block's rows only)
-        rank, world = wp[:2] if wp is not None else (0, 1)
+        rank, world = (wp.rank, wp.world) if wp is not None else (0, 1)
         info = dict(window_parallel_info(window_cols_table(tsteps_abs, times, offsets, drop_last, asc), len(tsteps_abs), world), rank=rank)
     if wp is not None:                                  # this rank's contiguous block of the final window list
-        b_lo, b_hi = window_blocks(len(times), wp[1])[wp[0]]
+        b_lo, b_hi = window_blocks(len(times), wp.world)[wp.rank]
         times, lo, hi = times[b_lo:b_hi], lo[b_lo:b_hi], hi[b_lo:b_hi]
     if stack_on_device:
         # the whole loop's [n, T] column table once (-1: an offset that adds nothing); a flush hands the kernel its rows of it
@@ -292,29 +312,25 @@ def apply_windows_device(net, geom, P, trv_times, tsteps_abs=None, t_win=6.0, st
             keeps = [torch.from_numpy(k_).to(dev) for _, k_ in wc]
     acc_done = [None]
 
-    def stack(x, first):                # x [n, Q, T, 1] (or one window's [Q, T, 1]) -> Out_2, windows first.. in order, one launch
-        n = x.shape[0] if x.dim() == 4 else 1
-        used = h_cols[first:first + n]
-        used = used[used >= 0]
-        if used.size:
-            engine.stack_windows(Out_2, x, d_cols[first:first + n], scale, int(used.min()), int(used.max()))
-
     def window_vals(xw, w):             # xw [Q, T, 1] of window w -> the kept offsets
         if keeps is not None:
             return xw[:, keeps[w], 0]
         return xw[:, :-1, 0] if drop_last else xw[:, :, 0]
 
-    def flush(first):
-        # tail + read-outs of the pushed windows in one set of launches on a side stream; the accumulation into Out_2 follows
-        # on that stream, window by window and batch by batch in order (overlapping columns: a fixed summation order)
-        y, x, _ = net.flush_windows(xg, xq, tq)
+    def accumulate(x, first):
+        # x [n, Q, T, 1] of windows first .. first + n - 1 -> Out_2, on the side stream the forward / flush call before this one set:
+        # window by window and batch by batch in order (overlapping columns: a fixed summation order), each behind the one before it
+        n = x.shape[0]
         with torch.cuda.stream(hp.side_stream):
             if acc_done[0] is not None:
                 hp.side_stream.wait_event(acc_done[0])
-            if stack_on_device:
-                stack(x, first)
+            if stack_on_device:         # one launch
+                used = h_cols[first:first + n]
+                used = used[used >= 0]
+                if used.size:
+                    engine.stack_windows(Out_2, x, d_cols[first:first + n], scale, int(used.min()), int(used.max()))
             else:
-                for k in range(x.shape[0]):
+                for k in range(n):
                     Out_2.index_add_(1, cols[first + k], window_vals(x[k], first + k) / (n_overlap * n_grids))
             acc_done[0] = torch.cuda.Event()
             acc_done[0].record(hp.side_stream)
@@ -325,27 +341,19 @@ def apply_windows_device(net, geom, P, trv_times, tsteps_abs=None, t_win=6.0, st
             a, b = int(lo[w]), int(hi[w])
             Slice, Mask = net.embed_window(d_t[a:b], d_sta[a:b], d_ph[a:b], float(t0), max_t, kernel_sig_t, dt_embed, d_trv,
                                            presplit=True)    # the push below is the only consumer of (Slice, Mask)
-            if net.window_batch == 1:     # one tail per window (forward_fixed_source_pipelined), accumulated in window order
-                y, x, _ = net.forward_fixed_source_pipelined(Slice, Mask, None, None, None, locs, xg, xq, tq)
-                with torch.cuda.stream(hp.side_stream):
-                    if acc_done[0] is not None:
-                        hp.side_stream.wait_event(acc_done[0])
-                    if stack_on_device:
-                        stack(x, w)
-                    else:
-                        Out_2.index_add_(1, cols[w], window_vals(x, w) / (n_overlap * n_grids))
-                    acc_done[0] = torch.cuda.Event()
-                    acc_done[0].record(hp.side_stream)
+            if net.window_batch == 1:     # one tail per window: the batch of one (a view, no launch)
+                x = net.forward_fixed_source_pipelined(Slice, Mask, None, None, None, locs, xg, xq, tq)[1].unsqueeze(0)
             elif net.push_window(Slice, Mask) == net.window_batch or w == len(times) - 1:
-                flush(first)
-                first = w + 1
+                x = net.flush_windows(xg, xq, tq)[1]      # tail + read-outs of the pushed windows in one set of launches
+            else:
+                continue
+            accumulate(x, first)
+            first = w + 1
         hp.wait_tails()
-    # the verdicts of the day's last windows, on every context of the model (a shard's local one included): one wait per day
-    torch.cuda.current_stream(dev).synchronize()
-    for h in net._contexts():
-        h.check_input_range()
-    if wp is not None and wp[3]:        # group form: one all-reduce of the ranks' partials; every rank gets the day
-        _merge_partials(Out_2, wp[2], merge_timeout)
+    torch.cuda.current_stream(dev).synchronize()      # the verdicts of the day's last windows: one wait per day
+    _check_verdicts(net)
+    if wp is not None and wp.collective:        # group form: one all-reduce of the ranks' partials; every rank gets the day
+        _merge_partials(Out_2, wp.group, merge_timeout)
         times = all_times
     return (Out_2, times, info) if return_info else (Out_2, times)
 
@@ -465,8 +473,7 @@ class GridLeg(object):
     def check(self):
         """Raise what the device-side checks of the calls COMPLETED so far found (`HipPath.check_input_range` / `check_index_flags`);
         the per-day loops call it after their final copy to the host, which has waited for every window."""
-        for hp in self.net._contexts():
-            hp.check_input_range()
+        _check_verdicts(self.net)
 
     def embed(self, picks, t0, max_t, kernel_sig_t, dt):
         """(Slice, Mask) of the window starting at t0 (genie_embed_window = extract_input_from_data, process_utils.py:460-642), or None
@@ -481,31 +488,18 @@ def _dt_embed(kernel_sig_t, dt_embed):
     return float(dt_embed if dt_embed is not None else np.round(kernel_sig_t / 10.0, 2))          # process_continuous_days.py:608
 
 
-_PINNED = {}
+_pinned = threading.local()
 
 
 def _pinned_pair(n, device):
-    """Two page-locked float64 [n, 3] staging buffers per (size, device, calling thread), kept for the life of the process (pinning
-    2.7 MB costs ~20 ms: not per call). Keyed so that concurrent refine passes -- one per GPU, or one per thread -- never share a pair."""
-    import threading
-    key = (int(n), str(device), threading.get_ident())
-    if key not in _PINNED:
-        _PINNED[key] = [torch.empty((n, 3), dtype=torch.float64).pin_memory() for _ in range(2)]
-    return _PINNED[key]
-
-
-def _source_parallel(source_parallel, legs):
-    """(rank, world, group, is_group) of a `source_parallel` argument -- `(rank, world)`, a `torch.distributed` process group or True
-    for the default group: the three forms of `window_parallel` -- or None. Checked before anything touches a device."""
-    if source_parallel is None or source_parallel is False:
-        return None
-    if any(getattr(leg.net, "is_sharded", False) for leg in legs):
-        raise NotImplementedError("source_parallel on a source-node-sharded model: the hybrid of source-parallel replicas and "
-                                  "source-node shards is not built; use an unsharded model per GPU")
-    from . import dist as _dist
-    if isinstance(source_parallel, (tuple, list)):
-        return _dist.resolve_shard(shard=source_parallel) + (False,)
-    return _dist.resolve_shard(process_group=source_parallel) + (True,)
+    """Two page-locked float64 [n, 3] staging buffers per (size, device) of the calling thread, kept for the life of that thread (pinning
+    2.7 MB costs ~20 ms: not per call). Thread-local, so that concurrent refine passes -- one per GPU, or one per thread -- never share a
+    pair and a finished thread's buffers are released with it."""
+    pairs = _pinned.__dict__.setdefault("pairs", {})
+    key = (int(n), str(device))
+    if key not in pairs:
+        pairs[key] = [torch.empty((n, 3), dtype=torch.float64).pin_memory() for _ in range(2)]
+    return pairs[key]
 
 
 def _gather_blocks(rows, blocks, group, timeout):
@@ -529,8 +523,9 @@ def _gather_blocks(rows, blocks, group, timeout):
 
 def refined_from_found(found, srcs, tq, ftrns2):
     """The end of the refine pass on the host: `found` float64 [n, 7] = per source (query row, offset index, value, any query inside the
-    region, the refined query's Cartesian position) as the device branch of `refine_sources` leaves them (the rows of all ranks of a
-    source-parallel pass laid side by side in source order) -> (srcs_refined [n, 5] sorted by origin time, `order`)."""
+    region, the refined query's position, of which `ftrns2` makes the geographic one) as either branch of `refine_sources` leaves them
+    (the rows of all ranks of a source-parallel pass laid side by side in source order) -> (srcs_refined [n, 5] sorted by origin time,
+    `order`)."""
     srcs = np.asarray(srcs, dtype=np.float64)
     found = np.asarray(found, dtype=np.float64).reshape(-1, 7)
     tq_host = np.asarray(tq.detach().cpu() if torch.is_tensor(tq) else tq, dtype=np.float64).reshape(-1)
@@ -576,111 +571,115 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
       every rank finishes identically and returns the same (srcs_refined, order) as one GPU.
     A rank whose block is empty runs no window and still takes part in the collective; every rank checks the verdicts of its own
     contexts. A source-sharded model is refused."""
-    sp = _source_parallel(source_parallel, legs)
+    sp = _rank_split(source_parallel, "source_parallel", any(getattr(leg.net, "is_sharded", False) for leg in legs))
     rand = rand or np.random.rand
     srcs = np.asarray(srcs, dtype=np.float64)
     b_lo, b_hi = 0, srcs.shape[0]
     if sp is not None:
         if ftrns2_device is None:
             raise ValueError("refine_sources: source_parallel needs ftrns2_device (the ranks exchange the device branch's fixed-size rows)")
-        blocks = window_blocks(srcs.shape[0], sp[1])
-        b_lo, b_hi = blocks[sp[0]]
+        blocks = window_blocks(srcs.shape[0], sp.world)
+        b_lo, b_hi = blocks[sp.rank]
     tq_host = np.asarray(tq.detach().cpu() if torch.is_tensor(tq) else tq, dtype=np.float64).reshape(-1)
     dev = legs[0].device
     tq_d = torch.as_tensor(tq_host.reshape(-1, 1)).float().to(dev)
     locs_d = torch.as_tensor(locs_cart).float().to(dev)
     dt = _dt_embed(kernel_sig_t, dt_embed)
-    n_scale = float(len(legs))
-    clouds, found = [], []
-    on_device = ftrns2_device is not None
-    if on_device:      # constants of the loop and every source's Cartesian position: copied once
-        off_rng_d = torch.as_tensor(np.asarray(X_offset_range, dtype=np.float64).reshape(1, 3), device=dev)
-        off_min_d = torch.as_tensor(np.asarray(X_offset_min, dtype=np.float64).reshape(1, 3), device=dev)
-        src_cart_d = torch.from_numpy(np.ascontiguousarray(ftrns1(srcs[:, 0:3]), dtype=np.float64)).to(dev) if srcs.shape[0] else None
-        stage, stage_ev = _pinned_pair(n_rand_query, dev), [None, None]
-        from . import postproc
-        if int(n_rand_query) < 1:
-            raise ValueError("refine_sources: n_rand_query must be >= 1")
-        if len(legs) > postproc.REFINE_SELECT_MAX_LEGS:
-            raise ValueError("refine_sources: at most %d grid legs with ftrns2_device" % postproc.REFINE_SELECT_MAX_LEGS)
-        sel_scratch = postproc.refine_select_scratch(dev)
+
+    def readouts(i, xq):       # every leg's read-out [n_query, n_t, 1] at the queries `xq`, on the window that starts at source i's origin time
+        for leg in legs:
+            em = leg.embed(picks, srcs[i, 3], max_t, kernel_sig_t, dt)
+            if em is not None:                                                                                          # :966-967
+                yield leg.net.forward_fixed_source(em[0], em[1], None, None, None, locs_d, leg.x_grid_cart, xq, tq_d)[1]
+
+    cloud = (srcs, readouts, len(legs), tq_host.shape[0], X_offset_min, X_offset_range, ftrns1, (lat_range, lon_range, depth_range), dev)
+    if ftrns2_device is not None:
+        refine, to_geographic = _refine_on_device_cloud(*cloud, ftrns2_device, n_rand_query), ftrns2
+    else:
+        refine, to_geographic = _refine_on_host_cloud(*cloud, ftrns2), (lambda x: x)       # (its rows are geographic already)
+    found = []
     with torch.no_grad():
         for i in range(srcs.shape[0]):
-            if not b_lo <= i < b_hi:           # another rank's source: consume its draw, so that the stream is the one of one GPU
-                rand(n_rand_query, 3)
-                continue
-            if on_device:
-                # Nothing in this branch waits for the device (round 5, tools/sync_probe_day.py: eight waits per source before -- pageable
-                # copies, the boolean-mask compaction, three tensor-indexed reads): the draw goes through pinned memory, the queries outside
-                # the region stay in the cloud and are masked out of the argmax (a query's read-out depends on no other query: the same
-                # values and the same refined query as after the reference's compaction), and the refined query's row is gathered on the
-                # device. The host draws source i + 1's cloud while the GPU works on source i.
-                k = i % 2
-                if stage_ev[k] is not None:
-                    stage_ev[k].synchronize()              # the copy that last read this staging buffer (two sources ago) has finished
-                stage[k].numpy()[...] = rand(n_rand_query, 3)                                                         # the host's draw, float64
-                r = stage[k].to(dev, non_blocking=True)
-                stage_ev[k] = torch.cuda.Event()
-                stage_ev[k].record(torch.cuda.current_stream(dev))       # the stream of `dev` the copy was issued on
-                Xc_d = src_cart_d[i:i + 1] + (r * off_rng_d + off_min_d)                                                  # :929
-                X1_d = ftrns2_device(Xc_d)
-                keep = ((X1_d[:, 0] > lat_range[0]) & (X1_d[:, 0] < lat_range[1]) & (X1_d[:, 1] > lon_range[0]) & (X1_d[:, 1] < lon_range[1])
-                        & (X1_d[:, 2] > depth_range[0]) & (X1_d[:, 2] < depth_range[1]))
-                xq = Xc_d.float()
-                # the legs' read-outs stay where the read-out kernel wrote them; one launch pair sums them, masks and selects
-                xs = []
-                for leg in legs:
-                    em = leg.embed(picks, srcs[i, 3], max_t, kernel_sig_t, dt)
-                    if em is None:
-                        continue                                                                                        # :966-967
-                    xs.append(leg.net.forward_fixed_source(em[0], em[1], None, None, None, locs_d, leg.x_grid_cart, xq, tq_d)[1].contiguous())
-                sel = postproc.refine_select_device(xs, (xq.shape[0], tq_host.shape[0]), keep, n_scale, scratch=sel_scratch)  # :972-978
-                found.append(torch.cat((sel, Xc_d.index_select(0, sel[0:1].long()).view(3))))
-                continue
-            Xc = ftrns1(srcs[i, 0:3].reshape(1, -1)) + (rand(n_rand_query, 3) * X_offset_range + X_offset_min)      # :929
-            X1 = ftrns2(Xc)
-            inside = np.where((X1[:, 0] > lat_range[0]) * (X1[:, 0] < lat_range[1]) * (X1[:, 1] > lon_range[0]) * (X1[:, 1] < lon_range[1])
-                              * (X1[:, 2] > depth_range[0]) * (X1[:, 2] < depth_range[1]))[0]
-            X1, Xc = X1[inside], Xc[inside]
-            clouds.append(X1)
-            xq = torch.from_numpy(np.ascontiguousarray(Xc)).to(dev).float()                                       # torch.Tensor(...) :934 (rounded on the device)
-            acc = torch.zeros((xq.shape[0], tq_host.shape[0]), dtype=torch.float32, device=dev)
-            if xq.shape[0]:
-                for leg in legs:
-                    em = leg.embed(picks, srcs[i, 3], max_t, kernel_sig_t, dt)
-                    if em is None:
-                        continue                                                                                        # :966-967
-                    _, x = leg.net.forward_fixed_source(em[0], em[1], None, None, None, locs_d, leg.x_grid_cart, xq, tq_d)
-                    acc += x[:, :, 0] / n_scale                                                                         # :972
-                ip = torch.argmax(acc.max(1)[0])                                                                        # :976 (first maximum)
-                it = torch.argmax(acc[ip])                                                                              # :977
-                found.append(torch.stack((ip.double(), it.double(), acc[ip, it].double())))
-            else:
-                found.append(torch.full((3,), float("nan"), dtype=torch.float64, device=dev))
-    if on_device:
-        rows = torch.stack(found) if found else torch.zeros((0, 7), dtype=torch.float64, device=dev)
-        if sp is not None and sp[3]:
-            found = _gather_blocks(rows, blocks, sp[2], merge_timeout)
-        else:
-            found = rows.cpu().numpy()
-        for leg in legs:       # a copy to the host has waited for the device (after the collective, so that a rank that raises here
-            leg.check()        # leaves no other rank waiting): the verdicts of every window of this rank's pass are in
-        if sp is not None and not sp[3]:
-            return found, (b_lo, b_hi)
-        return refined_from_found(found, srcs, tq_host, ftrns2)
-    found = torch.stack(found).cpu().numpy() if found else np.zeros((0, 3))
-    for leg in legs:       # the copy above waited for the device: the verdicts of every window of this pass are in
-        leg.check()
-    out = np.zeros((srcs.shape[0], 5))
-    for i in range(srcs.shape[0]):
-        if clouds[i].shape[0] == 0:
-            raise ValueError("refine_sources: no query of source %d lies inside the region (the reference's argmax raises here too)" % i)
-        ip, it = int(found[i, 0]), int(found[i, 1])
-        out[i, 0:3] = clouds[i][ip]
-        out[i, 3] = srcs[i, 3] + tq_host[it]
-        out[i, 4] = found[i, 2]
-    order = np.argsort(out[:, 3])
-    return out[order], order
+            draw = rand(n_rand_query, 3)       # for another rank's source too, so that the stream is the one of one GPU
+            if b_lo <= i < b_hi:
+                found.append(refine(i, draw))
+    rows = torch.stack(found) if found else torch.zeros((0, 7), dtype=torch.float64, device=dev)
+    if sp is not None and sp.collective:
+        found = _gather_blocks(rows, blocks, sp.group, merge_timeout)
+    else:
+        found = rows.cpu().numpy()
+    for leg in legs:       # a copy to the host has waited for the device (after the collective, so that a rank that raises here
+        leg.check()        # leaves no other rank waiting): the verdicts of every window of this rank's pass are in
+    if sp is not None and not sp.collective:
+        return found, (b_lo, b_hi)
+    return refined_from_found(found, srcs, tq_host, to_geographic)
+
+
+def _inside_region(X, ranges):
+    """Boolean [n]: the rows of `X` [n, 3] (numpy array or tensor) strictly inside the three `ranges` (process_continuous_days.py:930-936)."""
+    return ((X[:, 0] > ranges[0][0]) & (X[:, 0] < ranges[0][1]) & (X[:, 1] > ranges[1][0]) & (X[:, 1] < ranges[1][1])
+            & (X[:, 2] > ranges[2][0]) & (X[:, 2] < ranges[2][1]))
+
+
+def _refine_on_device_cloud(srcs, readouts, n_legs, n_t, X_offset_min, X_offset_range, ftrns1, ranges, dev, ftrns2_device, n_rand_query):
+    """`refine(i, draw)` of `refine_sources(ftrns2_device=...)`: source i's row float64 [7] on the device = (query row, offset index,
+    value, any query inside the region, the refined query's CARTESIAN position), from its draw `rand(n_rand_query, 3)`."""
+    from . import postproc
+    # constants of the loop and every source's Cartesian position: copied once
+    off_rng_d = torch.as_tensor(np.asarray(X_offset_range, dtype=np.float64).reshape(1, 3), device=dev)
+    off_min_d = torch.as_tensor(np.asarray(X_offset_min, dtype=np.float64).reshape(1, 3), device=dev)
+    src_cart_d = torch.from_numpy(np.ascontiguousarray(ftrns1(srcs[:, 0:3]), dtype=np.float64)).to(dev) if srcs.shape[0] else None
+    stage, stage_ev = _pinned_pair(n_rand_query, dev), [None, None]
+    if int(n_rand_query) < 1:
+        raise ValueError("refine_sources: n_rand_query must be >= 1")
+    if n_legs > postproc.REFINE_SELECT_MAX_LEGS:
+        raise ValueError("refine_sources: at most %d grid legs with ftrns2_device" % postproc.REFINE_SELECT_MAX_LEGS)
+    sel_scratch = postproc.refine_select_scratch(dev)
+
+    def refine(i, draw):
+        # Nothing here waits for the device (round 5, tools/sync_probe_day.py: eight waits per source before -- pageable copies, the
+        # boolean-mask compaction, three tensor-indexed reads): the draw goes through pinned memory, the queries outside the region stay
+        # in the cloud and are masked out of the argmax (a query's read-out depends on no other query: the same values and the same
+        # refined query as after the reference's compaction), and the refined query's row is gathered on the device. The host draws
+        # source i + 1's cloud while the GPU works on source i.
+        k = i % 2
+        if stage_ev[k] is not None:
+            stage_ev[k].synchronize()              # the copy that last read this staging buffer (two sources ago) has finished
+        stage[k].numpy()[...] = draw                                                                              # the host's draw, float64
+        r = stage[k].to(dev, non_blocking=True)
+        stage_ev[k] = torch.cuda.Event()
+        stage_ev[k].record(torch.cuda.current_stream(dev))       # the stream of `dev` the copy was issued on
+        Xc_d = src_cart_d[i:i + 1] + (r * off_rng_d + off_min_d)                                                  # :929
+        keep = _inside_region(ftrns2_device(Xc_d), ranges)
+        xq = Xc_d.float()
+        # the legs' read-outs stay where the read-out kernel wrote them; one launch pair sums them, masks and selects
+        xs = [x.contiguous() for x in readouts(i, xq)]
+        sel = postproc.refine_select_device(xs, (xq.shape[0], n_t), keep, float(n_legs), scratch=sel_scratch)      # :972-978
+        return torch.cat((sel, Xc_d.index_select(0, sel[0:1].long()).view(3)))
+    return refine
+
+
+def _refine_on_host_cloud(srcs, readouts, n_legs, n_t, X_offset_min, X_offset_range, ftrns1, ranges, dev, ftrns2):
+    """`refine(i, draw)` of `refine_sources` without `ftrns2_device`, the reference's own statements: the cloud and its region filter in
+    numpy, the refined query by torch's `max` / `argmax`. The row is the device branch's, except that its position is GEOGRAPHIC: the
+    refined query's row of the batch transform `ftrns2(cloud)` (a second transform of that one row need not give the same bits)."""
+    one = torch.ones(1, dtype=torch.float64, device=dev)
+
+    def refine(i, draw):
+        Xc = ftrns1(srcs[i, 0:3].reshape(1, -1)) + (draw * X_offset_range + X_offset_min)                          # :929
+        X1 = ftrns2(Xc)
+        inside = np.where(_inside_region(X1, ranges))[0]
+        if inside.size == 0:
+            return torch.zeros(7, dtype=torch.float64, device=dev)          # no query inside the region: `refined_from_found` raises
+        X1_d = torch.from_numpy(np.ascontiguousarray(X1[inside], dtype=np.float64)).to(dev)
+        xq = torch.from_numpy(np.ascontiguousarray(Xc[inside])).to(dev).float()                                 # torch.Tensor(...) :934 (rounded on the device)
+        acc = torch.zeros((xq.shape[0], n_t), dtype=torch.float32, device=dev)
+        for x in readouts(i, xq):
+            acc += x[:, :, 0] / float(n_legs)                                                                       # :972
+        ip = torch.argmax(acc.max(1)[0])                                                                            # :976 (first maximum)
+        it = torch.argmax(acc[ip])                                                                                  # :977
+        return torch.cat((torch.stack((ip.double(), it.double(), acc[ip, it].double())), one, X1_d[ip]))
+    return refine
 
 
 def associate_sources(legs, picks, srcs_refined, locs_cart, tq, max_t, trv_out_srcs, ftrns1, x_save, kernel_sig_t=synthetic.KERNEL_SIG_T,
@@ -698,9 +697,9 @@ def associate_sources(legs, picks, srcs_refined, locs_cart, tq, max_t, trv_out_s
     * tuple form: returns (Out_p, Out_s of this rank's block only, Save_picks, lp_meta of all sources, (lo, hi)).
     * group form: one `all_gather_object` of the blocks' ragged likelihoods through the host (a few thousand floats per source; an
       RCCL group carries them as byte tensors on the current device); every rank returns the four full lists of one GPU."""
-    sp = _source_parallel(source_parallel, legs)
+    sp = _rank_split(source_parallel, "source_parallel", any(getattr(leg.net, "is_sharded", False) for leg in legs))
     srcs = np.asarray(srcs_refined, dtype=np.float64)
-    b_lo, b_hi = window_blocks(srcs.shape[0], sp[1])[sp[0]] if sp is not None else (0, srcs.shape[0])
+    b_lo, b_hi = window_blocks(srcs.shape[0], sp.world)[sp.rank] if sp is not None else (0, srcs.shape[0])
     dev = legs[0].device
     tq_d = torch.as_tensor(np.asarray(tq.detach().cpu() if torch.is_tensor(tq) else tq, dtype=np.float32).reshape(-1, 1)).to(dev)
     locs_d = torch.as_tensor(locs_cart).float().to(dev)
@@ -744,13 +743,13 @@ def associate_sources(legs, picks, srcs_refined, locs_cart, tq, max_t, trv_out_s
         torch.cuda.current_stream(dev).synchronize()      # (windows without picks copy nothing back)
     for leg in legs:       # device-side verdicts (a pick outside the time-pointer table, a station index outside the model) of every call above
         leg.check()
-    if sp is not None and not sp[3]:
+    if sp is not None and not sp.collective:
         return Out_p, Out_s, Save_picks, lp_meta, (b_lo, b_hi)
     if sp is not None:
         import torch.distributed as dist
-        parts = [None] * sp[1]
+        parts = [None] * sp.world
         with torch.cuda.device(dev):
-            dist.all_gather_object(parts, ([o.cpu().numpy() for o in Out_p], [o.cpu().numpy() for o in Out_s]), group=sp[2])
+            dist.all_gather_object(parts, ([o.cpu().numpy() for o in Out_p], [o.cpu().numpy() for o in Out_s]), group=sp.group)
         Out_p = [torch.from_numpy(o).to(dev) for part in parts for o in part[0]]
         Out_s = [torch.from_numpy(o).to(dev) for part in parts for o in part[1]]
     return Out_p, Out_s, Save_picks, lp_meta
@@ -794,9 +793,9 @@ def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, 
     the default one, or `(rank, world)` -- which, having no transport, must have world 1 here). Detection, both LocalMarchings and the
     `trv` calls are cheap and deterministic and run replicated on every rank; the returned dict equals the one-GPU dict on every rank."""
     from . import postproc
-    sp = _source_parallel(source_parallel, legs)
-    if sp is not None and not sp[3]:
-        if sp[1] != 1:
+    sp = _rank_split(source_parallel, "source_parallel", any(getattr(leg.net, "is_sharded", False) for leg in legs))
+    if sp is not None and not sp.collective:
+        if sp.world != 1:
             raise ValueError("detect_refine_associate: source_parallel = (rank, world) with world > 1 needs a process group (the "
                              "association pass reads every rank's refined sources)")
         source_parallel = None

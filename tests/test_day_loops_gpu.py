@@ -268,3 +268,89 @@ def test_two_identical_grid_legs_equal_one():
     assert len(a[2]) == len(b[2]) == 3 and sum(int(o.numel()) for o in a[2]) > 0
     for i in range(3):
         assert torch.equal(a[2][i], b[2][i]) and torch.equal(a[3][i], b[3][i]) and np.array_equal(a[4][i], b[4][i])
+
+
+def test_host_cloud_refine_returns_rows_of_the_batch_transform():
+    """`refine_sources` without `ftrns2_device`, under a transform that is not the identity (a fixed float64 rotation plus an offset,
+    `ftrns1` its inverse) and a region that cuts every cloud: the refined position is the (ip)-th row of `ftrns2(cloud)[inside]`, the
+    BATCH transform after the region filter, with (ip, it) of the torch statements on the same read-outs -- bit for bit, and `ftrns2` is
+    never called on a single row. A source whose whole cloud lies outside the region raises."""
+    s = _Setup()
+    n = 300
+    cz, sz, cx, sx = np.cos(0.3), np.sin(0.3), np.cos(0.2), np.sin(0.2)
+    R = np.array([[cz, -sz, 0.0], [sz, cz, 0.0], [0.0, 0.0, 1.0]]) @ np.array([[1.0, 0.0, 0.0], [0.0, cx, -sx], [0.0, sx, cx]])
+    b = np.array([[1.5e3, -2.5e3, 700.0]])
+    calls = []
+
+    def to_geo(X):
+        return X @ R.T + b
+
+    def ftrns1(X):
+        return (X - b) @ R
+
+    def ftrns2(X):
+        calls.append(X.shape)
+        return to_geo(X)
+
+    centre = s.geom_all.x_grid[[31]]                                    # three sources around one node: their clouds overlap
+    cart = centre + np.array([[0.0, 0.0, 0.0], [400.0, -300.0, 200.0], [-500.0, 600.0, -100.0]])
+    srcs = np.concatenate((to_geo(cart), [[7008.0], [7000.0], [7004.0]], np.full((3, 1), 0.5)), axis=1)
+    off_min, off_rng = np.array([[-5e3, -5e3, -3e3]]), np.array([[10e3, 10e3, 6e3]])
+    ranges = ((-1e9, float(to_geo(centre)[0, 0])), (-1e9, 1e9), (-1e9, 1e9))                # a plane through the node cuts every cloud
+    kw = dict(kernel_sig_t=s.sig, dt_embed=s.dt)
+    got, order = apply.refine_sources([s.leg], s.picks, srcs, s.locs, s.tq, s.max_t, off_min, off_rng, n, ftrns1, ftrns2, *ranges,
+                                      rand=np.random.RandomState(41).rand, **kw)
+    assert calls == [(n, 3)] * 3
+    rs = np.random.RandomState(41)
+    locs_d, tq_d = _t(s.locs), _t(s.tq)
+    want = np.zeros((3, 5))
+    for i in range(3):
+        Xc = ftrns1(srcs[i, 0:3].reshape(1, -1)) + (rs.rand(n, 3) * off_rng + off_min)
+        X1 = to_geo(Xc)
+        inside = np.nonzero((X1[:, 0] > ranges[0][0]) & (X1[:, 0] < ranges[0][1]))[0]
+        assert 0 < len(inside) < n
+        em = s.leg.embed(s.picks, srcs[i, 3], s.max_t, s.sig, s.dt)
+        xq = torch.from_numpy(np.ascontiguousarray(Xc[inside])).to(DEV).float()
+        with torch.no_grad():
+            x = s.net.forward_fixed_source(em[0], em[1], None, None, None, locs_d, s.leg.x_grid_cart, xq, tq_d)[1]
+        acc = torch.zeros((len(inside), s.tq.shape[0]), dtype=torch.float32, device=DEV) + x[:, :, 0] / 1.0
+        ip = int(torch.argmax(acc.max(1)[0]))
+        it = int(torch.argmax(acc[ip]))
+        want[i] = np.concatenate((X1[inside][ip], [srcs[i, 3] + s.tq[it, 0], float(acc[ip, it])]))
+    assert float(want[:, 4].max()) > 1e-3
+    assert np.array_equal(order, np.argsort(want[:, 3])) and order[-1] == 0
+    assert np.array_equal(got[:, 0:3], want[order][:, 0:3]) and np.array_equal(got, want[order])
+    far = to_geo(cart[[0]]) + np.array([[20e3, 0.0, 0.0]])                                  # its whole cloud lies beyond the plane
+    Xf = to_geo(ftrns1(far) + (np.random.RandomState(41).rand(n, 3) * off_rng + off_min))
+    assert not (Xf[:, 0] < ranges[0][1]).any()
+    with pytest.raises(ValueError, match="no query of source 0"):
+        apply.refine_sources([s.leg], s.picks, np.concatenate((far, [[7002.0, 0.5]]), axis=1), s.locs, s.tq, s.max_t, off_min, off_rng, n,
+                             ftrns1, ftrns2, *ranges, rand=np.random.RandomState(41).rand, **kw)
+
+
+def test_pinned_pair_belongs_to_its_thread():
+    """`_pinned_pair`: the same thread gets the same two pinned buffers back, another thread gets two others, and a finished thread's
+    buffers are released with it."""
+    import gc
+    import threading
+    import weakref
+    mine = apply._pinned_pair(8, DEV)
+    again = apply._pinned_pair(8, DEV)
+    assert len(mine) == 2 and mine[0] is again[0] and mine[1] is again[1]
+    assert all(x.is_pinned() and tuple(x.shape) == (8, 3) and x.dtype == torch.float64 for x in mine)
+    seen = {}
+
+    def worker():
+        pair = apply._pinned_pair(8, DEV)
+        seen["same"] = all(a is b for a, b in zip(pair, apply._pinned_pair(8, DEV)))
+        seen["pinned"] = all(x.is_pinned() for x in pair)
+        seen["ptrs"] = [x.data_ptr() for x in pair]                     # taken while both threads' pairs are alive
+        seen["refs"] = [weakref.ref(x) for x in pair]
+
+    t = threading.Thread(target=worker)
+    t.start()
+    t.join()
+    assert seen["same"] and seen["pinned"] and len(set(seen["ptrs"] + [x.data_ptr() for x in mine])) == 4
+    gc.collect()
+    assert all(r() is None for r in seen["refs"])
+    assert apply._pinned_pair(8, DEV)[0] is mine[0]
