@@ -521,6 +521,24 @@ def _gather_blocks(rows, blocks, group, timeout):
     return torch.cat([p[: hi - lo] for p, (lo, hi) in zip(parts, blocks)]).cpu().numpy()
 
 
+class PhiloxCloud(object):
+    """The draws of a refine pass as a pure function of (key, source index, element): `rand=PhiloxCloud(key)` of `refine_sources` /
+    `detect_refine_associate`. Source i's draw is `np.random.Generator(np.random.Philox(key=key, counter=[0, i, 0, 0])).random((n, 3))`
+    (Philox4x64-10, counter-based): `host(i, n)` makes exactly that with numpy, and with `ftrns2_device` the refine pass makes the same
+    bits on the device where they are consumed (`postproc.refine_cloud_device`), identical on any rank and never drawn for a source the
+    rank does not own. `key`: an int below 2**128 or a pair of 64-bit words, as numpy takes it. Nothing here is stateful: the same
+    (key, source, n) gives the same draw whenever and wherever it is asked for."""
+
+    def __init__(self, key):
+        from . import postproc
+        self.key = postproc.philox_key_words(key)
+
+    def host(self, source, n):
+        """Source number `source`'s draw, float64 [n, 3], on the host: the reference of the device draw and the host-cloud branch's draw."""
+        bits = np.random.Philox(key=np.array(self.key, dtype=np.uint64), counter=np.array([0, int(source), 0, 0], dtype=np.uint64))
+        return np.random.Generator(bits).random((int(n), 3))
+
+
 def refined_from_found(found, srcs, tq, ftrns2):
     """The end of the refine pass on the host: `found` float64 [n, 7] = per source (query row, offset index, value, any query inside the
     region, the refined query's position, of which `ftrns2` makes the geographic one) as either branch of `refine_sources` leaves them
@@ -551,7 +569,8 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
     (`argmax` of the row maxima, then of that row, :976-978: first maximum in both). Sources whose window holds no pick keep an all-zero
     read-out (:966-967), i.e. their first query and `tq[0]`. Returns (srcs_refined float64 [n, 5] sorted by origin time (:981-982),
     `order` = that sort's permutation of the input rows). `rand(n, 3)` defaults to `np.random.rand` (the reference's draw); the
-    per-source results stay on the device until one copy at the end. `ftrns2_device`: the inverse transform as a function of a float64
+    per-source results stay on the device until one copy at the end; `rand=PhiloxCloud(key)` is the keyed, source-indexed draw described
+    under `source_parallel` below. `ftrns2_device`: the inverse transform as a function of a float64
     GPU tensor [n, 3] (the reference also carries torch forms of its transforms, `ftrns2_diff`): the cloud's arithmetic, the region
     filter and the float32 rounding then run on the device in float64 -- the same values as the numpy path, whose 112 000 x 3 float64
     temporaries per source otherwise make the pass host-bound (37 ms per source at config 2 against ~6 ms of GPU work) -- and only the
@@ -562,9 +581,12 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
     `source_parallel`: split the sources over GPUs (needs `ftrns2_device`). `(rank, world)`, or a
     `torch.distributed` process group (True: the default group) -- the forms of `window_parallel`. Rank r refines the contiguous block
     `window_blocks(len(srcs), world)[r]` of `srcs`. Every source has its own window, cloud and picks, so the split is exact: a source's
-    row carries the same bits whichever rank computes it. The draws stay those of one GPU because every rank calls `rand` once per
-    source, in source order, and discards the draws of the sources it does not own -- host time only; a
-    caller who wants to save it passes a `rand` that is itself indexed by source.
+    row carries the same bits whichever rank computes it. With a plain callable `rand` the draws stay those of one GPU because every
+    rank calls `rand` once per source, in source order, and discards the draws of the sources it does not own -- host time only, but
+    `n_sources` draws on every rank whatever the split. `rand=PhiloxCloud(key)` removes that: source i's draw is a function of (key, i)
+    alone, so no `rand` is called, the sources outside the rank's block are skipped entirely, and with `ftrns2_device` the cloud is
+    made on the device by one launch per source (`postproc.refine_cloud_device`: no host draw, no staging copy); without
+    `ftrns2_device` the host-cloud branch draws the same numbers with `PhiloxCloud.host`, so both branches keep meaning the same thing.
     * tuple form: no collective; returns (this rank's rows float64 [hi - lo, 7], (lo, hi)): `refined_from_found` turns the rows of
       all ranks, concatenated in rank order, into (srcs_refined, order).
     * group form: one all-gather of the fixed-size rows (`_gather_blocks`; the gloo wait ends after `merge_timeout` seconds), after which
@@ -572,6 +594,7 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
     A rank whose block is empty runs no window and still takes part in the collective; every rank checks the verdicts of its own
     contexts. A source-sharded model is refused."""
     sp = _rank_split(source_parallel, "source_parallel", any(getattr(leg.net, "is_sharded", False) for leg in legs))
+    keyed = rand if isinstance(rand, PhiloxCloud) else None
     rand = rand or np.random.rand
     srcs = np.asarray(srcs, dtype=np.float64)
     b_lo, b_hi = 0, srcs.shape[0]
@@ -594,15 +617,19 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
 
     cloud = (srcs, readouts, len(legs), tq_host.shape[0], X_offset_min, X_offset_range, ftrns1, (lat_range, lon_range, depth_range), dev)
     if ftrns2_device is not None:
-        refine, to_geographic = _refine_on_device_cloud(*cloud, ftrns2_device, n_rand_query), ftrns2
+        refine, to_geographic = _refine_on_device_cloud(*cloud, ftrns2_device, n_rand_query, keyed), ftrns2
     else:
         refine, to_geographic = _refine_on_host_cloud(*cloud, ftrns2), (lambda x: x)       # (its rows are geographic already)
     found = []
     with torch.no_grad():
-        for i in range(srcs.shape[0]):
-            draw = rand(n_rand_query, 3)       # for another rank's source too, so that the stream is the one of one GPU
-            if b_lo <= i < b_hi:
-                found.append(refine(i, draw))
+        if keyed is not None:                  # a draw indexed by source: only the rank's own sources, and no `rand` call at all
+            for i in range(b_lo, b_hi):
+                found.append(refine(i, None if ftrns2_device is not None else keyed.host(i, n_rand_query)))
+        else:
+            for i in range(srcs.shape[0]):
+                draw = rand(n_rand_query, 3)   # for another rank's source too, so that the stream is the one of one GPU
+                if b_lo <= i < b_hi:
+                    found.append(refine(i, draw))
     rows = torch.stack(found) if found else torch.zeros((0, 7), dtype=torch.float64, device=dev)
     if sp is not None and sp.collective:
         found = _gather_blocks(rows, blocks, sp.group, merge_timeout)
@@ -621,27 +648,27 @@ def _inside_region(X, ranges):
             & (X[:, 2] > ranges[2][0]) & (X[:, 2] < ranges[2][1]))
 
 
-def _refine_on_device_cloud(srcs, readouts, n_legs, n_t, X_offset_min, X_offset_range, ftrns1, ranges, dev, ftrns2_device, n_rand_query):
+def _refine_on_device_cloud(srcs, readouts, n_legs, n_t, X_offset_min, X_offset_range, ftrns1, ranges, dev, ftrns2_device, n_rand_query,
+                            keyed=None):
     """`refine(i, draw)` of `refine_sources(ftrns2_device=...)`: source i's row float64 [7] on the device = (query row, offset index,
-    value, any query inside the region, the refined query's CARTESIAN position), from its draw `rand(n_rand_query, 3)`."""
+    value, any query inside the region, the refined query's CARTESIAN position), from its draw `rand(n_rand_query, 3)` -- or, with
+    `keyed` (a `PhiloxCloud`), from the cloud one kernel draws on the device (`draw` is then None)."""
     from . import postproc
-    # constants of the loop and every source's Cartesian position: copied once
-    off_rng_d = torch.as_tensor(np.asarray(X_offset_range, dtype=np.float64).reshape(1, 3), device=dev)
-    off_min_d = torch.as_tensor(np.asarray(X_offset_min, dtype=np.float64).reshape(1, 3), device=dev)
-    src_cart_d = torch.from_numpy(np.ascontiguousarray(ftrns1(srcs[:, 0:3]), dtype=np.float64)).to(dev) if srcs.shape[0] else None
-    stage, stage_ev = _pinned_pair(n_rand_query, dev), [None, None]
     if int(n_rand_query) < 1:
         raise ValueError("refine_sources: n_rand_query must be >= 1")
+    # constants of the loop and every source's Cartesian position: made once
+    off_rng = np.asarray(X_offset_range, dtype=np.float64).reshape(1, 3)
+    off_min = np.asarray(X_offset_min, dtype=np.float64).reshape(1, 3)
+    src_cart = np.ascontiguousarray(ftrns1(srcs[:, 0:3]), dtype=np.float64).reshape(-1, 3) if srcs.shape[0] else None
+    if keyed is None:          # the staged path's device copies and pinned pair; the keyed path passes the same numbers by value
+        off_rng_d, off_min_d = torch.as_tensor(off_rng, device=dev), torch.as_tensor(off_min, device=dev)
+        src_cart_d = torch.from_numpy(src_cart).to(dev) if srcs.shape[0] else None
+        stage, stage_ev = _pinned_pair(n_rand_query, dev), [None, None]
     if n_legs > postproc.REFINE_SELECT_MAX_LEGS:
         raise ValueError("refine_sources: at most %d grid legs with ftrns2_device" % postproc.REFINE_SELECT_MAX_LEGS)
     sel_scratch = postproc.refine_select_scratch(dev)
 
-    def refine(i, draw):
-        # Nothing here waits for the device (round 5, tools/sync_probe_day.py: eight waits per source before -- pageable copies, the
-        # boolean-mask compaction, three tensor-indexed reads): the draw goes through pinned memory, the queries outside the region stay
-        # in the cloud and are masked out of the argmax (a query's read-out depends on no other query: the same values and the same
-        # refined query as after the reference's compaction), and the refined query's row is gathered on the device. The host draws
-        # source i + 1's cloud while the GPU works on source i.
+    def staged_cloud(i, draw):
         k = i % 2
         if stage_ev[k] is not None:
             stage_ev[k].synchronize()              # the copy that last read this staging buffer (two sources ago) has finished
@@ -650,8 +677,20 @@ def _refine_on_device_cloud(srcs, readouts, n_legs, n_t, X_offset_min, X_offset_
         stage_ev[k] = torch.cuda.Event()
         stage_ev[k].record(torch.cuda.current_stream(dev))       # the stream of `dev` the copy was issued on
         Xc_d = src_cart_d[i:i + 1] + (r * off_rng_d + off_min_d)                                                  # :929
+        return Xc_d, Xc_d.float()
+
+    def refine(i, draw):
+        # Nothing here waits for the device (round 5, tools/sync_probe_day.py: eight waits per source before -- pageable copies, the
+        # boolean-mask compaction, three tensor-indexed reads): the draw goes through pinned memory, the queries outside the region stay
+        # in the cloud and are masked out of the argmax (a query's read-out depends on no other query: the same values and the same
+        # refined query as after the reference's compaction), and the refined query's row is gathered on the device. The host draws
+        # source i + 1's cloud while the GPU works on source i. A keyed draw has no host part at all: one launch makes the cloud's
+        # float64 and float32 forms from (key, i), with no pinned pair, no copy and no event.
+        if keyed is not None:
+            Xc_d, xq = postproc.refine_cloud_device(keyed.key, i, n_rand_query, src_cart[i], off_rng, off_min, dev)     # :929, :934
+        else:
+            Xc_d, xq = staged_cloud(i, draw)
         keep = _inside_region(ftrns2_device(Xc_d), ranges)
-        xq = Xc_d.float()
         # the legs' read-outs stay where the read-out kernel wrote them; one launch pair sums them, masks and selects
         xs = [x.contiguous() for x in readouts(i, xq)]
         sel = postproc.refine_select_device(xs, (xq.shape[0], n_t), keep, float(n_legs), scratch=sel_scratch)      # :972-978

@@ -1248,6 +1248,7 @@ __device__ __forceinline__ void gather_sum16(const float* __restrict__ base, lon
 #include "detect_kernels.hpp"
 #include "stack_kernels.hpp"
 #include "select_kernels.hpp"
+#include "cloud_kernels.hpp"
 
 }  // namespace
 
@@ -4091,6 +4092,26 @@ int genie_refine_select(const float* const* x, int n_used, int64_t n_query, int 
     RsPartial* part = (RsPartial*)scratch;
     if (nb > 0) k_refine_select_partial<<<nb, RS_BLOCK, 0, st>>>(legs, n_used, n_elem, n_t, keep, 1.0f / n_scale, part);
     k_refine_select_final<<<1, RS_BLOCK, 0, st>>>(part, nb, n_t, out);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+int genie_refine_cloud(uint64_t key0, uint64_t key1, uint64_t source, int64_t n_query, double sx, double sy, double sz, double rx, double ry,
+                       double rz, double mx, double my, double mz, double* r, double* xc, float* xq, void* stream) {
+    if (n_query < 0) return fail(GENIE_ERR_ARG, "genie_refine_cloud: n_query >= 0 required");
+    if (n_query == 0) return GENIE_OK;
+    if (!xc || !xq) return fail(GENIE_ERR_ARG, "genie_refine_cloud: null argument");
+    if (n_query > (int64_t)0x7fffffffffffffffLL / 8) return fail(GENIE_ERR_ARG, "genie_refine_cloud: n_query too large");
+    if (((((uintptr_t)r) | ((uintptr_t)xc) | ((uintptr_t)xq)) & 15) != 0) return fail(GENIE_ERR_ARG, "genie_refine_cloud: r, xc and xq must be 16-byte aligned");
+    const long long n_elem = 3 * (long long)n_query;
+    const long long n_blk = (n_elem + 3) / 4;                              // one thread per Philox block of four elements
+    const int nb = (int)std::min<long long>((n_blk + RC_BLOCK - 1) / RC_BLOCK, (long long)RC_MAX_WG);
+    RcAxes a;
+    a.sx = sx; a.sy = sy; a.sz = sz;
+    a.rx = rx; a.ry = ry; a.rz = rz;
+    a.mx = mx; a.my = my; a.mz = mz;
+    k_refine_cloud<<<nb, RC_BLOCK, 0, (hipStream_t)stream>>>((unsigned long long)key0, (unsigned long long)key1, (unsigned long long)source, n_elem, a, r,
+                                                            xc, xq);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }

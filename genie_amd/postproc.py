@@ -18,6 +18,9 @@ What runs where:
 * `refine_select_device` is the end of the refine pass per candidate source (process_continuous_days.py:972-978): the sum of the grid
   legs' query read-outs, the region mask and the nested first-maximum argmax in one launch pair (`genie_refine_select`,
   csrc/select_kernels.hpp); the torch statements of `apply.refine_sources` it replaces are its oracle (exact, ties included).
+* `refine_cloud_device` is the beginning of that pass per source (:929, :934): the random query cloud around a candidate source, drawn
+  on the device by a keyed Philox4x64-10 (`genie_refine_cloud`, csrc/cloud_kernels.hpp); numpy's `Generator(Philox(...)).random` and the
+  numpy statement of the cloud are its oracle (bit for bit).
 """
 import ctypes
 
@@ -359,3 +362,45 @@ def refine_select_device(xs, shape, keep, n_scale, device=None, scratch=None):
         _lib.check(lib.genie_refine_select(ptrs, len(xs), Q, n_t, _ptr(keep), float(n_scale), _ptr(scratch), _ptr(out), _stream(dev)),
                    "genie_refine_select")
     return out
+
+
+# ------------------------------------------------------------------------------------------------
+# The refine pass's query cloud, drawn on the device (genie_refine_cloud, csrc/cloud_kernels.hpp).
+# ------------------------------------------------------------------------------------------------
+REFINE_CLOUD_SWEEP = 1024 * 256 * 4       # elements one sweep of the capped grid covers (RC_MAX_WG x RC_BLOCK x 4): beyond it threads stride
+
+
+def philox_key_words(key):
+    """The two 64-bit key words (low, high) of a Philox4x64 key given as an int below 2**128 or as a pair of 64-bit words -- what
+    `np.random.Philox(key=...)` makes of either form."""
+    if isinstance(key, (int, np.integer)):
+        key = int(key)
+        if not 0 <= key < 1 << 128:
+            raise ValueError("Philox key: an int key must lie in [0, 2**128)")
+        return key & 0xFFFFFFFFFFFFFFFF, key >> 64
+    words = [int(k) for k in np.asarray(key, dtype=object).reshape(-1)]
+    if len(words) != 2 or not all(0 <= k < 1 << 64 for k in words):
+        raise ValueError("Philox key: a pair of words in [0, 2**64) or an int below 2**128")
+    return words[0], words[1]
+
+
+def refine_cloud_device(key, source, n_query, src_cart, off_range, off_min, device, want_draw=False):
+    """The query cloud of candidate source number `source` in one launch on the current stream of `device`: with
+    `r = np.random.Generator(np.random.Philox(key=key, counter=[0, source, 0, 0])).random((n_query, 3))`, returns
+    (Xc = src_cart + (r * off_range + off_min) float64 [n_query, 3], xq = Xc rounded to float32[, r]) as GPU tensors carrying the bits of
+    those numpy statements. `key`: an int below 2**128 or a pair of 64-bit words; `src_cart`, `off_range`, `off_min`: three host numbers
+    each (they travel in the kernel arguments). Nothing is copied to the device and nothing waits for it."""
+    k0, k1 = philox_key_words(key)
+    source, n = int(source), int(n_query)
+    if not 0 <= source < 1 << 64:
+        raise ValueError("refine_cloud_device: source must lie in [0, 2**64)")
+    if n < 0:
+        raise ValueError("refine_cloud_device: n_query must be >= 0")
+    vec = [float(v) for a in (src_cart, off_range, off_min) for v in np.asarray(a, dtype=np.float64).reshape(3)]
+    dev = torch.device(device)
+    Xc = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    xq = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    r = torch.empty((n, 3), dtype=torch.float64, device=dev) if want_draw else None
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().genie_refine_cloud(k0, k1, source, n, *vec, _ptr(r), _ptr(Xc), _ptr(xq), _stream(dev)), "genie_refine_cloud")
+    return (Xc, xq, r) if want_draw else (Xc, xq)

@@ -603,6 +603,25 @@ size_t genie_refine_select_scratch_bytes(void);
 int genie_refine_select(const float* const* x, int n_used, int64_t n_query, int n_t, const uint8_t* keep, float n_scale, void* scratch,
                         double* out, void* stream);
 
+/* The query cloud of one candidate source of the refine pass (process_continuous_days.py:929, :934), drawn on the device by a keyed
+ * counter-based generator, one launch per source and nothing copied from the host:
+ *   r   = np.random.Generator(np.random.Philox(key=[key0, key1], counter=[0, source, 0, 0])).random((n_query, 3))     as bits: flat
+ *         element j of the row-major [n_query, 3] array is word j % 4 of Philox4x64-10 block j / 4, whose counter is (j / 4 + 1, source,
+ *         0, 0) (numpy increments counter word 0 before it generates), made a double as (u >> 11) * 2^-53;
+ *   xc[q, a] = s[a] + (r[q, a] * rng[a] + mn[a])   in fp64, every operation rounded on its own (no fused multiply-add): the bits of the
+ *         numpy / torch statement `src + (r * X_offset_range + X_offset_min)`; s = (sx, sy, sz) the source's Cartesian position,
+ *         rng = (rx, ry, rz) = X_offset_range, mn = (mx, my, mz) = X_offset_min;
+ *   xq[q, a] = (float)xc[q, a], round to nearest even (`xc.astype(float32)`, `Xc.float()`).
+ * The draw depends on (key0, key1, source, element) alone: any rank, any launch and any split of the sources over GPUs gives the same
+ * cloud for a source, and a source nobody asks for costs nothing. Everything small travels by value in the kernel arguments, so the call
+ * copies nothing and never waits. r [n_query, 3] fp64 or NULL (the draw is not stored), xc [n_query, 3] fp64, xq [n_query, 3] fp32, all on
+ * the device, row-major, 16-byte aligned, addressed with 64-bit element offsets. No atomics, no scratch; two calls with the same
+ * arguments write the same bits. Non-finite or absurd offsets are the caller's: they propagate as IEEE arithmetic has them.
+ * n_query == 0 returns GENIE_OK without a launch and touches nothing. Bad arguments (n_query < 0, or with n_query > 0 a null xc or xq, a
+ * pointer that is not 16-byte aligned, n_query > 2^60) return GENIE_ERR_ARG before any launch. */
+int genie_refine_cloud(uint64_t key0, uint64_t key1, uint64_t source, int64_t n_query, double sx, double sy, double sz, double rx, double ry,
+                       double rz, double mx, double my, double mz, double* r, double* xc, float* xq, void* stream);
+
 /* Debug/parity access to intermediates kept in the workspace (which: 0 = c [P,30], 1 = wu [P,15], 2 = wv [P,15]);
  * copies de-padded rows into `out` (async). */
 int genie_ws_export(genie_ctx* ctx, int which, void* ws, float* out, void* stream);
