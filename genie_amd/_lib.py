@@ -120,6 +120,8 @@ SYMBOLS = [
     ("genie_refine_select_scratch_bytes", _c.c_size_t, []),
     ("genie_refine_select", _c.c_int, [_P, _c.c_int, _c.c_int64, _c.c_int, _P, _c.c_float, _P, _P, _P]),
     ("genie_refine_cloud", _c.c_int, [_c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64] + [_c.c_double] * 9 + [_P, _P, _P, _P]),
+    ("genie_adam_step", _c.c_int, [_P, _P, _P, _c.c_int64, _P, _c.c_int, _c.c_int64, _P, _c.c_double, _c.c_double, _c.c_double, _c.c_double,
+                                   _c.c_int64, _P]),
     ("genie_ws_export", _c.c_int, [_P, _c.c_int, _P, _P, _P]),
     ("genie_embed_ntime", _c.c_int, [_c.c_double, _c.c_double, _c.c_double, _c.c_double]),
     ("genie_embed_window", _c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _P, _P,

@@ -1249,6 +1249,7 @@ __device__ __forceinline__ void gather_sum16(const float* __restrict__ base, lon
 #include "stack_kernels.hpp"
 #include "select_kernels.hpp"
 #include "cloud_kernels.hpp"
+#include "optim_kernels.hpp"
 
 }  // namespace
 
@@ -4112,6 +4113,40 @@ int genie_refine_cloud(uint64_t key0, uint64_t key1, uint64_t source, int64_t n_
     a.mx = mx; a.my = my; a.mz = mz;
     k_refine_cloud<<<nb, RC_BLOCK, 0, (hipStream_t)stream>>>((unsigned long long)key0, (unsigned long long)key1, (unsigned long long)source, n_elem, a, r,
                                                             xc, xq);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+int genie_adam_step(float* param, float* exp_avg, float* exp_avg_sq, int64_t n, const float* grad_parts, int n_parts, int64_t part_stride,
+                    float* grad_out, double lr, double beta1, double beta2, double eps, int64_t step, void* stream) {
+    if (n < 0 || n_parts < 1 || step < 1) return fail(GENIE_ERR_ARG, "genie_adam_step: n >= 0, n_parts >= 1 and step >= 1 required");
+    if (n_parts > AD_MAX_PARTS) return fail(GENIE_ERR_ARG, "genie_adam_step: n_parts <= 32 required");
+    if (!dbl_finite(lr) || !(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !dbl_finite(eps))
+        return fail(GENIE_ERR_ARG, "genie_adam_step: lr and eps must be finite, eps >= 0 and 0 <= beta1, beta2 < 1");
+    if (n > (int64_t)0x7fffffffffffffffLL / 8) return fail(GENIE_ERR_ARG, "genie_adam_step: n too large");
+    if (n == 0) return GENIE_OK;
+    if (!param || !exp_avg || !exp_avg_sq || !grad_parts) return fail(GENIE_ERR_ARG, "genie_adam_step: null argument");
+    if ((((uintptr_t)param) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq) | ((uintptr_t)grad_parts) | ((uintptr_t)grad_out)) & 3)
+        return fail(GENIE_ERR_ARG, "genie_adam_step: arrays must be 4-byte aligned");
+    AdScalars s;
+    s.w1 = (float)(1.0 - beta1);
+    s.beta2 = (float)beta2;
+    s.w2 = (float)(1.0 - beta2);
+    s.neg_step_size = (float)(-(lr / (1.0 - std::pow(beta1, (double)step))));
+    s.bc2_sqrt = (float)std::sqrt(1.0 - std::pow(beta2, (double)step));
+    s.eps = (float)eps;
+    const bool vec_state = ((((uintptr_t)param) | ((uintptr_t)exp_avg) | ((uintptr_t)exp_avg_sq) | ((uintptr_t)grad_out)) & 15) == 0;
+    const bool vec_parts = (((uintptr_t)grad_parts) & 15) == 0 && (n_parts == 1 || (part_stride & 3) == 0);
+    const long long n_quad = ((long long)n + 3) / 4;                       // one thread per four consecutive floats
+    const int nb = (int)std::min<long long>((n_quad + AD_BLOCK - 1) / AD_BLOCK, (long long)AD_MAX_WG);
+    hipStream_t st = (hipStream_t)stream;
+#define GENIE_AD_LAUNCH(VS, VP) \
+    k_adam_step<VS, VP><<<nb, AD_BLOCK, 0, st>>>(param, exp_avg, exp_avg_sq, (long long)n, grad_parts, n_parts, (long long)part_stride, grad_out, s)
+    if (vec_state && vec_parts) GENIE_AD_LAUNCH(true, true);
+    else if (vec_state) GENIE_AD_LAUNCH(true, false);
+    else if (vec_parts) GENIE_AD_LAUNCH(false, true);
+    else GENIE_AD_LAUNCH(false, false);
+#undef GENIE_AD_LAUNCH
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }

@@ -514,6 +514,11 @@ class HipPath(object):
             self.set_weights(view(params) if view is not None else params)
             self._w_key = key
 
+    def mark_weights_changed(self):
+        """Forget what `sync_weights` last uploaded: the next call re-uploads. For a writer that `sync_weights`' key cannot see -- a kernel
+        that updates the parameters through their raw pointers moves neither `data_ptr` nor the in-place version (`train.FlatAdam`)."""
+        self._w_key = None
+
     def input_limit(self):
         """Largest |Slice| / |Mask| entry the f16x2 kernels are verified for with the weights committed so far (genie_input_range)."""
         lim = ctypes.c_float(0.0)

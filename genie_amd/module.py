@@ -571,6 +571,12 @@ class GCN_Detection_Network_extended(nn.Module):
             return self._shard.contexts
         return (self._hip,) if self._hip is not None else ()
 
+    def mark_weights_changed(self):
+        """Tell the live HIP context(s) that the parameters were rewritten behind autograd's back (through their raw pointers, as
+        `train.FlatAdam.step` does): the next forward uploads them again. In-place torch writes need no such call."""
+        for hp in self._contexts():
+            hp.mark_weights_changed()
+
     def _new_cartesian(self, sta_csr, src_csr, n_sta, n_grid, pos_loc, pos_src):
         """A context for the Cartesian product of two base graphs (CSR); on a sharded model this rank's part (genie_amd/dist.py): the
         shard plan from the base source graph and the space-filling-curve order of the source nodes (no collective), the local context

@@ -622,6 +622,26 @@ int genie_refine_select(const float* const* x, int n_used, int64_t n_query, int 
 int genie_refine_cloud(uint64_t key0, uint64_t key1, uint64_t source, int64_t n_query, double sx, double sy, double sz, double rx, double ry,
                        double rz, double mx, double my, double mz, double* r, double* xc, float* xq, void* stream);
 
+/* The optimizer step of a training batch in one launch: the ranks' gradient parts summed in rank order, then torch.optim.Adam's update
+ * (defaults: no weight decay, no amsgrad, not maximize; train_GENIE_model.py:1383, :1861) on flat arrays. Needs no context. Per element j:
+ *   g = 0.0f;  for r = 0 .. n_parts-1:  g = g + grad_parts[r * part_stride + j]      fp32, in that order, never fused or reassociated:
+ *       the bits of `g = zeros; g += part_r` part by part (one part: g is that part as a value);
+ *   m = fma(g - m, 1 - beta1, m);   v = fma((1 - beta2) * g, g, beta2 * v);
+ *   p = p + (-(lr / (1 - beta1^step)) * m) / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * in fp32, operation by operation as torch's single-tensor Adam rounds it on the CPU (lerp_ and addcmul_ end in one fused multiply-add
+ * each, written out here; everything else is rounded on its own: mul_, sqrt / div / add_, addcdiv_); square root and division are
+ * correctly rounded. step >= 1 is the step being taken; the scalars 1 - beta1, 1 - beta2,
+ * lr / (1 - beta1^step) and sqrt(1 - beta2^step) are formed here in double and rounded to fp32 once. An element with g = m = v = 0
+ * keeps the bits of p, m and v (a parameter that never gets a gradient rides along as zeros). param, exp_avg (m), exp_avg_sq (v) [n]
+ * fp32 on the device, updated in place; grad_parts: n_parts arrays of n floats, part r at grad_parts + r * part_stride (part_stride in
+ * floats, ignored for one part); grad_out [n] or NULL receives g and must not overlap the parts. 16-byte accesses are used where the
+ * pointers (and part_stride) are multiples of 16 bytes, 4-byte ones otherwise: any layout gives the same bits. 64-bit offsets, no
+ * atomics, no scratch; two calls with the same arguments and state write the same bits. n == 0 returns GENIE_OK without a launch. Bad
+ * arguments (n < 0, n_parts < 1 or > 32, step < 1, with n > 0 a null param / exp_avg / exp_avg_sq / grad_parts, a pointer that is not
+ * 4-byte aligned, beta outside [0, 1), negative eps, non-finite lr / eps) return GENIE_ERR_ARG before any launch and touch nothing. */
+int genie_adam_step(float* param, float* exp_avg, float* exp_avg_sq, int64_t n, const float* grad_parts, int n_parts, int64_t part_stride,
+                    float* grad_out, double lr, double beta1, double beta2, double eps, int64_t step, void* stream);
+
 /* Debug/parity access to intermediates kept in the workspace (which: 0 = c [P,30], 1 = wu [P,15], 2 = wv [P,15]);
  * copies de-padded rows into `out` (async). */
 int genie_ws_export(genie_ctx* ctx, int which, void* ws, float* out, void* stream);
