@@ -464,6 +464,7 @@ class GridLeg(object):
         if trv_times.ndim != 3 or trv_times.shape[1] != n_sta or trv_times.shape[2] != 2:
             raise ValueError("GridLeg: trv_times must be [G, %d, 2] over the model's stations (pass ind_use= to cut the table of all "
                              "stations down, process_utils.py:599), got %s" % (n_sta, tuple(trv_times.shape)))
+        self.n_sta = int(n_sta)
         if pairs is not None:
             pairs = np.asarray(pairs)
             self.trv = torch.from_numpy(np.ascontiguousarray(trv_times[pairs[1], pairs[0]]).reshape(-1, 2)).to(self.device)
@@ -640,6 +641,118 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
     if sp is not None and not sp.collective:
         return found, (b_lo, b_hi)
     return refined_from_found(found, srcs, tq_host, to_geographic)
+
+
+def apply_windows_legs(legs, picks, x_query_cart, locs_cart, max_t, tsteps_abs=None, t_win=6.0, step_size="half", min_required_picks=1,
+                       day_len=86400.0, kernel_sig_t=synthetic.KERNEL_SIG_T, dt_embed=None, times=None, tail_batch=16,
+                       window_parallel=None, return_info=False, merge_timeout=60.0):
+    """The day's apply loop over several source grids into ONE `Out_2` (process_continuous_days.py:761-810, `for n in times_need: for
+    x_grid_ind in x_grid_ind_list:`): every kept window runs on every leg of `legs` (`GridLeg`s, `use_subgraph` ones made with `pairs=`
+    included; at most `engine.STACK_MAX_LEGS`, every leg with a model of its own), and all of them add into the same `Out_2`
+    [n_query, len(tsteps_abs)], divided by `n_overlap * len(legs)` (:802-805). Returns (Out_2 on the device, window start times used) --
+    the `Out_2` that `detect_refine_associate(legs, picks, Out_2, ...)` takes. `picks`: the day's `ResidentPicks` (uploaded once, shared
+    by all legs); `x_query_cart` [Q, 3]: shared by all legs, each net caching its own kNN of the queries into its grid; `locs_cart`
+    [S, 3]: the stations, as the per-source passes take them (the window path reads station positions from each model's adjacencies:
+    here only the count is checked). Each leg brings its grid and its travel-time rows. The other arguments are those of
+    `apply_windows_device`; the schedule is made once, from `picks.t_host`, and a window without a pick in the embedding range is
+    skipped for every leg (:792-793).
+
+    Per kept window, in window order, every leg in leg order embeds and pushes the window; when `tail_batch` windows are pending (or at
+    the last one) every leg flushes its batched tail and ONE `genie_stack_windows_legs` launch adds all legs' read-outs, in (window,
+    leg) order: the summation order of the reference loop, which L single-grid runs added together afterwards, `(sum_w a_w) + (sum_w
+    b_w)`, do not have -- and one dense `Out_2` instead of L. With one leg the result is `apply_windows_device(stack_on_device=True)`
+    bit for bit.
+
+    `window_parallel`: `(rank, world)` or a process group, as in `apply_windows_device`: rank r runs all legs of the windows
+    `window_blocks(len(times), world)[r]` into a zero-initialised full-size `Out_2`; the tuple form returns that partial and the rank's
+    `times`, the group form merges once (`_merge_partials`) and returns the full `times`. What is exact: a rank's partial is bit for bit
+    what one GPU computes over that block of windows; the merged `Out_2` is bit-equal to one GPU in every column fed by one rank's
+    windows only; in a column at a block boundary it is `fl(prefix) + fl(suffix)`. With more than one leg that also differs from one
+    GPU on the default 'half' schedule, unlike the single-grid loop: a boundary column then has 2 L terms, split L | L, and two rounded
+    sums of L terms added are not the running sum of 2 L. `return_info`: `window_parallel_info` of the run plus `rank`; its
+    `exact_merge` keeps its meaning, independence from the order in which the collective adds the ranks. A source-node-sharded leg is
+    refused (batched tails do not run on shards). No multi-GPU wall time has been measured."""
+    legs = list(legs)
+    if not legs:
+        raise ValueError("apply_windows_legs: no grid leg")
+    if len(legs) > engine.STACK_MAX_LEGS:
+        raise ValueError("apply_windows_legs: at most %d grid legs" % engine.STACK_MAX_LEGS)
+    if any(getattr(leg.net, "is_sharded", False) for leg in legs):
+        raise NotImplementedError("apply_windows_legs on a source-node-sharded leg: batched tails do not run on shards and the hybrid is "
+                                  "not built; use an unsharded model per grid")
+    wp = _rank_split(window_parallel, "window_parallel", False)
+    dev = torch.device(picks.device)
+    for l, leg in enumerate(legs):
+        if torch.device(leg.device) != dev:
+            raise ValueError("apply_windows_legs: leg %d lives on %s, the picks on %s" % (l, leg.device, dev))
+        if leg.n_sta != picks.n_sta:
+            raise ValueError("apply_windows_legs: leg %d has %d stations, the picks %d" % (l, leg.n_sta, picks.n_sta))
+    if len({id(leg.net) for leg in legs}) != len(legs):
+        raise ValueError("apply_windows_legs: two legs share one model (their pending windows would interleave); build one model per leg")
+    if np.asarray(locs_cart).shape[0] != picks.n_sta:
+        raise ValueError("apply_windows_legs: locs_cart has %d stations, the picks %d" % (np.asarray(locs_cart).shape[0], picks.n_sta))
+    if len(picks) == 0:
+        raise ValueError("apply_windows_legs: no pick of the model's stations")
+    max_t = float(max_t)
+    dt_embed = _dt_embed(kernel_sig_t, dt_embed)
+    tsteps_abs, times, offsets, n_overlap = _day_schedule(picks.t_host.reshape(-1, 1), max_t, day_len, t_win, step_size, min_required_picks,
+                                                          tsteps_abs, times)
+    drop_last = step_size == "half"
+    lo = np.searchsorted(picks.t_host, times - 2.0 * kernel_sig_t, side="right")                  # strict >, process_utils.py:476
+    hi = np.searchsorted(picks.t_host, times + max_t + 2.0 * kernel_sig_t, side="left")           # strict <
+    nonempty = hi > lo                                                                             # process_continuous_days.py:792-793
+    times, lo, hi = times[nonempty], lo[nonempty], hi[nonempty]
+    asc = is_ascending(tsteps_abs)
+    all_times, info = times, None
+    if return_info:
+        rank, world = (wp.rank, wp.world) if wp is not None else (0, 1)
+        info = dict(window_parallel_info(window_cols_table(tsteps_abs, times, offsets, drop_last, asc), len(tsteps_abs), world), rank=rank)
+    if wp is not None:
+        b_lo, b_hi = window_blocks(len(times), wp.world)[wp.rank]
+        times, lo, hi = times[b_lo:b_hi], lo[b_lo:b_hi], hi[b_lo:b_hi]
+    h_cols = window_cols_table(tsteps_abs, times, offsets, drop_last, asc)
+    scale = float(np.float32(1.0) / np.float32(n_overlap * len(legs)))     # `tensor / host scalar` in torch: times the fp32 reciprocal
+    with torch.no_grad(), torch.cuda.device(dev):
+        for leg in legs:
+            leg.net.window_batch = tail_batch
+        d_cols = torch.from_numpy(h_cols).to(dev)
+        xq = torch.as_tensor(x_query_cart).float().to(dev)
+        tq = torch.from_numpy(offsets.reshape(-1, 1)).float().to(dev)
+        Out_2 = torch.zeros((xq.shape[0], len(tsteps_abs)), dtype=torch.float32, device=dev)
+        main = torch.cuda.current_stream(dev)
+        stacker = torch.cuda.Stream(device=dev)      # every flush's stack runs here, so each one is behind the one before it
+        stacker.wait_stream(main)                    # Out_2's zeros and the table
+        first = 0
+        for w, t0 in enumerate(times):
+            a, b = int(lo[w]), int(hi[w])
+            for leg in legs:
+                Slice, Mask = leg.net.embed_window(picks.t[a:b], picks.sta[a:b], picks.phase[a:b], float(t0), max_t, kernel_sig_t, dt_embed,
+                                                   leg.trv, presplit=True)
+                pending = leg.net.push_window(Slice, Mask)
+            if pending != tail_batch and w != len(times) - 1:
+                continue
+            xs = []
+            for leg in legs:                          # every leg's tail + read-outs of the pushed windows, each on a side stream of its own
+                x, done = leg.net.flush_windows(leg.x_grid_cart, xq, tq)[1:]
+                stacker.wait_event(done)
+                x.record_stream(stacker)
+                xs.append(x)
+            used = h_cols[first:w + 1]
+            used = used[used >= 0]
+            if used.size:
+                with torch.cuda.stream(stacker):      # one launch for all legs
+                    engine.stack_windows_legs(Out_2, xs, d_cols[first:w + 1], scale, int(used.min()), int(used.max()))
+            first = w + 1
+        for leg in legs:
+            leg.net._hip.wait_tails()
+        main.wait_stream(stacker)
+    main.synchronize()                                # the verdicts of the day's last windows: one wait per day
+    for leg in legs:
+        _check_verdicts(leg.net)
+    if wp is not None and wp.collective:
+        _merge_partials(Out_2, wp.group, merge_timeout)
+        times = all_times
+    return (Out_2, times, info) if return_info else (Out_2, times)
 
 
 def _inside_region(X, ranges):

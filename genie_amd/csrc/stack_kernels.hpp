@@ -40,3 +40,47 @@ __global__ __launch_bounds__(256) void k_stack_windows(const float* __restrict__
     }
     if (hit) *o = acc;
 }
+
+// ------------------------------------------------------------------------------------------------
+// The same stacking over the L source grids ("legs") of a day (process_continuous_days.py:761-810: `for n in times_need: for x_grid_ind
+// in x_grid_ind_list:`, every leg adding into the one Out_2):
+//   Out_2[q, cols[k][j]] += x_l[k, q, j] * scale, for k, then j, then l = 0..L-1 INNERMOST, entries cols[k][j] < 0 skipped.
+// A table row that lists no column twice (window_cols_table makes such rows) gives every output element at most one j per window, so
+// the owner's order (k, l) is the reference's `for window: for leg: Out_2[:, cols] += x / d`. Work split, LDS table, 64-bit offsets,
+// rounding (contraction off) and the untouched-element rule are the sibling's; L = 1 is the sibling bit for bit. The leg pointers
+// travel by value in the kernel arguments, as k_refine_select_partial takes them: the loop over l indexes the kernel-argument segment
+// (scalar loads), no private copy of the table exists and nothing is copied to the device before the launch.
+// ------------------------------------------------------------------------------------------------
+constexpr int SW_MAX_LEGS = 32;
+
+struct SwLegs {
+    const float* x[SW_MAX_LEGS];
+};
+
+__global__ __launch_bounds__(256) void k_stack_windows_legs(SwLegs legs, int L, const int32_t* __restrict__ cols, int B, long long Q, int T,
+                                                            float scale, float* __restrict__ out, long long n_cols, int c_min, int width) {
+#pragma clang fp contract(off)
+    __shared__ int32_t s_cols[SW_MAX_B * SW_MAX_T];
+    for (int i = threadIdx.x; i < B * T; i += 256) s_cols[i] = cols[i];
+    __syncthreads();
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= Q * width) return;
+    const long long q = i / width;
+    const int c = c_min + (int)(i - q * width);
+    float* o = out + q * n_cols + c;                 // 64-bit element offset, as in k_stack_windows
+    float acc = *o;
+    bool hit = false;
+    for (int k = 0; k < B; ++k) {
+        const long long row = ((long long)k * Q + q) * T;      // 64-bit element offset into every leg's x
+        for (int j = 0; j < T; ++j) {
+            if (s_cols[k * T + j] == c) {
+                for (int l = 0; l < L; ++l) {
+                    const float v = legs.x[l][row + j] * scale;
+                    acc = acc + v;
+                }
+                hit = true;
+            }
+        }
+    }
+    if (hit) *o = acc;
+}

@@ -72,6 +72,40 @@ def stack_windows(out, x, cols, scale, c_min, c_max):
     return out
 
 
+STACK_MAX_LEGS = 32       # leg pointers of one genie_stack_windows_legs launch (= postproc.REFINE_SELECT_MAX_LEGS: one limit for a day's legs)
+
+
+def stack_windows_legs(out, xs, cols, scale, c_min, c_max):
+    """`out[q, cols[k, j]] += xs[l][k, q, j] * scale` for k, then j, then l innermost, entries `cols < 0` skipped
+    (genie_stack_windows_legs: one launch on the current stream for all legs, no atomics). With a table whose rows list no column twice
+    (`apply.window_cols_table`) these are the bits of the reference's `for window: for leg: Out_2.index_add_(...)`; a row that lists a
+    column twice adds twice, in (k, j, l) order. `xs`: 1..STACK_MAX_LEGS tensors, each as `stack_windows` takes `x`, on `out`'s device;
+    their storage is read in place (keep them alive, and known to the launch's stream, until it has run)."""
+    lib = _lib.load()
+    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.is_contiguous()):
+        raise ValueError("stack_windows_legs: out must be a contiguous fp32 GPU tensor [n_query, n_cols]")
+    if not (torch.is_tensor(cols) and cols.is_cuda and cols.dtype == torch.int32 and cols.dim() == 2 and cols.is_contiguous()):
+        raise ValueError("stack_windows_legs: cols must be a contiguous int32 GPU tensor [n_windows, n_offsets]")
+    xs = list(xs)
+    if not 1 <= len(xs) <= STACK_MAX_LEGS:
+        raise ValueError("stack_windows_legs: 1 to %d legs per call, got %d" % (STACK_MAX_LEGS, len(xs)))
+    B, T = int(cols.shape[0]), int(cols.shape[1])
+    Q = int(out.shape[0])
+    xs = [_f32(x, "x") for x in xs]
+    for x in xs:
+        if x.device != out.device:
+            raise ValueError("stack_windows_legs: x lives on %s, out on %s" % (x.device, out.device))
+        if x.numel() != B * Q * T or tuple(x.shape[:3]) not in ((B, Q, T), (Q, T, 1), (Q, T)):
+            raise ValueError("stack_windows_legs: x %s does not match cols %s and out %s" % (tuple(x.shape), tuple(cols.shape), tuple(out.shape)))
+    if Q == 0:
+        return out
+    ptrs = (ctypes.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
+    with torch.cuda.device(out.device):
+        _lib.check(lib.genie_stack_windows_legs(ptrs, len(xs), _ptr(cols), B, Q, T, float(scale), _ptr(out), int(out.shape[1]), int(c_min),
+                                                int(c_max), _stream()), "genie_stack_windows_legs")
+    return out
+
+
 def knn_graph_device(points, k):
     """Base kNN graph of a point set on the device: the layout of `remove_self_loops(knn(x, x, k + 1).flip(0))`
     (process_utils.py:718-719) as (table int32 [n, k], edge list int64 [2, n * k] with row 0 = neighbour, row 1 = centre)."""

@@ -585,6 +585,20 @@ int genie_local_marching(const double* xs, const double* t, const float* val, co
 int genie_stack_windows(const float* x, const int32_t* cols, int n_windows, int64_t n_query, int n_offsets, float scale, float* out,
                         int64_t n_cols, int64_t c_min, int64_t c_max, void* stream);
 
+/* The same stacking over the source grids ("legs") of a day (process_continuous_days.py:761-810: every window runs on every grid and all
+ * of them add into the one Out_2), one launch per flush of all legs:
+ *   for k in 0..n_windows-1, for j in 0..n_offsets-1, for l in 0..n_legs-1 (innermost):
+ *       c = cols[k][j];  if c < 0: skip;   out[q, c] += x_legs[l][k, q, j] * scale   for every query q
+ * A row of cols that lists no column twice (apply.window_cols_table makes only such rows) feeds an element of out at most once per window,
+ * so the order is exactly `for window: for leg: out.index_add_(1, cols_k, x_l[k] * scale)`; a row that does list a column twice adds
+ * twice, in (k, j, l) order. x_legs: HOST array of n_legs device pointers, each to fp32 [n_windows, n_query, n_offsets] (64-bit element
+ * offsets); the pointers travel in the kernel arguments, so the call copies nothing and never waits. 1 <= n_legs <= 32; cols, out,
+ * [c_min, c_max], scale and the ranges of n_windows, n_offsets, n_cols as in genie_stack_windows, to which n_legs = 1 is equal bit for
+ * bit. No atomics, the product rounded before the add; an element no entry lists is not written. Bad arguments (a null table, a null
+ * pointer in it, n_legs outside 1..32, any range error of genie_stack_windows) return GENIE_ERR_ARG before any launch. */
+int genie_stack_windows_legs(const float* const* x_legs, int n_legs, const int32_t* cols, int n_windows, int64_t n_query, int n_offsets,
+                             float scale, float* out, int64_t n_cols, int64_t c_min, int64_t c_max, void* stream);
+
 /* Selection of the refined source out of the grid legs' query read-outs (the refine pass, process_continuous_days.py:972-978), one call
  * per candidate source instead of a chain of full passes over [n_query, n_t]:
  *   acc[q, t] = fp32 sum over l = 0..n_used-1, in that order and starting from 0.0f, of x[l][q, t] / n_scale, computed as torch computes
