@@ -16,10 +16,13 @@ output to the host, `:803-805`); nothing in the loop synchronises with the host.
 `apply_windows` takes any host embedding callable (default: `genie_amd.synthetic.make_slice_mask`, the exact
 nearest-pick semantics of `process_utils.py:262-275`). `apply_windows_device` is the GPU-only loop: picks and the static
 travel-time table stay resident on the device and every window's `Slice/Mask` is produced by `genie_embed_window`
-(`extract_input_from_data`, `process_utils.py:460-642`), so a window costs no host->device copy at all.
+(`extract_input_from_data`, `process_utils.py:460-642`), so a window costs no host->device copy at all. `apply_windows_legs` runs
+the same loop over several source grids into one `Out_2`. Both are adapters: their arguments become a `_day_plan` (schedule, pick
+ranges, this rank's windows, column table: host arithmetic, once) and a list of lanes, and `_run_day` is the one loop over them.
 """
 import collections
 import threading
+import types
 
 import numpy as np
 import torch
@@ -237,9 +240,10 @@ def apply_windows_device(net, geom, P, trv_times, tsteps_abs=None, t_win=6.0, st
     per G-sized tail (1..16; 16 is the default of the bench and measured best with the device embedding in the loop, bench.py --mode
     stream: the tail kernels are latency-bound, their fixed costs are paid once per batch).
 
-    `stack_on_device`: accumulate into `Out_2` with ONE `genie_stack_windows` launch per flush (per window when `window_batch == 1`)
-    instead of a slice, a scaling and an `index_add_` per window; same side stream, same event chain, same summation order, bit-equal
-    `Out_2`.
+    `stack_on_device`: accumulate into `Out_2` with ONE `genie_stack_windows_legs` launch per flush (per window when `window_batch == 1`)
+    instead of a slice, a scaling and an `index_add_` per window; same stacker stream, same summation order, bit-equal `Out_2`. The loop
+    is the one of `apply_windows_legs` (`_run_day`), of which this is the one-grid case: the torch statements stay as the reference the
+    kernel is held against.
 
     `window_parallel`: split the day's windows over GPUs. `(rank, world)`, or a `torch.distributed`
     process group (True: the default group). After all filters, rank r takes the contiguous block `window_blocks(len(times), world)[r]`
@@ -255,107 +259,148 @@ def apply_windows_device(net, geom, P, trv_times, tsteps_abs=None, t_win=6.0, st
     bits are independent of the collective's reduction order). A source-sharded model cannot be combined with `window_parallel`.
     No multi-GPU speed-up has been measured: ranks sharing one GPU say nothing about it, and the first run on N > 1 GPUs is still ahead
     (DESIGN.md section 9.1)."""
-    hp = net._hip
     sharded = getattr(net, "is_sharded", False)       # source-node-sharded model: this rank embeds and runs its owned + halo rows only;
     wp = _rank_split(window_parallel, "window_parallel", sharded)
-    stack_on_device = stack_on_device or wp is not None
     net.window_batch = 1 if sharded else tail_batch   # the tail follows the shard's all-gather, one per window (module.py docstring)
-    dev = hp.device
     max_t = float(max_t if max_t is not None else np.ceil(trv_times.max() + 1.0))
     dt_embed = _dt_embed(kernel_sig_t, dt_embed)
-    tsteps_abs, times, offsets, n_overlap = _day_schedule(P, max_t, day_len, t_win, step_size, min_required_picks, tsteps_abs, times)
-    order = np.argsort(P[:, 0], kind="stable")
-    Ps = P[order]
-    d_t = torch.from_numpy(Ps[:, 0].copy()).to(dev)
-    d_sta = torch.from_numpy(Ps[:, 1].astype(np.int32)).to(dev)
+    Ps = P[np.argsort(P[:, 0], kind="stable")]
+    plan = _day_plan(Ps[:, 0], max_t, day_len, t_win, step_size, min_required_picks, tsteps_abs, times, kernel_sig_t, n_grids, wp,
+                     return_info)                     # (host only: a bad schedule argument raises before anything is uploaded)
+    lane = GridLeg(net, geom.x_grid, trv_times, pairs=pairs)
+    dev = lane.device
     ph = Ps[:, 4].astype(np.int32)
     if not getattr(net, "use_phase_types", True):        # process_continuous_days.py:562-563 (the embedding zeroes columns 2, 3: :783-786)
         ph = np.zeros_like(ph)
-    d_ph = torch.from_numpy(ph).to(dev)
-    if pairs is not None:        # process_utils.py:605 `trv_times[src, ind_use[sta], :]` per listed product node
-        pairs = np.asarray(pairs)
-        d_trv = torch.from_numpy(np.ascontiguousarray(np.asarray(trv_times, dtype=np.float32)[pairs[1], pairs[0]])).to(dev)
-    else:
-        d_trv = net.node_rows(np.asarray(trv_times, dtype=np.float32), 2)          # (a shard: its own rows, cut out on the host)
-    Out_2 = torch.zeros((geom.x_query.shape[0], len(tsteps_abs)), dtype=torch.float32, device=dev)
-    locs = torch.from_numpy(geom.locs).float().to(dev)
-    xg = torch.from_numpy(geom.x_grid).float().to(dev)
+    picks = types.SimpleNamespace(t_host=Ps[:, 0], t=torch.from_numpy(Ps[:, 0].copy()).to(dev),
+                                  sta=torch.from_numpy(Ps[:, 1].astype(np.int32)).to(dev), phase=torch.from_numpy(ph).to(dev))
+    Out_2 = torch.zeros((geom.x_query.shape[0], len(plan.tsteps_abs)), dtype=torch.float32, device=dev)
     xq = torch.from_numpy(geom.x_query).float().to(dev)
-    tq = torch.from_numpy(offsets.reshape(-1, 1)).float().to(dev)
+    add = _fused_add(plan, Out_2) if stack_on_device or wp is not None else _torch_add(plan, Out_2)
+    return _run_day(plan, [lane], picks, xq, Out_2, add, dt_embed, merge_timeout)
+
+
+_DayPlan = collections.namedtuple(
+    "_DayPlan", "tsteps_abs offsets times lo hi all_times drop_last h_cols divisor scale info max_t kernel_sig_t split")
+
+
+def _day_plan(t_sorted, max_t, day_len, t_win, step_size, min_required_picks, tsteps_abs, times, kernel_sig_t, n_grids, split, return_info):
+    """What a day's apply loop knows before its first launch, host arithmetic on small arrays: the schedule (`_day_schedule` of the
+    time-sorted pick times `t_sorted`, or the caller's `tsteps_abs` / `times`); per kept window the range [lo, hi) of the picks its
+    embedding reads (a window whose range is empty is dropped); this rank's block of them under `split` (a `_RankSplit` or None;
+    `all_times`: every rank's); `h_cols` = the block's `window_cols_table` (-1: an offset that adds nothing), of which a flush takes its
+    rows; `divisor` = n_overlap * `n_grids` and `scale`, its fp32 reciprocal; `info` (`return_info`) = `window_parallel_info` plus
+    `rank`."""
+    tsteps_abs, times, offsets, n_overlap = _day_schedule(t_sorted.reshape(-1, 1), max_t, day_len, t_win, step_size, min_required_picks,
+                                                          tsteps_abs, times)
     drop_last = step_size == "half"
-    # per-window pick ranges and Out_2 column indices are host arithmetic on tiny arrays, done up front
-    lo = np.searchsorted(Ps[:, 0], times - 2.0 * kernel_sig_t, side="right")                      # strict >, process_utils.py:476
-    hi = np.searchsorted(Ps[:, 0], times + max_t + 2.0 * kernel_sig_t, side="left")               # strict <
+    lo = np.searchsorted(t_sorted, times - 2.0 * kernel_sig_t, side="right")                      # strict >, process_utils.py:476
+    hi = np.searchsorted(t_sorted, times + max_t + 2.0 * kernel_sig_t, side="left")               # strict <
     nonempty = hi > lo                                                                             # process_continuous_days.py:792-793
     times, lo, hi = times[nonempty], lo[nonempty], hi[nonempty]
     asc = is_ascending(tsteps_abs)
     all_times, info = times, None
     if return_info:                                     # (the table of ALL windows: a rank's loop needs its own block's rows only)
-        rank, world = (wp.rank, wp.world) if wp is not None else (0, 1)
+        rank, world = (split.rank, split.world) if split is not None else (0, 1)
         info = dict(window_parallel_info(window_cols_table(tsteps_abs, times, offsets, drop_last, asc), len(tsteps_abs), world), rank=rank)
-    if wp is not None:                                  # this rank's contiguous block of the final window list
-        b_lo, b_hi = window_blocks(len(times), wp.world)[wp.rank]
+    if split is not None:                               # this rank's contiguous block of the final window list
+        b_lo, b_hi = window_blocks(len(times), split.world)[split.rank]
         times, lo, hi = times[b_lo:b_hi], lo[b_lo:b_hi], hi[b_lo:b_hi]
-    if stack_on_device:
-        # the whole loop's [n, T] column table once (-1: an offset that adds nothing); a flush hands the kernel its rows of it
-        h_cols = window_cols_table(tsteps_abs, times, offsets, drop_last, asc)
-        d_cols = torch.from_numpy(h_cols).to(dev)
-        scale = float(np.float32(1.0) / np.float32(n_overlap * n_grids))   # `tensor / host scalar` in torch: times the fp32 reciprocal
+    h_cols = window_cols_table(tsteps_abs, times, offsets, drop_last, asc)
+    divisor = n_overlap * n_grids
+    scale = float(np.float32(1.0) / np.float32(divisor))       # `tensor / host scalar` in torch: times the fp32 reciprocal
+    return _DayPlan(tsteps_abs, offsets, times, lo, hi, all_times, drop_last, h_cols, divisor, scale, info, max_t, kernel_sig_t, split)
+
+
+def _fused_add(plan, Out_2):
+    """`add(xs, first, n)` of `_run_day`: ONE `genie_stack_windows_legs` launch for the read-outs `xs` (one per lane) of windows first ..
+    first + n - 1, over their rows of the column table."""
+    d_cols = torch.from_numpy(plan.h_cols).to(Out_2.device)
+
+    def add(xs, first, n):
+        used = plan.h_cols[first:first + n]
+        used = used[used >= 0]
+        if used.size:
+            engine.stack_windows_legs(Out_2, xs, d_cols[first:first + n], plan.scale, int(used.min()), int(used.max()))
+    return add
+
+
+def _torch_add(plan, Out_2):
+    """`add(xs, first, n)` of `_run_day` in torch statements, the reference of the fused one (one lane): per window a slice, a scaling
+    and an `index_add_`; a gather instead of the slice only for a window that lists a column twice."""
+    n_off = plan.h_cols.shape[1] - (1 if plan.drop_last else 0)
+    keeps = None
+    if (plan.h_cols[:, :n_off] >= 0).all():                # the usual case: no duplicate column inside a window
+        cols = torch.from_numpy(plan.h_cols[:, :n_off].astype(np.int64)).to(Out_2.device)
     else:
-        wc = [window_columns(tsteps_abs, t0, offsets, drop_last, asc) for t0 in times]
-        n_off = len(offsets) - (1 if drop_last else 0)
-        if all(len(k) == n_off for _, k in wc):            # the usual case: no duplicate column inside a window
-            cols = torch.from_numpy(np.stack([c_ for c_, _ in wc]) if wc else np.zeros((0, n_off), dtype=np.int64)).to(dev)
-            keeps = None
-        else:
-            cols = [torch.from_numpy(c_).to(dev) for c_, _ in wc]
-            keeps = [torch.from_numpy(k_).to(dev) for _, k_ in wc]
-    acc_done = [None]
+        cols = [torch.from_numpy(row[row >= 0].astype(np.int64)).to(Out_2.device) for row in plan.h_cols]
+        keeps = [torch.from_numpy(np.flatnonzero(row >= 0)).to(Out_2.device) for row in plan.h_cols]
 
-    def window_vals(xw, w):             # xw [Q, T, 1] of window w -> the kept offsets
-        if keeps is not None:
-            return xw[:, keeps[w], 0]
-        return xw[:, :-1, 0] if drop_last else xw[:, :, 0]
+    def add(xs, first, n):
+        (x,) = xs                                          # [n, Q, T, 1]
+        for k in range(n):
+            w = first + k
+            vals = x[k][:, keeps[w], 0] if keeps is not None else (x[k][:, :-1, 0] if plan.drop_last else x[k][:, :, 0])
+            Out_2.index_add_(1, cols[w], vals / plan.divisor)
+    return add
 
-    def accumulate(x, first):
-        # x [n, Q, T, 1] of windows first .. first + n - 1 -> Out_2, on the side stream the forward / flush call before this one set:
-        # window by window and batch by batch in order (overlapping columns: a fixed summation order), each behind the one before it
-        n = x.shape[0]
-        with torch.cuda.stream(hp.side_stream):
-            if acc_done[0] is not None:
-                hp.side_stream.wait_event(acc_done[0])
-            if stack_on_device:         # one launch
-                used = h_cols[first:first + n]
-                used = used[used >= 0]
-                if used.size:
-                    engine.stack_windows(Out_2, x, d_cols[first:first + n], scale, int(used.min()), int(used.max()))
-            else:
-                for k in range(n):
-                    Out_2.index_add_(1, cols[first + k], window_vals(x[k], first + k) / (n_overlap * n_grids))
-            acc_done[0] = torch.cuda.Event()
-            acc_done[0].record(hp.side_stream)
 
-    with torch.no_grad():
+def _run_day(plan, lanes, picks, xq, Out_2, add, dt_embed, merge_timeout):
+    """The day's loop over the windows of `plan`. `lanes`: one per source grid, each with `net`, `x_grid_cart` and `trv` (a `GridLeg`), all
+    with the same `window_batch`; `picks`: the time-sorted picks on the device (`t_host`, `t`, `sta`, `phase`: a `ResidentPicks`). Per
+    window, in window order, every lane in lane order embeds the window and runs its P-sized part (`push_window`), or the whole window
+    with a tail of its own when `window_batch` is 1 (`forward_fixed_source_pipelined`: a source-node-sharded model among them). When
+    `window_batch` windows are pending, or at the last one, every lane's tail runs on a side stream of its own (`flush_windows`) and
+    `add(xs, first, n)` puts the lanes' read-outs `xs` of windows first .. first + n - 1 into `Out_2`, on the one stacker stream: behind
+    each tail's `done` event, and every flush behind the one before it (overlapping columns: a fixed summation order). Nothing waits for
+    the host until the end: one synchronisation per day, then the verdicts of every lane and, in the group form of the plan's rank
+    split, the merge. Returns (Out_2, times used[, info])."""
+    dev = Out_2.device
+    times = plan.times
+    with torch.no_grad(), torch.cuda.device(dev):
+        tq = torch.from_numpy(plan.offsets.reshape(-1, 1)).float().to(dev)
+        batch = lanes[0].net.window_batch
+        main = torch.cuda.current_stream(dev)
+        stacker = torch.cuda.Stream(device=dev)      # every flush's stack runs here, so each one is behind the one before it
+        stacker.wait_stream(main)                    # Out_2's zeros and the tables
+
+        def on_stacker(x, done):                     # a lane's read-out, produced on its side stream, made known to the stacker
+            stacker.wait_event(done)
+            x.record_stream(stacker)
+            return x
+
         first = 0
         for w, t0 in enumerate(times):
-            a, b = int(lo[w]), int(hi[w])
-            Slice, Mask = net.embed_window(d_t[a:b], d_sta[a:b], d_ph[a:b], float(t0), max_t, kernel_sig_t, dt_embed, d_trv,
-                                           presplit=True)    # the push below is the only consumer of (Slice, Mask)
-            if net.window_batch == 1:     # one tail per window: the batch of one (a view, no launch)
-                x = net.forward_fixed_source_pipelined(Slice, Mask, None, None, None, locs, xg, xq, tq)[1].unsqueeze(0)
-            elif net.push_window(Slice, Mask) == net.window_batch or w == len(times) - 1:
-                x = net.flush_windows(xg, xq, tq)[1]      # tail + read-outs of the pushed windows in one set of launches
-            else:
-                continue
-            accumulate(x, first)
+            a, b = int(plan.lo[w]), int(plan.hi[w])
+            if batch == 1:
+                xs = []
+            for lane in lanes:
+                Slice, Mask = lane.net.embed_window(picks.t[a:b], picks.sta[a:b], picks.phase[a:b], float(t0), plan.max_t, plan.kernel_sig_t,
+                                                    dt_embed, lane.trv, presplit=True)    # the call below is the only consumer of (Slice, Mask)
+                if batch == 1:                        # one tail per window: the batch of one (a view, no launch)
+                    _, x, done = lane.net.forward_fixed_source_pipelined(Slice, Mask, None, None, None, None, lane.x_grid_cart, xq, tq)
+                    xs.append(on_stacker(x.unsqueeze(0), done))
+                else:
+                    pending = lane.net.push_window(Slice, Mask)
+            if batch > 1:
+                if pending != batch and w != len(times) - 1:
+                    continue
+                # every lane's tail + read-outs of the pushed windows in one set of launches, each on a side stream of its own
+                xs = [on_stacker(*lane.net.flush_windows(lane.x_grid_cart, xq, tq)[1:]) for lane in lanes]
+            with torch.cuda.stream(stacker):
+                add(xs, first, w + 1 - first)
             first = w + 1
-        hp.wait_tails()
-    torch.cuda.current_stream(dev).synchronize()      # the verdicts of the day's last windows: one wait per day
-    _check_verdicts(net)
-    if wp is not None and wp.collective:        # group form: one all-reduce of the ranks' partials; every rank gets the day
-        _merge_partials(Out_2, wp.group, merge_timeout)
-        times = all_times
-    return (Out_2, times, info) if return_info else (Out_2, times)
+        for lane in lanes:
+            lane.net._hip.wait_tails()
+        main.wait_stream(stacker)
+    main.synchronize()                                # the verdicts of the day's last windows: one wait per day
+    for lane in lanes:
+        _check_verdicts(lane.net)
+    split = plan.split
+    if split is not None and split.collective:        # group form: one all-reduce of the ranks' partials; every rank gets the day
+        _merge_partials(Out_2, split.group, merge_timeout)
+        times = plan.all_times
+    return (Out_2, times) if plan.info is None else (Out_2, times, plan.info)
 
 
 def _merge_partials(Out_2, group, timeout):
@@ -659,9 +704,9 @@ def apply_windows_legs(legs, picks, x_query_cart, locs_cart, max_t, tsteps_abs=N
 
     Per kept window, in window order, every leg in leg order embeds and pushes the window; when `tail_batch` windows are pending (or at
     the last one) every leg flushes its batched tail and ONE `genie_stack_windows_legs` launch adds all legs' read-outs, in (window,
-    leg) order: the summation order of the reference loop, which L single-grid runs added together afterwards, `(sum_w a_w) + (sum_w
-    b_w)`, do not have -- and one dense `Out_2` instead of L. With one leg the result is `apply_windows_device(stack_on_device=True)`
-    bit for bit.
+    leg) order (`tail_batch=1`: every window gets a tail and a launch of its own): the summation order of the reference loop, which L
+    single-grid runs added together afterwards, `(sum_w a_w) + (sum_w b_w)`, do not have -- and one dense `Out_2` instead of L. With
+    one leg the result is `apply_windows_device(stack_on_device=True)` bit for bit.
 
     `window_parallel`: `(rank, world)` or a process group, as in `apply_windows_device`: rank r runs all legs of the windows
     `window_blocks(len(times), world)[r]` into a zero-initialised full-size `Out_2`; the tuple form returns that partial and the rank's
@@ -693,66 +738,13 @@ def apply_windows_legs(legs, picks, x_query_cart, locs_cart, max_t, tsteps_abs=N
         raise ValueError("apply_windows_legs: locs_cart has %d stations, the picks %d" % (np.asarray(locs_cart).shape[0], picks.n_sta))
     if len(picks) == 0:
         raise ValueError("apply_windows_legs: no pick of the model's stations")
-    max_t = float(max_t)
-    dt_embed = _dt_embed(kernel_sig_t, dt_embed)
-    tsteps_abs, times, offsets, n_overlap = _day_schedule(picks.t_host.reshape(-1, 1), max_t, day_len, t_win, step_size, min_required_picks,
-                                                          tsteps_abs, times)
-    drop_last = step_size == "half"
-    lo = np.searchsorted(picks.t_host, times - 2.0 * kernel_sig_t, side="right")                  # strict >, process_utils.py:476
-    hi = np.searchsorted(picks.t_host, times + max_t + 2.0 * kernel_sig_t, side="left")           # strict <
-    nonempty = hi > lo                                                                             # process_continuous_days.py:792-793
-    times, lo, hi = times[nonempty], lo[nonempty], hi[nonempty]
-    asc = is_ascending(tsteps_abs)
-    all_times, info = times, None
-    if return_info:
-        rank, world = (wp.rank, wp.world) if wp is not None else (0, 1)
-        info = dict(window_parallel_info(window_cols_table(tsteps_abs, times, offsets, drop_last, asc), len(tsteps_abs), world), rank=rank)
-    if wp is not None:
-        b_lo, b_hi = window_blocks(len(times), wp.world)[wp.rank]
-        times, lo, hi = times[b_lo:b_hi], lo[b_lo:b_hi], hi[b_lo:b_hi]
-    h_cols = window_cols_table(tsteps_abs, times, offsets, drop_last, asc)
-    scale = float(np.float32(1.0) / np.float32(n_overlap * len(legs)))     # `tensor / host scalar` in torch: times the fp32 reciprocal
-    with torch.no_grad(), torch.cuda.device(dev):
-        for leg in legs:
-            leg.net.window_batch = tail_batch
-        d_cols = torch.from_numpy(h_cols).to(dev)
-        xq = torch.as_tensor(x_query_cart).float().to(dev)
-        tq = torch.from_numpy(offsets.reshape(-1, 1)).float().to(dev)
-        Out_2 = torch.zeros((xq.shape[0], len(tsteps_abs)), dtype=torch.float32, device=dev)
-        main = torch.cuda.current_stream(dev)
-        stacker = torch.cuda.Stream(device=dev)      # every flush's stack runs here, so each one is behind the one before it
-        stacker.wait_stream(main)                    # Out_2's zeros and the table
-        first = 0
-        for w, t0 in enumerate(times):
-            a, b = int(lo[w]), int(hi[w])
-            for leg in legs:
-                Slice, Mask = leg.net.embed_window(picks.t[a:b], picks.sta[a:b], picks.phase[a:b], float(t0), max_t, kernel_sig_t, dt_embed,
-                                                   leg.trv, presplit=True)
-                pending = leg.net.push_window(Slice, Mask)
-            if pending != tail_batch and w != len(times) - 1:
-                continue
-            xs = []
-            for leg in legs:                          # every leg's tail + read-outs of the pushed windows, each on a side stream of its own
-                x, done = leg.net.flush_windows(leg.x_grid_cart, xq, tq)[1:]
-                stacker.wait_event(done)
-                x.record_stream(stacker)
-                xs.append(x)
-            used = h_cols[first:w + 1]
-            used = used[used >= 0]
-            if used.size:
-                with torch.cuda.stream(stacker):      # one launch for all legs
-                    engine.stack_windows_legs(Out_2, xs, d_cols[first:w + 1], scale, int(used.min()), int(used.max()))
-            first = w + 1
-        for leg in legs:
-            leg.net._hip.wait_tails()
-        main.wait_stream(stacker)
-    main.synchronize()                                # the verdicts of the day's last windows: one wait per day
+    plan = _day_plan(picks.t_host, float(max_t), day_len, t_win, step_size, min_required_picks, tsteps_abs, times, kernel_sig_t, len(legs), wp,
+                     return_info)
     for leg in legs:
-        _check_verdicts(leg.net)
-    if wp is not None and wp.collective:
-        _merge_partials(Out_2, wp.group, merge_timeout)
-        times = all_times
-    return (Out_2, times, info) if return_info else (Out_2, times)
+        leg.net.window_batch = tail_batch
+    xq = torch.as_tensor(x_query_cart).float().to(dev)
+    Out_2 = torch.zeros((xq.shape[0], len(plan.tsteps_abs)), dtype=torch.float32, device=dev)
+    return _run_day(plan, legs, picks, xq, Out_2, _fused_add(plan, Out_2), _dt_embed(kernel_sig_t, dt_embed), merge_timeout)
 
 
 def _inside_region(X, ranges):

@@ -4054,47 +4054,47 @@ int genie_local_marching(const double* xs, const double* t, const float* val, co
     return GENIE_OK;
 }
 
-int genie_stack_windows(const float* x, const int32_t* cols, int n_windows, int64_t n_query, int n_offsets, float scale, float* out,
-                        int64_t n_cols, int64_t c_min, int64_t c_max, void* stream) {
+namespace {
+// The one launch of k_stack_windows, for the entry `name` (in messages): `legs` holds n_legs >= 1 read-out pointers.
+int stack_windows_launch(const char* name, const SwLegs& legs, int n_legs, const int32_t* cols, int n_windows, int64_t n_query, int n_offsets,
+                         float scale, float* out, int64_t n_cols, int64_t c_min, int64_t c_max, void* stream) {
     if (n_windows < 1 || n_windows > SW_MAX_B || n_offsets < 1 || n_offsets > SW_MAX_T)
-        return fail(GENIE_ERR_ARG, "genie_stack_windows: 1 <= n_windows <= 16 and 1 <= n_offsets <= 64 required");
+        return fail(GENIE_ERR_ARG, std::string(name) + ": 1 <= n_windows <= 16 and 1 <= n_offsets <= 64 required");
     if (n_query < 0 || n_cols < 1 || n_cols >= (1ll << 31) || c_min < 0 || c_max < c_min || c_max >= n_cols)
-        return fail(GENIE_ERR_ARG, "genie_stack_windows: n_query >= 0, 1 <= n_cols < 2^31 and 0 <= c_min <= c_max < n_cols required");
-    if (!cols || (n_query > 0 && (!x || !out))) return fail(GENIE_ERR_ARG, "genie_stack_windows: null argument");
+        return fail(GENIE_ERR_ARG, std::string(name) + ": n_query >= 0, 1 <= n_cols < 2^31 and 0 <= c_min <= c_max < n_cols required");
+    if (!cols || (n_query > 0 && (!legs.x[0] || !out))) return fail(GENIE_ERR_ARG, std::string(name) + ": null argument");
     if (n_query == 0) return GENIE_OK;
     const int64_t width = c_max - c_min + 1;
     const int64_t nb = (n_query * width + 255) / 256;                      // (n_query * width < 2^63: width < 2^31, n_query checked below)
-    if (n_query >= (1ll << 31) || nb >= (1ll << 31)) return fail(GENIE_ERR_ARG, "genie_stack_windows: n_query x (c_max - c_min + 1) too large for one launch");
-    k_stack_windows<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(x, cols, n_windows, (long long)n_query, n_offsets, scale, out, (long long)n_cols,
-                                                                  (int)c_min, (int)width);
+    if (n_query >= (1ll << 31) || nb >= (1ll << 31)) return fail(GENIE_ERR_ARG, std::string(name) + ": n_query x (c_max - c_min + 1) too large for one launch");
+    k_stack_windows<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(legs, n_legs, cols, n_windows, (long long)n_query, n_offsets, scale, out,
+                                                                  (long long)n_cols, (int)c_min, (int)width);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
+}
+}  // namespace
+
+int genie_stack_windows(const float* x, const int32_t* cols, int n_windows, int64_t n_query, int n_offsets, float scale, float* out,
+                        int64_t n_cols, int64_t c_min, int64_t c_max, void* stream) {
+    SwLegs legs;
+    memset(&legs, 0, sizeof(legs));
+    legs.x[0] = x;                                                         // the one-leg case (null passes only with n_query == 0)
+    return stack_windows_launch("genie_stack_windows", legs, 1, cols, n_windows, n_query, n_offsets, scale, out, n_cols, c_min, c_max, stream);
 }
 
 int genie_stack_windows_legs(const float* const* x_legs, int n_legs, const int32_t* cols, int n_windows, int64_t n_query, int n_offsets,
                              float scale, float* out, int64_t n_cols, int64_t c_min, int64_t c_max, void* stream) {
     static_assert(SW_MAX_LEGS == RS_MAX_LEGS, "one leg limit for the day's passes");
     if (n_legs < 1 || n_legs > SW_MAX_LEGS) return fail(GENIE_ERR_ARG, "genie_stack_windows_legs: 1 <= n_legs <= 32 required");
-    if (n_windows < 1 || n_windows > SW_MAX_B || n_offsets < 1 || n_offsets > SW_MAX_T)
-        return fail(GENIE_ERR_ARG, "genie_stack_windows_legs: 1 <= n_windows <= 16 and 1 <= n_offsets <= 64 required");
-    if (n_query < 0 || n_cols < 1 || n_cols >= (1ll << 31) || c_min < 0 || c_max < c_min || c_max >= n_cols)
-        return fail(GENIE_ERR_ARG, "genie_stack_windows_legs: n_query >= 0, 1 <= n_cols < 2^31 and 0 <= c_min <= c_max < n_cols required");
-    if (!x_legs || !cols || (n_query > 0 && !out)) return fail(GENIE_ERR_ARG, "genie_stack_windows_legs: null argument");
+    if (!x_legs) return fail(GENIE_ERR_ARG, "genie_stack_windows_legs: null argument");
     SwLegs legs;
     memset(&legs, 0, sizeof(legs));
-    for (int l = 0; l < n_legs; ++l) {
+    for (int l = 0; l < n_legs; ++l) {                                     // (whatever n_query is)
         if (!x_legs[l]) return fail(GENIE_ERR_ARG, "genie_stack_windows_legs: null read-out pointer");
         legs.x[l] = x_legs[l];
     }
-    if (n_query == 0) return GENIE_OK;
-    const int64_t width = c_max - c_min + 1;
-    const int64_t nb = (n_query * width + 255) / 256;                      // (n_query * width < 2^63: width < 2^31, n_query checked below)
-    if (n_query >= (1ll << 31) || nb >= (1ll << 31))
-        return fail(GENIE_ERR_ARG, "genie_stack_windows_legs: n_query x (c_max - c_min + 1) too large for one launch");
-    k_stack_windows_legs<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(legs, n_legs, cols, n_windows, (long long)n_query, n_offsets, scale, out,
-                                                                       (long long)n_cols, (int)c_min, (int)width);
-    HIP_TRY(hipGetLastError());
-    return GENIE_OK;
+    return stack_windows_launch("genie_stack_windows_legs", legs, n_legs, cols, n_windows, n_query, n_offsets, scale, out, n_cols, c_min, c_max,
+                                stream);
 }
 
 size_t genie_refine_select_scratch_bytes(void) { return (size_t)RS_MAX_WG * sizeof(RsPartial); }

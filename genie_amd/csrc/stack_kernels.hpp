@@ -2,21 +2,30 @@
 // into Out_2 (process_continuous_days.py:797-805), one launch per flush.
 
 // ------------------------------------------------------------------------------------------------
-// Out_2[q, cols[k][j]] += x[k, q, j] * scale, for k = 0..B-1 and j = 0..T-1 IN THAT ORDER, entries cols[k][j] < 0 skipped.
+// Out_2[q, cols[k][j]] += x_l[k, q, j] * scale, for k = 0..B-1, then j = 0..T-1, then l = 0..L-1 INNERMOST, entries cols[k][j] < 0
+// skipped. x_l: the read-outs of the L source grids ("legs") of a day (process_continuous_days.py:761-810: `for n in times_need: for
+// x_grid_ind in x_grid_ind_list:`, every leg adding into the one Out_2); a single-grid loop is L = 1.
 // Windows of a flush overlap in columns (at 1 s stride a column is fed by 6-8 of them), so the work is split by OUTPUT element:
 // one thread owns one (q, c) of the flush's column range [c_min, c_min + width) and walks the B x T table (in LDS; every lane reads
-// the same entry: a broadcast) in (k, j) order. No atomics: the owner adds its contributions in window order, which is the order
-// of the torch loop this replaces (`Out_2.index_add_` per window), so the sums carry the same bits. Lanes are consecutive in c: the
-// read-modify-write of Out_2 and the reads of x[k, q, :] are contiguous runs. An entry outside the range matches no thread, so no
-// table content can make a thread write outside its own element. Contraction is off: the product is rounded before the add (v_mul_f32 +
-// v_add_f32, no v_fma_f32), as the two torch kernels round it.
+// the same entry: a broadcast) in (k, j) order. No atomics: the owner adds its contributions in window order. A table row that lists no
+// column twice (window_cols_table makes such rows) gives every output element at most one j per window, so the owner's order (k, l) is
+// the order of the torch loop this replaces, `for window: for leg: Out_2.index_add_(...)`, and the sums carry the same bits. Lanes are
+// consecutive in c: the read-modify-write of Out_2 and the reads of x_l[k, q, :] are contiguous runs. An entry outside the range matches
+// no thread, so no table content can make a thread write outside its own element, and an element no entry lists is not written at all.
+// Contraction is off: the product is rounded before the add (v_mul_f32 + v_add_f32, no v_fma_f32), as the two torch kernels round it.
+// The leg pointers travel by value in the kernel arguments, as k_refine_select_partial takes them: the loop over l indexes the
+// kernel-argument segment (scalar loads), no private copy of the table exists and nothing is copied to the device before the launch.
 // ------------------------------------------------------------------------------------------------
 constexpr int SW_MAX_B = 16;
 constexpr int SW_MAX_T = 64;
+constexpr int SW_MAX_LEGS = 32;
 
-__global__ __launch_bounds__(256) void k_stack_windows(const float* __restrict__ x, const int32_t* __restrict__ cols, int B, long long Q,
-                                                       int T, float scale, float* __restrict__ out, long long n_cols, int c_min,
-                                                       int width) {
+struct SwLegs {
+    const float* x[SW_MAX_LEGS];
+};
+
+__global__ __launch_bounds__(256) void k_stack_windows(SwLegs legs, int L, const int32_t* __restrict__ cols, int B, long long Q, int T,
+                                                       float scale, float* __restrict__ out, long long n_cols, int c_min, int width) {
 #pragma clang fp contract(off)
     __shared__ int32_t s_cols[SW_MAX_B * SW_MAX_T];
     for (int i = threadIdx.x; i < B * T; i += 256) s_cols[i] = cols[i];
@@ -26,48 +35,6 @@ __global__ __launch_bounds__(256) void k_stack_windows(const float* __restrict__
     const long long q = i / width;
     const int c = c_min + (int)(i - q * width);
     float* o = out + q * n_cols + c;                 // 64-bit element offset: a day is 10 000 x 115 200 > 2^31 elements
-    float acc = *o;
-    bool hit = false;
-    for (int k = 0; k < B; ++k) {
-        const float* xk = x + ((long long)k * Q + q) * T;
-        for (int j = 0; j < T; ++j) {
-            if (s_cols[k * T + j] == c) {
-                const float v = xk[j] * scale;
-                acc = acc + v;
-                hit = true;
-            }
-        }
-    }
-    if (hit) *o = acc;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The same stacking over the L source grids ("legs") of a day (process_continuous_days.py:761-810: `for n in times_need: for x_grid_ind
-// in x_grid_ind_list:`, every leg adding into the one Out_2):
-//   Out_2[q, cols[k][j]] += x_l[k, q, j] * scale, for k, then j, then l = 0..L-1 INNERMOST, entries cols[k][j] < 0 skipped.
-// A table row that lists no column twice (window_cols_table makes such rows) gives every output element at most one j per window, so
-// the owner's order (k, l) is the reference's `for window: for leg: Out_2[:, cols] += x / d`. Work split, LDS table, 64-bit offsets,
-// rounding (contraction off) and the untouched-element rule are the sibling's; L = 1 is the sibling bit for bit. The leg pointers
-// travel by value in the kernel arguments, as k_refine_select_partial takes them: the loop over l indexes the kernel-argument segment
-// (scalar loads), no private copy of the table exists and nothing is copied to the device before the launch.
-// ------------------------------------------------------------------------------------------------
-constexpr int SW_MAX_LEGS = 32;
-
-struct SwLegs {
-    const float* x[SW_MAX_LEGS];
-};
-
-__global__ __launch_bounds__(256) void k_stack_windows_legs(SwLegs legs, int L, const int32_t* __restrict__ cols, int B, long long Q, int T,
-                                                            float scale, float* __restrict__ out, long long n_cols, int c_min, int width) {
-#pragma clang fp contract(off)
-    __shared__ int32_t s_cols[SW_MAX_B * SW_MAX_T];
-    for (int i = threadIdx.x; i < B * T; i += 256) s_cols[i] = cols[i];
-    __syncthreads();
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= Q * width) return;
-    const long long q = i / width;
-    const int c = c_min + (int)(i - q * width);
-    float* o = out + q * n_cols + c;                 // 64-bit element offset, as in k_stack_windows
     float acc = *o;
     bool hit = false;
     for (int k = 0; k < B; ++k) {

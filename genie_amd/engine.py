@@ -51,28 +51,39 @@ def knn_device(x_context, x_query, k, exclude_self=False):
     return out
 
 
+STACK_MAX_LEGS = 32       # leg pointers of one genie_stack_windows_legs launch (= postproc.REFINE_SELECT_MAX_LEGS: one limit for a day's legs)
+
+
+def _stack_args(name, out, xs, cols, scale, c_min, c_max):
+    """The checks of `stack_windows` (`xs` = [x]) and `stack_windows_legs` (`name`: the one the caller used, in messages) -> (the
+    read-outs as contiguous fp32, the arguments both C entries take after theirs)."""
+    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.is_contiguous()):
+        raise ValueError("%s: out must be a contiguous fp32 GPU tensor [n_query, n_cols]" % name)
+    if not (torch.is_tensor(cols) and cols.is_cuda and cols.dtype == torch.int32 and cols.dim() == 2 and cols.is_contiguous()):
+        raise ValueError("%s: cols must be a contiguous int32 GPU tensor [n_windows, n_offsets]" % name)
+    if not 1 <= len(xs) <= STACK_MAX_LEGS:
+        raise ValueError("%s: 1 to %d legs per call, got %d" % (name, STACK_MAX_LEGS, len(xs)))
+    B, T = int(cols.shape[0]), int(cols.shape[1])
+    Q = int(out.shape[0])
+    xs = [_f32(x, "x") for x in xs]
+    for x in xs:
+        if x.device != out.device:
+            raise ValueError("%s: x lives on %s, out on %s" % (name, x.device, out.device))
+        if x.numel() != B * Q * T or tuple(x.shape[:3]) not in ((B, Q, T), (Q, T, 1), (Q, T)):
+            raise ValueError("%s: x %s does not match cols %s and out %s" % (name, tuple(x.shape), tuple(cols.shape), tuple(out.shape)))
+    return xs, (_ptr(cols), B, Q, T, float(scale), _ptr(out), int(out.shape[1]), int(c_min), int(c_max))
+
+
 def stack_windows(out, x, cols, scale, c_min, c_max):
     """`out[q, cols[k, j]] += x[k, q, j] * scale` for k, then j, in order, entries `cols < 0` skipped (genie_stack_windows: one launch
     on the current stream, no atomics, the bits of the per-window `index_add_` loop). out fp32 [Q, n_cols]; x fp32 [B, Q, T] or
     [B, Q, T, 1] (B <= 16; a single window's [Q, T(, 1)] is B = 1); cols int32 [B, T] on the device; `[c_min, c_max]` contains every
-    column listed."""
+    column listed. The one-leg case of `stack_windows_legs`."""
     lib = _lib.load()
-    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.is_contiguous()):
-        raise ValueError("stack_windows: out must be a contiguous fp32 GPU tensor [n_query, n_cols]")
-    if not (torch.is_tensor(cols) and cols.is_cuda and cols.dtype == torch.int32 and cols.dim() == 2 and cols.is_contiguous()):
-        raise ValueError("stack_windows: cols must be a contiguous int32 GPU tensor [n_windows, n_offsets]")
-    B, T = int(cols.shape[0]), int(cols.shape[1])
-    Q = int(out.shape[0])
-    x = _f32(x, "x")
-    if x.numel() != B * Q * T or tuple(x.shape[:3]) not in ((B, Q, T), (Q, T, 1), (Q, T)):
-        raise ValueError("stack_windows: x %s does not match cols %s and out %s" % (tuple(x.shape), tuple(cols.shape), tuple(out.shape)))
+    (x,), args = _stack_args("stack_windows", out, [x], cols, scale, c_min, c_max)
     with torch.cuda.device(out.device):
-        _lib.check(lib.genie_stack_windows(_ptr(x), _ptr(cols), B, Q, T, float(scale), _ptr(out), int(out.shape[1]), int(c_min), int(c_max),
-                                           _stream()), "genie_stack_windows")
+        _lib.check(lib.genie_stack_windows(_ptr(x), *args, _stream()), "genie_stack_windows")
     return out
-
-
-STACK_MAX_LEGS = 32       # leg pointers of one genie_stack_windows_legs launch (= postproc.REFINE_SELECT_MAX_LEGS: one limit for a day's legs)
 
 
 def stack_windows_legs(out, xs, cols, scale, c_min, c_max):
@@ -82,27 +93,12 @@ def stack_windows_legs(out, xs, cols, scale, c_min, c_max):
     column twice adds twice, in (k, j, l) order. `xs`: 1..STACK_MAX_LEGS tensors, each as `stack_windows` takes `x`, on `out`'s device;
     their storage is read in place (keep them alive, and known to the launch's stream, until it has run)."""
     lib = _lib.load()
-    if not (torch.is_tensor(out) and out.is_cuda and out.dtype == torch.float32 and out.dim() == 2 and out.is_contiguous()):
-        raise ValueError("stack_windows_legs: out must be a contiguous fp32 GPU tensor [n_query, n_cols]")
-    if not (torch.is_tensor(cols) and cols.is_cuda and cols.dtype == torch.int32 and cols.dim() == 2 and cols.is_contiguous()):
-        raise ValueError("stack_windows_legs: cols must be a contiguous int32 GPU tensor [n_windows, n_offsets]")
-    xs = list(xs)
-    if not 1 <= len(xs) <= STACK_MAX_LEGS:
-        raise ValueError("stack_windows_legs: 1 to %d legs per call, got %d" % (STACK_MAX_LEGS, len(xs)))
-    B, T = int(cols.shape[0]), int(cols.shape[1])
-    Q = int(out.shape[0])
-    xs = [_f32(x, "x") for x in xs]
-    for x in xs:
-        if x.device != out.device:
-            raise ValueError("stack_windows_legs: x lives on %s, out on %s" % (x.device, out.device))
-        if x.numel() != B * Q * T or tuple(x.shape[:3]) not in ((B, Q, T), (Q, T, 1), (Q, T)):
-            raise ValueError("stack_windows_legs: x %s does not match cols %s and out %s" % (tuple(x.shape), tuple(cols.shape), tuple(out.shape)))
-    if Q == 0:
+    xs, args = _stack_args("stack_windows_legs", out, list(xs), cols, scale, c_min, c_max)
+    if out.shape[0] == 0:              # (an empty read-out has no address, and the entry takes no null pointer)
         return out
     ptrs = (ctypes.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
     with torch.cuda.device(out.device):
-        _lib.check(lib.genie_stack_windows_legs(ptrs, len(xs), _ptr(cols), B, Q, T, float(scale), _ptr(out), int(out.shape[1]), int(c_min),
-                                                int(c_max), _stream()), "genie_stack_windows_legs")
+        _lib.check(lib.genie_stack_windows_legs(ptrs, len(xs), *args, _stream()), "genie_stack_windows_legs")
     return out
 
 

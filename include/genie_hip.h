@@ -581,7 +581,8 @@ int genie_local_marching(const double* xs, const double* t, const float* val, co
  * 1 <= n_offsets <= 64, 1 <= n_cols < 2^31. No atomics: one thread owns one (q, c) and adds its contributions in (k, j) order, the product
  * rounded to fp32 before the add, so the result is reproducible and carries the bits of `out.index_add_(1, cols_k, x_k * scale)` issued
  * window by window. `scale`: the caller's fp32 factor (torch divides a tensor by a host scalar d as `x * (1.0f / (float)d)`; pass that
- * reciprocal to match it). Bad arguments return GENIE_ERR_ARG before any launch. */
+ * reciprocal to match it). This is genie_stack_windows_legs with the one leg x: the same kernel and the same launch. A null x or out
+ * passes only with n_query == 0. Bad arguments return GENIE_ERR_ARG before any launch. */
 int genie_stack_windows(const float* x, const int32_t* cols, int n_windows, int64_t n_query, int n_offsets, float scale, float* out,
                         int64_t n_cols, int64_t c_min, int64_t c_max, void* stream);
 
@@ -593,9 +594,10 @@ int genie_stack_windows(const float* x, const int32_t* cols, int n_windows, int6
  * so the order is exactly `for window: for leg: out.index_add_(1, cols_k, x_l[k] * scale)`; a row that does list a column twice adds
  * twice, in (k, j, l) order. x_legs: HOST array of n_legs device pointers, each to fp32 [n_windows, n_query, n_offsets] (64-bit element
  * offsets); the pointers travel in the kernel arguments, so the call copies nothing and never waits. 1 <= n_legs <= 32; cols, out,
- * [c_min, c_max], scale and the ranges of n_windows, n_offsets, n_cols as in genie_stack_windows, to which n_legs = 1 is equal bit for
- * bit. No atomics, the product rounded before the add; an element no entry lists is not written. Bad arguments (a null table, a null
- * pointer in it, n_legs outside 1..32, any range error of genie_stack_windows) return GENIE_ERR_ARG before any launch. */
+ * [c_min, c_max], scale and the ranges of n_windows, n_offsets, n_cols as in genie_stack_windows, which is the n_legs = 1 case of this
+ * entry (one kernel serves both). No atomics, the product rounded before the add; an element no entry lists is not written. Bad
+ * arguments (a null table, a null pointer in it, n_legs outside 1..32, any range error of genie_stack_windows) return GENIE_ERR_ARG
+ * before any launch; n_legs and the pointer table are checked first, then the ranges, then cols and out. */
 int genie_stack_windows_legs(const float* const* x_legs, int n_legs, const int32_t* cols, int n_windows, int64_t n_query, int n_offsets,
                              float scale, float* out, int64_t n_cols, int64_t c_min, int64_t c_max, void* stream);
 

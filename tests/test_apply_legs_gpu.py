@@ -3,7 +3,7 @@ several source grids (`apply.apply_windows_legs`).
 
 * the kernel alone, on random tensors: bit-equal to `for window: for leg: out.index_add_(...)`, to its one-leg sibling, untouched elements
   keep their bits, a column listed twice adds twice in (k, j, l) order, 64-bit offsets, bad arguments;
-* the loop: one leg == `apply_windows_device(stack_on_device=True)`; two and three legs (and a `use_subgraph` leg) == the reference loop
+* the loop: one leg == `apply_windows_device(stack_on_device=True)`, and both == the reference loop; two and three legs (and a `use_subgraph` leg) == the reference loop
   written here from public calls, window-major, and NOT the leg-major sum a caller had to form before; refusals; window-parallel in
   the tuple form (every rank in this process) and the group form (one process per rank).
 
@@ -336,6 +336,23 @@ def test_one_leg_is_the_single_grid_loop(step_size, tail_batch):
     got, times_l = _legs_run(("a",), **kw)
     assert len(times) >= (17 if step_size != "full" else 6) and np.array_equal(times, times_l)
     assert float(want.abs().max()) > 0 and torch.equal(got, want)
+
+
+@pytest.mark.parametrize("step_size", ["full", "partial", "half"])
+def test_both_entries_with_one_grid_are_the_reference_loop(step_size):
+    """The two entries share one loop, so comparing them with each other pins neither: each is held here against the reference loop
+    written from public calls (embed, the literal `forward_fixed_source`, `index_add_`), the single-grid entry on its torch arm and on
+    its fused arm, at three flush sizes."""
+    s = _setup()
+    want, _, times = _reference(("a",), step_size)
+    single = lambda **kw: apply.apply_windows_device(s.legs["a"].net, s.g64, s.P, s.trv, max_t=s.max_t, step_size=step_size, **dict(s.kw, **kw))
+    runs = [single(stack_on_device=False, tail_batch=3), single(stack_on_device=True, tail_batch=16),
+            _legs_run(("a",), step_size=step_size, tail_batch=1)]
+    torch.cuda.synchronize()
+    assert len(times) >= (17 if step_size != "full" else 6) and int((want != 0).sum()) > 100
+    for got, times_used in runs:
+        assert np.array_equal(times, times_used)
+        assert torch.equal(got, want)
 
 
 @pytest.mark.parametrize("names", [("a", "b"), ("a", "b", "a2")])
