@@ -116,6 +116,8 @@ SYMBOLS = [
     ("genie_time_groups", _c.c_int, [_P, _c.c_int64, _c.c_double, _P, _P, _P]),
     ("genie_local_marching_scratch_bytes", _c.c_size_t, [_c.c_int64]),
     ("genie_local_marching", _c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_double, _c.c_double, _c.c_int, _c.c_double, _c.c_int, _P, _P, _P]),
+    ("genie_time_pointers_scratch_bytes", _c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
+    ("genie_time_pointers", _c.c_int, [_P, _c.c_int64, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _P, _P]),
     ("genie_stack_windows", _c.c_int, [_P, _P, _c.c_int, _c.c_int64, _c.c_int, _c.c_float, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P]),
     ("genie_stack_windows_legs", _c.c_int, [_P, _c.c_int, _P, _c.c_int, _c.c_int64, _c.c_int, _c.c_float, _P, _c.c_int64, _c.c_int64, _c.c_int64,
                                             _P]),

@@ -1250,6 +1250,7 @@ __device__ __forceinline__ void gather_sum16(const float* __restrict__ base, lon
 #include "select_kernels.hpp"
 #include "cloud_kernels.hpp"
 #include "optim_kernels.hpp"
+#include "pointer_kernels.hpp"
 
 }  // namespace
 
@@ -4050,6 +4051,52 @@ int genie_local_marching(const double* xs, const double* t, const float* val, co
         cur = out;
     }
     k_local_marching_keep<<<nb, 256, 0, st>>>(val, cur, active, (long long)n, (float)tol, keep);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+namespace {
+// the argument checks genie_time_pointers and its scratch size share
+const char* tp_size_error(int64_t n_prod, int n_sta, int n_t) {
+    if (n_prod < 1 || n_prod >= (1ll << 31)) return "1 <= n_prod < 2^31 required";
+    if (n_sta < 1 || n_sta > n_prod) return "1 <= n_sta <= n_prod required";
+    if (n_t < 2 || n_t > (1 << 24)) return "2 <= n_t <= 2^24 required";
+    if ((int64_t)n_sta * ((n_t + TP_WAVES - 1) / TP_WAVES) >= (1ll << 31)) return "n_sta x n_t too large for one launch";
+    return nullptr;
+}
+}  // namespace
+
+size_t genie_time_pointers_scratch_bytes(int64_t n_prod, int n_sta, int n_t) {
+    return tp_size_error(n_prod, n_sta, n_t) ? 0 : tp_layout(n_prod, n_sta, n_t).total;
+}
+
+int genie_time_pointers(const float* trv, int64_t n_prod, int n_sta, const int32_t* sta_of_prod, const double* dt_partition, int n_t, int k,
+                        void* scratch, int32_t* edges_p, int32_t* edges_s, int32_t* status, void* stream) {
+    if (k < 1 || k > TP_MAX_K) return fail(GENIE_ERR_ARG, "genie_time_pointers: 1 <= k <= 32 required");
+    if (const char* why = tp_size_error(n_prod, n_sta, n_t)) return fail(GENIE_ERR_ARG, std::string("genie_time_pointers: ") + why);
+    if (!sta_of_prod && n_prod % n_sta != 0) return fail(GENIE_ERR_ARG, "genie_time_pointers: n_prod is not a multiple of n_sta (Cartesian form)");
+    if (!trv || !dt_partition || !scratch || !edges_p || !edges_s || !status) return fail(GENIE_ERR_ARG, "genie_time_pointers: null argument");
+    if ((((uintptr_t)scratch) & 15) != 0) return fail(GENIE_ERR_ARG, "genie_time_pointers: scratch must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const TpLayout L = tp_layout(n_prod, n_sta, n_t);
+    char* base = (char*)scratch;
+    unsigned long long* sorted = (unsigned long long*)(base + L.sorted);
+    int32_t* cnt = (int32_t*)(base + L.cnt);
+    int32_t* start = (int32_t*)(base + L.start);
+    int32_t* seg = (int32_t*)(base + L.seg);
+    int32_t* ncand = (int32_t*)(base + L.ncand);
+    const long long P = (long long)n_prod, G = sta_of_prod ? 0 : P / n_sta;
+    const int32_t* seg_arg = sta_of_prod ? seg : nullptr;      // (Cartesian: station i's candidates start at i * G)
+    HIP_TRY(hipMemsetAsync(cnt, 0, L.start - L.cnt, st));
+    HIP_TRY(hipMemsetAsync(ncand, 0, L.total - L.ncand, st));
+    HIP_TRY(hipMemsetAsync(status, 0, 2 * sizeof(int32_t), st));
+    const unsigned nb = (unsigned)std::min<long long>((2 * P + TP_BLOCK - 1) / TP_BLOCK, (long long)TP_MAX_WG);
+    k_tp_bins<false><<<nb, TP_BLOCK, 0, st>>>(trv, sta_of_prod, P, n_sta, G, dt_partition, n_t, cnt, seg_arg, sorted, status);
+    k_tp_scan<<<2u * (unsigned)n_sta, TP_BLOCK, 0, st>>>(cnt, start, n_sta, n_t, ncand);
+    k_tp_segments<<<1, TP_BLOCK, 0, st>>>(ncand, n_sta, seg, status);
+    k_tp_bins<true><<<nb, TP_BLOCK, 0, st>>>(trv, sta_of_prod, P, n_sta, G, dt_partition, n_t, cnt, seg_arg, sorted, status);
+    const dim3 grid((unsigned)n_sta * (unsigned)((n_t + TP_WAVES - 1) / TP_WAVES), 2);
+    k_tp_select<<<grid, TP_BLOCK, 0, st>>>(sorted, start, seg_arg, P, G, n_sta, dt_partition, n_t, k, edges_p, edges_s);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }

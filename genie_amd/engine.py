@@ -172,6 +172,105 @@ def subgraph_csr_device(pairs, n_grid, sta_csr, src_csr):
     return {"n_prod": n, "sta_csr": (rp[0], col1[:int(rp[0][-1])]), "src_csr": (rp[1], col2[:int(rp[1][-1])]), "seg_rowptr": seg}
 
 
+TIME_POINTERS_MAX_K = 32       # ranks genie_time_pointers keeps per (station, time step); its only size limit besides P < 2^31
+
+
+def tlatent_rows(tlatent, device, pairs=None):
+    """Travel times as the association heads take them: fp32 rows [P, 2] in product-node order on `device`. `tlatent` is that already
+    ([P, 2]; numpy or tensor), or the [G, S, 2] array `graph.time_pointers` takes: flattened for the Cartesian product (p = g * S + i),
+    gathered at (source, station) of `pairs` [2, N] for an irregular product graph."""
+    t = tlatent if torch.is_tensor(tlatent) else torch.from_numpy(np.ascontiguousarray(tlatent))
+    t = t.detach().to(device)
+    if t.dim() == 3:
+        if pairs is None:
+            t = t.reshape(t.shape[0] * t.shape[1], t.shape[2])
+        else:
+            idx = torch.as_tensor(pairs).to(device).long()
+            t = t[idx[1], idx[0]]
+    if t.dim() != 2 or t.shape[1] != 2:
+        raise ValueError("tlatent must be [P, 2] (product-node order) or [G, S, 2], got %s" % (tuple(t.shape),))
+    return t.to(torch.float32).contiguous()
+
+
+def time_pointers_device(tlatent, n_sta, max_t=None, dt=1.0, k=10, win=10.0, pairs=None, device=None):
+    """`graph.time_pointers` on the device (genie_time_pointers): the association heads' time-pointer tables
+    (`assemble_time_pointers_for_stations`, utils.py:602-622) without the host loop over stations and phases.
+
+    For every station i and every time step t of `dt_partition = np.arange(-win, win + max_t + dt, dt)` the k candidates of station i
+    smallest under the key (|float64(trv) - t|, product-node id), nearest first -- one total order, so the tables are unique.
+      * Cartesian product (`pairs=None`): the candidates are the G product nodes g * n_sta + i and k = min(k, G). The tables equal
+        `graph.time_pointers` (hence the reference's) bit for bit, ties included.
+      * Irregular product graph: `pairs` [2, N] = (station, source) of the product nodes, grouped by source node as `A_src_in_sta` is;
+        the candidates of station i are the product nodes listing it, and rank j of a station with n_i < k candidates is rank j mod n_i.
+        This rule is this package's own (the reference has no fixture for irregular tables). A station without a product node is a
+        ValueError: host-resident `pairs` are checked before anything is uploaded, device-resident ones by a device count read back once.
+    tlatent: fp32 [P, 2] rows in product-node order (`set_adjacencies`' tlatent), or the [G, S, 2] array the host function takes; on the
+    host or the device. Precondition: every travel time is finite (an inf / NaN entry is never listed; with device-resident `pairs` it
+    raises with the same read-back). `max_t=None` takes the largest travel time on the device (one read-back).
+    Returns (A_edges_p, A_edges_s, dt_partition): int32 device tensors [n_sta * len(dt_partition) * k], laid out
+    [station][time step][k] as `forward_fixed` / genie_lslc_fwd take them, and the float64 numpy `dt_partition` -- computed on the host as
+    the host function computes it and copied up, so both builders rank against identical time steps."""
+    k, n_sta = int(k), int(n_sta)
+    if not 1 <= k <= TIME_POINTERS_MAX_K:
+        raise ValueError("time_pointers_device: 1 <= k <= %d required, got %d" % (TIME_POINTERS_MAX_K, k))
+    if n_sta < 1:
+        raise ValueError("time_pointers_device: n_sta >= 1 required")
+    if not float(dt) > 0.0:
+        raise ValueError("time_pointers_device: dt > 0 required")
+    sta_host = None
+    if pairs is not None:
+        pairs = torch.as_tensor(pairs)
+        if pairs.dim() != 2 or pairs.shape[0] != 2 or pairs.shape[1] < 1:
+            raise ValueError("time_pointers_device: pairs must be [2, N] (station, source) with N >= 1")
+        if not pairs.is_cuda:
+            sta_host = pairs[0].long()
+            if int(sta_host.min()) < 0 or int(sta_host.max()) >= n_sta:
+                raise ValueError("time_pointers_device: a station of pairs lies outside [0, n_sta)")
+            empty = int((torch.bincount(sta_host, minlength=n_sta) == 0).sum())
+            if empty:
+                raise ValueError("time_pointers_device: %d station(s) without a product node in pairs" % empty)
+    if device is None:
+        device = next((t.device for t in (tlatent, pairs) if torch.is_tensor(t) and t.is_cuda), None)
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    device = torch.device(device)
+    lib = _lib.load()
+    tl = tlatent_rows(tlatent, device, pairs)
+    P = int(tl.shape[0])
+    sta = None
+    if pairs is None:
+        if P < 1 or P % n_sta != 0:
+            raise ValueError("time_pointers_device: %d travel-time rows are not a multiple of n_sta = %d" % (P, n_sta))
+        k = min(k, P // n_sta)
+    else:
+        if int(pairs.shape[1]) != P:
+            raise ValueError("time_pointers_device: %d travel-time rows for %d product nodes" % (P, int(pairs.shape[1])))
+        sta = pairs[0].to(device).to(torch.int32).contiguous()
+    if max_t is None:
+        max_t = np.float32(tl.max().item())        # (the host function's `trv.max()`: an fp32 scalar)
+    dt_partition = np.arange(-win, win + max_t + dt, dt)
+    n_t = int(dt_partition.size)
+    if n_t < 2:
+        raise ValueError("time_pointers_device: dt_partition needs at least two time steps")
+    with torch.cuda.device(device):
+        nbytes = int(lib.genie_time_pointers_scratch_bytes(P, n_sta, n_t))
+        if nbytes == 0:
+            raise ValueError("time_pointers_device: sizes out of contract (P = %d < 2^31, n_sta = %d, %d time steps)" % (P, n_sta, n_t))
+        dtp = torch.from_numpy(dt_partition).to(device)
+        scratch = torch.empty(size_class(nbytes), dtype=torch.uint8, device=device)
+        status = torch.empty(2, dtype=torch.int32, device=device)
+        edges_p = torch.empty(n_sta * n_t * k, dtype=torch.int32, device=device)
+        edges_s = torch.empty(n_sta * n_t * k, dtype=torch.int32, device=device)
+        _lib.check(lib.genie_time_pointers(_ptr(tl), P, n_sta, _ptr(sta), _ptr(dtp), n_t, k, _ptr(scratch), _ptr(edges_p), _ptr(edges_s),
+                                           _ptr(status), _stream()), "genie_time_pointers")
+        if sta is not None and sta_host is None:
+            empty, bad = status.tolist()             # the one read-back
+            if empty:
+                raise ValueError("time_pointers_device: %d station(s) without a product node in pairs" % empty)
+            if bad:
+                raise ValueError("time_pointers_device: travel times must be finite")
+    return edges_p, edges_s, dt_partition
+
+
 def csr_from_edges(edge_index, n_target):
     """[2,E] edge list (row0 = j source, row1 = i target) -> (rowptr int32 [n+1], col int32 [E]);
     in-edges grouped by target in stable edge order."""

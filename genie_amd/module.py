@@ -760,7 +760,7 @@ class GCN_Detection_Network_extended(nn.Module):
 
     def set_adjacencies_subgraph_from_positions(self, pos_loc, pos_src, edge_attr=None, k_sta_edges=10, k_spc_edges=15,
                                                 max_deg_offset=5.0, k_nearest_pairs=30, scale_deg=110e3,
-                                                scale_pairwise_sta_in_src_distances=100e3):
+                                                scale_pairwise_sta_in_src_distances=100e3, tlatent=None, time_pointers=None):
         """`use_subgraph: True` set up entirely on the device: `extract_inputs_adjacencies_subgraph` (process_utils.py:744-849,
         its defaults) without the host loops. Base kNN graphs by `genie_knn` (:782-783), the product nodes = every source node
         paired with the stations within `scale_deg * max_deg_offset` and its `k_nearest_pairs` nearest stations (:775-794),
@@ -768,8 +768,14 @@ class GCN_Detection_Network_extended(nn.Module):
         pos_loc [S, 3] / pos_src [G, 3] Cartesian metres; edge_attr [N, 3] for the N product nodes, a callable
         `edge_attr(pairs) -> [N, 3]`, or None = `(pos_src[source] - pos_loc[station]) / scale_pairwise_sta_in_src_distances`
         (:811). Returns (A_sta_sta, A_src_src, A_src_in_sta) with A_src_in_sta int64 [2, N] = the product nodes as
-        (station, source) pairs in node order; Slice / Mask / edge_attr rows follow that order."""
+        (station, source) pairs in node order; Slice / Mask / edge_attr rows follow that order.
+        `tlatent` (travel times: [N, 2] rows in that order, the [G, S, 2] array, or a callable `tlatent(pairs) -> [N, 2]`) with
+        `time_pointers=dict(max_t=, dt=, k=, win=)` also builds the time-pointer tables of the 4-output `forward_fixed` on the device
+        (`engine.time_pointers_device`, irregular form: a station with fewer than k product nodes cycles through them) and leaves
+        A_edges_p / A_edges_s / dt_partition / tlatent on the model."""
         self._not_sharded("an irregular product graph (use_subgraph)")
+        if time_pointers is not None and tlatent is None:
+            raise ValueError("time_pointers= needs the travel times (tlatent=)")
         dev = next(self.parameters()).device
         pos_loc, pos_src = _engine._f32(pos_loc.to(dev), "pos_loc"), _engine._f32(pos_src.to(dev), "pos_src")
         n_sta, n_grid = int(pos_loc.shape[0]), int(pos_src.shape[0])
@@ -786,6 +792,11 @@ class GCN_Detection_Network_extended(nn.Module):
         new = _engine.HipPath(n_sta, n_grid, None, src_csr, grid_order=order, scale_rel=self.scale_rel, device=dev, subgraph=sub)
         self._install(new, edge_attr, pos_loc, pos_src, pairs=pairs)
         self.A_src = A_src
+        if tlatent is not None:
+            self.tlatent = _engine.tlatent_rows(tlatent(pairs) if callable(tlatent) else tlatent, dev, pairs)
+        if time_pointers is not None:
+            self.A_edges_p, self.A_edges_s, self.dt_partition = _engine.time_pointers_device(self.tlatent, n_sta, pairs=pairs, device=dev,
+                                                                                             **time_pointers)
         return A_sta, A_src, pairs
 
     def set_adjacencies_from_positions(self, pos_loc, pos_src, edge_attr, k_sta_edges=8, k_spc_edges=15):
@@ -805,15 +816,31 @@ class GCN_Detection_Network_extended(nn.Module):
         return A_sta, A_src
 
     def set_adjacencies_base(self, A_sta_sta, A_src_src, edge_attr, pos_loc, pos_src, A_edges_p=None, A_edges_s=None,
-                             dt_partition=None, tlatent=None):
+                             dt_partition=None, tlatent=None, time_pointers=None):
         """Same effect as `set_adjacencies` from the BASE graphs only (process_utils.py:718-719), for sizes
-        where the explicit product edge lists cannot be materialised (config 4: 2.3 G edges). The last four arguments are
-        `set_adjacencies`' time-pointer tables and travel times (module.py:941): needed by the 4-output `forward_fixed` only."""
+        where the explicit product edge lists cannot be materialised (config 4: 2.3 G edges). `A_edges_p`, `A_edges_s`, `dt_partition`
+        and `tlatent` are `set_adjacencies`' time-pointer tables and travel times (module.py:941): needed by the 4-output
+        `forward_fixed` only. `time_pointers=dict(max_t=, dt=, k=, win=)` builds the three tables from `tlatent` ([P, 2] rows or the
+        [G, S, 2] array) on the device instead (`engine.time_pointers_device`: the tables of `graph.time_pointers`, bit for bit) and
+        leaves them on the model as if they had been passed; passing tables as well is a ValueError."""
+        if time_pointers is not None:
+            if A_edges_p is not None or A_edges_s is not None or dt_partition is not None:
+                raise ValueError("set_adjacencies_base: pass the time-pointer tables (A_edges_p, A_edges_s, dt_partition) or time_pointers=, "
+                                 "not both")
+            if tlatent is None:
+                raise ValueError("time_pointers= needs the travel times (tlatent=)")
+            self._not_sharded("time_pointers= (the association heads' tables)")
         n_sta, n_grid = int(pos_loc.shape[0]), int(pos_src.shape[0])
         self.A_edges_p, self.A_edges_s, self.dt_partition, self.tlatent = A_edges_p, A_edges_s, dt_partition, tlatent
         self.A_src = torch.as_tensor(A_src_src)
         self._install(self._new_cartesian(_engine.csr_from_edges(A_sta_sta, n_sta), _engine.csr_from_edges(A_src_src, n_grid),
                                           n_sta, n_grid, pos_loc, pos_src), edge_attr, pos_loc, pos_src)
+        if time_pointers is not None:
+            dev = self._hip.device
+            self.tlatent = _engine.tlatent_rows(tlatent, dev)
+            if int(self.tlatent.shape[0]) != n_sta * n_grid:
+                raise ValueError("tlatent: expected %d rows (n_grid x n_sta), got %d" % (n_sta * n_grid, int(self.tlatent.shape[0])))
+            self.A_edges_p, self.A_edges_s, self.dt_partition = _engine.time_pointers_device(self.tlatent, n_sta, device=dev, **time_pointers)
 
     # ---- hot path ------------------------------------------------------------------------------
     def _path(self, Slice, Mask, x_temp_cuda_cart, want_x_latent=False, want_bip=False):

@@ -571,6 +571,33 @@ size_t genie_local_marching_scratch_bytes(int64_t n);
 int genie_local_marching(const double* xs, const double* t, const float* val, const int32_t* group, int64_t n, double tc_win,
                          double sp_win, int n_steps_max, double tol, int use_directed, void* scratch, uint8_t* keep, void* stream);
 
+/* The time-pointer tables of the association heads on the device (`assemble_time_pointers_for_stations`, utils.py:602-622, called at
+ * train_GENIE_model.py:1364 and process_continuous_days.py:620; genie_amd/graph.py::time_pointers is the host statement): for every
+ * station i and every time step t of dt_partition, the k candidates of station i that are smallest under the key
+ *   ( |(double)trv - t| , product-node id ),   nearest first, equal distances to the lower id,
+ * the subtraction and the absolute value in fp64 on the fp32 travel time widened exactly. The key is a total order, so the tables are
+ * unique: equal to the reference's stable argsort of |trv - t| over all source nodes, bit for bit, ties included.
+ *   trv [n_prod, 2] fp32: P / S travel time of every product node, in product-node order (`tlatent` of set_adjacencies); must be finite.
+ *   sta_of_prod NULL: the Cartesian product, node p = g * n_sta + i (n_prod a multiple of n_sta); the candidates of station i are its
+ *     G = n_prod / n_sta nodes. The caller passes k <= G (the reference clips k to G).
+ *   sta_of_prod [n_prod] int32: an irregular product graph (`use_subgraph`), the station of every product node; the candidates of station
+ *     i are the nodes listing it. A station with n < k candidates gets rank j filled with rank j mod n (this package's own rule: the
+ *     reference has no fixture for irregular tables); a station with none gets zeros and is counted in status[0].
+ *   dt_partition [n_t] fp64 on the device, ascending; 1 <= k <= 32.
+ *   edges_p / edges_s: int32 [n_sta * n_t * k] each, laid out [station][time step][k] (what LocalSliceLgCollapse indexes, module.py:635-637,
+ *     and genie_lslc_fwd takes), both written by the one call.
+ *   status [2] int32 on the device, written by the call: [0] = stations without a candidate, [1] = 1 when a travel time was inf / NaN
+ *     (such entries are never listed). Nothing is read back here; the caller reads status when it wants the verdict.
+ *   scratch: genie_time_pointers_scratch_bytes(n_prod, n_sta, n_t) bytes on the device, 16-byte aligned, contents irrelevant before and
+ *     after (16 bytes per product node plus the bin tables; 0 when the sizes are out of contract).
+ * Every size lives in global memory: no limit on the nodes of a station. The order in which candidates meet inside the call depends on
+ * scheduling, the tables do not: two calls write the same bits. Vector stores and vector atomics only. Bad arguments (k < 1, k > 32,
+ * n_t < 2, n_prod < 1 or >= 2^31, n_sta < 1, n_prod not a multiple of n_sta in the Cartesian form, n_sta x n_t beyond one launch, a null
+ * pointer, misaligned scratch) return GENIE_ERR_ARG before any launch. */
+size_t genie_time_pointers_scratch_bytes(int64_t n_prod, int n_sta, int n_t);
+int genie_time_pointers(const float* trv, int64_t n_prod, int n_sta, const int32_t* sta_of_prod, const double* dt_partition, int n_t, int k,
+                        void* scratch, int32_t* edges_p, int32_t* edges_s, int32_t* status, void* stream);
+
 /* Stacking of window read-outs into Out_2 (the apply loop's accumulation, process_continuous_days.py:797-805), one launch per flush:
  *   for k in 0..n_windows-1 (window order), for j in 0..n_offsets-1 (offset order):
  *       c = cols[k][j];  if c < 0: skip;   out[q, c] += x[k, q, j] * scale   for every query q
