@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "genie_hip.h"
+#include "s2u_plan.hpp"
 
 // read-once rows (c, Mask, edge_attr of stage 2): plain loads (non-temporal ones measured slower, 0.354 vs 0.326 ms)
 #define GENIE_LD_STREAM(ptr) (*(ptr))
@@ -1344,7 +1345,7 @@ struct genie_ctx {
                                         // (flag_input_range), 0 = none; read by genie_input_range without synchronising. Pinned, owned
     // k_stage2_h2u: blocks of adjacent source nodes with the union of their neighbour rows, per launched range [gi_begin, gi_end) of the
     // processing order (the whole grid; the sharded path's four static sub-ranges): built on first use from the host copy of src_tab
-    struct S2uTables { DevBuf<S2uBlock> blocks; DevBuf<int32_t> xcd0; int nblk; };
+    struct S2uTables { DevBuf<S2uBlock> blocks; DevBuf<int32_t> xcd0; int nblk, ngroups; };
     std::map<std::pair<int, int>, S2uTables> s2u;
     std::vector<int32_t> tab_host;
     DevBuf<float> packed_s2h;  // f16x2 weight image of k_stage2_h2u (Bipartite_ReadIn.fc1)
@@ -2604,61 +2605,21 @@ float* genie_ws_v_ptr(const genie_ctx* c, void* ws) {
 int genie_ws_v_pitch(const genie_ctx* c) { (void)c; return ROWW; }
 
 namespace {
-// k_stage2_h2u's tables for the range [gb0, ge0) of the processing order: per XCD chunk (the chunks of ItemIter), blocks of up to
-// S2U_NB consecutive source nodes whose neighbour rows (their union, in first-use order) fit S2U_UCAP rows; a block is cut short
-// where the union would grow past that. Built once per range and kept with the context.
+// k_stage2_h2u's tables for the range [gb0, ge0) of the processing order (s2u_plan.hpp: blocks per XCD chunk, groups of S2U_GROUP
+// blocks with their LDS slot maps; a range's groups start at its own chunk boundaries). Built once per range and kept with the context.
 int get_s2u_tables(genie_ctx* c, int gb0, int ge0, const genie_ctx::S2uTables** out) {
     const auto key = std::make_pair(gb0, ge0);
     auto itf = c->s2u.find(key);
     if (itf != c->s2u.end()) { *out = &itf->second; return GENIE_OK; }
-    const std::vector<int32_t>& tab = c->tab_host;
-    std::vector<S2uBlock> blks;
-    std::vector<int32_t> seen_blk((size_t)c->G_ext, -1), seen_at((size_t)c->G_ext, 0);
-    int32_t serial = 0;
-    int32_t x0[9];
-    const int nxc = 8, n = ge0 - gb0;
-    for (int x = 0; x < nxc; ++x) {
-        x0[x] = (int32_t)blks.size();
-        const int gb = gb0 + (int)((long long)n * x / nxc), ge = gb0 + (int)((long long)n * (x + 1) / nxc);
-        int pos = gb;
-        while (pos < ge) {
-            S2uBlock b;
-            memset(&b, 0, sizeof(b));
-            b.gi0 = pos;
-            // membership of a neighbour row in the block's union by a stamp per source node (`seen_blk[nb]` = serial of the block that
-            // listed it, `seen_at[nb]` = its position there): the table of 10 000 source nodes builds in ~0.2 ms, where a linear search
-            // of the union per neighbour took 2.5 ms of every context (re)build of a training sample
-            ++serial;
-            int32_t uni[S2U_UCAP + 15];
-            int nuni = 0;
-            while (pos < ge && b.n < S2U_NB) {
-                int32_t where[15];
-                const int before = nuni;
-                for (int k = 0; k < 15; ++k) {
-                    const int32_t nb = tab[(size_t)pos * 16 + 1 + k];
-                    if (seen_blk[(size_t)nb] != serial) { seen_blk[(size_t)nb] = serial; seen_at[(size_t)nb] = nuni; uni[nuni++] = nb; }
-                    where[k] = seen_at[(size_t)nb];
-                }
-                if (b.n > 0 && nuni > S2U_UCAP) {       // the node does not fit: take its additions back, it opens the next block
-                    for (int u = before; u < nuni; ++u) seen_blk[(size_t)uni[u]] = -1;
-                    nuni = before;
-                    break;
-                }
-                b.idx[b.n][0] = tab[(size_t)pos * 16];
-                for (int k = 0; k < 15; ++k) b.idx[b.n][1 + k] = where[k];
-                ++b.n; ++pos;
-            }
-            for (int e = b.n; e < S2U_NB; ++e) b.idx[e][0] = -1;       // empty slots of a short block
-            b.U = (int32_t)nuni;
-            for (int u = 0; u < 64; ++u) b.ids[u] = uni[u < nuni ? u : 0];
-            blks.push_back(b);
-        }
-    }
-    x0[nxc] = (int32_t)blks.size();
+    s2u_plan::Plan plan;
+    if (!s2u_plan::build(c->tab_host.data(), c->G, c->G_ext, gb0, ge0, S2U_GROUP, plan))
+        return fail(GENIE_ERR_ARG, "stage 2: a source-neighbour index outside the context's source nodes");
     genie_ctx::S2uTables t;
-    t.nblk = (int)blks.size();
-    GENIE_TRY(dev_upload(t.blocks, blks));
-    GENIE_TRY(dev_upload(t.xcd0, x0, (size_t)nxc + 1));
+    t.nblk = (int)plan.blocks.size();
+    t.ngroups = 0;
+    for (int x = 0; x < s2u_plan::NXCD; ++x) t.ngroups += (plan.xcd0[x + 1] - plan.xcd0[x] + S2U_GROUP - 1) / S2U_GROUP;
+    GENIE_TRY(dev_upload(t.blocks, plan.blocks));
+    GENIE_TRY(dev_upload(t.xcd0, plan.xcd0, (size_t)s2u_plan::NXCD + 1));
     *out = &(c->s2u[key] = std::move(t));
     return GENIE_OK;
 }
@@ -2670,12 +2631,14 @@ int launch_stage2_h2u(genie_ctx* c, const DaArgs& a, int gi_begin, int gi_end, b
     const genie_ctx::S2uTables* tb = nullptr;
     if (int rc = get_s2u_tables(c, gi_begin, gi_end, &tb)) return rc;
     const size_t lds = sizeof(float) * S2H_IMG_FLOATS + (size_t)S2U_UCAP * 1024;
-    const long long items = (long long)tb->nblk * c->T;
+    static_assert(s2u_plan::NXCD == 8, "the grid below is a multiple of 8 workgroups, one share per chunk of the plan");
+    if (a.nxcd != s2u_plan::NXCD) return fail(GENIE_ERR_STATE, "stage 2: the block table is planned for 8 XCD chunks");
+    const long long items = (long long)tb->ngroups * c->T;
     const int grid = (int)std::max<long long>(8, std::min<long long>((long long)c->num_cu * GENIE_S2U_BPC, (items + 7) / 8 * 8) / 8 * 8);
     const bool big = c->P_ext * 128 >= (1ll << 32);
     auto launch = [&](auto kern) -> int {
         if (int r = raise_lds_limit(c, (const void*)kern, 160 * 1024)) return r;
-        kern<<<grid, S2U_WPB * 64, lds, st>>>(a, tb->blocks, tb->xcd0);
+        kern<<<grid, S2U_WPB * 64, lds, st>>>(a, tb->blocks, tb->xcd0, S2U_GROUP);
         return GENIE_OK;
     };
     if (xl) return big ? launch(k_stage2_h2u<true, true, SAVE>) : launch(k_stage2_h2u<true, false, SAVE>);

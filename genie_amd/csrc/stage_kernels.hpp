@@ -1545,14 +1545,24 @@ constexpr int S2U_UCAP = GENIE_S2U_UCAP;   // distinct neighbour rows of a block
                                            // (Round 5: 32 rows at 4 workgroups per CU, 48 at 3 -- more resident waves, less sharing and blocks cut short
                                            // with empty node slots -- 0.711 and 0.374 ms against 0.202: the staging is what this kernel lives on.)
 constexpr int S2U_NSTG = S2U_UCAP / S2U_WPB;
-struct S2uBlock {                    // one block of the processing order
-    int32_t gi0, n, U, pad;          // first position, source nodes (1 .. 8), union size
-    int32_t ids[64];                 // source node of union row u (padded with row 0); one per lane of the wave that stages them
-    int32_t idx[S2U_NB][16];         // node b: [0] = its source node id (-1: the block has no node b), [1 + k] = union row of its k-th neighbour
-};
+#ifndef GENIE_S2U_GROUP
+#define GENIE_S2U_GROUP 4
+#endif
+constexpr int S2U_GROUP = GENIE_S2U_GROUP; // blocks a workgroup runs in a row for one station tile, keeping the union rows they share in LDS.
+                                           // Config 2 (1289 blocks, 13 tiles, 512 workgroups), carried fraction f of the union rows / window, same box:
+                                           //   1: 0      0.615 ms (every block stages its whole union)      4: 0.354  0.605
+                                           //   2: 0.225  (under the 0.25 gate, not timed)                   8: 0.420  0.612
+                                           //   3: 0.317  0.607
+                                           // Longer groups carry more and make the items coarser: at 4 a workgroup runs 8 or 9 items (8.3 on
+                                           // average), at 8 it runs 4 or 5 (4.2), and the kernel ends with its slowest workgroup.
+                                           // Config 4 (125 tiles, ~390 items per workgroup, f = 0.359 at 4): kernel 13.74 -> 11.59 ms.
+// The block table is built by s2u_plan.hpp (host only): blocks, their LDS slot maps and the groups of S2U_GROUP consecutive blocks
+// that a workgroup runs in order for one station tile, so that the union rows two neighbouring blocks share are staged once.
+typedef s2u_plan::Block S2uBlock;
+static_assert(s2u_plan::NB == S2U_NB && s2u_plan::UCAP == S2U_UCAP, "s2u_plan.hpp cuts blocks for another kernel shape");
 
 template <bool XL, bool BIG, bool SAVE = false>      // SAVE: training forward (pre-activations of x_latent and of the Bipartite message kept)
-__global__ __launch_bounds__(S2U_WPB * 64, GENIE_S2U_BPC) void k_stage2_h2u(DaArgs a, const S2uBlock* __restrict__ blocks, const int32_t* __restrict__ xcd_blk0) {
+__global__ __launch_bounds__(S2U_WPB * 64, GENIE_S2U_BPC) void k_stage2_h2u(DaArgs a, const S2uBlock* __restrict__ blocks, const int32_t* __restrict__ xcd_blk0, int L) {
     constexpr int KS = 8, KP = 15;
     constexpr int NF4 = S2H_IMG_FLOATS / 4;
     extern __shared__ __attribute__((aligned(16))) f32x4 s2u_smem[];
@@ -1565,10 +1575,13 @@ __global__ __launch_bounds__(S2U_WPB * 64, GENIE_S2U_BPC) void k_stage2_h2u(DaAr
     const int jl = lane >> 2, ql = lane & 3;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int S = a.S, T = a.T;
-    const int nx = (a.nxcd > 1 && gridDim.x >= (unsigned)a.nxcd && (gridDim.x % a.nxcd) == 0) ? a.nxcd : 1;
+    // One chunk of the plan per XCD, always: the plan restarts its groups at every chunk boundary, so a sweep that ran over the
+    // chunks as one range would open groups on blocks that expect their predecessor's rows in LDS. launch_stage2_h2u gives a grid
+    // that is a multiple of the plan's chunk count and refuses any other `nxcd`.
+    constexpr int nx = s2u_plan::NXCD;
     const int xcd = blockIdx.x % nx, lb = blockIdx.x / nx, nbx = gridDim.x / nx;
-    const int blk0 = nx == 1 ? xcd_blk0[0] : xcd_blk0[xcd], blk1 = nx == 1 ? xcd_blk0[a.nxcd] : xcd_blk0[xcd + 1];
-    const long long n_items = (long long)(blk1 - blk0) * T;          // item = (block, station tile), swept backwards
+    const int blk0 = xcd_blk0[xcd], blk1 = xcd_blk0[xcd + 1];
+    const long long n_items = (long long)((blk1 - blk0 + L - 1) / L) * T;      // item = (group of <= L blocks, station tile), swept backwards
     __syncthreads();
     if (lb >= n_items) return;
     const float a2 = a.slope2 != nullptr ? *a.slope2 : lbias[32], ab1 = lbias[33];
@@ -1583,18 +1596,29 @@ __global__ __launch_bounds__(S2U_WPB * 64, GENIE_S2U_BPC) void k_stage2_h2u(DaAr
     const int bperm = (4 * m + kg) * 4;
     const unsigned m_T = ItemIter::recip((unsigned)T);
 
-    // item number (clamped to this workgroup's last one) -> (block, station tile)
-    long long it_last = lb;
-    while (it_last + nbx < n_items) it_last += nbx;
-    auto item_of = [&](long long it, int& blk, int& tb) {
-        const long long itr = n_items - 1 - (it <= it_last ? it : it_last);
+    // A workgroup's block-tiles in the order it runs them: its items lb, lb + nbx, ..., the blocks of an item's group in table order.
+    // `step` moves a cursor to the next block-tile and says whether there was one (the cursor stays on the last one otherwise).
+    struct Cur { long long it; int blk, end, tb; };      // item number, block, end of its group, station tile
+    auto item_at = [&](long long it) {
+        const long long itr = n_items - 1 - it;
         unsigned rem;
         const unsigned kb = T <= 1 ? (rem = 0u, (unsigned)itr) : ItemIter::fdiv((unsigned)itr, (unsigned)T, m_T, rem);
-        blk = __builtin_amdgcn_readfirstlane(blk0 + (int)kb);
-        tb = __builtin_amdgcn_readfirstlane((int)rem);
+        Cur c;
+        c.it = it;
+        c.blk = __builtin_amdgcn_readfirstlane(blk0 + (int)kb * L);
+        c.end = min(c.blk + L, blk1);
+        c.tb = __builtin_amdgcn_readfirstlane((int)rem);
+        return c;
     };
-    // ---- union rows of a block-tile: global -> registers (issued one block-tile ahead) -> LDS. `idl`: lane u holds the source node
-    // of union row u, lane 63's copy of U rides in `Uv` (both loaded one MORE block-tile ahead: nothing here waits on a fresh load)
+    auto step = [&](Cur& c) {
+        if (c.blk + 1 < c.end) { ++c.blk; return true; }
+        if (c.it + nbx >= n_items) return false;
+        c = item_at(c.it + nbx);
+        return true;
+    };
+    // ---- rows a block-tile stages (all of its union in a group's first block, the rows its predecessors did not leave in LDS in
+    // the others): global -> registers (issued one block-tile ahead) -> their LDS slots. `idl` / `sll`: lane e holds the source node
+    // and the slot of staged row e, `U` their number (all loaded one MORE block-tile ahead: nothing here waits on a fresh load)
     f32x4 stg[S2U_NSTG];
     auto stage_issue = [&](int idl, int U, int tb) {
         const int s = tb * 16 + m, sc = s < S ? s : S - 1;
@@ -1608,11 +1632,11 @@ __global__ __launch_bounds__(S2U_WPB * 64, GENIE_S2U_BPC) void k_stage2_h2u(DaAr
             }
         }
     };
-    auto stage_write = [&](int U) {
+    auto stage_write = [&](int sll, int U) {
 #pragma unroll
         for (int i = 0; i < S2U_NSTG; ++i) {
             const int u = wave + S2U_WPB * i;
-            if (u < U) *(f32x4*)(lrows + (unsigned)u * 1024u + (unsigned)lane * 16u) = stg[i];
+            if (u < U) *(f32x4*)(lrows + (unsigned)__builtin_amdgcn_readlane(sll, u) * 1024u + (unsigned)lane * 16u) = stg[i];
         }
     };
     // ---- per-node rows: streamed rows + station-neighbour gathers (one node-tile ahead)
@@ -1639,46 +1663,37 @@ __global__ __launch_bounds__(S2U_WPB * 64, GENIE_S2U_BPC) void k_stage2_h2u(DaAr
 #pragma unroll
         for (int k = 0; k < KS; ++k) R.ru[k] = *(grow)((gbytes)ub + ((unsigned)sta[k] * 64u + q16));
     };
-    // Every wave takes the two slots b = wave, wave + 4 of EVERY item of its workgroup (a short block leaves slots empty: their
+    // Every wave takes the two slots b = wave, wave + 4 of EVERY block-tile of its workgroup (a short block leaves slots empty: their
     // index row starts with -1): the slot sequence is regular, so no control decision waits on a table load.
-    // slot number j -> (item j / 2, half j % 2); index rows are loaded two slots ahead, station ids and per-node rows one ahead.
-    auto slot = [&](long long j, int& blk, int& tb, int& b) {
-        item_of(lb + (j >> 1) * nbx, blk, tb);
-        b = wave + S2U_WPB * (int)(j & 1);
-    };
-    auto idv_at = [&](long long j) {
-        int blk, tb, b;
-        slot(j, blk, tb, b);
-        return blocks[blk].idx[b][m];
-    };
-    const long long n_my_items = (n_items - lb + nbx - 1) / nbx;
-    int blk_c, tb_c, blk_n, tb_n, blk_2, tb_2, dummy;
-    item_of(lb, blk_c, tb_c);
-    item_of(lb + nbx, blk_n, tb_n);
-    int idl_c = blocks[blk_c].ids[lane], U_c = blocks[blk_c].U;
-    int idl_n = blocks[blk_n].ids[lane], U_n = blocks[blk_n].U;
+    // Index rows are loaded two slots ahead (the slots of the next block-tile, of this one again after the last), station ids and
+    // per-node rows one ahead.
+    Cur cc = item_at(lb), cn = cc;
+    bool has_next = step(cn);
+    Cur c2 = cn;
+    bool has_2 = step(c2);
+    int blk_c = cc.blk, tb_c = cc.tb, blk_n = cn.blk, tb_n = cn.tb;
+    int idl_c = blocks[blk_c].ids[lane], sll_c = blocks[blk_c].slot[lane], U_c = blocks[blk_c].nst;
+    int idl_n = blocks[blk_n].ids[lane], sll_n = blocks[blk_n].slot[lane], U_n = blocks[blk_n].nst;
     stage_issue(idl_c, __builtin_amdgcn_readfirstlane(U_c), tb_c);
-    int idv_c = idv_at(0), idv_n = idv_at(1);
+    int idv_c = blocks[blk_c].idx[wave][m], idv_n = blocks[blk_c].idx[wave + S2U_WPB][m];
     load_sta(tb_c);
     issue(idv_c, tb_c);
-    for (long long ii = 0; ii < n_my_items; ++ii) {
-        const bool has_next_item = ii + 1 < n_my_items;
-        item_of(lb + (ii + 2) * nbx, blk_2, tb_2);
-        const int idl_2 = blocks[blk_2].ids[lane], U_2 = blocks[blk_2].U;       // two items ahead (clamped), consumed next iteration
-        stage_write(__builtin_amdgcn_readfirstlane(U_c));
+    for (;;) {
+        const bool has_next_item = has_next;
+        const int blk_2 = c2.blk, tb_2 = c2.tb;
+        const int idl_2 = blocks[blk_2].ids[lane], sll_2 = blocks[blk_2].slot[lane], U_2 = blocks[blk_2].nst;   // two block-tiles ahead (clamped), consumed next iteration
+        stage_write(sll_c, __builtin_amdgcn_readfirstlane(U_c));
         __syncthreads();
         if (has_next_item) stage_issue(idl_n, __builtin_amdgcn_readfirstlane(U_n), tb_n);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             asm volatile("" : "+v"(lane));
-            const long long j = 2 * ii + h;
-            const int idv_2 = idv_at(j + 2 < 2 * n_my_items ? j + 2 : j);
+            const int idv_2 = blocks[blk_n].idx[wave + S2U_WPB * h][m];
             const int g_raw = __builtin_amdgcn_readlane(idv_c, 0);
             const bool live = g_raw >= 0;
             const int g_c = max(g_raw, 0);
             const int tbc = tb_c;
             const int tb_next = h == 0 ? tb_c : tb_n;          // station tile of the next slot
-            (void)dummy;
             // (1) neighbour sums in edge order: station rows from their registers (row layout -> operand layout), source rows from LDS
             f32x4 n1 = {0.f, 0.f, 0.f, 0.f}, n2 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -1753,6 +1768,8 @@ __global__ __launch_bounds__(S2U_WPB * 64, GENIE_S2U_BPC) void k_stage2_h2u(DaAr
         if (!has_next_item) break;
         __syncthreads();              // every wave has finished reading this block-tile's rows
         blk_c = blk_n; tb_c = tb_n; blk_n = blk_2; tb_n = tb_2;
-        idl_c = idl_n; U_c = U_n; idl_n = idl_2; U_n = U_2;
+        idl_c = idl_n; sll_c = sll_n; U_c = U_n; idl_n = idl_2; sll_n = sll_2; U_n = U_2;
+        has_next = has_2;
+        has_2 = step(c2);
     }
 }
