@@ -195,6 +195,8 @@ enum {
     W_AS_L1T12_P, W_AS_L1T22_P, W_AS_L2T12_P, W_AS_L2T22_P, W_AS_INIT_ABS,
     W_COUNT
 };
+// first weight id (fc1.weight) of SpatialAggregation `layer`; its other eight follow in the order of the enum
+constexpr int sa_base(int layer) { return layer == 1 ? W_SA1_FC1_W : (layer == 2 ? W_SA2_FC1_W : W_SA3_FC1_W); }
 
 Param g_params[W_COUNT] = {
     {"DataAggregation.init_trns.weight", 30 * 8, 0}, {"DataAggregation.init_trns.bias", 30, 0},
@@ -836,7 +838,7 @@ void build_tail_plans(StagePlan* plan) {
     }
     for (int layer = 1; layer <= 3; ++layer) {
         StagePlan& p = plan[PL_SA1 + layer - 1];
-        const int base = layer == 1 ? W_SA1_FC1_W : (layer == 2 ? W_SA2_FC1_W : W_SA3_FC1_W);
+        const int base = sa_base(layer);
         const int C = layer == 1 ? 15 : 30;
         for (int t = 0; t < 2; ++t) {
             if (C == 15) { add_block_group(p, base + 2, C + 30, 16 * t, rows2(t), 0, 15); add_unused_group(p); }
@@ -1589,13 +1591,7 @@ int da_grid_w(const genie_ctx* c, long long nitems_waves, int blocks_per_cu, int
     g = std::max<long long>(8, (g + 7) / 8 * 8);
     return (int)g;
 }
-int da_grid(const genie_ctx* c, long long nitems_waves, int blocks_per_cu) {
-    long long need = (nitems_waves + WAVES - 1) / WAVES;
-    long long cap = (long long)c->num_cu * blocks_per_cu;
-    long long g = std::min(need, cap);
-    g = std::max<long long>(8, (g + 7) / 8 * 8);
-    return (int)g;
-}
+int da_grid(const genie_ctx* c, long long nitems_waves, int blocks_per_cu) { return da_grid_w(c, nitems_waves, blocks_per_cu, WAVES); }
 
 DaArgs make_da_args(const genie_ctx* c, const StageCall& call, float* ws) {
     DaArgs a;
@@ -1718,7 +1714,7 @@ void build_tail_train_plans(StagePlan* plan) {
     }
     for (int layer = 1; layer <= 3; ++layer) {
         StagePlan& p = plan[PL_TSA1 + layer - 1];
-        const int base = layer == 1 ? W_SA1_FC1_W : (layer == 2 ? W_SA2_FC1_W : W_SA3_FC1_W);
+        const int base = sa_base(layer);
         const int C = layer == 1 ? 15 : 30;
         auto xrows = [&](int b) { return C == 15 ? 15 : rows2(b); };
         for (int b = 0; b < 2; ++b)                       // fc2^T, x_i part
@@ -1863,7 +1859,7 @@ int build_tail_grad_maps(ModelTables* tb) {
     for (int m = 0; m < 2; ++m)
         for (int h = 0; h < 5; ++h) V(TM_SN, O(m == 0 ? W_SAT_C_B : W_SAT_V_B), 15 * h, 15);
     for (int layer = 1; layer <= 3; ++layer) {
-        const int base = layer == 1 ? W_SA1_FC1_W : (layer == 2 ? W_SA2_FC1_W : W_SA3_FC1_W);
+        const int base = sa_base(layer);
         const int C = layer == 1 ? 15 : 30;
         const int sa = TM_SAA1 + layer - 1, sb = TM_SAB1 + layer - 1;
         for (int t = 0; t < 2; ++t) {
@@ -2785,8 +2781,12 @@ namespace {
 // virtual blocks of SpatialAggregation's grid-wide mean (SaArgs.vg): a function of the source-node count only, so that the sum's
 // partition -- hence every output bit -- is the same for any launch grid (per window, side streams, batches of 1..16 windows)
 int sa_vg(const genie_ctx* c) { return tl_blocks(c->G, 512); }
-void sa_fill_layer(const genie_ctx* c, int layer, SaArgs& a) {
-    const int base = layer == 1 ? W_SA1_FC1_W : (layer == 2 ? W_SA2_FC1_W : W_SA3_FC1_W);
+// the graph, weights and weight image of SpatialAggregation `layer`; everything else zero
+SaArgs make_sa_args(const genie_ctx* c, int layer) {
+    SaArgs a;
+    memset(&a, 0, sizeof(a));
+    const int base = sa_base(layer);
+    a.img = c->packed[PL_SA1 + layer - 1];
     a.G = c->G; a.C = layer == 1 ? 15 : 30; a.E = c->E_src; a.vg = sa_vg(c);
     a.rowptr = c->src_rowptr; a.col = c->src_col; a.outdeg = c->outdeg;
     a.raw = c->raw; a.scale_rel = c->scale_rel;
@@ -2795,54 +2795,85 @@ void sa_fill_layer(const genie_ctx* c, int layer, SaArgs& a) {
     a.fg_w = g_params[base + 4].off; a.fg_b = g_params[base + 5].off;
     a.act1 = g_params[base + 6].off; a.act2 = g_params[base + 7].off; a.act3 = g_params[base + 8].off;
     if (layer < 3) {
-        const int nb = layer == 1 ? W_SA2_FC1_W : W_SA3_FC1_W;
+        const int nb = sa_base(layer + 1);
         a.nx_fc1_w = g_params[nb + 0].off; a.nx_fg_w = g_params[nb + 4].off; a.nx_fg_b = g_params[nb + 5].off;
         a.nx_act3 = g_params[nb + 8].off;
     }
+    return a;
 }
 int sa_blocks(const genie_ctx* c) { return tl_blocks(c->G, std::min(1024, c->tail_cu_sa)); }
 
-// The pre-pass of `layer` was already produced (by k_sa_pre_m or by the previous layer's NEXT tail) in pj / gpart buffer `cur`;
-// with_next emits the next layer's pre-pass into the other buffer.
-int sa_launch_layer(genie_ctx* c, const StageCall& call, int layer, const float* x_in, const float* pos, float* out, float* ws, int cur,
-                    bool with_next, hipStream_t st) {
-    SaArgs a;
-    memset(&a, 0, sizeof(a));
-    sa_fill_layer(c, layer, a);
-    a.x_in = x_in; a.pos = pos; a.out = out;
-    const size_t so = c->slot * c->slot_stride;
-    float* pj[2] = {ws + c->o_pj0 + so, ws + c->o_pj1 + so};
-    float* gp[2] = {ws + c->o_gpart + so, ws + c->o_gpart + so + 1024 * 8};
-    a.pj_in = pj[cur]; a.gpart_in = gp[cur]; a.n_gpart_in = sa_vg(c);
-    a.pj_out = pj[cur ^ 1]; a.gpart_out = gp[cur ^ 1];
-    const int nb = sa_blocks(c);
-    { int rcp = ensure_packed(c, st); if (rcp) return rcp; }
-    a.img = c->packed[PL_SA1 + layer - 1];
-    if (tail_wide(c, call)) {
-        if (layer == 1) { if (with_next) k_sa_layer_m<15, true, true><<<nb, 256, 0, st>>>(a); else k_sa_layer_m<15, false, true><<<nb, 256, 0, st>>>(a); }
-        else { if (with_next) k_sa_layer_m<30, true, true><<<nb, 256, 0, st>>>(a); else k_sa_layer_m<30, false, true><<<nb, 256, 0, st>>>(a); }
-    } else if (layer == 1) {
-        if (with_next) k_sa_layer_m<15, true, false><<<nb, 256, 0, st>>>(a); else k_sa_layer_m<15, false, false><<<nb, 256, 0, st>>>(a);
-    } else {
-        if (with_next) k_sa_layer_m<30, true, false><<<nb, 256, 0, st>>>(a); else k_sa_layer_m<30, false, false><<<nb, 256, 0, st>>>(a);
-    }
+// ---- launchers: the only place that names the instantiations of a tail kernel family. The grid is the caller's (x: workgroups per
+// window, y: windows; the grids of the entry points differ and are tuned), the weight images must be packed (ensure_packed).
+typedef void (*SaKernel)(SaArgs);
+void launch_sa_layer(bool wide, int layer, bool with_next, dim3 grid, const SaArgs& a, hipStream_t st) {
+    static const SaKernel kern[2][2][2] = {      // [WIDE][C == 30][NEXT]
+        {{k_sa_layer_m<15, false, false>, k_sa_layer_m<15, true, false>}, {k_sa_layer_m<30, false, false>, k_sa_layer_m<30, true, false>}},
+        {{k_sa_layer_m<15, false, true>, k_sa_layer_m<15, true, true>}, {k_sa_layer_m<30, false, true>, k_sa_layer_m<30, true, true>}}};
+    const SaKernel k = kern[wide][layer != 1][with_next];
+    k<<<grid, 256, 0, st>>>(a);
+}
+void launch_sa_pre(bool wide, int layer, dim3 grid, const SaArgs& a, hipStream_t st) {
+    static const SaKernel kern[2][2] = {{k_sa_pre_m<15, false>, k_sa_pre_m<30, false>}, {k_sa_pre_m<15, true>, k_sa_pre_m<30, true>}};   // [WIDE][C == 30]
+    const SaKernel k = kern[wide][layer != 1];
+    k<<<grid, 256, 0, st>>>(a);
+}
+void launch_bip_pre(const genie_ctx* c, bool wide, dim3 grid, const float* part, long long part_ws, const SaArgs& a, hipStream_t st) {
+    const auto k = wide ? k_bip_pre_m<true> : k_bip_pre_m<false>;
+    k<<<grid, 256, 0, st>>>(part, part_T(c), c->packed[PL_BIP], part_ws, a);
+}
+
+// The two pj / gpart buffers of a workspace slot. A layer reads its own pre-pass from buffer `cur` (left there by k_sa_pre_m, k_bip_pre_m
+// or the previous layer's NEXT tail) and leaves the next layer's in the other one. Window w of a batch uses slot + w: `stride` floats on.
+struct SaPing {
+    float* pj[2];
+    float* gp[2];
+    long long stride;
+};
+SaPing sa_ping(const genie_ctx* c, float* ws, int slot) {
+    const size_t so = (size_t)slot * c->slot_stride;
+    return {{ws + c->o_pj0 + so, ws + c->o_pj1 + so}, {ws + c->o_gpart + so, ws + c->o_gpart + so + 1024 * 8}, (long long)c->slot_stride};
+}
+// pre-pass of `layer` on one window's x_in
+void sa_pre(const genie_ctx* c, bool wide, int layer, const float* x_in, float* pj_out, float* gpart_out, hipStream_t st) {
+    SaArgs a = make_sa_args(c, layer);
+    a.x_in = x_in; a.pj_out = pj_out; a.gpart_out = gpart_out;
+    launch_sa_pre(wide, layer, sa_blocks(c), a, st);
+}
+// Bipartite read-out of the station sums `part` -> bip, and the pre-pass of SpatialAggregation1 into buffer 0, in one launch
+void bip_pre(const genie_ctx* c, bool wide, dim3 grid, const float* part, const SaPing& p, float* bip, long long ws_bip, hipStream_t st) {
+    SaArgs a = make_sa_args(c, 1);
+    a.out = bip; a.ws_out = ws_bip; a.ws_slot = p.stride;
+    a.pj_out = p.pj[0]; a.gpart_out = p.gp[0];
+    launch_bip_pre(c, wide, grid, part, p.stride, a, st);
+}
+// one layer over the windows of `grid`; ws_x_in / ws_out: floats between the inputs / outputs of consecutive windows
+void sa_layer(const genie_ctx* c, bool wide, int layer, bool with_next, dim3 grid, const SaPing& p, int cur, const float* x_in,
+              long long ws_x_in, const float* pos, float* out, long long ws_out, hipStream_t st) {
+    SaArgs a = make_sa_args(c, layer);
+    a.x_in = x_in; a.ws_x_in = ws_x_in; a.pos = pos; a.out = out; a.ws_out = ws_out; a.ws_slot = p.stride;
+    a.pj_in = p.pj[cur]; a.gpart_in = p.gp[cur]; a.n_gpart_in = a.vg;
+    a.pj_out = p.pj[cur ^ 1]; a.gpart_out = p.gp[cur ^ 1];
+    launch_sa_layer(wide, layer, with_next, grid, a, st);
+}
+// SpatialAggregation 1 -> 2 -> 3 over the windows of `grid`: the one place where the pj / gpart buffers rotate. Layer 1's pre-pass is
+// in buffer 0; x_in [G, 15] -> mid[0] -> mid[1] -> out [G, 30], each with the floats between consecutive windows.
+struct SaChain {
+    const float* x_in; long long ws_x_in;
+    float* mid[2]; long long ws_mid;
+    float* out; long long ws_out;
+};
+int sa_chain(const genie_ctx* c, bool wide, dim3 grid, const SaPing& p, const SaChain& io, const float* pos, hipStream_t st) {
+    sa_layer(c, wide, 1, true, grid, p, 0, io.x_in, io.ws_x_in, pos, io.mid[0], io.ws_mid, st);
+    sa_layer(c, wide, 2, true, grid, p, 1, io.mid[0], io.ws_mid, pos, io.mid[1], io.ws_mid, st);
+    sa_layer(c, wide, 3, false, grid, p, 0, io.mid[1], io.ws_mid, pos, io.out, io.ws_out, st);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }
-int sa_launch_pre(genie_ctx* c, const StageCall& call, int layer, const float* x_in, float* ws, int cur, hipStream_t st) {
-    SaArgs a;
-    memset(&a, 0, sizeof(a));
-    sa_fill_layer(c, layer, a);
-    a.x_in = x_in;
-    a.pj_out = ws + (cur ? c->o_pj1 : c->o_pj0) + c->slot * c->slot_stride;
-    a.gpart_out = ws + c->o_gpart + c->slot * c->slot_stride + (cur ? 1024 * 8 : 0);
-    const int nb = sa_blocks(c);
-    { int rcp = ensure_packed(c, st); if (rcp) return rcp; }
-    a.img = c->packed[PL_SA1 + layer - 1];
-    if (tail_wide(c, call)) { if (layer == 1) k_sa_pre_m<15, true><<<nb, 256, 0, st>>>(a); else k_sa_pre_m<30, true><<<nb, 256, 0, st>>>(a); }
-    else { if (layer == 1) k_sa_pre_m<15, false><<<nb, 256, 0, st>>>(a); else k_sa_pre_m<30, false><<<nb, 256, 0, st>>>(a); }
-    HIP_TRY(hipGetLastError());
-    return GENIE_OK;
+// the chain whose intermediates live in the workspace slot(s) from `slot` on
+SaChain sa_slot_chain(const genie_ctx* c, float* ws, int slot, const float* x_in, long long ws_x_in, float* out, long long ws_out) {
+    const size_t so = (size_t)slot * c->slot_stride;
+    return {x_in, ws_x_in, {ws + c->o_sa0 + so, ws + c->o_sa1 + so}, (long long)c->slot_stride, out, ws_out};
 }
 }  // namespace
 
@@ -2854,8 +2885,13 @@ int genie_spatial_agg_fwd(genie_ctx* c, int layer, const float* x_in, const floa
     if (!x_in || !pos || !out) return fail(GENIE_ERR_ARG, "genie_spatial_agg_fwd: null argument");
     if (c->G_ext != c->G) return fail(GENIE_ERR_STATE, "genie_spatial_agg_fwd needs an unsharded source graph");
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = sa_launch_pre(c, kInference, layer, x_in, (float*)ws, 0, st))) return rc;
-    return sa_launch_layer(c, kInference, layer, x_in, pos, out, (float*)ws, 0, false, st);
+    if ((rc = ensure_packed(c, st))) return rc;
+    const bool wide = tail_wide(c, kInference);
+    const SaPing p = sa_ping(c, (float*)ws, c->slot);
+    sa_pre(c, wide, layer, x_in, p.pj[0], p.gp[0], st);
+    sa_layer(c, wide, layer, false, sa_blocks(c), p, 0, x_in, 0, pos, out, 0, st);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
 }
 
 int genie_spatial_agg3_fwd(genie_ctx* c, const float* x_in15, const float* pos, float* out, void* ws, void* stream) {
@@ -2864,12 +2900,11 @@ int genie_spatial_agg3_fwd(genie_ctx* c, const float* x_in15, const float* pos, 
     if (!x_in15 || !pos || !out) return fail(GENIE_ERR_ARG, "genie_spatial_agg3_fwd: null argument");
     if (c->G_ext != c->G) return fail(GENIE_ERR_STATE, "genie_spatial_agg3_fwd needs an unsharded source graph");
     hipStream_t st = (hipStream_t)stream;
-    float* w = (float*)ws;
-    if ((rc = sa_launch_pre(c, kInference, 1, x_in15, w, 0, st))) return rc;
-    const size_t so = c->slot * c->slot_stride;
-    if ((rc = sa_launch_layer(c, kInference, 1, x_in15, pos, w + c->o_sa0 + so, w, 0, true, st))) return rc;
-    if ((rc = sa_launch_layer(c, kInference, 2, w + c->o_sa0 + so, pos, w + c->o_sa1 + so, w, 1, true, st))) return rc;
-    return sa_launch_layer(c, kInference, 3, w + c->o_sa1 + so, pos, out, w, 0, false, st);
+    if ((rc = ensure_packed(c, st))) return rc;
+    const bool wide = tail_wide(c, kInference);
+    const SaPing p = sa_ping(c, (float*)ws, c->slot);
+    sa_pre(c, wide, 1, x_in15, p.pj[0], p.gp[0], st);
+    return sa_chain(c, wide, sa_blocks(c), p, sa_slot_chain(c, (float*)ws, c->slot, x_in15, 0, out, 0), pos, st);
 }
 
 int genie_path_fwd(genie_ctx* c, const float* slice, const float* mask, const float* edge_attr, const float* pos,
@@ -2889,22 +2924,10 @@ int genie_path_fwd(genie_ctx* c, const float* slice, const float* mask, const fl
     if ((rc = genie_da_stage2_partials(c, mask, edge_attr, x_latent_out, ws, stream))) return rc;
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_packed(c, st))) return rc;
-    const size_t so = c->slot * c->slot_stride;
-    {
-        SaArgs a;
-        memset(&a, 0, sizeof(a));
-        sa_fill_layer(c, 1, a);
-        a.out = bip;
-        a.pj_out = w + c->o_pj0 + so; a.gpart_out = w + c->o_gpart + so;
-        a.img = c->packed[PL_SA1];
-        const int nb = sa_blocks(c);
-        if (tail_wide(c, kInference)) k_bip_pre_m<true><<<nb, 256, 0, st>>>(w + c->o_part + so, part_T(c), c->packed[PL_BIP], 0, a);
-        else k_bip_pre_m<false><<<nb, 256, 0, st>>>(w + c->o_part + so, part_T(c), c->packed[PL_BIP], 0, a);
-        HIP_TRY(hipGetLastError());
-    }
-    if ((rc = sa_launch_layer(c, kInference, 1, bip, pos, w + c->o_sa0 + so, w, 0, true, st))) return rc;
-    if ((rc = sa_launch_layer(c, kInference, 2, w + c->o_sa0 + so, pos, w + c->o_sa1 + so, w, 1, true, st))) return rc;
-    return sa_launch_layer(c, kInference, 3, w + c->o_sa1 + so, pos, x_spatial_out, w, 0, false, st);
+    const bool wide = tail_wide(c, kInference);
+    const SaPing p = sa_ping(c, w, c->slot);
+    bip_pre(c, wide, sa_blocks(c), w + c->o_part + c->slot * c->slot_stride, p, bip, 0, st);
+    return sa_chain(c, wide, sa_blocks(c), p, sa_slot_chain(c, w, c->slot, bip, 0, x_spatial_out, 0), pos, st);
 }
 
 namespace {
@@ -2924,35 +2947,49 @@ RoArgs make_ro_args(const genie_ctx* c) {
     a.o_sa1 = g_params[W_SAT_ACT1].off; a.o_sa2 = g_params[W_SAT_ACT2].off;
     return a;
 }
-}  // namespace
 
-namespace {
+// ---- launchers of the read-out heads; their workgroup count follows tail_cu_ro in every entry point
 // grid read-out (k_readout_m<0>): fp64 chains for inference calls (their score scratch holds doubles), fp32 for the training forward
 int launch_readout_grid(genie_ctx* c, const StageCall& call, const RoArgs& a, bool with_cv, hipStream_t st) {
     const bool wide = tail_wide(c, call);
     const size_t lds = sizeof(float) * (ROM_LDS_FLOATS + (wide ? 4 * 16 * RO_SCS : 0) + (with_cv ? GP_IMG_FLOATS : 0));
     const int lds_max = (int)(sizeof(float) * (ROM_LDS_FLOATS + 4 * 16 * RO_SCS + GP_IMG_FLOATS));
-    if (wide) {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_readout_m<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        k_readout_m<0, true><<<tl_blocks(a.N, c->tail_cu_ro), 256, lds, st>>>(a);
-    } else {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_readout_m<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-        k_readout_m<0, false><<<tl_blocks(a.N, c->tail_cu_ro), 256, lds, st>>>(a);
-    }
+    const auto k = wide ? k_readout_m<0, true> : k_readout_m<0, false>;
+    GENIE_TRY(raise_lds_limit(c, (const void*)k, lds_max));
+    k<<<tl_blocks(a.N, c->tail_cu_ro), 256, lds, st>>>(a);
+    return GENIE_OK;
+}
+// query read-out (k_readout_m<1>), with or without the prefetch of the next tile's gathers
+int launch_readout_query(genie_ctx* c, bool prefetch, const RoArgs& a, hipStream_t st) {
+    const int lds = (int)(sizeof(float) * ROM_LDS_FLOATS);
+    const auto k = prefetch ? k_readout_m<1, false, true> : k_readout_m<1>;
+    GENIE_TRY(raise_lds_limit(c, (const void*)k, lds));
+    k<<<tl_blocks(a.N, c->tail_cu_ro), 256, lds, st>>>(a);
+    return GENIE_OK;
+}
+// the per-grid-node table cv of the query read-out, one window
+void launch_ro_pre(const genie_ctx* c, bool wide, const float* x_spatial, float* cv, hipStream_t st) {
+    const auto k = wide ? k_ro_pre_m<true> : k_ro_pre_m<false>;
+    k<<<tl_blocks(c->G, c->tail_cu_ro), 256, 0, st>>>(x_spatial, c->G, c->packed[PL_ROP], cv, c->G, 0);
+}
+
+// y = TemporalAttention(SpatialDirect(x_spatial)) per grid node, and optionally the SpatialDirect output itself
+int readout_grid_impl(genie_ctx* c, const char* who, const float* x_spatial, const float* t_query, int n_t, float* y_out, float* lat_out,
+                      void* stream) {
+    if (!c || !x_spatial || !t_query || !y_out) return fail(GENIE_ERR_ARG, std::string(who) + ": null argument");
+    if (n_t < 1 || n_t > RO_TMAX) return fail(GENIE_ERR_ARG, std::string(who) + ": 1 <= n_t <= 10 required");
+    RoArgs a = make_ro_args(c);
+    GENIE_TRY(ensure_packed(c, (hipStream_t)stream));
+    a.N = a.Nw = c->G; a.T = n_t; a.x_spatial = x_spatial; a.t_query = t_query; a.out = y_out; a.lat_out = lat_out;
+    a.img = c->packed[PL_RO0];
+    GENIE_TRY(launch_readout_grid(c, kInference, a, false, (hipStream_t)stream));
+    HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }
 }  // namespace
 
 int genie_readout_grid(genie_ctx* c, const float* x_spatial, const float* t_query, int n_t, float* y_out, void* stream) {
-    if (!c || !x_spatial || !t_query || !y_out) return fail(GENIE_ERR_ARG, "genie_readout_grid: null argument");
-    if (n_t < 1 || n_t > RO_TMAX) return fail(GENIE_ERR_ARG, "genie_readout_grid: 1 <= n_t <= 10 required");
-    RoArgs a = make_ro_args(c);
-    { int rcp = ensure_packed(c, (hipStream_t)stream); if (rcp) return rcp; }
-    a.N = a.Nw = c->G; a.T = n_t; a.x_spatial = x_spatial; a.t_query = t_query; a.out = y_out;
-    a.img = c->packed[PL_RO0];
-    { int rl = launch_readout_grid(c, kInference, a, false, (hipStream_t)stream); if (rl) return rl; }
-    HIP_TRY(hipGetLastError());
-    return GENIE_OK;
+    return readout_grid_impl(c, "genie_readout_grid", x_spatial, t_query, n_t, y_out, nullptr, stream);
 }
 
 namespace {
@@ -2970,16 +3007,10 @@ int readout_query_impl(genie_ctx* c, const float* x_spatial, const float* x_grid
     { int rcp = ensure_packed(c, (hipStream_t)stream); if (rcp) return rcp; }
     float* cvbuf = (float*)ws + c->o_cv + c->slot * c->slot_stride;
     a.cv = cvbuf;
-    if (tail_wide(c, kInference)) k_ro_pre_m<true><<<tl_blocks(c->G, c->tail_cu_ro), 256, 0, (hipStream_t)stream>>>(x_spatial, c->G, c->packed[PL_ROP], cvbuf, c->G, 0);
-    else k_ro_pre_m<false><<<tl_blocks(c->G, c->tail_cu_ro), 256, 0, (hipStream_t)stream>>>(x_spatial, c->G, c->packed[PL_ROP], cvbuf, c->G, 0);
+    launch_ro_pre(c, tail_wide(c, kInference), x_spatial, cvbuf, (hipStream_t)stream);
     a.img = c->packed[PL_RO1];
-    if (n_query <= 16384) {      // about one 16-query tile per wave of the launch: nothing else hides a wave's round trips (PF)
-        HIP_TRY(hipFuncSetAttribute((const void*)k_readout_m<1, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * ROM_LDS_FLOATS)));
-        k_readout_m<1, false, true><<<tl_blocks(a.N, c->tail_cu_ro), 256, sizeof(float) * ROM_LDS_FLOATS, (hipStream_t)stream>>>(a);
-    } else {
-        HIP_TRY(hipFuncSetAttribute((const void*)k_readout_m<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * ROM_LDS_FLOATS)));
-        k_readout_m<1><<<tl_blocks(a.N, c->tail_cu_ro), 256, sizeof(float) * ROM_LDS_FLOATS, (hipStream_t)stream>>>(a);
-    }
+    // up to about one 16-query tile per wave of the launch nothing else hides a wave's round trips: prefetch (PF)
+    GENIE_TRY(launch_readout_query(c, n_query <= 16384, a, (hipStream_t)stream));
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }
@@ -2994,15 +3025,8 @@ int genie_readout_query(genie_ctx* c, const float* x_spatial, const float* x_gri
 // y_latent = SpatialDirect(x_spatial) [n_grid, 30] and / or SpatialAttention(x_spatial, x_query, x_grid) [n_query, 30].
 int genie_readout_grid_latent(genie_ctx* c, const float* x_spatial, const float* t_query, int n_t, float* y_out, float* y_latent_out,
                               void* stream) {
-    if (!c || !x_spatial || !t_query || !y_out || !y_latent_out) return fail(GENIE_ERR_ARG, "genie_readout_grid_latent: null argument");
-    if (n_t < 1 || n_t > RO_TMAX) return fail(GENIE_ERR_ARG, "genie_readout_grid_latent: 1 <= n_t <= 10 required");
-    RoArgs a = make_ro_args(c);
-    { int rcp = ensure_packed(c, (hipStream_t)stream); if (rcp) return rcp; }
-    a.N = a.Nw = c->G; a.T = n_t; a.x_spatial = x_spatial; a.t_query = t_query; a.out = y_out; a.lat_out = y_latent_out;
-    a.img = c->packed[PL_RO0];
-    { int rl = launch_readout_grid(c, kInference, a, false, (hipStream_t)stream); if (rl) return rl; }
-    HIP_TRY(hipGetLastError());
-    return GENIE_OK;
+    if (!y_latent_out) return fail(GENIE_ERR_ARG, "genie_readout_grid_latent: null argument");
+    return readout_grid_impl(c, "genie_readout_grid_latent", x_spatial, t_query, n_t, y_out, y_latent_out, stream);
 }
 int genie_readout_query_latent(genie_ctx* c, const float* x_spatial, const float* x_grid, const float* x_query, const int32_t* knn,
                                int n_query, int k, const float* t_query, int n_t, float* x_out, float* latent_out, void* ws, void* stream) {
@@ -3031,45 +3055,13 @@ int genie_tail_batched(genie_ctx* c, int slot0, int nwin, const float* pos, cons
     float* w = (float*)ws;
     const long long ss = (long long)c->slot_stride;
     const size_t so = (size_t)slot0 * c->slot_stride;
-    // Bipartite read-out -> bip[slot] and the pre-pass of SpatialAggregation1, one launch
-    const int nbx = tl_blocks(c->G, std::min(1024, std::max(32, c->num_cu * 2 / nwin)));
-    float* pj[2] = {w + c->o_pj0 + so, w + c->o_pj1 + so};
-    float* gp[2] = {w + c->o_gpart + so, w + c->o_gpart + so + 1024 * 8};
-    const dim3 grid(nbx, nwin);
-    {
-        SaArgs a;
-        memset(&a, 0, sizeof(a));
-        sa_fill_layer(c, 1, a);
-        a.out = w + c->o_bip + so; a.ws_out = ss; a.ws_slot = ss;
-        a.pj_out = pj[0]; a.gpart_out = gp[0];
-        a.img = c->packed[PL_SA1];
-        if (tail_wide(c, kInference)) k_bip_pre_m<true><<<grid, 256, 0, st>>>(w + c->o_part + so, part_T(c), c->packed[PL_BIP], ss, a);
-        else k_bip_pre_m<false><<<grid, 256, 0, st>>>(w + c->o_part + so, part_T(c), c->packed[PL_BIP], ss, a);
-    }
-    // SpatialAggregation x3: bip -> sa0 -> sa1 -> x_spatial_out [nwin, G, 30]
-    for (int layer = 1; layer <= 3; ++layer) {
-        SaArgs a;
-        memset(&a, 0, sizeof(a));
-        sa_fill_layer(c, layer, a);
-        const int cur = (layer - 1) & 1;
-        a.pos = pos; a.ws_slot = ss;
-        a.x_in = layer == 1 ? w + c->o_bip + so : (layer == 2 ? w + c->o_sa0 + so : w + c->o_sa1 + so);
-        a.ws_x_in = ss;
-        a.out = layer == 1 ? w + c->o_sa0 + so : (layer == 2 ? w + c->o_sa1 + so : x_spatial_out);
-        a.ws_out = layer == 3 ? (long long)c->G * 30 : ss;
-        a.pj_in = pj[cur]; a.gpart_in = gp[cur]; a.n_gpart_in = sa_vg(c);
-        a.pj_out = pj[cur ^ 1]; a.gpart_out = gp[cur ^ 1];
-        a.img = c->packed[PL_SA1 + layer - 1];
-        if (tail_wide(c, kInference)) {
-            if (layer == 1) k_sa_layer_m<15, true, true><<<grid, 256, 0, st>>>(a);
-            else if (layer == 2) k_sa_layer_m<30, true, true><<<grid, 256, 0, st>>>(a);
-            else k_sa_layer_m<30, false, true><<<grid, 256, 0, st>>>(a);
-        } else {
-            if (layer == 1) k_sa_layer_m<15, true, false><<<grid, 256, 0, st>>>(a);
-            else if (layer == 2) k_sa_layer_m<30, true, false><<<grid, 256, 0, st>>>(a);
-            else k_sa_layer_m<30, false, false><<<grid, 256, 0, st>>>(a);
-        }
-    }
+    // Bipartite read-out -> bip[slot] and the pre-pass of SpatialAggregation1, one launch; then SpatialAggregation x3:
+    // bip -> sa0 -> sa1 -> x_spatial_out [nwin, G, 30]
+    const bool wide = tail_wide(c, kInference);
+    const dim3 grid(tl_blocks(c->G, std::min(1024, std::max(32, c->num_cu * 2 / nwin))), nwin);
+    const SaPing p = sa_ping(c, w, slot0);
+    bip_pre(c, wide, grid, w + c->o_part + so, p, w + c->o_bip + so, ss, st);
+    if ((rc = sa_chain(c, wide, grid, p, sa_slot_chain(c, w, slot0, w + c->o_bip + so, ss, x_spatial_out, (long long)c->G * 30), pos, st))) return rc;
     // read-out heads over the nwin * G grid nodes / nwin * Q queries
     RoArgs a = make_ro_args(c);
     a.T = n_t; a.x_spatial = x_spatial_out; a.t_query = t_query;
@@ -3083,8 +3075,7 @@ int genie_tail_batched(genie_ctx* c, int slot0, int nwin, const float* pos, cons
         RoArgs q = a;
         q.N = nwin * n_query; q.Nw = n_query; q.x_grid = pos; q.x_query = x_query; q.knn = knn; q.out = x_out;
         q.img = c->packed[PL_RO1]; q.cv = w + c->o_cv + so; q.cv_ws = ss;
-        HIP_TRY(hipFuncSetAttribute((const void*)k_readout_m<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * ROM_LDS_FLOATS)));
-        k_readout_m<1><<<tl_blocks(q.N, c->tail_cu_ro), 256, sizeof(float) * ROM_LDS_FLOATS, st>>>(q);
+        if ((rc = launch_readout_query(c, false, q, st))) return rc;
     }
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
@@ -3475,7 +3466,7 @@ int da_train_bwd_impl(genie_ctx* c, const float* slice, const float* mask, const
 // ---- training step: the G- / Q-sized tail (train_tail_kernels.hpp) -------------------------------------------------------
 namespace {
 constexpr int TT_R = 0, TT_BIP = 32, TT_SA1 = 48, TT_SA2 = 80, TT_XS = 112, TT_ROW = 144;     // floats per source node in `tsave`
-int tt_grid(long long n) { return (int)std::max<long long>(1, std::min<long long>((n + 63) / 64, 160)); }
+int tt_grid(long long n) { return tl_blocks(n, 160); }
 size_t tt_part_floats(int n_acc, int n_vec, int grid) { return (size_t)grid * 4 * ((size_t)n_acc * 256 + (size_t)n_vec * 16 + 16); }
 struct TtScratch {           // offsets (floats) into the backward's scratch
     size_t dxs_a, dxs_b, eb, dxm, cv, pj, gpart, dxd, dan, dx0, dx1, part_ro, part_ro0, part_a, part_b, total;
@@ -3528,12 +3519,11 @@ int genie_tail_train_fwd(genie_ctx* c, const float* pos, const float* x_query, c
     // inputs land in `tsave` instead of the workspace slot
     k_part_sum32<<<(c->G * 32 + 255) / 256, 256, 0, st>>>(w + c->o_part + so, c->G, part_T(c), r);
     k_bip_out_m<false><<<tl_blocks(c->G, c->tail_cu_sa), 256, 0, st>>>(w + c->o_part + so, c->G, part_T(c), c->packed[PL_BIP], bip, 0, 0);
-    if ((rc = raise_lds_limit(c, (const void*)k_readout_m<1>, (int)(sizeof(float) * ROM_LDS_FLOATS)))) return rc;
     const StageCall call{nullptr, true};     // fp32 chains (the tail's pre-activations go to `tsave`)
-    if ((rc = sa_launch_pre(c, call, 1, bip, w, 0, st))) return rc;
-    if ((rc = sa_launch_layer(c, call, 1, bip, pos, sa1, w, 0, true, st))) return rc;
-    if ((rc = sa_launch_layer(c, call, 2, sa1, pos, sa2, w, 1, true, st))) return rc;
-    if ((rc = sa_launch_layer(c, call, 3, sa2, pos, xs, w, 0, false, st))) return rc;
+    const bool wide = tail_wide(c, call);
+    const SaPing p = sa_ping(c, w, c->slot);
+    sa_pre(c, wide, 1, bip, p.pj[0], p.gp[0], st);
+    if ((rc = sa_chain(c, wide, sa_blocks(c), p, {bip, 0, {sa1, sa2}, 0, xs, 0}, pos, st))) return rc;
     RoArgs a = make_ro_args(c);
     a.T = n_t; a.x_spatial = xs; a.t_query = t_query;
     {
@@ -3542,11 +3532,11 @@ int genie_tail_train_fwd(genie_ctx* c, const float* pos, const float* x_query, c
         if ((rc = launch_readout_grid(c, call, g, false, st))) return rc;
     }
     float* cvbuf = w + c->o_cv + so;
-    k_ro_pre_m<false><<<tl_blocks(c->G, c->tail_cu_ro), 256, 0, st>>>(xs, c->G, c->packed[PL_ROP], cvbuf, c->G, 0);
+    launch_ro_pre(c, wide, xs, cvbuf, st);
     {
         RoArgs q = a;
         q.N = q.Nw = n_query; q.x_grid = pos; q.x_query = x_query; q.knn = knn; q.out = x_out; q.img = c->packed[PL_RO1]; q.cv = cvbuf;
-        k_readout_m<1><<<tl_blocks(q.N, c->tail_cu_ro), 256, sizeof(float) * ROM_LDS_FLOATS, st>>>(q);
+        if ((rc = launch_readout_query(c, false, q, st))) return rc;
     }
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
@@ -3570,8 +3560,8 @@ int genie_tail_train_bwd(genie_ctx* c, const float* pos, const float* x_query, c
     const TtScratch L = tt_layout(c, n_query);
     float* S = scratch;
     HIP_TRY(hipMemsetAsync(grad_blob, 0, sizeof(float) * genie_train_grad_floats(), st));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_ro_bwd<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * RB_LDS_FLOATS)));
-    HIP_TRY(hipFuncSetAttribute((const void*)k_ro_bwd<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * RB_LDS_FLOATS)));
+    if ((rc = raise_lds_limit(c, (const void*)k_ro_bwd<0>, (int)(sizeof(float) * RB_LDS_FLOATS)))) return rc;
+    if ((rc = raise_lds_limit(c, (const void*)k_ro_bwd<1>, (int)(sizeof(float) * RB_LDS_FLOATS)))) return rc;
     RoArgs ro = make_ro_args(c);
     ro.T = n_t; ro.x_spatial = xs; ro.t_query = t_query;
     // The y branch (grid read-out: 61 us) and the x branch (query read-out + its grid-node side: 159 + 37 us) are independent until
@@ -3602,7 +3592,7 @@ int genie_tail_train_bwd(genie_ctx* c, const float* pos, const float* x_query, c
         HIP_TRY(hipEventRecord(c->ev_join, c->side_stream));
     }
     {   // x branch: TemporalAttention + SpatialAttention (query side), then its grid-node side
-        k_ro_pre_m<false><<<tl_blocks(c->G, c->tail_cu_ro), 256, 0, st>>>(xs, c->G, c->packed[PL_ROP], S + L.cv, c->G, 0);
+        launch_ro_pre(c, false, xs, S + L.cv, st);
         RbArgs b;
         memset(&b, 0, sizeof(b));
         b.ro = ro; b.ro.N = b.ro.Nw = n_query; b.ro.x_grid = pos; b.ro.x_query = x_query; b.ro.knn = knn; b.ro.cv = S + L.cv;
@@ -3631,17 +3621,12 @@ int genie_tail_train_bwd(genie_ctx* c, const float* pos, const float* x_query, c
     float* dxl[2] = {S + L.dx0, S + L.dx1};
     const int gs = tt_grid(c->G);
     for (int layer = 3; layer >= 1; --layer) {
-        SaArgs pre;
-        memset(&pre, 0, sizeof(pre));
-        sa_fill_layer(c, layer, pre);
-        pre.x_in = x_in[layer - 1]; pre.pj_out = S + L.pj; pre.gpart_out = S + L.gpart; pre.img = c->packed[PL_SA1 + layer - 1];
-        const int nbp = sa_blocks(c);
-        if (layer == 1) k_sa_pre_m<15, false><<<nbp, 256, 0, st>>>(pre); else k_sa_pre_m<30, false><<<nbp, 256, 0, st>>>(pre);
+        sa_pre(c, false, layer, x_in[layer - 1], S + L.pj, S + L.gpart, st);
         SbArgs a;
         memset(&a, 0, sizeof(a));
         a.G = c->G; a.C = layer == 1 ? 15 : 30; a.E = c->E_src; a.x_in = x_in[layer - 1]; a.pos = pos;
         a.rowptr = c->src_rowptr; a.col = c->src_col; a.outdeg = c->outdeg; a.r_rowptr = c->r_src.rowptr; a.r_col = c->r_src.col;
-        a.raw = c->raw; a.fc1_w = g_params[(layer == 1 ? W_SA1_FC1_W : (layer == 2 ? W_SA2_FC1_W : W_SA3_FC1_W))].off;
+        a.raw = c->raw; a.fc1_w = g_params[sa_base(layer)].off;
         a.scale_rel = c->scale_rel; a.pj = S + L.pj; a.gpart = S + L.gpart; a.n_gpart = sa_vg(c);
         a.img = c->packed[PL_SA1 + layer - 1]; a.timg = c->packed[PL_TSA1 + layer - 1];
         if (layer == 3) { a.dout_a = S + L.dxs_a; a.dout_b = S + L.dxs_b; a.dout_x30 = d_xs_extra; }
@@ -3681,9 +3666,6 @@ int genie_train_bwd(genie_ctx* c, const float* slice, const float* mask, const f
     return da_train_bwd_impl(c, slice, mask, edge_attr, save, d_r_scratch, front_scratch, grad_blob, stream, false);
 }
 
-
-
-
 int genie_where_am_i(int32_t* out_dev, int n_blocks, void* stream) {
     if (!out_dev || n_blocks < 1) return fail(GENIE_ERR_ARG, "genie_where_am_i: bad argument");
     k_where_am_i<<<n_blocks, 64, 0, (hipStream_t)stream>>>(out_dev);
@@ -3697,7 +3679,6 @@ int genie_set_tail_grid(genie_ctx* c, int readout_workgroups, int sa_workgroups)
     c->tail_cu_sa = sa_workgroups > 0 ? sa_workgroups : c->num_cu * 2;
     return GENIE_OK;
 }
-
 
 size_t genie_assoc_workspace_bytes(const genie_ctx* c) { return c ? sizeof(float) * 3 * 32 * (size_t)c->P : 0; }
 
