@@ -112,6 +112,8 @@ SYMBOLS = [
     ("genie_row_select_count", _c.c_int, [_P, _c.c_int, _c.c_int64, _c.c_float, _c.c_int, _P, _P]),
     ("genie_row_select_fill", _c.c_int, [_P, _c.c_int, _c.c_int64, _c.c_float, _c.c_int, _P, _P, _P, _P, _P]),
     ("genie_peak_distance", _c.c_int, [_P, _c.c_int, _c.c_int64, _P, _P, _c.c_int, _P, _P]),
+    ("genie_band_peaks_count", _c.c_int, [_P, _c.c_int] + [_c.c_int64] * 6 + [_c.c_float, _P, _P, _P]),
+    ("genie_band_peaks_fill", _c.c_int, [_P, _c.c_int] + [_c.c_int64] * 6 + [_c.c_float, _P, _P, _P, _P, _P, _P]),
     ("genie_time_groups_scratch_ints", _c.c_int64, [_c.c_int64]),
     ("genie_time_groups", _c.c_int, [_P, _c.c_int64, _c.c_double, _P, _P, _P]),
     ("genie_local_marching_scratch_bytes", _c.c_size_t, [_c.c_int64]),

@@ -151,6 +151,117 @@ def window_parallel_info(cols, n_cols, world):
             "exact_merge": bool(per_col.max(initial=0) <= 2)}
 
 
+def window_band_plan(cols, n_cols, world, margin=1, n_rows=1, tsteps_abs=None, times=None):
+    """The column bands of a window-parallel run that keeps `Out_2` distributed (`merge="columns"`), on the host, from the `cols` table
+    of ALL windows (`window_cols_table`, [n, T], -1 = no column) -- next to `window_parallel_info`, which describes the dense merge. A
+    dict of per-rank lists:
+    * `own` [(o_lo, o_hi)]: half-open ranges that partition [0, n_cols). The cut between two ranks is the first column of the later
+      rank's first window; rank 0 starts at 0, the last rank with windows ends at n_cols, a rank without windows owns the empty range
+      (n_cols, n_cols) (rank 0 owns the whole axis of a day without windows). A rank reports the peaks whose column it owns.
+    * `band` [(b_lo, b_hi)]: what the rank allocates, the hull of the columns its own windows feed and of [o_lo - margin, o_hi +
+      margin), clipped to the axis: a peak needs its two neighbours, a flat top its whole extent (`postproc.detect_sources_banded`).
+    * `recv`, `send` [[(peer, c_lo, c_hi)]]: the strips of columns inside a rank's band that another rank's windows feed (the peer's
+      fed range cut to the band), each listed in the receiver's `recv` and in the feeder's `send`, ascending by peer.
+    * `band_bytes`, `strip_bytes` (received), `dense_bytes`: fp32 bytes per rank for `n_rows` rows of `Out_2` -- the band and its
+      strips against the full-size matrix every rank allocates and all-reduces under `merge="dense"`.
+    Plus `world`, `margin`, `n_cols`, `windows` (`window_blocks`) and `fed` [(c_min, c_max) or None].
+    The cuts need windows whose columns ascend: `tsteps_abs` and `times` (checked with `is_ascending` when given, as the window starts'
+    first columns always are) must ascend; otherwise a ValueError points to `merge="dense"`, which needs no order."""
+    cols = np.asarray(cols).astype(np.int64)
+    n_cols, world, margin = int(n_cols), int(world), int(margin)
+    if margin < 1:
+        raise ValueError("window_band_plan: margin must be >= 1 (a peak needs both neighbours)")
+    n = cols.shape[0]
+    big = np.iinfo(np.int64).max
+    first = np.where(cols >= 0, cols, big).min(axis=1) if n else np.zeros(0, dtype=np.int64)
+    last = cols.max(axis=1) if n else np.zeros(0, dtype=np.int64)
+    if not (all(is_ascending(a) for a in (first, last) + tuple(x for x in (tsteps_abs, times) if x is not None))
+            and (first < big).all() and (n == 0 or last.max() < n_cols)):
+        raise ValueError('window_band_plan: the column bands need an ascending tsteps_abs and ascending window times (every window '
+                         'inside the axis); use merge="dense" for a day whose windows are not ordered along the axis')
+    blocks = window_blocks(n, world)
+    fed = [(int(first[lo]), int(last[hi - 1])) if hi > lo else None for lo, hi in blocks]
+    cuts = [0 if r == 0 else (fed[r][0] if fed[r] is not None else n_cols) for r in range(world)] + [n_cols]
+    own = [(cuts[r], cuts[r + 1]) for r in range(world)]
+    band = []
+    for r in range(world):
+        lo, hi = own[r][0] - margin, own[r][1] + margin
+        if fed[r] is not None:
+            lo, hi = min(lo, fed[r][0]), max(hi, fed[r][1] + 1)
+        band.append((max(lo, 0), min(hi, n_cols)))
+    recv, send = [[] for _ in range(world)], [[] for _ in range(world)]
+    for r in range(world):
+        for p in range(world):
+            if p != r and fed[p] is not None:
+                c_lo, c_hi = max(band[r][0], fed[p][0]), min(band[r][1], fed[p][1] + 1)
+                if c_hi > c_lo:
+                    recv[r].append((p, c_lo, c_hi))
+                    send[p].append((r, c_lo, c_hi))
+    row = 4 * int(n_rows)
+    return {"world": world, "margin": margin, "n_cols": n_cols, "windows": blocks, "fed": fed, "own": own, "band": band, "recv": recv,
+            "send": send, "band_bytes": [row * (hi - lo) for lo, hi in band],
+            "strip_bytes": [row * sum(c_hi - c_lo for _, c_lo, c_hi in strips) for strips in recv], "dense_bytes": [row * n_cols] * world}
+
+
+class BandedOut2(object):
+    """This rank's column band of a window-parallel day's `Out_2` (`apply_windows_device` / `apply_windows_legs` with
+    `merge="columns"`): `band` = the fp32 device tensor [Q, b_hi - b_lo] of the global columns [b_lo, b_hi), of which this rank OWNS
+    [o_lo, o_hi) of the `n_cols` of the axis (`window_band_plan`, kept whole in `plan`, this rank being `rank`). `complete`: the other
+    ranks' strips have been added, so every column of the band holds the day's full sum; until then it holds this rank's windows only
+    (tuple form: the caller exchanges the strips of `plan["recv"][rank]` itself and calls `add_strips`). `group`, `timeout`: the process
+    group the strips came over (True: the default group), or None. `postproc.detect_sources_banded` takes it in place of the dense `Out_2`."""
+
+    def __init__(self, band, rank, plan, complete=False, group=None, timeout=60.0):
+        self.band, self.rank, self.plan, self.complete, self.group, self.timeout = band, int(rank), plan, bool(complete), group, float(timeout)
+        (self.b_lo, self.b_hi), (self.o_lo, self.o_hi) = plan["band"][self.rank], plan["own"][self.rank]
+        self.n_cols = plan["n_cols"]
+
+    def strip(self, c_lo, c_hi):
+        """The band's global columns [c_lo, c_hi) (a view): what this rank sends for an entry (peer, c_lo, c_hi) of its `send` list."""
+        if not self.b_lo <= c_lo <= c_hi <= self.b_hi:
+            raise ValueError("BandedOut2.strip: [%d, %d) is not inside the band [%d, %d)" % (c_lo, c_hi, self.b_lo, self.b_hi))
+        return self.band[:, c_lo - self.b_lo:c_hi - self.b_lo]
+
+    def add_strips(self, strips):
+        """Complete the band: `strips` = {peer: tensor [Q, c_hi - c_lo]} for every entry of `plan["recv"][rank]`, each that peer's own
+        (not yet completed) columns. A column's contributions are added in ascending rank order, this rank's own among them, `((p_a +
+        p_b) + p_c)`, from zero as a rank-ordered sum of dense partials runs; a rank that does not feed a column adds nothing. The
+        result is therefore a fixed function of the ranks' partials for any world size, and the dense all-reduce's wherever its own
+        order does not matter (`exact_merge`)."""
+        if self.complete:
+            raise ValueError("BandedOut2.add_strips: the band is complete already")
+        recv = self.plan["recv"][self.rank]
+        if sorted(strips) != [p for p, _, _ in recv]:
+            raise ValueError("BandedOut2.add_strips: strips of the peers %s expected" % [p for p, _, _ in recv])
+        lower = [e for e in recv if e[0] < self.rank]
+        if len(lower) > 1:       # (p_a + p_b) first, then this rank's part: fp32 addition commutes but does not associate
+            lo, hi = min(e[1] for e in lower), max(e[2] for e in lower)
+            acc = torch.zeros((self.band.shape[0], hi - lo), dtype=self.band.dtype, device=self.band.device)
+            for p, c_lo, c_hi in lower:
+                acc[:, c_lo - lo:c_hi - lo] += strips[p]
+            mine = self.strip(lo, hi)
+            torch.add(acc, mine, out=mine)
+        for p, c_lo, c_hi in (lower if len(lower) == 1 else []) + [e for e in recv if e[0] > self.rank]:
+            self.strip(c_lo, c_hi).add_(strips[p])
+        self.complete = True
+        return self
+
+    def dense(self):
+        """The full-size matrix [Q, n_cols] with this band in place and zeros elsewhere (for tests and callers that want it: it is what
+        `merge="columns"` avoids)."""
+        out = torch.zeros((self.band.shape[0], self.n_cols), dtype=self.band.dtype, device=self.band.device)
+        out[:, self.b_lo:self.b_hi] = self.band
+        return out
+
+    def own_dense(self):
+        """The full-size matrix with this rank's OWN columns only: the ranks' `own_dense()` of completed bands add up to the day's
+        `Out_2` with one non-zero term per element (the dense fallback of `postproc.detect_sources_banded`)."""
+        out = torch.zeros((self.band.shape[0], self.n_cols), dtype=self.band.dtype, device=self.band.device)
+        if self.o_hi > self.o_lo:
+            out[:, self.o_lo:self.o_hi] = self.strip(self.o_lo, self.o_hi)
+        return out
+
+
 def picks_in_embed_range(pick_times_sorted, t0, max_t, kernel_sig_t):
     """[lo, hi) of the picks with t0 - 2 sigma < t < t0 + max_t + 2 sigma (process_utils.py:476); the reference skips a window
     whose range is empty (process_continuous_days.py:792-793)."""
@@ -233,7 +344,7 @@ def apply_windows(net, geom, P, tsteps_abs=None, t_win=6.0, step_size="half", mi
 def apply_windows_device(net, geom, P, trv_times, tsteps_abs=None, t_win=6.0, step_size="half", min_required_picks=1,
                          n_grids=1.0, day_len=86400.0, kernel_sig_t=synthetic.KERNEL_SIG_T, dt_embed=None, max_t=None,
                          times=None, tail_batch=16, pairs=None, stack_on_device=False, window_parallel=None, return_info=False,
-                         merge_timeout=60.0):
+                         merge_timeout=60.0, merge="dense"):
     """GPU-only apply loop: `P` [n,5] (t, station index in the model's station order, amp, prob, phase) sorted by time,
     `trv_times` [G, S, 2] theoretical travel times; `pairs` [2, N] (station, source) = the product nodes of a `use_subgraph` model
     (`A_src_in_sta`), whose Slice / Mask rows follow that list. Returns (Out_2 on device, window start times used). `tail_batch`: windows
@@ -258,7 +369,18 @@ def apply_windows_device(net, geom, P, trv_times, tsteps_abs=None, t_win=6.0, st
     `return_info`: a third return value, `window_parallel_info` of this run plus `rank` (its `exact_merge` tells whether the merged
     bits are independent of the collective's reduction order). A source-sharded model cannot be combined with `window_parallel`.
     No multi-GPU speed-up has been measured: ranks sharing one GPU say nothing about it, and the first run on N > 1 GPUs is still ahead
-    (DESIGN.md section 9.1)."""
+    (DESIGN.md section 9.1).
+
+    `merge`: "dense" (the default) is everything above. "columns" (needs `window_parallel`, an ascending `tsteps_abs` and ascending
+    `times`) keeps `Out_2` distributed: the rank allocates and stacks into its column band [Q, b_hi - b_lo] of `window_band_plan` only
+    (the column table shifted by b_lo on the host, the stacking kernel unchanged), and the first return value is a `BandedOut2`.
+    * tuple form: nothing is exchanged; the band holds this rank's windows (`complete` False), the plan lists the strips to exchange.
+    * group form: after the day's one synchronisation the strips of the plan travel once, device to device over "nccl", staged
+      through the host over gloo (`merge_timeout`), and are added in ascending rank order (`BandedOut2.add_strips`): every rank's band
+      then holds the full sums of its columns, a fixed function of the ranks' partials that equals the dense all-reduce wherever
+      `exact_merge` holds. `postproc.detect_sources_banded` (or `detect_refine_associate`) takes the `BandedOut2` from there.
+    Not yet run on hardware: the device-to-device strip exchange between two or more GPUs (`batch_isend_irecv` over RCCL). What has run
+    is the exchange over gloo between processes sharing one GPU and a one-rank RCCL group, which exchanges nothing."""
     sharded = getattr(net, "is_sharded", False)       # source-node-sharded model: this rank embeds and runs its owned + halo rows only;
     wp = _rank_split(window_parallel, "window_parallel", sharded)
     net.window_batch = 1 if sharded else tail_batch   # the tail follows the shard's all-gather, one per window (module.py docstring)
@@ -266,7 +388,7 @@ def apply_windows_device(net, geom, P, trv_times, tsteps_abs=None, t_win=6.0, st
     dt_embed = _dt_embed(kernel_sig_t, dt_embed)
     Ps = P[np.argsort(P[:, 0], kind="stable")]
     plan = _day_plan(Ps[:, 0], max_t, day_len, t_win, step_size, min_required_picks, tsteps_abs, times, kernel_sig_t, n_grids, wp,
-                     return_info)                     # (host only: a bad schedule argument raises before anything is uploaded)
+                     return_info, merge)              # (host only: a bad schedule argument raises before anything is uploaded)
     lane = GridLeg(net, geom.x_grid, trv_times, pairs=pairs)
     dev = lane.device
     ph = Ps[:, 4].astype(np.int32)
@@ -274,23 +396,29 @@ def apply_windows_device(net, geom, P, trv_times, tsteps_abs=None, t_win=6.0, st
         ph = np.zeros_like(ph)
     picks = types.SimpleNamespace(t_host=Ps[:, 0], t=torch.from_numpy(Ps[:, 0].copy()).to(dev),
                                   sta=torch.from_numpy(Ps[:, 1].astype(np.int32)).to(dev), phase=torch.from_numpy(ph).to(dev))
-    Out_2 = torch.zeros((geom.x_query.shape[0], len(plan.tsteps_abs)), dtype=torch.float32, device=dev)
+    Out_2 = torch.zeros((geom.x_query.shape[0], plan.width), dtype=torch.float32, device=dev)
     xq = torch.from_numpy(geom.x_query).float().to(dev)
     add = _fused_add(plan, Out_2) if stack_on_device or wp is not None else _torch_add(plan, Out_2)
     return _run_day(plan, [lane], picks, xq, Out_2, add, dt_embed, merge_timeout)
 
 
 _DayPlan = collections.namedtuple(
-    "_DayPlan", "tsteps_abs offsets times lo hi all_times drop_last h_cols divisor scale info max_t kernel_sig_t split")
+    "_DayPlan", "tsteps_abs offsets times lo hi all_times drop_last h_cols divisor scale info max_t kernel_sig_t split bands width")
 
 
-def _day_plan(t_sorted, max_t, day_len, t_win, step_size, min_required_picks, tsteps_abs, times, kernel_sig_t, n_grids, split, return_info):
+def _day_plan(t_sorted, max_t, day_len, t_win, step_size, min_required_picks, tsteps_abs, times, kernel_sig_t, n_grids, split, return_info,
+              merge="dense"):
     """What a day's apply loop knows before its first launch, host arithmetic on small arrays: the schedule (`_day_schedule` of the
     time-sorted pick times `t_sorted`, or the caller's `tsteps_abs` / `times`); per kept window the range [lo, hi) of the picks its
     embedding reads (a window whose range is empty is dropped); this rank's block of them under `split` (a `_RankSplit` or None;
     `all_times`: every rank's); `h_cols` = the block's `window_cols_table` (-1: an offset that adds nothing), of which a flush takes its
     rows; `divisor` = n_overlap * `n_grids` and `scale`, its fp32 reciprocal; `info` (`return_info`) = `window_parallel_info` plus
-    `rank`."""
+    `rank`. `merge` "columns": `bands` = `window_band_plan` of all windows, `width` = this rank's band (otherwise None and the
+    whole axis) and `h_cols` counts from the band's first column, so that the loop stacks into the band as it would into `Out_2`."""
+    if merge not in ("dense", "columns"):
+        raise ValueError('merge must be "dense" or "columns"')
+    if merge == "columns" and split is None:
+        raise ValueError('merge="columns" splits Out_2 over the ranks of window_parallel: pass window_parallel=')
     tsteps_abs, times, offsets, n_overlap = _day_schedule(t_sorted.reshape(-1, 1), max_t, day_len, t_win, step_size, min_required_picks,
                                                           tsteps_abs, times)
     drop_last = step_size == "half"
@@ -299,17 +427,25 @@ def _day_plan(t_sorted, max_t, day_len, t_win, step_size, min_required_picks, ts
     nonempty = hi > lo                                                                             # process_continuous_days.py:792-793
     times, lo, hi = times[nonempty], lo[nonempty], hi[nonempty]
     asc = is_ascending(tsteps_abs)
-    all_times, info = times, None
-    if return_info:                                     # (the table of ALL windows: a rank's loop needs its own block's rows only)
+    all_times, info, bands, width = times, None, None, len(tsteps_abs)
+    if return_info or merge == "columns":               # (the table of ALL windows: a rank's loop needs its own block's rows only)
         rank, world = (split.rank, split.world) if split is not None else (0, 1)
-        info = dict(window_parallel_info(window_cols_table(tsteps_abs, times, offsets, drop_last, asc), len(tsteps_abs), world), rank=rank)
+        table = window_cols_table(tsteps_abs, times, offsets, drop_last, asc)
+        if return_info:
+            info = dict(window_parallel_info(table, len(tsteps_abs), world), rank=rank)
+        if merge == "columns":
+            bands = window_band_plan(table, len(tsteps_abs), world, tsteps_abs=tsteps_abs, times=times)
+            width = bands["band"][rank][1] - bands["band"][rank][0]
     if split is not None:                               # this rank's contiguous block of the final window list
         b_lo, b_hi = window_blocks(len(times), split.world)[split.rank]
         times, lo, hi = times[b_lo:b_hi], lo[b_lo:b_hi], hi[b_lo:b_hi]
     h_cols = window_cols_table(tsteps_abs, times, offsets, drop_last, asc)
+    if bands is not None:
+        h_cols = np.where(h_cols >= 0, h_cols - bands["band"][split.rank][0], -1).astype(np.int32)
     divisor = n_overlap * n_grids
     scale = float(np.float32(1.0) / np.float32(divisor))       # `tensor / host scalar` in torch: times the fp32 reciprocal
-    return _DayPlan(tsteps_abs, offsets, times, lo, hi, all_times, drop_last, h_cols, divisor, scale, info, max_t, kernel_sig_t, split)
+    return _DayPlan(tsteps_abs, offsets, times, lo, hi, all_times, drop_last, h_cols, divisor, scale, info, max_t, kernel_sig_t, split, bands,
+                    width)
 
 
 def _fused_add(plan, Out_2):
@@ -397,10 +533,42 @@ def _run_day(plan, lanes, picks, xq, Out_2, add, dt_embed, merge_timeout):
     for lane in lanes:
         _check_verdicts(lane.net)
     split = plan.split
-    if split is not None and split.collective:        # group form: one all-reduce of the ranks' partials; every rank gets the day
+    if plan.bands is not None:                        # merge="columns": the band stays where it is; only the strips travel
+        group = (True if split.group is None else split.group) if split.collective else None      # (True: the default group)
+        Out_2 = BandedOut2(Out_2, split.rank, plan.bands, group=group, timeout=merge_timeout)
+        if split.collective:
+            Out_2.add_strips(_exchange_strips(Out_2, split.group, merge_timeout))
+            times = plan.all_times
+    elif split is not None and split.collective:      # group form: one all-reduce of the ranks' partials; every rank gets the day
         _merge_partials(Out_2, split.group, merge_timeout)
         times = plan.all_times
     return (Out_2, times) if plan.info is None else (Out_2, times, plan.info)
+
+
+def _exchange_strips(banded, group, timeout):
+    """{peer: strip} for `BandedOut2.add_strips`: this rank's `send` strips of the band plan go out and its `recv` strips come in, one
+    message per (sender, receiver) pair -- device to device over RCCL ("nccl", one batch of point-to-point operations), staged through
+    host memory over gloo, where every wait ends after `timeout` seconds, as `_merge_partials` stages its all-reduce."""
+    import datetime
+    import torch.distributed as dist
+    recv, send = banded.plan["recv"][banded.rank], banded.plan["send"][banded.rank]
+    on_device = dist.get_backend(group) == "nccl"
+    where = banded.band.device if on_device else torch.device("cpu")
+    rows = banded.band.shape[0]
+    peer_rank = lambda p: dist.get_global_rank(group, p) if group is not None else p
+    inbox = {p: torch.empty((rows, c_hi - c_lo), dtype=banded.band.dtype, device=where) for p, c_lo, c_hi in recv}
+    outbox = [(p, banded.strip(c_lo, c_hi).contiguous().to(where)) for p, c_lo, c_hi in send]
+    if on_device:
+        ops = [dist.P2POp(dist.irecv, inbox[p], peer_rank(p), group) for p, _, _ in recv]
+        ops += [dist.P2POp(dist.isend, t, peer_rank(p), group) for p, t in outbox]
+        for work in (dist.batch_isend_irecv(ops) if ops else []):
+            work.wait()
+        return inbox
+    works = [dist.irecv(inbox[p], src=peer_rank(p), group=group) for p, _, _ in recv]
+    works += [dist.isend(t, dst=peer_rank(p), group=group) for p, t in outbox]
+    for work in works:
+        work.wait(datetime.timedelta(seconds=float(timeout)))
+    return {p: t.to(banded.band.device) for p, t in inbox.items()}
 
 
 def _merge_partials(Out_2, group, timeout):
@@ -690,7 +858,7 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
 
 def apply_windows_legs(legs, picks, x_query_cart, locs_cart, max_t, tsteps_abs=None, t_win=6.0, step_size="half", min_required_picks=1,
                        day_len=86400.0, kernel_sig_t=synthetic.KERNEL_SIG_T, dt_embed=None, times=None, tail_batch=16,
-                       window_parallel=None, return_info=False, merge_timeout=60.0):
+                       window_parallel=None, return_info=False, merge_timeout=60.0, merge="dense"):
     """The day's apply loop over several source grids into ONE `Out_2` (process_continuous_days.py:761-810, `for n in times_need: for
     x_grid_ind in x_grid_ind_list:`): every kept window runs on every leg of `legs` (`GridLeg`s, `use_subgraph` ones made with `pairs=`
     included; at most `engine.STACK_MAX_LEGS`, every leg with a model of its own), and all of them add into the same `Out_2`
@@ -716,7 +884,8 @@ def apply_windows_legs(legs, picks, x_query_cart, locs_cart, max_t, tsteps_abs=N
     GPU on the default 'half' schedule, unlike the single-grid loop: a boundary column then has 2 L terms, split L | L, and two rounded
     sums of L terms added are not the running sum of 2 L. `return_info`: `window_parallel_info` of the run plus `rank`; its
     `exact_merge` keeps its meaning, independence from the order in which the collective adds the ranks. A source-node-sharded leg is
-    refused (batched tails do not run on shards). No multi-GPU wall time has been measured."""
+    refused (batched tails do not run on shards). No multi-GPU wall time has been measured. `merge="columns"`: as in
+    `apply_windows_device` -- this rank's column band only, returned as a `BandedOut2`; the "dense" default is unchanged."""
     legs = list(legs)
     if not legs:
         raise ValueError("apply_windows_legs: no grid leg")
@@ -739,11 +908,11 @@ def apply_windows_legs(legs, picks, x_query_cart, locs_cart, max_t, tsteps_abs=N
     if len(picks) == 0:
         raise ValueError("apply_windows_legs: no pick of the model's stations")
     plan = _day_plan(picks.t_host, float(max_t), day_len, t_win, step_size, min_required_picks, tsteps_abs, times, kernel_sig_t, len(legs), wp,
-                     return_info)
+                     return_info, merge)
     for leg in legs:
         leg.net.window_batch = tail_batch
     xq = torch.as_tensor(x_query_cart).float().to(dev)
-    Out_2 = torch.zeros((xq.shape[0], len(plan.tsteps_abs)), dtype=torch.float32, device=dev)
+    Out_2 = torch.zeros((xq.shape[0], plan.width), dtype=torch.float32, device=dev)
     return _run_day(plan, legs, picks, xq, Out_2, _fused_add(plan, Out_2), _dt_embed(kernel_sig_t, dt_embed), merge_timeout)
 
 
@@ -932,7 +1101,9 @@ def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, 
     first marching), `srcs_refined` [m, 5], `trv_out_srcs` (device [m, S, 2]), `Out_p_save`, `Out_s_save` (lists of device tensors),
     `Save_picks`, `lp_meta` (lists of host arrays) -- the inputs of `competitive_assignment`, which is out of scope.
     `detect_on_device`: both LocalMarchings, the distance rule and the grouping run on the GPU (`postproc.detect_sources_device`,
-    `retained_after_marching(device=...)`) instead of on the host; the sources are the same.
+    `retained_after_marching(device=...)`) instead of on the host; the sources are the same. `Out_2` may then be the `BandedOut2` of a
+    window-parallel day run with `merge="columns"` (group form): detection goes through `postproc.detect_sources_banded`, same dict plus
+    `detect_info`, that call's info (`detect_info["fallback"]` says whether the day fell back to the dense merge, and why).
     `source_parallel`: the two per-source passes split over GPUs (`refine_sources`, `associate_sources`: a process group, True for
     the default one, or `(rank, world)` -- which, having no transport, must have world 1 here). Detection, both LocalMarchings and the
     `trv` calls are cheap and deterministic and run replicated on every rank; the returned dict equals the one-GPU dict on every rank."""
@@ -947,9 +1118,17 @@ def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, 
     empty = {"srcs": np.zeros((0, 5)), "srcs_refined": np.zeros((0, 5)), "trv_out_srcs": None, "Out_p_save": [], "Out_s_save": [],
              "Save_picks": [], "lp_meta": []}
     detect = postproc.detect_sources_device if detect_on_device else postproc.detect_sources
+    banded = isinstance(Out_2, BandedOut2)
+    if banded and not detect_on_device:
+        raise ValueError("detect_refine_associate: a BandedOut2 is detected on the device (detect_on_device=True)")
+    detect_info = {}                              # a banded day's info (its `fallback` above all) goes into the returned dict
+    if banded:
+        detect = postproc.detect_sources_banded
     srcs = detect(Out_2, X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_win, break_win, tc_win, sp_win, scale_depth_clustering)
+    if banded:
+        srcs, detect_info = srcs[0], {"detect_info": srcs[1]}
     if len(srcs) == 0:
-        return empty                                                                                                    # :886-888
+        return dict(empty, **detect_info)                                                                               # :886-888
     locs = np.asarray(locs, dtype=np.float64)
     locs_cart = ftrns1(locs)
     locs_d = torch.as_tensor(locs).float().to(dev)
@@ -968,6 +1147,6 @@ def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, 
         trv_kept = trv(locs_d, torch.as_tensor(srcs_kept[:, 0:3]).float().to(dev)).detach()                             # :1092
     order = np.argsort(srcs_kept[:, 3])                                                                                 # :1097
     pick = [int(keep[j]) for j in order]
-    return {"srcs": srcs, "srcs_refined": srcs_kept[order], "trv_out_srcs": trv_kept[torch.as_tensor(order, device=trv_kept.device)],
-            "Out_p_save": [Out_p[j] for j in pick], "Out_s_save": [Out_s[j] for j in pick],
-            "Save_picks": [Save_picks[j] for j in pick], "lp_meta": [lp_meta[j] for j in pick]}
+    return dict({"srcs": srcs, "srcs_refined": srcs_kept[order], "trv_out_srcs": trv_kept[torch.as_tensor(order, device=trv_kept.device)],
+                 "Out_p_save": [Out_p[j] for j in pick], "Out_s_save": [Out_s[j] for j in pick],
+                 "Save_picks": [Save_picks[j] for j in pick], "lp_meta": [lp_meta[j] for j in pick]}, **detect_info)

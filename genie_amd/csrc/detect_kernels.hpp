@@ -237,3 +237,100 @@ __global__ __launch_bounds__(256) void k_local_marching_keep(const float* __rest
     const bool same = fabsf(__fsub_rn(v0, v)) <= __fadd_rn(1e-8f, __fmul_rn(tol, fabsf(v)));
     keep[i] = (!active[i] || same) ? 1 : 0;
 }
+
+// ------------------------------------------------------------------------------------------------
+// (d) Peak candidates of a column BAND of Out_2 (`postproc.detect_sources_banded`): what k_row_select MODE 1 finds on the full matrix,
+// restricted to the peaks whose reported column lies in the caller's OWN range [o_lo, o_hi). band [rows, width] (row stride `stride`)
+// holds the global columns [b_lo, b_lo + width) of an axis of n_cols columns. A peak is a maximal run of equal values >= thr whose two
+// outer neighbours are lower, reported at the run's midpoint (start + end) / 2; a run that contains global column 0 or n_cols - 1 has
+// no outer neighbour there and is no peak (scipy `_local_maxima_1d`). The ranks' own ranges partition the axis, so of all the bands
+// that see a run exactly one reports it.
+// A run that touches an end of the band which is not an end of the axis may go on outside: its start (its end) is then only bounded,
+// start in [1, b_lo] (end in [b_hi - 1, n_cols - 2]). If the neighbour on the known side is lower and some admissible midpoint falls
+// into the own range, the band cannot decide the peak: *flag is set and nothing is reported for that run (the caller falls back to the
+// dense merge). If no admissible midpoint is the caller's, the run is another rank's in every case and is passed over in silence (so a rank
+// whose own range is empty reports nothing and never sets the flag).
+// One wave per row walks it in chunks of 64 columns, one coalesced load per chunk; the neighbours come from the adjacent lanes
+// (lane 0's from the chunk before, lane 63's by one load of the next column), a run's start from a ballot of the lanes where the
+// value changes, or from the wave-uniform carry when the run began in an earlier chunk. Peaks are decided at the run's END lane, so
+// they come out in ascending column order. bp_chunk is the one decision both passes make: COUNT adds up its ballots, FILL ranks them.
+// ------------------------------------------------------------------------------------------------
+constexpr int BP_ROWS_PER_BLOCK = 4;
+struct BpGeom { long long width, b_lo, o_lo, o_hi, n_cols; float thr; };
+struct BpCarry { float last; long long start; bool rise; };       // wave-uniform: the previous column's value, the open run's start
+
+__device__ __forceinline__ bool bp_chunk(const float* __restrict__ xr, long long c0, int lane, const BpGeom& g, BpCarry& carry,
+                                         long long* col, float* val, bool* undecided) {
+    const long long j = c0 + lane;
+    const bool valid = j < g.width;
+    const float v = valid ? xr[j] : 0.f;
+    float left = __shfl_up(v, 1);
+    if (lane == 0) left = carry.last;
+    float right = __shfl_down(v, 1);
+    if (lane == 63 && j + 1 < g.width) right = xr[j + 1];
+    const bool brk = valid && (j == 0 || left != v);                         // a run starts here
+    const bool rise = valid && j > 0 && left < v;
+    const unsigned long long bm = __ballot(brk), rm = __ballot(rise);
+    bool sel = false, und = false;
+    if (valid && v >= g.thr && (j == g.width - 1 || right != v)) {            // the end of a run that reaches the threshold
+        const unsigned long long below = bm & ((2ull << lane) - 1ull);
+        long long s = carry.start;
+        bool rising = carry.rise;
+        if (below) {
+            const int ls = 63 - __clzll(below);
+            s = c0 + ls;
+            rising = (rm >> ls) & 1ull;
+        }
+        const bool left_known = s > 0, right_known = j < g.width - 1;
+        const bool left_ok = left_known ? rising : g.b_lo > 0;                // lower on the left, or possibly so
+        const bool right_ok = right_known ? right < v : g.b_lo + g.width < g.n_cols;
+        if (left_ok && right_ok) {
+            const long long gs = g.b_lo + s, ge = g.b_lo + j;
+            const long long m_lo = ((left_known ? gs : 1) + ge) / 2;          // the admissible midpoints, inclusive
+            const long long m_hi = (gs + (right_known ? ge : g.n_cols - 2)) / 2;
+            const bool mine = g.o_lo < g.o_hi && m_hi >= g.o_lo && m_lo < g.o_hi;    // (an empty own range has no midpoint)
+            sel = mine && left_known && right_known;                           // (then m_lo == m_hi)
+            und = mine && !(left_known && right_known);
+            *col = m_lo;
+        }
+    }
+    *val = v;
+    *undecided = und;
+    carry.last = __shfl(v, 63);
+    if (bm) {
+        const int ls = 63 - __clzll(bm);
+        carry.start = c0 + ls;
+        carry.rise = (rm >> ls) & 1ull;
+    }
+    return sel;
+}
+
+template <bool COUNT>
+__global__ __launch_bounds__(256) void k_band_peaks(const float* __restrict__ band, int rows, long long stride, BpGeom g,
+                                                    int32_t* __restrict__ counts, const long long* __restrict__ offsets,
+                                                    int32_t* __restrict__ out_row, int32_t* __restrict__ out_col,
+                                                    float* __restrict__ out_val, int32_t* flag) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * BP_ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* xr = band + row * stride;
+    const long long base = COUNT ? 0 : offsets[row];
+    BpCarry carry{0.f, 0, false};
+    long long total = 0;
+    bool any_und = false;
+    for (long long c0 = 0; c0 < g.width; c0 += 64) {
+        long long col = 0;
+        float val;
+        bool und;
+        const bool sel = bp_chunk(xr, c0, lane, g, carry, &col, &val, &und);
+        const unsigned long long b = __ballot(sel);
+        if (!COUNT && sel) {
+            const long long o = base + total + __popcll(b & ((1ull << lane) - 1ull));
+            out_row[o] = (int32_t)row; out_col[o] = (int32_t)col; out_val[o] = val;
+        }
+        total += __popcll(b);
+        any_und |= und;
+    }
+    if (COUNT && lane == 0) counts[row] = (int32_t)total;
+    if (__any(any_und) && lane == 0) atomicOr(flag, 1);
+}

@@ -3945,6 +3945,46 @@ int genie_peak_distance(const int64_t* offsets, int rows, int64_t n, const int32
     return GENIE_OK;
 }
 
+namespace {
+const char* band_peaks_bad(const float* band, int rows, int64_t width, int64_t stride, int64_t b_lo, int64_t o_lo, int64_t o_hi,
+                           int64_t n_cols, const int32_t* flag) {
+    if (rows < 0 || width < 0 || stride < width || n_cols < 0 || n_cols >= (1ll << 31)) return "rows, width >= 0, stride >= width and n_cols < 2^31 required";
+    if (b_lo < 0 || b_lo + width > n_cols) return "the band [b_lo, b_lo + width) must lie inside [0, n_cols)";
+    if (o_lo < 0 || o_lo > o_hi || o_hi > n_cols) return "0 <= o_lo <= o_hi <= n_cols required";
+    if (o_lo < o_hi && (o_lo < b_lo || o_hi > b_lo + width)) return "a non-empty own range must lie inside the band";
+    if (!flag || (rows > 0 && width > 0 && !band)) return "null argument";
+    return nullptr;
+}
+}  // namespace
+
+int genie_band_peaks_count(const float* band, int rows, int64_t width, int64_t stride, int64_t b_lo, int64_t o_lo, int64_t o_hi,
+                           int64_t n_cols, float threshold, int32_t* counts, int32_t* flag, void* stream) {
+    if (const char* bad = band_peaks_bad(band, rows, width, stride, b_lo, o_lo, o_hi, n_cols, flag))
+        return fail(GENIE_ERR_ARG, std::string("genie_band_peaks_count: ") + bad);
+    if (rows > 0 && !counts) return fail(GENIE_ERR_ARG, "genie_band_peaks_count: null argument");
+    if (rows == 0) return GENIE_OK;
+    const BpGeom g{(long long)width, (long long)b_lo, (long long)o_lo, (long long)o_hi, (long long)n_cols, threshold};
+    const int nb = (rows + BP_ROWS_PER_BLOCK - 1) / BP_ROWS_PER_BLOCK;
+    k_band_peaks<true><<<nb, 256, 0, (hipStream_t)stream>>>(band, rows, (long long)stride, g, counts, nullptr, nullptr, nullptr, nullptr, flag);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+int genie_band_peaks_fill(const float* band, int rows, int64_t width, int64_t stride, int64_t b_lo, int64_t o_lo, int64_t o_hi,
+                          int64_t n_cols, float threshold, const int64_t* offsets, int32_t* out_row, int32_t* out_col, float* out_val,
+                          int32_t* flag, void* stream) {
+    if (const char* bad = band_peaks_bad(band, rows, width, stride, b_lo, o_lo, o_hi, n_cols, flag))
+        return fail(GENIE_ERR_ARG, std::string("genie_band_peaks_fill: ") + bad);
+    if (rows > 0 && (!offsets || !out_row || !out_col || !out_val)) return fail(GENIE_ERR_ARG, "genie_band_peaks_fill: null argument");
+    if (rows == 0) return GENIE_OK;
+    const BpGeom g{(long long)width, (long long)b_lo, (long long)o_lo, (long long)o_hi, (long long)n_cols, threshold};
+    const int nb = (rows + BP_ROWS_PER_BLOCK - 1) / BP_ROWS_PER_BLOCK;
+    k_band_peaks<false><<<nb, 256, 0, (hipStream_t)stream>>>(band, rows, (long long)stride, g, nullptr, (const long long*)offsets, out_row, out_col,
+                                                            out_val, flag);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
 int64_t genie_time_groups_scratch_ints(int64_t n) { return n > 0 ? (n + TG_BLOCK - 1) / TG_BLOCK : 0; }
 
 int genie_time_groups(const double* t, int64_t n, double break_win, int32_t* scratch, int32_t* group, void* stream) {

@@ -15,6 +15,9 @@ What runs where:
   the march stay on the GPU, `ftrns1` is applied once to the query positions on the host, and only the surviving [n, 5] rows come
   back. The host functions are their oracle (equal index sets and rows); they differ only where scipy itself is unspecified: of two
   equal peak heights closer than the distance, the device keeps the later column.
+* `detect_sources_banded` is `detect_sources_device` for a window-parallel day that keeps `Out_2` in column bands (`apply.BandedOut2`):
+  the candidates per band (`genie_band_peaks_*`), one all-gather of the triplets, the other stages replicated; `row_select` on the
+  full matrix is the oracle of the band kernel (equal triplets).
 * `refine_select_device` is the end of the refine pass per candidate source (process_continuous_days.py:972-978): the sum of the grid
   legs' query read-outs, the region mask and the nested first-maximum argmax in one launch pair (`genie_refine_select`,
   csrc/select_kernels.hpp); the torch statements of `apply.refine_sources` it replaces are its oracle (exact, ties included).
@@ -320,6 +323,119 @@ def _sources_from_peaks(r, c, v, X_query, tsteps_abs, ftrns1, break_win, tc_win,
     xq_d = torch.from_numpy(np.ascontiguousarray(xq[:, 0:3])).to(dev)
     srcs = torch.cat((xq_d[r[keep]], t[keep].reshape(-1, 1), v[keep].double().reshape(-1, 1)), dim=1)
     return srcs.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------------
+# Detection from column bands: a window-parallel day whose `Out_2` stays distributed (`apply.BandedOut2`, merge="columns").
+# Only the candidate step of find_peaks is local (a pixel's two neighbours, or the extent of its flat top), so that is what runs per
+# band (genie_band_peaks_*, csrc/detect_kernels.hpp); the distance rule is greedy along a whole row and the time groups and
+# LocalMarching are global, so they run replicated on the gathered triplets, with the kernels above.
+# ------------------------------------------------------------------------------------------------
+BAND_FALLBACK = "flat top at a band edge"
+
+
+def band_peaks(band, b_lo, o_lo, o_hi, n_cols, threshold):
+    """The mode-1 candidates of `row_select` on the full matrix whose column lies in [o_lo, o_hi), found on the column band `band`
+    [rows, width] = the global columns [b_lo, b_lo + width) of an axis of `n_cols` (an fp32 GPU matrix; rows may be strided, columns
+    not). Returns (row int32, GLOBAL col int32, value fp32, exclusive int64 row offsets, flag): GPU tensors, row-major, columns ascending
+    within a row; `flag` (int32 GPU tensor [1]) is non-zero when a flat top reached an end of the band that is not an end of the axis
+    and could not be decided there -- the triplets are then incomplete and must not be used. Own ranges that partition the axis give
+    every candidate of the full matrix exactly once."""
+    if not (torch.is_tensor(band) and band.is_cuda and band.dtype == torch.float32 and band.dim() == 2):
+        raise ValueError("band_peaks: band must be a 2-D fp32 GPU tensor")
+    if band.shape[1] > 1 and band.stride(1) != 1:
+        raise ValueError("band_peaks: the columns of band must be contiguous")
+    lib = _lib.load()
+    rows, width = int(band.shape[0]), int(band.shape[1])
+    stride = int(band.stride(0)) if rows > 1 else width
+    th = np.float32(threshold)                        # `>=` in fp32 as numpy decides it with a float64 threshold (`_row_select_offsets`)
+    if float(th) < float(threshold):
+        th = np.nextafter(th, np.float32(np.inf))
+    geom = (rows, width, stride, int(b_lo), int(o_lo), int(o_hi), int(n_cols), ctypes.c_float(float(th)))
+    dev = band.device
+    with torch.cuda.device(dev):
+        st = _stream(dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        counts = torch.empty(rows, dtype=torch.int32, device=dev)
+        _lib.check(lib.genie_band_peaks_count(_ptr(band), *geom, _ptr(counts), _ptr(flag), st), "genie_band_peaks_count")
+        ends = torch.cumsum(counts.long(), 0)
+        offsets = (ends - counts.long()).contiguous()
+        n = int(ends[-1].item()) if rows else 0
+        out_row = torch.empty(n, dtype=torch.int32, device=dev)
+        out_col = torch.empty(n, dtype=torch.int32, device=dev)
+        out_val = torch.empty(n, dtype=torch.float32, device=dev)
+        if n:
+            _lib.check(lib.genie_band_peaks_fill(_ptr(band), *geom, _ptr(offsets), _ptr(out_row), _ptr(out_col), _ptr(out_val), _ptr(flag),
+                                                 st), "genie_band_peaks_fill")
+    return out_row, out_col, out_val, offsets, flag
+
+
+def detect_sources_banded(banded, X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_win, break_win, tc_win, sp_win,
+                          scale_depth_clustering=0.2, group=None):
+    """`detect_sources_device` of a day whose `Out_2` stays distributed in column bands: `banded` = this rank's completed
+    `apply.BandedOut2` (group form of `merge="columns"`), or the list of ALL ranks' completed bands in rank order (every rank in one
+    process: nothing is gathered). Returns (srcs [n, 5] as `detect_sources_device` returns them, info).
+    * each rank finds the candidates it owns on its band (`band_peaks`);
+    * with a group (`group`, default: the one the band came over; True = the default group) ONE `all_gather_object` carries the ranks'
+      ragged triplets and edge flags through the host, as `apply.associate_sources` moves its ragged lists (a few thousand rows);
+    * the lists are concatenated in rank order (row-major within a rank, not across ranks), sorted once on the device by (row, col),
+      and the distance rule, the time groups and LocalMarching run replicated on the whole list (`_peak_distance_keep`,
+      `_sources_from_peaks`): identical sources on every rank, those of one GPU on the merged `Out_2`.
+    * if any rank's flat top reached a band edge undecided, EVERY rank falls back to the dense merge for this day: the ranks' own
+      columns, one non-zero term per element, are summed into a full-size matrix (`_merge_partials`) and `detect_sources_device`
+      runs on it; `info["fallback"]` is then "flat top at a band edge" (otherwise None).
+    `info` also holds `candidates` (per rank) and `gathered_bytes` (what the all-gather moved per rank)."""
+    from . import apply
+    distance = int(1.5 * src_t_kernel / dt_win)
+    if distance < 1:
+        raise ValueError("`distance` must be greater or equal to 1")
+    if not thresh > 0.01:
+        raise ValueError("detect_sources_banded: thresh must be > 0.01 (the reference's sparsification threshold)")
+    bands = list(banded) if isinstance(banded, (list, tuple)) else [banded]
+    if not bands or not all(isinstance(b, apply.BandedOut2) for b in bands):
+        raise ValueError("detect_sources_banded: an apply.BandedOut2 (or the list of every rank's) expected")
+    first = bands[0]
+    if group is None:
+        group = first.group
+    world = first.plan["world"]
+    if (len(bands) > 1 or group is None) and [b.rank for b in bands] != list(range(world)):
+        raise ValueError("detect_sources_banded: without a process group the bands of all %d ranks are needed, in rank order" % world)
+    for b in bands:
+        if not b.complete and b.plan["recv"][b.rank]:
+            raise ValueError("detect_sources_banded: the band of rank %d still lacks the other ranks' strips (BandedOut2.add_strips)" % b.rank)
+    dev, n_cols, rows = first.band.device, first.n_cols, int(first.band.shape[0])
+    found = [band_peaks(b.band, b.b_lo, b.o_lo, b.o_hi, b.n_cols, thresh) for b in bands]
+    if len(bands) == 1 and world > 1:                                       # one all-gather of (row, col, value, flag) per rank
+        import torch.distributed as dist
+        r, c, v, _, flag = found[0]
+        parts = [None] * world
+        with torch.cuda.device(dev):
+            dist.all_gather_object(parts, (r.cpu().numpy(), c.cpu().numpy(), v.cpu().numpy(), int(flag.item())),
+                                   group=None if group is True else group)
+    else:
+        parts = [(r, c, v, int(flag.item())) for r, c, v, _, flag in found]
+    info = {"fallback": None, "candidates": [int(len(p[0])) for p in parts], "gathered_bytes": [12 * int(len(p[0])) + 4 for p in parts]}
+    args = (X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_win, break_win, tc_win, sp_win, scale_depth_clustering)
+    if any(p[3] for p in parts):                                            # the same decision on every rank: all of them saw all flags
+        info["fallback"] = BAND_FALLBACK
+        dense = bands[0].own_dense()
+        for b in bands[1:]:
+            dense += b.own_dense()
+        if len(bands) == 1 and world > 1:
+            apply._merge_partials(dense, None if group is True else group, first.timeout)
+        return detect_sources_device(dense, *args), info
+    as_dev = lambda a, dt: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dev).to(dt)
+    r = torch.cat([as_dev(p[0], torch.int32) for p in parts])
+    c = torch.cat([as_dev(p[1], torch.int32) for p in parts])
+    v = torch.cat([as_dev(p[2], torch.float32) for p in parts])
+    if r.numel():
+        order = torch.sort(r.long() * int(n_cols) + c.long(), stable=True)[1]
+        r, c, v = r[order].contiguous(), c[order].contiguous(), v[order].contiguous()
+        counts = torch.bincount(r.long(), minlength=rows)
+        offsets = (torch.cumsum(counts, 0) - counts).contiguous()
+        keep = _peak_distance_keep(offsets, c, v, distance)
+        r, c, v = r[keep], c[keep], v[keep]
+    return _sources_from_peaks(r, c, v, X_query, tsteps_abs, ftrns1, break_win, tc_win, sp_win, scale_depth_clustering), info
 
 
 # ------------------------------------------------------------------------------------------------

@@ -571,6 +571,22 @@ size_t genie_local_marching_scratch_bytes(int64_t n);
 int genie_local_marching(const double* xs, const double* t, const float* val, const int32_t* group, int64_t n, double tc_win,
                          double sp_win, int n_steps_max, double tol, int use_directed, void* scratch, uint8_t* keep, void* stream);
 
+/* Peak candidates of a column band of Out_2 (window-parallel days that keep Out_2 distributed, genie_amd/postproc.py::
+ * detect_sources_banded): band [rows, width] fp32 with row stride `stride` (elements) holds the global columns [b_lo, b_lo + width) of an
+ * axis of n_cols columns. Written are the mode-1 peaks of the row selection above -- local maxima >= threshold, flat tops at their
+ * midpoint, never global column 0 or n_cols - 1 -- whose reported column lies in the own range [o_lo, o_hi): triplets (row, GLOBAL column, value),
+ * row-major, columns ascending within a row, the same two passes as the row selection: counts [rows] -> the caller's exclusive int64
+ * offsets [rows] -> fill. Own ranges that partition the axis report every peak of the full matrix exactly once.
+ * A flat top is followed to both of its ends inside the band. One that reaches an end of the band which is not an end of the axis, and
+ * whose midpoint could fall into the own range, cannot be decided from the band: *flag (int32, zeroed by the caller) is then set to 1
+ * and that top is not reported; the caller must not use the triplets of a call that set it. A non-empty own range must lie inside the
+ * band; bad arguments return GENIE_ERR_ARG before any launch. */
+int genie_band_peaks_count(const float* band, int rows, int64_t width, int64_t stride, int64_t b_lo, int64_t o_lo, int64_t o_hi,
+                           int64_t n_cols, float threshold, int32_t* counts, int32_t* flag, void* stream);
+int genie_band_peaks_fill(const float* band, int rows, int64_t width, int64_t stride, int64_t b_lo, int64_t o_lo, int64_t o_hi,
+                          int64_t n_cols, float threshold, const int64_t* offsets, int32_t* out_row, int32_t* out_col, float* out_val,
+                          int32_t* flag, void* stream);
+
 /* The time-pointer tables of the association heads on the device (`assemble_time_pointers_for_stations`, utils.py:602-622, called at
  * train_GENIE_model.py:1364 and process_continuous_days.py:620; genie_amd/graph.py::time_pointers is the host statement): for every
  * station i and every time step t of dt_partition, the k candidates of station i that are smallest under the key
