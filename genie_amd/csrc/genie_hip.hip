@@ -3281,7 +3281,20 @@ constexpr int TR_WPB_LIGHT = 8;
 #endif
 bool b1_split_on() { return GENIE_B1_SPLIT_DEFAULT != 0; }
 int train_grid(const genie_ctx* c) { return std::max(8, c->num_cu * 2 / 8 * 8); }      // 2 workgroups per CU (1: +10 %, 3: +6 %, 4: +1 % step time)
-size_t train_part_floats(const genie_ctx* c) { return (size_t)train_grid(c) * 4 * (30 * 256 + 12 * 16 + 16); }
+// one partial slot of a backward pass (write_partials): n_acc accumulator tiles of 256 floats, n_vec vectors of 16, 16 scalars
+size_t part_stride(int n_acc, int n_vec) { return (size_t)n_acc * 256 + (size_t)n_vec * 16 + 16; }
+size_t part_floats(int n_acc, int n_vec, int n_slots) { return (size_t)n_slots * part_stride(n_acc, n_vec); }
+size_t train_part_floats(const genie_ctx* c) { return part_floats(30, 12, train_grid(c) * 4); }      // the heaviest P-sized pass
+// a pass writes its partials to `part`, shaped by its gradient map `tm`
+extern "C++" template <class Args> void bind_part(Args& a, const genie_ctx* c, int tm, float* part) {
+    a.part = part; a.n_acc = c->tb->n_acc[tm]; a.n_vec = c->tb->n_vec[tm];
+}
+// the `n_slots` partial slots of a pass, summed in slot order through the map `tm` into the gradient blob (set, or added to it)
+void reduce_pass(genie_ctx* c, int tm, const float* part, int n_slots, float* blob, bool accumulate, hipStream_t st) {
+    const int stride = (int)part_stride(c->tb->n_acc[tm], c->tb->n_vec[tm]);
+    k_train_reduce<<<(stride + 31) / 32, 256, 0, st>>>(part, n_slots, c->tb->n_acc[tm], c->tb->n_vec[tm], c->tb->n_sc[tm], c->tb->d_acc[tm], c->tb->d_vec[tm],
+                                                        c->tb->d_sc[tm], blob, accumulate ? 1 : 0);
+}
 // `variants`: the call also serves DataAggregationEdges / use_absolute_pos (the forward_fixed_source step does; the association heads'
 // training step is the default model definition only)
 int train_check(const genie_ctx* c, const char* who, bool variants = false, bool pcsr_ok = false) {
@@ -3389,16 +3402,63 @@ int ensure_reversed(genie_ctx* c) {
     c->r_sta = std::move(sta); c->r_src = std::move(src); c->rp_sta = std::move(psta); c->rp_src = std::move(psrc);
     return GENIE_OK;
 }
-int da_train_bwd_impl(genie_ctx* c, const float* slice, const float* mask, const float* edge_attr, const float* save,
-                      const float* d_r, float* scratch, float* grad_blob, void* stream, bool zero_blob);
-}  // namespace
 
-int genie_da_train_bwd(genie_ctx* c, const float* slice, const float* mask, const float* edge_attr, const float* save,
-                       const float* d_r, float* scratch, float* grad_blob, void* stream) {
-    return da_train_bwd_impl(c, slice, mask, edge_attr, save, d_r, scratch, grad_blob, stream, true);
+// what both P-sized backwards hand their passes: sizes, reversed graphs, kept rows, `gr` and `part` at the head of `scratch`
+int make_tr_args(genie_ctx* c, const float* mask, const float* edge_attr, const float* save, float* scratch, hipStream_t st, TrArgs& a) {
+    memset(&a, 0, sizeof(a));
+    a.S = c->S; a.G = c->G; a.T = c->T; a.seg = std::max(1, c->seg); a.nxcd = 8;
+    a.P = c->P; a.order = c->order;
+    a.r_sta_rowptr = c->r_sta.rowptr; a.r_sta_col = c->r_sta.col; a.r_sta_w = c->r_sta.w;
+    a.r_src_rowptr = c->r_src.rowptr; a.r_src_col = c->r_src.col; a.r_src_w = c->r_src.w;
+    a.r_sta_cw = c->r_sta.cw; a.r_src_cw = c->r_src.cw;
+    a.mask = mask; a.edge_attr = edge_attr; a.save = save;
+    a.gr = scratch; a.part = scratch + (size_t)GR_BLOCKS * 16 * (size_t)c->P;
+    if (c->pcsr) {
+        GENIE_TRY(ensure_src_of(c, st));
+        a.src_of = c->p_src_of; a.ptile = c->ptile16;
+        a.r_sta_rowptr = c->rp_sta.rowptr; a.r_sta_cw = c->rp_sta.cw; a.r_src_rowptr = c->rp_src.rowptr; a.r_src_cw = c->rp_src.cw;
+        a.r_sta_col = a.r_src_col = nullptr; a.r_sta_w = a.r_src_w = nullptr;       // (the PCSR passes read the pair arrays only)
+    }
+    return GENIE_OK;
+}
+// 32-bit row offsets on scalar bases (ldo / sto) while each of the `kept` blocks of kept rows lies below 4 GiB (14: P < 4.79 M; 20: P < 3.35 M)
+bool tr_o32(const genie_ctx* c, int kept) { return !c->pcsr && (unsigned long long)kept * (unsigned long long)c->P * 64ull < (1ull << 32); }
+
+// The launchers of the P-sized passes: each alone names its kernel's instantiations and returns the number of partial slots written (what
+// reduce_pass sums); `grid` = train_grid(c). Pass 1 (AS: the association phase's): k_train_b1 holds one wave per SIMD (442 registers), one
+// workgroup per CU is all that is ever resident; k_train_b1s (two waves per tile, <= 256 registers) runs two and writes one partial per PAIR.
+extern "C++" template <bool AS> int launch_b1(const genie_ctx* c, const TrArgs& a, int grid, bool o32, hipStream_t st) {
+    if (c->pcsr) { k_train_b1p<AS><<<grid, 256, 0, st>>>(a); return grid * 4; }
+    if (o32 && b1_split_on()) { k_train_b1s<AS><<<grid, 256, 0, st>>>(a); return grid * 2; }
+    const int grid1 = std::max(8, grid / 2 / 8 * 8);
+    if (o32) k_train_b1<AS, true><<<grid1, 256, 0, st>>>(a); else k_train_b1<AS><<<grid1, 256, 0, st>>>(a);
+    return grid1 * 4;
+}
+int launch_b2(const genie_ctx* c, const TrArgs& a, int grid, hipStream_t st) {
+    if (c->pcsr) { k_train_b2<true><<<grid, 256, 0, st>>>(a); return grid * 4; }
+    k_train_b2<false, TR_WPB_LIGHT><<<grid, TR_WPB_LIGHT * 64, 0, st>>>(a);
+    return grid * TR_WPB_LIGHT;
+}
+int launch_b0(const genie_ctx* c, const TrArgs& a, int grid, bool o32, hipStream_t st) {
+    if (c->pcsr) k_train_b0<true><<<grid, 256, 0, st>>>(a);
+    else if (o32) k_train_b0<false, true><<<grid, 256, 0, st>>>(a); else k_train_b0<false><<<grid, 256, 0, st>>>(a);
+    return grid * 4;
+}
+int launch_as_b3(const genie_ctx* c, const TrArgs& a, int grid, const float* d_s, hipStream_t st) {
+    if (c->pcsr) k_as_b3<true><<<grid, 256, 0, st>>>(a, d_s, c->raw + g_params[W_AS_ACT2].off);
+    else k_as_b3<false><<<grid, 256, 0, st>>>(a, d_s, c->raw + g_params[W_AS_ACT2].off);
+    return grid * 4;
+}
+int launch_as_b1(const genie_ctx* c, const TrArgs& a, int grid, bool o32, hipStream_t st) {
+    if (c->pcsr) k_as_b1<true><<<grid, 256, 0, st>>>(a);
+    else if (o32) k_as_b1<false, true><<<grid, 256, 0, st>>>(a); else k_as_b1<false><<<grid, 256, 0, st>>>(a);
+    return grid * 4;
+}
+int launch_as_b0(const genie_ctx* c, const TrArgs& a, int grid, hipStream_t st) {
+    if (c->pcsr) k_as_b0<true><<<grid, 256, 0, st>>>(a); else k_as_b0<false><<<grid, 256, 0, st>>>(a);
+    return grid * 4;
 }
 
-namespace {
 int da_train_bwd_impl(genie_ctx* c, const float* slice, const float* mask, const float* edge_attr, const float* save,
                       const float* d_r, float* scratch, float* grad_blob, void* stream, bool zero_blob) {
     if (!c || !slice || !mask || !edge_attr || !save || !d_r || !scratch || !grad_blob)
@@ -3410,50 +3470,15 @@ int da_train_bwd_impl(genie_ctx* c, const float* slice, const float* mask, const
     if ((rc = ensure_reversed(c))) return rc;
     if (zero_blob) HIP_TRY(hipMemsetAsync(grad_blob, 0, sizeof(float) * g_raw_total, st));
     TrArgs a;
-    memset(&a, 0, sizeof(a));
-    a.S = c->S; a.G = c->G; a.T = c->T; a.seg = std::max(1, c->seg);
-    a.nxcd = 8;
-    a.P = c->P; a.order = c->order;
-    a.r_sta_rowptr = c->r_sta.rowptr; a.r_sta_col = c->r_sta.col; a.r_sta_w = c->r_sta.w;
-    a.r_src_rowptr = c->r_src.rowptr; a.r_src_col = c->r_src.col; a.r_src_w = c->r_src.w;
-    a.r_sta_cw = c->r_sta.cw; a.r_src_cw = c->r_src.cw;
-    a.slice = slice; a.mask = mask; a.edge_attr = edge_attr; a.save = save; a.dr = d_r;
-    a.gr = scratch; a.part = scratch + (size_t)GR_BLOCKS * 16 * (size_t)c->P;
+    if ((rc = make_tr_args(c, mask, edge_attr, save, scratch, st, a))) return rc;
+    a.slice = slice; a.dr = d_r; a.store_dz0 = c->abs_sta != nullptr;
     a.sv_t = SV_T; a.sv_up = SV_UP; a.sv_vp = SV_VP;
-    a.store_dz0 = c->abs_sta != nullptr;
-    if (c->pcsr) {
-        if ((rc = ensure_src_of(c, st))) return rc;
-        a.src_of = c->p_src_of; a.ptile = c->ptile16;
-        a.r_sta_rowptr = c->rp_sta.rowptr; a.r_sta_cw = c->rp_sta.cw; a.r_src_rowptr = c->rp_src.rowptr; a.r_src_cw = c->rp_src.cw;
-        a.r_sta_col = a.r_src_col = nullptr; a.r_sta_w = a.r_src_w = nullptr;       // (the PCSR passes read the pair arrays only)
-    }
     const int grid = train_grid(c);
-    // 32-bit row offsets on scalar bases (ldo / sto) while every block of the kept rows lies below 4 GiB
-    const bool o32 = !c->pcsr && (unsigned long long)SV_BLOCKS * (unsigned long long)c->P * 64ull < (1ull << 32);
-    for (int s = 0; s < 3; ++s) {
-        a.packed = c->packed[PL_B2 + s]; a.n_acc = c->tb->n_acc[s]; a.n_vec = c->tb->n_vec[s];
-        // k_train_b1 holds one wave per SIMD (442 registers): one workgroup per CU is all that is ever resident. Its pair-split form
-        // k_train_b1s (two waves per tile, <= 256 registers) runs two workgroups per CU and writes one partial per PAIR
-        const bool split1 = s == 1 && o32 && b1_split_on();
-        const int grid_s = (s == 1 && !split1) ? std::max(8, grid / 2 / 8 * 8) : grid;
-        const int grid_w = (c->pcsr && s == 1) ? grid : grid_s;        // workgroups of this pass (= 4 waves of partials each)
-        if (c->pcsr) {
-            if (s == 0) k_train_b2<true><<<grid, 256, 0, st>>>(a);
-            else if (s == 1) k_train_b1p<false><<<grid, 256, 0, st>>>(a);
-            else k_train_b0<true><<<grid, 256, 0, st>>>(a);
-        } else {
-            if (s == 0) k_train_b2<false, TR_WPB_LIGHT><<<grid, TR_WPB_LIGHT * 64, 0, st>>>(a);
-            else if (s == 1) {
-                if (split1) k_train_b1s<false><<<grid_s, 256, 0, st>>>(a);
-                else if (o32) k_train_b1<false, true><<<grid_s, 256, 0, st>>>(a); else k_train_b1<false><<<grid_s, 256, 0, st>>>(a);
-            }
-            else if (o32) k_train_b0<false, true><<<grid, 256, 0, st>>>(a);
-            else k_train_b0<false><<<grid, 256, 0, st>>>(a);
-        }
-        const int stride = a.n_acc * 256 + a.n_vec * 16 + 16;
-        const int wpb_s = (s == 0 && !c->pcsr) ? TR_WPB_LIGHT : (split1 ? 2 : 4);
-        k_train_reduce<<<(stride + 31) / 32, 256, 0, st>>>(a.part, grid_w * wpb_s, a.n_acc, a.n_vec, c->tb->n_sc[s], c->tb->d_acc[s], c->tb->d_vec[s],
-                                                            c->tb->d_sc[s], grad_blob, 0);
+    const bool o32 = tr_o32(c, SV_BLOCKS);
+    for (int s = 0; s < 3; ++s) {      // the gradient maps TM_B2, TM_B1, TM_B0
+        a.packed = c->packed[PL_B2 + s]; bind_part(a, c, s, a.part);
+        const int n_slots = s == 0 ? launch_b2(c, a, grid, st) : s == 1 ? launch_b1<false>(c, a, grid, o32, st) : launch_b0(c, a, grid, o32, st);
+        reduce_pass(c, s, a.part, n_slots, grad_blob, false, st);
     }
     if (c->has_edges || c->abs_sta) {
         if ((rc = static_term_grads(c, a.gr, a.part + train_part_floats(c), grad_blob, st))) return rc;
@@ -3463,11 +3488,16 @@ int da_train_bwd_impl(genie_ctx* c, const float* slice, const float* mask, const
 }
 }  // namespace
 
+int genie_da_train_bwd(genie_ctx* c, const float* slice, const float* mask, const float* edge_attr, const float* save,
+                       const float* d_r, float* scratch, float* grad_blob, void* stream) {
+    return da_train_bwd_impl(c, slice, mask, edge_attr, save, d_r, scratch, grad_blob, stream, true);
+}
+
 // ---- training step: the G- / Q-sized tail (train_tail_kernels.hpp) -------------------------------------------------------
 namespace {
 constexpr int TT_R = 0, TT_BIP = 32, TT_SA1 = 48, TT_SA2 = 80, TT_XS = 112, TT_ROW = 144;     // floats per source node in `tsave`
 int tt_grid(long long n) { return tl_blocks(n, 160); }
-size_t tt_part_floats(int n_acc, int n_vec, int grid) { return (size_t)grid * 4 * ((size_t)n_acc * 256 + (size_t)n_vec * 16 + 16); }
+size_t tt_part_floats(int n_acc, int n_vec, int grid) { return part_floats(n_acc, n_vec, grid * 4); }      // four waves per workgroup
 struct TtScratch {           // offsets (floats) into the backward's scratch
     size_t dxs_a, dxs_b, eb, dxm, cv, pj, gpart, dxd, dan, dx0, dx1, part_ro, part_ro0, part_a, part_b, total;
 };
@@ -3488,10 +3518,17 @@ TtScratch tt_layout(const genie_ctx* c, int n_query) {
     t.total = o;
     return t;
 }
-int tt_reduce(genie_ctx* c, int tm, const float* part, int n_waves, float* blob, hipStream_t st) {
-    const int stride = c->tb->n_acc[tm] * 256 + c->tb->n_vec[tm] * 16 + 16;
-    k_train_reduce<<<(stride + 31) / 32, 256, 0, st>>>(part, n_waves, c->tb->n_acc[tm], c->tb->n_vec[tm], c->tb->n_sc[tm], c->tb->d_acc[tm], c->tb->d_vec[tm],
-                                                        c->tb->d_sc[tm], blob, 1);
+// ONE side stream per device for every context (a stream is a hardware queue: creating one per context cost the first backward of
+// every rebuilt context ~10 ms -- the reference's training loop builds a context per sample); events per context
+int ensure_side_stream(genie_ctx* c) {
+    if (c->side_stream) return GENIE_OK;
+    static std::map<int, hipStream_t> side; static std::mutex mu;
+    std::lock_guard<std::mutex> lk(mu);
+    hipStream_t& s = side[c->device];
+    if (!s) HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    if (!c->ev_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    if (!c->ev_join) HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+    c->side_stream = s;
     return GENIE_OK;
 }
 }  // namespace
@@ -3567,19 +3604,8 @@ int genie_tail_train_bwd(genie_ctx* c, const float* pos, const float* x_query, c
     // The y branch (grid read-out: 61 us) and the x branch (query read-out + its grid-node side: 159 + 37 us) are independent until
     // SpatialAggregation3 and each is ONE wave tile per wave on a fraction of the CUs: the y branch runs on the context's side stream
     // beside the x branch and is joined (and reduced: both branches add into TemporalAttention's gradients) before the layers.
-    if (!c->side_stream) {
-        // ONE side stream per device for every context (a stream is a hardware queue: creating one per context cost the first
-        // backward of every rebuilt context ~10 ms -- the reference's training loop builds a context per sample); events per context
-        static std::map<int, hipStream_t> side;
-        static std::mutex mu;
-        std::lock_guard<std::mutex> lk(mu);
-        hipStream_t& s = side[c->device];
-        if (!s) HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        if (!c->ev_fork) HIP_TRY(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        if (!c->ev_join) HIP_TRY(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-        c->side_stream = s;
-    }
-    const int grid_y = tt_grid(c->G);
+    if ((rc = ensure_side_stream(c))) return rc;
+    const int gs = tt_grid(c->G);          // workgroups of every G-sized pass below
     HIP_TRY(hipEventRecord(c->ev_fork, st));
     HIP_TRY(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
     {   // y branch: TemporalAttention + SpatialDirect
@@ -3587,8 +3613,8 @@ int genie_tail_train_bwd(genie_ctx* c, const float* pos, const float* x_query, c
         memset(&b, 0, sizeof(b));
         b.ro = ro; b.ro.N = b.ro.Nw = c->G; b.ro.img = c->packed[PL_RO0];
         b.timg = c->packed[PL_TRO0]; b.d_out = d_y; b.d_lat = d_ylat_extra; b.dxs = S + L.dxs_a;
-        b.part = S + L.part_ro0; b.n_acc = c->tb->n_acc[TM_RO0]; b.n_vec = c->tb->n_vec[TM_RO0];
-        k_ro_bwd<0><<<grid_y, 256, sizeof(float) * RB_LDS_FLOATS, c->side_stream>>>(b);
+        bind_part(b, c, TM_RO0, S + L.part_ro0);
+        k_ro_bwd<0><<<gs, 256, sizeof(float) * RB_LDS_FLOATS, c->side_stream>>>(b);
         HIP_TRY(hipEventRecord(c->ev_join, c->side_stream));
     }
     {   // x branch: TemporalAttention + SpatialAttention (query side), then its grid-node side
@@ -3598,28 +3624,26 @@ int genie_tail_train_bwd(genie_ctx* c, const float* pos, const float* x_query, c
         b.ro = ro; b.ro.N = b.ro.Nw = n_query; b.ro.x_grid = pos; b.ro.x_query = x_query; b.ro.knn = knn; b.ro.cv = S + L.cv;
         b.ro.img = c->packed[PL_RO1];
         b.timg = c->packed[PL_TRO1]; b.d_out = d_x; b.d_lat = d_qlat_extra; b.eb = S + L.eb; b.dxm = S + L.dxm;
-        b.part = S + L.part_ro; b.n_acc = c->tb->n_acc[TM_RO1]; b.n_vec = c->tb->n_vec[TM_RO1];
+        bind_part(b, c, TM_RO1, S + L.part_ro);
         const int grid = tt_grid(n_query);
         k_ro_bwd<1><<<grid, 256, sizeof(float) * RB_LDS_FLOATS, st>>>(b);
-        tt_reduce(c, TM_RO1, b.part, grid * 4, grad_blob, st);
+        reduce_pass(c, TM_RO1, b.part, grid * 4, grad_blob, true, st);
         SnArgs n;
         memset(&n, 0, sizeof(n));
         n.G = c->G; n.nq = n_query; n.x_spatial = xs; n.x_grid = pos; n.x_query = x_query; n.r_rowptr = rknn_rowptr; n.r_edge = rknn_edge;
         n.eb = S + L.eb; n.dxm = S + L.dxm; n.raw = c->raw; n.o_sq_w = g_params[W_SAT_Q_W].off; n.o_sq_b = g_params[W_SAT_Q_B].off;
         n.scale_rel = c->scale_rel; n.timg = c->packed[PL_TSN]; n.dxs = S + L.dxs_b;
-        n.part = S + L.part_a; n.n_acc = c->tb->n_acc[TM_SN]; n.n_vec = c->tb->n_vec[TM_SN];
-        const int gn = tt_grid(c->G);
-        k_sat_node_bwd<<<gn, 256, 0, st>>>(n);
-        tt_reduce(c, TM_SN, n.part, gn * 4, grad_blob, st);
+        bind_part(n, c, TM_SN, S + L.part_a);
+        k_sat_node_bwd<<<gs, 256, 0, st>>>(n);
+        reduce_pass(c, TM_SN, n.part, gs * 4, grad_blob, true, st);
     }
     HIP_TRY(hipStreamWaitEvent(st, c->ev_join, 0));          // join: the y branch's d x_spatial (dxs_a) and partials are complete
-    tt_reduce(c, TM_RO0, S + L.part_ro0, grid_y * 4, grad_blob, st);
+    reduce_pass(c, TM_RO0, S + L.part_ro0, gs * 4, grad_blob, true, st);
     k_tq_bwd<<<1, 256, 0, st>>>(c->raw, grad_blob + g_raw_total, t_query, n_t, c->scale_t, g_params[W_TA_Q1_W].off, g_params[W_TA_Q1_B].off,
                                 g_params[W_TA_Q2_W].off, g_params[W_TA_Q2_B].off, g_params[W_TA_ACT3].off, grad_blob);
     // SpatialAggregation 3, 2, 1
     const float* x_in[3] = {bip, sa1, sa2};
     float* dxl[2] = {S + L.dx0, S + L.dx1};
-    const int gs = tt_grid(c->G);
     for (int layer = 3; layer >= 1; --layer) {
         sa_pre(c, false, layer, x_in[layer - 1], S + L.pj, S + L.gpart, st);
         SbArgs a;
@@ -3633,21 +3657,21 @@ int genie_tail_train_bwd(genie_ctx* c, const float* pos, const float* x_query, c
         else a.dout_a = dxl[layer & 1];
         a.dxd = S + L.dxd; a.dan = S + L.dan; a.dx = dxl[(layer - 1) & 1];
         const int tma = TM_SAA1 + layer - 1, tmb = TM_SAB1 + layer - 1;
-        a.part = S + L.part_b; a.n_acc = c->tb->n_acc[tma]; a.n_vec = c->tb->n_vec[tma];
+        bind_part(a, c, tma, S + L.part_b);
         if (layer == 1) k_sa_bwd_a<15><<<gs, 256, 0, st>>>(a); else k_sa_bwd_a<30><<<gs, 256, 0, st>>>(a);
-        tt_reduce(c, tma, a.part, gs * 4, grad_blob, st);
+        reduce_pass(c, tma, a.part, gs * 4, grad_blob, true, st);
         a.part_a = S + L.part_b; a.n_waves_a = gs * 4; a.n_acc_a = c->tb->n_acc[tma]; a.n_vec_a = c->tb->n_vec[tma];
-        a.part = S + L.part_a; a.n_acc = c->tb->n_acc[tmb]; a.n_vec = c->tb->n_vec[tmb]; a.blob = grad_blob;
+        bind_part(a, c, tmb, S + L.part_a); a.blob = grad_blob;
         if (layer == 1) k_sa_bwd_b<15><<<gs, 256, 0, st>>>(a); else k_sa_bwd_b<30><<<gs, 256, 0, st>>>(a);
-        tt_reduce(c, tmb, a.part, gs * 4, grad_blob, st);
+        reduce_pass(c, tmb, a.part, gs * 4, grad_blob, true, st);
     }
     {   // Bipartite_ReadIn.fc2: d bip (= the gradient of SpatialAggregation1's input) -> d r
         BbArgs b;
         memset(&b, 0, sizeof(b));
         b.G = c->G; b.r = r; b.dbip = dxl[0]; b.img = c->packed[PL_BIP]; b.timg = c->packed[PL_TBIP]; b.dr = d_r_out;
-        b.part = S + L.part_a; b.n_acc = c->tb->n_acc[TM_BIP]; b.n_vec = c->tb->n_vec[TM_BIP];
+        bind_part(b, c, TM_BIP, S + L.part_a);
         k_bip_bwd<<<gs, 256, 0, st>>>(b);
-        tt_reduce(c, TM_BIP, b.part, gs * 4, grad_blob, st);
+        reduce_pass(c, TM_BIP, b.part, gs * 4, grad_blob, true, st);
     }
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
@@ -3793,51 +3817,20 @@ int genie_assoc_train_bwd(genie_ctx* c, const float* y_latent, const float* mask
     assoc_pre_launch(c, y_latent, mask_src, st);          // pg[31] = mask1[g] (another forward may have overwritten the table)
     HIP_TRY(hipMemsetAsync(grad_blob, 0, sizeof(float) * g_raw_total, st));
     TrArgs a;
-    memset(&a, 0, sizeof(a));
-    a.S = c->S; a.G = c->G; a.T = c->T; a.seg = std::max(1, c->seg);
-    a.nxcd = 8;
-    a.P = c->P; a.order = c->order;
-    a.r_sta_rowptr = c->r_sta.rowptr; a.r_sta_col = c->r_sta.col; a.r_sta_w = c->r_sta.w;
-    a.r_src_rowptr = c->r_src.rowptr; a.r_src_col = c->r_src.col; a.r_src_w = c->r_src.w;
-    a.r_sta_cw = c->r_sta.cw; a.r_src_cw = c->r_src.cw;
-    a.mask = mask; a.edge_attr = edge_attr; a.save = asave; a.x_latent = x_latent; a.pg = c->as_pg;
-    a.gr = scratch; a.part = scratch + (size_t)GR_BLOCKS * 16 * (size_t)c->P;
-    a.zsum = a.part + train_part_floats(c);
+    if ((rc = make_tr_args(c, mask, edge_attr, asave, scratch, st, a))) return rc;
+    a.x_latent = x_latent; a.pg = c->as_pg; a.zsum = a.part + train_part_floats(c);
     float* sscr = a.zsum + (size_t)c->G * c->T * 32 + 64;
-    const bool variant = c->has_edges || c->abs_sta != nullptr;
-    if (c->pcsr) {
-        if ((rc = ensure_src_of(c, st))) return rc;
-        a.src_of = c->p_src_of; a.ptile = c->ptile16;
-        a.r_sta_rowptr = c->rp_sta.rowptr; a.r_sta_cw = c->rp_sta.cw; a.r_src_rowptr = c->rp_src.rowptr; a.r_src_cw = c->rp_src.cw;
-        a.r_sta_col = a.r_src_col = nullptr; a.r_sta_w = a.r_src_w = nullptr;
-    }
     a.sv_t = AV_T; a.sv_up = AV_UV; a.sv_vp = AV_UV + 2;
+    const bool variant = c->has_edges || c->abs_sta != nullptr, o32a = tr_o32(c, AV_BLOCKS);
     const int grid = train_grid(c);
-    const bool o32a = !c->pcsr && (unsigned long long)AV_BLOCKS * (unsigned long long)c->P * 64ull < (1ull << 32);      // (20 kept blocks: P < 3.35 M)
     const int tms[4] = {TM_AB3, TM_AB2, TM_AB1, TM_AB0};
     const int pls[4] = {-1, PL_TAB2, PL_TAB1, PL_TAB0};
     for (int s = 0; s < 4; ++s) {
         const int tm = tms[s];
-        a.packed = pls[s] >= 0 ? c->packed[pls[s]] : nullptr; a.n_acc = c->tb->n_acc[tm]; a.n_vec = c->tb->n_vec[tm];
-        const bool split1 = s == 1 && !c->pcsr && o32a && b1_split_on();      // k_train_b1s: two waves per tile, one partial per pair
-        const int grid_s = (s == 1 && !c->pcsr && !split1) ? std::max(8, grid / 2 / 8 * 8) : grid;      // k_train_b1: one workgroup per CU (see da_train_bwd_impl)
-        if (c->pcsr) {
-            if (s == 0) k_as_b3<true><<<grid, 256, 0, st>>>(a, d_s, c->raw + g_params[W_AS_ACT2].off);
-            else if (s == 1) k_train_b1p<true><<<grid, 256, 0, st>>>(a);
-            else if (s == 2) k_as_b1<true><<<grid, 256, 0, st>>>(a);
-            else k_as_b0<true><<<grid, 256, 0, st>>>(a);
-        } else {
-            if (s == 0) k_as_b3<false><<<grid, 256, 0, st>>>(a, d_s, c->raw + g_params[W_AS_ACT2].off);
-            else if (s == 1) {
-                if (split1) k_train_b1s<true><<<grid_s, 256, 0, st>>>(a);
-                else if (o32a) k_train_b1<true, true><<<grid_s, 256, 0, st>>>(a); else k_train_b1<true><<<grid_s, 256, 0, st>>>(a);
-            }
-            else if (s == 2) { if (o32a) k_as_b1<false, true><<<grid, 256, 0, st>>>(a); else k_as_b1<false><<<grid, 256, 0, st>>>(a); }
-            else k_as_b0<false><<<grid, 256, 0, st>>>(a);
-        }
-        const int stride = a.n_acc * 256 + a.n_vec * 16 + 16;
-        k_train_reduce<<<(stride + 31) / 32, 256, 0, st>>>(a.part, grid_s * (split1 ? 2 : 4), a.n_acc, a.n_vec, c->tb->n_sc[tm], c->tb->d_acc[tm], c->tb->d_vec[tm],
-                                                            c->tb->d_sc[tm], grad_blob, 0);
+        a.packed = pls[s] >= 0 ? c->packed[pls[s]] : nullptr; bind_part(a, c, tm, a.part);
+        const int n_slots = s == 0 ? launch_as_b3(c, a, grid, d_s, st) : s == 1 ? launch_b1<true>(c, a, grid, o32a, st)
+                          : s == 2 ? launch_as_b1(c, a, grid, o32a, st) : launch_as_b0(c, a, grid, st);
+        reduce_pass(c, tm, a.part, n_slots, grad_blob, false, st);
         // static terms of the two other model definitions: the layer-2 ones now (the next pass writes dtrp over do), the rest at the end;
         // on an irregular product graph the layer-1 ones after k_as_b1 already (k_as_b0<PCSR> leaves its d z1 rows in the dt blocks)
         if (variant && c->pcsr) {
@@ -3850,10 +3843,10 @@ int genie_assoc_train_bwd(genie_ctx* c, const float* y_latent, const float* mask
         AgArgs g;
         memset(&g, 0, sizeof(g));
         g.G = c->G; g.T = part_T(c); g.zsum = a.zsum; g.y_latent = y_latent; g.timg = c->packed[PL_TAG]; g.d_ylat = d_ylat_out;
-        g.part = a.part; g.n_acc = c->tb->n_acc[TM_AG]; g.n_vec = c->tb->n_vec[TM_AG];
+        bind_part(g, c, TM_AG, a.part);
         const int gg = tt_grid(c->G);
         k_as_g<<<gg, 256, 0, st>>>(g);
-        tt_reduce(c, TM_AG, g.part, gg * 4, grad_blob, st);
+        reduce_pass(c, TM_AG, g.part, gg * 4, grad_blob, true, st);
     }
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
@@ -4208,21 +4201,33 @@ int genie_adam_step(float* param, float* exp_avg, float* exp_avg_sq, int64_t n, 
     return GENIE_OK;
 }
 
+namespace {
+// the argument check of a LocalSliceLgCollapse call in either direction (`who`: its name) and the forward's arguments but img / out / flag
+int make_ls_args(const char* who, int phase_head, const float* s_rows, const int32_t* a_edges, int64_t n_edges, int l_dt, float t0, float dt,
+                 const float* dt_partition, float eps, const float* tlatent, int tl_stride, int tl_col, const float* tpick,
+                 const int32_t* ipick, const float* phase_label, int n_picks, bool picks_ok, LsArgs& a) {
+    if (phase_head < 0 || phase_head > 1 || l_dt < (dt_partition ? 2 : 1) || n_edges < LS_K || (!dt_partition && !(dt > 0.f)) || !(eps > 0.f) || tl_stride < 1 ||
+        tl_col < 0 || tl_col >= tl_stride || !picks_ok)
+        return fail(GENIE_ERR_ARG, std::string(who) + ": bad argument");
+    memset(&a, 0, sizeof(a));
+    a.n_picks = n_picks; a.l_dt = l_dt; a.n_edges = n_edges; a.t0 = t0; a.dt = dt; a.dtp = dt_partition; a.eps = eps;
+    a.s = s_rows; a.A_edges = a_edges; a.tlatent = tlatent; a.tl_stride = tl_stride; a.tl_col = tl_col;
+    a.tpick = tpick; a.ipick = ipick; a.phase = phase_label;
+    return GENIE_OK;
+}
+}  // namespace
+
 int genie_lslc_fwd(genie_ctx* c, int phase_head, const float* s_rows, const int32_t* a_edges, int64_t n_edges, int l_dt, float t0,
                    float dt, const float* dt_partition, float eps, const float* tlatent, int tl_stride, int tl_col, const float* tpick,
                    const int32_t* ipick, const float* phase_label, int n_picks, float* out, void* stream) {
     if (!c || !s_rows || !a_edges || !tlatent || !tpick || !ipick || !phase_label || !out) return fail(GENIE_ERR_ARG, "genie_lslc_fwd: null argument");
-    if (phase_head < 0 || phase_head > 1 || l_dt < (dt_partition ? 2 : 1) || n_edges < LS_K || (!dt_partition && !(dt > 0.f)) || !(eps > 0.f) || tl_stride < 1 ||
-        tl_col < 0 || tl_col >= tl_stride)
-        return fail(GENIE_ERR_ARG, "genie_lslc_fwd: bad argument");
+    LsArgs a;
+    GENIE_TRY(make_ls_args("genie_lslc_fwd", phase_head, s_rows, a_edges, n_edges, l_dt, t0, dt, dt_partition, eps, tlatent, tl_stride, tl_col, tpick,
+                           ipick, phase_label, n_picks, true, a));
     if (n_picks < 1) return GENIE_OK;
     hipStream_t st = (hipStream_t)stream;
     { int rcp = ensure_packed(c, st); if (rcp) return rcp; }
-    LsArgs a;
-    memset(&a, 0, sizeof(a));
-    a.n_picks = n_picks; a.l_dt = l_dt; a.n_edges = n_edges; a.t0 = t0; a.dt = dt; a.dtp = dt_partition; a.eps = eps;
-    a.s = s_rows; a.A_edges = a_edges; a.tlatent = tlatent; a.tl_stride = tl_stride; a.tl_col = tl_col;
-    a.tpick = tpick; a.ipick = ipick; a.phase = phase_label; a.img = c->packed[phase_head == 0 ? PL_LSP : PL_LSS]; a.out = out;
+    a.img = c->packed[phase_head == 0 ? PL_LSP : PL_LSS]; a.out = out;
     a.flag = c->h_inflag ? c->h_inflag + 1 : nullptr;
     k_lslc<<<tl_blocks(n_picks, c->num_cu * 4), 256, 0, st>>>(a);
     HIP_TRY(hipGetLastError());
@@ -4241,23 +4246,20 @@ int genie_lslc_bwd(genie_ctx* c, int phase_head, const float* s_rows, const int3
                    float* part_scratch, float* grad_blob, void* stream) {
     if (!c || !s_rows || !a_edges || !tlatent || !tpick || !ipick || !phase_label || !d_out || !erow || !etgt || !part_scratch || !grad_blob)
         return fail(GENIE_ERR_ARG, "genie_lslc_bwd: null argument");
-    if (phase_head < 0 || phase_head > 1 || l_dt < (dt_partition ? 2 : 1) || n_edges < LS_K || (!dt_partition && !(dt > 0.f)) || !(eps > 0.f) || tl_stride < 1 ||
-        tl_col < 0 || tl_col >= tl_stride || n_picks < 1)
-        return fail(GENIE_ERR_ARG, "genie_lslc_bwd: bad argument");
-    hipStream_t st = (hipStream_t)stream;
-    { int rcp = ensure_packed(c, st); if (rcp) return rcp; }
     LbArgs b;
     memset(&b, 0, sizeof(b));
-    b.f.n_picks = n_picks; b.f.l_dt = l_dt; b.f.n_edges = n_edges; b.f.t0 = t0; b.f.dt = dt; b.f.dtp = dt_partition; b.f.eps = eps;
-    b.f.s = s_rows; b.f.A_edges = a_edges; b.f.tlatent = tlatent; b.f.tl_stride = tl_stride; b.f.tl_col = tl_col;
-    b.f.tpick = tpick; b.f.ipick = ipick; b.f.phase = phase_label; b.f.img = c->packed[phase_head == 0 ? PL_LSP : PL_LSS];
+    GENIE_TRY(make_ls_args("genie_lslc_bwd", phase_head, s_rows, a_edges, n_edges, l_dt, t0, dt, dt_partition, eps, tlatent, tl_stride, tl_col, tpick,
+                           ipick, phase_label, n_picks, n_picks >= 1, b.f));
+    hipStream_t st = (hipStream_t)stream;
+    { int rcp = ensure_packed(c, st); if (rcp) return rcp; }
+    b.f.img = c->packed[phase_head == 0 ? PL_LSP : PL_LSS];
     b.timg = c->packed[phase_head == 0 ? PL_TLSP : PL_TLSS];
     b.d_out = d_out; b.erow = erow; b.etgt = etgt;
     const int tm = phase_head == 0 ? TM_LSP : TM_LSS;
-    b.part = part_scratch; b.n_acc = c->tb->n_acc[tm]; b.n_vec = c->tb->n_vec[tm];
+    bind_part(b, c, tm, part_scratch);
     const int grid = tt_grid(n_picks);
     k_lslc_bwd<<<grid, 256, 0, st>>>(b);
-    tt_reduce(c, tm, b.part, grid * 4, grad_blob, st);
+    reduce_pass(c, tm, b.part, grid * 4, grad_blob, true, st);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }
@@ -4294,13 +4296,12 @@ static int arrivals_fwd_impl(genie_ctx* c, int n_src, const float* stime, const 
     HIP_TRY(hipMemsetAsync(e0max_scratch, 0xff, sizeof(int32_t), st));       // -1
     k_arr_e0max<<<n_src * n_useg, 256, 0, st>>>(a);
     const size_t lds = sizeof(float) * (GA2_IMG_FLOATS + AR_CAP * AR_ENT + 2 * AR_CAP + 192 + 8);
-    HIP_TRY(hipFuncSetAttribute((const void*)k_arrivals, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    GENIE_TRY(raise_lds_limit(c, (const void*)k_arrivals, (int)lds));
     k_arrivals<<<n_src * n_useg, 256, lds, st>>>(a);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }
 constexpr int ARRT_GRID = 512;        // workgroups of the two backward passes (each wave owns one partial slot)
-inline size_t arrt_stride(int n_acc, int n_vec) { return (size_t)n_acc * 256 + (size_t)n_vec * 16 + 16; }
 }  // namespace
 
 int genie_arrivals_fwd(genie_ctx* c, int n_src, const float* stime, const float* src_embed, const float* trv_src, int n_sta,
@@ -4327,7 +4328,7 @@ int64_t genie_arrivals_bwd_scratch_floats(int n_src, int n_arv, int n_useg) {
     if (n_src < 1 || n_arv < 1 || n_useg < 1) return 0;
     const int64_t tgt = (int64_t)n_src * n_arv;
     return tgt * AT_TG + tgt * 32 + (int64_t)n_src * n_useg * 192 + (int64_t)n_src * AC_STRIDE +
-           (int64_t)ARRT_GRID * 4 * (int64_t)std::max(arrt_stride(AT_NACC, AT_NVEC), arrt_stride(AE_NACC, AE_NVEC));
+           (int64_t)std::max(part_floats(AT_NACC, AT_NVEC, ARRT_GRID * 4), part_floats(AE_NACC, AE_NVEC, ARRT_GRID * 4));
 }
 
 int genie_arrivals_bwd(genie_ctx* c, int n_src, const float* stime, const float* src_embed, const float* trv_src, int n_sta,
@@ -4339,9 +4340,8 @@ int genie_arrivals_bwd(genie_ctx* c, int n_src, const float* stime, const float*
         return fail(GENIE_ERR_ARG, "genie_arrivals_bwd: null argument");
     hipStream_t st = (hipStream_t)stream;
     ArArgs a;
-    { int rc = arrivals_fwd_impl(c, n_src, stime, src_embed, trv_src, n_sta, arrival_p, arrival_s, tpick, phase_label, n_arv, order, seg_sta,
-                                 seg_start, seg_len, n_useg, eps, (float*)ctx_scratch, (int32_t*)e0max_scratch, nullptr, nullptr, st, &a);
-      if (rc) return rc; }
+    GENIE_TRY(arrivals_fwd_impl(c, n_src, stime, src_embed, trv_src, n_sta, arrival_p, arrival_s, tpick, phase_label, n_arv, order, seg_sta,
+                                seg_start, seg_len, n_useg, eps, (float*)ctx_scratch, (int32_t*)e0max_scratch, nullptr, nullptr, st, &a));
     const long long n_tgt = (long long)n_src * n_arv;
     float* tg = scratch;
     float* darv = tg + n_tgt * AT_TG;
@@ -4352,25 +4352,23 @@ int genie_arrivals_bwd(genie_ctx* c, int n_src, const float* stime, const float*
         AtArgs b;
         memset(&b, 0, sizeof(b));
         b.n_tgt = (int)n_tgt; b.img = c->packed[PL_ARR]; b.timg = c->packed[PL_TARR]; b.tstat = save; b.d_out = d_out; b.tg = tg;
-        b.part = part; b.n_acc = c->tb->n_acc[TM_ART]; b.n_vec = c->tb->n_vec[TM_ART];
+        bind_part(b, c, TM_ART, part);
         const int grid = (int)std::min<long long>(ARRT_GRID, (n_tgt + 63) / 64);
         const size_t lds = sizeof(float) * (GA2_IMG_FLOATS + GTA_IMG_FLOATS + 4 * 16 * 17);
-        HIP_TRY(hipFuncSetAttribute((const void*)k_arrt_tgt_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        GENIE_TRY(raise_lds_limit(c, (const void*)k_arrt_tgt_bwd, (int)lds));
         k_arrt_tgt_bwd<<<grid, 256, lds, st>>>(b);
-        int rc = tt_reduce(c, TM_ART, part, grid * 4, grad_blob, st);
-        if (rc) return rc;
+        reduce_pass(c, TM_ART, part, grid * 4, grad_blob, true, st);
     }
     {
         AeArgs b;
         memset(&b, 0, sizeof(b));
         b.f = a; b.timg = c->packed[PL_TARR]; b.tg = tg; b.darv = darv; b.cpair = cpair;
-        b.part = part; b.n_acc = c->tb->n_acc[TM_ARE]; b.n_vec = c->tb->n_vec[TM_ARE];
+        bind_part(b, c, TM_ARE, part);
         const int grid = (int)std::min<long long>(ARRT_GRID, (long long)n_src * n_useg);
         const size_t lds = sizeof(float) * (GA2_IMG_FLOATS + GTA_IMG_FLOATS + 4 * 16 * 17 + 192 + AE_TCH * AT_TG + AE_TCH + 4 * 3 * 256);
-        HIP_TRY(hipFuncSetAttribute((const void*)k_arrt_ent_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        GENIE_TRY(raise_lds_limit(c, (const void*)k_arrt_ent_bwd, (int)lds));
         k_arrt_ent_bwd<<<grid, 256, lds, st>>>(b);
-        int rc = tt_reduce(c, TM_ARE, part, grid * 4, grad_blob, st);
-        if (rc) return rc;
+        reduce_pass(c, TM_ARE, part, grid * 4, grad_blob, true, st);
     }
     const int o1w = g_params[W_AR_C1_W].off, o1b = g_params[W_AR_C1_B].off, o2w = g_params[W_AR_C2_W].off, o2b = g_params[W_AR_C2_B].off,
               oa1 = g_params[W_AR_ACT1].off;

@@ -941,9 +941,7 @@ class HipPath(object):
         pos = _f32(pos, "pos", (self.n_grid, 3))
         x_query = _f32(x_query, "x_query")
         nq = x_query.shape[0]
-        if tuple(knn_idx.shape) != (nq, 10) or knn_idx.dtype != torch.int32 or not knn_idx.is_cuda:
-            raise ValueError("knn_idx must be an int32 GPU tensor of shape [n_query, 10]")
-        knn_idx = knn_idx.contiguous()
+        knn_idx = self._knn_table(knn_idx, nq)
         tq = _f32(t_query, "t_query").reshape(-1)
         main = torch.cuda.current_stream(self.device)
         ev = torch.cuda.Event()
@@ -991,6 +989,28 @@ class HipPath(object):
         for s in getattr(self, "side_streams", None) or ():
             stream.wait_stream(s)
 
+    def _knn_table(self, knn_idx, nq):
+        """The query kNN table of a read-out call, checked and contiguous."""
+        if tuple(knn_idx.shape) != (nq, 10) or knn_idx.dtype != torch.int32 or not knn_idx.is_cuda:
+            raise ValueError("knn_idx must be an int32 GPU tensor of shape [n_query, 10]")
+        return knn_idx.contiguous()
+
+    def _need_assoc(self):
+        if not getattr(self, "assoc_ready", False):
+            raise _lib.GenieHipError("association-head parameters were not uploaded (or have another model definition's shapes)")
+
+    def _scratch(self, attr, floats):
+        """The cached scratch tensor `attr` (_train_scratch, _tail_scratch, _assoc_ws), grown on demand to `floats` floats."""
+        buf = getattr(self, attr, None)
+        if buf is None or buf.numel() < floats:
+            buf = empty_f32(floats, self.device)
+            setattr(self, attr, buf)
+        return buf
+
+    def _grad_views(self, blob):
+        """dict parameter name -> gradient: views into a gradient blob laid out like the weight mirror."""
+        return {name: blob[off:off + n] for name, n, off in zip(self.w_names, self.w_numel, self.w_off)}
+
     def readout_grid(self, x_spatial, t_query):
         """y[n_grid, T, 1] = TemporalAttention(SpatialDirect(x_spatial), t_query) (module.py:1015-1016)."""
         x_spatial = _f32(x_spatial, "x_spatial", (self.n_grid, 30))
@@ -1007,9 +1027,7 @@ class HipPath(object):
         x_grid = _f32(x_grid, "x_grid", (self.n_grid, 3))
         x_query = _f32(x_query, "x_query")
         nq = x_query.shape[0]
-        if tuple(knn_idx.shape) != (nq, 10) or knn_idx.dtype != torch.int32 or not knn_idx.is_cuda:
-            raise ValueError("knn_idx must be an int32 GPU tensor of shape [n_query, 10]")
-        knn_idx = knn_idx.contiguous()
+        knn_idx = self._knn_table(knn_idx, nq)
         tq = _f32(t_query, "t_query").reshape(-1)
         out = torch.empty((nq, tq.numel(), 1), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.genie_readout_query(self.ctx, _ptr(x_spatial), _ptr(x_grid), _ptr(x_query), _ptr(knn_idx), nq, 10,
@@ -1057,12 +1075,11 @@ class HipPath(object):
         x_grid = _f32(x_grid, "x_grid", (self.n_grid, 3))
         x_query = _f32(x_query, "x_query")
         nq = x_query.shape[0]
-        if tuple(knn_idx.shape) != (nq, 10) or knn_idx.dtype != torch.int32 or not knn_idx.is_cuda:
-            raise ValueError("knn_idx must be an int32 GPU tensor of shape [n_query, 10]")
+        knn_idx = self._knn_table(knn_idx, nq)
         tq = _f32(t_query, "t_query").reshape(-1)
         out = torch.empty((nq, tq.numel(), 1), dtype=torch.float32, device=self.device)
         lat = torch.empty((nq, 30), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.genie_readout_query_latent(self.ctx, _ptr(x_spatial), _ptr(x_grid), _ptr(x_query), _ptr(knn_idx.contiguous()), nq, 10,
+        _lib.check(self.lib.genie_readout_query_latent(self.ctx, _ptr(x_spatial), _ptr(x_grid), _ptr(x_query), _ptr(knn_idx), nq, 10,
                                                        _ptr(tq), tq.numel(), _ptr(out), _ptr(lat), self._ws_ptr, _stream()),
                    "genie_readout_query_latent")
         return lat
@@ -1071,8 +1088,7 @@ class HipPath(object):
         """BipartiteGraphReadOutOperator + DataAggregationAssociationPhase (module.py:986-990) in HIP (genie_assoc_fwd):
         y_latent [G,30], mask_src [G] or [G,1], x_latent [P,30], Mask [P,4], edge_attr [P,3] -> [P,30]. Call after the
         DataAggregation stage 2 of the same window (it reuses the c / wu / wv rows of the current workspace slot)."""
-        if not getattr(self, "assoc_ready", False):
-            raise _lib.GenieHipError("association-head parameters were not uploaded (or have another model definition's shapes)")
+        self._need_assoc()
         P = self.n_prod
         y_latent = _f32(y_latent, "y_latent", (self.n_grid, 30))
         mask_src = _f32(mask_src, "mask_src").reshape(-1)
@@ -1082,29 +1098,24 @@ class HipPath(object):
         Mask = _f32(Mask, "Mask", (P, 4))
         edge_attr = _f32(edge_attr, "edge_attr", (P, 3))
         self._refresh_static_edge_attr(edge_attr)
-        need = int(self.lib.genie_assoc_workspace_bytes(self.ctx))
-        if getattr(self, "_assoc_ws", None) is None or self._assoc_ws.numel() * 4 < need:
-            self._assoc_ws = empty_f32((need + 3) // 4, self.device)
+        assoc_ws = self._scratch("_assoc_ws", (int(self.lib.genie_assoc_workspace_bytes(self.ctx)) + 3) // 4)
         out = torch.empty((P, 30), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.genie_assoc_fwd(self.ctx, _ptr(y_latent), _ptr(mask_src), _ptr(x_latent), _ptr(Mask), _ptr(edge_attr),
-                                            _ptr(out), _ptr(self._assoc_ws), self._ws_ptr, _stream()), "genie_assoc_fwd")
+                                            _ptr(out), _ptr(assoc_ws), self._ws_ptr, _stream()), "genie_assoc_fwd")
         return out
 
     def assoc_train_fwd(self, y_latent, mask_src, x_latent, Mask, edge_attr):
         """Training forward of the P-sized association heads (genie_assoc_train_fwd): as `assoc_fwd`, returns (s [P, 30], asave)."""
-        if not getattr(self, "assoc_ready", False):
-            raise _lib.GenieHipError("association-head parameters were not uploaded (or have another model definition's shapes)")
+        self._need_assoc()
         P = self.n_prod
         y_latent = _f32(y_latent, "y_latent", (self.n_grid, 30))
         mask_src = _f32(mask_src, "mask_src").reshape(-1)
         x_latent, Mask, edge_attr = _f32(x_latent, "x_latent", (P, 30)), _f32(Mask, "Mask", (P, 4)), _f32(edge_attr, "edge_attr", (P, 3))
-        need = int(self.lib.genie_assoc_workspace_bytes(self.ctx))
-        if getattr(self, "_assoc_ws", None) is None or self._assoc_ws.numel() * 4 < need:
-            self._assoc_ws = empty_f32((need + 3) // 4, self.device)
+        assoc_ws = self._scratch("_assoc_ws", (int(self.lib.genie_assoc_workspace_bytes(self.ctx)) + 3) // 4)
         asave = empty_f32(int(self.lib.genie_assoc_train_save_floats(self.ctx)), self.device)
         out = empty_f32(P * 30, self.device).view(P, 30)
         _lib.check(self.lib.genie_assoc_train_fwd(self.ctx, _ptr(y_latent), _ptr(mask_src), _ptr(x_latent), _ptr(Mask), _ptr(edge_attr),
-                                                  _ptr(out), _ptr(asave), _ptr(self._assoc_ws), self._ws_ptr, _stream()), "genie_assoc_train_fwd")
+                                                  _ptr(out), _ptr(asave), _ptr(assoc_ws), self._ws_ptr, _stream()), "genie_assoc_train_fwd")
         return out, asave
 
     def assoc_train_bwd(self, y_latent, mask_src, x_latent, Mask, edge_attr, asave, d_s):
@@ -1112,22 +1123,19 @@ class HipPath(object):
         P, G = self.n_prod, self.n_grid
         d_s = _f32(d_s, "d_s", (P, 30))
         mask_src = _f32(mask_src, "mask_src").reshape(-1)
-        need = int(self.lib.genie_assoc_train_scratch_floats(self.ctx))
-        if getattr(self, "_train_scratch", None) is None or self._train_scratch.numel() < need:
-            self._train_scratch = empty_f32(need, self.device)
+        scratch = self._scratch("_train_scratch", int(self.lib.genie_assoc_train_scratch_floats(self.ctx)))
         d_ylat = torch.empty((G, 30), dtype=torch.float32, device=self.device)
         blob = torch.empty(self._blob.numel(), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.genie_assoc_train_bwd(self.ctx, _ptr(y_latent), _ptr(mask_src), _ptr(x_latent), _ptr(Mask), _ptr(edge_attr),
-                                                  _ptr(asave), _ptr(d_s), _ptr(self._train_scratch), _ptr(d_ylat), _ptr(blob), _stream()),
+                                                  _ptr(asave), _ptr(d_s), _ptr(scratch), _ptr(d_ylat), _ptr(blob), _stream()),
                    "genie_assoc_train_bwd")
-        return d_ylat, {name: blob[off:off + n] for name, n, off in zip(self.w_names, self.w_numel, self.w_off)}
+        return d_ylat, self._grad_views(blob)
 
     def lslc_fwd(self, head, s_rows, a_edges, dt_partition, tpick, ipick, phase_label, tlatent, col, eps):
         """LocalSliceLgCollapse P (head 0) / S (head 1), module.py:610-659, in HIP (genie_lslc_fwd): s_rows [P, 30], a_edges int32
         [n_sta * l_dt * 10] time-pointer table, dt_partition [l_dt], tpick / phase_label fp32 [n], ipick int32 [n], tlatent
         [P, C] fp32 with the phase's theoretical arrival in column `col` -> [n, 15]."""
-        if not getattr(self, "assoc_ready", False):
-            raise _lib.GenieHipError("association-head parameters were not uploaded (or have another model definition's shapes)")
+        self._need_assoc()
         s_rows = _f32(s_rows, "s_rows", (self.n_prod, 30))
         tpick = _f32(tpick, "tpick").reshape(-1)
         n = int(tpick.numel())
@@ -1173,11 +1181,10 @@ class HipPath(object):
                                                n, _ptr(d_out), _ptr(erow), _ptr(etgt), _ptr(part), _ptr(blob), _stream()), "genie_lslc_bwd")
             order = torch.sort(etgt, stable=True)[1].to(torch.int32)
             _lib.check(self.lib.genie_seg_rows(_ptr(erow), _ptr(etgt), _ptr(order), n * 10, _ptr(ds), _stream()), "genie_seg_rows")
-        return ds, {name: blob[off:off + k] for name, k, off in zip(self.w_names, self.w_numel, self.w_off)}
+        return ds, self._grad_views(blob)
 
     def _arrivals_args(self, stime, src_embed, trv_src, arrival_p, arrival_s, tpick, ipick, phase_label):
-        if not getattr(self, "assoc_ready", False):
-            raise _lib.GenieHipError("association-head parameters were not uploaded (or have another model definition's shapes)")
+        self._need_assoc()
         stime = _f32(stime, "stime").reshape(-1)
         n_src = int(stime.numel())
         src_embed = _f32(src_embed, "src_embed", (n_src, 30))
@@ -1242,7 +1249,7 @@ class HipPath(object):
                                                _ptr(data[5]), _ptr(data[6]), n, _ptr(segs[0]), _ptr(segs[1]), _ptr(segs[2]), _ptr(segs[3]), n_useg,
                                                eps, _ptr(ctx), _ptr(flag), _ptr(save), _ptr(d_out), _ptr(scratch), _ptr(d_src), _ptr(d_p),
                                                _ptr(d_s), _ptr(blob), _stream()), "genie_arrivals_bwd")
-        return d_src, d_p, d_s, {name: blob[off:off + k] for name, k, off in zip(self.w_names, self.w_numel, self.w_off)}
+        return d_src, d_p, d_s, self._grad_views(blob)
 
     def train_fwd(self, Slice, Mask, edge_attr, want_x_latent=True):
         """Training forward of DataAggregation + the P-sized half of Bipartite_ReadIn (genie_da_train_fwd): returns
@@ -1263,13 +1270,11 @@ class HipPath(object):
         out like the weight mirror) for every DataAggregation parameter and Bipartite_ReadIn.fc1 / activate1."""
         d = torch.zeros((self.n_grid, 32), dtype=torch.float32, device=self.device)
         d[:, :30] = d_r
-        need = int(self.lib.genie_train_scratch_floats(self.ctx))
-        if getattr(self, "_train_scratch", None) is None or self._train_scratch.numel() < need:
-            self._train_scratch = empty_f32(need, self.device)
+        scratch = self._scratch("_train_scratch", int(self.lib.genie_train_scratch_floats(self.ctx)))
         blob = torch.empty(self._blob.numel(), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.genie_da_train_bwd(self.ctx, _ptr(Slice), _ptr(Mask), _ptr(edge_attr), _ptr(save), _ptr(d),
-                                               _ptr(self._train_scratch), _ptr(blob), _stream()), "genie_da_train_bwd")
-        return {name: blob[off:off + n] for name, n, off in zip(self.w_names, self.w_numel, self.w_off)}
+                                               _ptr(scratch), _ptr(blob), _stream()), "genie_da_train_bwd")
+        return self._grad_views(blob)
 
     # ---- training step of forward_fixed_source: the whole path in HIP, both directions ----------------------------------
     def reverse_query_table(self, knn_idx):
@@ -1296,9 +1301,7 @@ class HipPath(object):
         pos = _f32(pos, "pos", (self.n_grid, 3))
         x_query = _f32(x_query, "x_query")
         nq = int(x_query.shape[0])
-        if tuple(knn_idx.shape) != (nq, 10) or knn_idx.dtype != torch.int32 or not knn_idx.is_cuda:
-            raise ValueError("knn_idx must be an int32 GPU tensor of shape [n_query, 10]")
-        knn_idx = knn_idx.contiguous()
+        knn_idx = self._knn_table(knn_idx, nq)
         tq = _f32(t_query, "t_query").reshape(-1)
         dev, G = self.device, self.n_grid
         save = empty_f32(int(self.lib.genie_train_save_floats(self.ctx)), dev)
@@ -1328,9 +1331,7 @@ class HipPath(object):
         pos = _f32(pos, "pos", (G, 3))
         x_query = _f32(x_query, "x_query")
         nq = int(x_query.shape[0])
-        if tuple(knn_idx.shape) != (nq, 10) or knn_idx.dtype != torch.int32 or not knn_idx.is_cuda:
-            raise ValueError("knn_idx must be an int32 GPU tensor of shape [n_query, 10]")
-        knn_idx = knn_idx.contiguous()
+        knn_idx = self._knn_table(knn_idx, nq)
         tq = _f32(t_query, "t_query").reshape(-1)
         T = tq.numel()
         d_y = _f32(d_y, "d_y").reshape(G, T)
@@ -1339,19 +1340,15 @@ class HipPath(object):
         d_ylat = _f32(d_ylat, "d_ylat", (G, 30)) if d_ylat is not None else None
         d_qlat = _f32(d_qlat, "d_qlat", (nq, 30)) if d_qlat is not None else None
         rp, re = self.reverse_query_table(knn_idx)
-        need_t = int(self.lib.genie_tail_train_scratch_floats(self.ctx, nq))
-        need_f = int(self.lib.genie_train_scratch_floats(self.ctx))
-        if getattr(self, "_tail_scratch", None) is None or self._tail_scratch.numel() < need_t:
-            self._tail_scratch = empty_f32(need_t, dev)
-        if getattr(self, "_train_scratch", None) is None or self._train_scratch.numel() < need_f:
-            self._train_scratch = empty_f32(need_f, dev)
+        tail_scratch = self._scratch("_tail_scratch", int(self.lib.genie_tail_train_scratch_floats(self.ctx, nq)))
+        front_scratch = self._scratch("_train_scratch", int(self.lib.genie_train_scratch_floats(self.ctx)))
         d_r = torch.empty((G, 32), dtype=torch.float32, device=dev)
         blob = torch.empty(int(self.lib.genie_train_grad_floats()), dtype=torch.float32, device=dev)
         _lib.check(self.lib.genie_train_bwd(self.ctx, _ptr(Slice), _ptr(Mask), _ptr(edge_attr), _ptr(save), _ptr(pos), _ptr(x_query),
                                             _ptr(knn_idx), _ptr(rp), _ptr(re), nq, 10, _ptr(tq), T, _ptr(tsave), _ptr(d_y), _ptr(d_x),
-                                            _ptr(d_xs), _ptr(d_ylat), _ptr(d_qlat), _ptr(self._tail_scratch), _ptr(self._train_scratch), _ptr(d_r),
+                                            _ptr(d_xs), _ptr(d_ylat), _ptr(d_qlat), _ptr(tail_scratch), _ptr(front_scratch), _ptr(d_r),
                                             _ptr(blob), _stream()), "genie_train_bwd")
-        return {name: blob[off:off + n] for name, n, off in zip(self.w_names, self.w_numel, self.w_off)}
+        return self._grad_views(blob)
 
     def tail_train_bwd(self, pos, x_query, knn_idx, t_query, tsave, d_y, d_x, d_xs=None, d_ylat=None):
         """The tail half of `path_train_bwd` alone (genie_tail_train_bwd): returns (d_r [G, 32], gradient blob). Phase timing
@@ -1363,14 +1360,12 @@ class HipPath(object):
         T = tq.numel()
         d_y, d_x = _f32(d_y, "d_y").reshape(G, T), _f32(d_x, "d_x").reshape(nq, T)
         rp, re = self.reverse_query_table(knn_idx)
-        need_t = int(self.lib.genie_tail_train_scratch_floats(self.ctx, nq))
-        if getattr(self, "_tail_scratch", None) is None or self._tail_scratch.numel() < need_t:
-            self._tail_scratch = empty_f32(need_t, dev)
+        tail_scratch = self._scratch("_tail_scratch", int(self.lib.genie_tail_train_scratch_floats(self.ctx, nq)))
         d_r = torch.empty((G, 32), dtype=torch.float32, device=dev)
         blob = torch.empty(int(self.lib.genie_train_grad_floats()), dtype=torch.float32, device=dev)
         _lib.check(self.lib.genie_tail_train_bwd(self.ctx, _ptr(_f32(pos, "pos", (G, 3))), _ptr(x_query), _ptr(knn_idx), _ptr(rp), _ptr(re), nq, 10,
                                                  _ptr(tq), T, _ptr(tsave), _ptr(d_y), _ptr(d_x), _ptr(d_xs), _ptr(d_ylat), None,
-                                                 _ptr(self._tail_scratch), _ptr(d_r), _ptr(blob), _stream()), "genie_tail_train_bwd")
+                                                 _ptr(tail_scratch), _ptr(d_r), _ptr(blob), _stream()), "genie_tail_train_bwd")
         return d_r, blob
 
     def nbr_mean(self, x_sta=None, x_src=None):
