@@ -3704,11 +3704,14 @@ int genie_set_tail_grid(genie_ctx* c, int readout_workgroups, int sa_workgroups)
     return GENIE_OK;
 }
 
-size_t genie_assoc_workspace_bytes(const genie_ctx* c) { return c ? sizeof(float) * 3 * 32 * (size_t)c->P : 0; }
+// tr [P][32], q1 [P][32], q2 [P_ext][32]: q2 is what a layer gathers from neighbouring source nodes (owned rows, then the halo's)
+size_t genie_assoc_workspace_bytes(const genie_ctx* c) { return c ? sizeof(float) * 32 * (2 * (size_t)c->P + (size_t)c->P_ext) : 0; }
+size_t genie_assoc_halo_offset(const genie_ctx* c) { return c ? sizeof(float) * 32 * 3 * (size_t)c->P : 0; }
 
 namespace {
+enum { AS_PART_A = 1, AS_PART_B = 2, AS_PART_LAST = 4, AS_PART_ALL = 7 };
 int assoc_fwd_impl(genie_ctx* c, const float* y_latent, const float* mask_src, const float* x_latent, const float* mask,
-                   const float* edge_attr, float* out, void* assoc_ws, void* ws, void* stream, float* save);
+                   const float* edge_attr, float* out, void* assoc_ws, void* ws, void* stream, float* save, int parts = AS_PART_ALL);
 void assoc_pre_launch(genie_ctx* c, const float* y_latent, const float* mask_src, hipStream_t st) {
     AsPreOffs o;
     o.ro_fc1_w = g_params[W_RO_FC1_W].off; o.ro_fc1_b = g_params[W_RO_FC1_B].off; o.as_init_w = g_params[W_AS_INIT_W].off;
@@ -3734,21 +3737,30 @@ int genie_assoc_fwd(genie_ctx* c, const float* y_latent, const float* mask_src, 
     return assoc_fwd_impl(c, y_latent, mask_src, x_latent, mask, edge_attr, out, assoc_ws, ws, stream, nullptr);
 }
 
+int genie_assoc_fwd_part(genie_ctx* c, int part, const float* y_latent, const float* mask_src, const float* x_latent, const float* mask,
+                         const float* edge_attr, float* out, void* assoc_ws, void* ws, void* stream) {
+    if (part < 0 || part > 2) return fail(GENIE_ERR_ARG, "genie_assoc_fwd_part: part must be 0, 1 or 2");
+    if (c && c->pcsr) return fail(GENIE_ERR_STATE, "genie_assoc_fwd_part: needs a Cartesian product graph");
+    return assoc_fwd_impl(c, y_latent, mask_src, x_latent, mask, edge_attr, out, assoc_ws, ws, stream, nullptr, 1 << part);
+}
+
 namespace {
 int assoc_fwd_impl(genie_ctx* c, const float* y_latent, const float* mask_src, const float* x_latent, const float* mask,
-                   const float* edge_attr, float* out, void* assoc_ws, void* ws, void* stream, float* save) {
+                   const float* edge_attr, float* out, void* assoc_ws, void* ws, void* stream, float* save, int parts) {
     int rc = check_ws(c, ws);
     if (rc) return rc;
     if (!y_latent || !mask_src || !x_latent || !mask || !edge_attr || !out || !assoc_ws)
         return fail(GENIE_ERR_ARG, "genie_assoc_fwd: null argument");
-    if (c->G_ext != c->G) return fail(GENIE_ERR_STATE, "genie_assoc_fwd: needs an unsharded product graph");
+    // one call cannot run the layers of a shard: each gathers rows of halo nodes that another rank computes (genie_assoc_fwd_part)
+    if (c->G_ext != c->G && (parts == AS_PART_ALL || save))
+        return fail(GENIE_ERR_STATE, "genie_assoc_fwd: needs an unsharded product graph (a shard runs genie_assoc_fwd_part around its halo exchanges)");
     if (((uintptr_t)assoc_ws & 15) != 0) return fail(GENIE_ERR_ARG, "genie_assoc_fwd: assoc_ws must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_packed(c, st))) return rc;
     if (!c->as_pg) HIP_TRY(c->as_pg.alloc(AS_PG * (size_t)c->G));
     const bool variant = c->has_edges || c->abs_sta != nullptr;
     if (variant && !c->as_ps) HIP_TRY(c->as_ps.alloc(AS_PS * (size_t)edge_rows_sta(c)));
-    assoc_pre_launch(c, y_latent, mask_src, st);
+    if (parts & AS_PART_A) assoc_pre_launch(c, y_latent, mask_src, st);
     const StageCall call{save, save != nullptr};      // save: training forward (caller's station order, pre-activations kept)
     DaArgs d = make_da_args(c, call, (float*)ws);
     AsArgs a;
@@ -3772,16 +3784,17 @@ int assoc_fwd_impl(genie_ctx* c, const float* y_latent, const float* mask_src, c
         a.packed = c->packed[PL_ASB];
         k_assoc_b<true><<<grid, 256, 0, st>>>(a);
     } else {
-        const int grid = da_grid(c, (long long)c->G * c->T, std::max(1, c->bpc1));
         a.packed = c->packed[PL_ASA];
         // (40 registers, 21 KB of LDS: four workgroups per CU where stage 1's occupancy gave two -- 369 -> 322 us, six: 330; tools/assoc_ab.sh)
-        k_assoc_a<false><<<da_grid(c, (long long)c->G * c->T, 4), 256, 0, st>>>(a);
+        if (parts & AS_PART_A) k_assoc_a<false><<<da_grid(c, (long long)c->G * c->T, 4), 256, 0, st>>>(a);
         a.packed = c->packed[PL_ASB];
         // k_assoc_b is bound by its 23 gathered 128-B rows per node and, at 4 waves per workgroup, by LDS to 8 waves per CU (every
         // workgroup holds its own 52-KB copy of the weight image): ONE workgroup of 16 waves per CU shares one copy -- 969 -> 824 us at
         // config 2 (12 waves: 882; 8 waves in one workgroup: 987; `tools/assoc_ab.sh`)
-        k_assoc_b<false, 16><<<std::max(8, c->num_cu / 8 * 8), 1024, 0, st>>>(a);
+        if (parts & AS_PART_B) k_assoc_b<false, 16><<<std::max(8, c->num_cu / 8 * 8), 1024, 0, st>>>(a);
     }
+    HIP_TRY(hipGetLastError());
+    if (!(parts & AS_PART_LAST)) return GENIE_OK;
     // second pair of neighbour means + PReLU2 = the stage-2 kernel of this context without its Bipartite half
     if ((rc = run_stage2(c, call, mask, edge_attr, out, ws, stream, 0, c->G, c->raw + g_params[W_AS_ACT2].off, 1))) return rc;
     HIP_TRY(hipGetLastError());
@@ -4229,7 +4242,50 @@ int genie_lslc_fwd(genie_ctx* c, int phase_head, const float* s_rows, const int3
     { int rcp = ensure_packed(c, st); if (rcp) return rcp; }
     a.img = c->packed[phase_head == 0 ? PL_LSP : PL_LSS]; a.out = out;
     a.flag = c->h_inflag ? c->h_inflag + 1 : nullptr;
-    k_lslc<<<tl_blocks(n_picks, c->num_cu * 4), 256, 0, st>>>(a);
+    k_lslc<false><<<tl_blocks(n_picks, c->num_cu * 4), 256, 0, st>>>(a);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+int genie_lslc_rows(genie_ctx* c, const float* s_own, const int32_t* node_local, int n_grid, const int32_t* a_edges_p,
+                    const int32_t* a_edges_s, int64_t n_edges, int l_dt, float t0, float dt, const float* dt_partition, const float* tlatent,
+                    int tl_stride, const float* tpick, const int32_t* ipick, int n_picks, int32_t* count, float* rows, void* stream) {
+    if (!c || !s_own || !node_local || !a_edges_p || !a_edges_s || !tlatent || !count) return fail(GENIE_ERR_ARG, "genie_lslc_rows: null argument");
+    if (c->pcsr) return fail(GENIE_ERR_STATE, "genie_lslc_rows: needs a Cartesian product graph");
+    if (n_grid < c->G || n_picks < 0 || n_picks > 100000000 || l_dt < (dt_partition ? 2 : 1) || n_edges < LS_K || (!dt_partition && !(dt > 0.f)) ||
+        tl_stride < 2)
+        return fail(GENIE_ERR_ARG, "genie_lslc_rows: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(count, 0, sizeof(int32_t), st));
+    if (n_picks == 0) return GENIE_OK;
+    if (!tpick || !ipick || !rows) return fail(GENIE_ERR_ARG, "genie_lslc_rows: null argument");
+    if ((((uintptr_t)rows) | ((uintptr_t)s_own)) & 7) return fail(GENIE_ERR_ARG, "genie_lslc_rows: s_own and rows must be 8-byte aligned");
+    LrArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_picks = n_picks; a.l_dt = l_dt; a.S = c->S; a.n_grid = n_grid; a.n_edges = n_edges; a.t0 = t0; a.dt = dt; a.dtp = dt_partition;
+    a.s_own = s_own; a.node_local = node_local; a.A_edges[0] = a_edges_p; a.A_edges[1] = a_edges_s;
+    a.tlatent = tlatent; a.tl_stride = tl_stride; a.tpick = tpick; a.ipick = ipick; a.count = count; a.rows = rows;
+    a.flag = c->h_inflag ? c->h_inflag + 1 : nullptr;
+    const long long n_ent = 2LL * n_picks * LS_K;
+    k_lslc_rows<<<(int)std::max<long long>(1, std::min<long long>((n_ent + 15) / 16, (long long)c->num_cu * 8)), 256, 0, st>>>(a);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+int genie_lslc_fwd_rows(genie_ctx* c, int phase_head, const float* table, float eps, const float* tpick, const float* phase_label,
+                        int n_picks, float* out, void* stream) {
+    if (!c || !table || !tpick || !phase_label || !out) return fail(GENIE_ERR_ARG, "genie_lslc_fwd_rows: null argument");
+    if (phase_head < 0 || phase_head > 1 || !(eps > 0.f) || n_picks < 0 || (((uintptr_t)table) & 7))
+        return fail(GENIE_ERR_ARG, "genie_lslc_fwd_rows: bad argument");
+    if (n_picks < 1) return GENIE_OK;
+    LsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.n_picks = n_picks; a.l_dt = 1; a.n_edges = (long long)n_picks * LS_K; a.dt = 1.f; a.eps = eps;
+    a.s = table + (size_t)phase_head * n_picks * LS_K * LR_ROW; a.tpick = tpick; a.phase = phase_label;
+    hipStream_t st = (hipStream_t)stream;
+    { int rcp = ensure_packed(c, st); if (rcp) return rcp; }
+    a.img = c->packed[phase_head == 0 ? PL_LSP : PL_LSS]; a.out = out;
+    k_lslc<true><<<tl_blocks(n_picks, c->num_cu * 4), 256, 0, st>>>(a);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }

@@ -777,6 +777,10 @@ struct LsArgs {
     float* out;                   // [n_picks, 15]
     unsigned* flag;               // host-mapped word: bit 0 set when a pick indexes outside the time-pointer table (genie_index_flags)
 };
+// ROWS: the rows the table points to were gathered already (genie_lslc_rows + one all-gather on a source-node-sharded model): a.s is
+// [n_picks * K][LR_ROW] = the s row of (pick, slot), then its theoretical arrival; no table lookup, nothing to clamp or report.
+constexpr int LR_ROW = 32;
+template <bool ROWS>
 __global__ __launch_bounds__(256) void k_lslc(LsArgs a) {
     __shared__ __attribute__((aligned(16))) float sm[GL_IMG_FLOATS];
     const TlImg im = tl_stage_image(sm, a.img, GL_GROUPS, GL_BIAS);
@@ -791,21 +795,22 @@ __global__ __launch_bounds__(256) void k_lslc(LsArgs a) {
         const int pc = ok ? p : a.n_picks - 1;
         const float tp = a.tpick[pc], ph = a.phase[pc];
         const int ti = (int)floorf((tp - t0_) / dt_);                                     // :635
-        const int ipk = a.ipick[pc];
+        const int ipk = ROWS ? 0 : a.ipick[pc];
         long long base = ((long long)ipk * a.l_dt + ti) * LS_K;
         // the reference indexes the table with these and fails on an index outside it (module.py:635-640: a device-side assertion,
         // reported at the next synchronisation); here the index is clamped and the call that follows on the host raises
-        if (ok && (ti < 0 || ti >= a.l_dt || ipk < 0 || base + LS_K > a.n_edges) && a.flag != nullptr)
+        if (!ROWS && ok && (ti < 0 || ti >= a.l_dt || ipk < 0 || base + LS_K > a.n_edges) && a.flag != nullptr)
             __hip_atomic_fetch_or(a.flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         base = base < 0 ? 0 : (base > a.n_edges - LS_K ? a.n_edges - LS_K : base);
+        if (ROWS) base = (long long)pc * LS_K;
         f32x4 acc[2] = {tl_zero(), tl_zero()};
         float cnt = 0.f;
 #pragma unroll 2
         for (int k = 0; k < LS_K; ++k) {
-            const int e = a.A_edges[base + k];
-            const float rt = tp - a.tlatent[(long long)e * a.tl_stride + a.tl_col];
+            const int e = ROWS ? 0 : a.A_edges[base + k];
+            const float* row = ROWS ? a.s + (base + k) * LR_ROW : a.s + (long long)e * 30;
+            const float rt = tp - (ROWS ? row[30] : a.tlatent[(long long)e * a.tl_stride + a.tl_col]);
             const bool keep = ok && fabsf(rt) < 2.0f * a.eps;                             // :642-645
-            const float* row = a.s + (long long)e * 30;
             const f32x4 xb0 = tl_load30(row, 0, q), xb1 = tl_load30(row, 1, q);
             const float xs = q == 0 ? rt / a.eps : (q == 1 ? ph : 0.f);                   // columns 30, 31 of fc1
 #pragma unroll
@@ -827,6 +832,58 @@ __global__ __launch_bounds__(256) void k_lslc(LsArgs a) {
             og[0] = o.x; og[1] = o.y; og[2] = o.z;
             if (q < 3) og[3] = o.w;
         }
+    }
+}
+
+// The lookup half of k_lslc on a source-node-sharded model (genie_lslc_rows): the s rows live with the rank that owns their source
+// node. For both heads and every (pick, slot) of the time-pointer tables, the rank that owns the pointed-to product node appends one
+// row to its compact list: [0:30] the s row, [30] the theoretical arrival of the head's phase, [31] the bits of the entry number
+// (head * n_picks + pick) * K + slot. Sixteen lanes per entry (fifteen 8-byte pieces of the row + the two trailing words); list positions
+// come from one counter, so the ORDER of the list varies from run to run -- the consumer places rows by their entry number. An index
+// outside the table is clamped and reported exactly as k_lslc does; a table entry that is no product node is owned by nobody and
+// reported the same way.
+struct LrArgs {
+    int n_picks, l_dt, S, n_grid;
+    long long n_edges;
+    float t0, dt;
+    const float* dtp;
+    const float* s_own;           // [n_own * S, 30] rows of the owned source nodes, local node order
+    const int32_t* node_local;    // [n_grid] global source node -> local owned index, -1 = owned elsewhere
+    const int32_t* A_edges[2];    // P / S time-pointer tables [n_sta * l_dt * K], global product-node ids
+    const float* tlatent; int tl_stride;     // [n_grid * S][tl_stride], column = head
+    const float* tpick; const int32_t* ipick;
+    int32_t* count;               // [1], zeroed by the entry point
+    float* rows;                  // [2 * n_picks * K][LR_ROW]
+    unsigned* flag;
+};
+__global__ __launch_bounds__(256) void k_lslc_rows(LrArgs a) {
+    const int sub = threadIdx.x & 15;
+    const float t0_ = a.dtp ? a.dtp[0] : a.t0, dt_ = a.dtp ? a.dtp[1] - a.dtp[0] : a.dt;
+    const long long n_half = (long long)a.n_picks * LS_K, n_ent = 2 * n_half;
+    for (long long ent = (long long)blockIdx.x * 16 + (threadIdx.x >> 4); ent < n_ent; ent += (long long)gridDim.x * 16) {
+        const int head = ent >= n_half ? 1 : 0;
+        const long long rem = ent - head * n_half;
+        const int p = (int)(rem / LS_K), k = (int)(rem - (long long)p * LS_K);
+        const int ti = (int)floorf((a.tpick[p] - t0_) / dt_);                             // :635
+        const int ipk = a.ipick[p];
+        long long base = ((long long)ipk * a.l_dt + ti) * LS_K;
+        bool bad = ti < 0 || ti >= a.l_dt || ipk < 0 || base + LS_K > a.n_edges;
+        base = base < 0 ? 0 : (base > a.n_edges - LS_K ? a.n_edges - LS_K : base);
+        const int e = a.A_edges[head][base + k];
+        const int g = e / a.S;
+        int loc = -1;
+        if (e >= 0 && g < a.n_grid) loc = a.node_local[g];
+        else bad = true;
+        if (bad && sub == 0 && a.flag != nullptr) __hip_atomic_fetch_or(a.flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (loc < 0) continue;                                                             // (uniform over the entry's 16 lanes)
+        int slot = 0;
+        if (sub == 0) slot = atomicAdd(a.count, 1);
+        slot = __shfl(slot, 0, 16);
+        typedef float f32x2 __attribute__((ext_vector_type(2)));
+        const float* src = a.s_own + ((long long)loc * a.S + (e - g * a.S)) * 30;
+        float* dst = a.rows + (long long)slot * LR_ROW;
+        if (sub < 15) *(f32x2*)(dst + 2 * sub) = *(const f32x2*)(src + 2 * sub);
+        else *(f32x2*)(dst + 30) = f32x2{a.tlatent[(long long)e * a.tl_stride + head], __int_as_float((int)ent)};
     }
 }
 

@@ -247,6 +247,57 @@ class Transport(object):
         out.copy_(torch.stack(parts))
 
 
+    def all_gather_ragged(self, rows, count, timeout=60.0):
+        """Every rank's first `count` (device int32 [1]) rows of `rows` [cap, C], rank after rank: [sum of counts, C]. Counts first (one
+        read-back on every rank), then the rows padded to the longest count; a rank with no row joins both collectives. On the device
+        over RCCL; staged through the host over gloo, where each wait ends after `timeout` seconds."""
+        if self.emulate or not self.on:
+            if not self.emulate:
+                self._no_group()
+            return rows[: int(count.item())]
+        import datetime
+        dist, W, C = self.dist, self.world, rows.shape[1]
+        if self.device_collectives:
+            counts = torch.empty(W, dtype=count.dtype, device=count.device)
+            dist.all_gather_into_tensor(counts, count, group=self.group)
+            counts = counts.tolist()
+            n_max = max(counts)
+            if n_max == 0:
+                return rows[:0]
+            buf = rows.new_empty((W, n_max, C))
+            dist.all_gather_into_tensor(buf.view(-1, C), rows[:n_max], group=self.group)
+        else:
+            wait = datetime.timedelta(seconds=float(timeout))
+            parts = [torch.empty(1, dtype=count.dtype) for _ in range(W)]
+            dist.all_gather(parts, count.cpu(), group=self.group, async_op=True).wait(wait)
+            counts = [int(c) for c in parts]
+            n_max = max(counts)
+            if n_max == 0:
+                return rows[:0]
+            parts = [torch.empty((n_max, C), dtype=rows.dtype) for _ in range(W)]
+            dist.all_gather(parts, rows[:n_max].cpu(), group=self.group, async_op=True).wait(wait)
+            buf = torch.stack(parts).to(rows.device)
+        return torch.cat([buf[r, : counts[r]] for r in range(W)])
+
+
+def pointer_row_owners(a_edges, base, plan, n_sta, k=10):
+    """Which rank owns each of the `k` product nodes a pick's time-pointer entry lists: `a_edges` flat table of global product-node ids
+    (p = g * n_sta + s), `base` [n] the picks' entry numbers `ipick * l_dt + time bin` -> int64 [n, k] ranks. Pure numpy (the split the
+    ranks' `genie_lslc_rows` calls make between them)."""
+    e = np.asarray(a_edges).reshape(-1)[(np.asarray(base, dtype=np.int64).reshape(-1, 1) * k + np.arange(k)).reshape(-1)]
+    return plan.owner[e.astype(np.int64) // int(n_sta)].reshape(-1, k)
+
+
+def place_pick_rows(gathered, n_entries):
+    """The all-gathered compact lists of `genie_lslc_rows` ([m, 32]: row, arrival, bits of the entry number) PLACED at their entry
+    numbers in a zero table [n_entries, 32]. Every entry has one owner; adding instead would turn a -0.0 into +0.0."""
+    table = gathered.new_zeros((int(n_entries), gathered.shape[1]))
+    if gathered.shape[0]:
+        keys = gathered[:, 31].contiguous().view(torch.int32).long()
+        table.index_copy_(0, keys, gathered)
+    return table
+
+
 def exchange_halo_rows(rows_own, plan, n_sta, group=None, mode="a2a"):
     """Exchange of per-source-node row blocks: `rows_own` [n_own*S, C] -> halo rows [n_halo*S, C] in halo order: rank r sends, to
     every peer q, the S-row blocks of its owned nodes that q lists in `need[q][r]`. mode "a2a": one `all_to_all_single` with split
@@ -324,7 +375,10 @@ class ShardedPath(object):
         self._pitch = pitch
         # static exchange state: send-row index, send buffer, the halo part of `wv` inside the workspace (received in place)
         self._send_idx = torch.as_tensor(np.concatenate(p.send_local).astype(np.int64) if world > 1 else np.zeros(0, np.int64), device=dev)
-        self._send_buf = torch.empty((int(self._send_idx.numel()), S * pitch), dtype=torch.float32, device=dev)
+        self._send_bufs = {}             # row width -> send buffer (wv: 16 floats; the association heads' q2: 32)
+        nl = -np.ones(self.n_grid, dtype=np.int32)
+        nl[p.own_global] = np.arange(p.n_own, dtype=np.int32)
+        self.node_local = torch.as_tensor(nl, device=dev)          # global source node -> local owned index, -1 = owned elsewhere
         idx, n_max = gather_index(p)
         self._gather = (torch.as_tensor(idx, device=dev), n_max)
         self._bip_pad = torch.zeros((n_max, 15), dtype=torch.float32, device=dev)
@@ -398,27 +452,33 @@ class ShardedPath(object):
         return lp.ws[off: off + 4 * n].view(torch.float32).view(self.plan.n_ext * self.n_sta, self._pitch)
 
     def _exchange(self, wv):
-        """Pack the SEND rows, all-to-all, halo rows received in place (the halo part of `wv` is contiguous, grouped by owner)."""
+        """Pack the SEND rows, all-to-all, halo rows received in place (the halo part of `wv` is contiguous, grouped by owner). `wv`:
+        any per-product-node operand [n_ext * S, pitch] in the local row space (the workspace's wv rows, the association heads' q2)."""
         p, S = self.plan, self.n_sta
+        pitch = int(wv.shape[1])
+        send_buf = self._send_bufs.get(pitch)
+        if send_buf is None:
+            send_buf = self._send_bufs[pitch] = torch.empty((int(self._send_idx.numel()), S * pitch), dtype=torch.float32, device=self.device)
         if p.world == 1 and not self.transport.on and not self.transport.emulate:
             return                      # no process group at all. (With one, EVERY rank enters the collective, also a rank with
                                         # nothing to exchange and the single rank of a world-size-1 group: the RCCL code path of the
                                         # 1-GPU tests and of `bench.py --gpus 1 --mode sharded`)
-        blocks = wv[: p.n_own * S].view(p.n_own, S * self._pitch)
-        recv = wv[p.n_own * S:].view(p.n_halo, S * self._pitch)
+        blocks = wv[: p.n_own * S].view(p.n_own, S * pitch)
+        recv = wv[p.n_own * S:].view(p.n_halo, S * pitch)
         if self.halo == "p2p":       # bucketed by destination: pack of peer q + 1 under the transfer of peer q, largest pair first
             if getattr(self, "_send_idx_q", None) is None:
                 self._send_idx_q = [torch.as_tensor(x.astype(np.int64), device=self.device) for x in p.send_local]
-            self.transport.halo_p2p_rows(recv, self._send_buf, p.recv_counts, p.send_counts, p.rank,
+            self.transport.halo_p2p_rows(recv, send_buf, p.recv_counts, p.send_counts, p.rank,
                                          pack=lambda q, view: torch.index_select(blocks, 0, self._send_idx_q[q], out=view))
             return
         if self._send_idx.numel():
-            torch.index_select(blocks, 0, self._send_idx, out=self._send_buf)
-        self.transport.all_to_all_rows(recv, self._send_buf, p.recv_counts, p.send_counts)
+            torch.index_select(blocks, 0, self._send_idx, out=send_buf)
+        self.transport.all_to_all_rows(recv, send_buf, p.recv_counts, p.send_counts)
 
-    def front(self, Slice_ext, Mask_ext, edge_attr_own):
-        """Sharded DataAggregation + Bipartite of one window on the current stream (+ the communication stream): returns the
-        all-gathered Bipartite output `[G, 15]` in global order, produced on the current stream."""
+    def front(self, Slice_ext, Mask_ext, edge_attr_own, x_latent_out=None):
+        """Sharded DataAggregation + Bipartite of one window on the current stream (+ the communication stream): returns this rank's
+        Bipartite output `[n_own, 15]`, produced on the current stream. `x_latent_out` [n_own * S, 30]: the DataAggregation output of
+        the owned rows is written there too (the association heads' input)."""
         p, S = self.plan, self.n_sta
         lp = self.local
         lp.check_input_range()         # (verdicts of the windows that have completed: engine.HipPath.check_input_range)
@@ -438,7 +498,7 @@ class ShardedPath(object):
         if not self.overlap or (p.world == 1 and not self.transport.on and not self.transport.emulate):
             lp.da_stage1_range(Slice_ext, Mask_ext, 0, n, True)
             self._exchange(wv)
-            lp.da_stage2_partials_range(Mask_own, edge_attr_own, 0, n)
+            lp.da_stage2_partials_range(Mask_own, edge_attr_own, 0, n, x_latent_out)
         else:
             comm = self.comm_stream
             lp.da_stage1_range(Slice_ext, Mask_ext, s0, s1, True)                 # rows other ranks wait for
@@ -450,10 +510,10 @@ class ShardedPath(object):
                 halo = torch.cuda.Event()
                 halo.record(comm)
             lp.da_stage1_range(Slice_ext, Mask_ext, s1, n, False)                 # under the exchange
-            lp.da_stage2_partials_range(Mask_own, edge_attr_own, 0, n0)           # nodes without halo neighbours
-            lp.da_stage2_partials_range(Mask_own, edge_attr_own, n1, n)
+            lp.da_stage2_partials_range(Mask_own, edge_attr_own, 0, n0, x_latent_out)           # nodes without halo neighbours
+            lp.da_stage2_partials_range(Mask_own, edge_attr_own, n1, n, x_latent_out)
             main.wait_event(halo)
-            lp.da_stage2_partials_range(Mask_own, edge_attr_own, n0, n1)
+            lp.da_stage2_partials_range(Mask_own, edge_attr_own, n0, n1, x_latent_out)
         bip_own = lp.bipartite_readout()
         return bip_own
 
@@ -468,6 +528,26 @@ class ShardedPath(object):
         self.transport.all_gather_rows(buf, pad if pad is not None else bip_own)
         o = self.full.spatial_agg3(buf.view(-1, 15).index_select(0, idx_t), pos_global)
         return o if tail is None else tail(o)
+
+    def assoc_fwd(self, y_latent, mask_src, x_latent_own, Mask_own, edge_attr_own):
+        """The P-sized association heads on the shard (`HipPath.assoc_fwd_parts`): replicated y_latent [G, 30] / mask_src [G], this
+        rank's x_latent / Mask / edge_attr rows -> s [n_own * S, 30]. Two halo exchanges on the current stream, one per layer: the q2
+        rows (32 floats) before layer 1, the wv rows before the last pass -- the plan and transport of the DataAggregation window. Call
+        after `front` of the same window."""
+        own = getattr(self, "_own_idx", None)
+        if own is None:
+            own = self._own_idx = torch.as_tensor(self.plan.own_global, dtype=torch.int64, device=self.device)
+        y_own = engine._f32(y_latent, "y_latent", (self.n_grid, 30)).index_select(0, own)
+        m_own = engine._f32(mask_src, "mask_src").reshape(-1).index_select(0, own)
+        return self.local.assoc_fwd_parts(y_own, m_own, x_latent_own, Mask_own, edge_attr_own, self._exchange,
+                                          lambda: self._exchange(self.wv_view()))
+
+    def pick_rows(self, s_own, a_edges_p, a_edges_s, dt_partition, tpick, ipick, tlatent, timeout=60.0):
+        """The rows of `s` and `tlatent` that the picks' time-pointer entries list, for both LocalSliceLgCollapse heads, from the
+        ranks that own them: `HipPath.lslc_rows` on this rank's rows, ONE ragged all-gather of the compact lists, every row placed at
+        its entry number -> table [2 * n_picks * 10, 32] (`HipPath.lslc_fwd_rows` takes it), the same on every rank."""
+        count, rows = self.local.lslc_rows(s_own, self.node_local, a_edges_p, a_edges_s, dt_partition, tpick, ipick, tlatent)
+        return place_pick_rows(self.transport.all_gather_ragged(rows, count, timeout), rows.shape[0])
 
     def path_fwd(self, Slice_ext, Mask_ext, edge_attr_own, pos_global, tail=None, pipelined=False):
         """Slice_ext / Mask_ext: [n_ext*S, 4] rows of owned then halo source nodes (local order). Returns x_spatial [G,30]

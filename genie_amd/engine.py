@@ -732,9 +732,10 @@ class HipPath(object):
         _lib.check(self.lib.genie_da_stage1_range(self.ctx, _ptr(Slice), _ptr(Mask), int(gi_begin), int(gi_end), 1 if first else 0,
                                                   self._ws_ptr, _stream()), "genie_da_stage1_range")
 
-    def da_stage2_partials_range(self, Mask, edge_attr, gi_begin, gi_end):
-        """Stage-2 partials of the owned source nodes at positions [gi_begin, gi_end) (genie_da_stage2_partials_range)."""
-        _lib.check(self.lib.genie_da_stage2_partials_range(self.ctx, _ptr(Mask), _ptr(edge_attr), None, int(gi_begin), int(gi_end),
+    def da_stage2_partials_range(self, Mask, edge_attr, gi_begin, gi_end, x_latent_out=None):
+        """Stage-2 partials of the owned source nodes at positions [gi_begin, gi_end) (genie_da_stage2_partials_range); `x_latent_out`
+        [n_prod, 30]: the DataAggregation output of those nodes' rows is written there too."""
+        _lib.check(self.lib.genie_da_stage2_partials_range(self.ctx, _ptr(Mask), _ptr(edge_attr), _ptr(x_latent_out), int(gi_begin), int(gi_end),
                                                            self._ws_ptr, _stream()), "genie_da_stage2_partials_range")
 
     def bipartite_readout(self):
@@ -1102,6 +1103,80 @@ class HipPath(object):
         out = torch.empty((P, 30), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.genie_assoc_fwd(self.ctx, _ptr(y_latent), _ptr(mask_src), _ptr(x_latent), _ptr(Mask), _ptr(edge_attr),
                                             _ptr(out), _ptr(assoc_ws), self._ws_ptr, _stream()), "genie_assoc_fwd")
+        return out
+
+    def assoc_q2_view(self, assoc_ws):
+        """Float view [n_prod_ext, 32] of q2 inside `assoc_ws`: what layer 1 of the association heads gathers from neighbouring source
+        nodes; a shard's owned rows, then its halo rows (genie_assoc_halo_offset)."""
+        end = int(self.lib.genie_assoc_halo_offset(self.ctx)) // 4
+        return assoc_ws[end - 32 * self.n_prod: end + 32 * (self.n_prod_ext - self.n_prod)].view(self.n_prod_ext, 32)
+
+    def assoc_fwd_parts(self, y_latent, mask_src, x_latent, Mask, edge_attr, exchange_q2, exchange_wv):
+        """`assoc_fwd` on a source-node shard (genie_assoc_fwd_part): y_latent / mask_src of the OWNED source nodes in local order, the
+        other inputs and the result [n_own * S, .] the owned product-node rows. `exchange_q2(q2 [n_prod_ext, 32])` and `exchange_wv()`
+        fill the halo rows of the two gather operands between the layers (dist.ShardedPath)."""
+        self._need_assoc()
+        P = self.n_prod
+        y_latent = _f32(y_latent, "y_latent", (self.n_grid, 30))
+        mask_src = _f32(mask_src, "mask_src").reshape(-1)
+        if mask_src.numel() != self.n_grid:
+            raise ValueError("mask_src must have n_grid entries")
+        x_latent = _f32(x_latent, "x_latent", (P, 30))
+        Mask = _f32(Mask, "Mask", (P, 4))
+        edge_attr = _f32(edge_attr, "edge_attr", (P, 3))
+        self._refresh_static_edge_attr(edge_attr)
+        assoc_ws = self._scratch("_assoc_ws", (int(self.lib.genie_assoc_workspace_bytes(self.ctx)) + 3) // 4)
+        out = torch.empty((P, 30), dtype=torch.float32, device=self.device)
+
+        def part(k):
+            _lib.check(self.lib.genie_assoc_fwd_part(self.ctx, k, _ptr(y_latent), _ptr(mask_src), _ptr(x_latent), _ptr(Mask), _ptr(edge_attr),
+                                                     _ptr(out), _ptr(assoc_ws), self._ws_ptr, _stream()), "genie_assoc_fwd_part")
+        part(0)
+        exchange_q2(self.assoc_q2_view(assoc_ws))
+        part(1)
+        exchange_wv()
+        part(2)
+        return out
+
+    def lslc_rows(self, s_own, node_local, a_edges_p, a_edges_s, dt_partition, tpick, ipick, tlatent):
+        """The lookup half of both `lslc_fwd` heads on a source-node shard (genie_lslc_rows): s_own [n_own * S, 30], node_local int32
+        [G] (global source node -> local owned index, -1 elsewhere), the two int32 tables of GLOBAL product-node ids, tlatent [G * S, >= 2]
+        -> (count int32 [1] on the device, rows [2 * n * 10, 32]): the entries this rank owns, in no particular order; column 31 holds
+        the bits of the entry number (head * n + pick) * 10 + slot."""
+        s_own = _f32(s_own, "s_own", (self.n_prod, 30))
+        tpick = _f32(tpick, "tpick").reshape(-1)
+        n = int(tpick.numel())
+        tlatent = _f32(tlatent, "tlatent")
+        G = int(node_local.numel())
+        if (a_edges_p.dtype != torch.int32 or a_edges_s.dtype != torch.int32 or not a_edges_p.is_cuda or not a_edges_s.is_cuda
+                or a_edges_p.numel() != a_edges_s.numel() or ipick.dtype != torch.int32 or ipick.numel() != n
+                or node_local.dtype != torch.int32 or not node_local.is_cuda or tlatent.dim() != 2 or tlatent.shape[0] != G * self.n_sta
+                or tlatent.shape[1] < 2):
+            raise ValueError("lslc_rows: a_edges_p / a_edges_s (equal sizes), ipick and node_local must be int32 GPU tensors, one ipick per "
+                             "pick, tlatent [n_grid * n_sta, >= 2] over the whole product graph")
+        a_edges_p, a_edges_s, ipick, node_local = a_edges_p.contiguous(), a_edges_s.contiguous(), ipick.contiguous(), node_local.contiguous()
+        self.check_index_flags()
+        t0, dt, dtp, l_dt = time_partition(dt_partition)
+        count = torch.empty(1, dtype=torch.int32, device=self.device)
+        rows = torch.empty((2 * n * 10, 32), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.genie_lslc_rows(self.ctx, _ptr(s_own), _ptr(node_local), G, _ptr(a_edges_p), _ptr(a_edges_s),
+                                            int(a_edges_p.numel()), l_dt, t0, dt, _ptr(dtp), _ptr(tlatent), int(tlatent.shape[1]), _ptr(tpick),
+                                            _ptr(ipick), n, _ptr(count), _ptr(rows), _stream()), "genie_lslc_rows")
+        return count, rows
+
+    def lslc_fwd_rows(self, head, table, tpick, phase_label, eps):
+        """The rest of `lslc_fwd` on the gathered rows (genie_lslc_fwd_rows): table [2 * n * 10, 32] (both heads, rows placed at their
+        entry numbers) -> [n, 15] of head `head`."""
+        self._need_assoc()
+        tpick = _f32(tpick, "tpick").reshape(-1)
+        n = int(tpick.numel())
+        phase_label = _f32(phase_label, "phase_label").reshape(-1)
+        table = _f32(table, "table", (2 * n * 10, 32))
+        if phase_label.numel() != n:
+            raise ValueError("lslc_fwd_rows: one phase_label per pick")
+        out = torch.empty((n, 15), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.genie_lslc_fwd_rows(self.ctx, int(head), _ptr(table), float(eps), _ptr(tpick), _ptr(phase_label), n, _ptr(out),
+                                                _stream()), "genie_lslc_fwd_rows")
         return out
 
     def assoc_train_fwd(self, y_latent, mask_src, x_latent, Mask, edge_attr):

@@ -509,7 +509,8 @@ class GCN_Detection_Network_extended(nn.Module):
     per GPU, RCCL over xGMI) makes the SAME calls run source-node sharded: `set_adjacencies*` build this rank's shard plan and contexts,
     `forward_fixed_source` takes the reference's arguments and returns the replicated `(y, x)` -- bit-equal to the unsharded model --,
     `embed_window` / `node_rows` / `genie_amd.apply` produce and consume only the rank's owned + halo rows. `forward` / `forward_fixed`
-    (association heads) and training steps are not sharded and raise.
+    (association heads) run sharded in eval mode / under no_grad with the default model definition, `(y, x, arv_p, arv_s)` replicated and
+    bit-equal too; training steps are not sharded and raise.
     """
 
     def __init__(self, ftrns1, ftrns2, scale_rel=SCALE_REL, use_absolute_pos=False, device="cuda",
@@ -662,7 +663,8 @@ class GCN_Detection_Network_extended(nn.Module):
     def _not_sharded(self, what):
         if self._shard_cfg is not None:
             raise NotImplementedError("%s is not available on a source-node-sharded model (process_group / shard): the sharded calls are "
-                                      "set_adjacencies*, forward_fixed_source[_pipelined], embed_window, node_rows and genie_amd.apply" % what)
+                                      "set_adjacencies*, forward_fixed_source[_pipelined], forward / forward_fixed (eval mode, default model "
+                                      "definition), embed_window, node_rows and genie_amd.apply" % what)
 
     def set_adjacencies(self, A_in_sta, A_in_src, A_src_in_edges, A_Lg_in_src, A_src_in_sta, A_src, A_edges_p,
                         A_edges_s, dt_partition, tlatent, pos_loc, pos_src, _defer_checks=False):
@@ -991,10 +993,16 @@ class GCN_Detection_Network_extended(nn.Module):
         in HIP: the shared front and read-outs, the P-sized association heads (genie_assoc_fwd; under use_updated_model_definition
         / use_absolute_pos their static per-station / per-source-node terms are added inside the same kernels), LocalSliceLgCollapse
         P / S (genie_lslc_fwd) and the arrival head (genie_arrivals_fwd). In train() mode with gradients enabled the same modules
-        differentiate in HIP (`_PathTrain`, `_AssocTrain`, `_LslcTrain`, `_ArrivalsTrain`; all three model definitions on Cartesian product graphs, the default one on irregular ones too)."""
+        differentiate in HIP (`_PathTrain`, `_AssocTrain`, `_LslcTrain`, `_ArrivalsTrain`; all three model definitions on Cartesian product
+        graphs, the default one on irregular ones too).
+        On a source-node-sharded model (eval mode / no_grad, default model definition): `Slice` / `Mask` in every form
+        `forward_fixed_source` takes, everything else the same on every rank; the four outputs are replicated and bit-equal to the
+        unsharded model's (`_forward_fixed_sharded`)."""
         if self._hip is None:
             raise RuntimeError("call set_adjacencies(...) before forward_fixed")
-        self._not_sharded("forward / forward_fixed (the association heads)")
+        if self._shard_cfg is not None:
+            return self._forward_fixed_sharded(Slice, Mask, tpick, ipick, phase_label, x_temp_cuda_cart, x_query_cart, x_query_src_cart,
+                                               t_query, tq_sample, trv_out_q)
         if getattr(self, "A_edges_p", None) is None or getattr(self, "tlatent", None) is None:
             raise RuntimeError("forward_fixed needs the time-pointer tables and travel times (A_edges_p, A_edges_s, dt_partition, tlatent) "
                                "of set_adjacencies(...) / set_adjacencies_base(...)")
@@ -1027,18 +1035,8 @@ class GCN_Detection_Network_extended(nn.Module):
         if len(tpick) == 0:      # no pick in the window: the reference returns two empty [n_src, 0, 1] tensors
             e = s.new_zeros((n_src, 0, 1))
             return y, x, e, e.clone()
-        # :991-992 (genie_lslc_fwd); the int32 copies of the static time-pointer tables are cached with the tables
-        key = (self.A_edges_p.data_ptr(), self.A_edges_s.data_ptr(), self.A_edges_p._version, self.A_edges_s._version)
-        if getattr(self, "_a_edges_key", None) != key:
-            self._a_edges_i32 = (self.A_edges_p.to(s.device).to(torch.int32).contiguous(),
-                                 self.A_edges_s.to(s.device).to(torch.int32).contiguous())
-            self._a_edges_key, self._a_edges_refs = key, (self.A_edges_p, self.A_edges_s)
+        dth = self._pointer_tables(s.device)      # :991-992 (genie_lslc_fwd)
         ip32, tl, eps = ipick.to(torch.int32), self.tlatent, self.LocalSliceLgCollapseP.eps
-        dtp = self.dt_partition                   # in the form the lslc calls take it (a GPU tensor stays on the device: no read-back)
-        dkey = (dtp.data_ptr(), dtp._version) if torch.is_tensor(dtp) else id(dtp)
-        if getattr(self, "_dt_host_key", None) != dkey:
-            self._dt_host, self._dt_host_key, self._dt_host_ref = _engine.time_partition(dtp), dkey, dtp
-        dth = self._dt_host
         if train:
             arv_p, arv_s = _LslcTrain.apply(s, self._a_edges_i32[0], self._a_edges_i32[1], dth, _engine._f32(tpick, "tpick"),
                                             ip32, _engine._f32(phase_label, "phase_label"), _engine._f32(tl, "tlatent"), eps, hp,
@@ -1050,6 +1048,72 @@ class GCN_Detection_Network_extended(nn.Module):
             arv_s = hp.lslc_fwd(1, s, self._a_edges_i32[1], dth, tpick, ip32, phase_label, tl, 1, eps)
             arv = hp.arrivals_fwd(tq_sample, x_src, trv_out_q, arv_p, arv_s, tpick, ipick, phase_label, self.Arrivals.eps)   # :993
         return y, x, arv[:, :, 0].unsqueeze(-1), arv[:, :, 1].unsqueeze(-1)                          # :995-997
+
+    def _pointer_tables(self, device):
+        """The int32 copies of the static time-pointer tables (`self._a_edges_i32`, cached with the tables) and the time partition in the
+        form the lslc calls take it (returned; a GPU tensor stays on the device: no read-back)."""
+        key = (self.A_edges_p.data_ptr(), self.A_edges_s.data_ptr(), self.A_edges_p._version, self.A_edges_s._version)
+        if getattr(self, "_a_edges_key", None) != key:
+            self._a_edges_i32 = (self.A_edges_p.to(device).to(torch.int32).contiguous(),
+                                 self.A_edges_s.to(device).to(torch.int32).contiguous())
+            self._a_edges_key, self._a_edges_refs = key, (self.A_edges_p, self.A_edges_s)
+        dtp = self.dt_partition
+        dkey = (dtp.data_ptr(), dtp._version) if torch.is_tensor(dtp) else id(dtp)
+        if getattr(self, "_dt_host_key", None) != dkey:
+            self._dt_host, self._dt_host_key, self._dt_host_ref = _engine.time_partition(dtp), dkey, dtp
+        return self._dt_host
+
+    def _sharded_forward_guard(self, A_edges_p, A_edges_s, tlatent):
+        """What `forward` / `forward_fixed` on a source-node-sharded model do not serve, refused before anything touches a GPU."""
+        if self._differentiable():
+            self._not_sharded("a training step (train() mode with gradients enabled; use eval() / no_grad)")
+        if self.use_updated_model_definition or self.use_absolute_pos:
+            raise NotImplementedError("forward / forward_fixed with use_updated_model_definition / use_absolute_pos is not available on a "
+                                      "source-node-sharded model (process_group / shard): the sharded association heads serve the default "
+                                      "model definition")
+        if A_edges_p is None or A_edges_s is None or tlatent is None:
+            self._not_sharded("forward / forward_fixed without the time-pointer tables and travel times of the WHOLE product graph (pass A_edges_p, "
+                              "A_edges_s, dt_partition, tlatent to set_adjacencies / set_adjacencies_base; time_pointers= is not built on a shard)")
+
+    def _forward_fixed_sharded(self, Slice, Mask, tpick, ipick, phase_label, x_temp_cuda_cart, x_query_cart, x_query_src_cart, t_query,
+                               tq_sample, trv_out_q):
+        """`forward_fixed` on this rank's shard (genie_amd/dist.py). The front leaves the owned rows of x_latent; the replicated tail gives
+        every rank y, y_latent, x and x_src; the P-sized association heads run on the owned rows with one halo exchange per layer
+        (`ShardedPath.assoc_fwd`); the rows the picks' time-pointer entries list travel in ONE ragged all-gather from their owners
+        (`ShardedPath.pick_rows`, genie_lslc_rows), and the pick-sized heads run replicated on them. Every rank joins every collective,
+        whatever it owns."""
+        self._sharded_forward_guard(getattr(self, "A_edges_p", None), getattr(self, "A_edges_s", None), getattr(self, "tlatent", None))
+        sp, full = self._shard, self._hip
+        sp.sync_weights(self._path_params, self._weight_split())
+        if not (getattr(sp.local, "assoc_ready", False) and getattr(full, "assoc_ready", False)):
+            raise _engine._lib.GenieHipError("the association heads' parameters are not in the HIP context (unexpected shapes)")
+        full.check_input_range()                  # (the local context's verdicts: `ShardedPath.front`, `HipPath.lslc_rows`)
+        S, n_own = sp.n_sta, sp.plan.n_own
+        Slice_ext, Mask_ext = sp.local_rows(Slice, "Slice", 4), sp.local_rows(Mask, "Mask", 4)
+        x_latent = torch.empty((n_own * S, 30), dtype=torch.float32, device=sp.device)
+        bip_own = sp.front(Slice_ext, Mask_ext, self._edge_attr, x_latent_out=x_latent)                 # :973-976, owned rows
+        x_spatial = sp.gather_and_tail(bip_own, x_temp_cuda_cart)                                       # :977, replicated from here
+        y, y_latent = full.readout_grid_latent(x_spatial, t_query)                                      # :978-979
+        knn = self.SpatialAttention.query_table(x_query_cart, x_temp_cuda_cart, 10)
+        x = full.readout_query(x_spatial, x_temp_cuda_cart, x_query_cart, knn, t_query)                 # :980, :982
+        knn_src = _engine.knn_device(x_temp_cuda_cart, x_query_src_cart, 10)
+        x_src = full.spatial_attention(x_spatial, x_temp_cuda_cart, x_query_src_cart, knn_src, t_query) # :981
+        mask_out = 1.0 * (y[:, :, 0].detach().max(1, keepdim=True)[0] > 0.01)                           # :985
+        Mask_own = _engine._f32(Mask_ext, "Mask")[: n_own * S]
+        s_own = sp.assoc_fwd(y_latent, mask_out, x_latent, Mask_own, self._edge_attr)                   # :986-990, owned rows
+        n_src = int(x_query_src_cart.shape[0])
+        if not self.use_phase_types:      # module.py:632-633, :706-707
+            phase_label = phase_label * 0.0
+        if len(tpick) == 0:      # no pick in the window (the same on every rank): no collective follows
+            e = s_own.new_zeros((n_src, 0, 1))
+            return y, x, e, e.clone()
+        dth = self._pointer_tables(sp.device)
+        table = sp.pick_rows(s_own, self._a_edges_i32[0], self._a_edges_i32[1], dth, tpick, ipick.to(torch.int32), self.tlatent)
+        eps = self.LocalSliceLgCollapseP.eps
+        arv_p = full.lslc_fwd_rows(0, table, tpick, phase_label, eps)                                   # :991
+        arv_s = full.lslc_fwd_rows(1, table, tpick, phase_label, eps)                                   # :992
+        arv = full.arrivals_fwd(tq_sample, x_src, trv_out_q, arv_p, arv_s, tpick, ipick, phase_label, self.Arrivals.eps)   # :993
+        return y, x, arv[:, :, 0].unsqueeze(-1), arv[:, :, 1].unsqueeze(-1)                             # :995-997
 
     def invalidate_graph_cache(self):
         """Forget the graphs `forward` cached (next call rebuilds the HIP context) and the cached query kNN table."""
@@ -1063,8 +1127,11 @@ class GCN_Detection_Network_extended(nn.Module):
         train_GENIE_model.py:1786). The HIP context is rebuilt when any tensor that defines the graphs (edge lists, product
         node list, positions) changes address, shape or in-place version; the cache holds those tensors, so an address cannot
         be recycled while it is the key. The per-call tensors that do not shape the context (edge_attr, time-pointer tables,
-        tlatent) are simply taken from this call. `invalidate_graph_cache()` forces a rebuild."""
-        self._not_sharded("forward / forward_fixed (the association heads)")
+        tlatent) are simply taken from this call. `invalidate_graph_cache()` forces a rebuild. On a source-node-sharded model the graphs
+        are checked up front (no deferred verdicts) and the call ends in the sharded `forward_fixed`."""
+        sharded = self._shard_cfg is not None
+        if sharded:
+            self._sharded_forward_guard(A_edges_p, A_edges_s, tlatent)
 
         def tk(t):
             return (t.data_ptr(), t._version, tuple(t.shape), t.dtype) if torch.is_tensor(t) else id(t)
@@ -1081,7 +1148,7 @@ class GCN_Detection_Network_extended(nn.Module):
             # discarded forward + a second build, so the model remembers and builds with the checks up front from then on
             self._retire_later = []
             try:
-                if getattr(self, "_defer_failed", False):
+                if sharded or getattr(self, "_defer_failed", False):
                     self.set_adjacencies(*adj)
                 else:
                     try:
@@ -1100,7 +1167,15 @@ class GCN_Detection_Network_extended(nn.Module):
         else:
             self.A_src_in_edges, self.A_Lg_in_src = A_src_in_edges, A_Lg_in_src
             self.A_edges_p, self.A_edges_s, self.dt_partition, self.tlatent = A_edges_p, A_edges_s, dt_partition, tlatent
-            ea = _engine._f32(A_src_in_edges.x, "A_src_in_edges.x", tuple(self._edge_attr.shape))
+            if sharded:           # this rank's owned rows of the call's edge_attr, cut out again only when the caller's tensor changed
+                xk = tk(A_src_in_edges.x)
+                if getattr(self, "_edge_attr_src", None) != xk:
+                    ea = self._shard.local_rows(A_src_in_edges.x, "A_src_in_edges.x", 3, own_only=True).contiguous()
+                    self._edge_attr, self._edge_attr_version, self._edge_attr_src = ea, ea._version, xk
+                    self._shard.local.set_static_edge_attr(ea)
+                ea = self._edge_attr
+            else:
+                ea = _engine._f32(A_src_in_edges.x, "A_src_in_edges.x", tuple(self._edge_attr.shape))
             if ea.data_ptr() != self._edge_attr.data_ptr() or ea._version != getattr(self, "_edge_attr_version", None):
                 self._edge_attr, self._edge_attr_version = ea, ea._version
                 self._hip.set_static_edge_attr(ea)

@@ -419,7 +419,7 @@ int genie_train_bwd(genie_ctx* ctx, const float* slice, const float* mask, const
  * (module.py:986-990): BipartiteGraphReadOutOperator (:333-352) followed by DataAggregationAssociationPhase (:356-403).
  *   y_latent [n_grid, 30] (SpatialDirect output), mask_src [n_grid] (`mask_out`, :985), x_latent [P, 30] (DataAggregation
  *   output, detached at :990), mask [P, 4], edge_attr [P, 3]  ->  out [P, 30]
- * assoc_ws: genie_assoc_workspace_bytes(ctx) bytes of scratch (16-byte aligned; tr / q1 / q2 rows). The call reuses the c / wu /
+ * assoc_ws: genie_assoc_workspace_bytes(ctx) bytes of scratch (16-byte aligned; tr / q1 rows [P][32], q2 rows [P_ext][32]). The call reuses the c / wu /
  * wv buffers of the current workspace slot: issue it after the DataAggregation stage 2 of the same window. Parameters under
  * their state_dict names ("BipartiteGraphReadOutOperator.*", "DataAggregationAssociationPhase.*"; the static-term columns of the two
  * other model definitions under "<name>_pos" / "<name>_abs", as for DataAggregation).
@@ -427,6 +427,21 @@ int genie_train_bwd(genie_ctx* ctx, const float* slice, const float* mask, const
 size_t genie_assoc_workspace_bytes(const genie_ctx* ctx);
 int genie_assoc_fwd(genie_ctx* ctx, const float* y_latent, const float* mask_src, const float* x_latent, const float* mask,
                     const float* edge_attr, float* out, void* assoc_ws, void* ws, void* stream);
+
+/* genie_assoc_fwd on a source-node shard (a context with n_grid_ext > n_grid; Cartesian product graphs), cut where a layer gathers rows
+ * of neighbouring source nodes, which for the halo nodes another rank computes. Same arguments; y_latent / mask_src are the rows of the
+ * OWNED source nodes in local order, x_latent / mask / edge_attr / out the owned product-node rows [n_grid * n_sta, .].
+ *   part 0: the per-node front (k_assoc_pre, k_assoc_a) over the owned rows. Leaves q2, the operand of layer 1's source-side mean, in
+ *           assoc_ws: [n_grid_ext * n_sta][32] floats at byte offset genie_assoc_halo_offset(ctx) - 128 * n_grid * n_sta, owned rows first.
+ *           The caller fills the halo rows (from genie_assoc_halo_offset(ctx) on, halo order) with their owners' rows before part 1.
+ *   part 1: layer 1 and the node-local half of layer 2 (k_assoc_b) over the owned rows; reads q2 in the extended row space. Leaves
+ *           layer 2's gather operand in the workspace's wv rows (genie_ws_v_ptr), whose halo rows the caller fills before part 2.
+ *   part 2: the second pair of neighbour means (the stage-2 kernel) -> out.
+ * A node's neighbour rows are accumulated in the order of its in-edges, as genie_assoc_fwd does: the result does not depend on how the
+ * source nodes are split. On an unsharded context the three parts in sequence are genie_assoc_fwd. */
+size_t genie_assoc_halo_offset(const genie_ctx* ctx);
+int genie_assoc_fwd_part(genie_ctx* ctx, int part, const float* y_latent, const float* mask_src, const float* x_latent, const float* mask,
+                         const float* edge_attr, float* out, void* assoc_ws, void* ws, void* stream);
 
 /* Exact k nearest neighbours on the device, replacing the reference's `torch_cluster.knn(x_context / scale, x_query / scale, k)`
  * calls: out_idx [n_query, k] int32 = indices into x_context of the k nearest context points of every query, nearest first
@@ -473,6 +488,24 @@ int genie_assoc_train_bwd(genie_ctx* ctx, const float* y_latent, const float* ma
 int genie_lslc_fwd(genie_ctx* ctx, int phase_head, const float* s_rows, const int32_t* a_edges, int64_t n_edges, int l_dt, float t0,
                    float dt, const float* dt_partition, float eps, const float* tlatent, int tl_stride, int tl_col, const float* tpick,
                    const int32_t* ipick, const float* phase_label, int n_picks, float* out, void* stream);
+
+/* genie_lslc_fwd on a source-node shard, in two halves around one all-gather: the rows of `s` a pick's table entry points to live with
+ * the ranks that own their source nodes.
+ * genie_lslc_rows (on the shard's context): the lookup of genie_lslc_fwd for BOTH heads. s_own [n_grid * n_sta, 30] = the association
+ * embedding of the owned source nodes (local node order), node_local int32 [n_grid_all]: global source node -> local owned index or -1,
+ * a_edges_p / a_edges_s [n_edges] the two tables (GLOBAL product-node ids), tlatent [n_grid_all * n_sta][tl_stride] with the P / S
+ * arrival in columns 0 / 1. For every entry (head, pick, slot) whose product node this rank owns, one row of 32 floats is appended to
+ * `rows` (room for 2 * n_picks * 10 rows): [0:30] the s row, [30] its theoretical arrival, [31] the BITS of the int32 entry number
+ * (head * n_picks + pick) * 10 + slot. count [1] int32 = rows written (zeroed by the call). The order of the list is unspecified; an
+ * index outside the table is clamped and reported through genie_index_flags as genie_lslc_fwd does, so is a table entry that is no
+ * product node (which no rank owns).
+ * genie_lslc_fwd_rows (on any context with the head's parameters): the rest of genie_lslc_fwd on table [2 * n_picks * 10][32], the
+ * ranks' rows placed at their entry numbers (every entry has one owner: place, never add). */
+int genie_lslc_rows(genie_ctx* ctx, const float* s_own, const int32_t* node_local, int n_grid_all, const int32_t* a_edges_p,
+                    const int32_t* a_edges_s, int64_t n_edges, int l_dt, float t0, float dt, const float* dt_partition, const float* tlatent,
+                    int tl_stride, const float* tpick, const int32_t* ipick, int n_picks, int32_t* count, float* rows, void* stream);
+int genie_lslc_fwd_rows(genie_ctx* ctx, int phase_head, const float* table, float eps, const float* tpick, const float* phase_label,
+                        int n_picks, float* out, void* stream);
 
 /* Backward of genie_lslc_fwd for training steps (round 3; k_lslc_bwd, forward recomputed per tile): d_out [n_picks, 15] -> the head's
  * fc1 / fc2 / PReLU-slope gradients ADDED into grad_blob (weight-mirror layout; zero it once before the two heads), the gradient of every
