@@ -94,6 +94,9 @@ SYMBOLS = [
     ("genie_assoc_train_fwd", _c.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("genie_assoc_train_bwd", _c.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("genie_knn", _c.c_int, [_P, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _P, _P]),
+    ("genie_knn_index_plan", _c.c_int, [_c.c_int, _P, _P]),
+    ("genie_knn_index_build", _c.c_int, [_P, _c.c_int, _P, _P, _P, _P, _P, _P]),
+    ("genie_knn_indexed", _c.c_int, [_P, _P, _P, _c.c_int, _P, _c.c_int, _c.c_int, _c.c_int, _P, _P]),
     ("genie_product_check", _c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _c.c_int, _c.c_int, _P, _P]),
     ("genie_lslc_fwd", _c.c_int, [_P, _c.c_int, _P, _P, _c.c_int64, _c.c_int, _c.c_float, _c.c_float, _P, _c.c_float, _P, _c.c_int, _c.c_int,
                                   _P, _P, _P, _c.c_int, _P, _P]),
@@ -140,6 +143,13 @@ SYMBOLS = [
     ("genie_embed_window_split", _c.c_int, [_P, _P, _P, _P, _c.c_int, _c.c_double, _c.c_double, _c.c_double, _c.c_double, _P, _P,
                                             _P, _P, _P, _P]),
 ]
+
+
+class KnnIndexPlan(_c.Structure):
+    """`genie_knn_index_plan_t` of include/genie_hip.h (passed by `ctypes.byref`)."""
+    _fields_ = [("cells", _c.c_int32 * 3), ("n_cells", _c.c_int32), ("origin", _c.c_float * 3), ("upper", _c.c_float * 3),
+                ("inv_cell", _c.c_float), ("reserved", _c.c_int32), ("cell", _c.c_double), ("cell_start_bytes", _c.c_int64),
+                ("records_bytes", _c.c_int64), ("scratch_bytes", _c.c_int64)]
 
 
 class GenieHipError(RuntimeError):

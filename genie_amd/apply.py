@@ -660,14 +660,19 @@ class GridLeg(object):
     set on that grid, the grid's Cartesian node positions and its travel-time table `x_grids_trv[x_grid_ind]` [G, S, 2] resident on the
     device ([N, 2] rows per listed product node for a `use_subgraph` model: `pairs` [2, N] = `A_src_in_sta`)."""
 
-    def __init__(self, net, x_grid_cart, trv_times, pairs=None, ind_use=None):
-        """`trv_times` [G, S', 2]: with `ind_use` the reference's table over ALL stations (`compute_travel_times(trv, locs, ...)`), cut to
+    def __init__(self, net, x_grid_cart, trv_times, pairs=None, ind_use=None, knn_index=False):
+        """`knn_index`: SETS the model's attribute of that name, to False too -- with True the per-source passes' query clouds are
+        searched through a cell index of this grid (`engine.KnnIndex`, built at the first cloud) instead of brute force, with bit-equal
+        results. The switch lives on the model, not on the leg: a leg built with the default turns off a `net.knn_index = True` set
+        before it, and of several legs that share one model the one built last decides.
+        `trv_times` [G, S', 2]: with `ind_use` the reference's table over ALL stations (`compute_travel_times(trv, locs, ...)`), cut to
         the model's stations here as process_utils.py:599 does (`trv_times[:, ind_use]`); without it the table must already be restricted
         to the model's stations, in the model's station order (its station axis is checked against the model's station count)."""
         self.net = net
         hp = net._hip
         if hp is None:
             raise RuntimeError("GridLeg: call net.set_adjacencies*(...) first")
+        net.knn_index = bool(knn_index)
         self.device = hp.device
         self.x_grid_cart = torch.as_tensor(x_grid_cart).float().to(self.device)
         trv_times = np.asarray(trv_times, dtype=np.float32)

@@ -1254,6 +1254,7 @@ __device__ __forceinline__ void gather_sum16(const float* __restrict__ base, lon
 #include "cloud_kernels.hpp"
 #include "optim_kernels.hpp"
 #include "pointer_kernels.hpp"
+#include "knn_index_kernels.hpp"
 
 }  // namespace
 
@@ -3888,6 +3889,136 @@ int genie_knn(const float* x_context, int n_context, const float* x_query, int n
     if (k <= 8) k_knn<8><<<nb, 256, 0, st>>>(x_context, n_context, x_query, n_query, k, exclude_self, out_idx);
     else if (k <= 10) k_knn<10><<<nb, 256, 0, st>>>(x_context, n_context, x_query, n_query, k, exclude_self, out_idx);
     else k_knn<16><<<nb, 256, 0, st>>>(x_context, n_context, x_query, n_query, k, exclude_self, out_idx);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+namespace {
+constexpr double KIX_OCCUPANCY = 4.0;              // mean points per cell the cell edge aims at
+constexpr long long KIX_MAX_CELLS = 1ll << 20;     // cap of the cell count: cell_start stays within 4 MB
+constexpr double KIX_EDGE_MIN = 1e-30, KIX_EDGE_MAX = 0x1p126;   // range of the cell edge: 1 / edge is a normal fp32 number
+constexpr double KIX_EXTENT_MAX = 1e38;           // longest box edge: x - origin stays finite in fp32 (the bound of k_knn_ix counts on it)
+
+bool flt_finite(float x) {                         // (-fno-honor-nans: the exponent bits are what can be tested)
+    uint32_t u;
+    memcpy(&u, &x, sizeof u);
+    return (u & 0x7f800000u) != 0x7f800000u;
+}
+
+// a plan as genie_knn_index_plan fills it -- the cell count and its cap, a finite box with origin <= upper, a normal positive fp32
+// factor, and cell == 1 / (double)inv_cell exactly, which the bound of k_knn_ix is made from: anything else never reaches a kernel
+bool kix_plan_ok(const genie_knn_index_plan_t* p) {
+    if (!p) return false;
+    long long cells = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (p->cells[a] < 1 || p->cells[a] > KIX_MAX_CELLS || !flt_finite(p->origin[a]) || !flt_finite(p->upper[a])) return false;
+        if (p->upper[a] < p->origin[a] || (double)p->upper[a] - (double)p->origin[a] > KIX_EXTENT_MAX) return false;
+        cells *= p->cells[a];
+        if (cells > KIX_MAX_CELLS) return false;
+    }
+    if (cells != p->n_cells || !flt_finite(p->inv_cell) || !(p->inv_cell >= 0x1p-126f)) return false;
+    const double cell = 1.0 / (double)p->inv_cell;
+    return memcmp(&cell, &p->cell, sizeof cell) == 0 && cell >= KIX_EDGE_MIN * 0.5 && cell <= KIX_EDGE_MAX * 2.0;
+}
+
+KixGrid kix_grid(const genie_knn_index_plan_t* p, int n_context) {
+    KixGrid g;
+    g.nc = n_context;
+    for (int a = 0; a < 3; ++a) { g.o[a] = p->origin[a]; g.hi[a] = p->upper[a]; g.n[a] = p->cells[a]; }
+    g.inv = p->inv_cell; g.h = p->cell;
+    return g;
+}
+}  // namespace
+
+int genie_knn_index_plan(int n_context, const float* bbox, genie_knn_index_plan_t* plan) {
+    if (n_context < 1 || !bbox || !plan) return fail(GENIE_ERR_ARG, "genie_knn_index_plan: n_context >= 1, a bounding box and a plan required");
+    double ext[3];
+    for (int a = 0; a < 3; ++a) {
+        if (!flt_finite(bbox[a]) || !flt_finite(bbox[3 + a]) || bbox[3 + a] < bbox[a])
+            return fail(GENIE_ERR_ARG, "genie_knn_index_plan: the bounding box is not finite (or its upper corner lies below its lower one)");
+        ext[a] = (double)bbox[3 + a] - (double)bbox[a];
+        if (ext[a] > KIX_EXTENT_MAX) return fail(GENIE_ERR_ARG, "genie_knn_index_plan: the bounding box is longer than 1e38 on an axis");
+    }
+    // The cell edge h: the volume of the axes that get more than one cell, over n / occupancy cells. An axis shorter than h (a
+    // zero-extent one always) gets one cell and leaves the estimate: at most three rounds.
+    bool act[3] = {ext[0] > KIX_EDGE_MIN, ext[1] > KIX_EDGE_MIN, ext[2] > KIX_EDGE_MIN};
+    double h = 1.0;
+    for (int round = 0; round < 3; ++round) {
+        int m = 0;
+        double lv = 0.0;                                 // log of the active volume (no overflow for any fp32 box)
+        for (int a = 0; a < 3; ++a)
+            if (act[a]) { ++m; lv += log(ext[a]); }
+        if (m == 0) break;
+        h = exp((lv + log(KIX_OCCUPANCY / (double)n_context)) / m);
+        bool dropped = false;
+        for (int a = 0; a < 3; ++a)
+            if (act[a] && ext[a] < h) { act[a] = false; dropped = true; }
+        if (!dropped) break;
+    }
+    h = std::min(std::max(h, KIX_EDGE_MIN), KIX_EDGE_MAX);
+    long long cells;
+    int n[3];
+    for (;;) {                                          // the cap: a longer edge until the cell count fits
+        cells = 1;
+        for (int a = 0; a < 3; ++a) {
+            n[a] = act[a] ? (int)std::min<double>(std::max(ceil(ext[a] / h), 1.0), (double)KIX_MAX_CELLS + 1.0) : 1;
+            cells = std::min<long long>(cells * n[a], KIX_MAX_CELLS + 1);
+        }
+        if (cells <= KIX_MAX_CELLS || h >= KIX_EDGE_MAX) break;
+        h = std::min(h * 1.25, KIX_EDGE_MAX);
+    }
+    if (cells > KIX_MAX_CELLS) return fail(GENIE_ERR_STATE, "internal: genie_knn_index_plan found no cell edge within the cap");
+    const float inv = (float)(1.0 / h);
+    for (int a = 0; a < 3; ++a) { plan->cells[a] = n[a]; plan->origin[a] = bbox[a]; plan->upper[a] = bbox[3 + a]; }
+    plan->n_cells = (int32_t)cells;
+    plan->inv_cell = inv;
+    plan->cell = 1.0 / (double)inv;
+    plan->cell_start_bytes = (int64_t)sizeof(int32_t) * (cells + 1);
+    plan->records_bytes = 16ll * n_context;
+    plan->scratch_bytes = (int64_t)sizeof(int32_t) * cells;
+    return GENIE_OK;
+}
+
+int genie_knn_index_build(const float* x_context, int n_context, float* bbox_dev, genie_knn_index_plan_t* plan, int32_t* cell_start,
+                          float* records, int32_t* scratch, void* stream) {
+    if (!x_context || n_context < 1 || !plan) return fail(GENIE_ERR_ARG, "genie_knn_index_build: null argument or n_context < 1");
+    hipStream_t st = (hipStream_t)stream;
+    if (!cell_start) {                                  // pass 1: the bounding box, read back once, and the plan made from it
+        if (!bbox_dev) return fail(GENIE_ERR_ARG, "genie_knn_index_build: pass 1 needs the device bounding box buffer");
+        float bbox[6];
+        k_kix_bbox<<<1, 1024, 0, st>>>(x_context, n_context, bbox_dev);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(bbox, bbox_dev, sizeof bbox, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return genie_knn_index_plan(n_context, bbox, plan);
+    }
+    if (!records || !scratch || ((uintptr_t)records & 15) != 0) return fail(GENIE_ERR_ARG, "genie_knn_index_build: null or misaligned buffer");
+    if (!kix_plan_ok(plan) || plan->records_bytes != 16ll * n_context)
+        return fail(GENIE_ERR_ARG, "genie_knn_index_build: the plan is not one genie_knn_index_plan made for this n_context");
+    const KixGrid g = kix_grid(plan, n_context);
+    const int nb = (n_context + 255) / 256;
+    HIP_TRY(hipMemsetAsync(scratch, 0, sizeof(int32_t) * (size_t)plan->n_cells, st));
+    k_kix_count<<<nb, 256, 0, st>>>(x_context, n_context, g, scratch);
+    k_kix_scan<<<1, 1024, 0, st>>>(scratch, plan->n_cells, cell_start);
+    k_kix_scatter<<<nb, 256, 0, st>>>(x_context, n_context, g, cell_start, scratch, (f32x4*)records);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+int genie_knn_indexed(const int32_t* cell_start, const float* records, const genie_knn_index_plan_t* plan, int n_context,
+                      const float* x_query, int n_query, int k, int exclude_self, int32_t* out_idx, void* stream) {
+    if (!cell_start || !records || !x_query || !out_idx || n_context < 1 || n_query < 0 || k < 1 || k > 16)
+        return fail(GENIE_ERR_ARG, "genie_knn_indexed: bad argument (1 <= k <= 16)");
+    if (((uintptr_t)records & 15) != 0 || !kix_plan_ok(plan) || plan->records_bytes != 16ll * n_context)
+        return fail(GENIE_ERR_ARG, "genie_knn_indexed: misaligned records, or the plan is not this index's");
+    if (n_query == 0) return GENIE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const KixGrid g = kix_grid(plan, n_context);
+    const f32x4* rec = (const f32x4*)records;
+    const int nb = (n_query + 255) / 256;
+    if (k <= 8) k_knn_ix<8><<<nb, 256, 0, st>>>(cell_start, rec, g, x_query, n_query, k, exclude_self, out_idx);
+    else if (k <= 10) k_knn_ix<10><<<nb, 256, 0, st>>>(cell_start, rec, g, x_query, n_query, k, exclude_self, out_idx);
+    else k_knn_ix<16><<<nb, 256, 0, st>>>(cell_start, rec, g, x_query, n_query, k, exclude_self, out_idx);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }

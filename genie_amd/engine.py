@@ -33,10 +33,85 @@ def _f32(t, name, shape=None):
     return t
 
 
-def knn_device(x_context, x_query, k, exclude_self=False):
+KNN_INDEX_MIN_QUERIES = 16384     # query sets from this size on go through a model's `knn_index` (where genie_knn turns to a lane per query)
+
+
+def _positions_key(t):
+    return (t.data_ptr(), t._version, tuple(t.shape), t.dtype)
+
+
+class KnnIndex(object):
+    """Cell index of a context point set for `knn_device(..., index=)`: a uniform cell grid over the points' bounding box, built on the
+    device once (genie_knn_index_build) and searched per query set (genie_knn_indexed) -- the table of `genie_knn`, bit for bit. It
+    owns its buffers (`cell_start` int32 [n_cells + 1], `records` fp32 [n, 4] = x, y, z, bits of the original index, ordered by cell) and
+    HOLDS the tensor it was built from: while it lives that storage cannot be handed to another tensor, so (address, in-place version,
+    shape) identifies the contents, as in `SpatialAttention`'s query cache. `n_context`, `cells` (per axis), `origin` (lower corner of
+    the box), `cell` (edge length): the geometry; face j of axis a lies at `origin[a] + j * cell`. `calls` counts the searches."""
+
+    def __init__(self, x_context):
+        if not torch.is_tensor(x_context):
+            raise TypeError("KnnIndex: x_context must be a torch tensor")
+        if x_context.dim() != 2 or x_context.shape[1] != 3 or x_context.shape[0] < 1:
+            raise ValueError("KnnIndex: positions must be [n, 3] with n >= 1")
+        self._ref, self._key = x_context, _positions_key(x_context)
+        self.n_context = int(x_context.shape[0])
+        self.calls = 0
+        self._build()
+
+    def _build(self):
+        lib = _lib.load()
+        xc = self._xc = _f32(self._ref, "x_context")          # (the fp32 form the kernels read: the tensor itself when it is fp32)
+        dev, n = xc.device, self.n_context
+        self._plan = plan = _lib.KnnIndexPlan()
+        bbox = torch.empty(6, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.genie_knn_index_build(_ptr(xc), n, _ptr(bbox), ctypes.byref(plan), None, None, None, _stream()),
+                       "genie_knn_index_build")
+            self.cell_start = torch.empty(plan.n_cells + 1, dtype=torch.int32, device=dev)
+            self.records = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            scratch = torch.empty(plan.n_cells, dtype=torch.int32, device=dev)
+            _lib.check(lib.genie_knn_index_build(_ptr(xc), n, _ptr(bbox), ctypes.byref(plan), _ptr(self.cell_start), _ptr(self.records),
+                                                 _ptr(scratch), _stream()), "genie_knn_index_build")
+        self.cells = tuple(int(c) for c in plan.cells)
+        self.origin = tuple(float(o) for o in plan.origin)
+        self.cell = float(plan.cell)
+
+    def matches(self, x_context):
+        return torch.is_tensor(x_context) and _positions_key(x_context) == self._key
+
+    def query(self, x_context, x_query, k, exclude_self=False):
+        """`knn_device(x_context, x_query, k, exclude_self, index=self)`. Everything the host refuses is refused before the device is
+        touched."""
+        if not (torch.is_tensor(x_context) and torch.is_tensor(x_query)):
+            raise TypeError("knn_device: positions must be torch tensors")
+        if x_context.dim() != 2 or x_context.shape[1] != 3 or x_query.dim() != 2 or x_query.shape[1] != 3:
+            raise ValueError("knn_device: positions must be [n, 3]")
+        k = int(min(k, x_context.shape[0] - (1 if exclude_self else 0)))
+        if not 1 <= k <= 16:
+            raise ValueError("knn_device: 1 <= k <= 16")
+        if not self.matches(x_context):
+            raise ValueError("knn_device: the index was built from another context (tensor, in-place version or shape differ); "
+                             "build a KnnIndex of this one")
+        lib = _lib.load()
+        xq = _f32(x_query, "x_query")
+        if xq.device != self.records.device:
+            raise ValueError("knn_device: x_query lives on %s, the index on %s" % (xq.device, self.records.device))
+        out = torch.empty((xq.shape[0], k), dtype=torch.int32, device=xq.device)
+        with torch.cuda.device(xq.device):
+            _lib.check(lib.genie_knn_indexed(_ptr(self.cell_start), _ptr(self.records), ctypes.byref(self._plan), self.n_context, _ptr(xq),
+                                             int(xq.shape[0]), k, 1 if exclude_self else 0, _ptr(out), _stream()), "genie_knn_indexed")
+        self.calls += 1
+        return out
+
+
+def knn_device(x_context, x_query, k, exclude_self=False, index=None):
     """int32 GPU table [n_query, k]: indices of the k nearest context points of every query, nearest first (genie_knn: exact
     brute-force fp64 search on the device; the reference's `knn(x_context / 1000, x_query / 1000, k)`, module.py:282,
-    process_utils.py:718-719). `exclude_self`: query i never lists context i (query set = context set)."""
+    process_utils.py:718-719). `exclude_self`: query i never lists context i (query set = context set). `index`: a `KnnIndex` of
+    `x_context` -- the same table through its cell grid (genie_knn_indexed), for large query sets against a context that stays; an
+    index built from another tensor, in-place version or shape raises ValueError."""
+    if index is not None:
+        return index.query(x_context, x_query, k, exclude_self)
     lib = _lib.load()
     xc, xq = _f32(x_context, "x_context"), _f32(x_query, "x_query")
     if xc.dim() != 2 or xc.shape[1] != 3 or xq.dim() != 2 or xq.shape[1] != 3:

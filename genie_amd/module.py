@@ -337,20 +337,23 @@ class SpatialDirect(nn.Module):
 
 
 
-def knn_query_edges(x_context, x_query, k):
+def knn_query_edges(x_context, x_query, k, index=None):
     """Exact kNN of each query in the context set on `x/1000` (module.py:282), by one HIP kernel (genie_knn: brute force, fp64
-    distances). Returns LongTensor [2, Q*k]: row 0 = context j, row 1 = query i (the `.flip(0)` layout). GPU tensors only: the
-    product has no CPU path (the torch form the CPU tests use lives in tests/restatements.py)."""
+    distances; with `index`, a `KnnIndex` of `x_context`, the same table through its cell grid). Returns LongTensor [2, Q*k]: row 0 =
+    context j, row 1 = query i (the `.flip(0)` layout). GPU tensors only: the product has no CPU path (the torch form the CPU tests
+    use lives in tests/restatements.py)."""
     if not x_context.is_cuda:
         raise _engine._lib.GenieHipError("knn_query_edges: positions must live on the GPU (no CPU fallback)")
-    idx = _engine.knn_device(x_context, x_query, k).long()
+    idx = _engine.knn_device(x_context, x_query, k, index=index).long()
     row_q = torch.arange(x_query.shape[0], device=x_query.device).repeat_interleave(idx.shape[1])
     return torch.stack([idx.reshape(-1), row_q], dim=0)
 
 
 class SpatialAttention(nn.Module):
     """Parameters of module.py:262-297 (kNN k=10 of the queries into the grid, per-edge q/c/v, segment softmax, mean over heads:
-    k_ro_pre_m + k_readout_m<1>) and the cache of the query set's kNN table (genie_knn)."""
+    k_ro_pre_m + k_readout_m<1>) and the cache of the query set's kNN table (genie_knn). `knn_index` (default False; set through the
+    model's attribute of that name): query sets of at least `engine.KNN_INDEX_MIN_QUERIES` rows are searched through a `KnnIndex` of the
+    context, kept per context; the table is the same."""
 
     def __init__(self, inpt_dim, out_channels, n_dim, n_latent, n_hidden=30, n_heads=5, scale_rel=SCALE_REL):
         super().__init__()
@@ -365,6 +368,15 @@ class SpatialAttention(nn.Module):
         self.activate1 = nn.PReLU()
         self.activate2 = nn.PReLU()
         self._edge_cache = {}
+        self.knn_index = False
+        self._context_index = None
+
+    def context_index(self, x_context):
+        """The `KnnIndex` of `x_context`, built when the context is not the one last indexed (keyed like the query cache: address,
+        in-place version, shape; the index holds the tensor)."""
+        if self._context_index is None or not self._context_index.matches(x_context):
+            self._context_index = _engine.KnnIndex(x_context)
+        return self._context_index
 
     def query_edges(self, x_query, x_context, k):
         """kNN edges of a query set, cached for the set last used. The cache entry HOLDS the two position tensors: while it
@@ -374,13 +386,16 @@ class SpatialAttention(nn.Module):
                x_context._version, tuple(x_context.shape), x_context.dtype, k)
         hit = self._edge_cache.get("key") == key
         if not hit:
-            edges = knn_query_edges(x_context, x_query, k)
+            indexed = self.knn_index and x_query.shape[0] >= _engine.KNN_INDEX_MIN_QUERIES
+            edges = (knn_query_edges(x_context, x_query, k, index=self.context_index(x_context)) if indexed
+                     else knn_query_edges(x_context, x_query, k))
             self._edge_cache = {"key": key, "edges": edges, "refs": (x_query, x_context),
                                 "table": edges[0].view(x_query.shape[0], -1).to(torch.int32).contiguous()}
         return self._edge_cache["edges"]
 
     def invalidate_query_cache(self):
         self._edge_cache = {}
+        self._context_index = None
 
     def query_table(self, x_query, x_context, k=10):
         """int32 [Q, k] table of the k nearest context nodes of every query (cached per query set)."""
@@ -654,6 +669,17 @@ class GCN_Detection_Network_extended(nn.Module):
     @property
     def is_sharded(self):
         return self._shard_cfg is not None
+
+    @property
+    def knn_index(self):
+        """True: the kNN of query sets of at least `engine.KNN_INDEX_MIN_QUERIES` rows (the refine pass's clouds) goes through a cell
+        index of the source grid, built once per grid (`engine.KnnIndex`); the tables, and with them every output, are bit-equal.
+        Default False. The two small source-query searches of `forward_fixed` stay brute force either way."""
+        return self.SpatialAttention.knn_index
+
+    @knn_index.setter
+    def knn_index(self, on):
+        self.SpatialAttention.knn_index = bool(on)
 
     @property
     def shard_plan(self):

@@ -451,6 +451,40 @@ int genie_assoc_fwd_part(genie_ctx* ctx, int part, const float* y_latent, const 
 int genie_knn(const float* x_context, int n_context, const float* x_query, int n_query, int k, int exclude_self,
               int32_t* out_idx, void* stream);
 
+/* The same table through a cell index of the context points, for large query sets against a context that stays (the refine pass's
+ * 112 000-point cloud per candidate source against the source grid): EXACT -- out_idx of genie_knn_indexed equals out_idx of genie_knn
+ * on the same points bit for bit, ties and -1 entries included -- and opt-in; genie_knn is unchanged.
+ *   The index is a uniform cell grid over the bounding box of the context points (fp32 coordinates as passed): the cell edge gives a
+ *   mean occupancy of 4 points per cell, at most 2^20 cells, one cell on an axis of zero extent; cell id = (c2 * cells[1] + c1) *
+ *   cells[0] + c0 with c_a = clamp(floor(fl(fl(x_a - origin[a]) * inv_cell)), 0, cells[a] - 1) in fp32. Its buffers are the caller's:
+ *   cell_start int32 [n_cells + 1] and records [n_context] of 16 bytes (x, y, z, bits of the original index; 16-byte aligned), the
+ *   points ordered by cell.
+ * genie_knn_index_plan: host only, no device call. bbox = (min x, y, z, max x, y, z) -> the cells per axis, the cell function's
+ *   constants and the byte sizes of the buffers. A box that is not finite returns GENIE_ERR_ARG.
+ * genie_knn_index_build, two passes as the count / fill pairs of this header. Pass 1 (cell_start == NULL): the bounding box on the
+ *   device into bbox_dev (device, 6 floats), read back once (this pass waits for the stream), and *plan filled from it; a context with
+ *   a NaN or an infinity returns GENIE_ERR_ARG here. Pass 2 (the buffers of that plan; scratch = device int32 [n_cells], left as the
+ *   cells' counts): cell ids, histogram, exclusive scan, scatter, on the stream, no wait.
+ * genie_knn_indexed: the arguments of genie_knn with (cell_start, records, plan, n_context) in place of the context. One lane per
+ *   query; a query outside the box starts in the nearest cell. */
+typedef struct genie_knn_index_plan_t {
+    int32_t cells[3];
+    int32_t n_cells;             /* cells[0] * cells[1] * cells[2] <= 2^20 */
+    float origin[3];             /* lower corner of the bounding box */
+    float upper[3];              /* upper corner */
+    float inv_cell;              /* fp32 factor of the cell function */
+    int32_t reserved;
+    double cell;                 /* cell edge = 1 / (double)inv_cell */
+    int64_t cell_start_bytes;    /* 4 * (n_cells + 1) */
+    int64_t records_bytes;       /* 16 * n_context */
+    int64_t scratch_bytes;       /* 4 * n_cells */
+} genie_knn_index_plan_t;
+int genie_knn_index_plan(int n_context, const float* bbox, genie_knn_index_plan_t* plan);
+int genie_knn_index_build(const float* x_context, int n_context, float* bbox_dev, genie_knn_index_plan_t* plan, int32_t* cell_start,
+                          float* records, int32_t* scratch, void* stream);
+int genie_knn_indexed(const int32_t* cell_start, const float* records, const genie_knn_index_plan_t* plan, int n_context,
+                      const float* x_query, int n_query, int k, int exclude_self, int32_t* out_idx, void* stream);
+
 /* One-time graph setup, training call convention (round 5): `forward` receives the product edge lists of a NEW graph per sample
  * (train_GENIE_model.py:1722-1786; built at :1140-1149 as process_utils.py:720-721 builds them) and the library consumes only their base
  * graphs, so every sample's lists are verified to be the Cartesian product of their own first blocks:
