@@ -102,6 +102,8 @@ SYMBOLS = [
                                   _P, _P, _P, _c.c_int, _P, _P]),
     ("genie_lslc_rows", _c.c_int, [_P, _P, _P, _c.c_int, _P, _P, _c.c_int64, _c.c_int, _c.c_float, _c.c_float, _P, _P, _c.c_int, _P, _P,
                                    _c.c_int, _P, _P, _P]),
+    ("genie_lslc_rows_own", _c.c_int, [_P, _P, _P, _c.c_int, _P, _P, _c.c_int64, _c.c_int, _c.c_float, _c.c_float, _P, _P, _c.c_int, _P, _P,
+                                       _c.c_int, _P, _P, _P]),
     ("genie_lslc_fwd_rows", _c.c_int, [_P, _c.c_int, _P, _c.c_float, _P, _P, _c.c_int, _P, _P]),
     ("genie_lslc_bwd_part_floats", _c.c_size_t, [_c.c_int]),
     ("genie_lslc_bwd", _c.c_int, [_P, _c.c_int, _P, _P, _c.c_int64, _c.c_int, _c.c_float, _c.c_float, _P, _c.c_float, _P, _c.c_int, _c.c_int,
@@ -128,6 +130,8 @@ SYMBOLS = [
     ("genie_local_marching", _c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_double, _c.c_double, _c.c_int, _c.c_double, _c.c_int, _P, _P, _P]),
     ("genie_time_pointers_scratch_bytes", _c.c_size_t, [_c.c_int64, _c.c_int, _c.c_int]),
     ("genie_time_pointers", _c.c_int, [_P, _c.c_int64, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _P, _P]),
+    ("genie_time_pointers_candidates", _c.c_int, [_P, _c.c_int64, _c.c_int, _P, _P, _c.c_int, _c.c_int, _P, _P, _P, _P]),
+    ("genie_time_pointers_merge", _c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _c.c_int, _P, _P, _P, _P]),
     ("genie_stack_windows", _c.c_int, [_P, _P, _c.c_int, _c.c_int64, _c.c_int, _c.c_float, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P]),
     ("genie_stack_windows_legs", _c.c_int, [_P, _c.c_int, _P, _c.c_int, _c.c_int64, _c.c_int, _c.c_float, _P, _c.c_int64, _c.c_int64, _c.c_int64,
                                             _P]),

@@ -4191,13 +4191,18 @@ size_t genie_time_pointers_scratch_bytes(int64_t n_prod, int n_sta, int n_t) {
     return tp_size_error(n_prod, n_sta, n_t) ? 0 : tp_layout(n_prod, n_sta, n_t).total;
 }
 
-int genie_time_pointers(const float* trv, int64_t n_prod, int n_sta, const int32_t* sta_of_prod, const double* dt_partition, int n_t, int k,
-                        void* scratch, int32_t* edges_p, int32_t* edges_s, int32_t* status, void* stream) {
-    if (k < 1 || k > TP_MAX_K) return fail(GENIE_ERR_ARG, "genie_time_pointers: 1 <= k <= 32 required");
-    if (const char* why = tp_size_error(n_prod, n_sta, n_t)) return fail(GENIE_ERR_ARG, std::string("genie_time_pointers: ") + why);
-    if (!sta_of_prod && n_prod % n_sta != 0) return fail(GENIE_ERR_ARG, "genie_time_pointers: n_prod is not a multiple of n_sta (Cartesian form)");
-    if (!trv || !dt_partition || !scratch || !edges_p || !edges_s || !status) return fail(GENIE_ERR_ARG, "genie_time_pointers: null argument");
-    if ((((uintptr_t)scratch) & 15) != 0) return fail(GENIE_ERR_ARG, "genie_time_pointers: scratch must be 16-byte aligned");
+namespace {
+// Steps 1-4 of pointer_kernels.hpp over trv [n_prod, 2]: the tables (edges_p / edges_s), or the keys of a shard's rows (cand, with
+// node_global); `who`: the entry's name in messages.
+int time_pointers_launch(const char* who, const float* trv, int64_t n_prod, int n_sta, const int32_t* sta_of_prod, const int32_t* node_global,
+                         const double* dt_partition, int n_t, int k, void* scratch, int32_t* edges_p, int32_t* edges_s, tp_ll2* cand,
+                         int32_t* status, void* stream) {
+    if (k < 1 || k > TP_MAX_K) return fail(GENIE_ERR_ARG, std::string(who) + ": 1 <= k <= 32 required");
+    if (const char* why = tp_size_error(n_prod, n_sta, n_t)) return fail(GENIE_ERR_ARG, std::string(who) + ": " + why);
+    if (!sta_of_prod && n_prod % n_sta != 0) return fail(GENIE_ERR_ARG, std::string(who) + ": n_prod is not a multiple of n_sta (Cartesian form)");
+    if (!trv || !dt_partition || !scratch || !status || (cand ? !node_global : (!edges_p || !edges_s)))
+        return fail(GENIE_ERR_ARG, std::string(who) + ": null argument");
+    if (((((uintptr_t)scratch) | ((uintptr_t)cand)) & 15) != 0) return fail(GENIE_ERR_ARG, std::string(who) + ": scratch and cand must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     const TpLayout L = tp_layout(n_prod, n_sta, n_t);
     char* base = (char*)scratch;
@@ -4215,9 +4220,39 @@ int genie_time_pointers(const float* trv, int64_t n_prod, int n_sta, const int32
     k_tp_bins<false><<<nb, TP_BLOCK, 0, st>>>(trv, sta_of_prod, P, n_sta, G, dt_partition, n_t, cnt, seg_arg, sorted, status);
     k_tp_scan<<<2u * (unsigned)n_sta, TP_BLOCK, 0, st>>>(cnt, start, n_sta, n_t, ncand);
     k_tp_segments<<<1, TP_BLOCK, 0, st>>>(ncand, n_sta, seg, status);
-    k_tp_bins<true><<<nb, TP_BLOCK, 0, st>>>(trv, sta_of_prod, P, n_sta, G, dt_partition, n_t, cnt, seg_arg, sorted, status);
+    k_tp_bins<true><<<nb, TP_BLOCK, 0, st>>>(trv, sta_of_prod, P, n_sta, G, dt_partition, n_t, cnt, seg_arg, sorted, status, node_global);
     const dim3 grid((unsigned)n_sta * (unsigned)((n_t + TP_WAVES - 1) / TP_WAVES), 2);
-    k_tp_select<<<grid, TP_BLOCK, 0, st>>>(sorted, start, seg_arg, P, G, n_sta, dt_partition, n_t, k, edges_p, edges_s);
+    if (cand) k_tp_select<true><<<grid, TP_BLOCK, 0, st>>>(sorted, start, seg_arg, P, G, n_sta, dt_partition, n_t, k, nullptr, nullptr, cand);
+    else k_tp_select<false><<<grid, TP_BLOCK, 0, st>>>(sorted, start, seg_arg, P, G, n_sta, dt_partition, n_t, k, edges_p, edges_s, nullptr);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+}  // namespace
+
+int genie_time_pointers(const float* trv, int64_t n_prod, int n_sta, const int32_t* sta_of_prod, const double* dt_partition, int n_t, int k,
+                        void* scratch, int32_t* edges_p, int32_t* edges_s, int32_t* status, void* stream) {
+    return time_pointers_launch("genie_time_pointers", trv, n_prod, n_sta, sta_of_prod, nullptr, dt_partition, n_t, k, scratch, edges_p, edges_s,
+                                nullptr, status, stream);
+}
+
+int genie_time_pointers_candidates(const float* trv_own, int64_t n_prod_own, int n_sta, const int32_t* node_global, const double* dt_partition,
+                                   int n_t, int k, void* scratch, int64_t* cand, int32_t* status, void* stream) {
+    if (!cand || !node_global) return fail(GENIE_ERR_ARG, "genie_time_pointers_candidates: null argument");
+    return time_pointers_launch("genie_time_pointers_candidates", trv_own, n_prod_own, n_sta, nullptr, node_global, dt_partition, n_t, k, scratch,
+                                nullptr, nullptr, (tp_ll2*)cand, status, stream);
+}
+
+int genie_time_pointers_merge(const int64_t* cand, int world, int n_sta, int n_t, int k, int k_out, int32_t* edges_p, int32_t* edges_s,
+                              int32_t* status, void* stream) {
+    if (k < 1 || k > TP_MAX_K || k_out < 1 || k_out > k) return fail(GENIE_ERR_ARG, "genie_time_pointers_merge: 1 <= k_out <= k <= 32 required");
+    if (world < 1 || world > (1 << 16)) return fail(GENIE_ERR_ARG, "genie_time_pointers_merge: 1 <= world <= 65536 required");
+    if (const char* why = tp_size_error((int64_t)n_sta, n_sta, n_t)) return fail(GENIE_ERR_ARG, std::string("genie_time_pointers_merge: ") + why);
+    if (!cand || !edges_p || !edges_s || !status) return fail(GENIE_ERR_ARG, "genie_time_pointers_merge: null argument");
+    if ((((uintptr_t)cand) & 15) != 0) return fail(GENIE_ERR_ARG, "genie_time_pointers_merge: cand must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(status, 0, sizeof(int32_t), st));
+    const dim3 grid((unsigned)n_sta * (unsigned)((n_t + TP_WAVES - 1) / TP_WAVES), 2);
+    k_tp_merge<<<grid, TP_BLOCK, 0, st>>>((const tp_ll2*)cand, world, n_sta, n_t, k, k_out, edges_p, edges_s, status);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }
@@ -4378,29 +4413,46 @@ int genie_lslc_fwd(genie_ctx* c, int phase_head, const float* s_rows, const int3
     return GENIE_OK;
 }
 
-int genie_lslc_rows(genie_ctx* c, const float* s_own, const int32_t* node_local, int n_grid, const int32_t* a_edges_p,
-                    const int32_t* a_edges_s, int64_t n_edges, int l_dt, float t0, float dt, const float* dt_partition, const float* tlatent,
-                    int tl_stride, const float* tpick, const int32_t* ipick, int n_picks, int32_t* count, float* rows, void* stream) {
-    if (!c || !s_own || !node_local || !a_edges_p || !a_edges_s || !tlatent || !count) return fail(GENIE_ERR_ARG, "genie_lslc_rows: null argument");
-    if (c->pcsr) return fail(GENIE_ERR_STATE, "genie_lslc_rows: needs a Cartesian product graph");
+namespace {
+int lslc_rows_impl(genie_ctx* c, const float* s_own, const int32_t* node_local, int n_grid, const int32_t* a_edges_p,
+                   const int32_t* a_edges_s, int64_t n_edges, int l_dt, float t0, float dt, const float* dt_partition, const float* tlatent,
+                   int tl_stride, const float* tpick, const int32_t* ipick, int n_picks, int32_t* count, float* rows, void* stream, bool tl_own) {
+    const char* who = tl_own ? "genie_lslc_rows_own" : "genie_lslc_rows";
+    if (!c || !s_own || !node_local || !a_edges_p || !a_edges_s || !tlatent || !count) return fail(GENIE_ERR_ARG, std::string(who) + ": null argument");
+    if (c->pcsr) return fail(GENIE_ERR_STATE, std::string(who) + ": needs a Cartesian product graph");
     if (n_grid < c->G || n_picks < 0 || n_picks > 100000000 || l_dt < (dt_partition ? 2 : 1) || n_edges < LS_K || (!dt_partition && !(dt > 0.f)) ||
         tl_stride < 2)
-        return fail(GENIE_ERR_ARG, "genie_lslc_rows: bad argument");
+        return fail(GENIE_ERR_ARG, std::string(who) + ": bad argument");
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(count, 0, sizeof(int32_t), st));
     if (n_picks == 0) return GENIE_OK;
-    if (!tpick || !ipick || !rows) return fail(GENIE_ERR_ARG, "genie_lslc_rows: null argument");
-    if ((((uintptr_t)rows) | ((uintptr_t)s_own)) & 7) return fail(GENIE_ERR_ARG, "genie_lslc_rows: s_own and rows must be 8-byte aligned");
+    if (!tpick || !ipick || !rows) return fail(GENIE_ERR_ARG, std::string(who) + ": null argument");
+    if ((((uintptr_t)rows) | ((uintptr_t)s_own)) & 7) return fail(GENIE_ERR_ARG, std::string(who) + ": s_own and rows must be 8-byte aligned");
     LrArgs a;
     memset(&a, 0, sizeof(a));
     a.n_picks = n_picks; a.l_dt = l_dt; a.S = c->S; a.n_grid = n_grid; a.n_edges = n_edges; a.t0 = t0; a.dt = dt; a.dtp = dt_partition;
     a.s_own = s_own; a.node_local = node_local; a.A_edges[0] = a_edges_p; a.A_edges[1] = a_edges_s;
-    a.tlatent = tlatent; a.tl_stride = tl_stride; a.tpick = tpick; a.ipick = ipick; a.count = count; a.rows = rows;
+    a.tlatent = tlatent; a.tl_stride = tl_stride; a.tl_own = tl_own ? 1 : 0; a.tpick = tpick; a.ipick = ipick; a.count = count; a.rows = rows;
     a.flag = c->h_inflag ? c->h_inflag + 1 : nullptr;
     const long long n_ent = 2LL * n_picks * LS_K;
     k_lslc_rows<<<(int)std::max<long long>(1, std::min<long long>((n_ent + 15) / 16, (long long)c->num_cu * 8)), 256, 0, st>>>(a);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
+}
+}  // namespace
+
+int genie_lslc_rows(genie_ctx* c, const float* s_own, const int32_t* node_local, int n_grid, const int32_t* a_edges_p,
+                    const int32_t* a_edges_s, int64_t n_edges, int l_dt, float t0, float dt, const float* dt_partition, const float* tlatent,
+                    int tl_stride, const float* tpick, const int32_t* ipick, int n_picks, int32_t* count, float* rows, void* stream) {
+    return lslc_rows_impl(c, s_own, node_local, n_grid, a_edges_p, a_edges_s, n_edges, l_dt, t0, dt, dt_partition, tlatent, tl_stride, tpick, ipick,
+                          n_picks, count, rows, stream, false);
+}
+
+int genie_lslc_rows_own(genie_ctx* c, const float* s_own, const int32_t* node_local, int n_grid, const int32_t* a_edges_p,
+                        const int32_t* a_edges_s, int64_t n_edges, int l_dt, float t0, float dt, const float* dt_partition, const float* tlatent_own,
+                        int tl_stride, const float* tpick, const int32_t* ipick, int n_picks, int32_t* count, float* rows, void* stream) {
+    return lslc_rows_impl(c, s_own, node_local, n_grid, a_edges_p, a_edges_s, n_edges, l_dt, t0, dt, dt_partition, tlatent_own, tl_stride, tpick,
+                          ipick, n_picks, count, rows, stream, true);
 }
 
 int genie_lslc_fwd_rows(genie_ctx* c, int phase_head, const float* table, float eps, const float* tpick, const float* phase_label,

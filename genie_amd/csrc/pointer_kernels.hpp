@@ -26,6 +26,14 @@
 // size limit inside: segments live in global memory. Entries whose travel time is not finite (an integer test on the bits: the library
 // is built without NaN semantics) are skipped by both passes alike and raise status[1]; an out-of-range station index likewise is skipped.
 // Stores are ordinary vector stores; the atomics are vector atomics on the counters.
+//
+// Source-node-sharded model (genie_time_pointers_candidates + genie_time_pointers_merge, genie_amd/dist.py): a rank holds the travel
+// times of its OWNED source nodes only, rows in its local node order. The same four steps run over those rows with the GLOBAL
+// product-node id in every key (`node_global`: local source node -> global one), and k_tp_select<true> emits, per (phase, station,
+// time step), its min(k, n_own) best as (bits of the float64 distance, global id) pairs -- padded to k with the key (max double, max
+// int), which sorts after every candidate and is never listed; no cycling. The k smallest of the union of the ranks' lists are the k
+// smallest of the station (each rank's list holds every one of ITS candidates that can be among them), so after one all-gather
+// k_tp_merge ranks world x k keys per entry with the same wave-wide insertion and writes the replicated tables.
 // ------------------------------------------------------------------------------------------------
 constexpr int TP_MAX_K = 32;                    // ranks kept per (station, time step): at most one per lane of half a wave
 constexpr int TP_BLOCK = 256;
@@ -65,7 +73,7 @@ template <bool FILL>
 __global__ __launch_bounds__(TP_BLOCK) void k_tp_bins(const float* __restrict__ trv, const int32_t* __restrict__ sta_of, long long P, int S,
                                                       long long G, const double* __restrict__ t, int n_t, int32_t* __restrict__ cnt,
                                                       const int32_t* __restrict__ seg, unsigned long long* __restrict__ sorted,
-                                                      int32_t* __restrict__ status) {
+                                                      int32_t* __restrict__ status, const int32_t* __restrict__ node_global = nullptr) {
     const long long n = 2 * P, stride = (long long)gridDim.x * TP_BLOCK;
     for (long long e = (long long)blockIdx.x * TP_BLOCK + threadIdx.x; e < n; e += stride) {
         const long long p = e >> 1;
@@ -83,7 +91,9 @@ __global__ __launch_bounds__(TP_BLOCK) void k_tp_bins(const float* __restrict__ 
             atomicAdd(c, 1);
         } else {
             const long long pos = (seg ? (long long)seg[i] : (long long)i * G) + atomicAdd(c, 1);
-            sorted[(size_t)ph * (size_t)P + (size_t)pos] = ((unsigned long long)bits << 32) | (unsigned long long)(unsigned)p;
+            // a shard's rows (Cartesian form only): the key carries the GLOBAL product-node id of local row p = l * S + i
+            const long long id = node_global ? (long long)node_global[p / S] * S + i : p;
+            sorted[(size_t)ph * (size_t)P + (size_t)pos] = ((unsigned long long)bits << 32) | (unsigned long long)(unsigned)id;
         }
     }
 }
@@ -147,10 +157,39 @@ __global__ __launch_bounds__(TP_BLOCK) void k_tp_segments(const int32_t* __restr
 
 __device__ __forceinline__ bool tp_less(double d, int id, double od, int oid) { return d < od || (d == od && id < oid); }
 
+constexpr double TP_EMPTY_D = 1.7976931348623157e308;     // (max double, max int): an empty rank; sorts after every candidate
+constexpr int TP_EMPTY_ID = 0x7fffffff;
+
+// One chunk of up to 64 keys (one per lane, `have`: this lane holds one) into the wave's sorted list (lane r: the key of rank r): what
+// beats the key at rank k - 1 is inserted, one key at a time. Every lane takes part in the shuffles.
+__device__ __forceinline__ void tp_wave_insert(double& kd, int& kid, double d, int id, bool have, int k, int lane) {
+    const double td = __shfl(kd, k - 1);
+    const int tid = __shfl(kid, k - 1);
+    unsigned long long m = __ballot(have && tp_less(d, id, td, tid));
+    while (m) {                                               // wave-uniform
+        const int src = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const double cd = __shfl(d, src);
+        const int cid = __shfl(id, src);
+        if (!tp_less(cd, cid, __shfl(kd, k - 1), __shfl(kid, k - 1))) continue;   // rank k - 1 has moved past it meanwhile
+        const double pd = __shfl_up(kd, 1);
+        const int pid = __shfl_up(kid, 1);
+        if (tp_less(cd, cid, kd, kid)) {                      // it ranks before mine: I take my left neighbour's key, or the new one
+            const bool shift = lane > 0 && tp_less(cd, cid, pd, pid);
+            kd = shift ? pd : cd;
+            kid = shift ? pid : cid;
+        }
+    }
+}
+
+typedef long long tp_ll2 __attribute__((ext_vector_type(2)));     // one emitted key: (bits of the float64 distance, product-node id)
+
+// CAND: the keys go to cand [2][S][n_t][k] instead of the ids to the tables (a rank of a source-node-sharded model)
+template <bool CAND>
 __global__ __launch_bounds__(TP_BLOCK) void k_tp_select(const unsigned long long* __restrict__ sorted, const int32_t* __restrict__ start,
                                                         const int32_t* __restrict__ seg, long long P, long long G, int S,
                                                         const double* __restrict__ t, int n_t, int k, int32_t* __restrict__ out_p,
-                                                        int32_t* __restrict__ out_s) {
+                                                        int32_t* __restrict__ out_s, tp_ll2* __restrict__ cand_out) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int groups = (n_t + TP_WAVES - 1) / TP_WAVES;
     const int i = (int)(blockIdx.x / (unsigned)groups);
@@ -158,10 +197,14 @@ __global__ __launch_bounds__(TP_BLOCK) void k_tp_select(const unsigned long long
     const int ph = blockIdx.y;
     if (j >= n_t) return;                                     // (a whole wave; the kernel has no barrier)
     const int32_t* B = start + ((size_t)ph * S + i) * (size_t)(n_t + 2);
-    int32_t* out = (ph ? out_s : out_p) + ((size_t)i * n_t + j) * (size_t)k;
+    int32_t* out = CAND ? nullptr : (ph ? out_s : out_p) + ((size_t)i * n_t + j) * (size_t)k;
+    tp_ll2* ck = CAND ? cand_out + (((size_t)ph * S + i) * (size_t)n_t + j) * (size_t)k : nullptr;
     const int n = B[n_t + 1];
     if (n <= 0) {                                             // no candidate: the caller reads status[0] and raises
-        if (lane < k) out[lane] = 0;
+        if (lane < k) {
+            if (CAND) ck[lane] = tp_ll2{__double_as_longlong(TP_EMPTY_D), (long long)TP_EMPTY_ID};
+            else out[lane] = 0;
+        }
         return;
     }
     const int mid = B[j + 1];                                 // candidates left of t_j
@@ -184,36 +227,60 @@ __global__ __launch_bounds__(TP_BLOCK) void k_tp_select(const unsigned long long
     }
     const unsigned long long* cand = sorted + (size_t)ph * (size_t)P + (size_t)(seg ? (long long)seg[i] : (long long)i * G);
     const double tj = t[j];
-    double kd = 1.7976931348623157e308;                       // lane r: the key of rank r so far; (max double, max int) = empty
-    int kid = 0x7fffffff;
+    double kd = TP_EMPTY_D;                                   // lane r: the key of rank r so far
+    int kid = TP_EMPTY_ID;
     for (int c0 = a; c0 < b; c0 += 64) {
         const int c = c0 + lane;
         const bool have = c < b;
-        double d = 1.7976931348623157e308;
-        int id = 0x7fffffff;
+        double d = TP_EMPTY_D;
+        int id = TP_EMPTY_ID;
         if (have) {
             const unsigned long long e = cand[c];
             id = (int)(unsigned)e;
             d = fabs((double)__uint_as_float((unsigned)(e >> 32)) - tj);
         }
-        const double td = __shfl(kd, k - 1);                  // (every lane takes part in the shuffles)
-        const int tid = __shfl(kid, k - 1);
-        unsigned long long m = __ballot(have && tp_less(d, id, td, tid));
-        while (m) {                                           // wave-uniform
-            const int src = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            const double cd = __shfl(d, src);
-            const int cid = __shfl(id, src);
-            if (!tp_less(cd, cid, __shfl(kd, k - 1), __shfl(kid, k - 1))) continue;   // rank k - 1 has moved past it meanwhile
-            const double pd = __shfl_up(kd, 1);
-            const int pid = __shfl_up(kid, 1);
-            if (tp_less(cd, cid, kd, kid)) {                  // it ranks before mine: I take my left neighbour's key, or the new one
-                const bool shift = lane > 0 && tp_less(cd, cid, pd, pid);
-                kd = shift ? pd : cd;
-                kid = shift ? pid : cid;
-            }
-        }
+        tp_wave_insert(kd, kid, d, id, have, k, lane);
+    }
+    if (CAND) {                                               // ranks >= n stay empty: a rank that owns fewer than k nodes does not cycle
+        if (lane < k) ck[lane] = tp_ll2{__double_as_longlong(kd), (long long)kid};
+        return;
     }
     const int id_out = __shfl(kid, lane % (n < 64 ? n : 64));
     if (lane < k) out[lane] = id_out;
+}
+
+// The ranks' lists merged: cand [world][2][S][n_t][k] keys, every rank's k ascending (empty ones last) -> the k_out <= k smallest of the
+// world * k per (phase, station, time step), nearest first, as int32 ids in the tables [S][n_t][k_out]. One wave per entry, as
+// k_tp_select: lane c of a chunk reads key c % k of rank c / k (k consecutive 16-byte keys per rank). An entry with fewer than k_out
+// real keys (the ranks' lists do not cover the station: an inconsistent call) sets status[0].
+__global__ __launch_bounds__(TP_BLOCK) void k_tp_merge(const tp_ll2* __restrict__ cand, int world, int S, int n_t, int k, int k_out,
+                                                       int32_t* __restrict__ out_p, int32_t* __restrict__ out_s, int32_t* __restrict__ status) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int groups = (n_t + TP_WAVES - 1) / TP_WAVES;
+    const int i = (int)(blockIdx.x / (unsigned)groups);
+    const int j = (int)(blockIdx.x % (unsigned)groups) * TP_WAVES + wave;
+    const int ph = blockIdx.y;
+    if (j >= n_t) return;                                     // (a whole wave; the kernel has no barrier)
+    const size_t entry = (((size_t)ph * S + i) * (size_t)n_t + j) * (size_t)k, rank_stride = 2 * (size_t)S * (size_t)n_t * (size_t)k;
+    const int total = world * k;
+    double kd = TP_EMPTY_D;
+    int kid = TP_EMPTY_ID;
+    for (int c0 = 0; c0 < total; c0 += 64) {
+        const int c = c0 + lane;
+        const bool have = c < total;
+        double d = TP_EMPTY_D;
+        int id = TP_EMPTY_ID;
+        if (have) {
+            const int r = c / k;
+            const tp_ll2 e = cand[(size_t)r * rank_stride + entry + (size_t)(c - r * k)];
+            d = __longlong_as_double(e.x);
+            id = (int)e.y;
+        }
+        tp_wave_insert(kd, kid, d, id, have, k_out, lane);    // (an empty key never beats the list's own empty ranks)
+    }
+    if (lane < k_out) {
+        const bool empty = kid == TP_EMPTY_ID;
+        if (empty) atomicOr(status, 1);
+        ((ph ? out_s : out_p) + ((size_t)i * n_t + j) * (size_t)k_out)[lane] = empty ? 0 : kid;
+    }
 }

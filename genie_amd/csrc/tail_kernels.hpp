@@ -851,6 +851,7 @@ struct LrArgs {
     const int32_t* node_local;    // [n_grid] global source node -> local owned index, -1 = owned elsewhere
     const int32_t* A_edges[2];    // P / S time-pointer tables [n_sta * l_dt * K], global product-node ids
     const float* tlatent; int tl_stride;     // [n_grid * S][tl_stride], column = head
+    int tl_own;                              // 1: tlatent holds the OWNED rows only, [n_own * S][tl_stride] in local node order (as s_own)
     const float* tpick; const int32_t* ipick;
     int32_t* count;               // [1], zeroed by the entry point
     float* rows;                  // [2 * n_picks * K][LR_ROW]
@@ -880,10 +881,11 @@ __global__ __launch_bounds__(256) void k_lslc_rows(LrArgs a) {
         if (sub == 0) slot = atomicAdd(a.count, 1);
         slot = __shfl(slot, 0, 16);
         typedef float f32x2 __attribute__((ext_vector_type(2)));
-        const float* src = a.s_own + ((long long)loc * a.S + (e - g * a.S)) * 30;
+        const long long row = (long long)loc * a.S + (e - g * a.S);                         // the product node among the owned rows
+        const float* src = a.s_own + row * 30;
         float* dst = a.rows + (long long)slot * LR_ROW;
         if (sub < 15) *(f32x2*)(dst + 2 * sub) = *(const f32x2*)(src + 2 * sub);
-        else *(f32x2*)(dst + 30) = f32x2{a.tlatent[(long long)e * a.tl_stride + head], __int_as_float((int)ent)};
+        else *(f32x2*)(dst + 30) = f32x2{a.tlatent[(a.tl_own ? row : (long long)e) * a.tl_stride + head], __int_as_float((int)ent)};
     }
 }
 

@@ -298,6 +298,61 @@ def place_pick_rows(gathered, n_entries):
     return table
 
 
+def shard_time_pointers(tl_own, own_global, n_sta, n_grid, transport, max_t=None, dt=1.0, k=10, win=10.0, candidates=None, merge=None):
+    """The association heads' time-pointer tables of a source-node-sharded model from each rank's OWN travel-time rows: the tables of
+    `engine.time_pointers_device` / `graph.time_pointers` over the whole product graph, bit for bit, the same on every rank.
+
+    tl_own fp32 [n_own * n_sta, 2]: the rows of this rank's owned source nodes `own_global` in local node order. Every rank calls with the
+    same n_sta, n_grid, max_t, dt, k, win. Two collectives over `transport`, joined by every rank whatever it owns:
+      1. one [1, 2] float64 row per rank -- its largest travel time and whether it holds an inf / NaN -- so that `max_t=None` (the largest
+         travel time of the WHOLE graph) and the verdict agree: a bad travel time on one rank raises ValueError on all of them, here,
+         after the collective, and no rank waits for another in the next one;
+      2. the ranks' candidate blocks: per (phase, station, time step) a rank's min(k, n_own) smallest keys (float64 distance, global
+         product-node id), padded with a key that sorts last (`candidates`, default `engine.time_pointers_candidates`). A key among the
+         k smallest of the station is among the k smallest of its owner, so the k smallest of the gathered world x k keys (`merge`,
+         default `engine.time_pointers_merge`) are the station's.
+    dt_partition is computed on the host as `time_pointers_device` computes it. `candidates` / `merge`: the two kernels' stand-ins with
+    their signatures, for tensors that do not live on a GPU (tests/test_shard_time_pointers_cpu.py).
+    Returns (A_edges_p, A_edges_s, dt_partition): int32 [n_sta * len(dt_partition) * min(k, n_grid)] each, and the float64 numpy steps."""
+    k, n_sta, n_grid = int(k), int(n_sta), int(n_grid)
+    if not 1 <= k <= engine.TIME_POINTERS_MAX_K:
+        raise ValueError("time_pointers on a shard: 1 <= k <= %d required, got %d" % (engine.TIME_POINTERS_MAX_K, k))
+    if n_sta < 1 or n_grid < 1 or n_sta * n_grid >= 2 ** 31:
+        raise ValueError("time_pointers on a shard: 1 <= n_sta * n_grid < 2^31 required")
+    if not float(dt) > 0.0:
+        raise ValueError("time_pointers on a shard: dt > 0 required")
+    own_global = np.asarray(own_global, dtype=np.int64)
+    n_own = int(own_global.size)
+    if tuple(tl_own.shape) != (n_own * n_sta, 2) or tl_own.dtype != torch.float32:
+        raise ValueError("time_pointers on a shard: expected fp32 travel times [%d, 2] (owned rows), got %s" % (n_own * n_sta, tuple(tl_own.shape)))
+    dev = tl_own.device
+    mine = torch.tensor([[-np.inf, 0.0]], dtype=torch.float64, device=dev)
+    if n_own:
+        finite = torch.isfinite(tl_own)
+        mine[0, 0] = torch.where(finite, tl_own, tl_own.new_full((), -np.inf)).max().double()      # (fp32 -> fp64: exact)
+        mine[0, 1] = (~finite).any().double()
+    every = mine.new_empty((transport.world, 1, 2))
+    transport.all_gather_rows(every, mine)
+    every = every.view(-1, 2).cpu().numpy()                  # the one read-back of the agreed constants
+    if every[:, 1].any():
+        raise ValueError("time_pointers on a shard: travel times must be finite (inf / NaN in the rows of rank(s) %s)"
+                         % ", ".join(str(r) for r in np.nonzero(every[:, 1])[0]))
+    if max_t is None:
+        max_t = np.float32(every[:, 0].max())                # (the host function's `trv.max()`: an fp32 scalar)
+    dt_partition = np.arange(-win, win + max_t + dt, dt)
+    n_t = int(dt_partition.size)
+    if n_t < 2:
+        raise ValueError("time_pointers on a shard: dt_partition needs at least two time steps")
+    k_tab = min(k, n_grid)
+    dtp = torch.from_numpy(dt_partition).to(dev)
+    node_global = torch.from_numpy(own_global.astype(np.int32)).to(dev)
+    cand = (candidates or engine.time_pointers_candidates)(tl_own, n_sta, node_global, dtp, k_tab)
+    cand_all = cand.new_empty((transport.world,) + tuple(cand.shape))
+    transport.all_gather_rows(cand_all, cand)
+    edges_p, edges_s = (merge or engine.time_pointers_merge)(cand_all, n_sta, n_t, k_tab, k_tab)
+    return edges_p, edges_s, dt_partition
+
+
 def exchange_halo_rows(rows_own, plan, n_sta, group=None, mode="a2a"):
     """Exchange of per-source-node row blocks: `rows_own` [n_own*S, C] -> halo rows [n_halo*S, C] in halo order: rank r sends, to
     every peer q, the S-row blocks of its owned nodes that q lists in `need[q][r]`. mode "a2a": one `all_to_all_single` with split
@@ -542,11 +597,25 @@ class ShardedPath(object):
         return self.local.assoc_fwd_parts(y_own, m_own, x_latent_own, Mask_own, edge_attr_own, self._exchange,
                                           lambda: self._exchange(self.wv_view()))
 
+    def time_pointers(self, tlatent, max_t=None, dt=1.0, k=10, win=10.0):
+        """The time-pointer tables of the whole product graph from this rank's own travel-time rows (`shard_time_pointers`: candidates
+        per rank, one all-gather, merge on every rank). tlatent: a `ShardRows` of this rank's rows (owned, or owned + halo), or the whole [G * S, 2] table, of which only the owned rows are
+        taken (cut out where the table lives). Returns (A_edges_p, A_edges_s, dt_partition, the owned rows as an own-only `ShardRows`)."""
+        tl_own = self.local_rows(tlatent, "tlatent", 2, own_only=True).contiguous()
+        edges_p, edges_s, dt_partition = shard_time_pointers(tl_own, self.plan.own_global, self.n_sta, self.n_grid, self.transport,
+                                                             max_t=max_t, dt=dt, k=k, win=win)
+        return edges_p, edges_s, dt_partition, ShardRows(tl_own, own_only=True)
+
     def pick_rows(self, s_own, a_edges_p, a_edges_s, dt_partition, tpick, ipick, tlatent, timeout=60.0):
         """The rows of `s` and `tlatent` that the picks' time-pointer entries list, for both LocalSliceLgCollapse heads, from the
         ranks that own them: `HipPath.lslc_rows` on this rank's rows, ONE ragged all-gather of the compact lists, every row placed at
-        its entry number -> table [2 * n_picks * 10, 32] (`HipPath.lslc_fwd_rows` takes it), the same on every rank."""
-        count, rows = self.local.lslc_rows(s_own, self.node_local, a_edges_p, a_edges_s, dt_partition, tpick, ipick, tlatent)
+        its entry number -> table [2 * n_picks * 10, 32] (`HipPath.lslc_fwd_rows` takes it), the same on every rank. tlatent: the
+        travel times of the whole product graph [G * S, >= 2], or a `ShardRows` of this rank's rows (tables built by `time_pointers`):
+        either way the arrival of a listed row is read by its owner and travels in the row."""
+        own = isinstance(tlatent, ShardRows)
+        if own:
+            tlatent = self.local_rows(tlatent, "tlatent", int(tlatent.shape[1]), own_only=True)
+        count, rows = self.local.lslc_rows(s_own, self.node_local, a_edges_p, a_edges_s, dt_partition, tpick, ipick, tlatent, tlatent_own=own)
         return place_pick_rows(self.transport.all_gather_ragged(rows, count, timeout), rows.shape[0])
 
     def path_fwd(self, Slice_ext, Mask_ext, edge_attr_own, pos_global, tail=None, pipelined=False):

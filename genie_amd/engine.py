@@ -346,6 +346,62 @@ def time_pointers_device(tlatent, n_sta, max_t=None, dt=1.0, k=10, win=10.0, pai
     return edges_p, edges_s, dt_partition
 
 
+TIME_POINTERS_EMPTY_KEY = (np.float64(np.finfo(np.float64).max).view(np.int64).item(), 2 ** 31 - 1)   # sorts after every candidate
+
+
+def time_pointers_candidates(tl_own, n_sta, node_global, dtp, k):
+    """A rank's share of the time-pointer tables of a source-node-sharded model (genie_time_pointers_candidates): tl_own fp32
+    [n_own * n_sta, 2] = the travel times of its owned source nodes in local node order, node_global int32 [n_own] their global ids,
+    dtp float64 [n_t] the time steps, all on the device -> int64 [2 * n_sta * n_t * k, 2]: per (phase, station, time step) the
+    min(k, n_own) smallest keys (bits of the float64 distance, GLOBAL product-node id), ascending, padded to k with
+    `TIME_POINTERS_EMPTY_KEY`. A rank that owns nothing runs no kernel and emits empty keys only. Precondition: every travel time is
+    finite (an inf / NaN entry is never listed). Nothing is read back here: the verdict belongs to the caller that holds the collective,
+    `dist.shard_time_pointers`, which checks its rows before this call so that every rank raises together."""
+    n_sta, k, n_t = int(n_sta), int(k), int(dtp.numel())
+    device = dtp.device
+    n_own = int(node_global.numel())
+    cand = torch.empty((2 * n_sta * n_t * k, 2), dtype=torch.int64, device=device)
+    if n_own == 0:
+        cand[:, 0] = TIME_POINTERS_EMPTY_KEY[0]
+        cand[:, 1] = TIME_POINTERS_EMPTY_KEY[1]
+        return cand
+    tl_own = _f32(tl_own, "tlatent", (n_own * n_sta, 2))
+    if node_global.dtype != torch.int32 or dtp.dtype != torch.float64 or not (tl_own.is_cuda and node_global.is_cuda and dtp.is_cuda):
+        raise ValueError("time_pointers_candidates: node_global int32, dtp float64, all three on the GPU")
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        nbytes = int(lib.genie_time_pointers_scratch_bytes(n_own * n_sta, n_sta, n_t))
+        if nbytes == 0:
+            raise ValueError("time_pointers_candidates: sizes out of contract (%d rows, n_sta = %d, %d time steps)" % (n_own * n_sta, n_sta, n_t))
+        scratch = torch.empty(size_class(nbytes), dtype=torch.uint8, device=device)
+        status = torch.empty(2, dtype=torch.int32, device=device)
+        _lib.check(lib.genie_time_pointers_candidates(_ptr(tl_own), n_own * n_sta, n_sta, _ptr(node_global.contiguous()), _ptr(dtp), n_t, k,
+                                                      _ptr(scratch), _ptr(cand), _ptr(status), _stream()), "genie_time_pointers_candidates")
+    return cand
+
+
+def time_pointers_merge(cand_all, n_sta, n_t, k, k_out):
+    """The ranks' candidate blocks merged (genie_time_pointers_merge): cand_all int64 [world, 2 * n_sta * n_t * k, 2] on the device ->
+    (A_edges_p, A_edges_s) int32 [n_sta * n_t * k_out], the k_out smallest keys per entry, nearest first. One read-back: an entry
+    the blocks do not fill is a ValueError."""
+    world = int(cand_all.shape[0])
+    n_sta, n_t, k, k_out = int(n_sta), int(n_t), int(k), int(k_out)
+    if cand_all.dtype != torch.int64 or not cand_all.is_cuda or tuple(cand_all.shape[1:]) != (2 * n_sta * n_t * k, 2):
+        raise ValueError("time_pointers_merge: cand_all must be an int64 GPU tensor [world, 2 * n_sta * n_t * k, 2]")
+    cand_all = cand_all.contiguous()
+    device = cand_all.device
+    lib = _lib.load()
+    with torch.cuda.device(device):
+        status = torch.empty(1, dtype=torch.int32, device=device)
+        edges_p = torch.empty(n_sta * n_t * k_out, dtype=torch.int32, device=device)
+        edges_s = torch.empty(n_sta * n_t * k_out, dtype=torch.int32, device=device)
+        _lib.check(lib.genie_time_pointers_merge(_ptr(cand_all), world, n_sta, n_t, k, k_out, _ptr(edges_p), _ptr(edges_s), _ptr(status),
+                                                 _stream()), "genie_time_pointers_merge")
+        if int(status.item()):
+            raise ValueError("time_pointers_merge: the ranks' candidates do not fill %d ranks of every station" % k_out)
+    return edges_p, edges_s
+
+
 def csr_from_edges(edge_index, n_target):
     """[2,E] edge list (row0 = j source, row1 = i target) -> (rowptr int32 [n+1], col int32 [E]);
     in-edges grouped by target in stable edge order."""
@@ -1213,11 +1269,12 @@ class HipPath(object):
         part(2)
         return out
 
-    def lslc_rows(self, s_own, node_local, a_edges_p, a_edges_s, dt_partition, tpick, ipick, tlatent):
+    def lslc_rows(self, s_own, node_local, a_edges_p, a_edges_s, dt_partition, tpick, ipick, tlatent, tlatent_own=False):
         """The lookup half of both `lslc_fwd` heads on a source-node shard (genie_lslc_rows): s_own [n_own * S, 30], node_local int32
         [G] (global source node -> local owned index, -1 elsewhere), the two int32 tables of GLOBAL product-node ids, tlatent [G * S, >= 2]
         -> (count int32 [1] on the device, rows [2 * n * 10, 32]): the entries this rank owns, in no particular order; column 31 holds
-        the bits of the entry number (head * n + pick) * 10 + slot."""
+        the bits of the entry number (head * n + pick) * 10 + slot. `tlatent_own`: tlatent holds this rank's owned rows only,
+        [n_own * S, >= 2] in the order of s_own (genie_lslc_rows_own)."""
         s_own = _f32(s_own, "s_own", (self.n_prod, 30))
         tpick = _f32(tpick, "tpick").reshape(-1)
         n = int(tpick.numel())
@@ -1225,18 +1282,19 @@ class HipPath(object):
         G = int(node_local.numel())
         if (a_edges_p.dtype != torch.int32 or a_edges_s.dtype != torch.int32 or not a_edges_p.is_cuda or not a_edges_s.is_cuda
                 or a_edges_p.numel() != a_edges_s.numel() or ipick.dtype != torch.int32 or ipick.numel() != n
-                or node_local.dtype != torch.int32 or not node_local.is_cuda or tlatent.dim() != 2 or tlatent.shape[0] != G * self.n_sta
-                or tlatent.shape[1] < 2):
+                or node_local.dtype != torch.int32 or not node_local.is_cuda or tlatent.dim() != 2
+                or tlatent.shape[0] != (self.n_prod if tlatent_own else G * self.n_sta) or tlatent.shape[1] < 2):
             raise ValueError("lslc_rows: a_edges_p / a_edges_s (equal sizes), ipick and node_local must be int32 GPU tensors, one ipick per "
-                             "pick, tlatent [n_grid * n_sta, >= 2] over the whole product graph")
+                             "pick, tlatent [n_grid * n_sta, >= 2] over the whole product graph (tlatent_own: over the owned rows)")
         a_edges_p, a_edges_s, ipick, node_local = a_edges_p.contiguous(), a_edges_s.contiguous(), ipick.contiguous(), node_local.contiguous()
         self.check_index_flags()
         t0, dt, dtp, l_dt = time_partition(dt_partition)
         count = torch.empty(1, dtype=torch.int32, device=self.device)
         rows = torch.empty((2 * n * 10, 32), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.genie_lslc_rows(self.ctx, _ptr(s_own), _ptr(node_local), G, _ptr(a_edges_p), _ptr(a_edges_s),
-                                            int(a_edges_p.numel()), l_dt, t0, dt, _ptr(dtp), _ptr(tlatent), int(tlatent.shape[1]), _ptr(tpick),
-                                            _ptr(ipick), n, _ptr(count), _ptr(rows), _stream()), "genie_lslc_rows")
+        entry = self.lib.genie_lslc_rows_own if tlatent_own else self.lib.genie_lslc_rows
+        _lib.check(entry(self.ctx, _ptr(s_own), _ptr(node_local), G, _ptr(a_edges_p), _ptr(a_edges_s), int(a_edges_p.numel()), l_dt, t0, dt,
+                         _ptr(dtp), _ptr(tlatent), int(tlatent.shape[1]), _ptr(tpick), _ptr(ipick), n, _ptr(count), _ptr(rows), _stream()),
+                   "genie_lslc_rows_own" if tlatent_own else "genie_lslc_rows")
         return count, rows
 
     def lslc_fwd_rows(self, head, table, tpick, phase_label, eps):

@@ -525,7 +525,8 @@ class GCN_Detection_Network_extended(nn.Module):
     `forward_fixed_source` takes the reference's arguments and returns the replicated `(y, x)` -- bit-equal to the unsharded model --,
     `embed_window` / `node_rows` / `genie_amd.apply` produce and consume only the rank's owned + halo rows. `forward` / `forward_fixed`
     (association heads) run sharded in eval mode / under no_grad with the default model definition, `(y, x, arv_p, arv_s)` replicated and
-    bit-equal too; training steps are not sharded and raise.
+    bit-equal too; `set_adjacencies_base(..., time_pointers=)` builds their tables from each rank's own travel-time rows. Training steps
+    are not sharded and raise.
     """
 
     def __init__(self, ftrns1, ftrns2, scale_rel=SCALE_REL, use_absolute_pos=False, device="cuda",
@@ -850,20 +851,33 @@ class GCN_Detection_Network_extended(nn.Module):
         and `tlatent` are `set_adjacencies`' time-pointer tables and travel times (module.py:941): needed by the 4-output
         `forward_fixed` only. `time_pointers=dict(max_t=, dt=, k=, win=)` builds the three tables from `tlatent` ([P, 2] rows or the
         [G, S, 2] array) on the device instead (`engine.time_pointers_device`: the tables of `graph.time_pointers`, bit for bit) and
-        leaves them on the model as if they had been passed; passing tables as well is a ValueError."""
+        leaves them on the model as if they had been passed; passing tables as well is a ValueError.
+        On a source-node-sharded model `time_pointers=` builds the same tables from each rank's OWN rows (`dist.shard_time_pointers`:
+        candidates per rank, one all-gather, merge; every rank must make the call): `tlatent` is a `ShardRows` (`node_rows(...)`) or a
+        callable `tlatent(source_node_ids) -> their rows` as `node_rows` takes. A table of the WHOLE product graph with `time_pointers=`
+        stays refused on a shard (NotImplementedError): it is the replication this form exists to avoid -- cut it down with
+        `node_rows(table)` first, or pass the whole-graph tables themselves. The model then keeps the travel times of its owned rows
+        only (`self.tlatent`: an own-only `ShardRows`). A travel time that is not finite on any rank is a ValueError on every rank."""
         if time_pointers is not None:
             if A_edges_p is not None or A_edges_s is not None or dt_partition is not None:
                 raise ValueError("set_adjacencies_base: pass the time-pointer tables (A_edges_p, A_edges_s, dt_partition) or time_pointers=, "
                                  "not both")
             if tlatent is None:
                 raise ValueError("time_pointers= needs the travel times (tlatent=)")
-            self._not_sharded("time_pointers= (the association heads' tables)")
+            if not (isinstance(tlatent, _dist.ShardRows) or callable(tlatent)):
+                self._not_sharded("time_pointers= from a travel-time table of the whole product graph (pass this rank's rows: "
+                                  "tlatent=net.node_rows(table) or a callable over source-node ids)")
         n_sta, n_grid = int(pos_loc.shape[0]), int(pos_src.shape[0])
         self.A_edges_p, self.A_edges_s, self.dt_partition, self.tlatent = A_edges_p, A_edges_s, dt_partition, tlatent
         self.A_src = torch.as_tensor(A_src_src)
         self._install(self._new_cartesian(_engine.csr_from_edges(A_sta_sta, n_sta), _engine.csr_from_edges(A_src_src, n_grid),
                                           n_sta, n_grid, pos_loc, pos_src), edge_attr, pos_loc, pos_src)
-        if time_pointers is not None:
+        if time_pointers is not None and self._shard is not None:
+            sp = self._shard
+            if callable(tlatent):
+                tlatent = self._rows_from_callable(tlatent, sp, own_only=True)
+            self.A_edges_p, self.A_edges_s, self.dt_partition, self.tlatent = sp.time_pointers(tlatent, **time_pointers)
+        elif time_pointers is not None:
             dev = self._hip.device
             self.tlatent = _engine.tlatent_rows(tlatent, dev)
             if int(self.tlatent.shape[0]) != n_sta * n_grid:
@@ -1098,17 +1112,28 @@ class GCN_Detection_Network_extended(nn.Module):
                                       "source-node-sharded model (process_group / shard): the sharded association heads serve the default "
                                       "model definition")
         if A_edges_p is None or A_edges_s is None or tlatent is None:
-            self._not_sharded("forward / forward_fixed without the time-pointer tables and travel times of the WHOLE product graph (pass A_edges_p, "
-                              "A_edges_s, dt_partition, tlatent to set_adjacencies / set_adjacencies_base; time_pointers= is not built on a shard)")
+            self._not_sharded("forward / forward_fixed without the time-pointer tables and travel times (set_adjacencies_base(..., tlatent=this "
+                              "rank's rows, time_pointers=...) builds them from every rank's own rows; or pass A_edges_p, A_edges_s, dt_partition "
+                              "and tlatent of the whole product graph to set_adjacencies / set_adjacencies_base)")
 
     def _forward_fixed_sharded(self, Slice, Mask, tpick, ipick, phase_label, x_temp_cuda_cart, x_query_cart, x_query_src_cart, t_query,
                                tq_sample, trv_out_q):
         """`forward_fixed` on this rank's shard (genie_amd/dist.py). The front leaves the owned rows of x_latent; the replicated tail gives
         every rank y, y_latent, x and x_src; the P-sized association heads run on the owned rows with one halo exchange per layer
-        (`ShardedPath.assoc_fwd`); the rows the picks' time-pointer entries list travel in ONE ragged all-gather from their owners
-        (`ShardedPath.pick_rows`, genie_lslc_rows), and the pick-sized heads run replicated on them. Every rank joins every collective,
-        whatever it owns."""
+        (`ShardedPath.assoc_fwd`); the rows the picks' time-pointer entries list travel in ONE ragged all-gather from their owners, each with its
+        travel time (`ShardedPath.pick_rows`, genie_lslc_rows: `self.tlatent` is the whole table or this rank's `ShardRows`), and the
+        pick-sized heads run replicated on them. Every rank joins every collective, whatever it owns."""
         self._sharded_forward_guard(getattr(self, "A_edges_p", None), getattr(self, "A_edges_s", None), getattr(self, "tlatent", None))
+        return self._sharded_four_outputs(Slice, Mask, tpick, ipick, phase_label, x_temp_cuda_cart, x_query_cart, x_query_src_cart, t_query,
+                                          tq_sample, trv_out_q)
+
+    def _sharded_four_outputs(self, Slice, Mask, tpick, ipick, phase_label, x_temp_cuda_cart, x_query_cart, x_query_src_cart, t_query,
+                              tq_sample, trv_out_q):
+        """The computation behind `_forward_fixed_sharded`, past its guard. It holds for all three model definitions: under
+        `use_updated_model_definition` / `use_absolute_pos` the front and `genie_assoc_fwd_part` add the static per-station and
+        per-source-node terms from the tables `ShardedPath.set_edge_features` / `set_absolute_pos` placed in the local context over the
+        extended node list, the replicated context its own -- the unsharded bits (tests/test_shard_time_pointers_gpu.py). The public calls
+        still refuse the two definitions on a shard (`_sharded_forward_guard`)."""
         sp, full = self._shard, self._hip
         sp.sync_weights(self._path_params, self._weight_split())
         if not (getattr(sp.local, "assoc_ready", False) and getattr(full, "assoc_ready", False)):

@@ -538,6 +538,13 @@ int genie_lslc_fwd(genie_ctx* ctx, int phase_head, const float* s_rows, const in
 int genie_lslc_rows(genie_ctx* ctx, const float* s_own, const int32_t* node_local, int n_grid_all, const int32_t* a_edges_p,
                     const int32_t* a_edges_s, int64_t n_edges, int l_dt, float t0, float dt, const float* dt_partition, const float* tlatent,
                     int tl_stride, const float* tpick, const int32_t* ipick, int n_picks, int32_t* count, float* rows, void* stream);
+/* genie_lslc_rows for a rank that holds the travel times of its owned rows only (tables built by genie_time_pointers_candidates /
+ * _merge): tlatent_own [n_own * n_sta][tl_stride] (n_own = the context's n_grid) in the local node order of s_own. The arrival of a listed row is read where its s row
+ * is, on the rank that owns it, and travels in column 30 of the same compact row: the lists, and the one all-gather, are unchanged. */
+int genie_lslc_rows_own(genie_ctx* ctx, const float* s_own, const int32_t* node_local, int n_grid_all, const int32_t* a_edges_p,
+                        const int32_t* a_edges_s, int64_t n_edges, int l_dt, float t0, float dt, const float* dt_partition,
+                        const float* tlatent_own, int tl_stride, const float* tpick, const int32_t* ipick, int n_picks, int32_t* count,
+                        float* rows, void* stream);
 int genie_lslc_fwd_rows(genie_ctx* ctx, int phase_head, const float* table, float eps, const float* tpick, const float* phase_label,
                         int n_picks, float* out, void* stream);
 
@@ -680,6 +687,23 @@ int genie_band_peaks_fill(const float* band, int rows, int64_t width, int64_t st
 size_t genie_time_pointers_scratch_bytes(int64_t n_prod, int n_sta, int n_t);
 int genie_time_pointers(const float* trv, int64_t n_prod, int n_sta, const int32_t* sta_of_prod, const double* dt_partition, int n_t, int k,
                         void* scratch, int32_t* edges_p, int32_t* edges_s, int32_t* status, void* stream);
+
+/* The same tables of a source-node-sharded model (Cartesian form), built from each rank's OWN travel-time rows: candidates per rank, one
+ * all-gather of the fixed-size key blocks by the caller, merge on every rank. Both kernels rank with genie_time_pointers' key and its
+ * wave-wide insertion, so the tables are those of genie_time_pointers over the whole product graph, bit for bit.
+ * genie_time_pointers_candidates: trv_own [n_prod_own, 2] = the rows of the rank's owned source nodes in its local node order (local
+ *   row l * n_sta + i), node_global int32 [n_prod_own / n_sta]: local source node -> global one (global product node = g * n_sta + i,
+ *   which must stay below 2^31). cand: int64 [2][n_sta][n_t][k][2], 16-byte aligned: per (phase, station, time step) the rank's
+ *   min(k, n_own) smallest keys, ascending, each as (the bits of the float64 distance, the GLOBAL product-node id); the remaining
+ *   slots hold the key (max double, 2^31 - 1), which sorts after every candidate -- a rank that owns fewer than k nodes does not cycle.
+ *   scratch: genie_time_pointers_scratch_bytes(n_prod_own, n_sta, n_t); status [2] as genie_time_pointers.
+ * genie_time_pointers_merge: cand int64 [world][2][n_sta][n_t][k][2] = every rank's block, in any rank order -> the k_out <= k smallest
+ *   keys per entry, nearest first, as int32 ids in edges_p / edges_s [n_sta * n_t * k_out]. status [1] int32: 1 when an entry has
+ *   fewer than k_out real keys (the blocks do not cover the station). The caller passes k_out = min(k, number of source nodes). */
+int genie_time_pointers_candidates(const float* trv_own, int64_t n_prod_own, int n_sta, const int32_t* node_global, const double* dt_partition,
+                                   int n_t, int k, void* scratch, int64_t* cand, int32_t* status, void* stream);
+int genie_time_pointers_merge(const int64_t* cand, int world, int n_sta, int n_t, int k, int k_out, int32_t* edges_p, int32_t* edges_s,
+                              int32_t* status, void* stream);
 
 /* Stacking of window read-outs into Out_2 (the apply loop's accumulation, process_continuous_days.py:797-805), one launch per flush:
  *   for k in 0..n_windows-1 (window order), for j in 0..n_offsets-1 (offset order):
