@@ -2968,6 +2968,18 @@ int launch_readout_query(genie_ctx* c, bool prefetch, const RoArgs& a, hipStream
     k<<<tl_blocks(a.N, c->tail_cu_ro), 256, lds, st>>>(a);
     return GENIE_OK;
 }
+// both read-outs of one window in one launch (k_readouts_m): the query head's workgroups first, then the grid head's; each head gets the
+// workgroups its own launcher would give it. `q.cv` must be complete (launch_ro_pre in front on the same stream). No prefetch form:
+// see k_readouts_m.
+int launch_readouts(genie_ctx* c, const StageCall& call, const RoArgs& q, const RoArgs& g, hipStream_t st) {
+    const bool wide = tail_wide(c, call);
+    const int lds = (int)(sizeof(float) * (ROM_LDS_FLOATS + (wide ? 4 * 16 * RO_SCS : 0)));      // the larger of the two heads' sizes
+    const auto k = wide ? k_readouts_m<true> : k_readouts_m<false>;
+    GENIE_TRY(raise_lds_limit(c, (const void*)k, (int)(sizeof(float) * (ROM_LDS_FLOATS + 4 * 16 * RO_SCS))));
+    const int nb_q = tl_blocks(q.N, c->tail_cu_ro), nb_g = tl_blocks(g.N, c->tail_cu_ro);
+    k<<<nb_q + nb_g, 256, lds, st>>>(q, g, nb_q);
+    return GENIE_OK;
+}
 // the per-grid-node table cv of the query read-out, one window
 void launch_ro_pre(const genie_ctx* c, bool wide, const float* x_spatial, float* cv, hipStream_t st) {
     const auto k = wide ? k_ro_pre_m<true> : k_ro_pre_m<false>;
@@ -3020,6 +3032,28 @@ int readout_query_impl(genie_ctx* c, const float* x_spatial, const float* x_grid
 int genie_readout_query(genie_ctx* c, const float* x_spatial, const float* x_grid, const float* x_query, const int32_t* knn,
                         int n_query, int k, const float* t_query, int n_t, float* x_out, void* ws, void* stream) {
     return readout_query_impl(c, x_spatial, x_grid, x_query, knn, n_query, k, t_query, n_t, x_out, nullptr, ws, stream);
+}
+
+// genie_readout_grid and genie_readout_query of one window: k_ro_pre_m, then both heads in ONE launch (k_readouts_m)
+int genie_readouts(genie_ctx* c, const float* x_spatial, const float* x_grid, const float* x_query, const int32_t* knn, int n_query,
+                   int k, const float* t_query, int n_t, float* y_out, float* x_out, void* ws, void* stream) {
+    { int rcw = check_ws(c, ws); if (rcw) return rcw; }
+    if (!x_spatial || !x_grid || !x_query || !knn || !t_query || !y_out || !x_out) return fail(GENIE_ERR_ARG, "genie_readouts: null argument");
+    if (k != RO_K) return fail(GENIE_ERR_ARG, "genie_readouts: k must be 10 (module.py:280)");
+    if (n_t < 1 || n_t > RO_TMAX) return fail(GENIE_ERR_ARG, "genie_readouts: 1 <= n_t <= 10 required");
+    if (n_query < 1) return fail(GENIE_ERR_ARG, "genie_readouts: n_query < 1");
+    hipStream_t st = (hipStream_t)stream;
+    GENIE_TRY(ensure_packed(c, st));
+    RoArgs a = make_ro_args(c);
+    a.T = n_t; a.x_spatial = x_spatial; a.t_query = t_query;
+    RoArgs g = a, q = a;
+    g.N = g.Nw = c->G; g.out = y_out; g.img = c->packed[PL_RO0];
+    float* cvbuf = (float*)ws + c->o_cv + c->slot * c->slot_stride;
+    q.N = q.Nw = n_query; q.x_grid = x_grid; q.x_query = x_query; q.knn = knn; q.out = x_out; q.cv = cvbuf; q.img = c->packed[PL_RO1];
+    launch_ro_pre(c, tail_wide(c, kInference), x_spatial, cvbuf, st);
+    GENIE_TRY(launch_readouts(c, kInference, q, g, st));
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
 }
 
 // The latent inputs of TemporalAttention next to the read-outs (the 4-output forward needs them, module.py:978-981):

@@ -538,13 +538,14 @@ __global__ __launch_bounds__(256) void k_ro_pre_m(const float* __restrict__ x_sp
 // score x value products, per node, go through a per-wave LDS scratch (a lane needs all T x 5 scores of its node).
 constexpr int RO_SCS = 68;      // floats per node in the score scratch: [5 heads][12 time slots] + pad
 constexpr int ROM_LDS_FLOATS = GR_IMG_FLOATS + 5 * 256 + 10 * 80 + 4 * 16 * RO_SCS;
-template <int MODE, bool WIDE = false, bool PF = false>      // PF (MODE 1): the gathered rows of head h + 1 requested before head h is worked on
-__global__ __launch_bounds__(256) void k_readout_m(RoArgs a) {
+// The body of a read-out workgroup: block `blk` of `nblk` over the 16-node tiles of `a`, LDS from `sm` (k_readout_m runs one head per
+// launch, k_readouts_m both heads in one).
+template <int MODE, bool WIDE, bool PF>      // PF (MODE 1): the gathered rows of head h + 1 requested before head h is worked on
+__device__ __forceinline__ void ro_body(const RoArgs& a, const unsigned blk, const unsigned nblk, float* sm) {
     static_assert(!(WIDE && MODE != 0), "the fp64 form exists for the grid read-out (MODE 0)");
     typedef typename TlV<WIDE>::v V;
     typedef typename std::conditional<WIDE, double, float>::type R;
     constexpr int SCW = WIDE ? 2 : 1;        // the score scratch holds R values
-    extern __shared__ __attribute__((aligned(16))) float sm[];
     const TlImg im = tl_stage_image(sm, a.img, GR_GROUPS, GR_BIAS);
     float* qf = sm + GR_IMG_FLOATS;          // [5][64][4]: A fragments of the temporal queries, head h
     float* et = qf + 5 * 256;                // [10][80] (MODE 1): f_queries columns 0..2, f_context / f_values edge columns, f_queries bias
@@ -588,7 +589,7 @@ __global__ __launch_bounds__(256) void k_readout_m(RoArgs a) {
     const R inv_sqrt_l = WIDE ? (R)(1.0 / sqrt(15.0)) : (R)(1.f / sqrtf(15.f));
     R* ws = (R*)scr + (wave * 16 + j) * RO_SCS;
     const int ntiles = (a.N + 15) / 16;
-    for (int tile = blockIdx.x * 4 + wave; tile < ntiles; tile += gridDim.x * 4) {
+    for (int tile = blk * 4 + wave; tile < ntiles; tile += nblk * 4) {
         const int n = tile * 16 + j;
         const bool ok = n < a.N;
         const int nc = ok ? n : a.N - 1;
@@ -757,6 +758,24 @@ __global__ __launch_bounds__(256) void k_readout_m(RoArgs a) {
         }
         GSYNC();
     }
+}
+template <int MODE, bool WIDE = false, bool PF = false>
+__global__ __launch_bounds__(256) void k_readout_m(RoArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    ro_body<MODE, WIDE, PF>(a, blockIdx.x, gridDim.x, sm);
+}
+// Both heads of one window in ONE launch: given x_spatial (and cv) they are independent, and a window's 16-node tiles of both (625 + 625
+// one-wave tiles at 10 000 nodes / queries) fit on the chip together, so they run side by side without a second stream. Workgroups
+// [0, nb_q) are the query head (MODE 1 on `q`: the longer chain, handed out first), the rest the grid head (MODE 0 on `g`); the branch is
+// workgroup-uniform, no workgroup waits for another, and each body is the one k_readout_m runs: bit-identical results.
+// The query body is the one without the prefetch (186 VGPRs, two waves per SIMD): the PF body's 259 VGPRs leave a CU room for one
+// workgroup, so the 157 + 157 workgroups of a 10 000-node window no longer fit on 256 CUs at once, and held to 256 VGPRs it spills 6.
+// Measured, the launch lasts the same with and without PF (39.4 / 39.6 us at 10 000 nodes and queries).
+template <bool WIDE>
+__global__ __launch_bounds__(256) void k_readouts_m(RoArgs q, RoArgs g, int nb_q) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    if (blockIdx.x < (unsigned)nb_q) ro_body<1, false, false>(q, blockIdx.x, (unsigned)nb_q, sm);
+    else ro_body<0, WIDE, false>(g, blockIdx.x - (unsigned)nb_q, gridDim.x - (unsigned)nb_q, sm);
 }
 
 // LocalSliceLgCollapse (module.py:610-659), pick-sized: per pick a the K = 10 product nodes of its station whose theoretical

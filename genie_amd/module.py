@@ -933,7 +933,7 @@ class GCN_Detection_Network_extended(nn.Module):
             return y, x
         x_spatial, _, _ = self._path(Slice, Mask, x_temp_cuda_cart)                       # :1010-1014
         knn = self.SpatialAttention.query_table(x_query_cart, x_temp_cuda_cart, 10)        # :282 (cached per query set)
-        # :1015-1018: the grid read-out (y) and the query read-out (x) side by side on two streams, joined before returning
+        # :1015-1018: the grid read-out (y) and the query read-out (x) side by side in one launch (genie_readouts)
         return self._hip.readouts_forked(x_spatial, x_temp_cuda_cart, x_query_cart, knn, t_query)
 
     def forward_fixed_source_pipelined(self, Slice, Mask, tpick, ipick, phase_label, locs_use_cart, x_temp_cuda_cart,

@@ -295,6 +295,11 @@ int genie_readout_grid(genie_ctx* ctx, const float* x_spatial, const float* t_qu
 int genie_readout_query(genie_ctx* ctx, const float* x_spatial, const float* x_grid, const float* x_query,
                         const int32_t* knn, int n_query, int k, const float* t_query, int n_t, float* x_out,
                         void* ws, void* stream);
+/* Both read-outs of one window: y_out as genie_readout_grid, x_out as genie_readout_query (same arguments, same checks), bit-identical
+ * to the two calls. Given x_spatial the heads are independent and each fills a fraction of the GPU, so after the per-grid-node table of
+ * the query head both run in ONE launch, side by side on one stream. */
+int genie_readouts(genie_ctx* ctx, const float* x_spatial, const float* x_grid, const float* x_query, const int32_t* knn,
+                   int n_query, int k, const float* t_query, int n_t, float* y_out, float* x_out, void* ws, void* stream);
 /* The same read-outs with the latent input of TemporalAttention exported next to them, as the 4-output forward needs it
  * (module.py:978-981): y_latent_out [n_grid, 30] = SpatialDirect(x_spatial) (:978), latent_out [n_query, 30] =
  * SpatialAttention(x_spatial, x_query, x_grid) (:981, `x_src` for the candidate sources). */
