@@ -494,7 +494,10 @@ __global__ __launch_bounds__(1024) void k_knn_b(const float* __restrict__ xc, in
 // insertion happens ~K ln(n / K) times per query: after the first few hundred candidates a wave rarely leaves the distance-and-compare
 // path. That path is fp32 with a guard band (a candidate is dropped only if its fp32 distance exceeds the list's worst by more than
 // 1e-5 relative: fp32 rounding is < 1e-6); everything that passes is decided on the EXACT distance (fp64 of the fp32 coordinates,
-// as k_knn): same neighbours in the same order (distance, then index), bit for bit.
+// as k_knn): same neighbours in the same order (distance, then index), bit for bit -- on lists full of EXACTLY equal distances too
+// (tests/test_knn_ties_gpu.py against a float64 stable argsort on the host). The list is put in order by counting, not by exchanges:
+// the compare-and-swap network this kernel used to end with wrote an index twice and dropped another on the device when three or
+// more of the K best tied (profiles/EXPERIMENTS.md, tools/knn_tie_probe.hip).
 constexpr int KNN_TILE = 2048;
 template <int K>
 __global__ __launch_bounds__(256) void k_knn_t(const float* __restrict__ xc, int nc, const float* __restrict__ xq, int nq, int k,
@@ -507,7 +510,7 @@ __global__ __launch_bounds__(256) void k_knn_t(const float* __restrict__ xc, int
     // The K best so far UNSORTED, with the slot of the worst one (largest (distance, index)) tracked: an accepted candidate overwrites
     // that slot and the worst is found again (K compares) -- about half the instructions of keeping the list sorted by a K-step
     // bubble, and in this kernel the accept path is what a wave mostly pays for (some lane accepts in ~a quarter of the steps). The
-    // list is sorted once per query at the end.
+    // list is put in order once per query at the end: every entry is written at the place its rank among the K gives it.
     double bd[K];
     int bi[K];
 #pragma unroll
@@ -548,19 +551,16 @@ __global__ __launch_bounds__(256) void k_knn_t(const float* __restrict__ xc, int
             thr = thr + thr * 1e-5f;                    // inf stays inf
         }
     }
-    // sort by (distance, index): K is small, once per query
+    // in (distance, index) order, as k_knn_ix writes its list: an entry's place is the number of entries before it (the entries are
+    // distinct -- the placeholders by their indices --, so the places are 0 .. K - 1 once each); K is small, once per query
+    if (qi >= nq) return;
 #pragma unroll
-    for (int a = 0; a < K - 1; ++a) {
+    for (int t = 0; t < K; ++t) {
+        int place = 0;
 #pragma unroll
-        for (int t = 0; t < K - 1 - a; ++t) {
-            if (bd[t + 1] < bd[t] || (bd[t + 1] == bd[t] && bi[t + 1] < bi[t])) {
-                const double td = bd[t]; const int ti = bi[t];
-                bd[t] = bd[t + 1]; bi[t] = bi[t + 1]; bd[t + 1] = td; bi[t + 1] = ti;
-            }
-        }
+        for (int s = 0; s < K; ++s) place += (bd[s] < bd[t] || (bd[s] == bd[t] && bi[s] < bi[t])) ? 1 : 0;
+        if (place < k) out[(long long)qi * k + place] = bi[t] >= 0x7fffffff - K ? -1 : bi[t];
     }
-    if (qi < nq)
-        for (int r = 0; r < k; ++r) out[(long long)qi * k + r] = bi[r] >= 0x7fffffff - K ? -1 : bi[r];
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,7 +1,9 @@
 """GPU: the cell-index kNN (`engine.KnnIndex`, genie_knn_index_build / genie_knn_indexed) returns the table of the brute-force search.
 
 The yardstick everywhere is `engine.knn_device(..., index=None)` on the same tensors, compared with `torch.equal`: that call is pinned
-to an exact fp64 host search by tests/test_hip_parity.py, so it is the reference here and not the code under test. Shapes are small
+to an exact fp64 host search by tests/test_hip_parity.py and, on tie-laden inputs and for each of its three kernels, by
+tests/test_knn_ties_gpu.py (which holds the indexed search to the host as well), so it is the reference here and not the code under
+test; index on and off are bit-equal at every size, the lattice with at least 16 384 queries included. Shapes are small
 because what can go wrong is structural: the order of candidates (ties), the stop rule at cell faces, degenerate boxes, queries outside
 the box, empty cells. Then the switch: `knn_index` on a model, through `SpatialAttention.query_table`, `forward_fixed_source` and
 `refine_sources`, bit-equal with it on and off."""
@@ -105,6 +107,12 @@ def test_ties_on_a_lattice():
     check(xc, xc, KS, exclude_self=True, index=index)
     check(xc, _t(lat + 0.5), KS, index=index)
     check(xc, _t(lat * 7.0 - 30.0), (10, 16), index=index)                    # lattice-aligned queries far outside as well
+    # the size the model's switch acts on, where the brute-force arm is genie_knn's lane-per-query kernel: the lattice ten times
+    # (17 280 rows, on the points) and its cell centres ten times
+    big = np.tile(lat, (10, 1))
+    assert big.shape[0] >= engine.KNN_INDEX_MIN_QUERIES
+    check(xc, _t(big), (1, 8, 10), index=index)
+    check(xc, _t(big + 0.5), (8, 10), index=index)
 
 
 def test_all_points_identical():
