@@ -356,214 +356,6 @@ __global__ void k_where_am_i(int* __restrict__ out) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Exact k-nearest-neighbour search on the device: the `knn(x_context / 1000, x_query / 1000, k)` calls of the
-// reference -- SpatialAttention's query edges (module.py:282; a NEW 112 000-point query set per candidate in the refine pass,
-// process_continuous_days.py:926-980) and the base graphs of the product graph (`knn(x/1000, x/1000, k + 1)` +
-// `remove_self_loops`, process_utils.py:718-719). Brute force in fp64 on the fp32 coordinates themselves (the
-// common 1 / 1000 scale does not change the order; coordinate differences of fp32 values are exact in fp64) (3-D, n_context
-// is 10^4..10^5: 10^9 pair distances = a millisecond): one wave per query, lane l scans candidates l, l + 64, ... keeping its K
-// best in registers (sorted, ties by smaller index), then K rounds of a wave-wide lexicographic (distance, index) minimum pop
-// the global K best in order. exclude_self: skip candidate == query id (query set = context set).
-// ------------------------------------------------------------------------------------------------
-template <int K>
-__global__ __launch_bounds__(256) void k_knn(const float* __restrict__ xc, int nc, const float* __restrict__ xq, int nq, int k,
-                                             int exclude_self, int32_t* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int qi = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (qi >= nq) return;
-    const double q0 = (double)xq[qi * 3 + 0], q1 = (double)xq[qi * 3 + 1], q2 = (double)xq[qi * 3 + 2];
-    double bd[K];
-    int bi[K];
-#pragma unroll
-    for (int t = 0; t < K; ++t) { bd[t] = __builtin_inf(); bi[t] = 0x7fffffff; }
-    // candidates four at a time: their twelve coordinate loads are in flight together (112 000 queries x 10 000 points 4.3 -> 3.7 ms,
-    // 50 000 x 50 000 at k = 15 14.7 -> 10.4 ms, the 8 source queries of forward_fixed 210 -> 173 us: tools/knn_time.py, ff_time.py)
-    constexpr int UB = 4;
-    for (int c0 = lane; c0 < nc; c0 += 64 * UB) {
-        float cx[UB][3];
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-            const int c = min(c0 + 64 * u, nc - 1);
-            cx[u][0] = xc[c * 3 + 0]; cx[u][1] = xc[c * 3 + 1]; cx[u][2] = xc[c * 3 + 2];
-        }
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-            const int c = c0 + 64 * u;
-            if (c >= nc || (exclude_self && c == qi)) continue;
-            const double d0 = q0 - (double)cx[u][0], d1 = q1 - (double)cx[u][1], d2 = q2 - (double)cx[u][2];   // exact
-            double d = __dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2));
-            int id = c;
-            if (d < bd[K - 1]) {          // candidates arrive in increasing index order: a tie never displaces an earlier entry
-#pragma unroll
-                for (int t = 0; t < K; ++t) {
-                    if (d < bd[t] || (d == bd[t] && id < bi[t])) {       // lexicographic (distance, index): a displaced entry that ties with
-                                                                          // the next slot goes in front of it (it has the smaller index)
-                        const double td = bd[t]; const int ti = bi[t];
-                        bd[t] = d; bi[t] = id; d = td; id = ti;
-                    }
-                }
-            }
-        }
-    }
-    for (int r = 0; r < k; ++r) {
-        double md = bd[0];
-        int mi = bi[0];
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const double od = __shfl_xor(md, s);
-            const int oi = __shfl_xor(mi, s);
-            if (od < md || (od == md && oi < mi)) { md = od; mi = oi; }
-        }
-        if (bi[0] == mi && bd[0] == md) {        // the owner pops its head (indices are unique across lanes)
-#pragma unroll
-            for (int t = 0; t + 1 < K; ++t) { bd[t] = bd[t + 1]; bi[t] = bi[t + 1]; }
-            bd[K - 1] = __builtin_inf(); bi[K - 1] = 0x7fffffff;
-        }
-        if (lane == 0) out[(long long)qi * k + r] = mi == 0x7fffffff ? -1 : mi;
-    }
-}
-
-// A handful of queries (the one spatial query and the one candidate source of the association pass, process_continuous_days.py:1052;
-// the 4-8 source queries of a training sample): with a wave per query ONE wave walked the whole context -- 134-170 us per call at 10 000
-// grid nodes, twice per forward_fixed -- so a query gets a workgroup of 16 waves instead: every lane scans a 1024-th of the context
-// (same exact arithmetic and per-lane lists as k_knn), every wave pops its K best into LDS, wave 0 merges the 16 lists. Same table.
-template <int K>
-__global__ __launch_bounds__(1024) void k_knn_b(const float* __restrict__ xc, int nc, const float* __restrict__ xq, int nq, int k,
-                                                int exclude_self, int32_t* __restrict__ out) {
-    __shared__ double sd[16 * K];
-    __shared__ int si[16 * K];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int qi = blockIdx.x;
-    const double q0 = (double)xq[qi * 3 + 0], q1 = (double)xq[qi * 3 + 1], q2 = (double)xq[qi * 3 + 2];
-    double bd[K];
-    int bi[K];
-#pragma unroll
-    for (int t = 0; t < K; ++t) { bd[t] = __builtin_inf(); bi[t] = 0x7fffffff; }
-    auto insert = [&](double d, int id) {
-        if (d < bd[K - 1] || (d == bd[K - 1] && id < bi[K - 1])) {
-#pragma unroll
-            for (int t = 0; t < K; ++t) {
-                if (d < bd[t] || (d == bd[t] && id < bi[t])) {
-                    const double td = bd[t]; const int ti = bi[t];
-                    bd[t] = d; bi[t] = id; d = td; id = ti;
-                }
-            }
-        }
-    };
-    auto pop = [&](double& md, int& mi) {          // the wave's smallest (distance, index); its owner drops it
-        md = bd[0]; mi = bi[0];
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const double od = __shfl_xor(md, s);
-            const int oi = __shfl_xor(mi, s);
-            if (od < md || (od == md && oi < mi)) { md = od; mi = oi; }
-        }
-        if (bi[0] == mi && bd[0] == md && mi != 0x7fffffff) {
-#pragma unroll
-            for (int t = 0; t + 1 < K; ++t) { bd[t] = bd[t + 1]; bi[t] = bi[t + 1]; }
-            bd[K - 1] = __builtin_inf(); bi[K - 1] = 0x7fffffff;
-        }
-    };
-    for (int c = threadIdx.x; c < nc; c += 1024) {
-        if (exclude_self && c == qi) continue;
-        const double d0 = q0 - (double)xc[c * 3 + 0], d1 = q1 - (double)xc[c * 3 + 1], d2 = q2 - (double)xc[c * 3 + 2];   // exact
-        insert(__dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2)), c);
-    }
-    for (int r = 0; r < K; ++r) {
-        double md; int mi;
-        pop(md, mi);
-        if (lane == 0) { sd[wave * K + r] = md; si[wave * K + r] = mi; }
-    }
-    __syncthreads();
-    if (wave != 0) return;
-#pragma unroll
-    for (int t = 0; t < K; ++t) { bd[t] = __builtin_inf(); bi[t] = 0x7fffffff; }
-    for (int e = lane; e < 16 * K; e += 64)
-        if (si[e] != 0x7fffffff) insert(sd[e], si[e]);
-    for (int r = 0; r < k; ++r) {
-        double md; int mi;
-        pop(md, mi);
-        if (lane == 0) out[(long long)qi * k + r] = mi == 0x7fffffff ? -1 : mi;
-    }
-}
-
-// The same search with ONE LANE per query, for large query sets (the refine pass's 112 000-point clouds, process_continuous_days.py:929:
-// with a wave per query every candidate step paid a lane's insertion -- 156 candidates per lane, a quarter of them enter its list -- and
-// the 64 partial lists were merged afterwards: 4.3 ms of the pass's 4.9 ms per source). Here a lane scans every candidate (tiles of the
-// context staged in LDS, read by all lanes at the same address: a broadcast), its list only ever holds the K best so far, and an
-// insertion happens ~K ln(n / K) times per query: after the first few hundred candidates a wave rarely leaves the distance-and-compare
-// path. That path is fp32 with a guard band (a candidate is dropped only if its fp32 distance exceeds the list's worst by more than
-// 1e-5 relative: fp32 rounding is < 1e-6); everything that passes is decided on the EXACT distance (fp64 of the fp32 coordinates,
-// as k_knn): same neighbours in the same order (distance, then index), bit for bit -- on lists full of EXACTLY equal distances too
-// (tests/test_knn_ties_gpu.py against a float64 stable argsort on the host). The list is put in order by counting, not by exchanges:
-// the compare-and-swap network this kernel used to end with wrote an index twice and dropped another on the device when three or
-// more of the K best tied (profiles/EXPERIMENTS.md, tools/knn_tie_probe.hip).
-constexpr int KNN_TILE = 2048;
-template <int K>
-__global__ __launch_bounds__(256) void k_knn_t(const float* __restrict__ xc, int nc, const float* __restrict__ xq, int nq, int k,
-                                               int exclude_self, int32_t* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) float tile[KNN_TILE * 4];
-    const int qi = blockIdx.x * 256 + threadIdx.x;
-    const int qc = qi < nq ? qi : nq - 1;
-    const float f0 = xq[qc * 3 + 0], f1 = xq[qc * 3 + 1], f2 = xq[qc * 3 + 2];
-    const double q0 = (double)f0, q1 = (double)f1, q2 = (double)f2;
-    // The K best so far UNSORTED, with the slot of the worst one (largest (distance, index)) tracked: an accepted candidate overwrites
-    // that slot and the worst is found again (K compares) -- about half the instructions of keeping the list sorted by a K-step
-    // bubble, and in this kernel the accept path is what a wave mostly pays for (some lane accepts in ~a quarter of the steps). The
-    // list is put in order once per query at the end: every entry is written at the place its rank among the K gives it.
-    double bd[K];
-    int bi[K];
-#pragma unroll
-    for (int t = 0; t < K; ++t) { bd[t] = __builtin_inf(); bi[t] = 0x7fffffff - t; }      // (placeholders with distinct indices; slot 0 is the worst)
-    double wd = __builtin_inf();
-    int wi = 0x7fffffff;                             // the worst entry: candidates arrive in increasing index order, so a tie never displaces it
-    float thr = __builtin_inff();                    // fp32 guard of wd
-    // tiles of the context staged in LDS, read by all lanes at the same address (a broadcast). (Reading the wave-uniform candidate
-    // through the scalar cache instead -- three 16-byte scalar loads per four candidates, no staging, no barrier -- measured the same:
-    // 2.44 against 2.38 ms at 112 000 x 10 000.)
-    for (int c0 = 0; c0 < nc; c0 += KNN_TILE) {
-        const int n = min(KNN_TILE, nc - c0);
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += 256) {
-            const float* p = xc + (long long)(c0 + i) * 3;
-            *(f32x4*)(tile + i * 4) = f32x4{p[0], p[1], p[2], 0.f};
-        }
-        __syncthreads();
-        for (int i = 0; i < n; ++i) {
-            const f32x4 cv = *(const f32x4*)(tile + i * 4);
-            const float e0 = f0 - cv.x, e1 = f1 - cv.y, e2 = f2 - cv.z;
-            const float d32 = e0 * e0 + e1 * e1 + e2 * e2;
-            if (!(d32 <= thr)) continue;
-            const int c = c0 + i;
-            if (exclude_self && c == qi) continue;
-            const double d0 = q0 - (double)cv.x, d1 = q1 - (double)cv.y, d2 = q2 - (double)cv.z;                       // exact
-            const double d = __dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2));
-            if (!(d < wd)) continue;
-            double nd = -1.0;                            // replace the worst, find the new worst (lexicographic maximum)
-            int ni = 0;
-#pragma unroll
-            for (int t = 0; t < K; ++t) {
-                if (bi[t] == wi) { bd[t] = d; bi[t] = c; }
-                if (bd[t] > nd || (bd[t] == nd && bi[t] > ni)) { nd = bd[t]; ni = bi[t]; }
-            }
-            wd = nd; wi = ni;
-            thr = (float)wd;
-            thr = thr + thr * 1e-5f;                    // inf stays inf
-        }
-    }
-    // in (distance, index) order, as k_knn_ix writes its list: an entry's place is the number of entries before it (the entries are
-    // distinct -- the placeholders by their indices --, so the places are 0 .. K - 1 once each); K is small, once per query
-    if (qi >= nq) return;
-#pragma unroll
-    for (int t = 0; t < K; ++t) {
-        int place = 0;
-#pragma unroll
-        for (int s = 0; s < K; ++s) place += (bd[s] < bd[t] || (bd[s] == bd[t] && bi[s] < bi[t])) ? 1 : 0;
-        if (place < k) out[(long long)qi * k + place] = bi[t] >= 0x7fffffff - K ? -1 : bi[t];
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
 // Downstream reduction of the apply loop on the device: the stacked query output Out_2 [rows = queries,
 // cols = time steps] never leaves the GPU whole. MODE 0: entries above a threshold, `np.where(Out_2 > 0.01)`
 // (process_continuous_days.py:812-813). MODE 1: the local maxima of every row that reach `height`, i.e. the first two steps

@@ -1253,6 +1253,7 @@ __device__ __forceinline__ void gather_sum16(const float* __restrict__ base, lon
 #include "select_kernels.hpp"
 #include "cloud_kernels.hpp"
 #include "optim_kernels.hpp"
+#include "knn_kernels.hpp"
 #include "pointer_kernels.hpp"
 #include "knn_index_kernels.hpp"
 
@@ -2060,6 +2061,15 @@ int model_tables(const ModelTables** out) {
     }
     *out = it->second;
     return GENIE_OK;
+}
+
+// The list length K in {8, 10, 16} a kNN kernel is instantiated for, from k <= K <= KMAX (the caller has checked k <= KMAX): `f` gets
+// it as a std::integral_constant.
+template <int KMAX, class F>
+void knn_with_K(int k, F f) {
+    if (k <= 8) f(std::integral_constant<int, 8>());
+    else if (KMAX == 10 || k <= 10) f(std::integral_constant<int, 10>());
+    else if constexpr (KMAX > 10) f(std::integral_constant<int, 16>());
 }
 }  // namespace
 
@@ -3906,23 +3916,15 @@ int genie_knn(const float* x_context, int n_context, const float* x_query, int n
         return fail(GENIE_ERR_ARG, "genie_knn: bad argument (1 <= k <= 16)");
     if (n_query == 0) return GENIE_OK;
     hipStream_t st = (hipStream_t)stream;
-    if (n_query >= 16384 && k <= 10) {        // a lane per query (k_knn_t): enough queries to fill the device that way
-        const int nbt = (n_query + 255) / 256;
-        if (k <= 8) k_knn_t<8><<<nbt, 256, 0, st>>>(x_context, n_context, x_query, n_query, k, exclude_self, out_idx);
-        else k_knn_t<10><<<nbt, 256, 0, st>>>(x_context, n_context, x_query, n_query, k, exclude_self, out_idx);
-        HIP_TRY(hipGetLastError());
-        return GENIE_OK;
-    }
-    if (n_query <= 64 && n_context >= 4096 && k <= 10) {      // a workgroup of 16 waves per query (k_knn_b)
-        if (k <= 8) k_knn_b<8><<<n_query, 1024, 0, st>>>(x_context, n_context, x_query, n_query, k, exclude_self, out_idx);
-        else k_knn_b<10><<<n_query, 1024, 0, st>>>(x_context, n_context, x_query, n_query, k, exclude_self, out_idx);
-        HIP_TRY(hipGetLastError());
-        return GENIE_OK;
-    }
-    const int nb = (n_query + 3) / 4;
-    if (k <= 8) k_knn<8><<<nb, 256, 0, st>>>(x_context, n_context, x_query, n_query, k, exclude_self, out_idx);
-    else if (k <= 10) k_knn<10><<<nb, 256, 0, st>>>(x_context, n_context, x_query, n_query, k, exclude_self, out_idx);
-    else k_knn<16><<<nb, 256, 0, st>>>(x_context, n_context, x_query, n_query, k, exclude_self, out_idx);
+    const auto launch = [&](auto kernel, int blocks, int threads) {
+        kernel<<<blocks, threads, 0, st>>>(x_context, n_context, x_query, n_query, k, exclude_self, out_idx);
+    };
+    if (n_query >= 16384 && k <= 10)          // a lane per query (k_knn_t): enough queries to fill the device that way
+        knn_with_K<10>(k, [&](auto K) { launch(k_knn_t<K()>, (n_query + 255) / 256, 256); });
+    else if (n_query <= 64 && n_context >= 4096 && k <= 10)      // a workgroup of 16 waves per query (k_knn_b)
+        knn_with_K<10>(k, [&](auto K) { launch(k_knn_b<K()>, n_query, 1024); });
+    else                                       // a wave per query (k_knn)
+        knn_with_K<16>(k, [&](auto K) { launch(k_knn<K()>, (n_query + 3) / 4, 256); });
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }
@@ -4049,10 +4051,9 @@ int genie_knn_indexed(const int32_t* cell_start, const float* records, const gen
     hipStream_t st = (hipStream_t)stream;
     const KixGrid g = kix_grid(plan, n_context);
     const f32x4* rec = (const f32x4*)records;
-    const int nb = (n_query + 255) / 256;
-    if (k <= 8) k_knn_ix<8><<<nb, 256, 0, st>>>(cell_start, rec, g, x_query, n_query, k, exclude_self, out_idx);
-    else if (k <= 10) k_knn_ix<10><<<nb, 256, 0, st>>>(cell_start, rec, g, x_query, n_query, k, exclude_self, out_idx);
-    else k_knn_ix<16><<<nb, 256, 0, st>>>(cell_start, rec, g, x_query, n_query, k, exclude_self, out_idx);
+    knn_with_K<16>(k, [&](auto K) {
+        k_knn_ix<K()><<<(n_query + 255) / 256, 256, 0, st>>>(cell_start, rec, g, x_query, n_query, k, exclude_self, out_idx);
+    });
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }

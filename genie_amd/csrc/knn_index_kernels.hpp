@@ -112,18 +112,14 @@ __global__ __launch_bounds__(256) void k_kix_scatter(const float* __restrict__ x
     if (at < n) rec[at] = f32x4{p0, p1, p2, __int_as_float(i)};
 }
 
-// The search, ONE LANE per query as in k_knn_t (the query sets this serves are large). A query starts in its own cell -- its cell
-// coordinate clamped, clouds do reach outside the grid's box -- and visits shells of growing Chebyshev radius r in cell coordinates:
-// after shell r it has seen every point whose cell lies in the box [cq - r, cq + r] (cut to the grid) on all three axes. It keeps the K
-// best so far exactly as k_knn_t does -- the fp32 pre-filter with the same guard band, the decision on the exact fp64 distance of the
-// fp32 coordinates by the same __dmul_rn / __dadd_rn statements -- with two differences.
+// The search, ONE LANE per query with a KnnWorst list as in k_knn_t (the query sets this serves are large; knn_kernels.hpp has the
+// distance, the order, the list and its fp32 pre-filter). A query starts in its own cell -- its cell coordinate clamped, clouds do reach
+// outside the grid's box -- and visits shells of growing Chebyshev radius r in cell coordinates: after shell r it has seen every point
+// whose cell lies in the box [cq - r, cq + r] (cut to the grid) on all three axes. Two things are this kernel's own.
 //
-// (1) Candidates do not arrive in increasing index order, so every accept is the full lexicographic test (d, index) < (worst d, worst
-//     index); k_knn_t may drop a tie with the worst because there it can only have a larger index. The placeholders (inf, 0x7fffffff - t)
-//     are the lexicographically largest entries of a list, so while one is left it is the worst, any real candidate replaces it, and a
-//     list whose worst is real holds K real entries.
+// (1) Candidates do not arrive in increasing index order, so every accept is the full test: offer<false>.
 //
-// (2) Termination. After shell r the search stops when the list holds K real entries and its worst exact squared distance wd is
+// (2) Termination. After shell r the search stops when the list is full() and its worst exact squared distance wd is
 //     STRICTLY smaller than B, a lower bound of the kernel's own squared distance to every point outside the visited box (strictly: a
 //     point at exactly wd with a smaller index would belong in the table) -- or when the visited box is the whole grid.
 //     A point p outside the box lies beyond one of its faces on some axis a: cell(p_a) >= j = hi_a + 1, or cell(p_a) <= lo_a - 1.
@@ -137,8 +133,8 @@ __global__ __launch_bounds__(256) void k_kix_scatter(const float* __restrict__ x
 //     products, of q - o and of the difference (2^-53 each, relative to a term no larger than face + |q - o|) are covered by
 //     subtracting (face + |q - o|) * 2^-40 once more. So g_a <= |p_a - q_a| in real numbers, and because rounding is monotone also
 //     g_a <= |fl(q_a - p_a)|, the kernel's d_a. On the other axes b the point is at least E_b = the distance of q_b to the grid's
-//     box [o_b, hi_b] away (exact min / max of the floats, again monotone under fl). B is then the kernel's distance statement on
-//     these lower bounds in the same order, fl(fl(fl(l0 l0) + fl(l1 l1)) + fl(l2 l2)): every operation is monotone in non-negative
+//     box [o_b, hi_b] away (exact min / max of the floats, again monotone under fl). B is then knn_dist2's own statement on these
+//     lower bounds, knn_sum3 of their rounded squares in axis order: every operation is monotone in non-negative
 //     arguments, so B <= d(p), and wd < B <= d(p) keeps p out whatever its index. B is the minimum over the (at most six) faces.
 //     A loose bound costs one more shell now and then; nothing here is tight.
 template <int K>
@@ -148,14 +144,8 @@ __global__ __launch_bounds__(256) void k_knn_ix(const int32_t* __restrict__ cell
     if (qi >= nq) return;
     const float f[3] = {xq[(long long)qi * 3 + 0], xq[(long long)qi * 3 + 1], xq[(long long)qi * 3 + 2]};
     const double q0 = (double)f[0], q1 = (double)f[1], q2 = (double)f[2];
-    // the K best so far unsorted, the worst one (largest (distance, index)) tracked, as in k_knn_t
-    double bd[K];
-    int bi[K];
-#pragma unroll
-    for (int t = 0; t < K; ++t) { bd[t] = __builtin_inf(); bi[t] = 0x7fffffff - t; }
-    double wd = __builtin_inf();
-    int wi = 0x7fffffff;
-    float thr = __builtin_inff();                    // fp32 guard of wd
+    KnnWorst<K> best;
+    best.clear();
     int cq[3];
     double qo[3], E2[3];                             // q - o per axis; squared distance of q to the grid's box per axis
 #pragma unroll
@@ -187,23 +177,10 @@ __global__ __launch_bounds__(256) void k_knn_ix(const int32_t* __restrict__ cell
                     for (int i = max(cell_start[row + a0], 0); i < e; ++i) {
                         const f32x4 cv = rec[i];
                         const float e0 = f[0] - cv.x, e1 = f[1] - cv.y, e2 = f[2] - cv.z;
-                        const float d32 = e0 * e0 + e1 * e1 + e2 * e2;
-                        if (!(d32 <= thr)) continue;
+                        if (!best.passes(e0 * e0 + e1 * e1 + e2 * e2)) continue;
                         const int c = __float_as_int(cv.w);
                         if (exclude_self && c == qi) continue;
-                        const double d0 = q0 - (double)cv.x, d1 = q1 - (double)cv.y, d2 = q2 - (double)cv.z;                       // exact
-                        const double d = __dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2));
-                        if (!(d < wd || (d == wd && c < wi))) continue;          // (1): the full lexicographic test
-                        double nd = -1.0;                            // replace the worst, find the new worst (lexicographic maximum)
-                        int ni = 0;
-#pragma unroll
-                        for (int t = 0; t < K; ++t) {
-                            if (bi[t] == wi) { bd[t] = d; bi[t] = c; }
-                            if (bd[t] > nd || (bd[t] == nd && bi[t] > ni)) { nd = bd[t]; ni = bi[t]; }
-                        }
-                        wd = nd; wi = ni;
-                        thr = (float)wd;
-                        thr = thr + thr * 1e-5f;                    // inf stays inf
+                        best.template offer<false>(knn_dist2(q0, q1, q2, cv.x, cv.y, cv.z), c);
                     }
                 }
             }
@@ -213,12 +190,10 @@ __global__ __launch_bounds__(256) void k_knn_ix(const int32_t* __restrict__ cell
         double B = __builtin_inf();
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
-            auto face = [&](double gap) {                // the kernel's distance statement on the lower bounds, in its order
+            auto face = [&](double gap) {                // the distance statement on the lower bounds: gap on axis a, E on the others
                 gap = fmax(gap, 0.0);
                 const double gg = __dmul_rn(gap, gap);
-                const double b = a == 0 ? __dadd_rn(__dadd_rn(gg, E2[1]), E2[2])
-                               : a == 1 ? __dadd_rn(__dadd_rn(E2[0], gg), E2[2]) : __dadd_rn(__dadd_rn(E2[0], E2[1]), gg);
-                B = fmin(B, b);
+                B = fmin(B, knn_sum3(a == 0 ? gg : E2[0], a == 1 ? gg : E2[1], a == 2 ? gg : E2[2]));
             };
             if (hi[a] < g.n[a] - 1) {
                 whole = false;
@@ -232,15 +207,7 @@ __global__ __launch_bounds__(256) void k_knn_ix(const int32_t* __restrict__ cell
             }
         }
         if (whole) break;
-        if (wi < 0x7fffffff - K && wd < B) break;
+        if (best.full() && best.worst_d() < B) break;
     }
-    // in (distance, index) order: an entry's place is the number of entries before it (the entries are distinct, so the places are
-    // 0 .. K - 1 once each); K is small, once per query
-#pragma unroll
-    for (int t = 0; t < K; ++t) {
-        int place = 0;
-#pragma unroll
-        for (int s = 0; s < K; ++s) place += (bd[s] < bd[t] || (bd[s] == bd[t] && bi[s] < bi[t])) ? 1 : 0;
-        if (place < k) out[(long long)qi * k + place] = bi[t] >= 0x7fffffff - K ? -1 : bi[t];
-    }
+    best.write_ranked(out + (long long)qi * k, k);
 }

@@ -155,9 +155,7 @@ __global__ __launch_bounds__(TP_BLOCK) void k_tp_segments(const int32_t* __restr
     }
 }
 
-__device__ __forceinline__ bool tp_less(double d, int id, double od, int oid) { return d < od || (d == od && id < oid); }
-
-constexpr double TP_EMPTY_D = 1.7976931348623157e308;     // (max double, max int): an empty rank; sorts after every candidate
+constexpr double TP_EMPTY_D = 1.7976931348623157e308;     // (max double, max int): an empty rank; after every candidate in knn_before's order
 constexpr int TP_EMPTY_ID = 0x7fffffff;
 
 // One chunk of up to 64 keys (one per lane, `have`: this lane holds one) into the wave's sorted list (lane r: the key of rank r): what
@@ -165,17 +163,17 @@ constexpr int TP_EMPTY_ID = 0x7fffffff;
 __device__ __forceinline__ void tp_wave_insert(double& kd, int& kid, double d, int id, bool have, int k, int lane) {
     const double td = __shfl(kd, k - 1);
     const int tid = __shfl(kid, k - 1);
-    unsigned long long m = __ballot(have && tp_less(d, id, td, tid));
+    unsigned long long m = __ballot(have && knn_before(d, id, td, tid));
     while (m) {                                               // wave-uniform
         const int src = __ffsll((long long)m) - 1;
         m &= m - 1;
         const double cd = __shfl(d, src);
         const int cid = __shfl(id, src);
-        if (!tp_less(cd, cid, __shfl(kd, k - 1), __shfl(kid, k - 1))) continue;   // rank k - 1 has moved past it meanwhile
+        if (!knn_before(cd, cid, __shfl(kd, k - 1), __shfl(kid, k - 1))) continue;   // rank k - 1 has moved past it meanwhile
         const double pd = __shfl_up(kd, 1);
         const int pid = __shfl_up(kid, 1);
-        if (tp_less(cd, cid, kd, kid)) {                      // it ranks before mine: I take my left neighbour's key, or the new one
-            const bool shift = lane > 0 && tp_less(cd, cid, pd, pid);
+        if (knn_before(cd, cid, kd, kid)) {                      // it ranks before mine: I take my left neighbour's key, or the new one
+            const bool shift = lane > 0 && knn_before(cd, cid, pd, pid);
             kd = shift ? pd : cd;
             kid = shift ? pid : cid;
         }

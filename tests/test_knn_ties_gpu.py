@@ -189,6 +189,21 @@ def test_wave_per_query_exclude_self(indexed):
     compare(got, C.exact_knn(xc, xc, 15, exclude_self=True), "lattice(12) exclude_self k=15")
 
 
+def test_wave_per_query_fewer_context_points_than_k():
+    """5 identical context points through the C entry at k = 10 and k = 16: after five rounds the wave-wide minimum is the empty slot,
+    which every lane pops at once; rows `0 1 2 3 4 -1 ...`, nothing of the pre-filled table left."""
+    xc, xq = C.identical(5, 257)
+    dxc, dxq = _t(xc), _t(xq)
+    lib = _lib.load()
+    for k in (10, 16):
+        assert kernel_of(5, 257, k) == "k_knn"
+        got = torch.full((257, k), -7, dtype=torch.int32, device=DEV)
+        _lib.check(lib.genie_knn(engine._ptr(dxc), 5, engine._ptr(dxq), 257, k, 0, engine._ptr(got), engine._stream()))
+        want = C.exact_knn(xc, xq, k)
+        assert want[0].tolist() == [0, 1, 2, 3, 4] + [-1] * (k - 5)
+        compare(got, want, "5 identical context points, k=%d k_knn" % k)
+
+
 # ---- a workgroup per query ----------------------------------------------------------------------------------------------------------
 
 
