@@ -33,6 +33,20 @@ def _f32(t, name, shape=None):
     return t
 
 
+def _cotangent(t, name, shape):
+    """An upstream gradient of a backward entry point: an fp32 GPU tensor of exactly `shape` (made contiguous), or the call is refused.
+    Unlike `_f32` nothing is converted: the forward's outputs are fp32, so another dtype or shape is a caller's mistake."""
+    if not torch.is_tensor(t):
+        raise TypeError("%s must be a torch tensor" % name)
+    if t.dtype != torch.float32:
+        raise TypeError("%s must be float32 (got %s)" % (name, t.dtype))
+    if not t.is_cuda:
+        raise ValueError("%s must live on the GPU (got %s)" % (name, t.device))
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s: expected shape %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    return t.contiguous()
+
+
 KNN_INDEX_MIN_QUERIES = 16384     # query sets from this size on go through a model's `knn_index` (where genie_knn turns to a lane per query)
 
 
@@ -1359,21 +1373,33 @@ class HipPath(object):
 
     def lslc_bwd(self, s_rows, a_edges_ps, dt_partition, tpick, ipick, phase_label, tlatent, eps, d_p, d_s):
         """Backward of the two `lslc_fwd` heads of a training step (genie_lslc_bwd + genie_seg_rows): d_p / d_s [n, 15] (None = zero) ->
-        (d_s_rows [P, 30], dict parameter name -> gradient). The edge sort by product node is index plumbing (torch.sort, stable)."""
+        (d_s_rows [P, 30], dict parameter name -> gradient). The edge sort by product node is index plumbing (torch.sort, stable).
+        Refused before anything is launched: no pick, a cotangent that is not an fp32 GPU tensor [n, 15], tables / ipick that are not int32."""
+        self._need_assoc()
         s_rows = _f32(s_rows, "s_rows", (self.n_prod, 30))
         tpick = _f32(tpick, "tpick").reshape(-1)
         n = int(tpick.numel())
         phase_label = _f32(phase_label, "phase_label").reshape(-1)
         tlatent = _f32(tlatent, "tlatent")
+        # everything is refused here, before the first launch: the kernels read these buffers through raw pointers of fixed types
+        if n == 0:
+            raise ValueError("lslc_bwd: needs at least one pick")
+        a_edges_ps = tuple(a_edges_ps)
+        if (len(a_edges_ps) != 2 or any(not torch.is_tensor(a) or a.dtype != torch.int32 or not a.is_cuda for a in a_edges_ps)
+                or not torch.is_tensor(ipick) or ipick.dtype != torch.int32 or not ipick.is_cuda or ipick.numel() != n
+                or phase_label.numel() != n or tlatent.dim() != 2 or tlatent.shape[0] != self.n_prod or tlatent.shape[1] < 2):
+            raise ValueError("lslc_bwd: a_edges_ps (two tables) / ipick must be int32 GPU tensors, one ipick / phase_label per pick, "
+                             "tlatent [P, >= 2]")
+        d_p, d_s = (None if d is None else _cotangent(d, "lslc_bwd: d_p / d_s", (n, 15)) for d in (d_p, d_s))
+        a_edges_ps, ipick = tuple(a.contiguous() for a in a_edges_ps), ipick.contiguous()
         t0, dt, dtp, l_dt = time_partition(dt_partition)
         dev = self.device
         ds = torch.zeros((self.n_prod, 30), dtype=torch.float32, device=dev)
         blob = torch.zeros(self._blob.numel(), dtype=torch.float32, device=dev)
         part = torch.empty(int(self.lib.genie_lslc_bwd_part_floats(n)), dtype=torch.float32, device=dev)
         for head, d_out in ((0, d_p), (1, d_s)):
-            if d_out is None or n == 0:
+            if d_out is None:
                 continue
-            d_out = _f32(d_out, "d_out", (n, 15))
             a_edges = a_edges_ps[head]
             erow = torch.empty((n * 10, 32), dtype=torch.float32, device=dev)
             etgt = torch.empty(n * 10, dtype=torch.int32, device=dev)
@@ -1439,7 +1465,7 @@ class HipPath(object):
         d_arrival_p [n, 15], d_arrival_s [n, 15], dict parameter name -> gradient)."""
         data, segs, ctx, flag, save, eps = state
         n_src, n, n_sta, n_useg = int(data[0].numel()), int(data[5].numel()), int(data[2].shape[1]), int(segs[1].numel())
-        d_out = _f32(d_out, "d_out", (n_src, n, 2))
+        d_out = _cotangent(d_out, "arrivals_bwd: d_out", (n_src, n, 2))
         dev = self.device
         scratch = torch.empty(int(self.lib.genie_arrivals_bwd_scratch_floats(n_src, n, n_useg)), dtype=torch.float32, device=dev)
         blob = torch.zeros(self._blob.numel(), dtype=torch.float32, device=dev)
