@@ -136,6 +136,10 @@ SYMBOLS = [
     ("genie_stack_windows", _c.c_int, [_P, _P, _c.c_int, _c.c_int64, _c.c_int, _c.c_float, _P, _c.c_int64, _c.c_int64, _c.c_int64, _P]),
     ("genie_stack_windows_legs", _c.c_int, [_P, _c.c_int, _P, _c.c_int, _c.c_int64, _c.c_int, _c.c_float, _P, _c.c_int64, _c.c_int64, _c.c_int64,
                                             _P]),
+    ("genie_stack_windows_ring", _c.c_int, [_P, _c.c_int, _P, _c.c_int, _c.c_int64, _c.c_int, _c.c_float, _P, _c.c_int64, _c.c_int64, _c.c_int64,
+                                            _P]),
+    ("genie_ring_close", _c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P]),
+    ("genie_picks_merge", _c.c_int, [_P, _P, _P, _P, _c.c_int64, _P, _P, _P, _P, _c.c_int64, _P, _P, _P, _P, _P]),
     ("genie_refine_select_scratch_bytes", _c.c_size_t, []),
     ("genie_refine_select", _c.c_int, [_P, _c.c_int, _c.c_int64, _c.c_int, _P, _c.c_float, _P, _P, _P]),
     ("genie_refine_cloud", _c.c_int, [_c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64] + [_c.c_double] * 9 + [_P, _P, _P, _P]),

@@ -19,6 +19,8 @@ travel-time table stay resident on the device and every window's `Slice/Mask` is
 (`extract_input_from_data`, `process_utils.py:460-642`), so a window costs no host->device copy at all. `apply_windows_legs` runs
 the same loop over several source grids into one `Out_2`. Both are adapters: their arguments become a `_day_plan` (schedule, pick
 ranges, this rank's windows, column table: host arithmetic, once) and a list of lanes, and `_run_day` is the one loop over them.
+`OnlineDay` runs the same per-window body (`_WindowBody`) for a live feed: picks arrive in chunks (`PickStore`), windows run as they
+become ready, and the columns of `Out_2` are returned as they close.
 """
 import collections
 import threading
@@ -422,8 +424,7 @@ def _day_plan(t_sorted, max_t, day_len, t_win, step_size, min_required_picks, ts
     tsteps_abs, times, offsets, n_overlap = _day_schedule(t_sorted.reshape(-1, 1), max_t, day_len, t_win, step_size, min_required_picks,
                                                           tsteps_abs, times)
     drop_last = step_size == "half"
-    lo = np.searchsorted(t_sorted, times - 2.0 * kernel_sig_t, side="right")                      # strict >, process_utils.py:476
-    hi = np.searchsorted(t_sorted, times + max_t + 2.0 * kernel_sig_t, side="left")               # strict <
+    lo, hi = _embed_ranges(t_sorted, times, max_t, kernel_sig_t)
     nonempty = hi > lo                                                                             # process_continuous_days.py:792-793
     times, lo, hi = times[nonempty], lo[nonempty], hi[nonempty]
     asc = is_ascending(tsteps_abs)
@@ -442,10 +443,22 @@ def _day_plan(t_sorted, max_t, day_len, t_win, step_size, min_required_picks, ts
     h_cols = window_cols_table(tsteps_abs, times, offsets, drop_last, asc)
     if bands is not None:
         h_cols = np.where(h_cols >= 0, h_cols - bands["band"][split.rank][0], -1).astype(np.int32)
-    divisor = n_overlap * n_grids
-    scale = float(np.float32(1.0) / np.float32(divisor))       # `tensor / host scalar` in torch: times the fp32 reciprocal
+    divisor, scale = _stack_scale(n_overlap, n_grids)
     return _DayPlan(tsteps_abs, offsets, times, lo, hi, all_times, drop_last, h_cols, divisor, scale, info, max_t, kernel_sig_t, split, bands,
                     width)
+
+
+def _embed_ranges(t_sorted, times, max_t, kernel_sig_t):
+    """(lo, hi): per window start of `times` the range [lo, hi) of the time-sorted picks `t_sorted` its embedding reads."""
+    lo = np.searchsorted(t_sorted, times - 2.0 * kernel_sig_t, side="right")                      # strict >, process_utils.py:476
+    hi = np.searchsorted(t_sorted, times + max_t + 2.0 * kernel_sig_t, side="left")               # strict <
+    return lo, hi
+
+
+def _stack_scale(n_overlap, n_grids):
+    """(divisor, scale) of a day's stacking: `n_overlap * n_grids` and its fp32 reciprocal."""
+    divisor = n_overlap * n_grids
+    return divisor, float(np.float32(1.0) / np.float32(divisor))       # `tensor / host scalar` in torch: times the fp32 reciprocal
 
 
 def _fused_add(plan, Out_2):
@@ -481,55 +494,79 @@ def _torch_add(plan, Out_2):
     return add
 
 
+class _WindowBody(object):
+    """The per-window body of the day loops, shared by `_run_day` (a whole day, planned up front) and `OnlineDay.feed` (the windows that
+    became ready): `lanes`: one per source grid, each with `net`, `x_grid_cart` and `trv` (a `GridLeg`), all with the same `window_batch`.
+    `window` makes every lane, in lane order, embed one window and run its P-sized part (`push_window`), or the whole window with a tail
+    of its own when `window_batch` is 1 (`forward_fixed_source_pipelined`: a source-node-sharded model among them), and returns the number
+    of windows pending; `flush` runs every lane's tail on a side stream of its own (`flush_windows`) and hands `add(xs)` the lanes'
+    read-outs `xs` of the pending windows on the one stacker stream: behind each tail's `done` event, and every flush behind the one
+    before it (overlapping columns: a fixed summation order). `join` puts the main stream behind all of it; nothing here waits for the
+    host. Construct and use it under `torch.no_grad()` with `xq`'s device current."""
+
+    def __init__(self, lanes, xq, offsets, max_t, kernel_sig_t, dt_embed):
+        dev = xq.device
+        self.lanes, self.xq, self.max_t, self.kernel_sig_t, self.dt_embed = lanes, xq, max_t, kernel_sig_t, dt_embed
+        self.tq = torch.from_numpy(offsets.reshape(-1, 1)).float().to(dev)
+        self.batch = lanes[0].net.window_batch
+        self.main = torch.cuda.current_stream(dev)
+        self.stacker = torch.cuda.Stream(device=dev)      # every flush's stack runs here, so each one is behind the one before it
+        self.stacker.wait_stream(self.main)               # Out_2's zeros and the tables
+        self.xs = None
+
+    def _on_stacker(self, x, done):                       # a lane's read-out, produced on its side stream, made known to the stacker
+        self.stacker.wait_event(done)
+        x.record_stream(self.stacker)
+        return x
+
+    def window(self, picks, t0, a, b):
+        if self.batch == 1:
+            self.xs = []
+        for lane in self.lanes:
+            Slice, Mask = lane.net.embed_window(picks.t[a:b], picks.sta[a:b], picks.phase[a:b], float(t0), self.max_t, self.kernel_sig_t,
+                                                self.dt_embed, lane.trv, presplit=True)    # the call below is the only consumer of (Slice, Mask)
+            if self.batch == 1:                       # one tail per window: the batch of one (a view, no launch)
+                _, x, done = lane.net.forward_fixed_source_pipelined(Slice, Mask, None, None, None, None, lane.x_grid_cart, self.xq, self.tq)
+                self.xs.append(self._on_stacker(x.unsqueeze(0), done))
+                pending = 1
+            else:
+                pending = lane.net.push_window(Slice, Mask)
+        return pending
+
+    def flush(self, add):
+        xs = self.xs
+        if self.batch > 1:
+            # every lane's tail + read-outs of the pushed windows in one set of launches, each on a side stream of its own
+            xs = [self._on_stacker(*lane.net.flush_windows(lane.x_grid_cart, self.xq, self.tq)[1:]) for lane in self.lanes]
+        self.xs = None
+        with torch.cuda.stream(self.stacker):
+            add(xs)
+
+    def join(self):
+        for lane in self.lanes:
+            lane.net._hip.wait_tails()
+        self.main.wait_stream(self.stacker)
+
+
 def _run_day(plan, lanes, picks, xq, Out_2, add, dt_embed, merge_timeout):
-    """The day's loop over the windows of `plan`. `lanes`: one per source grid, each with `net`, `x_grid_cart` and `trv` (a `GridLeg`), all
-    with the same `window_batch`; `picks`: the time-sorted picks on the device (`t_host`, `t`, `sta`, `phase`: a `ResidentPicks`). Per
-    window, in window order, every lane in lane order embeds the window and runs its P-sized part (`push_window`), or the whole window
-    with a tail of its own when `window_batch` is 1 (`forward_fixed_source_pipelined`: a source-node-sharded model among them). When
-    `window_batch` windows are pending, or at the last one, every lane's tail runs on a side stream of its own (`flush_windows`) and
-    `add(xs, first, n)` puts the lanes' read-outs `xs` of windows first .. first + n - 1 into `Out_2`, on the one stacker stream: behind
-    each tail's `done` event, and every flush behind the one before it (overlapping columns: a fixed summation order). Nothing waits for
+    """The day's loop over the windows of `plan`: per window, in window order, the body of `_WindowBody` on `picks` (the time-sorted picks
+    on the device: `t_host`, `t`, `sta`, `phase`: a `ResidentPicks`); when `window_batch` windows are pending, or at the last one, the
+    flush, whose `add(xs, first, n)` puts the lanes' read-outs `xs` of windows first .. first + n - 1 into `Out_2`. Nothing waits for
     the host until the end: one synchronisation per day, then the verdicts of every lane and, in the group form of the plan's rank
     split, the merge. Returns (Out_2, times used[, info])."""
     dev = Out_2.device
     times = plan.times
     with torch.no_grad(), torch.cuda.device(dev):
-        tq = torch.from_numpy(plan.offsets.reshape(-1, 1)).float().to(dev)
-        batch = lanes[0].net.window_batch
-        main = torch.cuda.current_stream(dev)
-        stacker = torch.cuda.Stream(device=dev)      # every flush's stack runs here, so each one is behind the one before it
-        stacker.wait_stream(main)                    # Out_2's zeros and the tables
-
-        def on_stacker(x, done):                     # a lane's read-out, produced on its side stream, made known to the stacker
-            stacker.wait_event(done)
-            x.record_stream(stacker)
-            return x
-
+        body = _WindowBody(lanes, xq, plan.offsets, plan.max_t, plan.kernel_sig_t, dt_embed)
         first = 0
         for w, t0 in enumerate(times):
-            a, b = int(plan.lo[w]), int(plan.hi[w])
-            if batch == 1:
-                xs = []
-            for lane in lanes:
-                Slice, Mask = lane.net.embed_window(picks.t[a:b], picks.sta[a:b], picks.phase[a:b], float(t0), plan.max_t, plan.kernel_sig_t,
-                                                    dt_embed, lane.trv, presplit=True)    # the call below is the only consumer of (Slice, Mask)
-                if batch == 1:                        # one tail per window: the batch of one (a view, no launch)
-                    _, x, done = lane.net.forward_fixed_source_pipelined(Slice, Mask, None, None, None, None, lane.x_grid_cart, xq, tq)
-                    xs.append(on_stacker(x.unsqueeze(0), done))
-                else:
-                    pending = lane.net.push_window(Slice, Mask)
-            if batch > 1:
-                if pending != batch and w != len(times) - 1:
-                    continue
-                # every lane's tail + read-outs of the pushed windows in one set of launches, each on a side stream of its own
-                xs = [on_stacker(*lane.net.flush_windows(lane.x_grid_cart, xq, tq)[1:]) for lane in lanes]
-            with torch.cuda.stream(stacker):
-                add(xs, first, w + 1 - first)
+            pending = body.window(picks, t0, int(plan.lo[w]), int(plan.hi[w]))
+            if pending != body.batch and w != len(times) - 1:
+                continue
+            body.flush(lambda xs: add(xs, first, w + 1 - first))
             first = w + 1
-        for lane in lanes:
-            lane.net._hip.wait_tails()
-        main.wait_stream(stacker)
-    main.synchronize()                                # the verdicts of the day's last windows: one wait per day
+        body.join()
+    body.main.synchronize()                           # the verdicts of the day's last windows: one wait per day
     for lane in lanes:
         _check_verdicts(lane.net)
     split = plan.split
@@ -653,6 +690,126 @@ class ResidentPicks(object):
     def meta(self, index):
         """`lp_meta` rows (host float64 [m, 5]) of a `pick_inputs` index."""
         return self.P[index.cpu().numpy()]
+
+
+def merge_ranks(t_a, t_b):
+    """(pos_a, pos_b): where the elements of two ascending runs land in their stable merge with `t_a` first among equal times -- element
+    i of `t_a` moves up by the number of `t_b` entries strictly earlier, element j of `t_b` lands after every `t_a` entry <= it. The rule
+    of genie_picks_merge, on numpy arrays or CPU tensors."""
+    if torch.is_tensor(t_a):
+        return (torch.arange(t_a.shape[0]) + torch.searchsorted(t_b, t_a, right=False),
+                torch.arange(t_b.shape[0]) + torch.searchsorted(t_a, t_b, right=True))
+    return np.arange(len(t_a)) + np.searchsorted(t_b, t_a, side="left"), np.arange(len(t_b)) + np.searchsorted(t_a, t_b, side="right")
+
+
+class PickStore(ResidentPicks):
+    """A `ResidentPicks` that grows: the picks of a live feed, time-sorted on one device, with the same views (`t`, `sta`, `phase`,
+    `phase_f`, `index`, `t_host`) and methods (`embed_range`, `embed_args`, `pick_inputs`, `meta`), plus `append(P_chunk)`, `trim` and
+    `frozen_t`. After any sequence of appends the stored order is the one of `ResidentPicks(np.concatenate(chunks), ...)`: a stable sort by
+    time, ties in feed order; `index` counts rows of that concatenation (every row fed, kept or not).
+
+    `append` stable-sorts the chunk on the host (chunks are small) and uploads it. A chunk that starts no earlier than the resident tail
+    is copied onto the end; any other is merged by rank into a second buffer (genie_picks_merge on a GPU, one launch for the four
+    arrays; `merge_ranks` in torch on a CPU store, where the tests pin the order). Capacity doubles on demand (allocate, copy, swap),
+    so THE VIEWS ARE VALID UNTIL THE NEXT `append` ONLY: take them again after it. `trim(t_before)` forgets every pick with
+    `t <= t_before` by moving an offset; `embed_range` and all views count from it, and once it passes half the capacity the next append
+    compacts. The host keeps `t_host` (the binary searches run on it) and the fed rows of the live picks (`meta`) in step.
+    `frozen_t`: `append` refuses a pick of the model's stations with `t < frozen_t` -- a window that has already run would have read
+    it -- with a ValueError that names both and leaves the store as it was; with `late="drop"` such picks are left out (they still count
+    in `index`) and `append` returns how many. `phase_f` is `phase` as float64: phase labels are whole numbers (0 = P, 1 = S)."""
+
+    def __init__(self, ind_use, n_sta_all, device, use_phase_types=True, capacity=4096):
+        ind_use = np.asarray(ind_use).astype(np.int64)
+        self._perm = -np.ones(int(n_sta_all), dtype=np.int64)
+        self._perm[ind_use] = np.arange(len(ind_use))
+        self.device = torch.device(device)
+        self.n_sta = int(len(ind_use))
+        self.use_phase_types = bool(use_phase_types)
+        self.frozen_t = -np.inf
+        self.n_fed = 0                          # rows fed so far: the next chunk's first `index`
+        self._base = self._n = 0                # the live picks are [base, n) of the buffers
+        self._dev = self._device_buffers(max(1, int(capacity)))
+        self._host = self._host_buffers(max(1, int(capacity)))
+
+    def _device_buffers(self, cap):
+        return tuple(torch.empty(cap, dtype=dtype, device=self.device) for _, dtype in engine.PICK_FIELDS)
+
+    @staticmethod
+    def _host_buffers(cap):
+        return np.empty(cap, dtype=np.float64), np.empty((cap, 5), dtype=np.float64), np.empty(cap, dtype=np.int64)
+
+    capacity = property(lambda self: int(self._host[0].shape[0]))
+    t = property(lambda self: self._dev[0][self._base:self._n])
+    sta = property(lambda self: self._dev[1][self._base:self._n])
+    phase = property(lambda self: self._dev[2][self._base:self._n])
+    index = property(lambda self: self._dev[3][self._base:self._n])
+    phase_f = property(lambda self: self.phase.double())
+    t_host = property(lambda self: self._host[0][self._base:self._n])
+    index_host = property(lambda self: self._host[2][self._base:self._n])
+
+    def meta(self, index):
+        """`lp_meta` rows (host float64 [m, 5]) of a `pick_inputs` index, among the live picks (a trimmed pick raises KeyError)."""
+        index = np.asarray(index.cpu() if torch.is_tensor(index) else index, dtype=np.int64)
+        live = self.index_host
+        order = np.argsort(live, kind="stable")
+        at = np.clip(np.searchsorted(live[order], index), 0, max(len(live) - 1, 0))
+        if index.size and (len(live) == 0 or not np.array_equal(live[order[at]], index)):
+            raise KeyError("PickStore.meta: a pick of the index has been trimmed")
+        return self._host[1][self._base:self._n][order[at]] if index.size else np.zeros((0, 5))
+
+    def trim(self, t_before):
+        """Forget every pick with `t <= t_before` (an offset moves; the memory is reclaimed by a later append). Returns the live count."""
+        self._base += int(np.searchsorted(self.t_host, float(t_before), side="right"))
+        return len(self)
+
+    def append(self, P_chunk, late="raise"):
+        """Add the rows `P_chunk` [m, 5] float64 (t, ABSOLUTE station index, amp, prob, phase), in the caller's order. Returns the
+        number of picks dropped as late (always 0 with `late="raise"`, which raises ValueError instead and changes nothing)."""
+        if late not in ("raise", "drop"):
+            raise ValueError('PickStore.append: late must be "raise" or "drop"')
+        P = np.asarray(P_chunk, dtype=np.float64).reshape(-1, 5)
+        sta = self._perm[P[:, 1].astype(np.int64)]
+        keep = np.nonzero(sta > -1)[0]
+        too_late = P[keep, 0] < self.frozen_t
+        dropped = int(too_late.sum())
+        if dropped and late == "raise":
+            raise ValueError("PickStore.append: a pick at t = %r is earlier than frozen_t = %r (a window that has run would have read it)"
+                             % (float(P[keep[too_late], 0].min()), float(self.frozen_t)))
+        keep = keep[~too_late]
+        keep = keep[np.argsort(P[keep, 0], kind="stable")]
+        m, live = len(keep), len(self)
+        ph = P[keep, 4] if self.use_phase_types else np.zeros(m)                  # process_continuous_days.py:562-563
+        h_chunk = (np.ascontiguousarray(P[keep, 0]), P[keep], self.n_fed + keep)
+        self.n_fed += P.shape[0]
+        if m == 0:
+            return dropped
+        d_chunk = tuple(torch.from_numpy(np.ascontiguousarray(x)).to(self.device) for x in
+                        (h_chunk[0], sta[keep].astype(np.int32), ph.astype(np.int32), h_chunk[2]))
+        in_order = live == 0 or h_chunk[0][0] >= self._host[0][self._n - 1]
+        if in_order and self._n + m <= self.capacity and 2 * self._base <= self.capacity:
+            lo, hi = self._n, self._n + m                                          # onto the end, in place
+            for buf, x in zip(self._dev + self._host, d_chunk + h_chunk):
+                buf[lo:hi] = x
+            self._n = hi
+            return dropped
+        cap = self.capacity                                                        # a second buffer: grown, compacted, or the merge's target
+        while cap < live + m:
+            cap *= 2
+        dev, host = self._device_buffers(cap), self._host_buffers(cap)
+        pos_a, pos_b = merge_ranks(self.t_host, h_chunk[0])
+        for new, old, x in zip(host, self._host, h_chunk):
+            new[pos_a], new[pos_b] = old[self._base:self._n], x
+        if in_order:
+            for new, old, x in zip(dev, self._dev, d_chunk):
+                new[:live], new[live:live + m] = old[self._base:self._n], x
+        elif self.device.type == "cuda":
+            engine.picks_merge((self.t, self.sta, self.phase, self.index), d_chunk, tuple(x[:live + m] for x in dev))
+        else:
+            t_pos_a, t_pos_b = merge_ranks(self.t, d_chunk[0])
+            for new, old, x in zip(dev, self._dev, d_chunk):
+                new[t_pos_a], new[t_pos_b] = old[self._base:self._n], x
+        self._dev, self._host, self._base, self._n = dev, host, 0, live + m
+        return dropped
 
 
 class GridLeg(object):
@@ -919,6 +1076,219 @@ def apply_windows_legs(legs, picks, x_query_cart, locs_cart, max_t, tsteps_abs=N
     xq = torch.as_tensor(x_query_cart).float().to(dev)
     Out_2 = torch.zeros((xq.shape[0], plan.width), dtype=torch.float32, device=dev)
     return _run_day(plan, legs, picks, xq, Out_2, _fused_add(plan, Out_2), _dt_embed(kernel_sig_t, dt_embed), merge_timeout)
+
+
+# ---- the online day loop: picks fed as they arrive, columns of Out_2 returned as they close ------------------------
+
+def online_read_bounds(times, max_t, kernel_sig_t, t_win):
+    """What the windows starting at `times` read of the pick axis, on the host: (first, embed_end, count_end), float64 arrays.
+    * the embedding reads `t0 - 2 sigma < t < embed_end = t0 + max_t + 2 sigma`, both strict (`_embed_ranges`);
+    * the `min_required_picks` count reads `t0 - t_win <= t <= count_end = t0 + max_t + t_win`, both inclusive, in the arithmetic of
+      `windows_with_enough_picks` (centre `t0 + max_t / 2`, radius `t_win + max_t / 2`);
+    * `first`: no pick with `t < first` is read at all -- the earlier of `t0 - 2 sigma` and the count's lower end."""
+    times = np.asarray(times, dtype=np.float64)
+    c, r = times + max_t / 2.0, t_win + max_t / 2.0
+    return np.minimum(times - 2.0 * kernel_sig_t, c - r), times + max_t + 2.0 * kernel_sig_t, c + r
+
+
+def online_ready(times, t_now, max_t, kernel_sig_t, t_win):
+    """Boolean [n]: the windows whose every read pick has been fed, under the caller's promise that every pick with `t < t_now` has:
+    `embed_end <= t_now` (the embedding's bound is strict, so a bound equal to `t_now` is ready) and `count_end < t_now` (the count's is
+    inclusive: a pick exactly at `t_now` may still be missing). The later of the two decides."""
+    _, embed_end, count_end = online_read_bounds(times, max_t, kernel_sig_t, t_win)
+    return (embed_end <= t_now) & (count_end < t_now)
+
+
+def online_frontiers(cols, n_cols):
+    """int64 [n + 1]: entry k = the first column that a window k, k + 1, ... of the `cols` table (`window_cols_table`, -1 = no column)
+    lists, `n_cols` past the last one: once windows 0 .. k - 1 have run, the columns below entry k are closed. Never decreasing in k."""
+    cols = np.asarray(cols).astype(np.int64)
+    first = np.where(cols >= 0, cols, int(n_cols)).min(axis=1, initial=int(n_cols))
+    return np.minimum.accumulate(np.append(first, int(n_cols))[::-1])[::-1]
+
+
+def online_batch_spans(cols, n_cols, tail_batch):
+    """int64 [n]: entry k = the columns that are open at once when a batch of the loop starts at window k -- from the frontier of k
+    (`online_frontiers`: everything below is closed before the batch starts) to the last column listed by any window up to the batch's
+    end, window min(k + tail_batch, n) - 1. A batch never spans more than `tail_batch` windows of the schedule, skipped ones included."""
+    cols = np.asarray(cols).astype(np.int64)
+    n = cols.shape[0]
+    last = np.maximum.accumulate(cols.max(axis=1, initial=-1)) if n else np.zeros(0, dtype=np.int64)
+    end = np.minimum(np.arange(n) + int(tail_batch), n) - 1
+    return np.maximum(last[end] - online_frontiers(cols, n_cols)[:n] + 1, 0)
+
+
+def online_batches(start, end, tail_batch):
+    """[(a, b)]: the windows [start, end) of the schedule that one `feed` runs, cut into its batches [a, b) of at most `tail_batch`
+    windows, skipped ones included; after each batch the columns below `online_frontiers(...)[b]` close."""
+    return [(a, min(a + int(tail_batch), end)) for a in range(start, end, int(tail_batch))]
+
+
+def online_ring_min(cols, n_cols, tail_batch):
+    """The smallest ring (in columns) in which no two open columns of `OnlineDay` ever share a slot, whichever way the windows become
+    ready: the widest `online_batch_spans` entry (at least 1)."""
+    return int(max(1, online_batch_spans(cols, n_cols, tail_batch).max(initial=1)))
+
+
+class OnlineDay(object):
+    """The day's apply loop fed as the picks arrive: `feed(P_chunk, t_now)` runs every window that has become ready and returns the
+    columns of `Out_2` that closed, `(first_col, block [Q, n] float32 on the device)` with n possibly 0 -- the shape
+    `postproc.band_peaks` takes a band in; `finish()` does the same for everything left (`feed(None, inf)`); `closed` counts the
+    columns returned so far. Memory is bounded: the picks live in a `PickStore` trimmed behind the windows, `Out_2` exists only as a
+    ring of `ring_cols` open columns.
+
+    `net`: the model (adjacencies set), or its `GridLeg`; `geom`: anything with `x_grid` and `x_query` (Cartesian); `trv_times`
+    [G, S, 2] (or [N, 2] rows with `pairs`, as `GridLeg` takes them). `tsteps_abs`: the column axis, ascending, REQUIRED -- the
+    offline default depends on the day's last pick. `times`: the candidate window starts, ascending; default: `_day_schedule`'s
+    windows for picks spanning the axis, i.e. from `tsteps_abs[0] + t_win / 2` in steps of `step_size` while the window's centre lies on
+    the axis. Per candidate, WHEN IT BECOMES READY, `windows_with_enough_picks(min_required_picks)` and the empty-range rule decide
+    whether it runs; a window they drop counts as run. (Offline, an explicit `times=` is taken as filtered already: the two agree
+    whenever every candidate passes the count, which `min_required_picks=1` with `t_win >= 2 kernel_sig_t` guarantees for every window
+    with a pick to embed.) `P_chunk` [m, 5]: rows as `apply_windows_device` takes them -- station index in the model's order, or
+    absolute with `ind_use` / `n_sta_all` as `ResidentPicks` takes them -- in any order, or None.
+
+    The caller's promise: when `feed(P_chunk, t_now)` is called, every pick with `t < t_now` has been fed (picks at or after `t_now` may
+    have been, too); `t_now` never decreases (ValueError). A window is ready when nothing it reads can still arrive (`online_ready`).
+    `feed` runs the ready windows in ascending order through the body of the offline loop (`_WindowBody`: embedding, `push_window` /
+    `flush_windows` in batches of at most `tail_batch`, the stacker stream), stacking into the ring (genie_stack_windows_ring); after
+    each batch the columns no unrun window lists (`online_frontiers`) leave the ring (genie_ring_close). Then the store's `frozen_t`
+    moves to the first time the next unrun window reads and the store is trimmed to it: a later pick older than that raises ValueError
+    in `feed` (nothing changes; feed on). One synchronisation per `feed`, then the model's verdicts (`_check_verdicts`).
+    `ring_cols`: default `online_ring_min` of the schedule, the least that can never alias; a smaller value raises ValueError.
+
+    Equality contract: with the same `tsteps_abs`, `times` and options the blocks, concatenated, are the `Out_2` of
+    `apply_windows_device(..., stack_on_device=True)` BIT FOR BIT, for `tail_batch` 1 and above 1 alike and however the picks are cut
+    into chunks: a column's sum is one fp32 running sum over its windows in ascending order in both loops, and a window's read-out does
+    not depend on how windows are grouped into batched tails (tests/test_hip_parity.py pins every window of a batched tail, batches of
+    1, 3, 8 and 16, bit-equal to the plain forward). Not built (NotImplementedError): a source-node-sharded model, `window_parallel`,
+    `merge="columns"`, more than one leg. Online detection on the closed blocks is the next step."""
+
+    def __init__(self, net, geom, trv_times, tsteps_abs, times=None, t_win=6.0, step_size="half", min_required_picks=1, n_grids=1.0,
+                 kernel_sig_t=synthetic.KERNEL_SIG_T, dt_embed=None, max_t=None, tail_batch=16, pairs=None, ring_cols=None, ind_use=None,
+                 n_sta_all=None, window_parallel=None, merge="dense"):
+        legs = list(net) if isinstance(net, (list, tuple)) else [net]
+        if len(legs) != 1:
+            raise NotImplementedError("OnlineDay over %d grid legs: the online loop runs one leg" % len(legs))
+        model = legs[0].net if isinstance(legs[0], GridLeg) else legs[0]
+        if getattr(model, "is_sharded", False):
+            raise NotImplementedError("OnlineDay on a source-node-sharded model: batched tails do not run on shards; use an unsharded model")
+        if window_parallel is not None and window_parallel is not False:
+            raise NotImplementedError("OnlineDay with window_parallel: the online loop runs on one GPU")
+        if merge != "dense":
+            raise NotImplementedError('OnlineDay with merge="%s": the online loop returns dense blocks of closed columns' % (merge,))
+        if tsteps_abs is None or not is_ascending(tsteps_abs) or len(tsteps_abs) == 0:
+            raise ValueError("OnlineDay: tsteps_abs is required and must ascend (the offline default needs the day's last pick)")
+        tsteps_abs = np.asarray(tsteps_abs, dtype=np.float64)
+        self.max_t = float(max_t if max_t is not None else np.ceil(np.asarray(trv_times).max() + 1.0))
+        self.t_win, self.kernel_sig_t, self.min_required_picks = float(t_win), float(kernel_sig_t), min_required_picks
+        # `window_schedule` for stand-in picks at both ends of the axis: the offsets, the overlap and the default window starts
+        ends = [tsteps_abs[0] + t_win / 2.0 + self.max_t, tsteps_abs[-1] - t_win / 2.0]
+        dt_win = window_schedule(ends, self.max_t, np.inf, t_win, 9, step_size)[4]
+        tsteps, self.offsets, _, n_overlap, _ = window_schedule([ends[0], ends[1] + dt_win / 2.0], self.max_t, np.inf, t_win, 9, step_size)
+        self.tsteps_abs = tsteps_abs
+        self.times = np.asarray(tsteps if times is None else times, dtype=np.float64).reshape(-1)
+        if not is_ascending(self.times):
+            raise ValueError("OnlineDay: times must ascend (windows run in the order in which they become ready)")
+        self.h_cols = window_cols_table(tsteps_abs, self.times, self.offsets, step_size == "half", True)
+        self.frontiers = online_frontiers(self.h_cols, len(tsteps_abs))
+        self.tail_batch = int(tail_batch)
+        if not 1 <= self.tail_batch <= engine.HipPath.MAX_BATCH:
+            raise ValueError("OnlineDay: tail_batch must be in [1, %d]" % engine.HipPath.MAX_BATCH)
+        self.ring_min = online_ring_min(self.h_cols, len(tsteps_abs), self.tail_batch)
+        self.ring_cols = int(self.ring_min if ring_cols is None else ring_cols)
+        if self.ring_cols < self.ring_min:
+            raise ValueError("OnlineDay: ring_cols = %d is below the minimum of this schedule, %d columns (online_ring_min)"
+                             % (self.ring_cols, self.ring_min))
+        _, self.scale = _stack_scale(n_overlap, n_grids)
+        self.lane = legs[0] if isinstance(legs[0], GridLeg) else GridLeg(model, geom.x_grid, trv_times, pairs=pairs)
+        dev = self.lane.device
+        model.window_batch = self.tail_batch
+        n_sta = self.lane.n_sta
+        self.picks = PickStore(np.arange(n_sta) if ind_use is None else ind_use, n_sta if n_sta_all is None else n_sta_all, dev,
+                               use_phase_types=getattr(model, "use_phase_types", True))
+        self.dt_embed = _dt_embed(kernel_sig_t, dt_embed)
+        self.t_now = -np.inf
+        self.n_run = 0                            # candidate windows run so far (dropped ones included): the next one's index
+        self.closed = 0                           # columns returned so far
+        self.last_col = -1                        # the last column any window has fed
+        self.times_used = []                      # the starts of the windows that ran
+        with torch.no_grad(), torch.cuda.device(dev):
+            self.ring = torch.zeros((np.asarray(geom.x_query).shape[0], self.ring_cols), dtype=torch.float32, device=dev)
+            self.d_cols = torch.from_numpy(self.h_cols).to(dev)
+            xq = torch.as_tensor(geom.x_query).float().to(dev)
+            self.body = _WindowBody([self.lane], xq, self.offsets, self.max_t, self.kernel_sig_t, self.dt_embed)
+
+    def _close(self, blocks, upto):
+        """On the stacker stream: the columns [closed, upto) leave the loop as blocks appended to `blocks` -- out of the ring (one
+        genie_ring_close launch: the open columns never span more than the ring) up to the last column any window has fed so far,
+        as zeros beyond it (columns no window feeds, whose slots may already belong to later columns)."""
+        fed = min(upto, self.last_col + 1)
+        if fed > self.closed:
+            blocks.append(engine.ring_close(self.ring, self.closed, fed))
+            self.closed = fed
+        if upto > self.closed:
+            blocks.append(torch.zeros((self.ring.shape[0], upto - self.closed), dtype=torch.float32, device=self.ring.device))
+            self.closed = upto
+
+    def feed(self, P_chunk, t_now):
+        t_now = float(t_now)
+        if not t_now >= self.t_now:
+            raise ValueError("OnlineDay.feed: t_now = %r after t_now = %r (it never decreases)" % (t_now, self.t_now))
+        net, n, first_col, blocks = self.lane.net, len(self.times), self.closed, []
+        if net.window_batch != self.tail_batch:
+            raise RuntimeError("OnlineDay.feed: the model's window_batch was changed to %d (this loop set %d)" % (net.window_batch, self.tail_batch))
+        if P_chunk is not None and self.n_run < n:           # (after the last window nothing reads a pick)
+            self.picks.append(P_chunk)                       # a pick older than frozen_t raises here, before anything has changed
+        self.t_now = t_now
+        ready = online_ready(self.times[self.n_run:], t_now, self.max_t, self.kernel_sig_t, self.t_win)
+        end = self.n_run + (int(np.argmin(ready)) if not ready.all() else len(ready))        # ascending times: the ready ones are a prefix
+        cand = self.times[self.n_run:end]
+        keep = np.isin(cand, windows_with_enough_picks(self.picks.t_host, cand, self.max_t, self.t_win, self.min_required_picks))
+        lo, hi = _embed_ranges(self.picks.t_host, cand, self.max_t, self.kernel_sig_t)
+        keep &= hi > lo                                                                       # process_continuous_days.py:792-793
+        body, dev = self.body, self.ring.device
+        with torch.no_grad(), torch.cuda.device(dev):
+            body.main = torch.cuda.current_stream(dev)
+            body.stacker.wait_stream(body.main)              # the uploads of this call's chunk, the ring's zeros
+            with torch.cuda.stream(body.stacker):            # (the first call only: the columns before the first window's)
+                self._close(blocks, int(self.frontiers[self.n_run]))
+            for a, b in online_batches(self.n_run, end, self.tail_batch):
+                ws = [w for w in range(a, b) if keep[w - self.n_run]]
+                for w in ws:
+                    k = w - self.n_run
+                    body.window(self.picks, cand[k], int(lo[k]), int(hi[k]))
+                if ws:
+                    body.flush(lambda xs: self._add(xs, ws))
+                    self.times_used.extend(self.times[ws])
+                with torch.cuda.stream(body.stacker):
+                    self._close(blocks, int(self.frontiers[b]))
+            self.n_run = end
+            with torch.cuda.stream(body.stacker):            # (after the last window frontiers[n] = the whole axis)
+                block = blocks[0] if len(blocks) == 1 else (
+                    torch.cat(blocks, dim=1) if blocks else torch.zeros((self.ring.shape[0], 0), dtype=torch.float32, device=dev))
+            block.record_stream(body.main)
+            body.join()
+        body.main.synchronize()                              # this call's one wait
+        _check_verdicts(net)
+        first_read = online_read_bounds(self.times[self.n_run:self.n_run + 1], self.max_t, self.kernel_sig_t, self.t_win)[0]
+        first_read = float(first_read[0]) if self.n_run < n else np.inf
+        self.picks.frozen_t = min(first_read, t_now)         # (a pick from t_now on that no window reads any more is not late: it is trimmed)
+        self.picks.trim(np.nextafter(first_read, -np.inf))
+        return first_col, block
+
+    def _add(self, xs, ws):
+        """One genie_stack_windows_ring launch for the read-outs `xs` of the candidate windows `ws` (ascending; contiguous unless the
+        filters dropped one in between: then their rows of the table are gathered on the device)."""
+        used = self.h_cols[ws]
+        used = used[used >= 0]
+        if used.size:
+            self.last_col = max(self.last_col, int(used.max()))
+            rows = self.d_cols[ws[0]:ws[-1] + 1] if ws[-1] - ws[0] + 1 == len(ws) else torch.cat([self.d_cols[w:w + 1] for w in ws])
+            engine.stack_windows_ring(self.ring, xs, rows, self.scale, int(used.min()), int(used.max()))
+
+    def finish(self):
+        """Everything left: `feed(None, inf)`; afterwards `closed == len(tsteps_abs)`."""
+        return self.feed(None, np.inf)
 
 
 def _inside_region(X, ranges):

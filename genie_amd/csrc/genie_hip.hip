@@ -1250,6 +1250,7 @@ __device__ __forceinline__ void gather_sum16(const float* __restrict__ base, lon
 #include "train_arrival_kernels.hpp"
 #include "detect_kernels.hpp"
 #include "stack_kernels.hpp"
+#include "picks_kernels.hpp"
 #include "select_kernels.hpp"
 #include "cloud_kernels.hpp"
 #include "optim_kernels.hpp"
@@ -4294,19 +4295,29 @@ int genie_time_pointers_merge(const int64_t* cand, int world, int n_sta, int n_t
 
 namespace {
 // The one launch of k_stack_windows, for the entry `name` (in messages): `legs` holds n_legs >= 1 read-out pointers.
+// `ring`: out is the ring of genie_stack_windows_ring (n_cols slots, column c in slot c % n_cols); the range must be narrower than it.
 int stack_windows_launch(const char* name, const SwLegs& legs, int n_legs, const int32_t* cols, int n_windows, int64_t n_query, int n_offsets,
-                         float scale, float* out, int64_t n_cols, int64_t c_min, int64_t c_max, void* stream) {
+                         float scale, float* out, int64_t n_cols, int64_t c_min, int64_t c_max, void* stream, bool ring = false) {
     if (n_windows < 1 || n_windows > SW_MAX_B || n_offsets < 1 || n_offsets > SW_MAX_T)
         return fail(GENIE_ERR_ARG, std::string(name) + ": 1 <= n_windows <= 16 and 1 <= n_offsets <= 64 required");
-    if (n_query < 0 || n_cols < 1 || n_cols >= (1ll << 31) || c_min < 0 || c_max < c_min || c_max >= n_cols)
+    if (ring) {
+        if (n_query < 0 || n_cols < 1 || n_cols >= (1ll << 31) || c_min < 0 || c_max < c_min || c_max >= (1ll << 31))
+            return fail(GENIE_ERR_ARG, std::string(name) + ": n_query >= 0, 1 <= ring_cols < 2^31 and 0 <= c_min <= c_max < 2^31 required");
+        if (c_max - c_min >= n_cols)
+            return fail(GENIE_ERR_ARG, std::string(name) + ": the columns c_min..c_max span the ring or more (two of them would share a slot)");
+    } else if (n_query < 0 || n_cols < 1 || n_cols >= (1ll << 31) || c_min < 0 || c_max < c_min || c_max >= n_cols)
         return fail(GENIE_ERR_ARG, std::string(name) + ": n_query >= 0, 1 <= n_cols < 2^31 and 0 <= c_min <= c_max < n_cols required");
     if (!cols || (n_query > 0 && (!legs.x[0] || !out))) return fail(GENIE_ERR_ARG, std::string(name) + ": null argument");
     if (n_query == 0) return GENIE_OK;
     const int64_t width = c_max - c_min + 1;
     const int64_t nb = (n_query * width + 255) / 256;                      // (n_query * width < 2^63: width < 2^31, n_query checked below)
     if (n_query >= (1ll << 31) || nb >= (1ll << 31)) return fail(GENIE_ERR_ARG, std::string(name) + ": n_query x (c_max - c_min + 1) too large for one launch");
-    k_stack_windows<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(legs, n_legs, cols, n_windows, (long long)n_query, n_offsets, scale, out,
-                                                                  (long long)n_cols, (int)c_min, (int)width);
+    if (ring)
+        k_stack_windows<true><<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(legs, n_legs, cols, n_windows, (long long)n_query, n_offsets, scale,
+                                                                            out, (long long)n_cols, (int)c_min, (int)width);
+    else
+        k_stack_windows<false><<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(legs, n_legs, cols, n_windows, (long long)n_query, n_offsets, scale,
+                                                                             out, (long long)n_cols, (int)c_min, (int)width);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }
@@ -4320,19 +4331,66 @@ int genie_stack_windows(const float* x, const int32_t* cols, int n_windows, int6
     return stack_windows_launch("genie_stack_windows", legs, 1, cols, n_windows, n_query, n_offsets, scale, out, n_cols, c_min, c_max, stream);
 }
 
+namespace {
+// The leg table of genie_stack_windows_legs / _ring from the caller's host array, checked; the error (already recorded) or GENIE_OK.
+int stack_legs_table(const char* name, const float* const* x_legs, int n_legs, SwLegs& legs) {
+    if (n_legs < 1 || n_legs > SW_MAX_LEGS) return fail(GENIE_ERR_ARG, std::string(name) + ": 1 <= n_legs <= 32 required");
+    if (!x_legs) return fail(GENIE_ERR_ARG, std::string(name) + ": null argument");
+    memset(&legs, 0, sizeof(legs));
+    for (int l = 0; l < n_legs; ++l) {                                     // (whatever n_query is)
+        if (!x_legs[l]) return fail(GENIE_ERR_ARG, std::string(name) + ": null read-out pointer");
+        legs.x[l] = x_legs[l];
+    }
+    return GENIE_OK;
+}
+}  // namespace
+
 int genie_stack_windows_legs(const float* const* x_legs, int n_legs, const int32_t* cols, int n_windows, int64_t n_query, int n_offsets,
                              float scale, float* out, int64_t n_cols, int64_t c_min, int64_t c_max, void* stream) {
     static_assert(SW_MAX_LEGS == RS_MAX_LEGS, "one leg limit for the day's passes");
-    if (n_legs < 1 || n_legs > SW_MAX_LEGS) return fail(GENIE_ERR_ARG, "genie_stack_windows_legs: 1 <= n_legs <= 32 required");
-    if (!x_legs) return fail(GENIE_ERR_ARG, "genie_stack_windows_legs: null argument");
     SwLegs legs;
-    memset(&legs, 0, sizeof(legs));
-    for (int l = 0; l < n_legs; ++l) {                                     // (whatever n_query is)
-        if (!x_legs[l]) return fail(GENIE_ERR_ARG, "genie_stack_windows_legs: null read-out pointer");
-        legs.x[l] = x_legs[l];
-    }
+    if (int rc = stack_legs_table("genie_stack_windows_legs", x_legs, n_legs, legs)) return rc;
     return stack_windows_launch("genie_stack_windows_legs", legs, n_legs, cols, n_windows, n_query, n_offsets, scale, out, n_cols, c_min, c_max,
                                 stream);
+}
+
+int genie_stack_windows_ring(const float* const* x_legs, int n_legs, const int32_t* cols, int n_windows, int64_t n_query, int n_offsets,
+                             float scale, float* ring, int64_t ring_cols, int64_t c_min, int64_t c_max, void* stream) {
+    SwLegs legs;
+    if (int rc = stack_legs_table("genie_stack_windows_ring", x_legs, n_legs, legs)) return rc;
+    return stack_windows_launch("genie_stack_windows_ring", legs, n_legs, cols, n_windows, n_query, n_offsets, scale, ring, ring_cols, c_min,
+                                c_max, stream, true);
+}
+
+int genie_ring_close(float* ring, int64_t n_query, int64_t ring_cols, int64_t c_lo, int64_t c_hi, float* out, void* stream) {
+    if (n_query < 0 || n_query >= (1ll << 31) || ring_cols < 1 || ring_cols >= (1ll << 31) || c_lo < 0 || c_hi < c_lo || c_hi > (1ll << 31))
+        return fail(GENIE_ERR_ARG, "genie_ring_close: 0 <= n_query < 2^31, 1 <= ring_cols < 2^31 and 0 <= c_lo <= c_hi <= 2^31 required");
+    if (c_hi - c_lo > ring_cols) return fail(GENIE_ERR_ARG, "genie_ring_close: more columns than the ring has slots");
+    const int64_t n = c_hi - c_lo;
+    if (n_query == 0 || n == 0) return GENIE_OK;
+    if (!ring || !out) return fail(GENIE_ERR_ARG, "genie_ring_close: null argument");
+    const int64_t nb = (n_query * n + 255) / 256;
+    if (nb >= (1ll << 31)) return fail(GENIE_ERR_ARG, "genie_ring_close: n_query x (c_hi - c_lo) too large for one launch");
+    k_ring_close<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(ring, (long long)n_query, (long long)ring_cols, (long long)c_lo, (long long)n, out);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+int genie_picks_merge(const double* t_a, const int32_t* sta_a, const int32_t* phase_a, const int64_t* index_a, int64_t n_a, const double* t_b,
+                      const int32_t* sta_b, const int32_t* phase_b, const int64_t* index_b, int64_t n_b, double* t_out, int32_t* sta_out,
+                      int32_t* phase_out, int64_t* index_out, void* stream) {
+    if (n_a < 0 || n_b < 0 || n_a >= (1ll << 38) || n_b >= (1ll << 38))
+        return fail(GENIE_ERR_ARG, "genie_picks_merge: 0 <= n_a, n_b < 2^38 required");
+    if (n_a + n_b == 0) return GENIE_OK;
+    if ((n_a > 0 && (!t_a || !sta_a || !phase_a || !index_a)) || (n_b > 0 && (!t_b || !sta_b || !phase_b || !index_b)) || !t_out || !sta_out ||
+        !phase_out || !index_out)
+        return fail(GENIE_ERR_ARG, "genie_picks_merge: null argument");
+    const PickRun a{t_a, sta_a, phase_a, (const long long*)index_a, (long long)n_a};
+    const PickRun b{t_b, sta_b, phase_b, (const long long*)index_b, (long long)n_b};
+    const int64_t nb = (n_a + n_b + 255) / 256;
+    k_picks_merge<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(a, b, t_out, sta_out, phase_out, (long long*)index_out);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
 }
 
 size_t genie_refine_select_scratch_bytes(void) { return (size_t)RS_MAX_WG * sizeof(RsPartial); }

@@ -15,6 +15,9 @@
 // Contraction is off: the product is rounded before the add (v_mul_f32 + v_add_f32, no v_fma_f32), as the two torch kernels round it.
 // The leg pointers travel by value in the kernel arguments, as k_refine_select_partial takes them: the loop over l indexes the
 // kernel-argument segment (scalar loads), no private copy of the table exists and nothing is copied to the device before the launch.
+// RING (the online day loop): out is a ring [Q, n_cols] of the day's open columns and the element of column c lives in slot c % n_cols;
+// everything else is the dense kernel, statement for statement, so a column's running sum carries the same bits in either form. The
+// launcher admits a range narrower than the ring only: two columns of one launch never share a slot.
 // ------------------------------------------------------------------------------------------------
 constexpr int SW_MAX_B = 16;
 constexpr int SW_MAX_T = 64;
@@ -24,6 +27,7 @@ struct SwLegs {
     const float* x[SW_MAX_LEGS];
 };
 
+template <bool RING>
 __global__ __launch_bounds__(256) void k_stack_windows(SwLegs legs, int L, const int32_t* __restrict__ cols, int B, long long Q, int T,
                                                        float scale, float* __restrict__ out, long long n_cols, int c_min, int width) {
 #pragma clang fp contract(off)
@@ -34,7 +38,7 @@ __global__ __launch_bounds__(256) void k_stack_windows(SwLegs legs, int L, const
     if (i >= Q * width) return;
     const long long q = i / width;
     const int c = c_min + (int)(i - q * width);
-    float* o = out + q * n_cols + c;                 // 64-bit element offset: a day is 10 000 x 115 200 > 2^31 elements
+    float* o = out + q * n_cols + (RING ? (long long)c % n_cols : (long long)c);   // 64-bit element offset: a day is 10 000 x 115 200 > 2^31 elements
     float acc = *o;
     bool hit = false;
     for (int k = 0; k < B; ++k) {
@@ -50,4 +54,20 @@ __global__ __launch_bounds__(256) void k_stack_windows(SwLegs legs, int L, const
         }
     }
     if (hit) *o = acc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// out[q, j] = ring[q, (c_lo + j) % W]; ring[q, (c_lo + j) % W] = 0, for j = 0..n-1 (n <= W: every slot is read and zeroed by exactly one
+// thread): the columns [c_lo, c_lo + n) of the online day loop leave the ring as a dense block and their slots are free for the columns
+// W further on. One pass, one thread per element, lanes consecutive in j (the block's rows are contiguous runs, the ring's wrap at most
+// once per row).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ring_close(float* __restrict__ ring, long long Q, long long W, long long c_lo, long long n,
+                                                    float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= Q * n) return;
+    const long long q = i / n;
+    float* r = ring + q * W + (c_lo + (i - q * n)) % W;
+    out[i] = *r;
+    *r = 0.f;
 }

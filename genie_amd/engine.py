@@ -191,6 +191,55 @@ def stack_windows_legs(out, xs, cols, scale, c_min, c_max):
     return out
 
 
+def stack_windows_ring(ring, xs, cols, scale, c_min, c_max):
+    """`stack_windows_legs` into a ring of open columns (genie_stack_windows_ring; the online day loop): `ring` fp32 [Q, W], `cols` holds
+    ABSOLUTE columns of the day and column c is added in slot `c % W`. Same kernel, same summation order, so `ring[:, c % W]` carries the
+    bits of the dense `Out_2[:, c]`. Refused (GenieHipError, nothing written) when `c_max - c_min >= W`: two columns of one call never
+    share a slot; freeing the slots of closed columns is `ring_close`."""
+    lib = _lib.load()
+    xs, args = _stack_args("stack_windows_ring", ring, list(xs), cols, scale, c_min, c_max)
+    if ring.shape[0] == 0:
+        return ring
+    ptrs = (ctypes.c_void_p * len(xs))(*[x.data_ptr() for x in xs])
+    with torch.cuda.device(ring.device):
+        _lib.check(lib.genie_stack_windows_ring(ptrs, len(xs), *args, _stream()), "genie_stack_windows_ring")
+    return ring
+
+
+def ring_close(ring, c_lo, c_hi):
+    """The columns [c_lo, c_hi) of a `stack_windows_ring` ring as a new dense fp32 tensor [Q, c_hi - c_lo]; their slots are zeroed in the
+    same pass (genie_ring_close, one launch on the current stream). `c_hi - c_lo <= W`; the range may wrap the ring's end."""
+    if not (torch.is_tensor(ring) and ring.is_cuda and ring.dtype == torch.float32 and ring.dim() == 2 and ring.is_contiguous()):
+        raise ValueError("ring_close: ring must be a contiguous fp32 GPU tensor [n_query, ring_cols]")
+    c_lo, c_hi = int(c_lo), int(c_hi)
+    if not 0 <= c_lo <= c_hi or c_hi - c_lo > ring.shape[1]:
+        raise ValueError("ring_close: 0 <= c_lo <= c_hi and c_hi - c_lo <= %d slots required, got [%d, %d)" % (ring.shape[1], c_lo, c_hi))
+    out = torch.empty((ring.shape[0], c_hi - c_lo), dtype=torch.float32, device=ring.device)
+    with torch.cuda.device(ring.device):
+        _lib.check(_lib.load().genie_ring_close(_ptr(ring), int(ring.shape[0]), int(ring.shape[1]), c_lo, c_hi, _ptr(out), _stream()),
+                   "genie_ring_close")
+    return out
+
+
+PICK_FIELDS = (("t", torch.float64), ("sta", torch.int32), ("phase", torch.int32), ("index", torch.int64))
+
+
+def picks_merge(a, b, out):
+    """Merge two time-sorted runs of picks on the device into `out` (genie_picks_merge, one launch on the current stream): `a`, `b`,
+    `out` = (t float64, sta int32, phase int32, index int64) tuples of contiguous 1-d GPU tensors, `out`'s of len(a) + len(b) elements and
+    not overlapping the inputs. The order is the stable merge with `a` first among equal times. Returns `out`."""
+    n_a, n_b = int(a[0].shape[0]), int(b[0].shape[0])
+    for name, run, n in (("a", a, n_a), ("b", b, n_b), ("out", out, n_a + n_b)):
+        for (field, dtype), x in zip(PICK_FIELDS, run):
+            if not (torch.is_tensor(x) and x.is_cuda and x.dtype == dtype and x.dim() == 1 and x.is_contiguous() and x.shape[0] == n
+                    and x.device == out[0].device):
+                raise ValueError("picks_merge: %s.%s must be a contiguous %s GPU tensor [%d] on %s" % (name, field, dtype, n, out[0].device))
+    with torch.cuda.device(out[0].device):
+        _lib.check(_lib.load().genie_picks_merge(*[_ptr(x) for x in a], n_a, *[_ptr(x) for x in b], n_b, *[_ptr(x) for x in out], _stream()),
+                   "genie_picks_merge")
+    return out
+
+
 def knn_graph_device(points, k):
     """Base kNN graph of a point set on the device: the layout of `remove_self_loops(knn(x, x, k + 1).flip(0))`
     (process_utils.py:718-719) as (table int32 [n, k], edge list int64 [2, n * k] with row 0 = neighbour, row 1 = centre)."""

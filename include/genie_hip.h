@@ -740,6 +740,36 @@ int genie_stack_windows(const float* x, const int32_t* cols, int n_windows, int6
 int genie_stack_windows_legs(const float* const* x_legs, int n_legs, const int32_t* cols, int n_windows, int64_t n_query, int n_offsets,
                              float scale, float* out, int64_t n_cols, int64_t c_min, int64_t c_max, void* stream);
 
+/* The same stacking into a RING of open columns (the online day loop, apply.OnlineDay, whose Out_2 never exists as a whole): ring
+ * [n_query, ring_cols] fp32 and column c of the day lives in slot c % ring_cols,
+ *   for k, for j, for l (innermost):  c = cols[k][j];  if c < 0: skip;   ring[q, c % ring_cols] += x_legs[l][k, q, j] * scale
+ * cols holds ABSOLUTE columns of the day (0 <= c < 2^31), [c_min, c_max] contains every entry >= 0 as in genie_stack_windows, and the
+ * call is refused with GENIE_ERR_ARG, before any launch and writing nothing, when c_max - c_min >= ring_cols: two columns of one call
+ * never share a slot. That a slot holds nothing of an older column is the caller's business (genie_ring_close frees slots). One kernel
+ * serves this entry and genie_stack_windows_legs, so a column's running sum (windows in ascending order, legs in order, the product
+ * rounded before the add) carries the same bits in the ring as in a dense Out_2. Every other argument, range and error as there. */
+int genie_stack_windows_ring(const float* const* x_legs, int n_legs, const int32_t* cols, int n_windows, int64_t n_query, int n_offsets,
+                             float scale, float* ring, int64_t ring_cols, int64_t c_min, int64_t c_max, void* stream);
+
+/* Columns [c_lo, c_hi) leave the ring: out[q, j] = ring[q, (c_lo + j) % ring_cols] for j < c_hi - c_lo, out dense [n_query, c_hi - c_lo]
+ * fp32, and those slots are set to zero -- one pass, every slot read and zeroed by the one thread that owns it. c_hi - c_lo <= ring_cols
+ * (a range may wrap the ring's end), 0 <= c_lo <= c_hi <= 2^31, n_query < 2^31; an empty range or n_query == 0 returns GENIE_OK without
+ * a launch. Bad arguments return GENIE_ERR_ARG before any launch. */
+int genie_ring_close(float* ring, int64_t n_query, int64_t ring_cols, int64_t c_lo, int64_t c_hi, float* out, void* stream);
+
+/* Merge by rank of two time-sorted runs of picks (the growable pick store of the online day loop, apply.PickStore): the resident run a
+ * (n_a picks) and a chunk b (n_b picks), each given as four arrays on the device -- t fp64 ascending, sta int32, phase int32, index int64
+ * -- into the four output arrays of n_a + n_b elements, which must not overlap the inputs:
+ *   a[i] lands at i + #{j: t_b[j] < t_a[i]},     b[j] lands at j + #{i: t_a[i] <= t_b[j]}
+ * the stable merge in which a resident pick precedes a chunk pick of the same time, i.e. a stable sort by time of a followed by b. One
+ * thread per element and a binary search in the other run; every output position is written exactly once, no atomics, and the result
+ * does not depend on scheduling. A run that is not ascending gives an unspecified permutation, never an access outside the arrays.
+ * n_a + n_b == 0 returns GENIE_OK without a launch; an empty run may pass null pointers. Bad arguments (a negative count, a null
+ * pointer of a non-empty run or of the output) return GENIE_ERR_ARG before any launch. */
+int genie_picks_merge(const double* t_a, const int32_t* sta_a, const int32_t* phase_a, const int64_t* index_a, int64_t n_a, const double* t_b,
+                      const int32_t* sta_b, const int32_t* phase_b, const int64_t* index_b, int64_t n_b, double* t_out, int32_t* sta_out,
+                      int32_t* phase_out, int64_t* index_out, void* stream);
+
 /* Selection of the refined source out of the grid legs' query read-outs (the refine pass, process_continuous_days.py:972-978), one call
  * per candidate source instead of a chain of full passes over [n_query, n_t]:
  *   acc[q, t] = fp32 sum over l = 0..n_used-1, in that order and starting from 0.0f, of x[l][q, t] / n_scale, computed as torch computes
