@@ -10,7 +10,7 @@
 //  * stage 1 (k_stage1_h2, the default on the reference's 8 / 15-degree kNN graphs) runs on the 16-bit matrix pipe with every
 //    fp32 operand split into two fp16 pieces (round to nearest: x within one fp32 ulp) and three partial products per product
 //    (fp32 accumulation): fp32 MFMAs share the vector datapath on this hardware. Two tiles per wave, v_mfma_f32_32x32x16_f16.
-//    The fp32 MFMA kernels (k_stage1, k_stage1_pcsr; v_mfma_f32_16x16x4_f32, lane (j = lane&15,
+//    The fp32 MFMA kernels (k_stage1<PCSR>; v_mfma_f32_16x16x4_f32, lane (j = lane&15,
 //    q = lane>>4) holds channels 16t+4q+{0..3} of node j) serve ragged / irregular graphs and use_absolute_pos.
 //  * a neighbour's hidden state is RECOMPUTED from its raw input row instead of gathered (h0 is never stored), u / v are
 //    projected through the neighbour-mean columns before they are averaged (64-B gather rows), and the node-local layer-2
@@ -1028,7 +1028,7 @@ struct DaArgs {
     const float* packed;       // packed A fragments for the stage
     const void* xs;            // k_stage1_h2: the two 16-B fp16 pieces of every [Slice || Mask] row, planar
     long long xs_plane;        // ... bytes per plane (= rows x 16)
-    long long Pn;              // k_stage?_pcsr: number of product nodes (rowptr / col arrays are product-level there)
+    long long Pn;              // PCSR kernels: number of product nodes (rowptr / col arrays are product-level there)
     const float* abs_sta;      // use_absolute_pos: [S][4] = {loc / (3 scale_rel), 0}, or null
     const float* abs_src;      // ... [G_ext][4] = {x_grid / (3 scale_rel), 0}
     const unsigned* abs_ts;    // k_stage1_h2<.., ABS>: [S][2] x 8 B = the fp16 pieces of a station's scaled position {x, y, z, 0} (processing order)
@@ -1040,7 +1040,6 @@ struct DaArgs {
                                // [SV_*][P][16] (genie_da_train_fwd), or null
     const float* slope2;       // stage 2: PReLU slope to use instead of the image's (association heads), or null
     int no_bip;                // stage 2: stop after x_latent (no Bipartite message / station sum): the association heads' last pass
-    int rev;                   // k_stage2_fast: sweep every XCD's chunk backwards (the rows stage 1 wrote last are read first)
     int wgmap;                 // k_stage2_ord: blocks of 4 source nodes per workgroup, one node per wave (see the kernel)
     const int32_t* ptile;      // irregular product graph: processing order of the kernel's tiles (16 or 32 consecutive product nodes), or null
     int np;                    // c / wv rows are NODE-PLANAR (k_stage1_h2 writes, k_stage2_h2u reads): inside the block of a source node,
@@ -1419,18 +1418,18 @@ bool tail_wide(const genie_ctx* c, const StageCall& call) { return !c->tail_f32 
 // The DataAggregation stage kernels a call runs. stage_routes() is the one place that chooses them; run_stage1 / run_stage2 issue
 // the launches of the route they are given.
 enum class S1Route {
-    Generic,     // k_stage1: fp32 MFMA, any graph (64-bit safe); use_absolute_pos with edge features or outside the fp16 range
+    Generic,     // k_stage1<false>: fp32 MFMA, any graph (64-bit safe); use_absolute_pos with edge features or outside the fp16 range
     PcsrH2,      // irregular product graph, f16x2: k_split_rows + k_stage1_h2<.., PCSR>
-    PcsrF32,     // irregular product graph, fp32 MFMA: k_stage1_pcsr
+    PcsrF32,     // irregular product graph, fp32 MFMA: k_stage1<true>
     H2,          // k_split_rows(_g) + k_stage1_h2: c / wv node-planar when stage 2 is k_stage2_h2u, else rows
 };
 enum class S2Route {
     TrainAssoc,  // training forward, last pass of the association heads: k_stage2_ord SAVE in the caller's station order
     TrainH2u,    // training forward on the reference's kNN graphs, f16x2: k_stage2_h2u SAVE in the caller's station order
     TrainOrd,    // ... the same on a sub-range of the source nodes (k_stage2_h2u SAVE covers the whole grid only): k_stage2_ord SAVE
-    Generic,     // k_stage2: fp32 MFMA, any graph
+    Generic,     // k_stage2<false>: fp32 MFMA, any graph
     PcsrPseg,    // irregular product graph, inference: k_stage2_pseg (station sum folded in, straight into the window's slot)
-    PcsrSeg,     // irregular product graph otherwise: k_stage2_pcsr (+ k_seg_sum32 of the station sums into the window's slot)
+    PcsrSeg,     // irregular product graph otherwise: k_stage2<true> (+ k_seg_sum32 of the station sums into the window's slot)
     AssocLast,   // last pass of the association heads in station processing order: k_stage2_ord NB on the rows k_assoc_b wrote
     H2u,         // the production stage 2 (kNN graphs, station processing order): k_stage2_h2u
 };
@@ -2189,8 +2188,8 @@ int genie_ctx_create(genie_ctx** out, int n_sta, int n_grid, int n_grid_ext, con
             auto it = occ.find(dev);
             if (it == occ.end()) {
                 std::array<int, 3> o{};
-                HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o[0], k_stage1, 256, 0));
-                HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o[1], k_stage2, 256, 0));
+                HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o[0], k_stage1<false>, 256, 0));
+                HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o[1], k_stage2<false>, 256, 0));
                 HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o[2], k_stage2_ord<8, 15, false>, 256, 0));
                 it = occ.emplace(dev, o).first;
             }
@@ -2513,7 +2512,7 @@ int run_stage1(genie_ctx* c, const StageCall& call, const float* slice, const fl
     }
     switch (r.s1) {
     case S1Route::Generic:
-        if (n_tiles) k_stage1<<<da_grid(c, n_tiles, c->bpc1), 256, 0, st>>>(a);
+        if (n_tiles) k_stage1<false><<<da_grid(c, n_tiles, c->bpc1), 256, 0, st>>>(a);
         break;
     case S1Route::PcsrH2: {
         unsigned* xs = (unsigned*)((float*)ws + c->o_xs);
@@ -2538,7 +2537,7 @@ int run_stage1(genie_ctx* c, const StageCall& call, const float* slice, const fl
         const long long ntiles = (c->P + 15) / 16;
         a.ptile = c->ptile16;
         const long long gw = std::min<long long>((ntiles + 3) / 4, (long long)c->num_cu * c->bpc1);
-        k_stage1_pcsr<<<(int)std::max<long long>(8, gw / 8 * 8), 256, 0, st>>>(a);
+        k_stage1<true><<<(int)std::max<long long>(8, gw / 8 * 8), 256, 0, st>>>(a);
         break;
     }
     case S1Route::H2: {
@@ -2713,7 +2712,7 @@ int run_stage2(genie_ctx* c, const StageCall& call, const float* mask, const flo
         else k_stage2_ord<8, 15, false, false, true><<<da_grid(c, n_tiles, c->bpc2o), 256, 0, st>>>(a);
         break;
     case S2Route::Generic:
-        k_stage2<<<da_grid(c, n_tiles, c->bpc2), 256, 0, st>>>(a);
+        k_stage2<false><<<da_grid(c, n_tiles, c->bpc2), 256, 0, st>>>(a);
         break;
     case S2Route::PcsrPseg: {
         // a wave per source node, the station sum folded into the pass, straight into the window's slot (a.part)
@@ -2726,7 +2725,7 @@ int run_stage2(genie_ctx* c, const StageCall& call, const float* mask, const flo
         const long long ntiles = (c->P + 15) / 16;
         a.ptile = c->ptile16;
         const long long gw = std::min<long long>((ntiles + 3) / 4, (long long)c->num_cu * c->bpc2);      // 2 .. 12 workgroups per CU: +-1 %
-        k_stage2_pcsr<<<(int)std::max<long long>(8, gw / 8 * 8), 256, 0, st>>>(a);                       // (a multiple of the 8 XCDs)
+        k_stage2<true><<<(int)std::max<long long>(8, gw / 8 * 8), 256, 0, st>>>(a);                      // (a multiple of the 8 XCDs)
         // the gated messages sit in the c rows, which exist GENIE_NBIG times only: their station sums (row order) go to the window's
         // own slot right away, one partial row per source node, so that every tail form (per window, side streams, batched) reads
         // `part` as it does on a Cartesian graph

@@ -1,4 +1,4 @@
-// Part of genie_hip.hip (one translation unit, included inside its anonymous namespace): the P-sized stage kernels of DataAggregation + Bipartite_ReadIn: generic fp32-MFMA stage 1 / stage 2 (any graph), the f16x2 stage 1 (k_stage1_h2) with its split / pack kernels, the straight-line stage 2 (k_stage2_ord).
+// Part of genie_hip.hip (one translation unit, included inside its anonymous namespace): the P-sized stage kernels of DataAggregation + Bipartite_ReadIn: the fp32-MFMA tile pieces and their walkers (k_stage1<PCSR>, k_stage2<PCSR>, k_stage2_pseg: any graph), the f16x2 stage 1 (k_stage1_h2) with its split / pack kernels, the straight-line stage 2 (k_stage2_ord), the f16x2 stage 2 on node-planar rows (k_stage2_h2u).
 
 // ------------------------------------------------------------------------------------------------
 // stage 1: everything of DataAggregation that does not need the SECOND pair of neighbour means
@@ -132,147 +132,131 @@ __device__ __forceinline__ void stage1_dense(const DaArgs& a, const f32x4* lw, c
     }
 }
 
-// generic stage 1: any CSR graphs (ragged degrees, empty neighbourhoods)
-__global__ __launch_bounds__(256) void k_stage1(DaArgs a) {
-    constexpr int NF4 = (G1_GROUPS * 256 + G1_BIAS * 16 + 16) / 4;
-    __shared__ f32x4 lw[NF4];
-    for (int i = threadIdx.x; i < NF4; i += 256) lw[i] = ((const f32x4*)a.packed)[i];
+// ---- tile pieces of the fp32-MFMA stage kernels: each exists once, the kernels below are walkers that compute a tile's
+// (valid, p, table indices, list bounds) and call them
+// the LDS image of a stage: GROUPS A-fragment groups, BIAS 16-float bias blocks, 16 scalars (PReLU slopes)
+constexpr int image_f4(int groups, int bias) { return (groups * 256 + bias * 16 + 16) / 4; }
+struct StageImage { const float* bias; const float* scal; };
+template <int GROUPS, int BIAS>
+__device__ __forceinline__ StageImage load_image(f32x4 (&lw)[image_f4(GROUPS, BIAS)], const float* packed) {
+    for (int i = threadIdx.x; i < image_f4(GROUPS, BIAS); i += 256) lw[i] = ((const f32x4*)packed)[i];
     __syncthreads();
-    const float* lbias = (const float*)(lw + G1_GROUPS * 64);
-    const float* lscal = lbias + G1_BIAS * 16;
-    const float a0 = lscal[0], a1 = lscal[3], a21 = lscal[4], a22 = lscal[5];
-    const float s11 = compose_slopes(a0, lscal[1]), s12 = compose_slopes(a0, lscal[2]);
+    const float* bias = (const float*)(lw + GROUPS * 64);
+    return StageImage{bias, bias + BIAS * 16};
+}
+
+// init_trns as this lane's A fragments and bias chunks: the own node and every recomputed neighbour use them
+struct InitFrag { f32x4 w0, w1, b0, b1; };
+__device__ __forceinline__ InitFrag init_frag(const f32x4* lw, const float* lbias, int lane, int q) {
+    return InitFrag{lw[G1_INIT(0) * 64 + lane], lw[G1_INIT(1) * 64 + lane], *(const f32x4*)(lbias + 0 * 16 + 4 * q),
+                    *(const f32x4*)(lbias + 1 * 16 + 4 * q)};
+}
+
+// stage 1 front: own hidden state h0 = PReLU(init_trns [X || M (|| station position || source position)]) of node p.
+// use_absolute_pos: lq / gq = this node's station / source position channel q, rows is / ig of the tables (the caller knows
+// which rows are the node's), or 0
+template <typename I>
+__device__ __forceinline__ void stage1_front(const DaArgs& a, const InitFrag& f, int q, bool valid, long long p, I is, I ig, float xs,
+                                             float mq, float a0, float& lq, float& gq, f32x4& x0, f32x4& x1) {
+    x0 = MFMA16(f.w0.x, xs, f.b0); x1 = MFMA16(f.w1.x, xs, f.b1);
+    x0 = MFMA16(f.w0.y, mq, x0);
+    x1 = MFMA16(f.w1.y, mq, x1);
+    lq = 0.f; gq = 0.f;
+    if (a.abs_sta != nullptr) {
+        lq = a.abs_sta[is * 4 + q];
+        gq = a.abs_src[ig * 4 + q];
+        x0 = MFMA16(f.w0.z, lq, x0); x1 = MFMA16(f.w1.z, lq, x1);
+        x0 = MFMA16(f.w0.w, gq, x0); x1 = MFMA16(f.w1.w, gq, x1);
+    }
+    if (a.save != nullptr && valid) {      // training forward: the pre-activation of h0
+        *(f32x4*)(a.save + ((size_t)(SV_Z0 + 0) * a.Pn + p) * 16 + 4 * q) = x0;
+        *(f32x4*)(a.save + ((size_t)(SV_Z0 + 1) * a.Pn + p) * 16 + 4 * q) = x1;
+    }
+    x0 = prelu4u(x0, a0);
+    x1 = prelu4u(x1, a0);
+}
+
+// stage 1 neighbour mean of PReLU_slope(h0) over the list col[eb, ee) (slope: composed with h0's own PReLU); row(c) = row0 + c * stride
+template <bool UNI>
+__device__ __forceinline__ void stage1_nbr_mean(const DaArgs& a, long long row0, long long stride, int q, const int32_t* __restrict__ col,
+                                                int eb, int ee, const InitFrag& f, float slope, const AbsNbr ab, f32x4& na, f32x4& nb) {
+    f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};      // local sums, stored once: summed through the references the tile loop compiles to 15 more branches
+    if (slope <= 1.f) gather_recompute<UNI, true>(a.slice, a.mask, row0, stride, q, col, eb, ee, f.w0, f.w1, f.b0, f.b1, slope, s0, s1, ab);
+    else gather_recompute<UNI, false>(a.slice, a.mask, row0, stride, q, col, eb, ee, f.w0, f.w1, f.b0, f.b1, slope, s0, s1, ab);
+    const float inv = 1.f / (float)max(ee - eb, 1);
+    na = s0 * inv; nb = s1 * inv;
+}
+
+// Stage 1, fp32 MFMA, any CSR graphs (ragged degrees, empty neighbourhoods).
+// !PCSR: Cartesian product graph. Walks ItemIter items (source node g, station tile): node p = g S + s, station list of s inside
+// the rows of g, wave-uniform source list of g, position / edge-term tables indexed by station and source node.
+// PCSR: IRREGULAR product graph (`use_subgraph: True`, process_utils.py:744-849): the product nodes are an arbitrary list of
+// (station, source) pairs and both edge sets are CSR lists over PRODUCT-node ids (a.sta_rowptr/col, a.src_rowptr/col are indexed by
+// product node). Walks PtileIter tiles of 16 consecutive product nodes; every table (genie_set_absolute_pos on a subgraph
+// context, the static terms of DataAggregationEdges) is per product node too.
+template <bool PCSR>
+__global__ __launch_bounds__(256) void k_stage1(DaArgs a) {
+    __shared__ f32x4 lw[image_f4(G1_GROUPS, G1_BIAS)];
+    const StageImage im = load_image<G1_GROUPS, G1_BIAS>(lw, a.packed);
+    const float* lbias = im.bias;
+    const float a0 = im.scal[0], a1 = im.scal[3], a21 = im.scal[4], a22 = im.scal[5];
+    const float s11 = compose_slopes(a0, im.scal[1]), s12 = compose_slopes(a0, im.scal[2]);
     int lane = threadIdx.x & 63;
     const int j = lane & 15, q = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int S = a.S;
     ItemIter w(a.G, a.T, a.seg, a.nxcd, wave, a.gi0);
-    for (; w.it < w.nitems; w.it += w.stride) {
-        int gi, tb;
-        w.decode(w.it, gi, tb);
-        const int g = __builtin_amdgcn_readfirstlane(a.order[gi]);
+    PtileIter pt(PCSR ? (a.Pn + 15) / 16 : 0, blockDim.x >> 6, threadIdx.x >> 6);
+    const long long n_it = PCSR ? pt.end : w.nitems, it0 = PCSR ? pt.i : w.it, its = PCSR ? pt.stride : w.stride;
+    for (long long it = it0; it < n_it; it += its) {
+        int g = 0, tb = 0;
+        long long tile = 0;
+        if (PCSR) tile = ptile_at(a.ptile, it);
+        else {
+            int gi;
+            w.decode(it, gi, tb);
+            g = __builtin_amdgcn_readfirstlane(a.order[gi]);
+        }
         asm volatile("" : "+v"(lane));  // A fragments are re-read from LDS per tile, not held in VGPRs across tiles
-        const int s = tb * 16 + j;
-        const bool valid = s < S;
-        const int sc = valid ? s : S - 1;
-        const long long p = (long long)g * S + sc;
+        bool valid;
+        long long p;
+        int sc = 0;
+        if (PCSR) {
+            const long long pr = tile * 16 + j;
+            valid = pr < a.Pn;
+            p = valid ? pr : a.Pn - 1;
+        } else {
+            const int s = tb * 16 + j;
+            valid = s < S;
+            sc = valid ? s : S - 1;
+            p = (long long)g * S + sc;
+        }
+        typedef typename std::conditional<PCSR, long long, int>::type idx_t;
+        const idx_t is = PCSR ? (idx_t)p : (idx_t)sc, ig = PCSR ? (idx_t)p : (idx_t)g;      // the node's rows in the station / source tables
         const float xs = a.slice[p * 4 + q];
         const float mq = a.mask[p * 4 + q];
-        const f32x4 wi0 = lw[G1_INIT(0) * 64 + lane], wi1 = lw[G1_INIT(1) * 64 + lane];
-        const f32x4 bi0 = *(const f32x4*)(lbias + 0 * 16 + 4 * q), bi1 = *(const f32x4*)(lbias + 1 * 16 + 4 * q);
-        // own hidden state
-        f32x4 x0 = MFMA16(wi0.x, xs, bi0), x1 = MFMA16(wi1.x, xs, bi1);
-        x0 = MFMA16(wi0.y, mq, x0);
-        x1 = MFMA16(wi1.y, mq, x1);
-        float lq = 0.f, gq = 0.f;                 // use_absolute_pos: this node's station / source position channel q
-        if (a.abs_sta != nullptr) {
-            lq = a.abs_sta[sc * 4 + q];
-            gq = a.abs_src[g * 4 + q];
-            x0 = MFMA16(wi0.z, lq, x0); x1 = MFMA16(wi1.z, lq, x1);
-            x0 = MFMA16(wi0.w, gq, x0); x1 = MFMA16(wi1.w, gq, x1);
+        const InitFrag f = init_frag(lw, lbias, lane, q);
+        float lq, gq;
+        f32x4 x0, x1, n1a, n1b, n2a, n2b;
+        stage1_front(a, f, q, valid, p, is, ig, xs, mq, a0, lq, gq, x0, x1);
+        {   // station-neighbour mean of PReLU11(h0): rows of the same source node. Such a neighbour's source position is this node's, its
+            // station position is looked up by its id
+            const int eb = a.sta_rowptr[is], ee = a.sta_rowptr[is + 1];
+            stage1_nbr_mean<false>(a, PCSR ? 0 : (long long)g * S, 1, q, a.sta_col, eb, ee, f, s11, AbsNbr{a.abs_sta, true, gq}, n1a, n1b);
         }
-        if (a.save != nullptr && valid) {
-            *(f32x4*)(a.save + ((size_t)(SV_Z0 + 0) * a.Pn + p) * 16 + 4 * q) = x0;
-            *(f32x4*)(a.save + ((size_t)(SV_Z0 + 1) * a.Pn + p) * 16 + 4 * q) = x1;
+        {   // source-neighbour mean of PReLU12(h0): same station, neighbouring source nodes (!PCSR: one wave-uniform list per tile)
+            int eb = a.src_rowptr[ig], ee = a.src_rowptr[ig + 1];
+            if (!PCSR) { eb = __builtin_amdgcn_readfirstlane(eb); ee = __builtin_amdgcn_readfirstlane(ee); }
+            stage1_nbr_mean<!PCSR>(a, PCSR ? 0 : (long long)sc, PCSR ? 1 : (long long)S, q, a.src_col, eb, ee, f, s12,
+                                   AbsNbr{a.abs_src, false, lq}, n2a, n2b);
         }
-        x0 = prelu4u(x0, a0);
-        x1 = prelu4u(x1, a0);
-        // station-neighbour mean of PReLU11(h0): rows of the same source node
-        f32x4 n1a = {0.f, 0.f, 0.f, 0.f}, n1b = {0.f, 0.f, 0.f, 0.f};
-        {
-            const int eb = a.sta_rowptr[sc], ee = a.sta_rowptr[sc + 1];
-            if (s11 <= 1.f)
-                gather_recompute<false, true>(a.slice, a.mask, (long long)g * S, 1, q, a.sta_col, eb, ee, wi0, wi1, bi0, bi1,
-                                              s11, n1a, n1b, AbsNbr{a.abs_sta, true, gq});
-            else
-                gather_recompute<false, false>(a.slice, a.mask, (long long)g * S, 1, q, a.sta_col, eb, ee, wi0, wi1, bi0, bi1,
-                                               s11, n1a, n1b, AbsNbr{a.abs_sta, true, gq});
-            const float inv = 1.f / (float)max(ee - eb, 1);
-            n1a *= inv; n1b *= inv;
-        }
-        // source-neighbour mean of PReLU12(h0): same station, neighbouring source nodes (wave-uniform list)
-        f32x4 n2a = {0.f, 0.f, 0.f, 0.f}, n2b = {0.f, 0.f, 0.f, 0.f};
-        {
-            const int eb = __builtin_amdgcn_readfirstlane(a.src_rowptr[g]);
-            const int ee = __builtin_amdgcn_readfirstlane(a.src_rowptr[g + 1]);
-            if (s12 <= 1.f)
-                gather_recompute<true, true>(a.slice, a.mask, (long long)sc, (long long)S, q, a.src_col, eb, ee, wi0, wi1, bi0,
-                                             bi1, s12, n2a, n2b, AbsNbr{a.abs_src, false, lq});
-            else
-                gather_recompute<true, false>(a.slice, a.mask, (long long)sc, (long long)S, q, a.src_col, eb, ee, wi0, wi1, bi0,
-                                              bi1, s12, n2a, n2b, AbsNbr{a.abs_src, false, lq});
-            const float inv = 1.f / (float)max(ee - eb, 1);
-            n2a *= inv; n2b *= inv;
-        }
-        stage1_dense(a, lw, lbias, lane, q, valid, p, g, sc, mq, x0, x1, n1a, n1b, n2a, n2b, a1, a21, a22);
-    }
-}
-
-// Stage 1 on an IRREGULAR product graph (`use_subgraph: True`, process_utils.py:744-849): the product nodes are an arbitrary
-// list of (station, source) pairs and both edge sets are CSR lists over PRODUCT-node ids (a.sta_rowptr/col, a.src_rowptr/col
-// are indexed by product node here). A tile is 16 consecutive product nodes; same arithmetic as k_stage1.
-__global__ __launch_bounds__(256) void k_stage1_pcsr(DaArgs a) {
-    constexpr int NF4 = (G1_GROUPS * 256 + G1_BIAS * 16 + 16) / 4;
-    __shared__ f32x4 lw[NF4];
-    for (int i = threadIdx.x; i < NF4; i += 256) lw[i] = ((const f32x4*)a.packed)[i];
-    __syncthreads();
-    const float* lbias = (const float*)(lw + G1_GROUPS * 64);
-    const float* lscal = lbias + G1_BIAS * 16;
-    const float a0 = lscal[0], a1 = lscal[3], a21 = lscal[4], a22 = lscal[5];
-    const float s11 = compose_slopes(a0, lscal[1]), s12 = compose_slopes(a0, lscal[2]);
-    int lane = threadIdx.x & 63;
-    const int j = lane & 15, q = lane >> 4;
-    const long long ntiles = (a.Pn + 15) / 16;
-    PtileIter pt(ntiles, blockDim.x >> 6, threadIdx.x >> 6);
-    for (; pt.i < pt.end; pt.i += pt.stride) {
-        const long long tile = ptile_at(a.ptile, pt.i);
-        asm volatile("" : "+v"(lane));
-        const long long pr = tile * 16 + j;
-        const bool valid = pr < a.Pn;
-        const long long p = valid ? pr : a.Pn - 1;
-        const float xs = a.slice[p * 4 + q];
-        const float mq = a.mask[p * 4 + q];
-        const f32x4 wi0 = lw[G1_INIT(0) * 64 + lane], wi1 = lw[G1_INIT(1) * 64 + lane];
-        const f32x4 bi0 = *(const f32x4*)(lbias + 0 * 16 + 4 * q), bi1 = *(const f32x4*)(lbias + 1 * 16 + 4 * q);
-        f32x4 x0 = MFMA16(wi0.x, xs, bi0), x1 = MFMA16(wi1.x, xs, bi1);
-        x0 = MFMA16(wi0.y, mq, x0);
-        x1 = MFMA16(wi1.y, mq, x1);
-        float lq = 0.f, gq = 0.f;     // use_absolute_pos: the position tables are per PRODUCT node here (genie_set_absolute_pos on a subgraph context)
-        if (a.abs_sta != nullptr) {
-            lq = a.abs_sta[p * 4 + q];
-            gq = a.abs_src[p * 4 + q];
-            x0 = MFMA16(wi0.z, lq, x0); x1 = MFMA16(wi1.z, lq, x1);
-            x0 = MFMA16(wi0.w, gq, x0); x1 = MFMA16(wi1.w, gq, x1);
-        }
-        if (a.save != nullptr && valid) {      // training forward: the pre-activation of h0
-            *(f32x4*)(a.save + ((size_t)(SV_Z0 + 0) * a.Pn + p) * 16 + 4 * q) = x0;
-            *(f32x4*)(a.save + ((size_t)(SV_Z0 + 1) * a.Pn + p) * 16 + 4 * q) = x1;
-        }
-        x0 = prelu4u(x0, a0);
-        x1 = prelu4u(x1, a0);
-        f32x4 n1a = {0.f, 0.f, 0.f, 0.f}, n1b = n1a, n2a = n1a, n2b = n1a;
-        {       // a station-type neighbour shares the source node: its source position is this node's; its station position is its own row
-            const int eb = a.sta_rowptr[p], ee = a.sta_rowptr[p + 1];
-            if (s11 <= 1.f) gather_recompute<false, true>(a.slice, a.mask, 0, 1, q, a.sta_col, eb, ee, wi0, wi1, bi0, bi1, s11, n1a, n1b, AbsNbr{a.abs_sta, true, gq});
-            else gather_recompute<false, false>(a.slice, a.mask, 0, 1, q, a.sta_col, eb, ee, wi0, wi1, bi0, bi1, s11, n1a, n1b, AbsNbr{a.abs_sta, true, gq});
-            const float inv = 1.f / (float)max(ee - eb, 1);
-            n1a *= inv; n1b *= inv;
-        }
-        {
-            const int eb = a.src_rowptr[p], ee = a.src_rowptr[p + 1];
-            if (s12 <= 1.f) gather_recompute<false, true>(a.slice, a.mask, 0, 1, q, a.src_col, eb, ee, wi0, wi1, bi0, bi1, s12, n2a, n2b, AbsNbr{a.abs_src, false, lq});
-            else gather_recompute<false, false>(a.slice, a.mask, 0, 1, q, a.src_col, eb, ee, wi0, wi1, bi0, bi1, s12, n2a, n2b, AbsNbr{a.abs_src, false, lq});
-            const float inv = 1.f / (float)max(ee - eb, 1);
-            n2a *= inv; n2b *= inv;
-        }
-        // (DataAggregationEdges on an irregular graph: the static-term tables are per product node, indexed by p on both sides)
-        stage1_dense(a, lw, lbias, lane, q, valid, p, (int)p, (int)p, mq, x0, x1, n1a, n1b, n2a, n2b, a1, a21, a22);
+        stage1_dense(a, lw, lbias, lane, q, valid, p, (int)ig, (int)is, mq, x0, x1, n1a, n1b, n2a, n2b, a1, a21, a22);
     }
 }
 
 // the KS station-neighbour ids of one station as wide loads: a dword load whose lanes hit 16 different 32-B segments costs the
-// texture path about as much as two and a half full 1-KB row loads (tools/: skeleton ablations of k_stage2_fast), and a tile
-// issued KS of them
+// texture path about as much as two and a half full 1-KB row loads (measured by taking the loads out of a skeleton of the stage-2 tile
+// loop), and a tile issued KS of them
 template <int KS>
 __device__ __forceinline__ void load_sta_ids(const int32_t* __restrict__ sta_col, int sc, int (&sta)[KS]) {
     static_assert(KS % 4 == 0, "station-neighbour rows are read as 16-byte chunks");
@@ -867,202 +851,186 @@ __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
 // stage 2: second pair of neighbour means (of the projected operands), PReLU2 -> x_latent; Bipartite fc1 + PReLU,
 // mask gate, and the per-tile station sum.                      module.py:94-96, :229
 // ------------------------------------------------------------------------------------------------
+// ---- tile pieces of the fp32-MFMA stage-2 kernels (each exists once; the three kernels below are walkers over them)
+// 16-byte chunk qc of node pc's two rows before PReLU2: node-local terms c + the means of the projected operands over the
+// station list [eb1, ee1) (rows wu0 + c * ROWW) and the source list [eb2, ee2) (rows wv0 + c * wv_stride; UNI: wave-uniform list).
+// The gathered sums ARE the accumulator contributions: one fused multiply-add per channel with the reciprocal degree.
+template <bool UNI>
+__device__ __forceinline__ void stage2_row_sums(const DaArgs& a, long long pc, int qc, const float* wu0, const float* wv0,
+                                                long long wv_stride, int eb1, int ee1, int eb2, int ee2, f32x4 (&o)[2]) {
+    o[0] = *(const f32x4*)(a.c + pc * ROWC + 4 * qc);
+    o[1] = *(const f32x4*)(a.c + pc * ROWC + 16 + 4 * qc);
+    f32x4 n1 = {0.f, 0.f, 0.f, 0.f}, n2 = {0.f, 0.f, 0.f, 0.f};
+    gather_sum16<false>(wu0 + 4 * qc, ROWW, a.sta_col, eb1, ee1, n1);
+    o[0] = fma4(n1, 1.f / (float)max(ee1 - eb1, 1), o[0]);
+    gather_sum16<UNI>(wv0 + 4 * qc, wv_stride, a.src_col, eb2, ee2, n2);
+    o[1] = fma4(n2, 1.f / (float)max(ee2 - eb2, 1), o[1]);
+}
+
+// chunk qc of node pc: keep the pre-activations (training forward), x_latent = PReLU2 (channels 4 qc .. 4 qc + 3 of either half, channel
+// 15 is zero), optional [P, 30] output
+__device__ __forceinline__ void stage2_x_latent(const DaArgs& a, bool valid, long long pc, int qc, float a2, f32x4 (&o)[2]) {
+    if (a.save != nullptr && valid) {
+        *(f32x4*)(a.save + ((size_t)(SV_O + 0) * a.Pn + pc) * 16 + 4 * qc) = o[0];
+        *(f32x4*)(a.save + ((size_t)(SV_O + 1) * a.Pn + pc) * 16 + 4 * qc) = o[1];
+    }
+    o[0] = prelu4u(o[0], a2);
+    o[1] = prelu4u(o[1], a2);
+    if (a.x_latent != nullptr && valid) {
+        float* xl = a.x_latent + pc * 30;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (4 * qc + r < 15) {
+                xl[4 * qc + r] = o[0][r];
+                xl[15 + 4 * qc + r] = o[1][r];
+            }
+        }
+    }
+}
+
+// row layout (lane = 4 node + chunk: the four lanes of a node hold one 64-B row, as in k_stage2_ord) -> MFMA layout (lane (j, q) holds
+// chunk q of node j) through the wave's LDS scratch ts (16 rows of 36 floats)
+__device__ __forceinline__ void rows_to_mfma(float* ts, int jl, int ql, int j, int q, f32x4 (&o)[2]) {
+    *(f32x4*)(ts + jl * 36 + 4 * ql) = o[0];
+    *(f32x4*)(ts + jl * 36 + 16 + 4 * ql) = o[1];
+    GSYNC();
+    o[0] = *(const f32x4*)(ts + j * 36 + 4 * q);
+    o[1] = *(const f32x4*)(ts + j * 36 + 16 + 4 * q);
+    GSYNC();        // the scratch is rewritten by the next tile of this wave
+}
+
+// Bipartite message before its mask gate: PReLU_b1(fc1 [x_latent || edge_attr]) of node p, x_latent = o in the MFMA layout.
+// SAVE: keep the pre-activations when the training forward asks for them
+template <bool SAVE>
+__device__ __forceinline__ void bipartite_message(const DaArgs& a, const f32x4* lw, const float* lbias, int lane, int q, bool valid,
+                                                  long long p, float eq, float ab1, const f32x4 (&o)[2], f32x4 (&bp)[2]) {
+    bp[0] = *(const f32x4*)(lbias + 0 * 16 + 4 * q);
+    bp[1] = *(const f32x4*)(lbias + 1 * 16 + 4 * q);
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        bp[t] = mma_block(bp[t], lw[G2_BP(t, 0) * 64 + lane], o[0]);
+        bp[t] = mma_block(bp[t], lw[G2_BP(t, 1) * 64 + lane], o[1]);
+        bp[t] = MFMA16(lw[G2_BP(t, 2) * 64 + lane].x, eq, bp[t]);
+        if (SAVE && a.save != nullptr && valid) *(f32x4*)(a.save + ((size_t)(SV_ZB + t) * a.Pn + p) * 16 + 4 * q) = bp[t];
+        bp[t] = prelu4u(bp[t], ab1);
+    }
+}
+
+// the message gate max_k Mask[p][k]: lane (j, q) holds Mask[p][q]
+__device__ __forceinline__ float mask_max4(float mq) {
+    const float mm = fmaxf(mq, __shfl_xor(mq, 16));
+    return fmaxf(mm, __shfl_xor(mm, 32));
+}
+
+// sum over the 16 node columns of a tile (every lane of a row of 16 ends with it): the station sum's tree
+__device__ __forceinline__ f32x4 xor_sum16(f32x4 v) {
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1) {
+        v.x += __shfl_xor(v.x, d);
+        v.y += __shfl_xor(v.y, d);
+        v.z += __shfl_xor(v.z, d);
+        v.w += __shfl_xor(v.w, d);
+    }
+    return v;
+}
+
+// Stage 2, fp32 MFMA, any CSR graphs.
+// !PCSR: Cartesian product graph, walked as k_stage1<false> walks it. Rows are loaded and gathered in the MFMA layout; the gated
+// messages of a tile are summed over its 16 stations into part[g T + tb].
+// PCSR: irregular product graph (see k_stage1<true>), PtileIter tiles of 16 product nodes. Rows are loaded, summed and activated in
+// the row layout and cross the wave's LDS scratch into the MFMA layout for fc1. The Bipartite messages of a source node are not the
+// rows of whole tiles here, so every node's gated message row is written in place of its c row and k_seg_sum32 sums the row range of
+// each source node (product nodes are grouped by source node, process_utils.py:790-794) in row order into the window's `part` slot.
+template <bool PCSR>
 __global__ __launch_bounds__(256) void k_stage2(DaArgs a) {
-    constexpr int NF4 = (G2_GROUPS * 256 + G2_BIAS * 16 + 16) / 4;
-    __shared__ f32x4 lw[NF4];
-    for (int i = threadIdx.x; i < NF4; i += 256) lw[i] = ((const f32x4*)a.packed)[i];
-    __syncthreads();
-    const float* lbias = (const float*)(lw + G2_GROUPS * 64);
-    const float* lscal = lbias + G2_BIAS * 16;
-    const float a2 = a.slope2 != nullptr ? *a.slope2 : lscal[0], ab1 = lscal[1];
+    __shared__ f32x4 lw[image_f4(G2_GROUPS, G2_BIAS)];
+    __shared__ __attribute__((aligned(16))) float tsc[4 * 16 * 36];      // (PCSR only)
+    const StageImage im = load_image<G2_GROUPS, G2_BIAS>(lw, a.packed);
+    const float* lbias = im.bias;
+    const float a2 = a.slope2 != nullptr ? *a.slope2 : im.scal[0], ab1 = im.scal[1];
     int lane = threadIdx.x & 63;
     const int j = lane & 15, q = lane >> 4;
+    const int jl = lane >> 2, ql = lane & 3;      // PCSR: (node, 16-B chunk) this lane LOADS: four consecutive lanes read one 64-B row
+    float* ts = tsc + (threadIdx.x >> 6) * 16 * 36;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int S = a.S;
     ItemIter w(a.G, a.T, a.seg, a.nxcd, wave, a.gi0);
-    for (; w.it < w.nitems; w.it += w.stride) {
-        int gi, tb;
-        w.decode(w.it, gi, tb);
-        const int g = __builtin_amdgcn_readfirstlane(a.order[gi]);
+    PtileIter pt(PCSR ? (a.Pn + 15) / 16 : 0, blockDim.x >> 6, threadIdx.x >> 6);
+    const long long n_it = PCSR ? pt.end : w.nitems, it0 = PCSR ? pt.i : w.it, its = PCSR ? pt.stride : w.stride;
+    for (long long it = it0; it < n_it; it += its) {
+        int g = 0, tb = 0;
+        long long tile = 0;
+        if (PCSR) tile = ptile_at(a.ptile, it);
+        else {
+            int gi;
+            w.decode(it, gi, tb);
+            g = __builtin_amdgcn_readfirstlane(a.order[gi]);
+        }
         asm volatile("" : "+v"(lane));
-        const int s = tb * 16 + j;
-        const bool valid = s < S;
-        const int sc = valid ? s : S - 1;
-        const long long p = (long long)g * S + sc;
-        f32x4 o[2];
-        o[0] = *(const f32x4*)(a.c + p * ROWC + 4 * q);
-        o[1] = *(const f32x4*)(a.c + p * ROWC + 16 + 4 * q);
+        // p: the node of this lane's column j (MFMA layout); (pl, qc): the node and chunk this lane loads and activates
+        bool valid, valid_l;
+        long long p, pl;
+        int sc = 0;
+        if (PCSR) {
+            const long long pr = tile * 16 + j, prl = tile * 16 + jl;
+            valid = pr < a.Pn;
+            p = valid ? pr : a.Pn - 1;
+            valid_l = prl < a.Pn;
+            pl = valid_l ? prl : a.Pn - 1;
+        } else {
+            const int s = tb * 16 + j;
+            valid = valid_l = s < S;
+            sc = valid ? s : S - 1;
+            p = pl = (long long)g * S + sc;
+        }
+        const int qc = PCSR ? ql : q;
         const float mq = a.mask[p * 4 + q];
         const float eq = q < 3 ? a.edge_attr[p * 3 + q] : 0.f;
-        // neighbour means of the projected operands (16-float rows): they ARE the accumulator contributions
-        f32x4 n1 = {0.f, 0.f, 0.f, 0.f}, n2 = {0.f, 0.f, 0.f, 0.f};
-        {
-            const int eb = a.sta_rowptr[sc], ee = a.sta_rowptr[sc + 1];
-            const float* base = a.wu + (long long)g * S * ROWW + 4 * q;
-            gather_sum16<false>(base, ROWW, a.sta_col, eb, ee, n1);
-            o[0] = fma4(n1, 1.f / (float)max(ee - eb, 1), o[0]);
+        f32x4 o[2], bp[2];
+        if (PCSR) {
+            stage2_row_sums<false>(a, pl, qc, a.wu, a.wv, ROWW, a.sta_rowptr[pl], a.sta_rowptr[pl + 1], a.src_rowptr[pl],
+                                   a.src_rowptr[pl + 1], o);
+        } else {      // station rows of this source node; this station's row of the neighbouring source nodes (wave-uniform list)
+            stage2_row_sums<true>(a, pl, qc, a.wu + (long long)g * S * ROWW, a.wv + (long long)sc * ROWW, (long long)S * ROWW,
+                                  a.sta_rowptr[sc], a.sta_rowptr[sc + 1], __builtin_amdgcn_readfirstlane(a.src_rowptr[g]),
+                                  __builtin_amdgcn_readfirstlane(a.src_rowptr[g + 1]), o);
         }
-        {
-            const int eb = __builtin_amdgcn_readfirstlane(a.src_rowptr[g]);
-            const int ee = __builtin_amdgcn_readfirstlane(a.src_rowptr[g + 1]);
-            const float* base = a.wv + (long long)sc * ROWW + 4 * q;
-            gather_sum16<true>(base, (long long)S * ROWW, a.src_col, eb, ee, n2);
-            o[1] = fma4(n2, 1.f / (float)max(ee - eb, 1), o[1]);
-        }
-        if (a.save != nullptr && valid) {
-            *(f32x4*)(a.save + ((size_t)(SV_O + 0) * a.Pn + p) * 16 + 4 * q) = o[0];
-            *(f32x4*)(a.save + ((size_t)(SV_O + 1) * a.Pn + p) * 16 + 4 * q) = o[1];
-        }
-        o[0] = prelu4u(o[0], a2);   // x_latent[0:15]  (lane (j,q) holds channels 4q..4q+3, channel 15 is zero)
-        o[1] = prelu4u(o[1], a2);   // x_latent[15:30]
-        if (a.x_latent != nullptr && valid) {
-            float* xl = a.x_latent + p * 30;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (4 * q + r < 15) {
-                    xl[4 * q + r] = o[0][r];
-                    xl[15 + 4 * q + r] = o[1][r];
-                }
-            }
-        }
-        if (a.no_bip) continue;
-        // Bipartite message: m_p * PReLU_b1(fc1 [x_latent || edge_attr])
-        f32x4 bp[2];
-        bp[0] = *(const f32x4*)(lbias + 0 * 16 + 4 * q);
-        bp[1] = *(const f32x4*)(lbias + 1 * 16 + 4 * q);
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            bp[t] = mma_block(bp[t], lw[G2_BP(t, 0) * 64 + lane], o[0]);
-            bp[t] = mma_block(bp[t], lw[G2_BP(t, 1) * 64 + lane], o[1]);
-            bp[t] = MFMA16(lw[G2_BP(t, 2) * 64 + lane].x, eq, bp[t]);
-            if (a.save != nullptr && valid) *(f32x4*)(a.save + ((size_t)(SV_ZB + t) * a.Pn + p) * 16 + 4 * q) = bp[t];
-            bp[t] = prelu4u(bp[t], ab1);
-        }
-        float mm = fmaxf(mq, __shfl_xor(mq, 16));
-        mm = fmaxf(mm, __shfl_xor(mm, 32));
-        if (!valid) mm = 0.f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            f32x4 v = bp[t] * mm;
-#pragma unroll
-            for (int d = 1; d < 16; d <<= 1) {
-                v.x += __shfl_xor(v.x, d);
-                v.y += __shfl_xor(v.y, d);
-                v.z += __shfl_xor(v.z, d);
-                v.w += __shfl_xor(v.w, d);
-            }
-            if (j == 0) *(f32x4*)(a.part + ((long long)g * a.T + tb) * 32 + 16 * t + 4 * q) = v;
-        }
-    }
-}
-
-// Stage 2 on an irregular product graph (see k_stage1_pcsr). The Bipartite messages of a source node are not the rows of
-// whole tiles here, so every node's gated message row is written in place of its c row and k_seg_sum32 sums the row range
-// of each source node (product nodes are grouped by source node, process_utils.py:790-794) in row order into the window's `part` slot.
-__global__ __launch_bounds__(256) void k_stage2_pcsr(DaArgs a) {
-    constexpr int NF4 = (G2_GROUPS * 256 + G2_BIAS * 16 + 16) / 4;
-    __shared__ f32x4 lw[NF4];
-    for (int i = threadIdx.x; i < NF4; i += 256) lw[i] = ((const f32x4*)a.packed)[i];
-    __syncthreads();
-    const float* lbias = (const float*)(lw + G2_GROUPS * 64);
-    const float* lscal = lbias + G2_BIAS * 16;
-    const float a2 = a.slope2 != nullptr ? *a.slope2 : lscal[0], ab1 = lscal[1];
-    __shared__ __attribute__((aligned(16))) float tsc[4 * 16 * 36];
-    int lane = threadIdx.x & 63;
-    const int j = lane & 15, q = lane >> 4;
-    const int jl = lane >> 2, ql = lane & 3;      // (node, 16-B chunk) this lane LOADS: four consecutive lanes read one 64-B row
-    float* ts = tsc + (threadIdx.x >> 6) * 16 * 36;
-    const long long ntiles = (a.Pn + 15) / 16;
-    PtileIter pt(ntiles, blockDim.x >> 6, threadIdx.x >> 6);
-    for (; pt.i < pt.end; pt.i += pt.stride) {
-        const long long tile = ptile_at(a.ptile, pt.i);
-        asm volatile("" : "+v"(lane));
-        const long long pr = tile * 16 + j;
-        const bool valid = pr < a.Pn;
-        const long long p = valid ? pr : a.Pn - 1;
-        // rows are loaded, summed and activated in the ROW layout (lane = 4 node + chunk: the four lanes of a node read one 64-B
-        // row, as in k_stage2_ord), then cross the wave's LDS scratch into the MFMA layout for fc1
-        const long long prl = tile * 16 + jl;
-        const bool valid_l = prl < a.Pn;
-        const long long pl = valid_l ? prl : a.Pn - 1;
-        f32x4 o[2];
-        o[0] = *(const f32x4*)(a.c + pl * ROWC + 4 * ql);
-        o[1] = *(const f32x4*)(a.c + pl * ROWC + 16 + 4 * ql);
-        const float mq = a.mask[p * 4 + q];
-        const float eq = q < 3 ? a.edge_attr[p * 3 + q] : 0.f;
-        f32x4 n1 = {0.f, 0.f, 0.f, 0.f}, n2 = {0.f, 0.f, 0.f, 0.f};
-        {
-            const int eb = a.sta_rowptr[pl], ee = a.sta_rowptr[pl + 1];
-            gather_sum16<false>(a.wu + 4 * ql, ROWW, a.sta_col, eb, ee, n1);
-            o[0] = fma4(n1, 1.f / (float)max(ee - eb, 1), o[0]);
-        }
-        {
-            const int eb = a.src_rowptr[pl], ee = a.src_rowptr[pl + 1];
-            gather_sum16<false>(a.wv + 4 * ql, ROWW, a.src_col, eb, ee, n2);
-            o[1] = fma4(n2, 1.f / (float)max(ee - eb, 1), o[1]);
-        }
-        if (a.save != nullptr && valid_l) {      // training forward: pre-activations of x_latent (chunk ql of node jl: the blocks' own layout)
-            *(f32x4*)(a.save + ((size_t)(SV_O + 0) * a.Pn + pl) * 16 + 4 * ql) = o[0];
-            *(f32x4*)(a.save + ((size_t)(SV_O + 1) * a.Pn + pl) * 16 + 4 * ql) = o[1];
-        }
-        o[0] = prelu4u(o[0], a2);
-        o[1] = prelu4u(o[1], a2);
-        if (a.x_latent != nullptr && valid_l) {
-            float* xl = a.x_latent + pl * 30;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (4 * ql + r < 15) {
-                    xl[4 * ql + r] = o[0][r];
-                    xl[15 + 4 * ql + r] = o[1][r];
-                }
-            }
-        }
+        stage2_x_latent(a, valid_l, pl, qc, a2, o);
         if (a.no_bip) continue;         // last pass of the association heads: x_latent only (wave-uniform)
-        *(f32x4*)(ts + jl * 36 + 4 * ql) = o[0];
-        *(f32x4*)(ts + jl * 36 + 16 + 4 * ql) = o[1];
-        GSYNC();
-        o[0] = *(const f32x4*)(ts + j * 36 + 4 * q);
-        o[1] = *(const f32x4*)(ts + j * 36 + 16 + 4 * q);
-        GSYNC();        // the scratch is rewritten by the next tile of this wave
-        f32x4 bp[2];
-        bp[0] = *(const f32x4*)(lbias + 0 * 16 + 4 * q);
-        bp[1] = *(const f32x4*)(lbias + 1 * 16 + 4 * q);
+        if (PCSR) rows_to_mfma(ts, jl, ql, j, q, o);
+        bipartite_message<true>(a, lw, lbias, lane, q, valid, p, eq, ab1, o, bp);
+        const float mm = mask_max4(mq);      // the gated message is m_p * bp
+        if (PCSR) {
+            if (valid) {      // the message row replaces the c row of the node (read above by these same lanes)
+                *(f32x4*)(a.c + p * ROWC + 4 * q) = bp[0] * mm;
+                *(f32x4*)(a.c + p * ROWC + 16 + 4 * q) = bp[1] * mm;
+            }
+        } else {
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            bp[t] = mma_block(bp[t], lw[G2_BP(t, 0) * 64 + lane], o[0]);
-            bp[t] = mma_block(bp[t], lw[G2_BP(t, 1) * 64 + lane], o[1]);
-            bp[t] = MFMA16(lw[G2_BP(t, 2) * 64 + lane].x, eq, bp[t]);
-            if (a.save != nullptr && valid) *(f32x4*)(a.save + ((size_t)(SV_ZB + t) * a.Pn + p) * 16 + 4 * q) = bp[t];
-            bp[t] = prelu4u(bp[t], ab1);
-        }
-        float mm = fmaxf(mq, __shfl_xor(mq, 16));
-        mm = fmaxf(mm, __shfl_xor(mm, 32));
-        if (valid) {      // the message row replaces the c row of the node (read above by these same lanes)
-            *(f32x4*)(a.c + p * ROWC + 4 * q) = bp[0] * mm;
-            *(f32x4*)(a.c + p * ROWC + 16 + 4 * q) = bp[1] * mm;
+            for (int t = 0; t < 2; ++t) {
+                const f32x4 v = xor_sum16(bp[t] * (valid ? mm : 0.f));
+                if (j == 0) *(f32x4*)(a.part + ((long long)g * a.T + tb) * 32 + 16 * t + 4 * q) = v;
+            }
         }
     }
 }
 
-// Stage 2 on an irregular product graph with the station sum FOLDED IN (round 6): a wave owns whole source nodes. The product nodes
-// of a source node are one contiguous row range (process_utils.py:790-794: `seg_rowptr`), so the wave walks that range 16 nodes at a
-// time -- the arithmetic of k_stage2_pcsr per tile -- and keeps the gated Bipartite messages of its node columns in two accumulators
-// across the tiles; one butterfly over the 16 columns at the end gives the source node's station sum, written straight to the
-// window's `part` row. No message row is written back over c (128 B per product node) and read again by k_seg_sum32 (one launch
-// less). Source nodes are taken in processing order (space-filling curve), chunked by XCD as the tiles of k_stage2_pcsr are, so the
-// wv rows the waves of a CU gather overlap. Inference only (no kept pre-activations, no x_latent output): the other calls keep
-// k_stage2_pcsr + k_seg_sum32. Station sum order: per node column over the tiles (rows j, j + 16, ...), then the butterfly.
+// Stage 2 on an irregular product graph with the station sum FOLDED IN: a wave owns whole source nodes. The product nodes of a
+// source node are one contiguous row range (process_utils.py:790-794: `seg_rowptr`), so the wave walks that range 16 nodes at a time
+// -- the tile pieces of k_stage2<true> -- and keeps the gated Bipartite messages of its node columns in two accumulators across the
+// tiles; one butterfly over the 16 columns at the end gives the source node's station sum, written straight to the window's `part`
+// row. No message row is written back over c (128 B per product node) and read again by k_seg_sum32 (one launch less). Source nodes
+// are taken in processing order (space-filling curve), chunked by XCD as the tiles of k_stage2<true> are, so the wv rows the waves of
+// a CU gather overlap. Inference only (no kept pre-activations, no x_latent output): the other calls keep k_stage2<true> +
+// k_seg_sum32. Station sum order: per node column over the tiles (rows j, j + 16, ...), then the butterfly.
 // Measured and dropped (profiles/EXPERIMENTS.md, round 6): the range's own `wu` rows staged in the wave's LDS for the 8 station
 // gathers of every node (48 KB per workgroup, a bounds check per neighbour): 0.310 -> 0.345 ms per window, back to the unfused time.
 __global__ __launch_bounds__(256) void k_stage2_pseg(DaArgs a, const int32_t* __restrict__ seg_rowptr, int n_src) {
-    constexpr int NF4 = (G2_GROUPS * 256 + G2_BIAS * 16 + 16) / 4;
-    __shared__ f32x4 lw[NF4];
-    for (int i = threadIdx.x; i < NF4; i += 256) lw[i] = ((const f32x4*)a.packed)[i];
-    __syncthreads();
-    const float* lbias = (const float*)(lw + G2_GROUPS * 64);
-    const float* lscal = lbias + G2_BIAS * 16;
-    const float a2 = a.slope2 != nullptr ? *a.slope2 : lscal[0], ab1 = lscal[1];
+    __shared__ f32x4 lw[image_f4(G2_GROUPS, G2_BIAS)];
     __shared__ __attribute__((aligned(16))) float tsc[4 * 16 * 36];
+    const StageImage im = load_image<G2_GROUPS, G2_BIAS>(lw, a.packed);
+    const float* lbias = im.bias;
+    const float a2 = a.slope2 != nullptr ? *a.slope2 : im.scal[0], ab1 = im.scal[1];
     int lane = threadIdx.x & 63;
     const int j = lane & 15, q = lane >> 4;
     const int jl = lane >> 2, ql = lane & 3;
@@ -1079,66 +1047,40 @@ __global__ __launch_bounds__(256) void k_stage2_pseg(DaArgs a, const int32_t* __
             const long long p = valid ? pr : r1 - 1;
             const long long prl = base + jl;
             const long long pl = prl < r1 ? prl : r1 - 1;
-            f32x4 o[2];
-            o[0] = *(const f32x4*)(a.c + pl * ROWC + 4 * ql);
-            o[1] = *(const f32x4*)(a.c + pl * ROWC + 16 + 4 * ql);
             const float mq = a.mask[p * 4 + q];
             const float eq = q < 3 ? a.edge_attr[p * 3 + q] : 0.f;
-            f32x4 n1 = {0.f, 0.f, 0.f, 0.f}, n2 = {0.f, 0.f, 0.f, 0.f};
-            {
-                const int eb = a.sta_rowptr[pl], ee = a.sta_rowptr[pl + 1];
-                gather_sum16<false>(a.wu + 4 * ql, ROWW, a.sta_col, eb, ee, n1);
-                o[0] = fma4(n1, 1.f / (float)max(ee - eb, 1), o[0]);
-            }
-            {
-                const int eb = a.src_rowptr[pl], ee = a.src_rowptr[pl + 1];
-                gather_sum16<false>(a.wv + 4 * ql, ROWW, a.src_col, eb, ee, n2);
-                o[1] = fma4(n2, 1.f / (float)max(ee - eb, 1), o[1]);
-            }
+            f32x4 o[2], bp[2];
+            stage2_row_sums<false>(a, pl, ql, a.wu, a.wv, ROWW, a.sta_rowptr[pl], a.sta_rowptr[pl + 1], a.src_rowptr[pl],
+                                   a.src_rowptr[pl + 1], o);
             o[0] = prelu4u(o[0], a2);
             o[1] = prelu4u(o[1], a2);
-            *(f32x4*)(ts + jl * 36 + 4 * ql) = o[0];
-            *(f32x4*)(ts + jl * 36 + 16 + 4 * ql) = o[1];
-            GSYNC();
-            o[0] = *(const f32x4*)(ts + j * 36 + 4 * q);
-            o[1] = *(const f32x4*)(ts + j * 36 + 16 + 4 * q);
-            GSYNC();
-            float mm = fmaxf(mq, __shfl_xor(mq, 16));
-            mm = fmaxf(mm, __shfl_xor(mm, 32));
+            rows_to_mfma(ts, jl, ql, j, q, o);
+            bipartite_message<false>(a, lw, lbias, lane, q, valid, p, eq, ab1, o, bp);
+            float mm = mask_max4(mq);
             mm = valid ? mm : 0.f;
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                f32x4 bp = *(const f32x4*)(lbias + t * 16 + 4 * q);
-                bp = mma_block(bp, lw[G2_BP(t, 0) * 64 + lane], o[0]);
-                bp = mma_block(bp, lw[G2_BP(t, 1) * 64 + lane], o[1]);
-                bp = MFMA16(lw[G2_BP(t, 2) * 64 + lane].x, eq, bp);
-                sum[t] += prelu4u(bp, ab1) * mm;
-            }
+            sum[0] += bp[0] * mm;
+            sum[1] += bp[1] * mm;
         }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            f32x4 v = sum[t];
-#pragma unroll
-            for (int d = 1; d < 16; d <<= 1) {
-                v.x += __shfl_xor(v.x, d); v.y += __shfl_xor(v.y, d); v.z += __shfl_xor(v.z, d); v.w += __shfl_xor(v.w, d);
-            }
+            const f32x4 v = xor_sum16(sum[t]);
             if (j == 0) *(f32x4*)(a.part + (long long)g * 32 + 16 * t + 4 * q) = v;
         }
     }
 }
 
-// k_stage2_fast for the production configuration (uniform-degree graphs, station processing order with a registered static
-// edge_attr, static item stream, Bipartite half on), straight-line: the ISA of k_stage2_fast spends a fifth of its vector
-// instructions on register copies at the joins of its option branches (the 15 source rows were copied out and back every tile),
-// 34 ds_bpermute per tile on the station sum and a dozen uniform branches. Here
+// k_stage2_ord: stage 2 for the production configuration (uniform-degree graphs, station processing order with a registered static
+// edge_attr, static item stream, Bipartite half on), straight-line. A software-pipelined tile loop that keeps those as run-time
+// options spends a fifth of its vector instructions on register copies at the joins of the option branches (the 15 source rows
+// are copied out and back every tile), 34 ds_bpermute per tile on the station sum and a dozen uniform branches. Here
 //  * the item after the last one is clamped to the last one, so every load of the software pipeline is unconditional and no
 //    value has two definitions at a join;
 //  * a tile's ids are its (wave-uniform) item number, one src_tab row and the 8 station-neighbour ids, which are loaded into the
 //    registers the previous tile's ids have just left: nothing rotates but one register;
 //  * the station sum over the 16 nodes of a tile is a DPP row reduction (row_shl:1, 2, 4, 8): lane 0 of every row adds the same
-//    operands in the same tree as the xor butterfly of k_stage2 (bitwise identical), without the LDS round trips;
+//    operands in the same tree as xor_sum16 in k_stage2<false> (bitwise identical), without the LDS round trips;
 //  * the message mask is read by all four lanes of a node (one address) instead of max-reduced across them.
-// Same arithmetic and summation order as k_stage2 / k_stage2_fast (bitwise identical results; tests).
+// Same arithmetic and summation order as k_stage2<false> (bitwise identical results; tests).
 template <int CTRL>
 __device__ __forceinline__ float dpp_add(float v) {
     return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));

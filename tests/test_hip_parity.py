@@ -302,7 +302,7 @@ def test_use_absolute_pos_forward_fixed_source(name):
 def test_updated_model_definition_on_an_irregular_product_graph(name, stage1, monkeypatch):
     """`use_updated_model_definition: True` with `use_subgraph: True`: the mean edge feature of a product node runs over its PRESENT
     neighbours, so the static terms are per product node (genie_set_edge_features with positions per product node: `k_edge_feat` on
-    the product-level CSRs, `[n_prod, 48]` term tables indexed by product node in k_stage1_h2<EDGES, .., PCSR> / k_stage1_pcsr).
+    the product-level CSRs, `[n_prod, 48]` term tables indexed by product node in k_stage1_h2<EDGES, .., PCSR> / k_stage1<PCSR = true>).
     Fixture: the reference imported with the flag, run on the irregular graph of `subgraph_14x50`."""
     if stage1 == "f32":
         monkeypatch.setattr(engine, "STAGE_PRECISION", "f32")
@@ -361,7 +361,7 @@ def test_both_model_options_together_forward_fixed_source():
 def test_use_subgraph_irregular_product_graph(name, stage1, monkeypatch):
     """f-4: `use_subgraph: True` (config.yaml:86, process_utils.py:744-849). set_adjacencies receives irregular product edge
     lists; the module builds product-level CSRs (genie_ctx_create_subgraph); stage 1 runs k_stage1_h2<.., PCSR> (neighbours as
-    product-node ids, missing ones with weight 0; stage_precision="f32": the generic fp32-MFMA k_stage1_pcsr), then k_stage2_pcsr /
+    product-node ids, missing ones with weight 0; stage_precision="f32": the generic fp32-MFMA k_stage1<PCSR = true>), then k_stage2<PCSR = true> /
     k_bip_out_seg. Checked against the reference's own run on that graph and against the oracle."""
     if stage1 == "f32":
         monkeypatch.setattr(engine, "STAGE_PRECISION", "f32")
@@ -440,9 +440,8 @@ def test_random_shapes_vs_structured_oracle(S, G):
     assert max_abs(out.cpu(), o) <= rel_tol(o)
 
 
-def test_non_uniform_degree_and_empty_neighbourhoods():
-    """CSR graphs with ragged degrees, including nodes with NO in-edges (mean of an empty set = 0, SURVEY App. B)."""
-    from oracle import genie_oracle as O
+def _ragged_graph_21x40():
+    """S = 21, G = 40: base graphs with ragged degrees, a station and a source node with NO in-edges, random inputs on the product."""
     S, G = 21, 40
     rng = np.random.default_rng(7)
     geom = synthetic.Geometry(S, G, L=100e3, n_query=5, seed=8)
@@ -452,13 +451,20 @@ def test_non_uniform_degree_and_empty_neighbourhoods():
     keep_src[geom.A_src_src[1] == 5] = False                       # source node 5 has no neighbours
     A_sta = torch.from_numpy(geom.A_sta_sta[:, keep_sta])
     A_src = torch.from_numpy(geom.A_src_src[:, keep_src])
+    P = S * G
+    Slice = torch.from_numpy(rng.random((P, 4)).astype(np.float32))
+    Mask = torch.from_numpy((rng.random((P, 4)) < 0.5).astype(np.float32))
+    return S, G, geom, A_sta, A_src, Slice, Mask
+
+
+def test_non_uniform_degree_and_empty_neighbourhoods():
+    """CSR graphs with ragged degrees, including nodes with NO in-edges (mean of an empty set = 0, SURVEY App. B)."""
+    from oracle import genie_oracle as O
+    S, G, geom, A_sta, A_src, Slice, Mask = _ragged_graph_21x40()
     c = Case("odd_33x257")
     w = c.weights
     hp = engine.HipPath(S, G, engine.csr_from_edges(A_sta, S), engine.csr_from_edges(A_src, G), device=DEV)
     hp.set_weights({k: v.to(DEV) for k, v in w.items()})
-    P = S * G
-    Slice = torch.from_numpy(rng.random((P, 4)).astype(np.float32))
-    Mask = torch.from_numpy((rng.random((P, 4)) < 0.5).astype(np.float32))
     ea = torch.from_numpy(geom.edge_attr())
     pos = torch.from_numpy(geom.x_grid).float()
     out, x_latent, bip = hp.path_fwd(Slice.to(DEV), Mask.to(DEV), ea.to(DEV), pos.to(DEV), True, True)
@@ -471,6 +477,37 @@ def test_non_uniform_degree_and_empty_neighbourhoods():
     assert max_abs(x_latent.cpu(), da["x_latent"]) <= rel_tol(da["x_latent"])
     assert max_abs(bip.cpu(), o_bip) <= rel_tol(o_bip)
     assert max_abs(out.cpu(), o) <= rel_tol(o)
+
+
+def test_fp32_kernels_agree_bit_for_bit_across_graph_forms():
+    """The fp32-MFMA stage kernels are walkers over one set of tile pieces (k_stage1<PCSR>, k_stage2<PCSR>): the same graph given as
+    a Cartesian context and as an irregular-product-graph context that lists ALL S G pairs (ordered by source node, then station, so
+    product node p = g S + s in both) gives the same h0, h1 and x_latent bit for bit. The product-level lists are the explicit
+    product edge lists grouped by target in stable edge order: a node's neighbours come in the order of the base lists, and the list
+    order is the summation order. The module routes an all-pairs list to the Cartesian kernels, so the irregular context is built
+    at the engine level. (`bip` is not compared: the station-sum orders of the kernels differ by design and are held to the
+    oracle elsewhere.)"""
+    S, G, geom, A_sta, A_src, Slice, Mask = _ragged_graph_21x40()
+    P = S * G
+    w = Case("odd_33x257").weights
+    ea = torch.from_numpy(geom.edge_attr())
+    sta_csr, src_csr = engine.csr_from_edges(A_sta, S), engine.csr_from_edges(A_src, G)
+    A_in_sta, A_in_src, _, A_src_in_sta = graph.cartesian_product_edges(A_sta, A_src, S, G)
+    assert torch.equal(A_src_in_sta[1] * S + A_src_in_sta[0], torch.arange(P))
+    sub = {"n_prod": P, "sta_csr": engine.csr_from_edges(A_in_sta, P), "src_csr": engine.csr_from_edges(A_in_src, P),
+           "seg_rowptr": torch.arange(G + 1, dtype=torch.int32) * S}
+    # same list order in both forms: station neighbours of (g, s) = those of s inside the rows of g
+    assert torch.equal(sub["sta_csr"][1].long(), (sta_csr[1].long().view(1, -1) + S * torch.arange(G).view(-1, 1)).reshape(-1))
+    res = []
+    for subgraph in (None, sub):
+        hp = engine.HipPath(S, G, sta_csr, src_csr, device=DEV, subgraph=subgraph, stage_precision="f32")
+        assert (hp._n_prod is not None) == (subgraph is not None)
+        hp.set_weights({k: v.to(DEV) for k, v in w.items()})
+        _, _, h0, h1 = hp.da_stage1(Slice.to(DEV), Mask.to(DEV), debug=True)
+        x_latent, _ = hp.da_stage2_bipartite(Mask.to(DEV), ea.to(DEV), want_x_latent=True)
+        res.append({"h0": h0.cpu(), "h1": h1.cpu(), "x_latent": x_latent.cpu()})
+    for k in ("h0", "h1", "x_latent"):
+        assert torch.equal(res[0][k], res[1][k]), (k, max_abs(res[0][k], res[1][k]))
 
 
 def test_bitwise_deterministic_and_order_independent():
@@ -489,8 +526,8 @@ def test_bitwise_deterministic_and_order_independent():
 
 @pytest.mark.parametrize("case", ["cfg1_20x500", "random_50x700"])
 def test_kernel_variants_agree(case, monkeypatch):
-    """The stage kernels exist in two forms: generic CSR fp32-MFMA (any graph; stage_precision="f32" selects them on the reference's kNN
-    graphs too: the A/B reference) and the production pair k_stage1_h2 (two-piece fp16 operands on the matrix pipe) + k_stage2_ord (pipelined,
+    """The stage kernels exist in two forms: generic CSR fp32-MFMA (k_stage1<PCSR = false> + k_stage2<PCSR = false>: any graph;
+    stage_precision="f32" selects them on the reference's kNN graphs too: the A/B reference) and the production pair k_stage1_h2 (two-piece fp16 operands on the matrix pipe) + k_stage2_ord (pipelined,
     row-layout loads): another summation order, fp32 tolerance."""
     if case == "cfg1_20x500":
         c = Case(case)
@@ -741,7 +778,7 @@ def test_training_step_of_the_other_model_definitions_matches_oracle_autograd(na
 @pytest.mark.parametrize("stage1", ["default", "f32"])
 def test_training_step_on_an_irregular_product_graph_matches_oracle_autograd(stage1, monkeypatch):
     """`use_subgraph: True` (config.yaml:86): the training step of `forward_fixed_source` on an irregular product graph. Forward = the
-    PCSR stage kernels with the pre-activations kept (k_stage1_h2<.., PCSR> / k_stage1_pcsr, k_stage2_pcsr, per-source-node segment
+    PCSR stage kernels with the pre-activations kept (k_stage1_h2<.., PCSR> / k_stage1<PCSR = true>, k_stage2<PCSR = true>, per-source-node segment
     sums of the messages); backward = k_train_b2<PCSR>, k_train_b1p, k_train_b0<PCSR>: tiles of 16 consecutive product nodes, the
     transposed means over the reversed PRODUCT-level graphs. Outputs equal the eval path and the reference's fixture; every parameter
     gradient equals the oracle's autograd (literal edge-list formulation on the same irregular graph) to 1e-5 of the gradient scale."""
