@@ -125,6 +125,9 @@ SYMBOLS = [
     ("genie_peak_distance", _c.c_int, [_P, _c.c_int, _c.c_int64, _P, _P, _c.c_int, _P, _P]),
     ("genie_band_peaks_count", _c.c_int, [_P, _c.c_int] + [_c.c_int64] * 6 + [_c.c_float, _P, _P, _P]),
     ("genie_band_peaks_fill", _c.c_int, [_P, _c.c_int] + [_c.c_int64] * 6 + [_c.c_float, _P, _P, _P, _P, _P, _P]),
+    ("genie_stream_peaks_carry_bytes", _c.c_size_t, [_c.c_int]),
+    ("genie_stream_peaks_count", _c.c_int, [_P, _c.c_int] + [_c.c_int64] * 4 + [_c.c_float, _P, _P, _P, _P, _P]),
+    ("genie_stream_peaks_fill", _c.c_int, [_P, _c.c_int] + [_c.c_int64] * 4 + [_c.c_float, _P, _P, _P, _P, _P, _P]),
     ("genie_time_groups_scratch_ints", _c.c_int64, [_c.c_int64]),
     ("genie_time_groups", _c.c_int, [_P, _c.c_int64, _c.c_double, _P, _P, _P]),
     ("genie_local_marching_scratch_bytes", _c.c_size_t, [_c.c_int64]),

@@ -1161,7 +1161,8 @@ class OnlineDay(object):
     into chunks: a column's sum is one fp32 running sum over its windows in ascending order in both loops, and a window's read-out does
     not depend on how windows are grouped into batched tails (tests/test_hip_parity.py pins every window of a batched tail, batches of
     1, 3, 8 and 16, bit-equal to the plain forward). Not built (NotImplementedError): a source-node-sharded model, `window_parallel`,
-    `merge="columns"`, more than one leg. Online detection on the closed blocks is the next step."""
+    `merge="columns"`, more than one leg. Detection on the closed blocks as they arrive: `postproc.OnlineDetector`
+    (`det.push(*day.feed(P_chunk, t_now))`)."""
 
     def __init__(self, net, geom, trv_times, tsteps_abs, times=None, t_win=6.0, step_size="half", min_required_picks=1, n_grids=1.0,
                  kernel_sig_t=synthetic.KERNEL_SIG_T, dt_embed=None, max_t=None, tail_batch=16, pairs=None, ring_cols=None, ind_use=None,

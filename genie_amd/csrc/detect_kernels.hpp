@@ -334,3 +334,117 @@ __global__ __launch_bounds__(256) void k_band_peaks(const float* __restrict__ ba
     if (COUNT && lane == 0) counts[row] = (int32_t)total;
     if (__any(any_und) && lane == 0) atomicOr(flag, 1);
 }
+
+// ------------------------------------------------------------------------------------------------
+// (e) Peak candidates of a STREAM of column blocks (`postproc.StreamPeaks`, the online day loop's closed columns): the peaks of
+// k_row_select MODE 1 on the full matrix, found block by block. block [rows, width] (row stride `stride`) holds the global columns
+// [c0, c0 + width) of an axis of n_cols columns; blocks arrive in order and without gaps. The definition is (d)'s: a maximal run of
+// equal values >= thr whose two outer neighbours are lower, reported at (start + end) / 2; a run that holds column 0 or n_cols - 1
+// is no peak. Where (d) has to flag a run that touches an end of its band, the stream carries it: per row, SpCarry is what BpCarry
+// holds wave-uniformly inside one call, kept in device memory from call to call -- `last` the value of column c0 - 1, `start` the
+// GLOBAL column where the run that holds it began, `rise` whether the value before that run was lower (0 if the run holds column
+// 0). Before the first block (c0 == 0) there is no previous column and carry_in is not read.
+// A call decides every run whose end it knows: the runs that end inside the block with their successor in the block (at the END
+// lane, sp_chunk) and the carried run when the block's first value differs from `last` (sp_carried). The carried run's end lane is
+// gone, so lane 0 emits it at rank 0, ahead of everything the block itself yields: a row's columns ascend within a call and
+// from call to call. A run that reaches the block's last column is deferred through the carry -- if that column is n_cols - 1 no
+// later call comes and it is no peak. No flag, no fallback.
+// COUNT reads carry_in, writes carry_out, counts and lowers *bound; FILL reads the same carry_in and writes the triplets at
+// offsets[row] + rank: neither pass reads what the other writes, and both take every decision from sp_carried / sp_chunk.
+// *bound (set to c0 + width by k_stream_bound_init in front of the COUNT launch): no peak a LATER call emits has a column below
+// it. The only peaks of later calls that can lie below c0 + width are those of runs still open at the block's end; such a run
+// [start, e] with e >= c0 + width - 1 is reported at (start + e) / 2 >= (start + c0 + width - 1) / 2, and only if it reaches thr, rose
+// and does not hold column 0: one atomicMin per such row, by lane 0.
+// ------------------------------------------------------------------------------------------------
+constexpr int SP_ROWS_PER_BLOCK = 4;
+struct __attribute__((aligned(16))) SpCarry { float last; int32_t rise; long long start; };
+struct SpGeom { long long width, c0, n_cols; float thr; };
+
+// the run carried into the block, decided by the block's first value
+__device__ __forceinline__ bool sp_carried(const SpGeom& g, const SpCarry& carry, float first, long long* col) {
+    if (g.c0 == 0 || first == carry.last) return false;                        // no previous column / the run goes on
+    *col = (carry.start + g.c0 - 1) / 2;
+    return carry.last >= g.thr && carry.rise != 0 && first < carry.last;
+}
+
+// the runs that end inside the chunk [cc, cc + 64) of the block with their successor in the block; advances the carry
+__device__ __forceinline__ bool sp_chunk(const float* __restrict__ xr, long long cc, int lane, const SpGeom& g, SpCarry& carry,
+                                         long long* col, float* val) {
+    const long long j = cc + lane, gj = g.c0 + j;
+    const bool valid = j < g.width;
+    const float v = valid ? xr[j] : 0.f;
+    float left = __shfl_up(v, 1);
+    if (lane == 0) left = carry.last;
+    float right = __shfl_down(v, 1);
+    if (lane == 63 && j + 1 < g.width) right = xr[j + 1];
+    const bool brk = valid && (gj == 0 || left != v);                          // a run starts here
+    const bool rise = valid && gj > 0 && left < v;
+    const unsigned long long bm = __ballot(brk), rm = __ballot(rise);
+    bool sel = false;
+    if (valid && j < g.width - 1 && right != v && v >= g.thr) {                // the known end of a run that reaches the threshold
+        const unsigned long long below = bm & ((2ull << lane) - 1ull);
+        long long s = carry.start;
+        bool rising = carry.rise != 0;
+        if (below) {
+            const int ls = 63 - __clzll(below);
+            s = g.c0 + cc + ls;
+            rising = (rm >> ls) & 1ull;
+        }
+        sel = rising && right < v;                                             // (`rising` implies s > 0)
+        *col = (s + gj) / 2;
+    }
+    *val = v;
+    const long long rest = g.width - 1 - cc;                                   // the chunk's last valid lane holds the carry's value
+    carry.last = __shfl(v, rest < 63 ? (int)rest : 63);
+    if (bm) {
+        const int ls = 63 - __clzll(bm);
+        carry.start = g.c0 + cc + ls;
+        carry.rise = (int32_t)((rm >> ls) & 1ull);
+    }
+    return sel;
+}
+
+__global__ void k_stream_bound_init(long long* bound, long long value) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *bound = value;
+}
+
+// launched with width >= 1 only
+template <bool COUNT>
+__global__ __launch_bounds__(256) void k_stream_peaks(const float* __restrict__ block, int rows, long long stride, SpGeom g,
+                                                      const SpCarry* __restrict__ carry_in, SpCarry* __restrict__ carry_out,
+                                                      int32_t* __restrict__ counts, long long* bound,
+                                                      const long long* __restrict__ offsets, int32_t* __restrict__ out_row,
+                                                      int32_t* __restrict__ out_col, float* __restrict__ out_val) {
+    const int lane = threadIdx.x & 63;
+    const long long row = (long long)blockIdx.x * SP_ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const float* xr = block + row * stride;
+    const long long base = COUNT ? 0 : offsets[row];
+    SpCarry carry{0.f, 0, 0};
+    if (g.c0 > 0) carry = carry_in[row];
+    long long total = 0;
+    {
+        long long col = 0;
+        if (sp_carried(g, carry, xr[0], &col)) {
+            if (!COUNT && lane == 0) { out_row[base] = (int32_t)row; out_col[base] = (int32_t)col; out_val[base] = carry.last; }
+            total = 1;
+        }
+    }
+    for (long long cc = 0; cc < g.width; cc += 64) {
+        long long col = 0;
+        float val;
+        const bool sel = sp_chunk(xr, cc, lane, g, carry, &col, &val);
+        const unsigned long long b = __ballot(sel);
+        if (!COUNT && sel) {
+            const long long o = base + total + __popcll(b & ((1ull << lane) - 1ull));
+            out_row[o] = (int32_t)row; out_col[o] = (int32_t)col; out_val[o] = val;
+        }
+        total += __popcll(b);
+    }
+    if (COUNT && lane == 0) {
+        counts[row] = (int32_t)total;
+        carry_out[row] = carry;
+        if (g.c0 + g.width < g.n_cols && carry.last >= g.thr && carry.rise != 0 && carry.start > 0)
+            atomicMin((unsigned long long*)bound, (unsigned long long)((carry.start + g.c0 + g.width - 1) / 2));
+    }
+}

@@ -4157,6 +4157,50 @@ int genie_band_peaks_fill(const float* band, int rows, int64_t width, int64_t st
     return GENIE_OK;
 }
 
+namespace {
+const char* stream_peaks_bad(const float* block, int rows, int64_t width, int64_t stride, int64_t c0, int64_t n_cols, const void* carry_in) {
+    if (rows < 0 || width < 0 || n_cols < 0 || n_cols >= (1ll << 31)) return "rows, width >= 0 and 0 <= n_cols < 2^31 required";
+    if (c0 < 0 || width > n_cols || c0 > n_cols - width) return "the block [c0, c0 + width) must lie inside [0, n_cols)";
+    if (width > 1 && stride < width) return "stride >= width required";
+    if (rows > 0 && width > 0 && (!block || !carry_in)) return "null argument";
+    return nullptr;
+}
+}  // namespace
+
+size_t genie_stream_peaks_carry_bytes(int rows) { return rows > 0 ? (size_t)rows * sizeof(SpCarry) : 0; }
+
+int genie_stream_peaks_count(const float* block, int rows, int64_t width, int64_t stride, int64_t c0, int64_t n_cols, float threshold,
+                             const void* carry_in, void* carry_out, int32_t* counts, int64_t* bound, void* stream) {
+    if (const char* bad = stream_peaks_bad(block, rows, width, stride, c0, n_cols, carry_in))
+        return fail(GENIE_ERR_ARG, std::string("genie_stream_peaks_count: ") + bad);
+    if (rows > 0 && width > 0 && (!carry_out || !counts || !bound)) return fail(GENIE_ERR_ARG, "genie_stream_peaks_count: null argument");
+    if (rows == 0 || width == 0) return GENIE_OK;                         // nothing arrived: the carry and the bound stay as they are
+    const SpGeom g{(long long)width, (long long)c0, (long long)n_cols, threshold};
+    const int nb = (rows + SP_ROWS_PER_BLOCK - 1) / SP_ROWS_PER_BLOCK;
+    hipStream_t st = (hipStream_t)stream;
+    k_stream_bound_init<<<1, 64, 0, st>>>((long long*)bound, (long long)(c0 + width));
+    k_stream_peaks<true><<<nb, 256, 0, st>>>(block, rows, (long long)stride, g, (const SpCarry*)carry_in, (SpCarry*)carry_out, counts,
+                                             (long long*)bound, nullptr, nullptr, nullptr, nullptr);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+int genie_stream_peaks_fill(const float* block, int rows, int64_t width, int64_t stride, int64_t c0, int64_t n_cols, float threshold,
+                            const void* carry_in, const int64_t* offsets, int32_t* out_row, int32_t* out_col, float* out_val,
+                            void* stream) {
+    if (const char* bad = stream_peaks_bad(block, rows, width, stride, c0, n_cols, carry_in))
+        return fail(GENIE_ERR_ARG, std::string("genie_stream_peaks_fill: ") + bad);
+    if (rows > 0 && width > 0 && (!offsets || !out_row || !out_col || !out_val))
+        return fail(GENIE_ERR_ARG, "genie_stream_peaks_fill: null argument");
+    if (rows == 0 || width == 0) return GENIE_OK;
+    const SpGeom g{(long long)width, (long long)c0, (long long)n_cols, threshold};
+    const int nb = (rows + SP_ROWS_PER_BLOCK - 1) / SP_ROWS_PER_BLOCK;
+    k_stream_peaks<false><<<nb, 256, 0, (hipStream_t)stream>>>(block, rows, (long long)stride, g, (const SpCarry*)carry_in, nullptr, nullptr,
+                                                              nullptr, (const long long*)offsets, out_row, out_col, out_val);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
 int64_t genie_time_groups_scratch_ints(int64_t n) { return n > 0 ? (n + TG_BLOCK - 1) / TG_BLOCK : 0; }
 
 int genie_time_groups(const double* t, int64_t n, double break_win, int32_t* scratch, int32_t* group, void* stream) {

@@ -18,6 +18,9 @@ What runs where:
 * `detect_sources_banded` is `detect_sources_device` for a window-parallel day that keeps `Out_2` in column bands (`apply.BandedOut2`):
   the candidates per band (`genie_band_peaks_*`), one all-gather of the triplets, the other stages replicated; `row_select` on the
   full matrix is the oracle of the band kernel (equal triplets).
+* `OnlineDetector` is `detect_sources_device` for an `Out_2` that arrives in blocks of closed columns (`apply.OnlineDay`): the
+  candidates per block with a row's open run carried from block to block (`StreamPeaks`, `genie_stream_peaks_*`), the other stages on
+  finished stretches of the axis (`online_release`); `detect_sources_device` on the whole matrix is its oracle (equal rows).
 * `refine_select_device` is the end of the refine pass per candidate source (process_continuous_days.py:972-978): the sum of the grid
   legs' query read-outs, the region mask and the nested first-maximum argmax in one launch pair (`genie_refine_select`,
   csrc/select_kernels.hpp); the torch statements of `apply.refine_sources` it replaces are its oracle (exact, ties included).
@@ -436,6 +439,193 @@ def detect_sources_banded(banded, X_query, tsteps_abs, ftrns1, thresh, src_t_ker
         keep = _peak_distance_keep(offsets, c, v, distance)
         r, c, v = r[keep], c[keep], v[keep]
     return _sources_from_peaks(r, c, v, X_query, tsteps_abs, ftrns1, break_win, tc_win, sp_win, scale_depth_clustering), info
+
+
+# ------------------------------------------------------------------------------------------------
+# Detection from the closed columns of the online day loop (`apply.OnlineDay.feed` -> `(first_col, block)`), as they arrive.
+# The candidate step carries a row's open run from block to block (genie_stream_peaks_*, csrc/detect_kernels.hpp: every flat top is
+# decided exactly, there is no flag); the distance rule, the time groups and LocalMarching run, with the kernels above, on finished
+# stretches of the axis that `online_release` hands over as soon as nothing later can change them.
+# ------------------------------------------------------------------------------------------------
+class StreamPeaks(object):
+    """The mode-1 candidates of `row_select` on a matrix [rows, n_cols] that arrives in column blocks: owner of the two carry buffers
+    of genie_stream_peaks_count / _fill. `push(first_col, block)` takes the next block (fp32 GPU matrix [rows, width] of the global
+    columns [first_col, first_col + width); rows may be strided, columns not; width 0 is allowed and changes nothing) and returns
+    (row int32, GLOBAL col int32, value fp32, exclusive int64 row offsets), GPU tensors of the kind `band_peaks` returns: every peak
+    whose run ended with this block, among them a run carried in from earlier blocks (first in its row; its midpoint may lie several
+    blocks back). Over all pushes the triplets are those of `row_select(full, threshold, 1)`; within a row the columns ascend, across
+    calls too. `seen`: the next column expected. `bound` (a Python int, read together with the count: one host read per push): no
+    candidate of any later push has a column below it; `n_cols` once the axis has ended."""
+
+    def __init__(self, rows, n_cols, threshold, device):
+        self.rows, self.n_cols = int(rows), int(n_cols)
+        if self.rows < 0 or not 0 <= self.n_cols < 1 << 31:
+            raise ValueError("StreamPeaks: rows >= 0 and 0 <= n_cols < 2**31 required")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("StreamPeaks: a GPU device is required")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        th = np.float32(threshold)                        # `>=` in fp32 as numpy decides it with a float64 threshold (`band_peaks`)
+        if float(th) < float(threshold):
+            th = np.nextafter(th, np.float32(np.inf))
+        self.threshold = float(th)
+        self.seen, self.bound = 0, 0
+        nbytes = max(int(_lib.load().genie_stream_peaks_carry_bytes(self.rows)), 16)
+        self._carry = [torch.zeros(nbytes // 8, dtype=torch.int64, device=self.device) for _ in range(2)]     # [in, out]
+        self._bound = torch.zeros(1, dtype=torch.int64, device=self.device)
+
+    def push(self, first_col, block):
+        if not (torch.is_tensor(block) and block.is_cuda and block.dtype == torch.float32 and block.dim() == 2):
+            raise ValueError("StreamPeaks.push: block must be a 2-D fp32 GPU tensor")
+        if block.device != self.device:
+            raise ValueError("StreamPeaks.push: block is on %s, the stream on %s" % (block.device, self.device))
+        rows, width = int(block.shape[0]), int(block.shape[1])
+        if rows != self.rows:
+            raise ValueError("StreamPeaks.push: block has %d rows, the stream %d" % (rows, self.rows))
+        if int(first_col) != self.seen:
+            raise ValueError("StreamPeaks.push: first_col = %d, but the next column of the stream is %d (blocks arrive in order, without gaps)"
+                             % (int(first_col), self.seen))
+        if self.seen + width > self.n_cols:
+            raise ValueError("StreamPeaks.push: columns [%d, %d) leave the axis of %d columns" % (self.seen, self.seen + width, self.n_cols))
+        if width > 1 and block.stride(1) != 1:
+            raise ValueError("StreamPeaks.push: the columns of block must be contiguous")
+        dev = self.device
+        empty = lambda dt: torch.empty(0, dtype=dt, device=dev)
+        if rows == 0 or width == 0:
+            self.seen += width
+            if rows == 0:
+                self.bound = self.seen
+            return empty(torch.int32), empty(torch.int32), empty(torch.float32), torch.zeros(rows, dtype=torch.int64, device=dev)
+        lib = _lib.load()
+        stride = int(block.stride(0)) if rows > 1 else width
+        geom = (rows, width, stride, self.seen, self.n_cols, ctypes.c_float(self.threshold))
+        carry_in, carry_out = self._carry
+        with torch.cuda.device(dev):
+            st = _stream(dev)
+            counts = torch.empty(rows, dtype=torch.int32, device=dev)
+            _lib.check(lib.genie_stream_peaks_count(_ptr(block), *geom, _ptr(carry_in), _ptr(carry_out), _ptr(counts), _ptr(self._bound), st),
+                       "genie_stream_peaks_count")
+            ends = torch.cumsum(counts.long(), 0)
+            offsets = (ends - counts.long()).contiguous()
+            n, bound = torch.cat((ends[-1:], self._bound)).tolist()          # the one host read of a push
+            out_row = torch.empty(n, dtype=torch.int32, device=dev)
+            out_col = torch.empty(n, dtype=torch.int32, device=dev)
+            out_val = torch.empty(n, dtype=torch.float32, device=dev)
+            if n:
+                _lib.check(lib.genie_stream_peaks_fill(_ptr(block), *geom, _ptr(carry_in), _ptr(offsets), _ptr(out_row), _ptr(out_col),
+                                                       _ptr(out_val), st), "genie_stream_peaks_fill")
+        self._carry = [carry_out, carry_in]               # (FILL has read carry_in on this stream before the next COUNT overwrites it)
+        self.seen += width
+        self.bound = int(bound)
+        return out_row, out_col, out_val, offsets
+
+
+def online_release(cols, bound, tsteps_abs, d, break_win):
+    """How many of the held candidates' columns `cols` (ascending, repeats allowed) are final: the pure host rule of `OnlineDetector`.
+    Let c_1 < ... < c_m be the distinct held columns below `bound` and c_{m+1} = `bound` (no later candidate has a column below it,
+    `StreamPeaks.bound`; a held column at or above the bound waits behind it). A cut after c_i is valid when
+        c_{i+1} - c_i >= d   and   tsteps_abs[c_{i+1}] - tsteps_abs[c_i] >= break_win;
+    with `bound == len(tsteps_abs)` the axis has ended, nothing comes after c_m, and the last cut is always valid. Everything up to the
+    LAST valid cut goes as one unit: returned is the number of entries of `cols` at or before it (0: nothing may go)."""
+    cols = np.asarray(cols, dtype=np.int64).reshape(-1)
+    ts = np.asarray(tsteps_abs, dtype=np.float64)
+    bound, n_cols = int(bound), len(ts)
+    c = np.unique(cols[cols < bound])
+    if c.size == 0:
+        return 0
+    if bound >= n_cols:
+        return int(cols.size)                             # the axis has ended (every column is below n_cols)
+    nxt = np.r_[c[1:], bound]
+    valid = (nxt - c >= int(d)) & (ts[nxt] - ts[c] >= float(break_win))
+    if not valid.any():
+        return 0
+    return int(np.searchsorted(cols, c[np.flatnonzero(valid)[-1]], side="right"))
+
+
+class OnlineDetector(object):
+    """`detect_sources_device` on an `Out_2` that arrives in blocks of closed columns: `det.push(*day.feed(P_chunk, t_now))` returns the
+    sources [n, 5] (float64, sorted by time, possibly none) that became FINAL with this block, `det.finish()` the rest (ValueError
+    unless every column has been pushed). All returns concatenated are the rows `detect_sources_device` finds on the offline `Out_2`,
+    exactly and however the axis is cut into blocks. `held`: the candidates still waiting; `seen`: the next column expected.
+
+    A push runs the streaming candidate kernel on the block (`StreamPeaks`: flat tops across block edges are carried, never flagged),
+    adds the new candidates to the held ones and asks `online_release` for the last valid cut: with d = int(1.5 src_t_kernel / dt_win),
+    a cut between two consecutive distinct candidate columns -- or between the last one and the stream's bound, below which no later
+    candidate can fall -- is valid when they are >= d columns AND >= break_win seconds apart. Everything before the last valid cut is
+    one unit and goes through the offline stages, unchanged: sort by (row, col), row offsets, `_peak_distance_keep`,
+    `_sources_from_peaks`.
+
+    Why the result does not depend on when blocks arrive: (1) the distance rule only ever pairs peaks of a row closer than d columns, so
+    no peak of a unit meets a peak outside it; (2) the time groups are cut on the candidates that SURVIVE the rule, but removing
+    candidates only widens gaps: two candidates that are consecutive before the rule and >= break_win apart (tsteps_abs ascends, so
+    consecutive in column is consecutive in time) separate two groups after it, whatever the rule removes on either side, so no group
+    spans a cut; (3) LocalMarching never leaves a group. Hence the full pipeline on a union of units is the concatenation of the
+    pipeline on each unit, units come out in ascending time, and releasing late only merges units -- the offline call is the one
+    unit of everything.
+
+    Stated limit: candidates that never leave a gap of d columns and break_win seconds are held until `finish()`: memory is bounded by
+    the activity, not by the ring, and `held` shows it. There is no forced flush, because it would break the equality. Besides
+    `StreamPeaks`' one host read per push, a push that found candidates reads their columns (the release rule is host arithmetic)."""
+
+    def __init__(self, X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_win, break_win, tc_win, sp_win, scale_depth_clustering=0.2,
+                 device="cuda"):
+        self.distance = int(1.5 * src_t_kernel / dt_win)
+        if self.distance < 1:
+            raise ValueError("`distance` must be greater or equal to 1")
+        if not thresh > 0.01:
+            raise ValueError("OnlineDetector: thresh must be > 0.01 (the reference's sparsification threshold)")
+        self.tsteps_abs = np.asarray(tsteps_abs, dtype=np.float64).reshape(-1)
+        if self.tsteps_abs.size > 1 and not np.all(self.tsteps_abs[1:] >= self.tsteps_abs[:-1]):
+            raise ValueError("OnlineDetector: tsteps_abs must ascend")
+        self.X_query = np.asarray(X_query, dtype=np.float64)
+        self.n_cols, self.break_win = len(self.tsteps_abs), float(break_win)
+        self._tail = (ftrns1, break_win, tc_win, sp_win, scale_depth_clustering)
+        self.peaks = StreamPeaks(self.X_query.shape[0], self.n_cols, thresh, device)
+        dev = self.peaks.device
+        self._r = torch.empty(0, dtype=torch.int32, device=dev)
+        self._c = torch.empty(0, dtype=torch.int32, device=dev)
+        self._v = torch.empty(0, dtype=torch.float32, device=dev)
+        self._cols = np.zeros(0, dtype=np.int64)          # the held columns on the host, ascending
+
+    @property
+    def seen(self):
+        return self.peaks.seen
+
+    @property
+    def held(self):
+        return int(self._cols.size)
+
+    def _run_unit(self, r, c, v):
+        """The offline stages on one released unit (GPU triplets in any order)."""
+        if r.numel() == 0:
+            return np.zeros((0, 5))
+        order = torch.sort(r.long() * int(self.n_cols) + c.long(), stable=True)[1]
+        r, c, v = r[order].contiguous(), c[order].contiguous(), v[order].contiguous()
+        counts = torch.bincount(r.long(), minlength=self.peaks.rows)
+        offsets = (torch.cumsum(counts, 0) - counts).contiguous()
+        keep = _peak_distance_keep(offsets, c, v, self.distance)
+        return _sources_from_peaks(r[keep], c[keep], v[keep], self.X_query, self.tsteps_abs, *self._tail)
+
+    def push(self, first_col, block):
+        r, c, v, _ = self.peaks.push(first_col, block)
+        if r.numel():
+            self._r, self._c, self._v = torch.cat((self._r, r)), torch.cat((self._c, c)), torch.cat((self._v, v))
+            self._cols = np.sort(np.concatenate((self._cols, c.cpu().numpy().astype(np.int64))), kind="stable")
+        k = online_release(self._cols, self.peaks.bound, self.tsteps_abs, self.distance, self.break_win)
+        if k == 0:
+            return np.zeros((0, 5))
+        go = self._c <= int(self._cols[k - 1])
+        unit = (self._r[go], self._c[go], self._v[go])
+        self._r, self._c, self._v, self._cols = self._r[~go], self._c[~go], self._v[~go], self._cols[k:]
+        return self._run_unit(*unit)
+
+    def finish(self):
+        if self.peaks.seen != self.n_cols:
+            raise ValueError("OnlineDetector.finish: %d of %d columns have been pushed" % (self.peaks.seen, self.n_cols))
+        unit = (self._r, self._c, self._v)
+        self._r, self._c, self._v, self._cols = self._r[:0], self._c[:0], self._v[:0], self._cols[:0]
+        return self._run_unit(*unit)
 
 
 # ------------------------------------------------------------------------------------------------

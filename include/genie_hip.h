@@ -666,6 +666,35 @@ int genie_band_peaks_fill(const float* band, int rows, int64_t width, int64_t st
                           int64_t n_cols, float threshold, const int64_t* offsets, int32_t* out_row, int32_t* out_col, float* out_val,
                           int32_t* flag, void* stream);
 
+/* Peak candidates of a STREAM of column blocks (the closed columns of the online day loop, genie_amd/postproc.py::StreamPeaks,
+ * OnlineDetector): block [rows, width] fp32 with row stride `stride` (elements; columns contiguous) holds the global columns
+ * [c0, c0 + width) of an axis of n_cols columns; the blocks of a stream arrive in order and without gaps, the first with c0 = 0. Over
+ * the whole stream the calls write exactly the mode-1 peaks of the row selection above on the full matrix -- local maxima >= threshold,
+ * flat tops at their midpoint (start + end) / 2, never a run that holds global column 0 or n_cols - 1 -- as triplets (row, GLOBAL column,
+ * value), row-major within a call, a row's columns ascending within a call and from call to call.
+ * The carry: genie_stream_peaks_carry_bytes(rows) bytes per buffer (16 per row, 16-byte aligned), two buffers that the caller swaps
+ * after every COUNT call that launched. Per row it holds the value of column c0 - 1, the global column where the run that holds it
+ * began, and whether the value before that run was lower. carry_in is not read when c0 = 0 (it must still be non-null).
+ * A call decides every run whose end it knows: the runs that end inside the block with their successor in the block, and the carried run
+ * when the block's first value differs from the carried one -- emitted first in its row, at a midpoint that may lie several blocks
+ * back. A run that reaches the block's last column is deferred through the carry (if that column is n_cols - 1 it is no peak). There is no
+ * flag and no fallback: every flat top is decided exactly.
+ * Two passes: genie_stream_peaks_count reads carry_in and writes carry_out, counts [rows] and bound [1]; the caller turns the counts
+ * into exclusive int64 offsets [rows]; genie_stream_peaks_fill reads the SAME carry_in and writes the triplets at offsets[row] + rank
+ * (no atomics on the output; it may be skipped when the total is 0).
+ * bound (int64 [1], written by every COUNT call that launches): no triplet of any LATER call of the stream has a column below it. It is
+ * c0 + width, lowered to (start + c0 + width - 1) / 2 for every row whose run is still open after the block, reaches the threshold,
+ * rose and does not hold column 0 (the smallest midpoint that run can still get); n_cols after the block that ends the axis.
+ * rows = 0 or width = 0: no launch, the carry and the bound stay as they are. Bad arguments (a negative size, n_cols >= 2^31, c0 < 0,
+ * c0 + width > n_cols, width > 1 with stride < width, a null pointer with rows and width positive) return GENIE_ERR_ARG before any
+ * launch. */
+size_t genie_stream_peaks_carry_bytes(int rows);
+int genie_stream_peaks_count(const float* block, int rows, int64_t width, int64_t stride, int64_t c0, int64_t n_cols, float threshold,
+                             const void* carry_in, void* carry_out, int32_t* counts, int64_t* bound, void* stream);
+int genie_stream_peaks_fill(const float* block, int rows, int64_t width, int64_t stride, int64_t c0, int64_t n_cols, float threshold,
+                            const void* carry_in, const int64_t* offsets, int32_t* out_row, int32_t* out_col, float* out_val,
+                            void* stream);
+
 /* The time-pointer tables of the association heads on the device (`assemble_time_pointers_for_stations`, utils.py:602-622, called at
  * train_GENIE_model.py:1364 and process_continuous_days.py:620; genie_amd/graph.py::time_pointers is the host statement): for every
  * station i and every time step t of dt_partition, the k candidates of station i that are smallest under the key
