@@ -504,6 +504,17 @@ __device__ __forceinline__ void mma3(f32x16 (&acc)[N], const f32x4* lw, const in
         for (int k = 0; k < N; ++k) acc[k] = MFMA32H(w[k][WP[t]], b[BP[t]], acc[k]);
 }
 
+#ifndef GENIE_S1_NT_C
+#define GENIE_S1_NT_C 1              // non-temporal stores of c in k_stage1_h2: c is read once, by stage 2, and is as large as wu + wv together;
+#endif                               // stored plainly it shares the 256-MB Infinity Cache with them (k_stage2_h2u 185 -> 175 us at config 2, L2 fills unchanged)
+__device__ __forceinline__ void h2_store_c(f32x4* p, f32x4 v) {
+#if GENIE_S1_NT_C
+    __builtin_nontemporal_store(v, p);
+#else
+    *p = v;
+#endif
+}
+
 template <int KS, int KP, bool EDGES, bool BIG, bool ABS = false, bool PCSR = false>
 __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
     // PCSR: irregular product graph (use_subgraph). A wave item is 32 consecutive product nodes; the neighbours of a node are
@@ -802,7 +813,7 @@ __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
             const long long cs = a.np ? 2 * npl : 8;
 #pragma unroll
             for (int b = 0; b < 4; ++b)
-                *(f32x4*)(cr + b * cs) = f32x4{o3[2][4 * b], o3[2][4 * b + 1], o3[2][4 * b + 2], o3[2][4 * b + 3]};
+                h2_store_c((f32x4*)(cr + b * cs), f32x4{o3[2][4 * b], o3[2][4 * b + 1], o3[2][4 * b + 2], o3[2][4 * b + 3]});
         }
         if (a.save != nullptr && valid) { h2_save32(a.save, a.Pn, SV_UP, p, h, o3[0]); h2_save32(a.save, a.Pn, SV_VP, p, h, o3[1]); }
         o3[0] = prelu16(o3[0], a21, sel21);
@@ -1501,6 +1512,17 @@ constexpr int S2U_GROUP = GENIE_S2U_GROUP; // blocks a workgroup runs in a row f
 // The block table is built by s2u_plan.hpp (host only): blocks, their LDS slot maps and the groups of S2U_GROUP consecutive blocks
 // that a workgroup runs in order for one station tile, so that the union rows two neighbouring blocks share are staged once.
 typedef s2u_plan::Block S2uBlock;
+#ifndef GENIE_S2U_NT_STREAMS
+#define GENIE_S2U_NT_STREAMS 1       // non-temporal loads of the read-once streams (c, message mask, edge fragments) of k_stage2_h2u
+#endif
+template <class P>
+__device__ __forceinline__ auto s2u_stream_load(P p) -> decltype(*p + *p) {
+#if GENIE_S2U_NT_STREAMS
+    return __builtin_nontemporal_load(p);
+#else
+    return *p;
+#endif
+}
 static_assert(s2u_plan::NB == S2U_NB && s2u_plan::UCAP == S2U_UCAP, "s2u_plan.hpp cuts blocks for another kernel shape");
 
 template <bool XL, bool BIG, bool SAVE = false>      // SAVE: training forward (pre-activations of x_latent and of the Bipartite message kept)
@@ -1594,13 +1616,15 @@ __global__ __launch_bounds__(S2U_WPB * 64, GENIE_S2U_BPC) void k_stage2_h2u(DaAr
         const unsigned so = (unsigned)sc * 16u;
         const unsigned lo = kgp + so;
         const unsigned long long cb = s2h_base<BIG>(a.c, g, pc);
-        R.c1 = *(grow)((gbytes)cb + lo);
-        R.c2 = *(grow)((gbytes)cb + (lo + 4u * plane));
+        // c, the message mask and the edge fragments are read exactly once per launch: streamed (GENIE_S2U_NT_STREAMS), so that they
+        // do not push the wu / wv rows, which have 8 and 15 readers, out of the XCD's L2
+        R.c1 = s2u_stream_load((grow)((gbytes)cb + lo));
+        R.c2 = s2u_stream_load((grow)((gbytes)cb + (lo + 4u * plane)));
         const unsigned long long mb = s2h_base<BIG>(a.mm_int, g, pm);
-        R.mq = *(gflt)((gbytes)mb + (unsigned)sc * 4u);
+        R.mq = s2u_stream_load((gflt)((gbytes)mb + (unsigned)sc * 4u));
         if (s >= S) R.mq = 0.f;
         const unsigned long long eb = s2h_base<BIG>(a.ea_frag, g, pe);
-        R.ea = *(gfrag)((gbytes)eb + (kge + so));
+        R.ea = s2u_stream_load((gfrag)((gbytes)eb + (kge + so)));
         const unsigned long long ub = s2h_base<BIG>(a.wu, g, pw);
 #pragma unroll
         for (int k = 0; k < KS; ++k) R.ru[k] = *(grow)((gbytes)ub + ((unsigned)sta[k] * 64u + q16));
