@@ -143,6 +143,9 @@ SYMBOLS = [
                                             _P]),
     ("genie_ring_close", _c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P]),
     ("genie_picks_merge", _c.c_int, [_P, _P, _P, _P, _c.c_int64, _P, _P, _P, _P, _c.c_int64, _P, _P, _P, _P, _P]),
+    ("genie_pick_lists_max_sta", _c.c_int, []),
+    ("genie_pick_lists", _c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int, _c.c_double, _c.c_int, _c.c_double, _c.c_double, _P, _P, _P, _P, _P,
+                                    _P]),
     ("genie_refine_select_scratch_bytes", _c.c_size_t, []),
     ("genie_refine_select", _c.c_int, [_P, _c.c_int, _c.c_int64, _c.c_int, _P, _c.c_float, _P, _P, _P]),
     ("genie_refine_cloud", _c.c_int, [_c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64] + [_c.c_double] * 9 + [_P, _P, _P, _P]),

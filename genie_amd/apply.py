@@ -687,6 +687,27 @@ class ResidentPicks(object):
         order = torch.sort(sta, stable=True)[1]
         return t[order] - float(t0), sta[order].long(), ph[order], idx[order]
 
+    def pick_inputs_device(self, t0, max_t, kernel_sig_t, t_win=10.0):
+        """`pick_inputs` in one launch (genie_pick_lists through `engine.pick_lists`: ball query, counting sort by station and the four
+        lists in one workgroup) instead of a slice, a mask, a `torch.sort`, four gathers and a subtraction: the same four tensors, bit
+        for bit -- `pick_inputs` is its oracle. The number of kept picks is counted on the host from `t_host` with the ball query's own
+        float64 arithmetic, so nothing here waits for the device. A GPU store only; a station set too large for the kernel's LDS
+        table (`engine.pick_lists_max_sta()`) goes through `pick_inputs`."""
+        if self.device.type != "cuda":
+            raise ValueError("pick_inputs_device: the picks live on %s (pick_inputs runs anywhere)" % (self.device,))
+        lo, hi = self.embed_range(t0, max_t, kernel_sig_t)
+        if hi <= lo:
+            f, i = (torch.empty(0, dtype=dt, device=self.device) for dt in (torch.float64, torch.int64))
+            return f, i, f.clone(), i.clone()
+        ball, m = None, hi - lo
+        if 2.0 * float(kernel_sig_t) > float(t_win):
+            ball = (float(t0) + float(max_t) / 2.0, float(t_win) + float(max_t) / 2.0)
+            m = int(np.count_nonzero(np.abs(self.t_host[lo:hi] - ball[0]) <= ball[1]))
+        out = engine.pick_lists((self.t[lo:hi], self.sta[lo:hi], self.phase[lo:hi], self.index[lo:hi]), self.n_sta, float(t0), ball)
+        if out is None:
+            return self.pick_inputs(t0, max_t, kernel_sig_t, t_win)
+        return out[0][:m], out[1][:m], out[2][:m], out[3][:m]
+
     def meta(self, index):
         """`lp_meta` rows (host float64 [m, 5]) of a `pick_inputs` index."""
         return self.P[index.cpu().numpy()]
@@ -936,7 +957,7 @@ def refined_from_found(found, srcs, tq, ftrns2):
 
 def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offset_range, n_rand_query, ftrns1, ftrns2,
                    lat_range, lon_range, depth_range, kernel_sig_t=synthetic.KERNEL_SIG_T, dt_embed=None, rand=None, ftrns2_device=None,
-                   source_parallel=None, merge_timeout=60.0):
+                   source_parallel=None, merge_timeout=60.0, source_offset=0):
     """The refine pass of the caller (process_continuous_days.py:926-980) on the device: for every candidate source `srcs[i]` = (lat, lon,
     depth, origin time, value) a cloud of `n_rand_query` random queries around it (`ftrns1(src) + rand(n, 3) * X_offset_range +
     X_offset_min`, kept where `ftrns2` of it lies strictly inside the three ranges, :929-936), one `forward_fixed_source` per grid
@@ -968,9 +989,16 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
     * group form: one all-gather of the fixed-size rows (`_gather_blocks`; the gloo wait ends after `merge_timeout` seconds), after which
       every rank finishes identically and returns the same (srcs_refined, order) as one GPU.
     A rank whose block is empty runs no window and still takes part in the collective; every rank checks the verdicts of its own
-    contexts. A source-sharded model is refused."""
+    contexts. A source-sharded model is refused.
+
+    `source_offset`: the place of `srcs[0]` in a longer list of which `srcs` is a contiguous part (`OnlineCatalogue` refines a day's
+    sources a few at a time): a keyed draw for local source i uses counter `source_offset + i`, so the part draws the clouds the whole
+    list would have drawn for these sources. A plain callable `rand` has no counter and ignores it; 0 is the whole list."""
     sp = _rank_split(source_parallel, "source_parallel", any(getattr(leg.net, "is_sharded", False) for leg in legs))
     keyed = rand if isinstance(rand, PhiloxCloud) else None
+    source_offset = int(source_offset)
+    if source_offset < 0:
+        raise ValueError("refine_sources: source_offset must be >= 0")
     rand = rand or np.random.rand
     srcs = np.asarray(srcs, dtype=np.float64)
     b_lo, b_hi = 0, srcs.shape[0]
@@ -993,14 +1021,14 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
 
     cloud = (srcs, readouts, len(legs), tq_host.shape[0], X_offset_min, X_offset_range, ftrns1, (lat_range, lon_range, depth_range), dev)
     if ftrns2_device is not None:
-        refine, to_geographic = _refine_on_device_cloud(*cloud, ftrns2_device, n_rand_query, keyed), ftrns2
+        refine, to_geographic = _refine_on_device_cloud(*cloud, ftrns2_device, n_rand_query, keyed, source_offset), ftrns2
     else:
         refine, to_geographic = _refine_on_host_cloud(*cloud, ftrns2), (lambda x: x)       # (its rows are geographic already)
     found = []
     with torch.no_grad():
         if keyed is not None:                  # a draw indexed by source: only the rank's own sources, and no `rand` call at all
             for i in range(b_lo, b_hi):
-                found.append(refine(i, None if ftrns2_device is not None else keyed.host(i, n_rand_query)))
+                found.append(refine(i, None if ftrns2_device is not None else keyed.host(source_offset + i, n_rand_query)))
         else:
             for i in range(srcs.shape[0]):
                 draw = rand(n_rand_query, 3)   # for another rank's source too, so that the stream is the one of one GPU
@@ -1130,6 +1158,74 @@ def online_ring_min(cols, n_cols, tail_batch):
     return int(max(1, online_batch_spans(cols, n_cols, tail_batch).max(initial=1)))
 
 
+def _tq_span(tq):
+    """(tq_lo, tq_hi) = (min(tq, 0), max(tq, 0)) over the time offsets `tq`, float64: a refined time lies in [t_d + tq_lo, t_d + tq_hi]."""
+    tq = np.asarray(tq.detach().cpu() if torch.is_tensor(tq) else tq, dtype=np.float64).reshape(-1)
+    return float(min(tq.min(initial=0.0), 0.0)), float(max(tq.max(initial=0.0), 0.0))
+
+
+def online_source_ready(t_det, t_now, tq, max_t, kernel_sig_t):
+    """Boolean [n]: the detected sources (origin times `t_det`) whose refine AND association passes read nothing that can still arrive,
+    under the promise of `online_ready` (every pick with `t < t_now` has been fed). The refine pass embeds the window that starts at
+    `t_det`, the association pass the one that starts at the refined time `t_r = t_det + tq[j]` for a j not known beforehand; both
+    read `t0 - 2 sigma < t < t0 + max_t + 2 sigma`, strict. The latest upper bound is the one of `t0 = t_det + tq_hi`, so the source is
+    ready when `t_det + tq_hi + max_t + 2 sigma <= t_now` (equality allowed: the bound is strict). Evaluated in the operation order of
+    `picks_in_embed_range`, so that float rounding cannot put a read bound above the tested one (rounding is monotonic)."""
+    t_det = np.asarray(t_det, dtype=np.float64)
+    return (t_det + _tq_span(tq)[1]) + max_t + 2.0 * kernel_sig_t <= t_now
+
+
+def online_t_low(pending_t, held_cols, bound, closed, tsteps_abs):
+    """`T_low`: no source that has not run yet -- released and waiting, or still to be detected -- has an origin time below it. The
+    minimum of the waiting sources' times `pending_t`, the times of the detector's held candidate columns `held_cols`, T(`bound`)
+    (`StreamPeaks.bound`: no later candidate falls below it) and T(`closed`) (the columns still open in the day's ring), with
+    T(c) = tsteps_abs[c] and T(len(tsteps_abs)) = +inf. +inf when nothing is left."""
+    ts = np.asarray(tsteps_abs, dtype=np.float64).reshape(-1)
+    at = lambda c: float(ts[int(c)]) if int(c) < len(ts) else np.inf
+    pending_t, held_cols = np.asarray(pending_t, dtype=np.float64).reshape(-1), np.asarray(held_cols).reshape(-1)
+    return min(pending_t.min(initial=np.inf), at(held_cols.min()) if held_cols.size else np.inf, at(bound), at(closed))
+
+
+def online_retain_from(pending_t, held_cols, bound, closed, tsteps_abs, tq, kernel_sig_t):
+    """The time from which the pick store must keep everything (`OnlineDay.retain_from`) for the sources that have not run yet: a
+    source at `t_d >= T_low` (`online_t_low`) is refined on `t > t_d - 2 sigma` and associated on `t > t_r - 2 sigma` with
+    `t_r >= t_d + tq_lo`, so every pick with `t > T_low + tq_lo - 2 sigma` stays. Evaluated as `(T_low + tq_lo) - 2 sigma`, which no
+    read bound `t0 - 2 sigma` with `t0 >= T_low + tq_lo` falls below."""
+    return (online_t_low(pending_t, held_cols, bound, closed, tsteps_abs) + _tq_span(tq)[0]) - 2.0 * kernel_sig_t
+
+
+def online_marching_final(t_refined, t_low, tq, tc_win):
+    """How many of the refined sources (refined times `t_refined`, ASCENDING) have their verdict of the second LocalMarching fixed:
+    the marching (`n_steps_max = 2`) lets a source see the refined sources within two hops, a hop spans at most `tc_win` in refined
+    time, and every source not refined yet will have `t_r >= t_low + tq_lo` (`t_low` = `online_t_low` over everything not refined).
+    Source i is final when `t_refined[i] + 2 tc_win < t_low + tq_lo`; these are a prefix, whose length is returned."""
+    t_refined = np.asarray(t_refined, dtype=np.float64).reshape(-1)
+    return int(np.searchsorted(t_refined + 2.0 * float(tc_win), t_low + _tq_span(tq)[0], side="left"))
+
+
+def online_marching_verdicts(decided, rows, t_low, tq, tc_win, keep_flags):
+    """One step of the second LocalMarching as the refined sources arrive. `rows` [n, 5]: the refined sources without a verdict,
+    ASCENDING in refined time; `decided` [m, 5]: sources with a verdict (kept or not) that an undecided one may still reach; `t_low`:
+    `online_t_low` over everything not refined yet; `keep_flags(srcs)` -> bool [len(srcs)]: the marching of the caller's choice
+    (`n_steps_max = 2, use_directed = False`; `postproc.local_marching_keep_device`, or the host `postproc.local_marching`).
+    The first `online_marching_final(...)` rows are final. Their verdicts are read from ONE marching over `decided` within `2 tc_win` of
+    `rows[0]` plus all of `rows`: a final row's two-hop neighbourhood lies within `2 tc_win` of it, hence at or above
+    `rows[0] - 2 tc_win` (every earlier source is in `decided`) and below every source still to come (all of it is in `rows`), and
+    every edge among those nodes is present, so the row sees what it sees in the whole day's list. Returns (keep bool [n_final],
+    the new `decided`): the final rows join `decided`, which is then cut to what the earliest source without a verdict -- `rows`'
+    next one, or one still to come at `t_low + tq_lo` or later -- can reach."""
+    rows, decided = np.asarray(rows, dtype=np.float64).reshape(-1, 5), np.asarray(decided, dtype=np.float64).reshape(-1, 5)
+    n_final = online_marching_final(rows[:, 3], t_low, tq, tc_win)
+    if n_final == 0:
+        return np.zeros(0, dtype=bool), decided
+    reach = 2.0 * float(tc_win)
+    near = decided[decided[:, 3] >= rows[0, 3] - reach]
+    keep = np.asarray(keep_flags(np.concatenate((near, rows))), dtype=bool)[len(near):len(near) + n_final]
+    decided = np.concatenate((near, rows[:n_final]))
+    first = min(rows[n_final, 3] if n_final < len(rows) else np.inf, t_low + _tq_span(tq)[0])
+    return keep, decided[decided[:, 3] >= first - reach]
+
+
 class OnlineDay(object):
     """The day's apply loop fed as the picks arrive: `feed(P_chunk, t_now)` runs every window that has become ready and returns the
     columns of `Out_2` that closed, `(first_col, block [Q, n] float32 on the device)` with n possibly 0 -- the shape
@@ -1154,6 +1250,10 @@ class OnlineDay(object):
     each batch the columns no unrun window lists (`online_frontiers`) leave the ring (genie_ring_close). Then the store's `frozen_t`
     moves to the first time the next unrun window reads and the store is trimmed to it: a later pick older than that raises ValueError
     in `feed` (nothing changes; feed on). One synchronisation per `feed`, then the model's verdicts (`_check_verdicts`).
+    `retain_from` (an attribute, default +inf: no effect): `feed` trims to the earlier of that first read time and `retain_from`, so a
+    reader behind the windows (`OnlineCatalogue`: the refine and association passes of sources not yet run) sets, BEFORE each `feed`,
+    the time from which it still needs picks -- and then picks are stored after the last window has run, too; `frozen_t` does not
+    depend on it.
     `ring_cols`: default `online_ring_min` of the schedule, the least that can never alias; a smaller value raises ValueError.
 
     Equality contract: with the same `tsteps_abs`, `times` and options the blocks, concatenated, are the `Out_2` of
@@ -1209,6 +1309,7 @@ class OnlineDay(object):
                                use_phase_types=getattr(model, "use_phase_types", True))
         self.dt_embed = _dt_embed(kernel_sig_t, dt_embed)
         self.t_now = -np.inf
+        self.retain_from = np.inf                 # `feed` keeps every pick with t >= this, whatever the windows still read
         self.n_run = 0                            # candidate windows run so far (dropped ones included): the next one's index
         self.closed = 0                           # columns returned so far
         self.last_col = -1                        # the last column any window has fed
@@ -1238,8 +1339,8 @@ class OnlineDay(object):
         net, n, first_col, blocks = self.lane.net, len(self.times), self.closed, []
         if net.window_batch != self.tail_batch:
             raise RuntimeError("OnlineDay.feed: the model's window_batch was changed to %d (this loop set %d)" % (net.window_batch, self.tail_batch))
-        if P_chunk is not None and self.n_run < n:           # (after the last window nothing reads a pick)
-            self.picks.append(P_chunk)                       # a pick older than frozen_t raises here, before anything has changed
+        if P_chunk is not None and (self.n_run < n or self.retain_from < np.inf):      # (after the last window only a reader behind
+            self.picks.append(P_chunk)                       # the windows, `retain_from`, reads a pick) a pick older than frozen_t raises here
         self.t_now = t_now
         ready = online_ready(self.times[self.n_run:], t_now, self.max_t, self.kernel_sig_t, self.t_win)
         end = self.n_run + (int(np.argmin(ready)) if not ready.all() else len(ready))        # ascending times: the ready ones are a prefix
@@ -1274,7 +1375,7 @@ class OnlineDay(object):
         first_read = online_read_bounds(self.times[self.n_run:self.n_run + 1], self.max_t, self.kernel_sig_t, self.t_win)[0]
         first_read = float(first_read[0]) if self.n_run < n else np.inf
         self.picks.frozen_t = min(first_read, t_now)         # (a pick from t_now on that no window reads any more is not late: it is trimmed)
-        self.picks.trim(np.nextafter(first_read, -np.inf))
+        self.picks.trim(np.nextafter(min(first_read, self.retain_from), -np.inf))
         return first_col, block
 
     def _add(self, xs, ws):
@@ -1299,10 +1400,10 @@ def _inside_region(X, ranges):
 
 
 def _refine_on_device_cloud(srcs, readouts, n_legs, n_t, X_offset_min, X_offset_range, ftrns1, ranges, dev, ftrns2_device, n_rand_query,
-                            keyed=None):
+                            keyed=None, source_offset=0):
     """`refine(i, draw)` of `refine_sources(ftrns2_device=...)`: source i's row float64 [7] on the device = (query row, offset index,
     value, any query inside the region, the refined query's CARTESIAN position), from its draw `rand(n_rand_query, 3)` -- or, with
-    `keyed` (a `PhiloxCloud`), from the cloud one kernel draws on the device (`draw` is then None)."""
+    `keyed` (a `PhiloxCloud`), from the cloud one kernel draws on the device for counter `source_offset + i` (`draw` is then None)."""
     from . import postproc
     if int(n_rand_query) < 1:
         raise ValueError("refine_sources: n_rand_query must be >= 1")
@@ -1337,7 +1438,7 @@ def _refine_on_device_cloud(srcs, readouts, n_legs, n_t, X_offset_min, X_offset_
         # source i + 1's cloud while the GPU works on source i. A keyed draw has no host part at all: one launch makes the cloud's
         # float64 and float32 forms from (key, i), with no pinned pair, no copy and no event.
         if keyed is not None:
-            Xc_d, xq = postproc.refine_cloud_device(keyed.key, i, n_rand_query, src_cart[i], off_rng, off_min, dev)     # :929, :934
+            Xc_d, xq = postproc.refine_cloud_device(keyed.key, source_offset + i, n_rand_query, src_cart[i], off_rng, off_min, dev)     # :929, :934
         else:
             Xc_d, xq = staged_cloud(i, draw)
         keep = _inside_region(ftrns2_device(Xc_d), ranges)
@@ -1372,7 +1473,7 @@ def _refine_on_host_cloud(srcs, readouts, n_legs, n_t, X_offset_min, X_offset_ra
 
 
 def associate_sources(legs, picks, srcs_refined, locs_cart, tq, max_t, trv_out_srcs, ftrns1, x_save, kernel_sig_t=synthetic.KERNEL_SIG_T,
-                      dt_embed=None, t_win=10.0, source_parallel=None):
+                      dt_embed=None, t_win=10.0, source_parallel=None, pick_lists="torch"):
     """The association pass of the caller (process_continuous_days.py:1020-1065) on the device: for every refined source one 4-output
     `forward_fixed` per grid leg on the window that starts at its origin time, with the window's pick lists (`ResidentPicks.pick_inputs`
     = extract_pick_inputs_from_data), ONE spatial query `x_save` (lat, lon of the first node of the reference's coarse map; its depth
@@ -1385,7 +1486,12 @@ def associate_sources(legs, picks, srcs_refined, locs_cart, tq, max_t, trv_out_s
     `Save_picks` and `lp_meta` depend on the picks alone, so every rank makes them for ALL sources itself, without a collective.
     * tuple form: returns (Out_p, Out_s of this rank's block only, Save_picks, lp_meta of all sources, (lo, hi)).
     * group form: one `all_gather_object` of the blocks' ragged likelihoods through the host (a few thousand floats per source; an
-      RCCL group carries them as byte tensors on the current device); every rank returns the four full lists of one GPU."""
+      RCCL group carries them as byte tensors on the current device); every rank returns the four full lists of one GPU.
+
+    `pick_lists`: "torch" (default) makes a window's pick lists with `picks.pick_inputs`, "device" with `picks.pick_inputs_device`
+    (one launch per source, genie_pick_lists); the lists are the same bit for bit."""
+    if pick_lists not in ("torch", "device"):
+        raise ValueError('associate_sources: pick_lists must be "torch" or "device"')
     sp = _rank_split(source_parallel, "source_parallel", any(getattr(leg.net, "is_sharded", False) for leg in legs))
     srcs = np.asarray(srcs_refined, dtype=np.float64)
     b_lo, b_hi = window_blocks(srcs.shape[0], sp.world)[sp.rank] if sp is not None else (0, srcs.shape[0])
@@ -1403,9 +1509,10 @@ def associate_sources(legs, picks, srcs_refined, locs_cart, tq, max_t, trv_out_s
     xs_all[: srcs.shape[0], 2] = srcs[:, 2]                                                                          # :1046
     xs_cart_all = torch.from_numpy(np.ascontiguousarray(ftrns1(xs_all))).float().to(dev)
     src_cart_all = torch.from_numpy(np.ascontiguousarray(ftrns1(srcs[:, 0:3]))).float().to(dev) if srcs.shape[0] else None
+    pick_inputs = picks.pick_inputs_device if pick_lists == "device" else picks.pick_inputs
     with torch.no_grad():
         for i in range(srcs.shape[0]):
-            tp, ip, ph, idx = picks.pick_inputs(srcs[i, 3], max_t, kernel_sig_t, t_win)
+            tp, ip, ph, idx = pick_inputs(srcs[i, 3], max_t, kernel_sig_t, t_win)
             Save_picks.append((tp, ip))
             lp_meta.append(idx)
             if not b_lo <= i < b_hi:           # another rank's source: its pick lists only
@@ -1526,3 +1633,137 @@ def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, 
     return dict({"srcs": srcs, "srcs_refined": srcs_kept[order], "trv_out_srcs": trv_kept[torch.as_tensor(order, device=trv_kept.device)],
                  "Out_p_save": [Out_p[j] for j in pick], "Out_s_save": [Out_s[j] for j in pick],
                  "Save_picks": [Save_picks[j] for j in pick], "lp_meta": [lp_meta[j] for j in pick]}, **detect_info)
+
+
+# ---- the online catalogue: released sources refined and associated as they arrive ---------------------------------
+
+class OnlineCatalogue(object):
+    """The last two stages of the online day: `push(P_chunk, t_now)` feeds the day (`OnlineDay.feed`), detects on the closed columns
+    (`OnlineDetector.push`), runs every released source whose reads are complete through `refine_sources` and `associate_sources` on the
+    day's `PickStore`, and returns the sources whose verdict of the second LocalMarching has become final -- a dict with the keys of
+    `detect_refine_associate`: `srcs` (the detections RELEASED in this call, [n, 5]), and for the sources that became FINAL in this
+    call and survive the marching, in refined-time order: `srcs_refined` [m, 5], `trv_out_srcs` (device [m, S, 2]; [0, S, 2] when
+    none), `Out_p_save`, `Out_s_save` (lists of device tensors), `Save_picks`, `lp_meta` (lists of host arrays). `finish()` does the
+    same for everything left. `pending`: sources released but not run; `undecided`: sources refined but not final.
+
+    Equality contract: with `day` and `det` built on the same axis and options as the offline calls, all returns concatenated are the
+    dict of `apply_windows_device(stack_on_device=True)` -> `detect_refine_associate(detect_on_device=True, rand=PhiloxCloud(key),
+    ftrns2_device=...)` BIT FOR BIT, however the picks are cut into chunks (refined times distinct, as the offline sorts assume).
+    Why, rule by rule:
+    1. a source at `t_d` is refined on `t_d - 2 sigma < t < t_d + max_t + 2 sigma` and associated on the same range around
+       `t_r = t_d + tq[j]`, whatever else the day holds; its cloud is keyed by its place in the day's detection list, which is the
+       running count of released sources (`refine_sources(source_offset=...)`: units come out in ascending time);
+    2. it runs once `online_source_ready` says nothing it reads can still arrive -- possibly pushes after its release;
+    3. BEFORE each `day.feed`, `day.retain_from = online_retain_from(...)` keeps the picks every source not yet run can read;
+       `lp_meta` is read inside the association call, before any later trim;
+    4. the second LocalMarching (`n_steps_max = 2`) reaches two hops of at most `tc_win` each, so a refined source further than
+       `2 tc_win` below every refined time still to come is final (`online_marching_final`). The verdicts are taken from
+       `postproc.local_marching_keep_device` on the undecided sources plus the decided ones within `2 tc_win` of the earliest
+       undecided one. A survivor is a row of the input, so the match back to the refined list is the row's own index: for distinct
+       rows that is the nearest-neighbour (cKDTree) match of `retained_after_marching`, whose nearest row of a row is itself;
+    5. `trv(locs, srcs)` is called on the few sources of a push, offline on all of them at once: THE CALLABLE'S ROWS MUST NOT DEPEND ON
+       THE BATCH (row i a function of `srcs[i]` alone, bit for bit), as the straight-ray callable of `synthetic.Geometry` is.
+
+    `rand` must be a `PhiloxCloud` and `ftrns2_device` must be given (ValueError): a stateful draw or the host cloud has no offline twin
+    that a sub-list reproduces. `pick_lists`: how the association pass makes its pick lists (`associate_sources`; "device" here, one launch per source: at the
+    few hundred picks of a window it takes about half the time of the torch statements, profiles/EXPERIMENTS.md). There is no
+    `source_parallel`: a push carries a few sources. Every block of `day` must go through this object (a `day.feed` of the caller's
+    own loses columns: ValueError at the next call, nothing changed)."""
+
+    def __init__(self, day, det, locs, trv, tq, ftrns1, ftrns2, lat_range, lon_range, depth_range, X_offset_min, X_offset_range,
+                 n_rand_query, tc_win, sp_win, scale_depth_clustering=0.2, t_win_assoc=10.0, rand=None, ftrns2_device=None,
+                 pick_lists="device"):
+        if not isinstance(rand, PhiloxCloud):
+            raise ValueError("OnlineCatalogue: rand must be a PhiloxCloud (a source's draw must not depend on when it runs)")
+        if ftrns2_device is None:
+            raise ValueError("OnlineCatalogue: ftrns2_device is required (the keyed cloud is drawn on the device)")
+        if pick_lists not in ("torch", "device"):
+            raise ValueError('OnlineCatalogue: pick_lists must be "torch" or "device"')
+        if len(det.tsteps_abs) != len(day.tsteps_abs) or not np.array_equal(det.tsteps_abs, day.tsteps_abs):
+            raise ValueError("OnlineCatalogue: day and det must share one tsteps_abs")
+        self.day, self.det, self.leg = day, det, day.lane
+        self.trv, self.ftrns1, self.ftrns2, self.ftrns2_device, self.rand = trv, ftrns1, ftrns2, ftrns2_device, rand
+        self.tq = np.asarray(tq.detach().cpu() if torch.is_tensor(tq) else tq, dtype=np.float64).reshape(-1)
+        self.ranges = (lat_range, lon_range, depth_range)
+        self.offsets = (X_offset_min, X_offset_range)
+        self.n_rand_query, self.tc_win, self.sp_win = n_rand_query, float(tc_win), float(sp_win)
+        self.scale_depth_clustering, self.t_win_assoc, self.pick_lists = scale_depth_clustering, t_win_assoc, pick_lists
+        locs = np.asarray(locs, dtype=np.float64)
+        self.locs_cart = ftrns1(locs)
+        self.locs_d = torch.as_tensor(locs).float().to(self.leg.device)
+        self.x_save = np.array([lat_range[0], lon_range[0], 0.0])                 # as `detect_refine_associate` takes it
+        self.n_released = 0                       # sources released so far: the next one's place in the day's detection list
+        self._pending = np.zeros((0, 5))          # released, not run (ascending origin time)
+        self._rows = np.zeros((0, 5))             # refined, not final (ascending refined time), with their results in step:
+        self._results = []                        #   (trv row, Out_p, Out_s, Save_picks, lp_meta) per row of `_rows`
+        self._decided = np.zeros((0, 5))          # final rows, kept or not, that an undecided source may still reach
+
+    pending = property(lambda self: int(self._pending.shape[0]))
+    undecided = property(lambda self: int(self._rows.shape[0]))
+
+    def _t_low(self):
+        return online_t_low(self._pending[:, 3], self.det.held_cols, self.det.peaks.bound, self.day.closed, self.day.tsteps_abs)
+
+    def _run(self, srcs):
+        """Refine and associate the sources `srcs` (the head of `_pending`), and file the results by refined time."""
+        day, legs = self.day, [self.leg]
+        rows, _ = refine_sources(legs, day.picks, srcs, self.locs_cart, self.tq, day.max_t, self.offsets[0], self.offsets[1],
+                                 self.n_rand_query, self.ftrns1, self.ftrns2, *self.ranges, day.kernel_sig_t, day.dt_embed, self.rand,
+                                 self.ftrns2_device, source_offset=self.n_released - self._pending.shape[0])
+        dev = self.leg.device
+        with torch.no_grad():
+            trv_out = self.trv(self.locs_d, torch.as_tensor(rows[:, 0:3]).float().to(dev)).detach()
+        res = associate_sources(legs, day.picks, rows, self.locs_cart, self.tq, day.max_t, trv_out, self.ftrns1, self.x_save,
+                                day.kernel_sig_t, day.dt_embed, self.t_win_assoc, pick_lists=self.pick_lists)
+        results = self._results + [(trv_out[i],) + tuple(r[i] for r in res) for i in range(rows.shape[0])]
+        rows = np.concatenate((self._rows, rows))
+        order = np.argsort(rows[:, 3], kind="stable")
+        self._rows, self._results = rows[order], [results[i] for i in order]
+
+    def _final(self):
+        """Take the sources whose marching verdict is final out of the undecided ones; returns the kept ones' (rows, results)."""
+        from . import postproc
+        march = lambda srcs: postproc.local_marching_keep_device(srcs, self.ftrns1, tc_win=self.tc_win, sp_win=self.sp_win, n_steps_max=2,
+                                                                 scale_depth=self.scale_depth_clustering, use_directed=False,
+                                                                 device=self.leg.device)
+        keep, self._decided = online_marching_verdicts(self._decided, self._rows, self._t_low(), self.tq, self.tc_win, march)
+        n = len(keep)
+        rows, results = self._rows[:n][keep], [r for r, k in zip(self._results[:n], keep) if k]
+        self._rows, self._results = self._rows[n:], self._results[n:]
+        return rows, results
+
+    def _step(self, P_chunk, t_now, last):
+        day, det = self.day, self.det
+        if det.seen != day.closed:
+            raise ValueError("OnlineCatalogue: the detector has seen %d columns, the day has closed %d (every block of the day goes "
+                             "through this object)" % (det.seen, day.closed))
+        day.retain_from = online_retain_from(self._pending[:, 3], det.held_cols, det.peaks.bound, day.closed, day.tsteps_abs, self.tq,
+                                             day.kernel_sig_t)
+        srcs = det.push(*day.feed(P_chunk, t_now))
+        if last:
+            srcs = np.concatenate((srcs, det.finish()))
+        self.n_released += srcs.shape[0]
+        self._pending = np.concatenate((self._pending, srcs))
+        ready = online_source_ready(self._pending[:, 3], day.t_now, self.tq, day.max_t, day.kernel_sig_t)
+        n_ready = int(np.argmin(ready)) if not ready.all() else len(ready)        # ascending times: the ready ones are a prefix
+        if n_ready:
+            self._run(self._pending[:n_ready])
+            self._pending = self._pending[n_ready:]
+        rows, results = self._final()
+        if last:                                  # nothing reads a pick any more
+            day.retain_from = np.inf
+            day.picks.trim(np.inf)
+        self.leg.check()
+        n_sta = int(self.locs_d.shape[0])
+        return {"srcs": srcs, "srcs_refined": rows,
+                "trv_out_srcs": torch.stack([r[0] for r in results]) if results else torch.zeros((0, n_sta, 2), device=self.leg.device),
+                "Out_p_save": [r[1] for r in results], "Out_s_save": [r[2] for r in results],
+                "Save_picks": [r[3] for r in results], "lp_meta": [r[4] for r in results]}
+
+    def push(self, P_chunk, t_now):
+        return self._step(P_chunk, t_now, False)
+
+    def finish(self):
+        """Everything left: the day's last windows, the detector's last unit, every waiting source, every verdict. Raises as
+        `OnlineDetector.finish` does when the detector has not been given every column."""
+        return self._step(None, np.inf, True)

@@ -4436,6 +4436,23 @@ int genie_picks_merge(const double* t_a, const int32_t* sta_a, const int32_t* ph
     return GENIE_OK;
 }
 
+int genie_pick_lists_max_sta(void) { return PL_MAX_STA; }
+
+int genie_pick_lists(const double* t, const int32_t* sta, const int32_t* phase, const int64_t* index, int64_t n, int n_sta, double t0,
+                     int ball, double centre, double radius, double* tp_out, int64_t* ip_out, double* ph_out, int64_t* idx_out,
+                     int64_t* count_out, void* stream) {
+    if (n < 0 || n >= (1ll << 31)) return fail(GENIE_ERR_ARG, "genie_pick_lists: 0 <= n < 2^31 required");
+    if (n_sta < 1 || n_sta > PL_MAX_STA) return fail(GENIE_ERR_ARG, "genie_pick_lists: 1 <= n_sta <= 8192 required (the LDS station table)");
+    if (!count_out || (n > 0 && (!t || !sta || !phase || !index || !tp_out || !ip_out || !ph_out || !idx_out)))
+        return fail(GENIE_ERR_ARG, "genie_pick_lists: null argument");
+    if (ball && !(dbl_finite(centre) && dbl_finite(radius))) return fail(GENIE_ERR_ARG, "genie_pick_lists: the ball must be finite");
+    k_pick_lists<<<1, PL_BLOCK, 0, (hipStream_t)stream>>>(t, sta, phase, (const long long*)index, (int)n, n_sta, t0, ball ? 1 : 0, centre,
+                                                          radius, tp_out, (long long*)ip_out, ph_out, (long long*)idx_out,
+                                                          (long long*)count_out);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
 size_t genie_refine_select_scratch_bytes(void) { return (size_t)RS_MAX_WG * sizeof(RsPartial); }
 
 int genie_refine_select(const float* const* x, int n_used, int64_t n_query, int n_t, const uint8_t* keep, float n_scale, void* scratch,

@@ -240,6 +240,36 @@ def picks_merge(a, b, out):
     return out
 
 
+def pick_lists_max_sta():
+    """The largest station count `pick_lists` takes (the kernel's LDS station table)."""
+    return int(_lib.load().genie_pick_lists_max_sta())
+
+
+def pick_lists(run, n_sta, t0, ball=None):
+    """The pick lists of one window from a range of a time-sorted store (genie_pick_lists, one launch on the current stream): `run` =
+    (t float64, sta int32, phase int32, index int64) contiguous 1-d GPU tensors of n picks (`PICK_FIELDS`), stations in [0, n_sta);
+    `ball` = (centre, radius) keeps `|t - centre| <= radius` (float64), None keeps everything. The kept picks, stable-sorted by station,
+    go to the head of four new tensors [n]: (tp = t - t0 float64, ip int64, ph float64, idx int64, count int64 [1] on the device);
+    the tails are uninitialised. Returns None when `n_sta` exceeds `pick_lists_max_sta()`: the caller sorts with torch."""
+    n = int(run[0].shape[0])
+    dev = run[0].device
+    for (field, dtype), x in zip(PICK_FIELDS, run):
+        if not (torch.is_tensor(x) and x.is_cuda and x.dtype == dtype and x.dim() == 1 and x.is_contiguous() and x.shape[0] == n
+                and x.device == dev):
+            raise ValueError("pick_lists: %s must be a contiguous %s GPU tensor [%d] on %s" % (field, dtype, n, dev))
+    if not 1 <= int(n_sta) <= pick_lists_max_sta():
+        return None
+    out = (torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int64, device=dev),
+           torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int64, device=dev),
+           torch.empty(1, dtype=torch.int64, device=dev))
+    centre, radius = (float(ball[0]), float(ball[1])) if ball is not None else (0.0, 0.0)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().genie_pick_lists(*[_ptr(x) for x in run], n, int(n_sta), ctypes.c_double(float(t0)), int(ball is not None),
+                                                ctypes.c_double(centre), ctypes.c_double(radius), *[_ptr(x) for x in out], _stream()),
+                   "genie_pick_lists")
+    return out
+
+
 def knn_graph_device(points, k):
     """Base kNN graph of a point set on the device: the layout of `remove_self_loops(knn(x, x, k + 1).flip(0))`
     (process_utils.py:718-719) as (table int32 [n, k], edge list int64 [2, n * k] with row 0 = neighbour, row 1 = centre)."""

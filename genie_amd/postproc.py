@@ -287,9 +287,16 @@ def local_marching_device(srcs, ftrns1, tc_win=5, sp_win=35e3, n_steps_max=100, 
     """`local_marching` with the graph and the march on the device: same arguments, same surviving rows of `srcs` in index order.
     `ftrns1` and the depth scale are applied on the host (one call); nodes are sorted by time on the device and the flags mapped back."""
     srcs = np.asarray(srcs, dtype=np.float64)
+    return srcs[local_marching_keep_device(srcs, ftrns1, tc_win, sp_win, n_steps_max, tol, scale_depth, use_directed, device)]
+
+
+def local_marching_keep_device(srcs, ftrns1, tc_win=5, sp_win=35e3, n_steps_max=100, tol=1e-12, scale_depth=1.0, use_directed=True,
+                               device=None):
+    """The keep flags of `local_marching_device` (host bool [n], in the order of `srcs`): its survivors are `srcs[flags]`."""
+    srcs = np.asarray(srcs, dtype=np.float64)
     n = srcs.shape[0]
     if n == 0:
-        return srcs
+        return np.zeros(0, dtype=bool)
     dev = torch.device("cuda" if device is None else device)
     xs = np.asarray(ftrns1(srcs[:, 0:3]), dtype=np.float64) * np.array([1.0, 1.0, scale_depth]).reshape(1, -1)
     xs_d = torch.from_numpy(np.ascontiguousarray(xs)).to(dev)
@@ -298,7 +305,7 @@ def local_marching_device(srcs, ftrns1, tc_win=5, sp_win=35e3, n_steps_max=100, 
     keep_sorted = _marching_keep(xs_d[order], t_d, val_d[order], None, tc_win, sp_win, n_steps_max, tol, use_directed)
     keep = torch.empty_like(keep_sorted)
     keep[order] = keep_sorted
-    return srcs[keep.cpu().numpy()]
+    return keep.cpu().numpy()
 
 
 def detect_sources_device(Out_2, X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_win, break_win, tc_win, sp_win,
@@ -595,6 +602,11 @@ class OnlineDetector(object):
     @property
     def held(self):
         return int(self._cols.size)
+
+    @property
+    def held_cols(self):
+        """The columns of the held candidates (host int64, ascending, repeats included)."""
+        return self._cols.copy()
 
     def _run_unit(self, r, c, v):
         """The offline stages on one released unit (GPU triplets in any order)."""

@@ -799,6 +799,22 @@ int genie_picks_merge(const double* t_a, const int32_t* sta_a, const int32_t* ph
                       const int32_t* sta_b, const int32_t* phase_b, const int64_t* index_b, int64_t n_b, double* t_out, int32_t* sta_out,
                       int32_t* phase_out, int64_t* index_out, void* stream);
 
+/* The pick lists of one window (apply.ResidentPicks.pick_inputs, extract_pick_inputs_from_data of the reference) in one launch: the n
+ * picks of a contiguous range of the time-sorted store (t fp64, sta int32 in [0, n_sta), phase int32, index int64, on the device), cut by
+ * the ball query when ball != 0 -- kept where fabs(t - centre) <= radius in fp64 -- and stable-sorted by station (a counting sort: within
+ * a station the picks keep the order of the range). Written, for the m kept picks in that order: tp_out = t - t0 (fp64), ip_out = station
+ * (int64), ph_out = phase (fp64), idx_out = index (int64), each with room for n elements (the elements from m on are not touched), and
+ * count_out[0] = m (int64, on the device). One workgroup of 256 threads; the station histogram and its exclusive scan live in LDS, so
+ * n_sta <= genie_pick_lists_max_sta() (8192): a larger station set returns GENIE_ERR_ARG and the caller sorts by other means. Every
+ * output element is written once with a vector store, nothing is atomic in global memory, and the result does not depend on
+ * scheduling. A pick whose station lies outside [0, n_sta) is left out and never used as an index. n == 0 writes count_out[0] = 0 and
+ * may pass null arrays. Bad arguments (n outside [0, 2^31), n_sta outside the table, a null pointer, a ball that is not finite) return
+ * GENIE_ERR_ARG before any launch. */
+int genie_pick_lists_max_sta(void);
+int genie_pick_lists(const double* t, const int32_t* sta, const int32_t* phase, const int64_t* index, int64_t n, int n_sta, double t0,
+                     int ball, double centre, double radius, double* tp_out, int64_t* ip_out, double* ph_out, int64_t* idx_out,
+                     int64_t* count_out, void* stream);
+
 /* Selection of the refined source out of the grid legs' query read-outs (the refine pass, process_continuous_days.py:972-978), one call
  * per candidate source instead of a chain of full passes over [n_query, n_t]:
  *   acc[q, t] = fp32 sum over l = 0..n_used-1, in that order and starting from 0.0f, of x[l][q, t] / n_scale, computed as torch computes
