@@ -363,6 +363,7 @@ __global__ void k_where_am_i(int* __restrict__ out) {
 // of a flat run that is strictly higher than both neighbours, never the first or last sample; then `x >= height`).
 // One workgroup per row, chunks of 256 columns, selected entries written in column order at `offsets[row]` + rank
 // (two passes: COUNT fills counts[row], the caller scans them; the second pass fills) -> row-major order like np.where.
+// MODE 1's definition of a peak is stated once, in detect_kernels.hpp (d), for this kernel and the band / stream kernels there.
 // ------------------------------------------------------------------------------------------------
 template <int MODE, bool COUNT>
 __global__ __launch_bounds__(256) void k_row_select(const float* __restrict__ x, long long cols, float thr, int32_t* __restrict__ counts,

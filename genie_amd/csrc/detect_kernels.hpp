@@ -239,70 +239,152 @@ __global__ __launch_bounds__(256) void k_local_marching_keep(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
-// (d) Peak candidates of a column BAND of Out_2 (`postproc.detect_sources_banded`): what k_row_select MODE 1 finds on the full matrix,
-// restricted to the peaks whose reported column lies in the caller's OWN range [o_lo, o_hi). band [rows, width] (row stride `stride`)
-// holds the global columns [b_lo, b_lo + width) of an axis of n_cols columns. A peak is a maximal run of equal values >= thr whose two
-// outer neighbours are lower, reported at the run's midpoint (start + end) / 2; a run that contains global column 0 or n_cols - 1 has
-// no outer neighbour there and is no peak (scipy `_local_maxima_1d`). The ranks' own ranges partition the axis, so of all the bands
-// that see a run exactly one reports it.
-// A run that touches an end of the band which is not an end of the axis may go on outside: its start (its end) is then only bounded,
-// start in [1, b_lo] (end in [b_hi - 1, n_cols - 2]). If the neighbour on the known side is lower and some admissible midpoint falls
-// into the own range, the band cannot decide the peak: *flag is set and nothing is reported for that run (the caller falls back to the
-// dense merge). If no admissible midpoint is the caller's, the run is another rank's in every case and is passed over in silence (so a rank
-// whose own range is empty reports nothing and never sets the flag).
-// One wave per row walks it in chunks of 64 columns, one coalesced load per chunk; the neighbours come from the adjacent lanes
-// (lane 0's from the chunk before, lane 63's by one load of the next column), a run's start from a ballot of the lanes where the
-// value changes, or from the wave-uniform carry when the run began in an earlier chunk. Peaks are decided at the run's END lane, so
-// they come out in ascending column order. bp_chunk is the one decision both passes make: COUNT adds up its ballots, FILL ranks them.
+// (d) Peak candidates of a SEGMENT of Out_2's columns: what k_row_select MODE 1 finds on the full matrix, found on a piece of it.
+// THE DEFINITION, stated here for all three paths (k_row_select in aux_kernels.hpp follows it on the dense matrix): a peak is a
+// maximal run of equal values >= thr whose two outer neighbours are lower, reported at the run's midpoint (start + end) / 2; a
+// run that holds global column 0 or n_cols - 1 has no outer neighbour there and is no peak (scipy `_local_maxima_1d`). pk_is_peak is
+// that sentence; pk_scan (with pk_load and pk_run_start) is the only code that loads a chunk and that knows how a run's start is found.
+// seg [rows, width] (row stride `stride`) holds the global columns [lo, lo + width) of an axis of n_cols columns. One wave per row
+// walks it in chunks of 64 columns, one coalesced load per chunk, issued one chunk ahead; the neighbours come from the adjacent lanes
+// (lane 0's from the carry, lane 63's by one load of the next column), a run's start from a ballot of the lanes where the value
+// changes, or from the carry when the run began in an earlier chunk. PkCarry is wave-uniform: `last` the value of the column before
+// the chunk, `start` the GLOBAL column where the run that holds it began, `rise` whether the value before that run was lower (0 when
+// unknown: the run holds column 0 or began at a cut left end). Peaks are decided at the run's END lane, in ascending column order.
+// Each kernel loops over chunks: scanner, end policy, emitter; COUNT and FILL differ in pk_emit's stores alone. The end policies:
+// * BAND (`postproc.detect_sources_banded`, k_band_peaks): the segment is a column band [b_lo, b_lo + width) of the finished axis, and
+//   only the peaks whose column lies in the caller's OWN range [o_lo, o_hi) are reported; own ranges partition the axis, so exactly
+//   one band reports a run. The carry lives in registers. A run that touches an end of the band which is not an end of the axis may
+//   go on outside: its start (end) is only bounded, start in [1, b_lo] (end in [b_hi - 1, n_cols - 2]). If the known side is lower
+//   and some admissible midpoint falls into the own range, the band cannot decide: *flag is set and the run not reported (the caller
+//   falls back to the dense merge). If no admissible midpoint is the caller's, the run is another rank's in every case and is passed
+//   over (so a rank whose own range is empty reports nothing and never sets the flag).
+// * STREAM (`postproc.StreamPeaks`, k_stream_peaks): the segment is the next block [c0, c0 + width) of closed columns of the online
+//   day loop; blocks arrive in order and without gaps. Where the band flags, the stream carries: the carry is kept per row in
+//   device memory from call to call (with c0 == 0 carry_in is not read). A call decides every run whose end it knows: those that
+//   end inside the block with their successor in the block (sp_decide) and the carried run when the block's first value differs
+//   from `last` (sp_carried). The carried run's end lane is gone, so lane 0 emits it at rank 0, ahead of everything the block
+//   yields: a row's columns ascend within a call and from call to call. A run that reaches the block's last column is deferred
+//   through the carry -- if that column is n_cols - 1 no later call comes and it is no peak. No flag, no fallback. COUNT reads
+//   carry_in, writes carry_out, counts and lowers *bound; FILL reads the same carry_in: neither pass reads what the other writes.
+//   *bound (set to c0 + width by k_stream_bound_init in front of the COUNT launch): no peak a LATER call emits has a column below
+//   it. Only runs still open at the block's end can yield one below c0 + width; such a run [start, e], e >= c0 + width - 1, is
+//   reported at (start + e) / 2 >= (start + c0 + width - 1) / 2, and only if it reaches thr, rose and does not hold column 0:
+//   one atomicMin per such row, by lane 0.
 // ------------------------------------------------------------------------------------------------
-constexpr int BP_ROWS_PER_BLOCK = 4;
-struct BpGeom { long long width, b_lo, o_lo, o_hi, n_cols; float thr; };
-struct BpCarry { float last; long long start; bool rise; };       // wave-uniform: the previous column's value, the open run's start
+constexpr int PK_ROWS_PER_BLOCK = 4;
+struct __attribute__((aligned(16))) PkCarry { float last; int32_t rise; long long start; };
+static_assert(sizeof(PkCarry) == 16, "genie_stream_peaks_carry_bytes hands this size to the caller");
+struct PkRun {                                            // per lane, of the run that ends at this lane (if one does)
+    bool ends, last_col;                                  // `last_col`: the lane is the segment's last column, `right` is then unknown
+    float v, right;
+    unsigned long long brk, rise; long long lane0; PkCarry open;      // where the run began, read through pk_run_start: the chunk's
+};                                                        // ballots, lane 0's global column, the carry in front of the chunk
 
-__device__ __forceinline__ bool bp_chunk(const float* __restrict__ xr, long long c0, int lane, const BpGeom& g, BpCarry& carry,
-                                         long long* col, float* val, bool* undecided) {
+// a run [start, end] of value v with the neighbours' verdicts `rose` (the left one is lower) and `right`
+__device__ __forceinline__ bool pk_is_peak(float v, float thr, bool rose, float right, long long start, long long end, long long n_cols) {
+    return v >= thr && rose && right < v && start > 0 && end < n_cols - 1;
+}
+
+// a lane's column of the chunk [c0, c0 + 64) of a row of `width` >= 1 columns and the column behind the chunk (lane 63's right neighbour).
+// Unconditional (past the row's end the row's last column is read, and not used) so that the NEXT chunk's loads can stay in flight
+struct PkLoad { float v, next; };
+__device__ __forceinline__ PkLoad pk_load(const float* __restrict__ xr, long long c0, int lane, long long width) {
+    const long long j = c0 + lane, n = c0 + 64;
+    return PkLoad{xr[j < width ? j : width - 1], xr[n < width ? n : width - 1]};
+}
+
+// the chunk [c0, c0 + 64) of the segment [lo, lo + width) in the row xr; advances the carry. `cut_left`: the segment's first column
+// starts a run whatever came before it, and whether that run rose is unknown (it is in any case when the column is global column 0).
+// `ahead` holds this chunk's values (pk_load of chunk 0 first) and leaves with the next chunk's, loading while this one is decided
+__device__ __forceinline__ PkRun pk_scan(const float* __restrict__ xr, long long c0, int lane, long long width, long long lo,
+                                         bool cut_left, PkCarry& carry, PkLoad& ahead) {
     const long long j = c0 + lane;
-    const bool valid = j < g.width;
-    const float v = valid ? xr[j] : 0.f;
+    const bool valid = j < width;
+    const float v = valid ? ahead.v : 0.f, next = ahead.next;
+    ahead = pk_load(xr, c0 + 64, lane, width);
     float left = __shfl_up(v, 1);
     if (lane == 0) left = carry.last;
     float right = __shfl_down(v, 1);
-    if (lane == 63 && j + 1 < g.width) right = xr[j + 1];
-    const bool brk = valid && (j == 0 || left != v);                         // a run starts here
-    const bool rise = valid && j > 0 && left < v;
+    if (lane == 63 && j + 1 < width) right = next;
+    const bool first = j == 0 && (cut_left || lo == 0);                       // no left neighbour
+    const bool brk = valid && (first || left != v);                           // a run starts here
+    const bool rise = valid && !first && left < v;
     const unsigned long long bm = __ballot(brk), rm = __ballot(rise);
-    bool sel = false, und = false;
-    if (valid && v >= g.thr && (j == g.width - 1 || right != v)) {            // the end of a run that reaches the threshold
-        const unsigned long long below = bm & ((2ull << lane) - 1ull);
-        long long s = carry.start;
-        bool rising = carry.rise;
-        if (below) {
-            const int ls = 63 - __clzll(below);
-            s = c0 + ls;
-            rising = (rm >> ls) & 1ull;
-        }
-        const bool left_known = s > 0, right_known = j < g.width - 1;
-        const bool left_ok = left_known ? rising : g.b_lo > 0;                // lower on the left, or possibly so
-        const bool right_ok = right_known ? right < v : g.b_lo + g.width < g.n_cols;
-        if (left_ok && right_ok) {
-            const long long gs = g.b_lo + s, ge = g.b_lo + j;
-            const long long m_lo = ((left_known ? gs : 1) + ge) / 2;          // the admissible midpoints, inclusive
-            const long long m_hi = (gs + (right_known ? ge : g.n_cols - 2)) / 2;
-            const bool mine = g.o_lo < g.o_hi && m_hi >= g.o_lo && m_lo < g.o_hi;    // (an empty own range has no midpoint)
-            sel = mine && left_known && right_known;                           // (then m_lo == m_hi)
-            und = mine && !(left_known && right_known);
-            *col = m_lo;
-        }
-    }
-    *val = v;
-    *undecided = und;
-    carry.last = __shfl(v, 63);
+    const bool last_col = j == width - 1;
+    const PkRun r{valid && (last_col || right != v), last_col, v, right, bm, rm, lo + c0, carry};
+    const long long rest = width - 1 - c0;                                    // the chunk's last valid lane holds the carry's value
+    carry.last = __shfl(v, rest < 63 ? (int)rest : 63);
     if (bm) {
         const int ls = 63 - __clzll(bm);
-        carry.start = c0 + ls;
-        carry.rise = (rm >> ls) & 1ull;
+        carry.start = lo + c0 + ls;
+        carry.rise = (int32_t)((rm >> ls) & 1ull);
     }
+    return r;
+}
+
+// the global start of the run that ends at this lane and whether it rose. The policies ask only at the end of a run that reaches thr:
+// most chunks of a day hold none, and what every chunk executes is what the walk's time is made of
+__device__ __forceinline__ bool pk_run_start(const PkRun& r, int lane, long long* start) {
+    const unsigned long long below = r.brk & ((2ull << lane) - 1ull);         // none: the run began in an earlier chunk
+    const int ls = below ? 63 - __clzll(below) : 0;
+    *start = below ? r.lane0 + ls : r.open.start;
+    return below ? (r.rise >> ls) & 1ull : r.open.rise != 0;
+}
+
+// ranks the wave's selected lanes behind the `total` triplets the row has so far; FILL writes (row, col, val) at base + total + rank
+template <bool COUNT>
+__device__ __forceinline__ void pk_emit(bool sel, int lane, long long row, long long col, float val, long long base, long long& total,
+                                        int32_t* __restrict__ out_row, int32_t* __restrict__ out_col, float* __restrict__ out_val) {
+    const unsigned long long b = __ballot(sel);
+    if (!COUNT && sel) {
+        const long long o = base + total + __popcll(b & ((1ull << lane) - 1ull));
+        out_row[o] = (int32_t)row; out_col[o] = (int32_t)col; out_val[o] = val;
+    }
+    total += __popcll(b);
+}
+
+struct BpGeom { long long width, b_lo, o_lo, o_hi, n_cols; float thr; };
+struct SpGeom { long long width, c0, n_cols; float thr; };
+
+// the band's end policy on the run that ends at global column `end`: a peak of the own range, undecidable, or neither
+__device__ __forceinline__ bool bp_decide(const PkRun& r, int lane, const BpGeom& g, long long* col, bool* undecided) {
+    bool sel = false, und = false;
+    if (r.ends && r.v >= g.thr) {
+        long long start;
+        const bool rose = pk_run_start(r, lane, &start);
+        const long long end = r.lane0 + lane;
+        const bool left_known = start > g.b_lo, right_known = !r.last_col;
+        const long long m_lo = ((left_known ? start : 1) + end) / 2;         // the admissible midpoints, inclusive
+        const long long m_hi = (start + (right_known ? end : g.n_cols - 2)) / 2;
+        const bool mine = g.o_lo < g.o_hi && m_hi >= g.o_lo && m_lo < g.o_hi;        // (an empty own range has no midpoint)
+        if (left_known && right_known) {                                      // (then m_lo == m_hi)
+            sel = mine && pk_is_peak(r.v, g.thr, rose, r.right, start, end, g.n_cols);
+        } else {                                                              // lower on the known side, possibly so on the other
+            const bool left_ok = left_known ? rose : g.b_lo > 0;
+            const bool right_ok = right_known ? r.right < r.v : g.b_lo + g.width < g.n_cols;
+            und = mine && left_ok && right_ok;
+        }
+        *col = m_lo;
+    }
+    *undecided = und;
     return sel;
+}
+
+// the stream's end policy: a run whose successor is in the block is decided, one that reaches the block's end is left to the carry
+__device__ __forceinline__ bool sp_decide(const PkRun& r, int lane, const SpGeom& g, long long* col) {
+    if (!(r.ends && !r.last_col && r.v >= g.thr)) return false;
+    long long start;
+    const bool rose = pk_run_start(r, lane, &start);
+    const long long end = r.lane0 + lane;
+    *col = (start + end) / 2;
+    return pk_is_peak(r.v, g.thr, rose, r.right, start, end, g.n_cols);
+}
+
+// the run carried into the block, decided by the block's first value
+__device__ __forceinline__ bool sp_carried(const SpGeom& g, const PkCarry& carry, float first, long long* col) {
+    if (g.c0 == 0 || first == carry.last) return false;                        // no previous column / the run goes on
+    *col = (carry.start + g.c0 - 1) / 2;
+    return pk_is_peak(carry.last, g.thr, carry.rise != 0, first, carry.start, g.c0 - 1, g.n_cols);
 }
 
 template <bool COUNT>
@@ -311,97 +393,25 @@ __global__ __launch_bounds__(256) void k_band_peaks(const float* __restrict__ ba
                                                     int32_t* __restrict__ out_row, int32_t* __restrict__ out_col,
                                                     float* __restrict__ out_val, int32_t* flag) {
     const int lane = threadIdx.x & 63;
-    const long long row = (long long)blockIdx.x * BP_ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    const long long row = (long long)blockIdx.x * PK_ROWS_PER_BLOCK + (threadIdx.x >> 6);
     if (row >= rows) return;
     const float* xr = band + row * stride;
     const long long base = COUNT ? 0 : offsets[row];
-    BpCarry carry{0.f, 0, false};
+    PkCarry carry{0.f, 0, g.b_lo};
     long long total = 0;
     bool any_und = false;
+    if (g.width == 0) { if (COUNT && lane == 0) counts[row] = 0; return; }    // (nothing to load)
+    PkLoad ahead = pk_load(xr, 0, lane, g.width);
     for (long long c0 = 0; c0 < g.width; c0 += 64) {
+        const PkRun r = pk_scan(xr, c0, lane, g.width, g.b_lo, true, carry, ahead);
         long long col = 0;
-        float val;
         bool und;
-        const bool sel = bp_chunk(xr, c0, lane, g, carry, &col, &val, &und);
-        const unsigned long long b = __ballot(sel);
-        if (!COUNT && sel) {
-            const long long o = base + total + __popcll(b & ((1ull << lane) - 1ull));
-            out_row[o] = (int32_t)row; out_col[o] = (int32_t)col; out_val[o] = val;
-        }
-        total += __popcll(b);
+        const bool sel = bp_decide(r, lane, g, &col, &und);
+        pk_emit<COUNT>(sel, lane, row, col, r.v, base, total, out_row, out_col, out_val);
         any_und |= und;
     }
     if (COUNT && lane == 0) counts[row] = (int32_t)total;
     if (__any(any_und) && lane == 0) atomicOr(flag, 1);
-}
-
-// ------------------------------------------------------------------------------------------------
-// (e) Peak candidates of a STREAM of column blocks (`postproc.StreamPeaks`, the online day loop's closed columns): the peaks of
-// k_row_select MODE 1 on the full matrix, found block by block. block [rows, width] (row stride `stride`) holds the global columns
-// [c0, c0 + width) of an axis of n_cols columns; blocks arrive in order and without gaps. The definition is (d)'s: a maximal run of
-// equal values >= thr whose two outer neighbours are lower, reported at (start + end) / 2; a run that holds column 0 or n_cols - 1
-// is no peak. Where (d) has to flag a run that touches an end of its band, the stream carries it: per row, SpCarry is what BpCarry
-// holds wave-uniformly inside one call, kept in device memory from call to call -- `last` the value of column c0 - 1, `start` the
-// GLOBAL column where the run that holds it began, `rise` whether the value before that run was lower (0 if the run holds column
-// 0). Before the first block (c0 == 0) there is no previous column and carry_in is not read.
-// A call decides every run whose end it knows: the runs that end inside the block with their successor in the block (at the END
-// lane, sp_chunk) and the carried run when the block's first value differs from `last` (sp_carried). The carried run's end lane is
-// gone, so lane 0 emits it at rank 0, ahead of everything the block itself yields: a row's columns ascend within a call and
-// from call to call. A run that reaches the block's last column is deferred through the carry -- if that column is n_cols - 1 no
-// later call comes and it is no peak. No flag, no fallback.
-// COUNT reads carry_in, writes carry_out, counts and lowers *bound; FILL reads the same carry_in and writes the triplets at
-// offsets[row] + rank: neither pass reads what the other writes, and both take every decision from sp_carried / sp_chunk.
-// *bound (set to c0 + width by k_stream_bound_init in front of the COUNT launch): no peak a LATER call emits has a column below
-// it. The only peaks of later calls that can lie below c0 + width are those of runs still open at the block's end; such a run
-// [start, e] with e >= c0 + width - 1 is reported at (start + e) / 2 >= (start + c0 + width - 1) / 2, and only if it reaches thr, rose
-// and does not hold column 0: one atomicMin per such row, by lane 0.
-// ------------------------------------------------------------------------------------------------
-constexpr int SP_ROWS_PER_BLOCK = 4;
-struct __attribute__((aligned(16))) SpCarry { float last; int32_t rise; long long start; };
-struct SpGeom { long long width, c0, n_cols; float thr; };
-
-// the run carried into the block, decided by the block's first value
-__device__ __forceinline__ bool sp_carried(const SpGeom& g, const SpCarry& carry, float first, long long* col) {
-    if (g.c0 == 0 || first == carry.last) return false;                        // no previous column / the run goes on
-    *col = (carry.start + g.c0 - 1) / 2;
-    return carry.last >= g.thr && carry.rise != 0 && first < carry.last;
-}
-
-// the runs that end inside the chunk [cc, cc + 64) of the block with their successor in the block; advances the carry
-__device__ __forceinline__ bool sp_chunk(const float* __restrict__ xr, long long cc, int lane, const SpGeom& g, SpCarry& carry,
-                                         long long* col, float* val) {
-    const long long j = cc + lane, gj = g.c0 + j;
-    const bool valid = j < g.width;
-    const float v = valid ? xr[j] : 0.f;
-    float left = __shfl_up(v, 1);
-    if (lane == 0) left = carry.last;
-    float right = __shfl_down(v, 1);
-    if (lane == 63 && j + 1 < g.width) right = xr[j + 1];
-    const bool brk = valid && (gj == 0 || left != v);                          // a run starts here
-    const bool rise = valid && gj > 0 && left < v;
-    const unsigned long long bm = __ballot(brk), rm = __ballot(rise);
-    bool sel = false;
-    if (valid && j < g.width - 1 && right != v && v >= g.thr) {                // the known end of a run that reaches the threshold
-        const unsigned long long below = bm & ((2ull << lane) - 1ull);
-        long long s = carry.start;
-        bool rising = carry.rise != 0;
-        if (below) {
-            const int ls = 63 - __clzll(below);
-            s = g.c0 + cc + ls;
-            rising = (rm >> ls) & 1ull;
-        }
-        sel = rising && right < v;                                             // (`rising` implies s > 0)
-        *col = (s + gj) / 2;
-    }
-    *val = v;
-    const long long rest = g.width - 1 - cc;                                   // the chunk's last valid lane holds the carry's value
-    carry.last = __shfl(v, rest < 63 ? (int)rest : 63);
-    if (bm) {
-        const int ls = 63 - __clzll(bm);
-        carry.start = g.c0 + cc + ls;
-        carry.rise = (int32_t)((rm >> ls) & 1ull);
-    }
-    return sel;
 }
 
 __global__ void k_stream_bound_init(long long* bound, long long value) {
@@ -411,35 +421,29 @@ __global__ void k_stream_bound_init(long long* bound, long long value) {
 // launched with width >= 1 only
 template <bool COUNT>
 __global__ __launch_bounds__(256) void k_stream_peaks(const float* __restrict__ block, int rows, long long stride, SpGeom g,
-                                                      const SpCarry* __restrict__ carry_in, SpCarry* __restrict__ carry_out,
+                                                      const PkCarry* __restrict__ carry_in, PkCarry* __restrict__ carry_out,
                                                       int32_t* __restrict__ counts, long long* bound,
                                                       const long long* __restrict__ offsets, int32_t* __restrict__ out_row,
                                                       int32_t* __restrict__ out_col, float* __restrict__ out_val) {
     const int lane = threadIdx.x & 63;
-    const long long row = (long long)blockIdx.x * SP_ROWS_PER_BLOCK + (threadIdx.x >> 6);
+    const long long row = (long long)blockIdx.x * PK_ROWS_PER_BLOCK + (threadIdx.x >> 6);
     if (row >= rows) return;
     const float* xr = block + row * stride;
     const long long base = COUNT ? 0 : offsets[row];
-    SpCarry carry{0.f, 0, 0};
+    PkCarry carry{0.f, 0, 0};
     if (g.c0 > 0) carry = carry_in[row];
     long long total = 0;
     {
         long long col = 0;
-        if (sp_carried(g, carry, xr[0], &col)) {
-            if (!COUNT && lane == 0) { out_row[base] = (int32_t)row; out_col[base] = (int32_t)col; out_val[base] = carry.last; }
-            total = 1;
-        }
+        const bool sel = sp_carried(g, carry, xr[0], &col) && lane == 0;
+        pk_emit<COUNT>(sel, lane, row, col, carry.last, base, total, out_row, out_col, out_val);
     }
-    for (long long cc = 0; cc < g.width; cc += 64) {
+    PkLoad ahead = pk_load(xr, 0, lane, g.width);
+    for (long long c0 = 0; c0 < g.width; c0 += 64) {
+        const PkRun r = pk_scan(xr, c0, lane, g.width, g.c0, false, carry, ahead);
         long long col = 0;
-        float val;
-        const bool sel = sp_chunk(xr, cc, lane, g, carry, &col, &val);
-        const unsigned long long b = __ballot(sel);
-        if (!COUNT && sel) {
-            const long long o = base + total + __popcll(b & ((1ull << lane) - 1ull));
-            out_row[o] = (int32_t)row; out_col[o] = (int32_t)col; out_val[o] = val;
-        }
-        total += __popcll(b);
+        const bool sel = sp_decide(r, lane, g, &col);
+        pk_emit<COUNT>(sel, lane, row, col, r.v, base, total, out_row, out_col, out_val);
     }
     if (COUNT && lane == 0) {
         counts[row] = (int32_t)total;

@@ -4127,6 +4127,18 @@ const char* band_peaks_bad(const float* band, int rows, int64_t width, int64_t s
     if (!flag || (rows > 0 && width > 0 && !band)) return "null argument";
     return nullptr;
 }
+// one pass of k_band_peaks over checked arguments: COUNT takes `counts`, FILL the offsets and the three outputs
+int band_peaks_launch(bool count, const float* band, int rows, int64_t width, int64_t stride, int64_t b_lo, int64_t o_lo, int64_t o_hi,
+                      int64_t n_cols, float threshold, int32_t* counts, const int64_t* offsets, int32_t* out_row, int32_t* out_col,
+                      float* out_val, int32_t* flag, void* stream) {
+    if (rows == 0) return GENIE_OK;
+    const BpGeom g{(long long)width, (long long)b_lo, (long long)o_lo, (long long)o_hi, (long long)n_cols, threshold};
+    const int nb = (rows + PK_ROWS_PER_BLOCK - 1) / PK_ROWS_PER_BLOCK;
+    const auto k = count ? k_band_peaks<true> : k_band_peaks<false>;
+    k<<<nb, 256, 0, (hipStream_t)stream>>>(band, rows, (long long)stride, g, counts, (const long long*)offsets, out_row, out_col, out_val, flag);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
 }  // namespace
 
 int genie_band_peaks_count(const float* band, int rows, int64_t width, int64_t stride, int64_t b_lo, int64_t o_lo, int64_t o_hi,
@@ -4134,12 +4146,7 @@ int genie_band_peaks_count(const float* band, int rows, int64_t width, int64_t s
     if (const char* bad = band_peaks_bad(band, rows, width, stride, b_lo, o_lo, o_hi, n_cols, flag))
         return fail(GENIE_ERR_ARG, std::string("genie_band_peaks_count: ") + bad);
     if (rows > 0 && !counts) return fail(GENIE_ERR_ARG, "genie_band_peaks_count: null argument");
-    if (rows == 0) return GENIE_OK;
-    const BpGeom g{(long long)width, (long long)b_lo, (long long)o_lo, (long long)o_hi, (long long)n_cols, threshold};
-    const int nb = (rows + BP_ROWS_PER_BLOCK - 1) / BP_ROWS_PER_BLOCK;
-    k_band_peaks<true><<<nb, 256, 0, (hipStream_t)stream>>>(band, rows, (long long)stride, g, counts, nullptr, nullptr, nullptr, nullptr, flag);
-    HIP_TRY(hipGetLastError());
-    return GENIE_OK;
+    return band_peaks_launch(true, band, rows, width, stride, b_lo, o_lo, o_hi, n_cols, threshold, counts, nullptr, nullptr, nullptr, nullptr, flag, stream);
 }
 
 int genie_band_peaks_fill(const float* band, int rows, int64_t width, int64_t stride, int64_t b_lo, int64_t o_lo, int64_t o_hi,
@@ -4148,13 +4155,7 @@ int genie_band_peaks_fill(const float* band, int rows, int64_t width, int64_t st
     if (const char* bad = band_peaks_bad(band, rows, width, stride, b_lo, o_lo, o_hi, n_cols, flag))
         return fail(GENIE_ERR_ARG, std::string("genie_band_peaks_fill: ") + bad);
     if (rows > 0 && (!offsets || !out_row || !out_col || !out_val)) return fail(GENIE_ERR_ARG, "genie_band_peaks_fill: null argument");
-    if (rows == 0) return GENIE_OK;
-    const BpGeom g{(long long)width, (long long)b_lo, (long long)o_lo, (long long)o_hi, (long long)n_cols, threshold};
-    const int nb = (rows + BP_ROWS_PER_BLOCK - 1) / BP_ROWS_PER_BLOCK;
-    k_band_peaks<false><<<nb, 256, 0, (hipStream_t)stream>>>(band, rows, (long long)stride, g, nullptr, (const long long*)offsets, out_row, out_col,
-                                                            out_val, flag);
-    HIP_TRY(hipGetLastError());
-    return GENIE_OK;
+    return band_peaks_launch(false, band, rows, width, stride, b_lo, o_lo, o_hi, n_cols, threshold, nullptr, offsets, out_row, out_col, out_val, flag, stream);
 }
 
 namespace {
@@ -4165,24 +4166,31 @@ const char* stream_peaks_bad(const float* block, int rows, int64_t width, int64_
     if (rows > 0 && width > 0 && (!block || !carry_in)) return "null argument";
     return nullptr;
 }
+// one pass of k_stream_peaks over checked arguments; COUNT runs behind the reset of its bound. Nothing arrived: carry and bound stay
+int stream_peaks_launch(bool count, const float* block, int rows, int64_t width, int64_t stride, int64_t c0, int64_t n_cols, float threshold,
+                        const void* carry_in, void* carry_out, int32_t* counts, int64_t* bound, const int64_t* offsets, int32_t* out_row,
+                        int32_t* out_col, float* out_val, void* stream) {
+    if (rows == 0 || width == 0) return GENIE_OK;
+    const SpGeom g{(long long)width, (long long)c0, (long long)n_cols, threshold};
+    const int nb = (rows + PK_ROWS_PER_BLOCK - 1) / PK_ROWS_PER_BLOCK;
+    const auto k = count ? k_stream_peaks<true> : k_stream_peaks<false>;
+    if (count) k_stream_bound_init<<<1, 64, 0, (hipStream_t)stream>>>((long long*)bound, (long long)(c0 + width));
+    k<<<nb, 256, 0, (hipStream_t)stream>>>(block, rows, (long long)stride, g, (const PkCarry*)carry_in, (PkCarry*)carry_out, counts, (long long*)bound,
+                                           (const long long*)offsets, out_row, out_col, out_val);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
 }  // namespace
 
-size_t genie_stream_peaks_carry_bytes(int rows) { return rows > 0 ? (size_t)rows * sizeof(SpCarry) : 0; }
+size_t genie_stream_peaks_carry_bytes(int rows) { return rows > 0 ? (size_t)rows * sizeof(PkCarry) : 0; }
 
 int genie_stream_peaks_count(const float* block, int rows, int64_t width, int64_t stride, int64_t c0, int64_t n_cols, float threshold,
                              const void* carry_in, void* carry_out, int32_t* counts, int64_t* bound, void* stream) {
     if (const char* bad = stream_peaks_bad(block, rows, width, stride, c0, n_cols, carry_in))
         return fail(GENIE_ERR_ARG, std::string("genie_stream_peaks_count: ") + bad);
     if (rows > 0 && width > 0 && (!carry_out || !counts || !bound)) return fail(GENIE_ERR_ARG, "genie_stream_peaks_count: null argument");
-    if (rows == 0 || width == 0) return GENIE_OK;                         // nothing arrived: the carry and the bound stay as they are
-    const SpGeom g{(long long)width, (long long)c0, (long long)n_cols, threshold};
-    const int nb = (rows + SP_ROWS_PER_BLOCK - 1) / SP_ROWS_PER_BLOCK;
-    hipStream_t st = (hipStream_t)stream;
-    k_stream_bound_init<<<1, 64, 0, st>>>((long long*)bound, (long long)(c0 + width));
-    k_stream_peaks<true><<<nb, 256, 0, st>>>(block, rows, (long long)stride, g, (const SpCarry*)carry_in, (SpCarry*)carry_out, counts,
-                                             (long long*)bound, nullptr, nullptr, nullptr, nullptr);
-    HIP_TRY(hipGetLastError());
-    return GENIE_OK;
+    return stream_peaks_launch(true, block, rows, width, stride, c0, n_cols, threshold, carry_in, carry_out, counts, bound, nullptr, nullptr,
+                               nullptr, nullptr, stream);
 }
 
 int genie_stream_peaks_fill(const float* block, int rows, int64_t width, int64_t stride, int64_t c0, int64_t n_cols, float threshold,
@@ -4192,13 +4200,8 @@ int genie_stream_peaks_fill(const float* block, int rows, int64_t width, int64_t
         return fail(GENIE_ERR_ARG, std::string("genie_stream_peaks_fill: ") + bad);
     if (rows > 0 && width > 0 && (!offsets || !out_row || !out_col || !out_val))
         return fail(GENIE_ERR_ARG, "genie_stream_peaks_fill: null argument");
-    if (rows == 0 || width == 0) return GENIE_OK;
-    const SpGeom g{(long long)width, (long long)c0, (long long)n_cols, threshold};
-    const int nb = (rows + SP_ROWS_PER_BLOCK - 1) / SP_ROWS_PER_BLOCK;
-    k_stream_peaks<false><<<nb, 256, 0, (hipStream_t)stream>>>(block, rows, (long long)stride, g, (const SpCarry*)carry_in, nullptr, nullptr,
-                                                              nullptr, (const long long*)offsets, out_row, out_col, out_val);
-    HIP_TRY(hipGetLastError());
-    return GENIE_OK;
+    return stream_peaks_launch(false, block, rows, width, stride, c0, n_cols, threshold, carry_in, nullptr, nullptr, nullptr, offsets, out_row,
+                               out_col, out_val, stream);
 }
 
 int64_t genie_time_groups_scratch_ints(int64_t n) { return n > 0 ? (n + TG_BLOCK - 1) / TG_BLOCK : 0; }

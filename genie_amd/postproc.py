@@ -43,6 +43,52 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _fp32_threshold(threshold, mode):
+    """The device compares in fp32 where numpy / scipy compare the fp32 entries with a float64 threshold: the fp32 value (a Python
+    float) that gives the same decisions. Mode 0 (`>`): the largest fp32 <= threshold; mode 1 (`>=`): the smallest fp32 >= threshold."""
+    th = np.float32(threshold)
+    if mode == 0 and float(th) > float(threshold):
+        th = np.nextafter(th, np.float32(-np.inf))
+    elif mode == 1 and float(th) < float(threshold):
+        th = np.nextafter(th, np.float32(np.inf))
+    return float(th)
+
+
+def _check_peak_args(who, thresh, distance):
+    """What every entry point of the peak search asks of `find_peaks`' height and distance."""
+    if distance is not None and distance < 1:
+        raise ValueError("`distance` must be greater or equal to 1")          # scipy's own check
+    if not thresh > 0.01:
+        # the reference runs find_peaks on the array REBUILT from `Out_2 > 0.01` (everything else zero, process_continuous_days.py:812-846);
+        # that equals find_peaks on Out_2 itself only for thresholds above the sparsification level
+        raise ValueError("%s: the peak height must be > 0.01 (the reference's sparsification threshold)" % who)
+
+
+def _count_scan_fill(rows, dev, count, fill, extra=None):
+    """The two-pass selection every candidate kernel is driven by: `count(counts)` launches the pass that writes the rows' int32
+    counts, `fill(offsets, out_row, out_col, out_val)` the pass that writes the triplets at the exclusive int64 row offsets (skipped
+    when there are none). Returns (out_row, out_col, out_val, offsets), plus the host value of the device scalar `extra` (an int64
+    tensor [1] that `count` wrote) when one is given: the total and `extra` cross in the ONE host read of the call."""
+    with torch.cuda.device(dev):
+        counts = torch.empty(rows, dtype=torch.int32, device=dev)
+        count(counts)
+        ends = torch.cumsum(counts.long(), 0)
+        offsets = (ends - counts.long()).contiguous()
+        total = ends[-1:] if rows else ends.new_zeros(1)
+        host = rows > 0 or extra is not None              # (an empty matrix without `extra` costs no host read)
+        n, *got = (total if extra is None else torch.cat((total, extra))).tolist() if host else [0]
+        out_row = torch.empty(n, dtype=torch.int32, device=dev)
+        out_col = torch.empty(n, dtype=torch.int32, device=dev)
+        out_val = torch.empty(n, dtype=torch.float32, device=dev)
+        if n:
+            fill(offsets, out_row, out_col, out_val)
+    return (out_row, out_col, out_val, offsets, *got)
+
+
 def _row_select_offsets(x, threshold, mode):
     """`row_select` plus the exclusive int64 row offsets of its triplets (what `genie_peak_distance` walks rows by)."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2):
@@ -51,28 +97,12 @@ def _row_select_offsets(x, threshold, mode):
         raise ValueError("row_select: x must be contiguous (a silent copy of a multi-GB Out_2 is not what the caller wants)")
     lib = _lib.load()
     rows, cols = int(x.shape[0]), int(x.shape[1])
-    # the device compares in fp32 where numpy / scipy compare the fp32 entries with a float64 threshold: round the threshold to
-    # the fp32 value that gives the same decisions (`>`: the largest fp32 <= threshold; `>=`: the smallest fp32 >= threshold)
-    th = np.float32(threshold)
-    if mode == 0 and float(th) > float(threshold):
-        th = np.nextafter(th, np.float32(-np.inf))
-    if mode == 1 and float(th) < float(threshold):
-        th = np.nextafter(th, np.float32(np.inf))
-    with torch.cuda.device(x.device):
-        st = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        counts = torch.empty(rows, dtype=torch.int32, device=x.device)
-        _lib.check(lib.genie_row_select_count(_ptr(x), rows, cols, ctypes.c_float(float(th)), int(mode), _ptr(counts), st),
-                   "genie_row_select_count")
-        ends = torch.cumsum(counts.long(), 0)
-        offsets = (ends - counts.long()).contiguous()
-        n = int(ends[-1].item()) if rows else 0
-        out_row = torch.empty(n, dtype=torch.int32, device=x.device)
-        out_col = torch.empty(n, dtype=torch.int32, device=x.device)
-        out_val = torch.empty(n, dtype=torch.float32, device=x.device)
-        if n:
-            _lib.check(lib.genie_row_select_fill(_ptr(x), rows, cols, ctypes.c_float(float(th)), int(mode), _ptr(offsets),
-                                                 _ptr(out_row), _ptr(out_col), _ptr(out_val), st), "genie_row_select_fill")
-    return out_row, out_col, out_val, offsets
+    head = (_ptr(x), rows, cols, ctypes.c_float(_fp32_threshold(threshold, mode)), int(mode))
+    st = _stream(x.device)
+    return _count_scan_fill(
+        rows, x.device,
+        lambda counts: _lib.check(lib.genie_row_select_count(*head, _ptr(counts), st), "genie_row_select_count"),
+        lambda offsets, *out: _lib.check(lib.genie_row_select_fill(*head, _ptr(offsets), *map(_ptr, out), st), "genie_row_select_fill"))
 
 
 def row_select(x, threshold, mode):
@@ -116,12 +146,7 @@ def find_peaks_rows(Out_2, height, distance):
     """`find_peaks(Out[i, :], height = thresh, distance = d)` for every row i (process_continuous_days.py:846): candidates (local
     maxima reaching `height`) on the device, the distance rule per row on the host. Returns numpy (row, col, peak height),
     rows ascending, columns ascending within a row."""
-    if distance is not None and distance < 1:
-        raise ValueError("`distance` must be greater or equal to 1")          # scipy's own check
-    if not height > 0.01:
-        # the reference runs find_peaks on the array REBUILT from `Out_2 > 0.01` (everything else zero, process_continuous_days.py:812-846);
-        # that equals find_peaks on Out_2 itself only for thresholds above the sparsification level
-        raise ValueError("find_peaks_rows: height must be > 0.01 (the reference's sparsification threshold)")
+    _check_peak_args("find_peaks_rows", height, distance)
     r, c, v = row_select(Out_2, height, 1)
     r, c, v = r.cpu().numpy().astype(np.int64), c.cpu().numpy().astype(np.int64), v.cpu().numpy()
     if distance is None or r.size == 0:
@@ -220,19 +245,12 @@ def detect_sources(Out_2, X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_
 # The same three stages on the device (genie_peak_distance / genie_time_groups / genie_local_marching, csrc/detect_kernels.hpp).
 # The host functions above stay as they are and are the oracle of these: index sets and surviving rows are equal, not close.
 # ------------------------------------------------------------------------------------------------
-def _stream(dev):
-    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def find_peaks_rows_device(Out_2, height, distance):
     """`find_peaks_rows` without the host: candidates and the distance rule both on the device. Returns GPU tensors (row int32,
     col int32, peak height fp32), rows ascending, columns ascending within a row. Equal to `find_peaks_rows` wherever the distance
     rule is decided by heights; of two EQUAL heights closer than ceil(distance) the later column is kept (scipy decides that case
     by an unstable sort, so its own answer is not specified)."""
-    if distance is not None and distance < 1:
-        raise ValueError("`distance` must be greater or equal to 1")
-    if not height > 0.01:
-        raise ValueError("find_peaks_rows_device: height must be > 0.01 (the reference's sparsification threshold)")
+    _check_peak_args("find_peaks_rows_device", height, distance)
     r, c, v, offsets = _row_select_offsets(Out_2, height, 1)
     if distance is None or r.numel() == 0:
         return r, c, v
@@ -248,6 +266,18 @@ def _peak_distance_keep(offsets, c, v, distance):
         _lib.check(_lib.load().genie_peak_distance(_ptr(offsets), int(offsets.numel()), int(c.numel()), _ptr(c), _ptr(v),
                                                    int(np.ceil(distance)), _ptr(keep), _stream(c.device)), "genie_peak_distance")
     return keep.bool()
+
+
+def _distance_rule_unsorted(r, c, v, rows, n_cols, distance):
+    """The distance rule on GPU peak triplets of a [rows, n_cols] matrix in ANY order: sorted once by (row, col), row offsets,
+    `_peak_distance_keep`. Returns the surviving triplets, row-major."""
+    if r.numel() == 0:
+        return r, c, v
+    order = torch.sort(r.long() * int(n_cols) + c.long(), stable=True)[1]
+    r, c, v = r[order].contiguous(), c[order].contiguous(), v[order].contiguous()
+    counts = torch.bincount(r.long(), minlength=rows)
+    keep = _peak_distance_keep((torch.cumsum(counts, 0) - counts).contiguous(), c, v, distance)
+    return r[keep], c[keep], v[keep]
 
 
 def time_groups_device(t, break_win):
@@ -358,26 +388,15 @@ def band_peaks(band, b_lo, o_lo, o_hi, n_cols, threshold):
     lib = _lib.load()
     rows, width = int(band.shape[0]), int(band.shape[1])
     stride = int(band.stride(0)) if rows > 1 else width
-    th = np.float32(threshold)                        # `>=` in fp32 as numpy decides it with a float64 threshold (`_row_select_offsets`)
-    if float(th) < float(threshold):
-        th = np.nextafter(th, np.float32(np.inf))
-    geom = (rows, width, stride, int(b_lo), int(o_lo), int(o_hi), int(n_cols), ctypes.c_float(float(th)))
+    head = (_ptr(band), rows, width, stride, int(b_lo), int(o_lo), int(o_hi), int(n_cols), ctypes.c_float(_fp32_threshold(threshold, 1)))
     dev = band.device
-    with torch.cuda.device(dev):
-        st = _stream(dev)
-        flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        counts = torch.empty(rows, dtype=torch.int32, device=dev)
-        _lib.check(lib.genie_band_peaks_count(_ptr(band), *geom, _ptr(counts), _ptr(flag), st), "genie_band_peaks_count")
-        ends = torch.cumsum(counts.long(), 0)
-        offsets = (ends - counts.long()).contiguous()
-        n = int(ends[-1].item()) if rows else 0
-        out_row = torch.empty(n, dtype=torch.int32, device=dev)
-        out_col = torch.empty(n, dtype=torch.int32, device=dev)
-        out_val = torch.empty(n, dtype=torch.float32, device=dev)
-        if n:
-            _lib.check(lib.genie_band_peaks_fill(_ptr(band), *geom, _ptr(offsets), _ptr(out_row), _ptr(out_col), _ptr(out_val), _ptr(flag),
-                                                 st), "genie_band_peaks_fill")
-    return out_row, out_col, out_val, offsets, flag
+    st = _stream(dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    return _count_scan_fill(
+        rows, dev,
+        lambda counts: _lib.check(lib.genie_band_peaks_count(*head, _ptr(counts), _ptr(flag), st), "genie_band_peaks_count"),
+        lambda offsets, *out: _lib.check(lib.genie_band_peaks_fill(*head, _ptr(offsets), *map(_ptr, out), _ptr(flag), st),
+                                         "genie_band_peaks_fill")) + (flag,)
 
 
 def detect_sources_banded(banded, X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_win, break_win, tc_win, sp_win,
@@ -397,10 +416,7 @@ def detect_sources_banded(banded, X_query, tsteps_abs, ftrns1, thresh, src_t_ker
     `info` also holds `candidates` (per rank) and `gathered_bytes` (what the all-gather moved per rank)."""
     from . import apply
     distance = int(1.5 * src_t_kernel / dt_win)
-    if distance < 1:
-        raise ValueError("`distance` must be greater or equal to 1")
-    if not thresh > 0.01:
-        raise ValueError("detect_sources_banded: thresh must be > 0.01 (the reference's sparsification threshold)")
+    _check_peak_args("detect_sources_banded", thresh, distance)
     bands = list(banded) if isinstance(banded, (list, tuple)) else [banded]
     if not bands or not all(isinstance(b, apply.BandedOut2) for b in bands):
         raise ValueError("detect_sources_banded: an apply.BandedOut2 (or the list of every rank's) expected")
@@ -438,13 +454,7 @@ def detect_sources_banded(banded, X_query, tsteps_abs, ftrns1, thresh, src_t_ker
     r = torch.cat([as_dev(p[0], torch.int32) for p in parts])
     c = torch.cat([as_dev(p[1], torch.int32) for p in parts])
     v = torch.cat([as_dev(p[2], torch.float32) for p in parts])
-    if r.numel():
-        order = torch.sort(r.long() * int(n_cols) + c.long(), stable=True)[1]
-        r, c, v = r[order].contiguous(), c[order].contiguous(), v[order].contiguous()
-        counts = torch.bincount(r.long(), minlength=rows)
-        offsets = (torch.cumsum(counts, 0) - counts).contiguous()
-        keep = _peak_distance_keep(offsets, c, v, distance)
-        r, c, v = r[keep], c[keep], v[keep]
+    r, c, v = _distance_rule_unsorted(r, c, v, rows, n_cols, distance)
     return _sources_from_peaks(r, c, v, X_query, tsteps_abs, ftrns1, break_win, tc_win, sp_win, scale_depth_clustering), info
 
 
@@ -473,10 +483,7 @@ class StreamPeaks(object):
             raise ValueError("StreamPeaks: a GPU device is required")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        th = np.float32(threshold)                        # `>=` in fp32 as numpy decides it with a float64 threshold (`band_peaks`)
-        if float(th) < float(threshold):
-            th = np.nextafter(th, np.float32(np.inf))
-        self.threshold = float(th)
+        self.threshold = _fp32_threshold(threshold, 1)
         self.seen, self.bound = 0, 0
         nbytes = max(int(_lib.load().genie_stream_peaks_carry_bytes(self.rows)), 16)
         self._carry = [torch.zeros(nbytes // 8, dtype=torch.int64, device=self.device) for _ in range(2)]     # [in, out]
@@ -506,22 +513,15 @@ class StreamPeaks(object):
             return empty(torch.int32), empty(torch.int32), empty(torch.float32), torch.zeros(rows, dtype=torch.int64, device=dev)
         lib = _lib.load()
         stride = int(block.stride(0)) if rows > 1 else width
-        geom = (rows, width, stride, self.seen, self.n_cols, ctypes.c_float(self.threshold))
         carry_in, carry_out = self._carry
-        with torch.cuda.device(dev):
-            st = _stream(dev)
-            counts = torch.empty(rows, dtype=torch.int32, device=dev)
-            _lib.check(lib.genie_stream_peaks_count(_ptr(block), *geom, _ptr(carry_in), _ptr(carry_out), _ptr(counts), _ptr(self._bound), st),
-                       "genie_stream_peaks_count")
-            ends = torch.cumsum(counts.long(), 0)
-            offsets = (ends - counts.long()).contiguous()
-            n, bound = torch.cat((ends[-1:], self._bound)).tolist()          # the one host read of a push
-            out_row = torch.empty(n, dtype=torch.int32, device=dev)
-            out_col = torch.empty(n, dtype=torch.int32, device=dev)
-            out_val = torch.empty(n, dtype=torch.float32, device=dev)
-            if n:
-                _lib.check(lib.genie_stream_peaks_fill(_ptr(block), *geom, _ptr(carry_in), _ptr(offsets), _ptr(out_row), _ptr(out_col),
-                                                       _ptr(out_val), st), "genie_stream_peaks_fill")
+        head = (_ptr(block), rows, width, stride, self.seen, self.n_cols, ctypes.c_float(self.threshold), _ptr(carry_in))
+        st = _stream(dev)
+        out_row, out_col, out_val, offsets, bound = _count_scan_fill(
+            rows, dev,
+            lambda counts: _lib.check(lib.genie_stream_peaks_count(*head, _ptr(carry_out), _ptr(counts), _ptr(self._bound), st),
+                                      "genie_stream_peaks_count"),
+            lambda offsets, *out: _lib.check(lib.genie_stream_peaks_fill(*head, _ptr(offsets), *map(_ptr, out), st), "genie_stream_peaks_fill"),
+            extra=self._bound)                            # the count and the bound: the one host read of a push
         self._carry = [carry_out, carry_in]               # (FILL has read carry_in on this stream before the next COUNT overwrites it)
         self.seen += width
         self.bound = int(bound)
@@ -578,10 +578,7 @@ class OnlineDetector(object):
     def __init__(self, X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_win, break_win, tc_win, sp_win, scale_depth_clustering=0.2,
                  device="cuda"):
         self.distance = int(1.5 * src_t_kernel / dt_win)
-        if self.distance < 1:
-            raise ValueError("`distance` must be greater or equal to 1")
-        if not thresh > 0.01:
-            raise ValueError("OnlineDetector: thresh must be > 0.01 (the reference's sparsification threshold)")
+        _check_peak_args("OnlineDetector", thresh, self.distance)
         self.tsteps_abs = np.asarray(tsteps_abs, dtype=np.float64).reshape(-1)
         if self.tsteps_abs.size > 1 and not np.all(self.tsteps_abs[1:] >= self.tsteps_abs[:-1]):
             raise ValueError("OnlineDetector: tsteps_abs must ascend")
@@ -610,14 +607,8 @@ class OnlineDetector(object):
 
     def _run_unit(self, r, c, v):
         """The offline stages on one released unit (GPU triplets in any order)."""
-        if r.numel() == 0:
-            return np.zeros((0, 5))
-        order = torch.sort(r.long() * int(self.n_cols) + c.long(), stable=True)[1]
-        r, c, v = r[order].contiguous(), c[order].contiguous(), v[order].contiguous()
-        counts = torch.bincount(r.long(), minlength=self.peaks.rows)
-        offsets = (torch.cumsum(counts, 0) - counts).contiguous()
-        keep = _peak_distance_keep(offsets, c, v, self.distance)
-        return _sources_from_peaks(r[keep], c[keep], v[keep], self.X_query, self.tsteps_abs, *self._tail)
+        r, c, v = _distance_rule_unsorted(r, c, v, self.peaks.rows, self.n_cols, self.distance)
+        return _sources_from_peaks(r, c, v, self.X_query, self.tsteps_abs, *self._tail)
 
     def push(self, first_col, block):
         r, c, v, _ = self.peaks.push(first_col, block)

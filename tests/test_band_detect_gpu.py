@@ -19,40 +19,16 @@ import pytest
 import torch
 
 from genie_amd import apply, module, postproc, synthetic
+from tests.peak_cases import THR, TOP, by_row_col as _by_row_col, matrix as _planted, trip as _trip
 from tests.util import Case
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-TOP = 0.9375                        # above every level of the quantised noise (k / 8, k < 8)
-THR = 0.5                           # one of those levels: a value equal to the threshold is common
+N_COLS = [3, 40, 64, 65, 257]       # 64 and 65: a band that ends exactly at, and one past, a chunk's last lane
 
 
 # ---- the kernel against row_select on the full matrix ---------------------------------------------------------------------------------------
-
-def _matrix(rows, n_cols, seed):
-    """Seeded noise on 8 levels (flat tops everywhere) plus the planted cases the sizes have room for. Returned inside a wider
-    buffer, so that the matrix and every band cut from it have a row stride larger than their width."""
-    rng = np.random.default_rng(seed)
-    x = (np.floor(rng.random((rows, n_cols)) * 8.0) / 8.0).astype(np.float32)
-    r = lambda k: k % rows
-    x[r(0), 0], x[r(0), 1], x[r(0), 2] = 0.0, TOP, 0.0                     # a peak at global column 1 ...
-    x[r(0), n_cols - 3], x[r(0), n_cols - 2], x[r(0), n_cols - 1] = 0.0, TOP, 0.0        # ... and at n_cols - 2
-    if n_cols >= 40:
-        x[r(0), 9:15] = [0.0, TOP, TOP, TOP, TOP, 0.0]                     # an even flat top, columns 10..13
-        x[r(0), 19:24] = [0.0, TOP, TOP, TOP, 0.0]                         # an odd one, columns 20..22
-        x[r(0), 29:32] = [0.25, THR, 0.25]                                 # a peak of exactly the threshold
-    if n_cols >= 40 and rows >= 2:
-        x[r(1), 9:15] = [0.25, THR, THR, 0.75, 0.75, 1.0]                  # steps on a slope: flat, at a cut undecidable, no peak
-        x[r(1), 0:3] = TOP                                                 # flat runs that contain the ends of the axis: no peaks
-        x[r(1), n_cols - 3:] = TOP
-        x[r(1), 19:27] = [1.0, TOP, TOP, TOP, TOP, TOP, TOP, 0.0]          # a run below its left neighbour: decidable, no peak
-    if rows >= 3:
-        x[2, :] = 0.0                                                      # an all-zero row
-    buf = torch.zeros((rows, n_cols + 5), dtype=torch.float32, device=DEV)
-    buf[:, 2:2 + n_cols] = torch.from_numpy(x).to(DEV)
-    return x, buf[:, 2:2 + n_cols]
-
 
 def _runs(x, thr):
     """Every maximal run of equal values >= thr of the full matrix: (row, start, end inclusive, lower on the left, lower on the right)."""
@@ -110,25 +86,20 @@ def _ranks(xd, n_cols, cuts, thr, margin=1):
         assert off.dtype == torch.int64 and off.numel() == xd.shape[0]
         cnt = torch.bincount(r.long(), minlength=xd.shape[0])
         assert torch.equal(off, torch.cumsum(cnt, 0) - cnt)                # the exclusive row offsets genie_peak_distance walks by
-        trip.append(np.stack((r.cpu().numpy(), c.cpu().numpy(), v.cpu().numpy().view(np.int32)), axis=1))
+        trip.append(_trip(r, c, v))
         flags.append(bool(flag.item()))
         bands.append((b_lo, b_hi, o_lo, o_hi))
     return trip, flags, bands
 
 
-def _by_row_col(t):
-    return t[np.lexsort((t[:, 1], t[:, 0]))]
-
-
 @functools.lru_cache(maxsize=None)
 def _case(rows, n_cols):
-    x, xd = _matrix(rows, n_cols, seed=100 * rows + n_cols)
+    x, xd = _planted(rows, n_cols, 100 * rows + n_cols, DEV, streamed=False)
     r, c, v = postproc.row_select(xd.contiguous(), THR, 1)                 # the reference: computed once per shape
-    want = np.stack((r.cpu().numpy(), c.cpu().numpy(), v.cpu().numpy().view(np.int32)), axis=1)
-    return x, xd, want, _runs(x, THR)
+    return x, xd, _trip(r, c, v), _runs(x, THR)
 
 
-@pytest.mark.parametrize("n_cols", [3, 40, 257])
+@pytest.mark.parametrize("n_cols", N_COLS)
 @pytest.mark.parametrize("rows", [1, 3, 70])
 def test_band_peaks_of_two_ranks_equal_row_select_at_every_cut(rows, n_cols):
     x, xd, want, runs = _case(rows, n_cols)
@@ -161,7 +132,7 @@ def test_band_peaks_of_two_ranks_equal_row_select_at_every_cut(rows, n_cols):
                 assert not any(_ranks(xd, n_cols, [0, cut, n_cols], THR)[1]), cut
 
 
-@pytest.mark.parametrize("n_cols", [3, 40, 257])
+@pytest.mark.parametrize("n_cols", N_COLS)
 @pytest.mark.parametrize("rows", [1, 3, 70])
 def test_band_peaks_of_three_and_five_ranks_equal_row_select(rows, n_cols):
     x, xd, want, runs = _case(rows, n_cols)
@@ -186,6 +157,41 @@ def test_band_peaks_of_three_and_five_ranks_equal_row_select(rows, n_cols):
         assert flags[0] and not flags[1] and flags[2]
     if n_cols >= 40 and rows == 1:            # a margin wider than the planted tops decides every one of them
         assert not any(_ranks(xd, n_cols, [0, 12, 21, n_cols], THR, 6)[1])
+
+
+@pytest.mark.parametrize("n_cols", [65, 257])
+def test_band_peaks_on_runs_longer_than_a_chunk(n_cols):
+    """Runs whose start a band reads back from the carry of an earlier chunk (the 8-level noise never yields one of 65 columns): a run
+    over the whole axis (no peak; it begins at b_lo in every band) and a flat top on columns 2..n_cols - 3 (one peak; it begins inside
+    the bands that see column 1). Two ranks at every cut, three ranks with a middle band that touches neither end of the axis."""
+    x = np.zeros((2, n_cols), dtype=np.float32)
+    x[0, :] = TOP
+    x[1, 2:n_cols - 2] = TOP
+    buf = torch.zeros((2, n_cols + 5), dtype=torch.float32, device=DEV)
+    buf[:, 2:2 + n_cols] = torch.from_numpy(x).to(DEV)
+    xd = buf[:, 2:2 + n_cols]
+    want = _trip(*postproc.row_select(xd.contiguous(), THR, 1))
+    assert want.tolist() == [[1, (2 + n_cols - 3) // 2, int(np.float32(TOP).view(np.int32))]]
+    runs = _runs(x, THR)
+    whole = xd[0:1]                                                         # the whole-axis run alone, read off the matrix, not off
+    for cut in range(n_cols + 1):                                           # `_undecidable`: one of two ranks' bands always holds an end
+        trip, flags, _ = _ranks(whole, n_cols, [0, cut, n_cols], THR)      # of the axis, so nothing is flagged and nothing reported
+        assert not any(flags) and sum(len(t) for t in trip) == 0, cut
+    for a, b in ((1, 2), (1, n_cols - 1), (20, 64), (63, 64), (3, n_cols - 3)):
+        flags = _ranks(whole, n_cols, [0, a, b, n_cols], THR, margin=0)[1]  # the middle band sees neither end: it alone must flag
+        assert flags == [False, True, False], (a, b)
+    decided = raised = 0
+    splits = [[0, cut, n_cols] for cut in range(n_cols + 1)] + [[0, 1, 2, n_cols], [0, 20, 64, n_cols], [0, 64, 65, n_cols], [0, 2, n_cols - 2, n_cols]]
+    for cuts in splits:
+        for margin in (1, 70):
+            trip, flags, bands = _ranks(xd, n_cols, cuts, THR, margin)
+            for (b_lo, b_hi, o_lo, o_hi), flag in zip(bands, flags):
+                assert flag == _undecidable(runs, n_cols, b_lo, b_hi, o_lo, o_hi), (cuts, margin, b_lo, b_hi)
+            raised += any(flags)
+            if not any(flags):
+                assert np.array_equal(_by_row_col(np.concatenate(trip)), want), (cuts, margin)
+                decided += 1
+    assert decided >= 4 and raised >= 4
 
 
 def test_band_peaks_threshold_rounding_and_bad_arguments():

@@ -16,56 +16,21 @@ import pytest
 import torch
 
 from genie_amd import _lib, apply, module, postproc, synthetic
+from tests.peak_cases import THR, TOP, by_row_col as _by_row_col, matrix as _planted, trip as _trip
 from tests.util import Case
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-TOP = 0.9375                        # above every level of the quantised noise (k / 8, k < 8)
-THR = 0.5                           # one of those levels: a value equal to the threshold is common
 ROWS = [1, 4, 5, 9]                 # the kernel works four rows per workgroup
 N_COLS = [1, 2, 3, 64, 65, 130]
 
 
 # ---- the kernel against row_select on the full matrix ---------------------------------------------------------------------------------------
 
-def _matrix(rows, n_cols, seed):
-    """Seeded noise on 8 levels (runs and ties everywhere) plus the planted flat tops the sizes have room for, inside a wider buffer:
-    the matrix and every block cut from it have a row stride larger than their width."""
-    rng = np.random.default_rng(seed)
-    x = (np.floor(rng.random((rows, n_cols)) * 8.0) / 8.0).astype(np.float32)
-    r = lambda k: k % rows
-    if n_cols >= 64:
-        x[r(0), 17:27] = [0.0, TOP, TOP, TOP, TOP, TOP, TOP, TOP, TOP, 0.0]    # a flat top on columns 18..25: midpoint 21
-        x[r(0), 40:44] = [0.25, THR, THR, 0.25]                                # a top of exactly the threshold, midpoint 41
-        x[r(0), 61:64] = [0.0, TOP, 0.0]                                       # a peak on the last lane of the first chunk
-    if rows >= 2:
-        x[1, 0:min(3, n_cols)] = TOP                                           # runs that hold column 0 / column n_cols - 1: no peaks
-        x[1, max(n_cols - 3, 0):] = TOP
-        if n_cols >= 64:
-            x[1, 3], x[1, n_cols - 4] = 0.0, 0.0
-            x[1, 19:27] = [1.0, TOP, TOP, TOP, TOP, TOP, TOP, 0.0]             # a run below its left neighbour: no peak
-            x[1, 30:36] = [0.25, THR, THR, 0.75, 0.75, 1.0]                    # steps on a slope: no peak
-    if rows >= 3:
-        x[2, :] = 0.0                                                          # an all-zero row
-    if rows >= 4:
-        x[3, :] = TOP                                                          # a run that covers the whole axis
-    buf = torch.zeros((rows, n_cols + 5), dtype=torch.float32, device=DEV)
-    buf[:, 2:2 + n_cols] = torch.from_numpy(x).to(DEV)
-    return x, buf[:, 2:2 + n_cols]
-
-
-def _trip(r, c, v):
-    return np.stack((r.cpu().numpy(), c.cpu().numpy(), v.cpu().numpy().view(np.int32)), axis=1).reshape(-1, 3)
-
-
-def _by_row_col(t):
-    return t[np.lexsort((t[:, 1], t[:, 0]))]
-
-
 @functools.lru_cache(maxsize=None)
 def _case(rows, n_cols):
-    x, xd = _matrix(rows, n_cols, seed=100 * rows + n_cols)
+    x, xd = _planted(rows, n_cols, 100 * rows + n_cols, DEV, streamed=True)
     r, c, v = postproc.row_select(xd.contiguous(), THR, 1)                 # the reference: computed once per shape
     return x, xd, _trip(r, c, v)
 
