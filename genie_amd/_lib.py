@@ -142,6 +142,8 @@ SYMBOLS = [
     ("genie_stack_windows_ring", _c.c_int, [_P, _c.c_int, _P, _c.c_int, _c.c_int64, _c.c_int, _c.c_float, _P, _c.c_int64, _c.c_int64, _c.c_int64,
                                             _P]),
     ("genie_ring_close", _c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P]),
+    ("genie_ring_save", _c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P]),
+    ("genie_ring_load", _c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _P, _P]),
     ("genie_picks_merge", _c.c_int, [_P, _P, _P, _P, _c.c_int64, _P, _P, _P, _P, _c.c_int64, _P, _P, _P, _P, _P]),
     ("genie_pick_lists_max_sta", _c.c_int, []),
     ("genie_pick_lists", _c.c_int, [_P, _P, _P, _P, _c.c_int64, _c.c_int, _c.c_double, _c.c_int, _c.c_double, _c.c_double, _P, _P, _P, _P, _P,

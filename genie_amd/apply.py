@@ -29,7 +29,7 @@ import types
 import numpy as np
 import torch
 
-from . import engine, synthetic
+from . import checkpoint, engine, synthetic
 
 
 def window_schedule(pick_times, max_t, day_len=86400.0, t_win=6.0, n_resolution=9, step_size="half"):
@@ -737,7 +737,8 @@ class PickStore(ResidentPicks):
     compacts. The host keeps `t_host` (the binary searches run on it) and the fed rows of the live picks (`meta`) in step.
     `frozen_t`: `append` refuses a pick of the model's stations with `t < frozen_t` -- a window that has already run would have read
     it -- with a ValueError that names both and leaves the store as it was; with `late="drop"` such picks are left out (they still count
-    in `index`) and `append` returns how many. `phase_f` is `phase` as float64: phase labels are whole numbers (0 = P, 1 = S)."""
+    in `index`) and `append` returns how many. `phase_f` is `phase` as float64: phase labels are whole numbers (0 = P, 1 = S).
+    `state_dict()` / `load_state_dict(state)`: the live picks, `n_fed` and `frozen_t` as host arrays, into a new store of the same stations."""
 
     def __init__(self, ind_use, n_sta_all, device, use_phase_types=True, capacity=4096):
         ind_use = np.asarray(ind_use).astype(np.int64)
@@ -831,6 +832,42 @@ class PickStore(ResidentPicks):
                 new[t_pos_a], new[t_pos_b] = old[self._base:self._n], x
         self._dev, self._host, self._base, self._n = dev, host, 0, live + m
         return dropped
+
+    def _fingerprint(self):
+        return {"station_map": self._perm, "use_phase_types": self.use_phase_types}
+
+    def state_dict(self):
+        """What `append` and `trim` have made of the store, on the host: the live picks (their times, fed rows and `index`), `n_fed` and
+        `frozen_t`, with the station map as fingerprint. A trimmed pick is not saved: the trim offset is how this object forgets, not
+        something a reader can see. The device arrays are functions of the saved rows and are made again on load, as `append` makes them."""
+        return {"fingerprint": checkpoint.to_host(self._fingerprint()), "frozen_t": float(self.frozen_t), "n_fed": int(self.n_fed),
+                "t": self.t_host.copy(), "rows": self._host[1][self._base:self._n].copy(), "index": self.index_host.copy()}
+
+    def _check_state(self, state):
+        if self.n_fed or self._n:
+            raise RuntimeError("PickStore.load_state_dict: this store has been fed; a state is loaded into a new one")
+        checkpoint.check_fingerprint("PickStore", state, self._fingerprint())
+        t, rows, index = (np.asarray(state[k]) for k in ("t", "rows", "index"))
+        if not (t.dtype == np.float64 and index.dtype == np.int64 and t.ndim == 1 and rows.shape == (len(t), 5) and index.shape == t.shape
+                and is_ascending(t)):
+            raise ValueError("PickStore.load_state_dict: the saved picks are not a time-sorted run (t [n], rows [n, 5], index [n])")
+
+    def load_state_dict(self, state):
+        """Into a store nothing has been fed to (RuntimeError otherwise), built with the same stations (ValueError naming the field
+        otherwise, nothing changed): the views `t`, `sta`, `phase`, `index`, `t_host`, and `meta`, `frozen_t` and the next `index` are
+        those of the saved store, bit for bit; the picks sit at the start of the buffers, as after a compacting `append`."""
+        self._check_state(state)
+        t, rows, index = (np.ascontiguousarray(state[k]) for k in ("t", "rows", "index"))
+        live, cap = len(t), self.capacity
+        while cap < live:
+            cap *= 2
+        sta = self._perm[rows[:, 1].astype(np.int64)]
+        ph = rows[:, 4] if self.use_phase_types else np.zeros(live)
+        dev, host = self._device_buffers(cap), self._host_buffers(cap)
+        for buf, x in zip(dev + host, (t, sta.astype(np.int32), ph.astype(np.int32), index, t, rows, index)):
+            buf[:live] = torch.from_numpy(np.ascontiguousarray(x)).to(self.device) if torch.is_tensor(buf) else x
+        self._dev, self._host, self._base, self._n = dev, host, 0, live
+        self.n_fed, self.frozen_t = int(state["n_fed"]), float(state["frozen_t"])
 
 
 class GridLeg(object):
@@ -1262,7 +1299,11 @@ class OnlineDay(object):
     not depend on how windows are grouped into batched tails (tests/test_hip_parity.py pins every window of a batched tail, batches of
     1, 3, 8 and 16, bit-equal to the plain forward). Not built (NotImplementedError): a source-node-sharded model, `window_parallel`,
     `merge="columns"`, more than one leg. Detection on the closed blocks as they arrive: `postproc.OnlineDetector`
-    (`det.push(*day.feed(P_chunk, t_now))`)."""
+    (`det.push(*day.feed(P_chunk, t_now))`).
+
+    A restart: `state_dict()` between any two `feed` calls (everything `feed` has changed, on the host) and `load_state_dict(state)` on
+    a newly constructed object with the same arguments; from there on the blocks are the saved object's, bit for bit (DESIGN.md
+    section 5.17)."""
 
     def __init__(self, net, geom, trv_times, tsteps_abs, times=None, t_win=6.0, step_size="half", min_required_picks=1, n_grids=1.0,
                  kernel_sig_t=synthetic.KERNEL_SIG_T, dt_embed=None, max_t=None, tail_batch=16, pairs=None, ring_cols=None, ind_use=None,
@@ -1290,6 +1331,7 @@ class OnlineDay(object):
         self.times = np.asarray(tsteps if times is None else times, dtype=np.float64).reshape(-1)
         if not is_ascending(self.times):
             raise ValueError("OnlineDay: times must ascend (windows run in the order in which they become ready)")
+        self.step_size = step_size
         self.h_cols = window_cols_table(tsteps_abs, self.times, self.offsets, step_size == "half", True)
         self.frontiers = online_frontiers(self.h_cols, len(tsteps_abs))
         self.tail_batch = int(tail_batch)
@@ -1391,6 +1433,57 @@ class OnlineDay(object):
     def finish(self):
         """Everything left: `feed(None, inf)`; afterwards `closed == len(tsteps_abs)`."""
         return self.feed(None, np.inf)
+
+    def _fingerprint(self):
+        """The schedule and options a saved day belongs to, in the order in which `load_state_dict` compares them."""
+        return {"tsteps_abs": self.tsteps_abs, "times": self.times, "offsets": self.offsets, "step_size": self.step_size,
+                "scale": self.scale, "tail_batch": self.tail_batch, "max_t": self.max_t, "kernel_sig_t": self.kernel_sig_t,
+                "t_win": self.t_win, "min_required_picks": self.min_required_picks, "dt_embed": self.dt_embed,
+                "n_query": int(self.ring.shape[0])}
+
+    def _state(self):
+        """`state_dict()` before the copy to the host: the open columns are still a device tensor."""
+        lo, hi = self.closed, max(self.closed, self.last_col + 1)
+        with torch.no_grad():
+            block = engine.ring_save(self.ring, lo, hi)                   # [closed, last_col + 1): the ring holds zeros everywhere else
+        return {"fingerprint": self._fingerprint(), "t_now": float(self.t_now), "retain_from": float(self.retain_from),
+                "n_run": int(self.n_run), "closed": int(self.closed), "last_col": int(self.last_col),
+                "times_used": np.asarray(self.times_used, dtype=np.float64), "ring_block": block, "picks": self.picks.state_dict()}
+
+    def state_dict(self):
+        """Everything `feed` has changed, between any two `feed` calls: the counters, the open columns
+        `[closed, last_col + 1)` of the ring as one dense CPU block (genie_ring_save and a copy of that block, not of the ring), the
+        `PickStore`'s state and the fingerprint of the schedule. Python scalars, numpy arrays and CPU tensors only: it goes through
+        `torch.save` / `torch.load(weights_only=False)`. One synchronisation; the object is left as it was."""
+        return checkpoint.to_host(self._state())
+
+    def _check_state(self, state):
+        if self.n_run or self.closed or self.t_now != -np.inf or self.last_col != -1:
+            raise RuntimeError("OnlineDay.load_state_dict: this day has been fed; a state is loaded into a newly constructed OnlineDay")
+        checkpoint.check_fingerprint("OnlineDay", state, self._fingerprint())
+        block, n_open = state["ring_block"], max(int(state["last_col"]) + 1 - int(state["closed"]), 0)
+        if not (torch.is_tensor(block) and block.dtype == torch.float32 and tuple(block.shape) == (self.ring.shape[0], n_open)):
+            raise ValueError("OnlineDay.load_state_dict: ring_block must be fp32 [%d, %d] (the open columns)" % (self.ring.shape[0], n_open))
+        if n_open > self.ring.shape[1]:
+            raise ValueError("OnlineDay.load_state_dict: ring_cols = %d is below the %d open columns of the state" % (self.ring.shape[1], n_open))
+        self.picks._check_state(state["picks"])
+
+    def _load_state(self, state):
+        dev = self.ring.device
+        with torch.no_grad(), torch.cuda.device(dev):
+            engine.ring_load(self.ring, state["ring_block"].to(dev).contiguous(), int(state["closed"]))
+        self.picks.load_state_dict(state["picks"])
+        self.t_now, self.retain_from = float(state["t_now"]), float(state["retain_from"])
+        self.n_run, self.closed, self.last_col = int(state["n_run"]), int(state["closed"]), int(state["last_col"])
+        self.times_used = list(np.asarray(state["times_used"], dtype=np.float64))
+
+    def load_state_dict(self, state):
+        """Resume a saved day in a NEWLY CONSTRUCTED object (nothing fed: RuntimeError otherwise) built with the arguments of the one that
+        saved it: a difference in the schedule or the options raises ValueError naming the first differing field, and nothing has
+        changed. `ring_cols` may differ (any value the constructor accepts holds the open columns; genie_ring_load puts them in this
+        ring's slots). From here on `feed` returns what the saved object would have returned, bit for bit."""
+        self._check_state(state)
+        self._load_state(state)
 
 
 def _inside_region(X, ranges):
@@ -1668,7 +1761,10 @@ class OnlineCatalogue(object):
     that a sub-list reproduces. `pick_lists`: how the association pass makes its pick lists (`associate_sources`; "device" here, one launch per source: at the
     few hundred picks of a window it takes about half the time of the torch statements, profiles/EXPERIMENTS.md). There is no
     `source_parallel`: a push carries a few sources. Every block of `day` must go through this object (a `day.feed` of the caller's
-    own loses columns: ValueError at the next call, nothing changed)."""
+    own loses columns: ValueError at the next call, nothing changed).
+
+    A restart: `state_dict()` between any two `push` calls saves the day, the detector and this object in one call,
+    `load_state_dict(state)` on newly constructed objects with the same arguments resumes all three or none."""
 
     def __init__(self, day, det, locs, trv, tq, ftrns1, ftrns2, lat_range, lon_range, depth_range, X_offset_min, X_offset_range,
                  n_rand_query, tc_win, sp_win, scale_depth_clustering=0.2, t_win_assoc=10.0, rand=None, ftrns2_device=None,
@@ -1767,3 +1863,40 @@ class OnlineCatalogue(object):
         """Everything left: the day's last windows, the detector's last unit, every waiting source, every verdict. Raises as
         `OnlineDetector.finish` does when the detector has not been given every column."""
         return self._step(None, np.inf, True)
+
+    def _fingerprint(self):
+        return {"philox_key": np.asarray(self.rand.key, dtype=np.uint64), "tq": self.tq, "lat_range": self.ranges[0],
+                "lon_range": self.ranges[1], "depth_range": self.ranges[2], "X_offset_min": self.offsets[0], "X_offset_range": self.offsets[1],
+                "n_rand_query": self.n_rand_query, "tc_win": self.tc_win, "sp_win": self.sp_win,
+                "scale_depth_clustering": self.scale_depth_clustering, "t_win_assoc": self.t_win_assoc, "pick_lists": self.pick_lists,
+                "locs_cart": self.locs_cart, "x_save": self.x_save}
+
+    def state_dict(self):
+        """`{"day": ..., "det": ..., "catalogue": ...}`: the states of the day, the detector and this object taken at one moment,
+        between any two `push` calls. Of this object: `n_released`, the waiting, the undecided and the decided
+        sources, and per undecided source its results -- the device tensors (travel-time row, the two likelihood vectors) as CPU tensors
+        of the same dtype, shape and bytes. Every device tensor of the three states is queued for its copy first, then the host waits
+        once. No model, no callable, no device tensor: it goes through `torch.save` / `torch.load(weights_only=False)`."""
+        own = {"fingerprint": self._fingerprint(), "n_released": int(self.n_released), "pending": self._pending, "rows": self._rows,
+               "decided": self._decided, "results": [tuple(r) for r in self._results]}
+        return checkpoint.to_host({"day": self.day._state(), "det": self.det._state(), "catalogue": own})
+
+    def load_state_dict(self, state):
+        """Resume all three objects from one `state_dict()`, or none: this object, its day and its detector must be newly constructed
+        (RuntimeError otherwise) with the arguments of the saved ones, and all three fingerprints are compared before anything changes
+        (ValueError naming the first differing field). The results of the undecided sources go back onto the leg's device."""
+        if not isinstance(state, dict) or sorted(state) != ["catalogue", "day", "det"]:
+            raise ValueError('OnlineCatalogue.load_state_dict: a state has the keys "day", "det" and "catalogue"')
+        if self.n_released or self.pending or self.undecided or self._decided.shape[0]:
+            raise RuntimeError("OnlineCatalogue.load_state_dict: this catalogue has run; a state is loaded into a newly constructed one")
+        own = state["catalogue"]
+        self.day._check_state(state["day"])
+        self.det._check_state(state["det"])
+        checkpoint.check_fingerprint("OnlineCatalogue", own, self._fingerprint())
+        self.day._load_state(state["day"])
+        self.det._load_state(state["det"])
+        dev = self.leg.device
+        f64 = lambda a: np.array(a, dtype=np.float64).reshape(-1, 5)
+        self.n_released = int(own["n_released"])
+        self._pending, self._rows, self._decided = f64(own["pending"]), f64(own["rows"]), f64(own["decided"])
+        self._results = [tuple(x.to(dev) if torch.is_tensor(x) else np.array(x) for x in r) for r in own["results"]]

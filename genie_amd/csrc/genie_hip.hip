@@ -4408,16 +4408,51 @@ int genie_stack_windows_ring(const float* const* x_legs, int n_legs, const int32
                                 c_max, stream, true);
 }
 
-int genie_ring_close(float* ring, int64_t n_query, int64_t ring_cols, int64_t c_lo, int64_t c_hi, float* out, void* stream) {
+namespace {
+// The argument checks the three ring-block entries share; the error (already recorded), or GENIE_OK with nb = the launch's workgroups
+// (0: nothing to do, no launch).
+int ring_block_args(const char* name, const void* ring, int64_t n_query, int64_t ring_cols, int64_t c_lo, int64_t c_hi, const void* block,
+                    int64_t& nb) {
+    nb = 0;
     if (n_query < 0 || n_query >= (1ll << 31) || ring_cols < 1 || ring_cols >= (1ll << 31) || c_lo < 0 || c_hi < c_lo || c_hi > (1ll << 31))
-        return fail(GENIE_ERR_ARG, "genie_ring_close: 0 <= n_query < 2^31, 1 <= ring_cols < 2^31 and 0 <= c_lo <= c_hi <= 2^31 required");
-    if (c_hi - c_lo > ring_cols) return fail(GENIE_ERR_ARG, "genie_ring_close: more columns than the ring has slots");
+        return fail(GENIE_ERR_ARG, std::string(name) + ": 0 <= n_query < 2^31, 1 <= ring_cols < 2^31 and 0 <= c_lo <= c_hi <= 2^31 required");
+    if (c_hi - c_lo > ring_cols) return fail(GENIE_ERR_ARG, std::string(name) + ": more columns than the ring has slots");
     const int64_t n = c_hi - c_lo;
     if (n_query == 0 || n == 0) return GENIE_OK;
-    if (!ring || !out) return fail(GENIE_ERR_ARG, "genie_ring_close: null argument");
-    const int64_t nb = (n_query * n + 255) / 256;
-    if (nb >= (1ll << 31)) return fail(GENIE_ERR_ARG, "genie_ring_close: n_query x (c_hi - c_lo) too large for one launch");
-    k_ring_close<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(ring, (long long)n_query, (long long)ring_cols, (long long)c_lo, (long long)n, out);
+    if (!ring || !block) return fail(GENIE_ERR_ARG, std::string(name) + ": null argument");
+    const int64_t blocks = (n_query * n + 255) / 256;
+    if (blocks >= (1ll << 31)) return fail(GENIE_ERR_ARG, std::string(name) + ": n_query x (c_hi - c_lo) too large for one launch");
+    nb = blocks;
+    return GENIE_OK;
+}
+}  // namespace
+
+int genie_ring_close(float* ring, int64_t n_query, int64_t ring_cols, int64_t c_lo, int64_t c_hi, float* out, void* stream) {
+    int64_t nb;
+    if (int rc = ring_block_args("genie_ring_close", ring, n_query, ring_cols, c_lo, c_hi, out, nb)) return rc;
+    if (nb == 0) return GENIE_OK;
+    k_ring_close<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(ring, (long long)n_query, (long long)ring_cols, (long long)c_lo,
+                                                                (long long)(c_hi - c_lo), out);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+int genie_ring_save(const float* ring, int64_t n_query, int64_t ring_cols, int64_t c_lo, int64_t c_hi, float* out, void* stream) {
+    int64_t nb;
+    if (int rc = ring_block_args("genie_ring_save", ring, n_query, ring_cols, c_lo, c_hi, out, nb)) return rc;
+    if (nb == 0) return GENIE_OK;
+    k_ring_save<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(ring, (long long)n_query, (long long)ring_cols, (long long)c_lo,
+                                                               (long long)(c_hi - c_lo), out);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+int genie_ring_load(float* ring, int64_t n_query, int64_t ring_cols, int64_t c_lo, int64_t c_hi, const float* block, void* stream) {
+    int64_t nb;
+    if (int rc = ring_block_args("genie_ring_load", ring, n_query, ring_cols, c_lo, c_hi, block, nb)) return rc;
+    if (nb == 0) return GENIE_OK;
+    k_ring_load<<<(unsigned)nb, 256, 0, (hipStream_t)stream>>>(ring, (long long)n_query, (long long)ring_cols, (long long)c_lo,
+                                                               (long long)(c_hi - c_lo), block);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }

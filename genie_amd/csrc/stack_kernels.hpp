@@ -71,3 +71,25 @@ __global__ __launch_bounds__(256) void k_ring_close(float* __restrict__ ring, lo
     out[i] = *r;
     *r = 0.f;
 }
+
+// ------------------------------------------------------------------------------------------------
+// The ring's open columns as a checkpoint (apply.OnlineDay.state_dict / load_state_dict), k_ring_close's indexing without its zeroing:
+// k_ring_save reads, out[q, j] = ring[q, (c_lo + j) % W], and writes nothing of the ring; k_ring_load is the inverse store,
+// ring[q, (c_lo + j) % W] = block[q, j], into a ring whose W may differ from the saving ring's (n <= W: every slot written by exactly one
+// thread, every other slot untouched). The dense block is what travels, so neither side knows the other's W.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_ring_save(const float* __restrict__ ring, long long Q, long long W, long long c_lo, long long n,
+                                                   float* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= Q * n) return;
+    const long long q = i / n;
+    out[i] = ring[q * W + (c_lo + (i - q * n)) % W];
+}
+
+__global__ __launch_bounds__(256) void k_ring_load(float* __restrict__ ring, long long Q, long long W, long long c_lo, long long n,
+                                                   const float* __restrict__ block) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= Q * n) return;
+    const long long q = i / n;
+    ring[q * W + (c_lo + (i - q * n)) % W] = block[i];
+}

@@ -206,19 +206,51 @@ def stack_windows_ring(ring, xs, cols, scale, c_min, c_max):
     return ring
 
 
+def _ring_range(name, ring, c_lo, c_hi):
+    """The checks `ring_close`, `ring_save` and `ring_load` share; the range as ints."""
+    if not (torch.is_tensor(ring) and ring.is_cuda and ring.dtype == torch.float32 and ring.dim() == 2 and ring.is_contiguous()):
+        raise ValueError("%s: ring must be a contiguous fp32 GPU tensor [n_query, ring_cols]" % name)
+    c_lo, c_hi = int(c_lo), int(c_hi)
+    if not 0 <= c_lo <= c_hi or c_hi - c_lo > ring.shape[1]:
+        raise ValueError("%s: 0 <= c_lo <= c_hi and c_hi - c_lo <= %d slots required, got [%d, %d)" % (name, ring.shape[1], c_lo, c_hi))
+    return c_lo, c_hi
+
+
 def ring_close(ring, c_lo, c_hi):
     """The columns [c_lo, c_hi) of a `stack_windows_ring` ring as a new dense fp32 tensor [Q, c_hi - c_lo]; their slots are zeroed in the
     same pass (genie_ring_close, one launch on the current stream). `c_hi - c_lo <= W`; the range may wrap the ring's end."""
-    if not (torch.is_tensor(ring) and ring.is_cuda and ring.dtype == torch.float32 and ring.dim() == 2 and ring.is_contiguous()):
-        raise ValueError("ring_close: ring must be a contiguous fp32 GPU tensor [n_query, ring_cols]")
-    c_lo, c_hi = int(c_lo), int(c_hi)
-    if not 0 <= c_lo <= c_hi or c_hi - c_lo > ring.shape[1]:
-        raise ValueError("ring_close: 0 <= c_lo <= c_hi and c_hi - c_lo <= %d slots required, got [%d, %d)" % (ring.shape[1], c_lo, c_hi))
+    c_lo, c_hi = _ring_range("ring_close", ring, c_lo, c_hi)
     out = torch.empty((ring.shape[0], c_hi - c_lo), dtype=torch.float32, device=ring.device)
     with torch.cuda.device(ring.device):
         _lib.check(_lib.load().genie_ring_close(_ptr(ring), int(ring.shape[0]), int(ring.shape[1]), c_lo, c_hi, _ptr(out), _stream()),
                    "genie_ring_close")
     return out
+
+
+def ring_save(ring, c_lo, c_hi):
+    """The columns [c_lo, c_hi) of a ring as a new dense fp32 tensor [Q, c_hi - c_lo] on the ring's device, the ring left as it is
+    (genie_ring_save, one launch on the current stream): `ring_close` without the zeroing, for a checkpoint of the open columns."""
+    c_lo, c_hi = _ring_range("ring_save", ring, c_lo, c_hi)
+    out = torch.empty((ring.shape[0], c_hi - c_lo), dtype=torch.float32, device=ring.device)
+    with torch.cuda.device(ring.device):
+        _lib.check(_lib.load().genie_ring_save(_ptr(ring), int(ring.shape[0]), int(ring.shape[1]), c_lo, c_hi, _ptr(out), _stream()),
+                   "genie_ring_save")
+    return out
+
+
+def ring_load(ring, block, c_lo):
+    """`ring[q, (c_lo + j) % W] = block[q, j]` (genie_ring_load, one launch on the current stream): the inverse of `ring_save`, into a ring
+    whose W need not be the saving ring's, only >= block.shape[1]. `block` fp32 [Q, n] contiguous on the ring's device; no other slot is
+    written. Returns `ring`."""
+    if not (torch.is_tensor(block) and block.dim() == 2):
+        raise ValueError("ring_load: block must be a contiguous fp32 GPU tensor [n_query, n] on the ring's device")
+    c_lo, c_hi = _ring_range("ring_load", ring, c_lo, int(c_lo) + int(block.shape[1]))
+    if not (block.dtype == torch.float32 and block.is_contiguous() and block.device == ring.device and block.shape[0] == ring.shape[0]):
+        raise ValueError("ring_load: block must be a contiguous fp32 GPU tensor [%d, n] on %s" % (ring.shape[0], ring.device))
+    with torch.cuda.device(ring.device):
+        _lib.check(_lib.load().genie_ring_load(_ptr(ring), int(ring.shape[0]), int(ring.shape[1]), c_lo, c_hi, _ptr(block), _stream()),
+                   "genie_ring_load")
+    return ring
 
 
 PICK_FIELDS = (("t", torch.float64), ("sta", torch.int32), ("phase", torch.int32), ("index", torch.int64))

@@ -36,7 +36,7 @@ from scipy.sparse import coo_matrix
 from scipy.sparse.csgraph import connected_components
 from scipy.spatial import cKDTree
 
-from . import _lib
+from . import _lib, checkpoint
 
 
 def _ptr(t):
@@ -472,7 +472,8 @@ class StreamPeaks(object):
     whose run ended with this block, among them a run carried in from earlier blocks (first in its row; its midpoint may lie several
     blocks back). Over all pushes the triplets are those of `row_select(full, threshold, 1)`; within a row the columns ascend, across
     calls too. `seen`: the next column expected. `bound` (a Python int, read together with the count: one host read per push): no
-    candidate of any later push has a column below it; `n_cols` once the axis has ended."""
+    candidate of any later push has a column below it; `n_cols` once the axis has ended. `state_dict()` / `load_state_dict(state)`:
+    `seen`, `bound` and the carry the next push reads, into a new stream of the same rows, axis and threshold."""
 
     def __init__(self, rows, n_cols, threshold, device):
         self.rows, self.n_cols = int(rows), int(n_cols)
@@ -527,6 +528,35 @@ class StreamPeaks(object):
         self.bound = int(bound)
         return out_row, out_col, out_val, offsets
 
+    def _fingerprint(self):
+        return {"rows": self.rows, "n_cols": self.n_cols, "thresh": self.threshold}
+
+    def _state(self):
+        """`seen`, `bound` and the carry the next push reads (every row's open run across the last block edge; the other buffer of
+        the pair is the next push's output, and the device `bound` is set by every push before it is read)."""
+        return {"fingerprint": self._fingerprint(), "seen": int(self.seen), "bound": int(self.bound), "carry": self._carry[0]}
+
+    def state_dict(self):
+        return checkpoint.to_host(self._state())
+
+    def _check_state(self, state):
+        if self.seen:
+            raise RuntimeError("StreamPeaks.load_state_dict: this stream has been pushed to; a state is loaded into a new one")
+        checkpoint.check_fingerprint("StreamPeaks", state, self._fingerprint())
+        carry = state["carry"]
+        if not (torch.is_tensor(carry) and carry.dtype == torch.int64 and carry.shape == self._carry[0].shape):
+            raise ValueError("StreamPeaks.load_state_dict: carry must be int64 [%d]" % self._carry[0].shape[0])
+
+    def _load_state(self, state):
+        self._carry[0].copy_(state["carry"])
+        self.seen, self.bound = int(state["seen"]), int(state["bound"])
+
+    def load_state_dict(self, state):
+        """Into a stream nothing has been pushed to (RuntimeError otherwise) of the same rows, axis and threshold (ValueError naming
+        the field otherwise, nothing changed); the next `push` continues the saved stream."""
+        self._check_state(state)
+        self._load_state(state)
+
 
 def online_release(cols, bound, tsteps_abs, d, break_win):
     """How many of the held candidates' columns `cols` (ascending, repeats allowed) are final: the pure host rule of `OnlineDetector`.
@@ -573,7 +603,10 @@ class OnlineDetector(object):
 
     Stated limit: candidates that never leave a gap of d columns and break_win seconds are held until `finish()`: memory is bounded by
     the activity, not by the ring, and `held` shows it. There is no forced flush, because it would break the equality. Besides
-    `StreamPeaks`' one host read per push, a push that found candidates reads their columns (the release rule is host arithmetic)."""
+    `StreamPeaks`' one host read per push, a push that found candidates reads their columns (the release rule is host arithmetic).
+
+    A restart: `state_dict()` between any two pushes (the held candidates and the `StreamPeaks` carry, on the host) and
+    `load_state_dict(state)` on a newly constructed detector with the same arguments."""
 
     def __init__(self, X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_win, break_win, tc_win, sp_win, scale_depth_clustering=0.2,
                  device="cuda"):
@@ -629,6 +662,44 @@ class OnlineDetector(object):
         unit = (self._r, self._c, self._v)
         self._r, self._c, self._v, self._cols = self._r[:0], self._c[:0], self._v[:0], self._cols[:0]
         return self._run_unit(*unit)
+
+    def _fingerprint(self):
+        _, break_win, tc_win, sp_win, scale_depth = self._tail
+        return {"tsteps_abs": self.tsteps_abs, "X_query": self.X_query, "distance": self.distance, "break_win": break_win, "tc_win": tc_win,
+                "sp_win": sp_win, "scale_depth_clustering": scale_depth}
+
+    def _state(self):
+        return {"fingerprint": self._fingerprint(), "peaks": self.peaks._state(), "held_row": self._r, "held_col": self._c,
+                "held_val": self._v, "held_cols_sorted": self._cols}
+
+    def state_dict(self):
+        """Everything `push` has changed, between any two pushes: the held candidates (row, column, value as
+        CPU tensors in their device order, and the sorted host columns), the `StreamPeaks` state (`seen`, `bound`, the scanner's carry
+        across the last block edge) and the fingerprint of the axis, the queries, the threshold and the windows. One synchronisation;
+        the object is left as it was."""
+        return checkpoint.to_host(self._state())
+
+    def _check_state(self, state):
+        if self.held:
+            raise RuntimeError("OnlineDetector.load_state_dict: this detector holds candidates; a state is loaded into a new one")
+        checkpoint.check_fingerprint("OnlineDetector", state, self._fingerprint())
+        self.peaks._check_state(state["peaks"])
+        r, c, v, cols = state["held_row"], state["held_col"], state["held_val"], np.asarray(state["held_cols_sorted"])
+        if not (all(torch.is_tensor(x) and x.dim() == 1 and x.shape == r.shape for x in (r, c, v)) and r.dtype == c.dtype == torch.int32
+                and v.dtype == torch.float32 and cols.dtype == np.int64 and cols.shape == tuple(r.shape)):
+            raise ValueError("OnlineDetector.load_state_dict: the held candidates are (int32, int32, fp32) tensors and int64 columns [n]")
+
+    def _load_state(self, state):
+        dev = self.peaks.device
+        self.peaks._load_state(state["peaks"])
+        self._r, self._c, self._v = (state[k].to(dev) for k in ("held_row", "held_col", "held_val"))
+        self._cols = np.array(state["held_cols_sorted"], dtype=np.int64)
+
+    def load_state_dict(self, state):
+        """Resume a saved detector in a newly constructed one (nothing pushed: RuntimeError otherwise) built with the same arguments
+        (ValueError naming the first differing field otherwise, nothing changed): all returns from here on are the saved object's."""
+        self._check_state(state)
+        self._load_state(state)
 
 
 # ------------------------------------------------------------------------------------------------

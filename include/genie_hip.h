@@ -786,6 +786,17 @@ int genie_stack_windows_ring(const float* const* x_legs, int n_legs, const int32
  * a launch. Bad arguments return GENIE_ERR_ARG before any launch. */
 int genie_ring_close(float* ring, int64_t n_query, int64_t ring_cols, int64_t c_lo, int64_t c_hi, float* out, void* stream);
 
+/* A checkpoint of the ring's open columns (apply.OnlineDay.state_dict): genie_ring_close without the zeroing,
+ *   out[q, j] = ring[q, (c_lo + j) % ring_cols]   for j < c_hi - c_lo,  out dense [n_query, c_hi - c_lo] fp32,
+ * and the ring is only read. One launch, one thread per element; arguments, ranges and errors as genie_ring_close. */
+int genie_ring_save(const float* ring, int64_t n_query, int64_t ring_cols, int64_t c_lo, int64_t c_hi, float* out, void* stream);
+
+/* The inverse store (apply.OnlineDay.load_state_dict): ring[q, (c_lo + j) % ring_cols] = block[q, j] for j < c_hi - c_lo, block dense
+ * [n_query, c_hi - c_lo] fp32. ring_cols is this ring's own and need not be that of the ring the block was saved from, only
+ * >= c_hi - c_lo; exactly those slots are written (each by the one thread that owns it) and no others. One launch; arguments, ranges and
+ * errors as genie_ring_close. */
+int genie_ring_load(float* ring, int64_t n_query, int64_t ring_cols, int64_t c_lo, int64_t c_hi, const float* block, void* stream);
+
 /* Merge by rank of two time-sorted runs of picks (the growable pick store of the online day loop, apply.PickStore): the resident run a
  * (n_a picks) and a chunk b (n_b picks), each given as four arrays on the device -- t fp64 ascending, sta int32, phase int32, index int64
  * -- into the four output arrays of n_a + n_b elements, which must not overlap the inputs:
