@@ -128,6 +128,7 @@ SYMBOLS = [
     ("genie_stream_peaks_carry_bytes", _c.c_size_t, [_c.c_int]),
     ("genie_stream_peaks_count", _c.c_int, [_P, _c.c_int] + [_c.c_int64] * 4 + [_c.c_float, _P, _P, _P, _P, _P]),
     ("genie_stream_peaks_fill", _c.c_int, [_P, _c.c_int] + [_c.c_int64] * 4 + [_c.c_float, _P, _P, _P, _P, _P, _P]),
+    ("genie_col_counts", _c.c_int, [_P, _c.c_int64, _P, _c.c_int64, _P]),
     ("genie_time_groups_scratch_ints", _c.c_int64, [_c.c_int64]),
     ("genie_time_groups", _c.c_int, [_P, _c.c_int64, _c.c_double, _P, _P, _P]),
     ("genie_local_marching_scratch_bytes", _c.c_size_t, [_c.c_int64]),

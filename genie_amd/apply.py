@@ -1666,7 +1666,7 @@ def retained_after_marching(srcs_refined, ftrns1, tc_win, sp_win, scale_depth_cl
 def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, tq, max_t, ftrns1, ftrns2, lat_range, lon_range,
                             depth_range, X_offset_min, X_offset_range, n_rand_query, thresh, src_t_kernel, dt_win, break_win, tc_win,
                             sp_win, scale_depth_clustering=0.2, kernel_sig_t=synthetic.KERNEL_SIG_T, dt_embed=None, t_win_assoc=10.0,
-                            rand=None, ftrns2_device=None, detect_on_device=False, source_parallel=None):
+                            rand=None, ftrns2_device=None, detect_on_device=False, source_parallel=None, max_unit_cols=None):
     """Everything the caller does between the apply loop and the competitive assignment, with the network calls on the device
     (process_continuous_days.py:811-1105): peaks of the device-resident `Out_2` -> time groups -> LocalMarching (`postproc.
     detect_sources`, :811-891), the refine pass (`refine_sources`, :926-982), travel times of the refined sources (`trv(locs, srcs)`
@@ -1682,8 +1682,15 @@ def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, 
     `detect_info`, that call's info (`detect_info["fallback"]` says whether the day fell back to the dense merge, and why).
     `source_parallel`: the two per-source passes split over GPUs (`refine_sources`, `associate_sources`: a process group, True for
     the default one, or `(rank, world)` -- which, having no transport, must have world 1 here). Detection, both LocalMarchings and the
-    `trv` calls are cheap and deterministic and run replicated on every rank; the returned dict equals the one-GPU dict on every rank."""
+    `trv` calls are cheap and deterministic and run replicated on every rank; the returned dict equals the one-GPU dict on every rank.
+    `max_unit_cols`: detection in units of at most that many columns (`postproc.detect_sources_device(max_unit_cols=...)`, the offline
+    twin of an `OnlineDetector` with the same argument); device detection on a dense `Out_2` only (ValueError otherwise)."""
     from . import postproc
+    if max_unit_cols is not None:
+        if not detect_on_device:
+            raise ValueError("detect_refine_associate: max_unit_cols needs detect_on_device=True (the host detection has no unit rule)")
+        if isinstance(Out_2, BandedOut2):
+            raise ValueError("detect_refine_associate: max_unit_cols is not available on a BandedOut2 (detect_sources_banded has no unit rule)")
     sp = _rank_split(source_parallel, "source_parallel", any(getattr(leg.net, "is_sharded", False) for leg in legs))
     if sp is not None and not sp.collective:
         if sp.world != 1:
@@ -1700,7 +1707,8 @@ def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, 
     detect_info = {}                              # a banded day's info (its `fallback` above all) goes into the returned dict
     if banded:
         detect = postproc.detect_sources_banded
-    srcs = detect(Out_2, X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_win, break_win, tc_win, sp_win, scale_depth_clustering)
+    units = {} if max_unit_cols is None else {"max_unit_cols": max_unit_cols}
+    srcs = detect(Out_2, X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_win, break_win, tc_win, sp_win, scale_depth_clustering, **units)
     if banded:
         srcs, detect_info = srcs[0], {"detect_info": srcs[1]}
     if len(srcs) == 0:
@@ -1740,8 +1748,10 @@ class OnlineCatalogue(object):
     same for everything left. `pending`: sources released but not run; `undecided`: sources refined but not final.
 
     Equality contract: with `day` and `det` built on the same axis and options as the offline calls, all returns concatenated are the
-    dict of `apply_windows_device(stack_on_device=True)` -> `detect_refine_associate(detect_on_device=True, rand=PhiloxCloud(key),
-    ftrns2_device=...)` BIT FOR BIT, however the picks are cut into chunks (refined times distinct, as the offline sorts assume).
+    dict of `apply_windows_device(stack_on_device=True)` -> `detect_refine_associate(detect_on_device=True,
+    max_unit_cols=det.max_unit_cols, rand=PhiloxCloud(key), ftrns2_device=...)` BIT FOR BIT, however the picks are cut into chunks
+    (refined times distinct, as the offline sorts assume). The catalogue takes the detector it is given: with forced unit cuts
+    (`OnlineDetector(max_unit_cols=M)`) the units still come out in ascending time, so rules 1-5 stand as they are.
     Why, rule by rule:
     1. a source at `t_d` is refined on `t_d - 2 sigma < t < t_d + max_t + 2 sigma` and associated on the same range around
        `t_r = t_d + tq[j]`, whatever else the day holds; its cloud is keyed by its place in the day's detection list, which is the
@@ -1797,8 +1807,13 @@ class OnlineCatalogue(object):
     pending = property(lambda self: int(self._pending.shape[0]))
     undecided = property(lambda self: int(self._rows.shape[0]))
 
+    def _held_low(self):
+        """What `online_t_low` reads of the detector's held columns: their minimum alone, as an array of one (or none)."""
+        first = self.det.held_first_col
+        return np.zeros(0, dtype=np.int64) if first is None else np.array([first], dtype=np.int64)
+
     def _t_low(self):
-        return online_t_low(self._pending[:, 3], self.det.held_cols, self.det.peaks.bound, self.day.closed, self.day.tsteps_abs)
+        return online_t_low(self._pending[:, 3], self._held_low(), self.det.peaks.bound, self.day.closed, self.day.tsteps_abs)
 
     def _run(self, srcs):
         """Refine and associate the sources `srcs` (the head of `_pending`), and file the results by refined time."""
@@ -1833,7 +1848,7 @@ class OnlineCatalogue(object):
         if det.seen != day.closed:
             raise ValueError("OnlineCatalogue: the detector has seen %d columns, the day has closed %d (every block of the day goes "
                              "through this object)" % (det.seen, day.closed))
-        day.retain_from = online_retain_from(self._pending[:, 3], det.held_cols, det.peaks.bound, day.closed, day.tsteps_abs, self.tq,
+        day.retain_from = online_retain_from(self._pending[:, 3], self._held_low(), det.peaks.bound, day.closed, day.tsteps_abs, self.tq,
                                              day.kernel_sig_t)
         srcs = det.push(*day.feed(P_chunk, t_now))
         if last:

@@ -414,6 +414,14 @@ __global__ __launch_bounds__(256) void k_band_peaks(const float* __restrict__ ba
     if (__any(any_und) && lane == 0) atomicOr(flag, 1);
 }
 
+// Column occupancy of the held candidates (`postproc.OnlineDetector`): one thread per new candidate, ring[col mod W] += 1. Integer
+// atomics commute, so the counts do not depend on the schedule. The slot is taken on the unsigned column: always inside [0, W).
+__global__ __launch_bounds__(256) void k_col_counts(const int32_t* __restrict__ cols, long long n, int32_t* ring, unsigned W) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    atomicAdd(&ring[(unsigned)cols[i] % W], 1);
+}
+
 __global__ void k_stream_bound_init(long long* bound, long long value) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *bound = value;
 }

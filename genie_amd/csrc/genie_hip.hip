@@ -4204,6 +4204,16 @@ int genie_stream_peaks_fill(const float* block, int rows, int64_t width, int64_t
                                out_col, out_val, stream);
 }
 
+int genie_col_counts(const int32_t* cols, int64_t n, int32_t* ring, int64_t W, void* stream) {
+    if (n < 0 || n >= (1ll << 31)) return fail(GENIE_ERR_ARG, "genie_col_counts: 0 <= n < 2^31 required");
+    if (W < 1 || W >= (1ll << 31)) return fail(GENIE_ERR_ARG, "genie_col_counts: 1 <= W < 2^31 required");
+    if (n > 0 && (!cols || !ring)) return fail(GENIE_ERR_ARG, "genie_col_counts: null argument");
+    if (n == 0) return GENIE_OK;
+    k_col_counts<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(cols, (long long)n, ring, (unsigned)W);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
 int64_t genie_time_groups_scratch_ints(int64_t n) { return n > 0 ? (n + TG_BLOCK - 1) / TG_BLOCK : 0; }
 
 int genie_time_groups(const double* t, int64_t n, double break_win, int32_t* scratch, int32_t* group, void* stream) {

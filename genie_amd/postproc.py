@@ -20,7 +20,8 @@ What runs where:
   full matrix is the oracle of the band kernel (equal triplets).
 * `OnlineDetector` is `detect_sources_device` for an `Out_2` that arrives in blocks of closed columns (`apply.OnlineDay`): the
   candidates per block with a row's open run carried from block to block (`StreamPeaks`, `genie_stream_peaks_*`), the other stages on
-  finished stretches of the axis (`online_release`); `detect_sources_device` on the whole matrix is its oracle (equal rows).
+  finished stretches of the axis (`online_units`, read from per-column candidate counts kept on the device, `genie_col_counts`);
+  `detect_sources_device` on the whole matrix is its oracle (equal rows), with the same `max_unit_cols` when units are bounded.
 * `refine_select_device` is the end of the refine pass per candidate source (process_continuous_days.py:972-978): the sum of the grid
   legs' query read-outs, the region mask and the nested first-maximum argmax in one launch pair (`genie_refine_select`,
   csrc/select_kernels.hpp); the torch statements of `apply.refine_sources` it replaces are its oracle (exact, ties included).
@@ -339,13 +340,33 @@ def local_marching_keep_device(srcs, ftrns1, tc_win=5, sp_win=35e3, n_steps_max=
 
 
 def detect_sources_device(Out_2, X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_win, break_win, tc_win, sp_win,
-                          scale_depth_clustering=0.2):
+                          scale_depth_clustering=0.2, max_unit_cols=None):
     """`detect_sources` with every stage on the device: peaks and distance rule (`find_peaks_rows_device`), a stable sort by time,
     the time groups, LocalMarching within the groups (`n_steps_max = 2, use_directed = False`). `ftrns1` is applied once to the
     query positions on the host (every candidate sits on a query row). Only the surviving rows cross to the host: [n, 5], sorted by
-    time, equal to the rows `detect_sources` returns (sources of equal time may come in another order)."""
-    r, c, v = find_peaks_rows_device(Out_2, thresh, int(1.5 * src_t_kernel / dt_win))
-    return _sources_from_peaks(r, c, v, X_query, tsteps_abs, ftrns1, break_win, tc_win, sp_win, scale_depth_clustering)
+    time, equal to the rows `detect_sources` returns (sources of equal time may come in another order).
+    `max_unit_cols=M` (an integer >= the peak distance in columns; ValueError otherwise): the offline twin of
+    `OnlineDetector(max_unit_cols=M)`. The candidates are cut into the units of `online_units` on the whole axis, every unit goes
+    through the distance rule, the time groups and LocalMarching on its own, and the units' sources are concatenated in ascending time.
+    Not the unbounded result: across a forced cut two peaks of a row closer than the distance both survive, and no time group and no
+    march crosses it. M >= the number of columns gives the unbounded result."""
+    d = int(1.5 * src_t_kernel / dt_win)
+    if max_unit_cols is None:
+        r, c, v = find_peaks_rows_device(Out_2, thresh, d)
+        return _sources_from_peaks(r, c, v, X_query, tsteps_abs, ftrns1, break_win, tc_win, sp_win, scale_depth_clustering)
+    _check_peak_args("detect_sources_device", thresh, d)
+    _check_max_unit_cols("detect_sources_device", max_unit_cols, d)
+    r, c, v = row_select(Out_2, thresh, 1)
+    n_cols, rows = int(Out_2.shape[1]), int(Out_2.shape[0])
+    if len(np.asarray(tsteps_abs).reshape(-1)) != n_cols:
+        raise ValueError("detect_sources_device: tsteps_abs has %d entries, Out_2 %d columns" % (len(np.asarray(tsteps_abs).reshape(-1)), n_cols))
+    out, prev = [np.zeros((0, 5))], -1
+    for end in online_units(c.cpu().numpy(), n_cols, tsteps_abs, d, break_win, max_unit_cols).tolist():
+        go = (c > prev) & (c <= end)
+        u = _distance_rule_unsorted(r[go], c[go], v[go], rows, n_cols, d)
+        out.append(_sources_from_peaks(*u, X_query, tsteps_abs, ftrns1, break_win, tc_win, sp_win, scale_depth_clustering))
+        prev = end
+    return np.concatenate(out)
 
 
 def _sources_from_peaks(r, c, v, X_query, tsteps_abs, ftrns1, break_win, tc_win, sp_win, scale_depth_clustering):
@@ -580,18 +601,87 @@ def online_release(cols, bound, tsteps_abs, d, break_win):
     return int(np.searchsorted(cols, c[np.flatnonzero(valid)[-1]], side="right"))
 
 
+def _check_max_unit_cols(who, max_unit_cols, d):
+    if max_unit_cols is None:
+        return None
+    if int(max_unit_cols) != max_unit_cols or max_unit_cols < 1 or max_unit_cols < d:
+        raise ValueError("%s: max_unit_cols must be an integer >= 1 and >= the peak distance (%d columns), or None" % (who, d))
+    return int(max_unit_cols)
+
+
+def online_units(cols, bound, tsteps_abs, d, break_win, max_unit_cols=None):
+    """The unit rule of the detection, offline and online: the LAST COLUMN of every unit of the candidate columns `cols` (any order,
+    repeats allowed) that is final under `bound`, ascending (int64, possibly empty). The unit of an entry holds the candidates of the
+    columns after the entry before it (or from the start) up to it; every unit goes through the offline stages on its own, and every
+    column above the last entry waits. `bound` as in `online_release`; `bound == len(tsteps_abs)` is the ended axis -- the one-shot
+    form, which returns the units of the whole list.
+
+    On the distinct columns c_1 < ... < c_m below the bound, with c_{m+1} = `bound`: a cut after c_i is NATURAL when
+    c_{i+1} - c_i >= d and tsteps_abs[c_{i+1}] - tsteps_abs[c_i] >= break_win (after c_m always, once the axis has ended).
+    * `max_unit_cols=None`: the rule of `online_release` -- at most one entry, the column before the last natural cut.
+    * `max_unit_cols=M` (M >= d, M >= 1; ValueError otherwise): a piece starts at s = c_1. A natural cut after a column in [s, s + M)
+      ends it (the FIRST such cut; the next piece starts at the next column). Without one, the piece ends after the last column below
+      s + M -- a FORCED cut -- as soon as all of [s, s + M) is known: a column at or beyond s + M is there, or `bound >= s + M`. The next
+      piece starts at the first column at or beyond s + M and the rule repeats; a piece that is neither ended nor known to its limit
+      waits, with everything after it. Entries: the column before every forced cut, and the column before the last natural cut after
+      the last forced one (pieces between natural cuts go as one unit: merging across a natural cut changes nothing, `OnlineDetector`).
+    The pieces do not depend on the bound: a piece that starts at s is decided by the columns in [s, s + M) and the natural cuts among
+    them alone. When the cut at the limit is taken with the bound standing in for an unknown c_{m+1} >= bound >= s + M, it is a cut
+    whether that gap later proves natural (the piece ended by itself) or not (it is forced): the unit is the same, only its name is
+    not -- which is why no count of forced cuts is returned."""
+    cols = np.asarray(cols, dtype=np.int64).reshape(-1)
+    ts = np.asarray(tsteps_abs, dtype=np.float64).reshape(-1)
+    bound, n_cols, d = int(bound), len(ts), int(d)
+    M = _check_max_unit_cols("online_units", max_unit_cols, d)
+    c = np.unique(cols[cols < bound])
+    m = c.size
+    none = np.zeros(0, dtype=np.int64)
+    if m == 0:
+        return none
+    ended = bound >= n_cols
+    nxt = np.r_[c[1:], min(bound, n_cols - 1)]
+    natural = (nxt - c >= d) & (ts[nxt] - ts[c] >= float(break_win))
+    natural[-1] |= ended                                                    # (the index was clamped for that case only)
+    if M is None:
+        return c[np.flatnonzero(natural)[-1:]]
+    ends, i, last_natural = [], 0, -1
+    while i < m:
+        lim = c[i] + M
+        j = int(np.searchsorted(c, lim, side="left")) - 1                   # the last column below the limit (>= i)
+        nat = np.flatnonzero(natural[i:j + 1])
+        if nat.size:
+            last_natural = i + int(nat[0])
+            i = last_natural + 1
+        elif j + 1 < m or bound >= lim:
+            ends.append(c[j])
+            i, last_natural = j + 1, -1
+        else:
+            break
+    if last_natural >= 0:
+        ends.append(c[last_natural])
+    return np.asarray(ends, dtype=np.int64)
+
+
 class OnlineDetector(object):
     """`detect_sources_device` on an `Out_2` that arrives in blocks of closed columns: `det.push(*day.feed(P_chunk, t_now))` returns the
     sources [n, 5] (float64, sorted by time, possibly none) that became FINAL with this block, `det.finish()` the rest (ValueError
     unless every column has been pushed). All returns concatenated are the rows `detect_sources_device` finds on the offline `Out_2`,
-    exactly and however the axis is cut into blocks. `held`: the candidates still waiting; `seen`: the next column expected.
+    exactly and however the axis is cut into blocks. `held`: the candidates still waiting; `held_first_col`: the lowest column among
+    them (None when nothing is held); `seen`: the next column expected.
 
     A push runs the streaming candidate kernel on the block (`StreamPeaks`: flat tops across block edges are carried, never flagged),
-    adds the new candidates to the held ones and asks `online_release` for the last valid cut: with d = int(1.5 src_t_kernel / dt_win),
+    adds the new candidates to the held ones and asks `online_units` for the cuts: with d = int(1.5 src_t_kernel / dt_win),
     a cut between two consecutive distinct candidate columns -- or between the last one and the stream's bound, below which no later
     candidate can fall -- is valid when they are >= d columns AND >= break_win seconds apart. Everything before the last valid cut is
     one unit and goes through the offline stages, unchanged: sort by (row, col), row offsets, `_peak_distance_keep`,
     `_sources_from_peaks`.
+
+    The rule needs which columns are occupied, not the candidates: the detector owns a ring of per-column candidate counts on the device
+    (`genie_col_counts` adds the new candidates' columns behind the FILL pass, on its stream), whose live columns run from the first
+    held column -- or the previous bound -- to `seen`. A push that found candidates reads that window (at most two slices, one copy of a
+    few hundred integers) instead of the candidates' columns; released slots are cleared; a window wider than the ring (`ring_cols`; a
+    lagging bound) grows it, rebuilt from the held columns by one launch of the same kernel. The host work of a push does not grow
+    with `held`; `held_cols` is rebuilt from the counts when asked.
 
     Why the result does not depend on when blocks arrive: (1) the distance rule only ever pairs peaks of a row closer than d columns, so
     no peak of a unit meets a peak outside it; (2) the time groups are cut on the candidates that SURVIVE the rule, but removing
@@ -601,17 +691,43 @@ class OnlineDetector(object):
     pipeline on each unit, units come out in ascending time, and releasing late only merges units -- the offline call is the one
     unit of everything.
 
-    Stated limit: candidates that never leave a gap of d columns and break_win seconds are held until `finish()`: memory is bounded by
-    the activity, not by the ring, and `held` shows it. There is no forced flush, because it would break the equality. Besides
-    `StreamPeaks`' one host read per push, a push that found candidates reads their columns (the release rule is host arithmetic).
+    `max_unit_cols=None`: candidates that never leave a gap of d columns and break_win seconds are held until `finish()`; memory is
+    then bounded by the activity, and `held` shows it.
+
+    `max_unit_cols=M` (an integer >= d; ValueError otherwise) bounds it with FORCED cuts, under a contract of its own: all returns
+    concatenated are `detect_sources_device(Out_2, ..., max_unit_cols=M)`, exactly and however the axis is cut into blocks. That is NOT
+    the unbounded result: a piece of the axis that starts at the candidate column s and has no natural cut in [s, s + M) is cut after its
+    last candidate column below s + M, the next piece starts at the first candidate column at or beyond s + M, and every unit between two
+    forced cuts goes through the offline stages on its own (`online_units`). Across a forced cut two peaks of one row closer than d
+    both survive, and neither a time group nor LocalMarching crosses it. M >= n_cols gives the unbounded result.
+    Why arrival does not matter here either. The detector takes no state for it: s is the first held column below the bound. (a) The
+    decision for s depends only on the candidates in [s, s + M) and the natural cuts among them, and it is taken when they are all
+    known: a candidate at or beyond s + M has arrived, or `bound >= s + M`. (b) With the bound standing in for the unknown next column,
+    the cut at the limit is taken whether or not that gap later proves natural; natural or forced, the unit before it is the same set
+    of candidates, and running two units apart that a natural cut separates changes nothing (1-3 above). So which cuts count as
+    forced may depend on arrival -- no such count is exposed -- the sources cannot. (c) Everything after a cut restarts from the first
+    candidate at or beyond it, and that candidate is below the bound when it is used, so it is the first of ALL candidates there. By
+    induction over the pieces, online and offline cut the same units. A push, and `finish()`, run every piece they complete as a
+    separate unit, in ascending time.
+    Invariant, after every push: no held column lies below `peaks.bound`, or `peaks.bound - held_first_col < M`. A row's candidates are
+    at least two columns apart, so after a push `held <= rows * ceil((M + lag) / 2)` with lag = `seen - peaks.bound`, and inside a
+    push of a block B columns wide `held <= rows * ceil((M + B + lag) / 2)`. lag is about half the longest run of equal values at or above the threshold that is
+    still open at the block's end (a column or two on a smooth field); the one exception that remains is a long run of exactly equal
+    values above the threshold, which holds the bound back at its midpoint for as long as it lasts ("The
+    bound").
+
+    Besides `StreamPeaks`' one host read per push, a push that found candidates reads the ring's window.
 
     A restart: `state_dict()` between any two pushes (the held candidates and the `StreamPeaks` carry, on the host) and
     `load_state_dict(state)` on a newly constructed detector with the same arguments."""
 
     def __init__(self, X_query, tsteps_abs, ftrns1, thresh, src_t_kernel, dt_win, break_win, tc_win, sp_win, scale_depth_clustering=0.2,
-                 device="cuda"):
+                 device="cuda", max_unit_cols=None, ring_cols=1024):
         self.distance = int(1.5 * src_t_kernel / dt_win)
         _check_peak_args("OnlineDetector", thresh, self.distance)
+        self.max_unit_cols = _check_max_unit_cols("OnlineDetector", max_unit_cols, self.distance)
+        if int(ring_cols) < 1:
+            raise ValueError("OnlineDetector: ring_cols >= 1 required")
         self.tsteps_abs = np.asarray(tsteps_abs, dtype=np.float64).reshape(-1)
         if self.tsteps_abs.size > 1 and not np.all(self.tsteps_abs[1:] >= self.tsteps_abs[:-1]):
             raise ValueError("OnlineDetector: tsteps_abs must ascend")
@@ -623,7 +739,9 @@ class OnlineDetector(object):
         self._r = torch.empty(0, dtype=torch.int32, device=dev)
         self._c = torch.empty(0, dtype=torch.int32, device=dev)
         self._v = torch.empty(0, dtype=torch.float32, device=dev)
-        self._cols = np.zeros(0, dtype=np.int64)          # the held columns on the host, ascending
+        self._ring = torch.zeros(int(ring_cols), dtype=torch.int32, device=dev)    # candidates per column, slot = column mod its length
+        self._win_lo = 0                                  # the host's copy of the ring's live window as the last push left it:
+        self._win = np.zeros(0, dtype=np.int64)           #   the counts of the columns [_win_lo, ...), the first one held (or empty)
 
     @property
     def seen(self):
@@ -631,46 +749,95 @@ class OnlineDetector(object):
 
     @property
     def held(self):
-        return int(self._cols.size)
+        return int(self._c.numel())
+
+    @property
+    def held_first_col(self):
+        """The lowest column of a held candidate (an int), None when nothing is held."""
+        return int(self._win_lo) if self._win.size else None
 
     @property
     def held_cols(self):
-        """The columns of the held candidates (host int64, ascending, repeats included)."""
-        return self._cols.copy()
+        """The columns of the held candidates (host int64, ascending, repeats included), rebuilt from the column counts."""
+        return np.repeat(self._win_lo + np.arange(self._win.size, dtype=np.int64), self._win)
 
     def _run_unit(self, r, c, v):
         """The offline stages on one released unit (GPU triplets in any order)."""
         r, c, v = _distance_rule_unsorted(r, c, v, self.peaks.rows, self.n_cols, self.distance)
         return _sources_from_peaks(r, c, v, self.X_query, self.tsteps_abs, *self._tail)
 
+    def _slices(self, lo, n):
+        """The ring's slots of the columns [lo, lo + n), n <= its length: one or two contiguous slices."""
+        W = int(self._ring.numel())
+        a = lo % W
+        return (self._ring[a:a + n],) if a + n <= W else (self._ring[a:], self._ring[:a + n - W])
+
+    def _count(self, cols, span):
+        """Add the candidates' columns `cols` (int32 GPU tensor) to the ring; a live window of `span` columns that the ring cannot
+        hold grows it first, and it is then rebuilt from ALL held columns (which `cols` must be part of by now)."""
+        W = int(self._ring.numel())
+        if span > W:
+            while W < span:
+                W *= 2
+            self._ring = torch.zeros(W, dtype=torch.int32, device=self._ring.device)
+            cols = self._c
+        dev = self._ring.device
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().genie_col_counts(_ptr(cols.contiguous()), int(cols.numel()), _ptr(self._ring), W, _stream(dev)),
+                       "genie_col_counts")
+
+    def _set_window(self, lo, counts):
+        """Keep the counts of the columns [lo, ...) from their first occupied column on."""
+        held = np.flatnonzero(counts)
+        k = int(held[0]) if held.size else len(counts)
+        self._win_lo, self._win = lo + k, counts[k:]
+
+    def _release(self):
+        """The units that are final under the stream's bound, each through the offline stages on its own; they leave the held
+        candidates, the ring and the window."""
+        lo, counts = self._win_lo, self._win
+        ends = online_units(lo + np.flatnonzero(counts), self.peaks.bound, self.tsteps_abs, self.distance, self.break_win, self.max_unit_cols)
+        if ends.size == 0:
+            return np.zeros((0, 5))
+        out, prev = [], -1
+        for end in ends.tolist():
+            go = (self._c > prev) & (self._c <= end)
+            out.append(self._run_unit(self._r[go], self._c[go], self._v[go]))
+            prev = end
+        stay = self._c > prev
+        self._r, self._c, self._v = self._r[stay], self._c[stay], self._v[stay]
+        for part in self._slices(lo, prev + 1 - lo):
+            part.zero_()
+        self._set_window(prev + 1, counts[prev + 1 - lo:])
+        return np.concatenate(out)
+
     def push(self, first_col, block):
+        first, bound = self.held_first_col, self.peaks.bound
+        lo = bound if first is None else min(first, bound)                  # no candidate of this push has a column below the bound
         r, c, v, _ = self.peaks.push(first_col, block)
         if r.numel():
             self._r, self._c, self._v = torch.cat((self._r, r)), torch.cat((self._c, c)), torch.cat((self._v, v))
-            self._cols = np.sort(np.concatenate((self._cols, c.cpu().numpy().astype(np.int64))), kind="stable")
-        k = online_release(self._cols, self.peaks.bound, self.tsteps_abs, self.distance, self.break_win)
-        if k == 0:
-            return np.zeros((0, 5))
-        go = self._c <= int(self._cols[k - 1])
-        unit = (self._r[go], self._c[go], self._v[go])
-        self._r, self._c, self._v, self._cols = self._r[~go], self._c[~go], self._v[~go], self._cols[k:]
-        return self._run_unit(*unit)
+            span = self.peaks.seen - lo
+            self._count(c, span)
+            self._set_window(lo, torch.cat(self._slices(lo, span)).cpu().numpy().astype(np.int64))
+        return self._release()
 
     def finish(self):
         if self.peaks.seen != self.n_cols:
             raise ValueError("OnlineDetector.finish: %d of %d columns have been pushed" % (self.peaks.seen, self.n_cols))
-        unit = (self._r, self._c, self._v)
-        self._r, self._c, self._v, self._cols = self._r[:0], self._c[:0], self._v[:0], self._cols[:0]
-        return self._run_unit(*unit)
+        return self._release()
 
     def _fingerprint(self):
         _, break_win, tc_win, sp_win, scale_depth = self._tail
-        return {"tsteps_abs": self.tsteps_abs, "X_query": self.X_query, "distance": self.distance, "break_win": break_win, "tc_win": tc_win,
-                "sp_win": sp_win, "scale_depth_clustering": scale_depth}
+        own = {"tsteps_abs": self.tsteps_abs, "X_query": self.X_query, "distance": self.distance, "break_win": break_win, "tc_win": tc_win,
+               "sp_win": sp_win, "scale_depth_clustering": scale_depth}
+        if self.max_unit_cols is not None:                # (a state saved before the argument existed has no such field)
+            own["max_unit_cols"] = self.max_unit_cols
+        return own
 
     def _state(self):
         return {"fingerprint": self._fingerprint(), "peaks": self.peaks._state(), "held_row": self._r, "held_col": self._c,
-                "held_val": self._v, "held_cols_sorted": self._cols}
+                "held_val": self._v, "held_cols_sorted": self.held_cols}
 
     def state_dict(self):
         """Everything `push` has changed, between any two pushes: the held candidates (row, column, value as
@@ -693,7 +860,11 @@ class OnlineDetector(object):
         dev = self.peaks.device
         self.peaks._load_state(state["peaks"])
         self._r, self._c, self._v = (state[k].to(dev) for k in ("held_row", "held_col", "held_val"))
-        self._cols = np.array(state["held_cols_sorted"], dtype=np.int64)
+        cols = np.array(state["held_cols_sorted"], dtype=np.int64)
+        if cols.size:                                     # the ring and its window, from the held columns
+            self._ring.zero_()
+            self._count(self._c, self.peaks.seen - int(cols[0]))
+            self._set_window(int(cols[0]), np.bincount(cols - cols[0]))
 
     def load_state_dict(self, state):
         """Resume a saved detector in a newly constructed one (nothing pushed: RuntimeError otherwise) built with the same arguments

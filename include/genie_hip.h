@@ -695,6 +695,14 @@ int genie_stream_peaks_fill(const float* block, int rows, int64_t width, int64_t
                             const void* carry_in, const int64_t* offsets, int32_t* out_row, int32_t* out_col, float* out_val,
                             void* stream);
 
+/* Column occupancy of a stream's candidates (genie_amd/postproc.py::OnlineDetector): ring[cols[i] mod W] += 1 for every i < n, with
+ * integer atomics (the counts do not depend on the schedule), one thread per candidate. cols [n] int32, the non-negative global columns
+ * genie_stream_peaks_fill wrote (the slot is taken on the unsigned value: always inside the ring); ring [W] int32, which the caller
+ * zeroes once and where it clears the slots of the columns it releases. The call ACCUMULATES: the caller keeps the live columns within
+ * one span of W, so that a slot stands for one column. n = 0: no launch. Bad arguments (n < 0 or >= 2^31, W < 1 or >= 2^31, a null
+ * pointer with n > 0) return GENIE_ERR_ARG before any launch. */
+int genie_col_counts(const int32_t* cols, int64_t n, int32_t* ring, int64_t W, void* stream);
+
 /* The time-pointer tables of the association heads on the device (`assemble_time_pointers_for_stations`, utils.py:602-622, called at
  * train_GENIE_model.py:1364 and process_continuous_days.py:620; genie_amd/graph.py::time_pointers is the host statement): for every
  * station i and every time step t of dt_partition, the k candidates of station i that are smallest under the key

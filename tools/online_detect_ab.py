@@ -15,7 +15,13 @@ concatenated blocks (not timed; asserted equal).
 
 Then the candidate step alone at 10 000 rows: `StreamPeaks.push` of one block of width 8, 28 and 4096 (host clock around the call and a
 synchronise: COUNT, the scan, the host read of count and bound, FILL; noise below the threshold and a peak on one row in 97) and the COUNT launch alone (HIP events), medians of 50 calls after 10, three
-repeats each. No threshold: the figures are for `profiles/EXPERIMENTS.md`."""
+repeats each. No threshold: the figures are for `profiles/EXPERIMENTS.md`.
+
+  timeout -k 10 600 python tools/online_detect_ab.py --active-cols 3000 [--max-unit-cols 300] [--active-rows 10000] [--active-width 2]
+                                                     [--active-per-col 40] [--out FILE.json]
+
+runs, instead of all of the above, the detector alone over a continuously ACTIVE stretch (`active_stretch`): per-push wall time and
+`held` per quarter of the stretch, with and without a unit limit. The question it answers: does the cost of a push grow with `held`?"""
 import argparse
 import ctypes
 import json
@@ -94,8 +100,54 @@ def stream_peaks_times(rows, widths, dev, repeats=3, calls=50, warm=10):
     return out
 
 
+def active_stretch(dev, rows, n_cols, width, per_col, max_unit_cols, seed=7):
+    """The detector alone on a field whose columns [200, n_cols - 200) are continuously active: `3 * per_col` of the `rows` rows carry a
+    one-column spike every third column (about `per_col` candidates in every column, no gap of d columns anywhere), so that nothing
+    but a forced cut releases the stretch. Blocks of `width` columns; each `det.push` is timed on the host around its own
+    synchronisation. Reported per quarter of the stretch, over the pushes that released nothing: the median ms and the median `held`;
+    the pushes that released, apart. `max_unit_cols` None: the argument is not passed (the tool then runs on a tree without it)."""
+    rng = np.random.default_rng(seed)
+    xq = np.c_[rng.uniform(0, 100e3, (rows, 2)), rng.uniform(-30e3, 0, rows)]
+    ts = np.arange(n_cols) * DETECT["dt_win"] + 1000.0
+    x = torch.zeros((rows, n_cols), dtype=torch.float32, device=dev)
+    lo, hi = 200, n_cols - 200
+    busy = torch.from_numpy(np.sort(rng.choice(rows, 3 * per_col, replace=False))).to(dev)
+    col = torch.arange(lo, hi, device=dev)
+    spike = ((col[None, :] + busy[:, None]) % 3 == 0).float() * (0.3 + 0.5 * torch.rand((len(busy), hi - lo), device=dev))
+    x[busy, lo:hi] = spike
+    args = (xq, ts, lambda p: p, DETECT["thresh"], DETECT["src_t_kernel"], DETECT["dt_win"], DETECT["break_win"], DETECT["tc_win"], DETECT["sp_win"])
+    kw = {} if max_unit_cols is None else {"max_unit_cols": int(max_unit_cols)}
+    out = {"rows": rows, "columns": n_cols, "block_width": width, "candidates_per_column": per_col, "max_unit_cols": max_unit_cols}
+    for rep in range(2):                                  # the first pass warms up (allocator, first launches)
+        det = postproc.OnlineDetector(*args, device=dev, **kw)
+        ms, held, released, at = [], [], [], []
+        torch.cuda.synchronize()
+        for a in range(0, hi, width):                     # (the quiet end and `finish` are not part of the figures)
+            t0 = time.perf_counter()
+            s = det.push(a, x[:, a:a + width])
+            torch.cuda.synchronize()
+            ms.append((time.perf_counter() - t0) * 1e3)
+            held.append(det.held)
+            released.append(len(s) > 0)
+            at.append(a)
+    ms, held, released, at = np.asarray(ms), np.asarray(held), np.asarray(released), np.asarray(at)
+    quarters = []
+    for q in range(4):
+        m = (at >= lo + q * (hi - lo) // 4) & (at < lo + (q + 1) * (hi - lo) // 4) & ~released
+        quarters.append({"pushes": int(m.sum()), "ms_median": round(float(np.median(ms[m])), 3), "ms_p90": round(float(np.percentile(ms[m], 90)), 3),
+                         "held_median": int(np.median(held[m]))})
+    out.update({"quarters_of_the_stretch": quarters, "held_max": int(held.max()), "releasing_pushes": int(released.sum()),
+                "releasing_ms_median": round(float(np.median(ms[released])), 3) if released.any() else None})
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--active-cols", type=int, default=0, help="run ONLY the active-stretch measurement, on an axis of this many columns")
+    ap.add_argument("--active-rows", type=int, default=10000)
+    ap.add_argument("--active-width", type=int, default=2)
+    ap.add_argument("--active-per-col", type=int, default=40)
+    ap.add_argument("--max-unit-cols", type=int, default=0, help="the detector's limit in the active-stretch measurement (0: none)")
     ap.add_argument("--seconds", type=float, default=3600.0)
     ap.add_argument("--chunk", type=float, default=1.0)
     ap.add_argument("--tail-batch", type=int, default=16)
@@ -104,6 +156,16 @@ def main():
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = "cuda:0"
+    if a.active_cols:
+        line = {"tool": "online_detect_ab", "active_stretch": active_stretch(dev, a.active_rows, a.active_cols, a.active_width, a.active_per_col,
+                                                                             a.max_unit_cols or None), "detect": DETECT,
+                "device": torch.cuda.get_device_name(0)}
+        print(json.dumps(line))
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(json.dumps(line, indent=1) + "\n")
+        return
     S, G, _, L_box, nq = synthetic.CONFIGS["cfg2_200x10k"]
     geom = synthetic.Geometry(S, G, L=L_box, n_query=nq, seed=1)
     torch.manual_seed(0)
