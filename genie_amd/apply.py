@@ -1263,6 +1263,36 @@ def online_marching_verdicts(decided, rows, t_low, tq, tc_win, keep_flags):
     return keep, decided[decided[:, 3] >= first - reach]
 
 
+_OnlinePlan = collections.namedtuple("_OnlinePlan", "tsteps_abs times offsets h_cols frontiers tail_batch ring_min ring_cols scale")
+
+
+def online_day_plan(tsteps_abs, times, max_t, t_win, step_size, tail_batch, n_grids, ring_cols=None):
+    """What `OnlineDay` knows of its schedule before it touches a device, host arithmetic only: the axis, the candidate window starts
+    (`times`, or the default ones: `window_schedule` for stand-in picks at both ends of the axis), the offsets, the column table
+    `h_cols`, `online_frontiers`, `online_ring_min`, the ring's size and `scale`, the fp32 reciprocal of `n_overlap * n_grids`. The
+    number of grid legs enters through `n_grids` and therefore through `scale` ALONE: the table, the frontiers, the ready rule and the
+    ring minimum are functions of the schedule (none of `online_ready`, `online_frontiers`, `online_batch_spans`, `online_ring_min`
+    takes a leg argument), because every leg runs every window and all legs of a window add into the same columns in one launch."""
+    tsteps_abs = np.asarray(tsteps_abs, dtype=np.float64)
+    # `window_schedule` for stand-in picks at both ends of the axis: the offsets, the overlap and the default window starts
+    ends = [tsteps_abs[0] + t_win / 2.0 + max_t, tsteps_abs[-1] - t_win / 2.0]
+    dt_win = window_schedule(ends, max_t, np.inf, t_win, 9, step_size)[4]
+    tsteps, offsets, _, n_overlap, _ = window_schedule([ends[0], ends[1] + dt_win / 2.0], max_t, np.inf, t_win, 9, step_size)
+    times = np.asarray(tsteps if times is None else times, dtype=np.float64).reshape(-1)
+    if not is_ascending(times):
+        raise ValueError("OnlineDay: times must ascend (windows run in the order in which they become ready)")
+    h_cols = window_cols_table(tsteps_abs, times, offsets, step_size == "half", True)
+    frontiers = online_frontiers(h_cols, len(tsteps_abs))
+    tail_batch = int(tail_batch)
+    if not 1 <= tail_batch <= engine.HipPath.MAX_BATCH:
+        raise ValueError("OnlineDay: tail_batch must be in [1, %d]" % engine.HipPath.MAX_BATCH)
+    ring_min = online_ring_min(h_cols, len(tsteps_abs), tail_batch)
+    ring_cols = int(ring_min if ring_cols is None else ring_cols)
+    if ring_cols < ring_min:
+        raise ValueError("OnlineDay: ring_cols = %d is below the minimum of this schedule, %d columns (online_ring_min)" % (ring_cols, ring_min))
+    return _OnlinePlan(tsteps_abs, times, offsets, h_cols, frontiers, tail_batch, ring_min, ring_cols, _stack_scale(n_overlap, n_grids)[1])
+
+
 class OnlineDay(object):
     """The day's apply loop fed as the picks arrive: `feed(P_chunk, t_now)` runs every window that has become ready and returns the
     columns of `Out_2` that closed, `(first_col, block [Q, n] float32 on the device)` with n possibly 0 -- the shape
@@ -1270,9 +1300,10 @@ class OnlineDay(object):
     columns returned so far. Memory is bounded: the picks live in a `PickStore` trimmed behind the windows, `Out_2` exists only as a
     ring of `ring_cols` open columns.
 
-    `net`: the model (adjacencies set), or its `GridLeg`; `geom`: anything with `x_grid` and `x_query` (Cartesian); `trv_times`
-    [G, S, 2] (or [N, 2] rows with `pairs`, as `GridLeg` takes them). `tsteps_abs`: the column axis, ascending, REQUIRED -- the
-    offline default depends on the day's last pick. `times`: the candidate window starts, ascending; default: `_day_schedule`'s
+    `net`: the model (adjacencies set), its `GridLeg`, or a list / tuple of 1..`engine.STACK_MAX_LEGS` `GridLeg`s, one per source grid
+    (below); `geom`: anything with `x_query` (Cartesian; and `x_grid`, read for a bare model only); `trv_times` [G, S, 2] (or [N, 2]
+    rows with `pairs`, as `GridLeg` takes them; read for a bare model, and for the default `max_t` of one leg). `tsteps_abs`: the
+    column axis, ascending, REQUIRED -- the offline default depends on the day's last pick. `times`: the candidate window starts, ascending; default: `_day_schedule`'s
     windows for picks spanning the axis, i.e. from `tsteps_abs[0] + t_win / 2` in steps of `step_size` while the window's centre lies on
     the axis. Per candidate, WHEN IT BECOMES READY, `windows_with_enough_picks(min_required_picks)` and the empty-range rule decide
     whether it runs; a window they drop counts as run. (Offline, an explicit `times=` is taken as filtered already: the two agree
@@ -1298,7 +1329,19 @@ class OnlineDay(object):
     into chunks: a column's sum is one fp32 running sum over its windows in ascending order in both loops, and a window's read-out does
     not depend on how windows are grouped into batched tails (tests/test_hip_parity.py pins every window of a batched tail, batches of
     1, 3, 8 and 16, bit-equal to the plain forward). Not built (NotImplementedError): a source-node-sharded model, `window_parallel`,
-    `merge="columns"`, more than one leg. Detection on the closed blocks as they arrive: `postproc.OnlineDetector`
+    `merge="columns"`, two legs that share one model (their pending windows would interleave: build one model per leg).
+
+    Several legs (the reference's `for window: for grid:` loop, process_continuous_days.py:761-810): every ready window runs on every
+    leg in leg order, every leg flushes its batched tail, and ONE genie_stack_windows_ring launch per batch adds all legs' read-outs
+    in (window, leg) order, scaled by `1 / (n_overlap * L)` (`n_grids` must be left at its default, or be L; with one leg it keeps its
+    meaning). The legs share one device, one station set (one `PickStore`), one ring and one `max_t` (required). `lanes`: the legs;
+    `lane` = `lanes[0]`. `window_batch` is set on every leg's model and checked at every `feed`; the verdicts of every leg are raised
+    after the call's one wait. Nothing of the schedule depends on L -- `ring_min`, the frontiers, the ready rule, the trim and
+    `retain_from` are those of one leg (`online_day_plan`) -- so the contract is the same sentence with
+    `apply_windows_legs(legs, ResidentPicks(...), ..., tsteps_abs=, times=, tail_batch=)` as the twin: a column's sum is one fp32
+    running sum over (window, leg) in both loops. `OnlineDay([leg])` IS `OnlineDay(leg)`.
+
+    Detection on the closed blocks as they arrive: `postproc.OnlineDetector`
     (`det.push(*day.feed(P_chunk, t_now))`).
 
     A restart: `state_dict()` between any two `feed` calls (everything `feed` has changed, on the host) and `load_state_dict(state)` on
@@ -1308,47 +1351,57 @@ class OnlineDay(object):
     def __init__(self, net, geom, trv_times, tsteps_abs, times=None, t_win=6.0, step_size="half", min_required_picks=1, n_grids=1.0,
                  kernel_sig_t=synthetic.KERNEL_SIG_T, dt_embed=None, max_t=None, tail_batch=16, pairs=None, ring_cols=None, ind_use=None,
                  n_sta_all=None, window_parallel=None, merge="dense"):
-        legs = list(net) if isinstance(net, (list, tuple)) else [net]
-        if len(legs) != 1:
-            raise NotImplementedError("OnlineDay over %d grid legs: the online loop runs one leg" % len(legs))
-        model = legs[0].net if isinstance(legs[0], GridLeg) else legs[0]
-        if getattr(model, "is_sharded", False):
-            raise NotImplementedError("OnlineDay on a source-node-sharded model: batched tails do not run on shards; use an unsharded model")
+        items = list(net) if isinstance(net, (list, tuple)) else [net]
+        n_legs = len(items)
+        if n_legs == 0:
+            raise ValueError("OnlineDay: no grid leg")
+        if n_legs > engine.STACK_MAX_LEGS:
+            raise ValueError("OnlineDay: at most %d grid legs" % engine.STACK_MAX_LEGS)
+        if n_legs > 1 and not all(isinstance(item, GridLeg) for item in items):
+            raise ValueError("OnlineDay: a list of %d items holds a bare model, which has no grid and no travel-time table of its own; "
+                             "pass one GridLeg per grid" % n_legs)
+        models = [item.net if isinstance(item, GridLeg) else item for item in items]
+        if any(getattr(model, "is_sharded", False) for model in models):
+            raise NotImplementedError("OnlineDay on a source-node-sharded model: batched tails do not run on shards; use an unsharded model"
+                                      + (" per grid" if n_legs > 1 else ""))
         if window_parallel is not None and window_parallel is not False:
             raise NotImplementedError("OnlineDay with window_parallel: the online loop runs on one GPU")
         if merge != "dense":
             raise NotImplementedError('OnlineDay with merge="%s": the online loop returns dense blocks of closed columns' % (merge,))
+        if n_legs > 1:                            # the checks of `apply_windows_legs`, on the legs alone: nothing is allocated yet
+            for l, leg in enumerate(items):
+                if torch.device(leg.device) != torch.device(items[0].device):
+                    raise ValueError("OnlineDay: leg %d lives on %s, leg 0 on %s" % (l, leg.device, items[0].device))
+                if leg.n_sta != items[0].n_sta:
+                    raise ValueError("OnlineDay: leg %d has %d stations, leg 0 has %d (one station set, one pick store)"
+                                     % (l, leg.n_sta, items[0].n_sta))
+            if len({id(model) for model in models}) != n_legs:
+                raise NotImplementedError("OnlineDay: two legs share one model (their pending windows would interleave); build one model "
+                                          "per leg")
+            if len({bool(getattr(model, "use_phase_types", True)) for model in models}) != 1:
+                raise ValueError("OnlineDay: the legs' models disagree on use_phase_types (one pick store serves all legs)")
+            if n_grids != 1.0 and n_grids != n_legs:
+                raise ValueError("OnlineDay: n_grids = %r with %d legs (the divisor is n_overlap * %d, as apply_windows_legs computes it; "
+                                 "leave n_grids at its default)" % (n_grids, n_legs, n_legs))
+            if max_t is None:
+                raise ValueError("OnlineDay: max_t is required with several legs (one max_t for the day, whichever grids run)")
+            n_grids = n_legs
         if tsteps_abs is None or not is_ascending(tsteps_abs) or len(tsteps_abs) == 0:
             raise ValueError("OnlineDay: tsteps_abs is required and must ascend (the offline default needs the day's last pick)")
-        tsteps_abs = np.asarray(tsteps_abs, dtype=np.float64)
         self.max_t = float(max_t if max_t is not None else np.ceil(np.asarray(trv_times).max() + 1.0))
         self.t_win, self.kernel_sig_t, self.min_required_picks = float(t_win), float(kernel_sig_t), min_required_picks
-        # `window_schedule` for stand-in picks at both ends of the axis: the offsets, the overlap and the default window starts
-        ends = [tsteps_abs[0] + t_win / 2.0 + self.max_t, tsteps_abs[-1] - t_win / 2.0]
-        dt_win = window_schedule(ends, self.max_t, np.inf, t_win, 9, step_size)[4]
-        tsteps, self.offsets, _, n_overlap, _ = window_schedule([ends[0], ends[1] + dt_win / 2.0], self.max_t, np.inf, t_win, 9, step_size)
-        self.tsteps_abs = tsteps_abs
-        self.times = np.asarray(tsteps if times is None else times, dtype=np.float64).reshape(-1)
-        if not is_ascending(self.times):
-            raise ValueError("OnlineDay: times must ascend (windows run in the order in which they become ready)")
-        self.step_size = step_size
-        self.h_cols = window_cols_table(tsteps_abs, self.times, self.offsets, step_size == "half", True)
-        self.frontiers = online_frontiers(self.h_cols, len(tsteps_abs))
-        self.tail_batch = int(tail_batch)
-        if not 1 <= self.tail_batch <= engine.HipPath.MAX_BATCH:
-            raise ValueError("OnlineDay: tail_batch must be in [1, %d]" % engine.HipPath.MAX_BATCH)
-        self.ring_min = online_ring_min(self.h_cols, len(tsteps_abs), self.tail_batch)
-        self.ring_cols = int(self.ring_min if ring_cols is None else ring_cols)
-        if self.ring_cols < self.ring_min:
-            raise ValueError("OnlineDay: ring_cols = %d is below the minimum of this schedule, %d columns (online_ring_min)"
-                             % (self.ring_cols, self.ring_min))
-        _, self.scale = _stack_scale(n_overlap, n_grids)
-        self.lane = legs[0] if isinstance(legs[0], GridLeg) else GridLeg(model, geom.x_grid, trv_times, pairs=pairs)
+        plan = online_day_plan(tsteps_abs, times, self.max_t, t_win, step_size, tail_batch, n_grids, ring_cols)
+        self.tsteps_abs, self.times, self.offsets, self.step_size = plan.tsteps_abs, plan.times, plan.offsets, step_size
+        self.h_cols, self.frontiers, self.tail_batch = plan.h_cols, plan.frontiers, plan.tail_batch
+        self.ring_min, self.ring_cols, self.scale = plan.ring_min, plan.ring_cols, plan.scale
+        self.lanes = [item if isinstance(item, GridLeg) else GridLeg(item, geom.x_grid, trv_times, pairs=pairs) for item in items]
+        self.lane = self.lanes[0]                 # (the one-leg name, kept for its readers)
         dev = self.lane.device
-        model.window_batch = self.tail_batch
+        for model in models:
+            model.window_batch = self.tail_batch
         n_sta = self.lane.n_sta
         self.picks = PickStore(np.arange(n_sta) if ind_use is None else ind_use, n_sta if n_sta_all is None else n_sta_all, dev,
-                               use_phase_types=getattr(model, "use_phase_types", True))
+                               use_phase_types=getattr(models[0], "use_phase_types", True))
         self.dt_embed = _dt_embed(kernel_sig_t, dt_embed)
         self.t_now = -np.inf
         self.retain_from = np.inf                 # `feed` keeps every pick with t >= this, whatever the windows still read
@@ -1360,7 +1413,7 @@ class OnlineDay(object):
             self.ring = torch.zeros((np.asarray(geom.x_query).shape[0], self.ring_cols), dtype=torch.float32, device=dev)
             self.d_cols = torch.from_numpy(self.h_cols).to(dev)
             xq = torch.as_tensor(geom.x_query).float().to(dev)
-            self.body = _WindowBody([self.lane], xq, self.offsets, self.max_t, self.kernel_sig_t, self.dt_embed)
+            self.body = _WindowBody(self.lanes, xq, self.offsets, self.max_t, self.kernel_sig_t, self.dt_embed)
 
     def _close(self, blocks, upto):
         """On the stacker stream: the columns [closed, upto) leave the loop as blocks appended to `blocks` -- out of the ring (one
@@ -1378,9 +1431,11 @@ class OnlineDay(object):
         t_now = float(t_now)
         if not t_now >= self.t_now:
             raise ValueError("OnlineDay.feed: t_now = %r after t_now = %r (it never decreases)" % (t_now, self.t_now))
-        net, n, first_col, blocks = self.lane.net, len(self.times), self.closed, []
-        if net.window_batch != self.tail_batch:
-            raise RuntimeError("OnlineDay.feed: the model's window_batch was changed to %d (this loop set %d)" % (net.window_batch, self.tail_batch))
+        n, first_col, blocks = len(self.times), self.closed, []
+        for lane in self.lanes:
+            if lane.net.window_batch != self.tail_batch:
+                raise RuntimeError("OnlineDay.feed: the model's window_batch was changed to %d (this loop set %d)"
+                                   % (lane.net.window_batch, self.tail_batch))
         if P_chunk is not None and (self.n_run < n or self.retain_from < np.inf):      # (after the last window only a reader behind
             self.picks.append(P_chunk)                       # the windows, `retain_from`, reads a pick) a pick older than frozen_t raises here
         self.t_now = t_now
@@ -1413,7 +1468,8 @@ class OnlineDay(object):
             block.record_stream(body.main)
             body.join()
         body.main.synchronize()                              # this call's one wait
-        _check_verdicts(net)
+        for lane in self.lanes:
+            _check_verdicts(lane.net)
         first_read = online_read_bounds(self.times[self.n_run:self.n_run + 1], self.max_t, self.kernel_sig_t, self.t_win)[0]
         first_read = float(first_read[0]) if self.n_run < n else np.inf
         self.picks.frozen_t = min(first_read, t_now)         # (a pick from t_now on that no window reads any more is not late: it is trimmed)
@@ -1421,7 +1477,8 @@ class OnlineDay(object):
         return first_col, block
 
     def _add(self, xs, ws):
-        """One genie_stack_windows_ring launch for the read-outs `xs` of the candidate windows `ws` (ascending; contiguous unless the
+        """One genie_stack_windows_ring launch for the read-outs `xs` (one per leg, in leg order) of the candidate windows `ws`
+        (ascending; contiguous unless the
         filters dropped one in between: then their rows of the table are gathered on the device)."""
         used = self.h_cols[ws]
         used = used[used >= 0]
@@ -1439,7 +1496,7 @@ class OnlineDay(object):
         return {"tsteps_abs": self.tsteps_abs, "times": self.times, "offsets": self.offsets, "step_size": self.step_size,
                 "scale": self.scale, "tail_batch": self.tail_batch, "max_t": self.max_t, "kernel_sig_t": self.kernel_sig_t,
                 "t_win": self.t_win, "min_required_picks": self.min_required_picks, "dt_embed": self.dt_embed,
-                "n_query": int(self.ring.shape[0])}
+                "n_query": int(self.ring.shape[0]), "n_legs": len(self.lanes)}
 
     def _state(self):
         """`state_dict()` before the copy to the host: the open columns are still a device tensor."""
@@ -1767,6 +1824,17 @@ class OnlineCatalogue(object):
     5. `trv(locs, srcs)` is called on the few sources of a push, offline on all of them at once: THE CALLABLE'S ROWS MUST NOT DEPEND ON
        THE BATCH (row i a function of `srcs[i]` alone, bit for bit), as the straight-ray callable of `synthetic.Geometry` is.
 
+    Several legs: the catalogue runs over `day.lanes` -- `refine_sources` and `associate_sources` take all of them, as
+    `detect_refine_associate(legs, ...)` does offline, the verdicts of every leg are raised at the end of each call, and the device
+    tensors live on the legs' one device. The twin is then `apply_windows_legs(legs, ...)` -> `detect_refine_associate(legs, ...)`. None
+    of the rules reads the grid:
+    1. every leg embeds the same pick range (`GridLeg.embed` -> `picks.embed_args(t0, max_t, sigma)`: one store, one `max_t`), and the
+       cloud's key is the source's place in the list, not a leg's;
+    2. `online_source_ready` takes `t_det`, `tq`, `max_t` and sigma, which the legs share;
+    3. `online_retain_from` likewise; `lp_meta` comes from the store, once per source whatever L is;
+    4. the marching sees refined sources only -- the mean over the legs was taken before;
+    5. `trv(locs, srcs)` takes stations and sources, no grid.
+
     `rand` must be a `PhiloxCloud` and `ftrns2_device` must be given (ValueError): a stateful draw or the host cloud has no offline twin
     that a sub-list reproduces. `pick_lists`: how the association pass makes its pick lists (`associate_sources`; "device" here, one launch per source: at the
     few hundred picks of a window it takes about half the time of the torch statements, profiles/EXPERIMENTS.md). There is no
@@ -1787,7 +1855,8 @@ class OnlineCatalogue(object):
             raise ValueError('OnlineCatalogue: pick_lists must be "torch" or "device"')
         if len(det.tsteps_abs) != len(day.tsteps_abs) or not np.array_equal(det.tsteps_abs, day.tsteps_abs):
             raise ValueError("OnlineCatalogue: day and det must share one tsteps_abs")
-        self.day, self.det, self.leg = day, det, day.lane
+        self.day, self.det, self.legs = day, det, list(day.lanes)
+        self.device = self.legs[0].device         # (`OnlineDay` has checked that the legs share one device)
         self.trv, self.ftrns1, self.ftrns2, self.ftrns2_device, self.rand = trv, ftrns1, ftrns2, ftrns2_device, rand
         self.tq = np.asarray(tq.detach().cpu() if torch.is_tensor(tq) else tq, dtype=np.float64).reshape(-1)
         self.ranges = (lat_range, lon_range, depth_range)
@@ -1796,7 +1865,7 @@ class OnlineCatalogue(object):
         self.scale_depth_clustering, self.t_win_assoc, self.pick_lists = scale_depth_clustering, t_win_assoc, pick_lists
         locs = np.asarray(locs, dtype=np.float64)
         self.locs_cart = ftrns1(locs)
-        self.locs_d = torch.as_tensor(locs).float().to(self.leg.device)
+        self.locs_d = torch.as_tensor(locs).float().to(self.device)
         self.x_save = np.array([lat_range[0], lon_range[0], 0.0])                 # as `detect_refine_associate` takes it
         self.n_released = 0                       # sources released so far: the next one's place in the day's detection list
         self._pending = np.zeros((0, 5))          # released, not run (ascending origin time)
@@ -1817,11 +1886,11 @@ class OnlineCatalogue(object):
 
     def _run(self, srcs):
         """Refine and associate the sources `srcs` (the head of `_pending`), and file the results by refined time."""
-        day, legs = self.day, [self.leg]
+        day, legs = self.day, self.legs
         rows, _ = refine_sources(legs, day.picks, srcs, self.locs_cart, self.tq, day.max_t, self.offsets[0], self.offsets[1],
                                  self.n_rand_query, self.ftrns1, self.ftrns2, *self.ranges, day.kernel_sig_t, day.dt_embed, self.rand,
                                  self.ftrns2_device, source_offset=self.n_released - self._pending.shape[0])
-        dev = self.leg.device
+        dev = self.device
         with torch.no_grad():
             trv_out = self.trv(self.locs_d, torch.as_tensor(rows[:, 0:3]).float().to(dev)).detach()
         res = associate_sources(legs, day.picks, rows, self.locs_cart, self.tq, day.max_t, trv_out, self.ftrns1, self.x_save,
@@ -1836,7 +1905,7 @@ class OnlineCatalogue(object):
         from . import postproc
         march = lambda srcs: postproc.local_marching_keep_device(srcs, self.ftrns1, tc_win=self.tc_win, sp_win=self.sp_win, n_steps_max=2,
                                                                  scale_depth=self.scale_depth_clustering, use_directed=False,
-                                                                 device=self.leg.device)
+                                                                 device=self.device)
         keep, self._decided = online_marching_verdicts(self._decided, self._rows, self._t_low(), self.tq, self.tc_win, march)
         n = len(keep)
         rows, results = self._rows[:n][keep], [r for r, k in zip(self._results[:n], keep) if k]
@@ -1864,10 +1933,11 @@ class OnlineCatalogue(object):
         if last:                                  # nothing reads a pick any more
             day.retain_from = np.inf
             day.picks.trim(np.inf)
-        self.leg.check()
+        for leg in self.legs:
+            leg.check()
         n_sta = int(self.locs_d.shape[0])
         return {"srcs": srcs, "srcs_refined": rows,
-                "trv_out_srcs": torch.stack([r[0] for r in results]) if results else torch.zeros((0, n_sta, 2), device=self.leg.device),
+                "trv_out_srcs": torch.stack([r[0] for r in results]) if results else torch.zeros((0, n_sta, 2), device=self.device),
                 "Out_p_save": [r[1] for r in results], "Out_s_save": [r[2] for r in results],
                 "Save_picks": [r[3] for r in results], "lp_meta": [r[4] for r in results]}
 
@@ -1899,7 +1969,7 @@ class OnlineCatalogue(object):
     def load_state_dict(self, state):
         """Resume all three objects from one `state_dict()`, or none: this object, its day and its detector must be newly constructed
         (RuntimeError otherwise) with the arguments of the saved ones, and all three fingerprints are compared before anything changes
-        (ValueError naming the first differing field). The results of the undecided sources go back onto the leg's device."""
+        (ValueError naming the first differing field). The results of the undecided sources go back onto the legs' device."""
         if not isinstance(state, dict) or sorted(state) != ["catalogue", "day", "det"]:
             raise ValueError('OnlineCatalogue.load_state_dict: a state has the keys "day", "det" and "catalogue"')
         if self.n_released or self.pending or self.undecided or self._decided.shape[0]:
@@ -1910,7 +1980,7 @@ class OnlineCatalogue(object):
         checkpoint.check_fingerprint("OnlineCatalogue", own, self._fingerprint())
         self.day._load_state(state["day"])
         self.det._load_state(state["det"])
-        dev = self.leg.device
+        dev = self.device
         f64 = lambda a: np.array(a, dtype=np.float64).reshape(-1, 5)
         self.n_released = int(own["n_released"])
         self._pending, self._rows, self._decided = f64(own["pending"]), f64(own["rows"]), f64(own["decided"])

@@ -1,14 +1,18 @@
 """The online day loop against the offline one on the same synthetic hour, in ONE process on one GPU: the config-5 stream shape of
 `tools/stack_ab.py` (200 stations x 10 000 grid nodes, 10 000 queries, ~250 picks per station and day, windows at 1 s stride).
 
-  timeout -k 10 900 python tools/online_feed_ab.py [--out FILE.json] [--seconds 3600] [--chunk 1.0] [--tail-batch 16] [--rounds 3]
+  timeout -k 10 900 python tools/online_feed_ab.py [--out FILE.json] [--seconds 3600] [--chunk 1.0] [--tail-batch 16] [--rounds 3] [--legs 1]
 
 Online arm: `apply.OnlineDay` fed the hour's picks in chunks of `--chunk` seconds (`feed(picks of [t, t + chunk), t + chunk)`, then
 `finish()`); every `feed` is timed on the host around its own synchronisation: median, 90th percentile and maximum in ms, the number of
 calls, the windows the busiest call ran, the ring's size and the peak device memory of the arm. Offline arm: one
 `apply_windows_device(stack_on_device=True)` over the same `tsteps_abs` / `times`, wall time of the whole loop. After one warm-up each
 the arms alternate `--rounds` times; every run is printed. The two `Out_2` are asserted bit-equal. No threshold: the figures are for
-`profiles/EXPERIMENTS.md`."""
+`profiles/EXPERIMENTS.md`.
+
+`--legs N` (1..32): N models with weights of their own on N source grids over the one station set (leg l: 10 000 - 16 l nodes of the
+same seed, which leaves the stations where they are); the online arm is `OnlineDay(legs, ...)`, the offline arm
+`apply_windows_legs(legs, ...)` on the same resident picks. With N = 1 the arms are the ones above."""
 import argparse
 import json
 import os
@@ -28,6 +32,7 @@ def main():
     ap.add_argument("--chunk", type=float, default=1.0)
     ap.add_argument("--tail-batch", type=int, default=16)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--legs", type=int, default=1)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = "cuda:0"
@@ -35,9 +40,21 @@ def main():
     geom = synthetic.Geometry(S, G, L=L_box, n_query=nq, seed=1)
     torch.manual_seed(0)
     trv = geom.travel_times().astype(np.float32)
-    net = module.GCN_Detection_Network_extended(lambda x: x, lambda x: x, device=dev).eval()
-    net.set_adjacencies_base(torch.from_numpy(geom.A_sta_sta), torch.from_numpy(geom.A_src_src), torch.from_numpy(geom.edge_attr()).to(dev),
-                             torch.from_numpy(geom.locs).float().to(dev), torch.from_numpy(geom.x_grid).float().to(dev))
+
+    def model_on(g):
+        net = module.GCN_Detection_Network_extended(lambda x: x, lambda x: x, device=dev).eval()
+        net.set_adjacencies_base(torch.from_numpy(g.A_sta_sta), torch.from_numpy(g.A_src_src), torch.from_numpy(g.edge_attr()).to(dev),
+                                 torch.from_numpy(g.locs).float().to(dev), torch.from_numpy(g.x_grid).float().to(dev))
+        return net
+
+    net = model_on(geom)
+    legs = [apply.GridLeg(net, geom.x_grid, trv)]
+    for l in range(1, a.legs):                       # (in leg order: the models draw their weights from the one seeded stream)
+        g = synthetic.Geometry(S, G - 16 * l, L=L_box, n_query=nq, seed=1)
+        assert np.array_equal(g.locs, geom.locs)
+        trv_l = g.travel_times().astype(np.float32)
+        assert trv_l.max() + 1.0 <= np.ceil(trv.max() + 1.0)
+        legs.append(apply.GridLeg(model_on(g), g.x_grid, trv_l))
     rng = np.random.default_rng(5)
     t_lo = 1000.0
     n = int(250 * S * a.seconds / 86400.0)
@@ -49,11 +66,12 @@ def main():
     kw = dict(times=times, max_t=max_t, dt_embed=0.3, tail_batch=a.tail_batch)
     cuts = t_lo + a.chunk * np.arange(1, int(np.ceil((a.seconds + max_t + 12.0) / a.chunk)) + 1)
     edges = np.searchsorted(P[:, 0], cuts, side="left")
+    resident = apply.ResidentPicks(P, np.arange(S), S, dev) if a.legs > 1 else None
 
     def online():
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
-        day = apply.OnlineDay(net, geom, trv, tsteps_abs, **kw)
+        day = apply.OnlineDay(net if a.legs == 1 else legs, geom, trv, tsteps_abs, **kw)
         blocks, ms, ran, lo = [], [], [], 0
         for t_now, hi in zip(cuts, edges):
             before = day.n_run
@@ -74,7 +92,11 @@ def main():
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         t0 = time.perf_counter()
-        out, used = apply.apply_windows_device(net, geom, P, trv, tsteps_abs=tsteps_abs, stack_on_device=True, **kw)
+        if a.legs == 1:
+            out, used = apply.apply_windows_device(net, geom, P, trv, tsteps_abs=tsteps_abs, stack_on_device=True, **kw)
+        else:
+            out, used = apply.apply_windows_legs(legs, resident, geom.x_query, geom.locs, max_t, tsteps_abs=tsteps_abs, times=times,
+                                                 dt_embed=0.3, tail_batch=a.tail_batch)
         torch.cuda.synchronize()
         wall = time.perf_counter() - t0
         return out, {"wall_s": round(wall, 4), "windows_run": len(used), "ms_per_window": round(wall / max(len(used), 1) * 1e3, 4),
@@ -89,7 +111,7 @@ def main():
         equal = bool(torch.equal(out_on, out_off))
         runs.append({"round": r, "online": res_on, "offline": res_off, "out_2_bit_equal": equal})
         del out_on, out_off
-    line = {"tool": "online_feed_ab", "shape": "config 5 stream: %d stations x %d grid nodes, %d queries, 1 s stride, tail_batch %d" % (
+    line = {"tool": "online_feed_ab", "legs": a.legs, "shape": "config 5 stream: %d stations x %d grid nodes, %d queries, 1 s stride, tail_batch %d" % (
         S, G, nq, a.tail_batch), "seconds": a.seconds, "chunk_s": a.chunk, "picks": n, "columns": len(tsteps_abs), "runs": runs,
         "device": torch.cuda.get_device_name(0)}
     print(json.dumps(line))
