@@ -38,6 +38,7 @@ SYMBOLS = [
     ("genie_set_phase_types", _c.c_int, [_P, _c.c_int]),
     ("genie_set_sign_input", _c.c_int, [_P, _c.c_int]),
     ("genie_set_stage2_workmap", _c.c_int, [_P, _c.c_int]),
+    ("genie_set_tail_packing", _c.c_int, [_P, _c.c_int]),
     ("genie_set_subgraph_stations", _c.c_int, [_P, _P, _P]),
     ("genie_set_tail_precision", _c.c_int, [_P, _c.c_int]),
     ("genie_set_stage_precision", _c.c_int, [_P, _c.c_int]),

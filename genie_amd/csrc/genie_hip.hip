@@ -34,6 +34,7 @@
 
 #include "genie_hip.h"
 #include "s2u_plan.hpp"
+#include "tile_items.hpp"
 
 // read-once rows (c, Mask, edge_attr of stage 2): plain loads (non-temporal ones measured slower, 0.354 vs 0.326 ms)
 #define GENIE_LD_STREAM(ptr) (*(ptr))
@@ -1337,6 +1338,7 @@ struct genie_ctx {
     int use_fast;              // the reference's kNN graphs (ks_uni == 8 && kp_uni == 15): the pipelined kernels k_stage1_h2 / k_stage2_ord apply
     int bpc2o;                 // workgroups of k_stage2_ord per CU (its occupancy: three per CU)
     int s2_wgmap;              // k_stage2_ord: blocks of 4 source nodes per workgroup (large station counts)
+    bool no_tail_pack;         // k_stage1_h2 keeps padded station tail tiles where it would pack them (genie_set_tail_packing: the A/B form)
     int bpc1b;                 // workgroups of k_stage1_h2 per CU in the grid (one is resident; more = dynamic balancing by the dispatcher)
     int use_h2;                // the SHAPE admits the f16x2 kernels (k_stage1_h2 / k_stage2_h2u): uniform 8 / 15-degree graphs, 24-bit
                                // multiplicands; whether they run is h2_on(): precision mode + the fp16 range guard below
@@ -2459,18 +2461,18 @@ size_t genie_workspace_bytes(const genie_ctx* c) { return c ? c->ws_floats * siz
 
 namespace {
 // k_stage1_h2's variants: absolute positions or edge terms (never both: stage_routes sends that model to the generic kernel), 64-bit
-// row offsets (big)
-extern "C++" template <bool PCSR>
+// row offsets (big), packed station tail tiles (MIX: tile_items.hpp)
+extern "C++" template <bool PCSR, bool MIX = false>
 void launch_stage1_h2(const DaArgs& a, bool abs, bool edges, bool big, int grid, hipStream_t st) {
     if (abs) {
-        if (big) k_stage1_h2<8, 15, false, true, true, PCSR><<<grid, H2_THREADS, 0, st>>>(a);
-        else k_stage1_h2<8, 15, false, false, true, PCSR><<<grid, H2_THREADS, 0, st>>>(a);
+        if (big) k_stage1_h2<8, 15, false, true, true, PCSR, MIX><<<grid, H2_THREADS, 0, st>>>(a);
+        else k_stage1_h2<8, 15, false, false, true, PCSR, MIX><<<grid, H2_THREADS, 0, st>>>(a);
     } else if (edges) {
-        if (big) k_stage1_h2<8, 15, true, true, false, PCSR><<<grid, H2_THREADS, 0, st>>>(a);
-        else k_stage1_h2<8, 15, true, false, false, PCSR><<<grid, H2_THREADS, 0, st>>>(a);
+        if (big) k_stage1_h2<8, 15, true, true, false, PCSR, MIX><<<grid, H2_THREADS, 0, st>>>(a);
+        else k_stage1_h2<8, 15, true, false, false, PCSR, MIX><<<grid, H2_THREADS, 0, st>>>(a);
     } else {
-        if (big) k_stage1_h2<8, 15, false, true, false, PCSR><<<grid, H2_THREADS, 0, st>>>(a);
-        else k_stage1_h2<8, 15, false, false, false, PCSR><<<grid, H2_THREADS, 0, st>>>(a);
+        if (big) k_stage1_h2<8, 15, false, true, false, PCSR, MIX><<<grid, H2_THREADS, 0, st>>>(a);
+        else k_stage1_h2<8, 15, false, false, false, PCSR, MIX><<<grid, H2_THREADS, 0, st>>>(a);
     }
 }
 
@@ -2565,7 +2567,10 @@ int run_stage1(genie_ctx* c, const StageCall& call, const float* slice, const fl
         }
         a.xs = xs; a.packed = c->packed_h2; a.xs_plane = c->P_ext * (long long)XPC;
         a.np = r.layout == RowLayout::NodePlanar ? 1 : 0;
-        const int grid = da_grid_w(c, (n_tiles + 1) / 2, c->bpc1b, H2_THREADS / 64);
+        // S mod 16 in 1 .. 8: the half-empty tail tiles of two adjacent source nodes share one item (tile_items.hpp)
+        const bool mix = tile_items::packs(c->S) && !c->no_tail_pack;
+        const long long n_items = mix ? n_tiles - a.G / 2 : n_tiles;      // (grid size only: the kernel counts its chunks' items itself)
+        const int grid = da_grid_w(c, (n_items + 1) / 2, c->bpc1b, H2_THREADS / 64);
         if (!n_tiles) break;
         if (c->abs_sta && (c->abs_dirty || !c->abs_ts || c->abs_ts_order != (so ? 1 : 0))) {
             // (a training forward runs in the caller's station order, inference in processing order)
@@ -2575,7 +2580,8 @@ int run_stage1(genie_ctx* c, const StageCall& call, const float* slice, const fl
             c->abs_dirty = false; c->abs_ts_order = so ? 1 : 0;
             a.abs_ts = c->abs_ts; a.abs_tg = c->abs_tg;
         }
-        launch_stage1_h2<false>(a, c->abs_sta != nullptr, c->has_edges, c->P_ext * XROW >= (1ll << 32), grid, st);
+        if (mix) launch_stage1_h2<false, true>(a, c->abs_sta != nullptr, c->has_edges, c->P_ext * XROW >= (1ll << 32), grid, st);
+        else launch_stage1_h2<false>(a, c->abs_sta != nullptr, c->has_edges, c->P_ext * XROW >= (1ll << 32), grid, st);
         break;
     }
     }
@@ -4857,6 +4863,12 @@ int genie_set_subgraph_stations(genie_ctx* c, const int32_t* sta_of_prod, void* 
     if (!c->pcsr) return fail(GENIE_ERR_STATE, "genie_set_subgraph_stations: the context is a Cartesian product graph (station = p % n_sta)");
     if (!c->p_sta_of) HIP_TRY(c->p_sta_of.alloc((size_t)c->P));
     HIP_TRY(hipMemcpyAsync(c->p_sta_of, sta_of_prod, sizeof(int32_t) * (size_t)c->P, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return GENIE_OK;
+}
+
+int genie_set_tail_packing(genie_ctx* c, int on) {
+    if (!c) return fail(GENIE_ERR_ARG, "genie_set_tail_packing: null context");
+    c->no_tail_pack = on == 0;
     return GENIE_OK;
 }
 

@@ -478,6 +478,17 @@ __device__ __forceinline__ int row_bcast_dyn(int v, int k) {     // k is a compi
         case 12: return row_bcast<12>(v); case 13: return row_bcast<13>(v); case 14: return row_bcast<14>(v); default: return row_bcast<15>(v);
     }
 }
+// ... of `hi` into lanes 8 .. 15 of the row only (DPP bank mask 0xc), lanes 0 .. 7 keep `lo`: the id of a mixed tile's upper half
+template <int K_>
+__device__ __forceinline__ int row_bcast_hi(int lo, int hi) { return __builtin_amdgcn_update_dpp(lo, hi, 0x150 + K_, 0xf, 0xc, false); }
+__device__ __forceinline__ int row_bcast_hi_dyn(int lo, int hi, int k) {
+    switch (k) {
+        case 0: return row_bcast_hi<0>(lo, hi); case 1: return row_bcast_hi<1>(lo, hi); case 2: return row_bcast_hi<2>(lo, hi); case 3: return row_bcast_hi<3>(lo, hi);
+        case 4: return row_bcast_hi<4>(lo, hi); case 5: return row_bcast_hi<5>(lo, hi); case 6: return row_bcast_hi<6>(lo, hi); case 7: return row_bcast_hi<7>(lo, hi);
+        case 8: return row_bcast_hi<8>(lo, hi); case 9: return row_bcast_hi<9>(lo, hi); case 10: return row_bcast_hi<10>(lo, hi); case 11: return row_bcast_hi<11>(lo, hi);
+        case 12: return row_bcast_hi<12>(lo, hi); case 13: return row_bcast_hi<13>(lo, hi); case 14: return row_bcast_hi<14>(lo, hi); default: return row_bcast_hi<15>(lo, hi);
+    }
+}
 template <int KS_>
 __device__ __forceinline__ void split8h(const f32x16& v, u32x4 (&p)[3], unsigned sixteenth) {
 #pragma unroll
@@ -515,8 +526,13 @@ __device__ __forceinline__ void h2_store_c(f32x4* p, f32x4 v) {
 #endif
 }
 
-template <int KS, int KP, bool EDGES, bool BIG, bool ABS = false, bool PCSR = false>
+template <int KS, int KP, bool EDGES, bool BIG, bool ABS = false, bool PCSR = false, bool MIX = false>
 __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
+    // MIX (S mod 16 in 1 .. 8, Cartesian graphs): the items of tile_items.hpp. The half-empty tail tiles of two adjacent source nodes
+    // share one row of 16 lanes, lanes 0 .. 7 for node g and 8 .. 15 for its partner: such a row carries two id lists (idv, idw) and
+    // every id is one row broadcast of idv plus one of idw into the upper half. A plain row has idw == idv. From the neighbour
+    // phase on every lane works on its own node p, so the rows a node gets are the bits of the padded tiles.
+    static_assert(!(MIX && PCSR), "an irregular product graph has no station tiles");
     // PCSR: irregular product graph (use_subgraph). A wave item is 32 consecutive product nodes; the neighbours of a node are
     // product-node ids from the product-level CSRs (at most KS / KP of them: a missing one is the node itself with weight 0,
     // the mean of an empty neighbourhood is 0); everything after the neighbour phase is the same code.
@@ -544,6 +560,9 @@ __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
     const bool hi = h != 0;
     const int S = a.S;
     ItemIter w(a.G, a.T, a.seg, a.nxcd, wave, a.gi0);
+    tile_items::Packed wp;
+    if constexpr (MIX) wp.init(w.gbeg, w.gend, a.T, a.seg);
+    const long long nitems = MIX ? wp.nitems : w.nitems;
     const char* xs = (const char*)a.xs;
     const off_t_ la = hi ? (off_t_)a.xs_plane : (off_t_)0;          // lane h = 0 loads x0, lane h = 1 loads x1: [x0 ; x1] is one K = 16 step
     const off_t_ gstride = (off_t_)((unsigned)S * (unsigned)XPC);
@@ -559,13 +578,23 @@ __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
     for (int r = 0; r < 16; ++r) biasA[r] *= 16.f;
 
     int jt = jj;
-    auto fetch_ids = [&](long long pit_, int& idv_, int& sc_, bool& valid_, int (&sta_)[KS]) {
-        int gi0, tb0, gi1, tb1;
-        w.decode(2 * pit_, gi0, tb0);
-        const bool second = 2 * pit_ + 1 < w.nitems;
-        w.decode(second ? 2 * pit_ + 1 : 2 * pit_, gi1, tb1);
+    auto fetch_ids = [&](long long pit_, int& idv_, int& idw_, int& sc_, bool& valid_, int (&sta_)[KS]) {
+        int gi0, tb0, gi1, tb1, gj0 = 0, gj1 = 0;
+        const bool second = 2 * pit_ + 1 < nitems;
+        if constexpr (MIX) {
+            wp.decode(2 * pit_, gi0, gj0, tb0);
+            wp.decode(second ? 2 * pit_ + 1 : 2 * pit_, gi1, gj1, tb1);
+        } else {
+            w.decode(2 * pit_, gi0, tb0);
+            w.decode(second ? 2 * pit_ + 1 : 2 * pit_, gi1, tb1);
+        }
         idv_ = a.src_tab[(half ? gi1 : gi0) * 16 + jt];
-        const int s = (half ? tb1 : tb0) * 16 + jt;
+        int js = jt;
+        if constexpr (MIX) {
+            idw_ = a.src_tab[(half ? gj1 : gj0) * 16 + jt];
+            js = (half ? gj1 != gi1 : gj0 != gi0) ? (jt & 7) : jt;      // mixed row: stations r' = 0 .. 7 of the tail tile in either half
+        }
+        const int s = (half ? tb1 : tb0) * 16 + js;
         valid_ = s < S && (second || !half);
         sc_ = s < S ? s : S - 1;
         load_sta_ids<KS>(a.sta_col, sc_, sta_);
@@ -589,28 +618,34 @@ __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
             src_[q] = q < dp_ ? v : (int)p_;
         }
     };
-    int idv = 0, sc = 0, sta_id[KS], src_id[KPP], dgs = 0, dgp = 0;
+    int idv = 0, idw = 0, sc = 0, sta_id[KS], src_id[KPP], dgs = 0, dgp = 0;
     long long pcur = 0;
     bool valid = false;
     // wave items: Cartesian = pairs of (source node, station tile) items of the XCD-aware sweep; PCSR = 32 consecutive product nodes
     PtileIter ptw(PCSR ? (a.Pn + 31) / 32 : 0, H2_THREADS / 64, wave);       // PCSR: positions in the processing order of the 32-node items
     const long long pit0 = PCSR ? ptw.i : w.it;
     const long long pstride = PCSR ? ptw.stride : w.stride;
-    const long long pend = PCSR ? ptw.end : (w.nitems + 1) / 2;
+    const long long pend = PCSR ? ptw.end : (nitems + 1) / 2;
     if (pit0 < pend) {
         if constexpr (PCSR) fetch_pcsr(pit0, pcur, valid, sta_id, src_id, dgs, dgp);
-        else fetch_ids(pit0, idv, sc, valid, sta_id);
+        else fetch_ids(pit0, idv, idw, sc, valid, sta_id);
     }
     for (long long pit = pit0, pnext = 0; pit < pend; pit = pnext) {
         asm volatile("" : "+v"(lane));    // keeps the LDS fragment reads inside the loop (LICM would park them all in VGPRs)
         // idv: every row of 16 lanes holds {source node, its KP neighbours} of its own tile: one DPP row broadcast per id
-        const int g = PCSR ? 0 : row_bcast<0>(idv);
+        int g = PCSR ? 0 : row_bcast<0>(idv);
+        if constexpr (MIX) g = row_bcast_hi<0>(g, idw);
         const long long p = PCSR ? pcur : (long long)g * S + sc;
         const off_t_ gbase0 = PCSR ? (off_t_)(unsigned long long)p * (off_t_)XPC : (off_t_)(unsigned)g * gstride;
         const unsigned sbase0 = PCSR ? 0u : (unsigned)sc * (unsigned)XPC;
         off_t_ gbase = gbase0 + la;                  // + this lane's plane: one multiply-add per neighbour row address
         off_t_ sbase = (off_t_)sbase0 + la;
-        const int srcv = idv;
+        const int srcv = idv, srcw = idw;
+        auto src_nb = [&](int k) {      // k-th source neighbour of this lane's node
+            int nb = row_bcast_dyn(srcv, k);
+            if constexpr (MIX) nb = row_bcast_hi_dyn(nb, srcw, k);
+            return (unsigned)nb;
+        };
         // PCSR: per-lane weights of a present neighbour (16 x scaling and 1 / degree folded in)
         float alS = 0.f, beS = 0.f, alP = 0.f, beP = 0.f;
         if constexpr (PCSR) {
@@ -635,13 +670,13 @@ __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
             else if (PCSR) off = (off_t_)(unsigned)(u <= KS ? sta_id[u - 1] : src_id[(u - KS - 1) % KPP]) * (off_t_)XPC + la;
             else if (u <= KS) off = gbase + (unsigned)sta_id[u - 1] * (unsigned)XPC;
             else {
-                const unsigned nb = (unsigned)row_bcast_dyn(srcv, u - KS);
+                const unsigned nb = src_nb(u - KS);
                 off = (BIG ? (off_t_)nb * gstride : (off_t_)__umul24(nb, (unsigned)gstride)) + sbase;
             }
             if (ABS && u > 0) {
                 if (u <= KS) tp[u] = *(const u32x2*)((const char*)a.abs_ts + (tp_h + (unsigned)sta_id[u - 1] * 16u));
                 else if (PCSR) tp[u] = *(const u32x2*)((const char*)a.abs_tg + (tp_h + (unsigned)src_id[(u - KS - 1) % KPP] * 16u));
-                else tp[u] = *(const u32x2*)((const char*)a.abs_tg + (tp_h + (unsigned)row_bcast_dyn(srcv, u - KS) * 16u));
+                else tp[u] = *(const u32x2*)((const char*)a.abs_tg + (tp_h + src_nb(u - KS) * 16u));
             }
             buf[u] = *(const u32x4*)(xs + off);
         };
@@ -710,7 +745,7 @@ __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
             }
             asm volatile("" : "+v"(sn), "+v"(gbase), "+v"(sbase), "+v"(jt));
         }
-        int idv_n = 0, sc_n = 0, sta_n[KS], src_n[KPP], dgs_n = 0, dgp_n = 0;
+        int idv_n = 0, idw_n = 0, sc_n = 0, sta_n[KS], src_n[KPP], dgs_n = 0, dgp_n = 0;
         long long p_n = 0;
         bool valid_n = false;
 #pragma unroll
@@ -721,7 +756,7 @@ __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
         const bool has_next = pnext < pend;
         if (has_next) {
             if constexpr (PCSR) fetch_pcsr(pnext, p_n, valid_n, sta_n, src_n, dgs_n, dgp_n);
-            else fetch_ids(pnext, idv_n, sc_n, valid_n, sta_n);
+            else fetch_ids(pnext, idv_n, idw_n, sc_n, valid_n, sta_n);
         }
         if (a.dbg_h0 != nullptr && valid) {
 #pragma unroll
@@ -850,7 +885,7 @@ __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
                 *(f32x4*)(vr + b * vs) = f32x4{ow[1][8 + 4 * b], ow[1][8 + 4 * b + 1], ow[1][8 + 4 * b + 2], ow[1][8 + 4 * b + 3]};
             }
         }
-        idv = idv_n; sc = sc_n; valid = valid_n; pcur = p_n; dgs = dgs_n; dgp = dgp_n;
+        idv = idv_n; idw = idw_n; sc = sc_n; valid = valid_n; pcur = p_n; dgs = dgs_n; dgp = dgp_n;
 #pragma unroll
         for (int k = 0; k < KS; ++k) sta_id[k] = sta_n[k];
 #pragma unroll

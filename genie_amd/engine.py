@@ -801,6 +801,10 @@ class HipPath(object):
         v = -1 if blocks_of_four is None else (1 if blocks_of_four else 0)
         _lib.check(self.lib.genie_set_stage2_workmap(self.ctx, v), "genie_set_stage2_workmap")
 
+    def set_tail_packing(self, on):
+        """Packed (default) or padded station tail tiles of the f16x2 stage 1 (genie_set_tail_packing): same bits either way."""
+        _lib.check(self.lib.genie_set_tail_packing(self.ctx, 1 if on else 0), "genie_set_tail_packing")
+
     def set_sign_input(self, use_sign_input):
         """`use_sign_input` of config.yaml:93 for the device embedding (genie_set_sign_input): features signed by the series' negative slope."""
         _lib.check(self.lib.genie_set_sign_input(self.ctx, 1 if use_sign_input else 0), "genie_set_sign_input")

@@ -114,6 +114,11 @@ int genie_set_sign_input(genie_ctx* ctx, int use_sign_input);
  * pays), 0 = interleaved items, -1 = the default for the context's station count. Results do not depend on it (tests). The library reads
  * no environment variable; this is the one scheduling choice a caller can make. */
 int genie_set_stage2_workmap(genie_ctx* ctx, int blocks_of_four);
+/* Station tail tiles of the f16x2 stage 1 (k_stage1_h2) on a Cartesian graph: with n_sta mod 16 in 1 .. 8 the half-empty last station
+ * tiles of two adjacent source nodes share one 16-lane row (on != 0, the default); 0 = every node keeps its own padded tail tile, the
+ * earlier item table, kept for A/B runs and the byte-equality tests. Results do not depend on it, to the bit (tests). Other station
+ * counts and other kernels have nothing to pack and ignore it. */
+int genie_set_tail_packing(genie_ctx* ctx, int on);
 /* Arithmetic of the G-sized tail of inference calls (Bipartite read-out, SpatialAggregation x3, SpatialDirect + TemporalAttention
  * on the grid): fp64_chains != 0 (default) = every Linear as a chain of fp64 MFMAs on the fp32 inputs and weights, fp64 PReLUs
  * and sums, one rounding to fp32 per kernel; 0 = fp32 MFMA chains (the arithmetic of the training forward, and the A/B form).
