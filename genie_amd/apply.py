@@ -900,7 +900,8 @@ class GridLeg(object):
         self.n_sta = int(n_sta)
         if pairs is not None:
             pairs = np.asarray(pairs)
-            self.trv = torch.from_numpy(np.ascontiguousarray(trv_times[pairs[1], pairs[0]]).reshape(-1, 2)).to(self.device)
+            # (a source-node shard of the irregular graph keeps its owned + halo rows only: cut once, not per window)
+            self.trv = net.node_rows(torch.from_numpy(np.ascontiguousarray(trv_times[pairs[1], pairs[0]]).reshape(-1, 2)), 2)
         else:
             self.trv = net.node_rows(trv_times, 2)
 

@@ -1029,7 +1029,9 @@ struct DaArgs {
     const float* packed;       // packed A fragments for the stage
     const void* xs;            // k_stage1_h2: the two 16-B fp16 pieces of every [Slice || Mask] row, planar
     long long xs_plane;        // ... bytes per plane (= rows x 16)
-    long long Pn;              // PCSR kernels: number of product nodes (rowptr / col arrays are product-level there)
+    long long Pn;              // PCSR kernels: number of product nodes (rowptr / col arrays are product-level there); a row-range
+                               // call (extended irregular context): the END of the range
+    long long p0;              // PCSR kernels: first row of the call's row range (tiles are cut from it); 0 = all product nodes
     const float* abs_sta;      // use_absolute_pos: [S][4] = {loc / (3 scale_rel), 0}, or null
     const float* abs_src;      // ... [G_ext][4] = {x_grid / (3 scale_rel), 0}
     const unsigned* abs_ts;    // k_stage1_h2<.., ABS>: [S][2] x 8 B = the fp16 pieces of a station's scaled position {x, y, z, 0} (processing order)
@@ -1319,6 +1321,9 @@ struct genie_ctx {
     DevBuf<int32_t> p_sta_rowptr, p_sta_col, p_src_rowptr, p_src_col, seg_rowptr;
     DevBuf<int32_t> p_src_of;  // ... source node of every product node (built on the first genie_assoc_fwd)
     DevBuf<int32_t> p_sta_of;  // ... station of every product node (genie_set_subgraph_stations: the device embedding needs it)
+    bool pcsr_ext;             // ... over an EXTENDED row list (genie_ctx_create_subgraph_ext: a source-node shard): P owned rows in
+                               // the processing order of their source nodes, then P_ext - P halo rows the source CSR may point into
+    std::vector<int32_t> seg_host;   // ... seg_rowptr on the host: the row range of a range of source nodes
     DevBuf<float> mpos_sta, mpos_src, ebias_sta, ebias_src;   // DataAggregationEdges: mean edge features [n,4] and their Linear [n,48]
     bool has_edges;
     // station processing order (genie_set_station_order): internal -> caller's station, its inverse, the station graph in
@@ -2221,20 +2226,24 @@ int genie_ctx_create(genie_ctx** out, int n_sta, int n_grid, int n_grid_ext, con
     return GENIE_OK;
 }
 
-int genie_ctx_create_subgraph(genie_ctx** out, int n_sta, int n_grid, int64_t n_prod, const int32_t* p_sta_rowptr,
-                              const int32_t* p_sta_col, const int32_t* p_src_rowptr, const int32_t* p_src_col,
-                              const int32_t* seg_rowptr, const int32_t* src_rowptr, const int32_t* src_col,
-                              const int32_t* grid_order, float scale_rel) {
+namespace {
+// The irregular context of genie_ctx_create_subgraph (n_prod_ext == n_prod, the base source graph given) and of
+// genie_ctx_create_subgraph_ext (ext: rows [n_prod, n_prod_ext) are halo rows, no base source graph, identity processing order).
+int create_subgraph(genie_ctx** out, int n_sta, int n_grid, int64_t n_prod, int64_t n_prod_ext, bool ext, const int32_t* p_sta_rowptr,
+                    const int32_t* p_sta_col, const int32_t* p_src_rowptr, const int32_t* p_src_col, const int32_t* seg_rowptr,
+                    const int32_t* src_rowptr, const int32_t* src_col, const int32_t* grid_order, float scale_rel) {
     if (!out) return fail(GENIE_ERR_ARG, "out is null");
     *out = nullptr;
-    if (n_prod < 1 || n_prod >= (1ll << 31)) return fail(GENIE_ERR_ARG, "genie_ctx_create_subgraph: bad n_prod");
+    if (n_prod < 1 || n_prod_ext < n_prod || n_prod_ext >= (1ll << 31)) return fail(GENIE_ERR_ARG, "genie_ctx_create_subgraph: bad n_prod");
     if (!p_sta_rowptr || !p_src_rowptr || !seg_rowptr) return fail(GENIE_ERR_ARG, "genie_ctx_create_subgraph: null rowptr");
     genie_ctx* c = nullptr;
     {   // empty base station graph: the station edges live in the product-level CSR (genie_ctx_create copies it and drains the device)
         DevBuf<int32_t> zeros;
-        HIP_TRY(zeros.alloc((size_t)n_sta + 1));
-        HIP_TRY(hipMemset(zeros, 0, sizeof(int32_t) * ((size_t)n_sta + 1)));
-        GENIE_TRY(genie_ctx_create(&c, n_sta, n_grid, n_grid, zeros, nullptr, src_rowptr, src_col, grid_order, scale_rel));
+        HIP_TRY(zeros.alloc((size_t)std::max(n_sta, n_grid) + 1));
+        HIP_TRY(hipMemset(zeros, 0, sizeof(int32_t) * ((size_t)std::max(n_sta, n_grid) + 1)));
+        // (an extended context has no base source graph either: nothing G-sized runs on a shard's local context)
+        GENIE_TRY(genie_ctx_create(&c, n_sta, n_grid, n_grid, zeros, nullptr, ext ? (const int32_t*)zeros : src_rowptr, ext ? nullptr : src_col,
+                                   grid_order, scale_rel));
     }
     CtxGuard guard(c);
     int32_t e1 = 0, e2 = 0, last = 0;
@@ -2250,7 +2259,8 @@ int genie_ctx_create_subgraph(genie_ctx** out, int n_sta, int n_grid, int64_t n_
     GENIE_TRY(dev_copy(c->p_src_col, p_src_col, (size_t)e2));
     GENIE_TRY(dev_copy(c->seg_rowptr, seg_rowptr, (size_t)n_grid + 1));
     c->pcsr = true;
-    c->P = c->P_ext = n_prod;
+    c->pcsr_ext = ext;
+    c->P = n_prod; c->P_ext = n_prod_ext;
     {   // the f16x2 stage-1 kernel unrolls 8 station + 15 source neighbour slots per node: enough for every induced subgraph of
         // the reference's kNN product graphs (process_utils.py:824-839); other graphs keep the generic fp32-MFMA kernel
         std::vector<int32_t> r1((size_t)n_prod + 1), r2((size_t)n_prod + 1);
@@ -2259,8 +2269,24 @@ int genie_ctx_create_subgraph(genie_ctx** out, int n_sta, int n_grid, int64_t n_
         int m1 = 0, m2 = 0;
         for (long long i = 0; i < n_prod; ++i) { m1 = std::max(m1, r1[i + 1] - r1[i]); m2 = std::max(m2, r2[i + 1] - r2[i]); }
         c->pcsr_h2 = m1 <= 8 && m2 <= 15;
+        if (ext) {      // a column outside the rows is an out-of-bounds gather on the device: checked here, once
+            // station neighbours are rows of the same source node (owned), source neighbours owned or halo rows
+            std::vector<int32_t> cs((size_t)e1), cg((size_t)e2);
+            if (e1) HIP_TRY(hipMemcpy(cs.data(), p_sta_col, sizeof(int32_t) * cs.size(), hipMemcpyDeviceToHost));
+            if (e2) HIP_TRY(hipMemcpy(cg.data(), p_src_col, sizeof(int32_t) * cg.size(), hipMemcpyDeviceToHost));
+            bool ok = r1[0] == 0 && r2[0] == 0 && r1[(size_t)n_prod] == e1 && r2[(size_t)n_prod] == e2;
+            for (long long i = 0; i < n_prod && ok; ++i) ok = r1[i + 1] >= r1[i] && r2[i + 1] >= r2[i];
+            for (int32_t v : cs) ok = ok && v >= 0 && v < n_prod;
+            for (int32_t v : cg) ok = ok && v >= 0 && v < n_prod_ext;
+            if (!ok) return fail(GENIE_ERR_ARG, "genie_ctx_create_subgraph_ext: a CSR row pointer or column outside the local rows");
+        }
     }
-    {   // processing order of the tiles: the product nodes stay where the caller put them (grouped by source node in HIS order), but
+    c->seg_host.resize((size_t)n_grid + 1);
+    HIP_TRY(hipMemcpy(c->seg_host.data(), seg_rowptr, sizeof(int32_t) * c->seg_host.size(), hipMemcpyDeviceToHost));
+    for (int g = 0; g < n_grid; ++g)
+        if (c->seg_host[g] > c->seg_host[g + 1] || c->seg_host[0] != 0)
+            return fail(GENIE_ERR_ARG, "genie_ctx_create_subgraph: seg_rowptr must start at 0 and not decrease");
+    if (!ext) {   // processing order of the tiles: the product nodes stay where the caller put them (grouped by source node in HIS order), but
         // the tiles are taken in the space-filling-curve order of their source nodes, one contiguous chunk of that list per XCD, so
         // the rows a tile gathers (neighbouring source nodes) are being read by the same L2 at about the same time
         std::vector<int32_t> seg((size_t)n_grid + 1), ord((size_t)n_grid), rank((size_t)n_grid, 0);
@@ -2283,9 +2309,27 @@ int genie_ctx_create_subgraph(genie_ctx** out, int n_sta, int n_grid, int64_t n_
     *out = guard.release();
     return GENIE_OK;
 }
+}  // namespace
+
+int genie_ctx_create_subgraph(genie_ctx** out, int n_sta, int n_grid, int64_t n_prod, const int32_t* p_sta_rowptr,
+                              const int32_t* p_sta_col, const int32_t* p_src_rowptr, const int32_t* p_src_col,
+                              const int32_t* seg_rowptr, const int32_t* src_rowptr, const int32_t* src_col,
+                              const int32_t* grid_order, float scale_rel) {
+    return create_subgraph(out, n_sta, n_grid, n_prod, n_prod, false, p_sta_rowptr, p_sta_col, p_src_rowptr, p_src_col, seg_rowptr,
+                           src_rowptr, src_col, grid_order, scale_rel);
+}
+
+int genie_ctx_create_subgraph_ext(genie_ctx** out, int n_sta, int n_own, int64_t n_prod_own, int64_t n_prod_ext,
+                                  const int32_t* p_sta_rowptr, const int32_t* p_sta_col, const int32_t* p_src_rowptr,
+                                  const int32_t* p_src_col, const int32_t* seg_rowptr, float scale_rel) {
+    return create_subgraph(out, n_sta, n_own, n_prod_own, n_prod_ext, true, p_sta_rowptr, p_sta_col, p_src_rowptr, p_src_col, seg_rowptr,
+                           nullptr, nullptr, nullptr, scale_rel);
+}
 
 int genie_set_absolute_pos(genie_ctx* c, const float* pos_sta, const float* pos_src, void* stream) {
     if (!c) return fail(GENIE_ERR_ARG, "genie_set_absolute_pos: null context");
+    if (c->pcsr_ext && pos_sta && pos_src)
+        return fail(GENIE_ERR_STATE, "genie_set_absolute_pos: not available on an extended irregular context (a source-node shard)");
     if (!pos_sta || !pos_src) {
         (void)hipDeviceSynchronize();        // pooled blocks are reused without the driver's implicit drain
         c->abs_sta.reset(); c->abs_src.reset(); c->abs_ts.reset(); c->abs_tg.reset();
@@ -2312,6 +2356,8 @@ int genie_set_absolute_pos(genie_ctx* c, const float* pos_sta, const float* pos_
 
 int genie_set_edge_features(genie_ctx* c, const float* pos_sta, const float* pos_src, void* stream) {
     if (!c) return fail(GENIE_ERR_ARG, "genie_set_edge_features: null context");
+    if (c->pcsr_ext && pos_sta && pos_src)
+        return fail(GENIE_ERR_STATE, "genie_set_edge_features: not available on an extended irregular context (a source-node shard)");
     hipStream_t st = (hipStream_t)stream;
     if (!pos_sta || !pos_src) {      // back to plain DataAggregation
         c->has_edges = false;
@@ -2494,7 +2540,10 @@ int run_stage1(genie_ctx* c, const StageCall& call, const float* slice, const fl
     if (!slice || !mask) return fail(GENIE_ERR_ARG, "genie_da_stage1: null input");
     if (gi_begin < 0 || gi_end > c->G || gi_begin > gi_end) return fail(GENIE_ERR_ARG, "genie_da_stage1: bad source-node range");
     const bool whole = gi_begin == 0 && gi_end == c->G;
-    if (!whole && c->pcsr) return fail(GENIE_ERR_STATE, "genie_da_stage1_range: not available on an irregular product graph");
+    // an irregular product graph: sub-ranges on an extended context only, whose rows lie in the processing order of their source nodes
+    // (a range of source nodes = a range of rows)
+    if (!whole && c->pcsr && !c->pcsr_ext)
+        return fail(GENIE_ERR_STATE, "genie_da_stage1_range: not available on an unsharded irregular product graph");
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_packed(c, st))) return rc;
     const StageRoutes r = stage_routes(c, call, gi_begin, gi_end, false, false);
@@ -2502,6 +2551,8 @@ int run_stage1(genie_ctx* c, const StageCall& call, const float* slice, const fl
     DaArgs a = make_da_args(c, call, (float*)ws);
     a.gi0 = gi_begin; a.G = gi_end - gi_begin;
     const long long n_tiles = (long long)a.G * c->T;
+    if (c->pcsr) { a.p0 = c->seg_host[gi_begin]; a.Pn = c->seg_host[gi_end]; }
+    const long long n_rows = a.Pn - a.p0;      // (PCSR routes)
     a.slice = slice; a.mask = mask; a.packed = c->packed[PL_S1];
     a.dbg_h0 = dbg_h0; a.dbg_h1 = dbg_h1;
     c->s1_layout = r.layout;
@@ -2518,11 +2569,14 @@ int run_stage1(genie_ctx* c, const StageCall& call, const float* slice, const fl
         break;
     case S1Route::PcsrH2: {
         unsigned* xs = (unsigned*)((float*)ws + c->o_xs);
-        k_split_rows<<<(unsigned)((c->P + 255) / 256), 256, 0, st>>>(slice, mask, c->P, xs, nullptr, c->S, nullptr, input_limit(c), c->h_inflag);
-        a.xs = xs; a.packed = c->packed_h2; a.xs_plane = c->P * (long long)XPC;
-        const long long nitems = (c->P + 31) / 32;
+        // the split rows of ALL rows, halo rows included: neighbours are gathered from them
+        if (do_split)
+            k_split_rows<<<(unsigned)((c->P_ext + 255) / 256), 256, 0, st>>>(slice, mask, c->P_ext, xs, nullptr, c->S, nullptr, input_limit(c), c->h_inflag);
+        if (n_rows <= 0) break;
+        a.xs = xs; a.packed = c->packed_h2; a.xs_plane = c->P_ext * (long long)XPC;
+        const long long nitems = (n_rows + 31) / 32;
         const int grid = (int)std::max<long long>(8, std::min<long long>((nitems + H2_THREADS / 64 - 1) / (H2_THREADS / 64), (long long)c->num_cu * c->bpc1b) / 8 * 8);
-        a.ptile = c->ptile32;
+        a.ptile = c->pcsr_ext ? nullptr : (const int32_t*)c->ptile32;
         if (c->abs_sta) {      // position pieces per product node (genie_set_absolute_pos on a subgraph context)
             if (c->abs_dirty || !c->abs_ts) {
                 if (!c->abs_ts) GENIE_TRY(alloc_abs_pieces(c, (size_t)c->P, (size_t)c->P));
@@ -2532,12 +2586,13 @@ int run_stage1(genie_ctx* c, const StageCall& call, const float* slice, const fl
             }
             a.abs_ts = c->abs_ts; a.abs_tg = c->abs_tg;
         }
-        launch_stage1_h2<true>(a, c->abs_sta != nullptr, c->has_edges, c->P * XROW >= (1ll << 32), grid, st);
+        launch_stage1_h2<true>(a, c->abs_sta != nullptr, c->has_edges, c->P_ext * XROW >= (1ll << 32), grid, st);
         break;
     }
     case S1Route::PcsrF32: {
-        const long long ntiles = (c->P + 15) / 16;
-        a.ptile = c->ptile16;
+        if (n_rows <= 0) break;
+        const long long ntiles = (n_rows + 15) / 16;
+        a.ptile = c->pcsr_ext ? nullptr : (const int32_t*)c->ptile16;
         const long long gw = std::min<long long>((ntiles + 3) / 4, (long long)c->num_cu * c->bpc1);
         k_stage1<true><<<(int)std::max<long long>(8, gw / 8 * 8), 256, 0, st>>>(a);
         break;
@@ -2665,8 +2720,8 @@ int run_stage2(genie_ctx* c, const StageCall& call, const float* mask, const flo
     if (rc) return rc;
     if (!mask || !edge_attr) return fail(GENIE_ERR_ARG, "genie_da_stage2_partials: null argument");
     if (gi_begin < 0 || gi_end > c->G || gi_begin > gi_end) return fail(GENIE_ERR_ARG, "genie_da_stage2_partials: bad source-node range");
-    if (!(gi_begin == 0 && gi_end == c->G) && c->pcsr)
-        return fail(GENIE_ERR_STATE, "genie_da_stage2_partials_range: not available on an irregular product graph");
+    if (!(gi_begin == 0 && gi_end == c->G) && c->pcsr && !c->pcsr_ext)
+        return fail(GENIE_ERR_STATE, "genie_da_stage2_partials_range: not available on an unsharded irregular product graph");
     hipStream_t st = (hipStream_t)stream;
     if ((rc = ensure_packed(c, st))) return rc;
     DaArgs a = make_da_args(c, call, (float*)ws);
@@ -2674,6 +2729,7 @@ int run_stage2(genie_ctx* c, const StageCall& call, const float* mask, const flo
     a.slope2 = slope2; a.no_bip = no_bip;
     const long long n_tiles = (long long)a.G * c->T;
     if (n_tiles == 0) return GENIE_OK;
+    if (c->pcsr) { a.p0 = c->seg_host[gi_begin]; a.Pn = c->seg_host[gi_end]; }
     const StageRoutes r = stage_routes(c, call, gi_begin, gi_end, no_bip != 0, x_latent_out != nullptr);
     // (no_bip: the association heads' last pass reads the rows k_assoc_b wrote, whatever stage 1 left)
     if (!no_bip && c->s1_layout != r.layout)
@@ -2722,22 +2778,24 @@ int run_stage2(genie_ctx* c, const StageCall& call, const float* mask, const flo
         break;
     case S2Route::PcsrPseg: {
         // a wave per source node, the station sum folded into the pass, straight into the window's slot (a.part)
-        a.ptile = c->ptile16;
-        const long long gs = std::min<long long>((c->G + 3) / 4, (long long)c->num_cu * c->bpc2);
-        k_stage2_pseg<<<(int)std::max<long long>(8, gs / 8 * 8), 256, 0, st>>>(a, c->seg_rowptr, c->G);
+        // (the range's source nodes at positions [a.gi0, a.gi0 + a.G) of the processing order; tiles are cut from a node's first row,
+        // so a node's sum does not depend on where its rows lie)
+        const long long gs = std::min<long long>((a.G + 3) / 4, (long long)c->num_cu * c->bpc2);
+        k_stage2_pseg<<<(int)std::max<long long>(8, gs / 8 * 8), 256, 0, st>>>(a, c->seg_rowptr, a.G);
         break;
     }
     case S2Route::PcsrSeg: {
-        const long long ntiles = (c->P + 15) / 16;
-        a.ptile = c->ptile16;
+        const long long ntiles = (a.Pn - a.p0 + 15) / 16;
+        a.ptile = c->pcsr_ext ? nullptr : (const int32_t*)c->ptile16;
         const long long gw = std::min<long long>((ntiles + 3) / 4, (long long)c->num_cu * c->bpc2);      // 2 .. 12 workgroups per CU: +-1 %
-        k_stage2<true><<<(int)std::max<long long>(8, gw / 8 * 8), 256, 0, st>>>(a);                      // (a multiple of the 8 XCDs)
+        if (ntiles > 0) k_stage2<true><<<(int)std::max<long long>(8, gw / 8 * 8), 256, 0, st>>>(a);      // (a multiple of the 8 XCDs)
         // the gated messages sit in the c rows, which exist GENIE_NBIG times only: their station sums (row order) go to the window's
         // own slot right away, one partial row per source node, so that every tail form (per window, side streams, batched) reads
         // `part` as it does on a Cartesian graph
         if (!no_bip)
-            k_seg_sum32<<<(c->G * 32 + 255) / 256, 256, 0, st>>>((const float*)ws + c->o_c + (c->slot % GENIE_NBIG) * c->big_stride, c->seg_rowptr,
-                                                                 c->G, (float*)ws + c->o_part + c->slot * c->slot_stride);
+            k_seg_sum32<<<(a.G * 32 + 255) / 256, 256, 0, st>>>((const float*)ws + c->o_c + (c->slot % GENIE_NBIG) * c->big_stride,
+                                                                c->seg_rowptr + gi_begin, a.G,
+                                                                (float*)ws + c->o_part + c->slot * c->slot_stride + (size_t)gi_begin * 32);
         break;
     }
     case S2Route::AssocLast:      // row-layout c / wu / wv written by k_assoc_b
@@ -3349,7 +3407,7 @@ void reduce_pass(genie_ctx* c, int tm, const float* part, int n_slots, float* bl
 // `variants`: the call also serves DataAggregationEdges / use_absolute_pos (the forward_fixed_source step does; the association heads'
 // training step is the default model definition only)
 int train_check(const genie_ctx* c, const char* who, bool variants = false, bool pcsr_ok = false) {
-    if ((c->pcsr && !pcsr_ok) || c->G_ext != c->G) return fail(GENIE_ERR_STATE, std::string(who) + ": needs an unsharded Cartesian product graph");
+    if ((c->pcsr && !pcsr_ok) || c->G_ext != c->G || c->pcsr_ext) return fail(GENIE_ERR_STATE, std::string(who) + ": needs an unsharded Cartesian product graph");
     if (!variants && (c->has_edges || c->abs_sta)) return fail(GENIE_ERR_STATE, std::string(who) + ": default model definition only");
     return GENIE_OK;
 }
@@ -3803,6 +3861,7 @@ int assoc_fwd_impl(genie_ctx* c, const float* y_latent, const float* mask_src, c
     if (!y_latent || !mask_src || !x_latent || !mask || !edge_attr || !out || !assoc_ws)
         return fail(GENIE_ERR_ARG, "genie_assoc_fwd: null argument");
     // one call cannot run the layers of a shard: each gathers rows of halo nodes that another rank computes (genie_assoc_fwd_part)
+    if (c->pcsr_ext) return fail(GENIE_ERR_STATE, "genie_assoc_fwd: not available on an extended irregular context (a source-node shard)");
     if (c->G_ext != c->G && (parts == AS_PART_ALL || save))
         return fail(GENIE_ERR_STATE, "genie_assoc_fwd: needs an unsharded product graph (a shard runs genie_assoc_fwd_part around its halo exchanges)");
     if (((uintptr_t)assoc_ws & 15) != 0) return fail(GENIE_ERR_ARG, "genie_assoc_fwd: assoc_ws must be 16-byte aligned");
@@ -4861,8 +4920,9 @@ int genie_set_phase_types(genie_ctx* c, int use_phase_types) {
 int genie_set_subgraph_stations(genie_ctx* c, const int32_t* sta_of_prod, void* stream) {
     if (!c || !sta_of_prod) return fail(GENIE_ERR_ARG, "genie_set_subgraph_stations: null argument");
     if (!c->pcsr) return fail(GENIE_ERR_STATE, "genie_set_subgraph_stations: the context is a Cartesian product graph (station = p % n_sta)");
-    if (!c->p_sta_of) HIP_TRY(c->p_sta_of.alloc((size_t)c->P));
-    HIP_TRY(hipMemcpyAsync(c->p_sta_of, sta_of_prod, sizeof(int32_t) * (size_t)c->P, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    // (every row the context holds: the halo rows of an extended context are embedded too)
+    if (!c->p_sta_of) HIP_TRY(c->p_sta_of.alloc((size_t)c->P_ext));
+    HIP_TRY(hipMemcpyAsync(c->p_sta_of, sta_of_prod, sizeof(int32_t) * (size_t)c->P_ext, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return GENIE_OK;
 }
 

@@ -206,7 +206,7 @@ __global__ __launch_bounds__(256) void k_stage1(DaArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int S = a.S;
     ItemIter w(a.G, a.T, a.seg, a.nxcd, wave, a.gi0);
-    PtileIter pt(PCSR ? (a.Pn + 15) / 16 : 0, blockDim.x >> 6, threadIdx.x >> 6);
+    PtileIter pt(PCSR ? (a.Pn - a.p0 + 15) / 16 : 0, blockDim.x >> 6, threadIdx.x >> 6);
     const long long n_it = PCSR ? pt.end : w.nitems, it0 = PCSR ? pt.i : w.it, its = PCSR ? pt.stride : w.stride;
     for (long long it = it0; it < n_it; it += its) {
         int g = 0, tb = 0;
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256) void k_stage1(DaArgs a) {
         long long p;
         int sc = 0;
         if (PCSR) {
-            const long long pr = tile * 16 + j;
+            const long long pr = a.p0 + tile * 16 + j;
             valid = pr < a.Pn;
             p = valid ? pr : a.Pn - 1;
         } else {
@@ -601,7 +601,7 @@ __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
     };
     constexpr int KPP = PCSR ? KP : 1;
     auto fetch_pcsr = [&](long long pit_, long long& p_, bool& valid_, int (&sta_)[KS], int (&src_)[KPP], int& ds_, int& dp_) {
-        const long long pr = ptile_at(a.ptile, pit_) * 32 + (lane & 31);
+        const long long pr = a.p0 + ptile_at(a.ptile, pit_) * 32 + (lane & 31);
         valid_ = pr < a.Pn;
         p_ = valid_ ? pr : a.Pn - 1;
         const int eb = a.sta_rowptr[p_], fb = a.src_rowptr[p_];
@@ -622,7 +622,7 @@ __global__ __launch_bounds__(H2_THREADS) void k_stage1_h2(DaArgs a) {
     long long pcur = 0;
     bool valid = false;
     // wave items: Cartesian = pairs of (source node, station tile) items of the XCD-aware sweep; PCSR = 32 consecutive product nodes
-    PtileIter ptw(PCSR ? (a.Pn + 31) / 32 : 0, H2_THREADS / 64, wave);       // PCSR: positions in the processing order of the 32-node items
+    PtileIter ptw(PCSR ? (a.Pn - a.p0 + 31) / 32 : 0, H2_THREADS / 64, wave);       // PCSR: positions in the processing order of the 32-node items
     const long long pit0 = PCSR ? ptw.i : w.it;
     const long long pstride = PCSR ? ptw.stride : w.stride;
     const long long pend = PCSR ? ptw.end : (nitems + 1) / 2;
@@ -1001,7 +1001,7 @@ __global__ __launch_bounds__(256) void k_stage2(DaArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int S = a.S;
     ItemIter w(a.G, a.T, a.seg, a.nxcd, wave, a.gi0);
-    PtileIter pt(PCSR ? (a.Pn + 15) / 16 : 0, blockDim.x >> 6, threadIdx.x >> 6);
+    PtileIter pt(PCSR ? (a.Pn - a.p0 + 15) / 16 : 0, blockDim.x >> 6, threadIdx.x >> 6);
     const long long n_it = PCSR ? pt.end : w.nitems, it0 = PCSR ? pt.i : w.it, its = PCSR ? pt.stride : w.stride;
     for (long long it = it0; it < n_it; it += its) {
         int g = 0, tb = 0;
@@ -1018,7 +1018,7 @@ __global__ __launch_bounds__(256) void k_stage2(DaArgs a) {
         long long p, pl;
         int sc = 0;
         if (PCSR) {
-            const long long pr = tile * 16 + j, prl = tile * 16 + jl;
+            const long long pr = a.p0 + tile * 16 + j, prl = a.p0 + tile * 16 + jl;
             valid = pr < a.Pn;
             p = valid ? pr : a.Pn - 1;
             valid_l = prl < a.Pn;
@@ -1083,7 +1083,7 @@ __global__ __launch_bounds__(256) void k_stage2_pseg(DaArgs a, const int32_t* __
     float* ts = tsc + (threadIdx.x >> 6) * 16 * 36;
     PtileIter pt(n_src, blockDim.x >> 6, threadIdx.x >> 6);
     for (; pt.i < pt.end; pt.i += pt.stride) {
-        const int g = __builtin_amdgcn_readfirstlane(a.order != nullptr ? a.order[pt.i] : (int)pt.i);
+        const int g = __builtin_amdgcn_readfirstlane(a.order != nullptr ? a.order[a.gi0 + pt.i] : a.gi0 + (int)pt.i);
         const long long r0 = __builtin_amdgcn_readfirstlane(seg_rowptr[g]), r1 = __builtin_amdgcn_readfirstlane(seg_rowptr[g + 1]);
         f32x4 sum[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
         for (long long base = r0; base < r1; base += 16) {

@@ -142,6 +142,116 @@ class ShardPlan(object):
         return self.n_halo / max(1, self.n_own)
 
 
+class SubgraphShardPlan(object):
+    """Static plan for one rank of an IRREGULAR product graph (`use_subgraph`) sharded over source nodes (pure numpy, the same logic on
+    every rank). The product nodes are rows grouped by source node (`seg_rowptr` [G + 1]); `src_csr` / `sta_csr` = (rowptr [n_prod + 1],
+    col) are the product-level CSRs (in-edges per row, in the edge order the unsharded context takes them in).
+
+    Ownership is by source node, in `order`, as in `ShardPlan`: rank r owns order[lo_r:hi_r] and with them their rows. The halo is
+    RAGGED: exactly the rows of source nodes owned elsewhere that appear as a neighbour in the source CSR of an owned row, grouped by
+    owner, in the owner's local row order. Local row numbering: the owned rows, source node after source node in the processing order
+    `[SEND only | SEND and NEED | NEED only | interior]` (a node is SEND when one of its rows is in another rank's halo, NEED when one of
+    its rows has a neighbour owned elsewhere), then the halo rows. A range of processing positions is therefore a range of rows.
+    Counts (`send_counts`, `recv_counts`) are in rows.
+
+    own_global  [n_own]   owned source nodes in `order` order (what `gather_index` places; `proc_order` indexes it)
+    own_proc    [n_own]   owned source nodes in processing order = the local node numbering of the rank's HIP context
+    seg_rowptr  [n_own+1] local row range of every local node
+    own_rows / halo_rows / ext_rows: global row ids of the local rows
+    sta_rowptr, sta_col, src_rowptr, src_col: local product-level CSRs of the owned rows, columns = local row ids
+    send_rows[q]: local owned rows this rank sends to q, in q's halo order."""
+
+    def __init__(self, seg_rowptr, src_csr, sta_csr, n_grid, world, rank, order=None):
+        seg = np.asarray(seg_rowptr, dtype=np.int64)
+        G, W, me = int(n_grid), int(world), int(rank)
+        n_prod = int(seg[-1])
+        assert seg.shape == (G + 1,) and seg[0] == 0 and (np.diff(seg) >= 0).all(), "seg_rowptr: row ranges of the G source nodes"
+        order = np.arange(G) if order is None else np.asarray(order, dtype=np.int64)
+        assert order.shape == (G,) and np.array_equal(np.sort(order), np.arange(G)), "order must be a permutation of the source nodes"
+        self.n_grid, self.world, self.rank, self.n_prod = G, W, me, n_prod
+        bounds = [(G * r) // W for r in range(W + 1)]
+        self.bounds = bounds
+        owner = np.empty(G, dtype=np.int64)
+        for r in range(W):
+            owner[order[bounds[r]:bounds[r + 1]]] = r
+        self.owner = owner
+        self.owned = [order[bounds[r]:bounds[r + 1]].copy() for r in range(W)]
+        n_rows = np.diff(seg)
+        src_of = np.repeat(np.arange(G, dtype=np.int64), n_rows)
+        row_owner = owner[src_of]
+        rp, col = np.asarray(src_csr[0], dtype=np.int64), np.asarray(src_csr[1], dtype=np.int64)
+        srp, scol = np.asarray(sta_csr[0], dtype=np.int64), np.asarray(sta_csr[1], dtype=np.int64)
+        assert rp.shape == (n_prod + 1,) and srp.shape == (n_prod + 1,), "product-level CSRs over the n_prod rows"
+        assert col.size == 0 or (col.min() >= 0 and col.max() < n_prod), "source CSR column outside the product nodes"
+        assert scol.size == 0 or (src_of[scol] == np.repeat(src_of, np.diff(srp))).all(), "a station neighbour is a row of the same source node"
+        centre = np.repeat(np.arange(n_prod, dtype=np.int64), np.diff(rp))
+        cross = row_owner[centre] != row_owner[col]
+        ci, cj = centre[cross], col[cross]
+        # classes of every source node (of every rank: the owners' row orders are needed for the halo order)
+        send_row = np.zeros(n_prod, dtype=bool)
+        send_row[cj] = True
+        need_row = np.zeros(n_prod, dtype=bool)
+        need_row[ci] = True
+        send_node = np.bincount(src_of, weights=send_row, minlength=G) > 0
+        need_node = np.bincount(src_of, weights=need_row, minlength=G) > 0
+        row_local = np.empty(n_prod, dtype=np.int64)         # position of a row in its OWNER's local list
+        procs, rows_of = [], []
+        for r in range(W):
+            nodes = self.owned[r]
+            s, n = send_node[nodes], need_node[nodes]
+            loc = np.arange(nodes.size)
+            parts = [loc[s & ~n], loc[s & n], loc[~s & n], loc[~s & ~n]]
+            po = np.concatenate(parts).astype(np.int64)
+            procs.append((po, np.cumsum([0] + [p.size for p in parts])))
+            gp = nodes[po]
+            cnt = n_rows[gp]
+            off = np.concatenate(([0], np.cumsum(cnt)))
+            rows = np.repeat(seg[gp] - off[:-1], cnt) + np.arange(int(off[-1]))
+            row_local[rows] = np.arange(rows.size)
+            rows_of.append(rows)
+        # need[r][q]: global rows owned by q that rows of r list as neighbours, in q's local row order
+        self.need = []
+        cr = row_owner[ci]
+        for r in range(W):
+            nb = np.unique(cj[cr == r])
+            nb = nb[np.argsort(row_local[nb], kind="stable")]
+            onb = row_owner[nb]
+            self.need.append([nb[onb == q] for q in range(W)])
+        po, c = procs[me]
+        self.own_global = self.owned[me]
+        self.n_own = int(self.own_global.size)
+        self.proc_order = po.astype(np.int32)
+        self.own_proc = self.own_global[po]
+        self.r_send, self.r_need = (int(c[0]), int(c[2])), (int(c[1]), int(c[3]))
+        self.n_send_nodes, self.n_need_nodes = int(c[2] - c[0]), int(c[3] - c[1])
+        self.own_rows = rows_of[me]
+        self.halo_rows = np.concatenate(self.need[me]) if W > 1 else np.zeros(0, dtype=np.int64)
+        self.ext_rows = np.concatenate([self.own_rows, self.halo_rows])
+        self.n_rows_own, self.n_rows_halo = int(self.own_rows.size), int(self.halo_rows.size)
+        self.n_rows_ext = self.n_rows_own + self.n_rows_halo
+        self.seg_rowptr = np.concatenate(([0], np.cumsum(n_rows[self.own_proc]))).astype(np.int32)
+        g2l = -np.ones(n_prod, dtype=np.int64)
+        g2l[self.ext_rows] = np.arange(self.n_rows_ext)
+        self.row_to_local = g2l
+
+        def local_csr(rowptr, cols):
+            deg = (rowptr[1:] - rowptr[:-1])[self.own_rows]
+            lrp = np.concatenate(([0], np.cumsum(deg)))
+            take = np.repeat(rowptr[:-1][self.own_rows] - lrp[:-1], deg) + np.arange(int(lrp[-1]))
+            lc = g2l[cols[take]] if take.size else np.zeros(0, dtype=np.int64)
+            assert (lc >= 0).all(), "halo is incomplete"
+            return lrp.astype(np.int32), lc.astype(np.int32)
+        self.src_rowptr, self.src_col = local_csr(rp, col)
+        self.sta_rowptr, self.sta_col = local_csr(srp, scol)
+        assert (self.sta_col < self.n_rows_own).all()
+        self.send_rows = [g2l[self.need[q][me]] if q != me else np.zeros(0, dtype=np.int64) for q in range(W)]
+        self.send_counts = [int(x.size) for x in self.send_rows]
+        self.recv_counts = [int(x.size) for x in self.need[me]]
+
+    def halo_fraction(self):
+        return self.n_rows_halo / max(1, self.n_rows_own)
+
+
 class Transport(object):
     """The two collectives of the sharded path. RCCL ("nccl") takes device buffers directly on the current stream; a process
     group without device collectives (gloo: the CPU tests and the several-processes-on-one-GPU test) is served by staging
@@ -404,22 +514,48 @@ class ShardedPath(object):
     sta_csr: (rowptr, col) of the station graph; A_src_src: global [2, E]; pos_global: [G, 3]; pos_sta: optional [S, 3]
     station positions -> station processing order (the same on every rank: the halo rows of `wv` travel in that order).
     `overlap=False` runs the window as four sequential steps (stage 1, exchange, stage 2, all-gather) on one stream: the
-    A/B reference for the overlapped schedule (bit-identical results)."""
+    A/B reference for the overlapped schedule (bit-identical results).
+    `subgraph` = dict(n_prod, sta_csr, src_csr, seg_rowptr) of the WHOLE irregular product graph (`use_subgraph`, as
+    `engine.HipPath(subgraph=)` takes it): the shard is then over rows (`SubgraphShardPlan`: ragged halo, exchange counts in rows, the
+    local context `genie_ctx_create_subgraph_ext`); `sta_csr` is ignored. The same schedules; the front and the replicated tail only
+    (no association heads, no time-pointer tables, the default model definition)."""
 
     def __init__(self, n_sta, n_grid, sta_csr, A_src_src, pos_global, world, rank, device, group=None, scale_rel=30000.0,
-                 pos_sta=None, overlap=True, halo="a2a", emulate=False):
+                 pos_sta=None, overlap=True, halo="a2a", emulate=False, subgraph=None):
         self.group = group
         self.n_sta, self.n_grid = int(n_sta), int(n_grid)
         order = engine.sfc_order(np.asarray(pos_global))
-        self.plan = ShardPlan(A_src_src, n_grid, world, rank, order)
-        p = self.plan
         self.overlap = bool(overlap)
         if halo not in ("a2a", "p2p"):
             raise ValueError("halo must be 'a2a' (one all_to_all_single) or 'p2p' (one send / receive pair per peer)")
         self.halo = halo
-        self.local = engine.HipPath(n_sta, p.n_own, sta_csr, (torch.from_numpy(p.src_rowptr), torch.from_numpy(p.src_col)),
-                                    n_grid_ext=p.n_ext, grid_order=p.proc_order, scale_rel=scale_rel, device=device,
-                                    sta_order=engine.sfc_order(np.asarray(pos_sta)) if pos_sta is not None else None)
+        self.irregular = subgraph is not None
+        if self.irregular:
+            to_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+            self.plan = p = SubgraphShardPlan(to_np(subgraph["seg_rowptr"]), [to_np(t) for t in subgraph["src_csr"]],
+                                              [to_np(t) for t in subgraph["sta_csr"]], n_grid, world, rank, order)
+            if p.n_prod != int(subgraph["n_prod"]):
+                raise ValueError("subgraph: seg_rowptr does not end at n_prod")
+            if p.n_rows_own < 1:
+                raise ValueError("rank %d of %d owns no product node of the irregular product graph" % (rank, world))
+            self.n_prod = p.n_prod
+            self.rows_own, self.rows_halo, self.rows_ext, self._unit = p.n_rows_own, p.n_rows_halo, p.n_rows_ext, 1
+            t = torch.from_numpy
+            self.local = engine.HipPath(n_sta, p.n_own, None, None, scale_rel=scale_rel, device=device, subgraph={
+                "n_prod": p.n_rows_own, "n_prod_ext": p.n_rows_ext, "sta_csr": (t(p.sta_rowptr), t(p.sta_col)),
+                "src_csr": (t(p.src_rowptr), t(p.src_col)), "seg_rowptr": t(p.seg_rowptr)})
+            send = p.send_rows
+        else:
+            self.plan = p = ShardPlan(A_src_src, n_grid, world, rank, order)
+            S = self.n_sta
+            self.n_prod = self.n_grid * S
+            # rows of the local lists; `_unit`: rows per exchanged block (a source node's S rows; one row on an irregular graph)
+            self.rows_own, self.rows_halo, self.rows_ext, self._unit = p.n_own * S, p.n_halo * S, p.n_ext * S, S
+            self.local = engine.HipPath(n_sta, p.n_own, sta_csr, (torch.from_numpy(p.src_rowptr), torch.from_numpy(p.src_col)),
+                                        n_grid_ext=p.n_ext, grid_order=p.proc_order, scale_rel=scale_rel, device=device,
+                                        sta_order=engine.sfc_order(np.asarray(pos_sta)) if pos_sta is not None else None)
+            send = p.send_local
+        self._send_blocks = send         # per peer: the local blocks (source nodes, or rows of an irregular graph) sent to it
         self.full = engine.HipPath(1, n_grid, (torch.zeros(2, dtype=torch.int32), torch.zeros(0, dtype=torch.int32)),
                                    engine.csr_from_edges(torch.as_tensor(A_src_src), n_grid), grid_order=None,
                                    scale_rel=scale_rel, device=device)
@@ -429,7 +565,7 @@ class ShardedPath(object):
         pitch = int(self.local.lib.genie_ws_v_pitch(self.local.ctx))
         self._pitch = pitch
         # static exchange state: send-row index, send buffer, the halo part of `wv` inside the workspace (received in place)
-        self._send_idx = torch.as_tensor(np.concatenate(p.send_local).astype(np.int64) if world > 1 else np.zeros(0, np.int64), device=dev)
+        self._send_idx = torch.as_tensor(np.concatenate(send).astype(np.int64) if world > 1 else np.zeros(0, np.int64), device=dev)
         self._send_bufs = {}             # row width -> send buffer (wv: 16 floats; the association heads' q2: 32)
         nl = -np.ones(self.n_grid, dtype=np.int32)
         nl[p.own_global] = np.arange(p.n_own, dtype=np.int32)
@@ -437,6 +573,8 @@ class ShardedPath(object):
         idx, n_max = gather_index(p)
         self._gather = (torch.as_tensor(idx, device=dev), n_max)
         self._bip_pad = torch.zeros((n_max, 15), dtype=torch.float32, device=dev)
+        # irregular: the local context numbers its nodes in processing order; its [n_own, 15] output goes back to `own_global` order
+        self._bip_unproc = torch.as_tensor(np.argsort(p.proc_order).astype(np.int64), device=dev) if self.irregular else None
         self.comm_stream = torch.cuda.Stream(device=dev) if self.local.device.type == "cuda" else None
         self.tail_stream = torch.cuda.Stream(device=dev) if self.local.device.type == "cuda" else None
         self._tail_done = None
@@ -460,7 +598,10 @@ class ShardedPath(object):
         that make up this rank's local rows (owned + halo blocks, or the owned blocks only). Built once."""
         key = "_rows_own" if own_only else "_rows_ext"
         idx = getattr(self, key, None)
-        if idx is None:
+        if idx is None and self.irregular:      # the plan's global row ids as they are
+            idx = torch.as_tensor(self.plan.own_rows if own_only else self.plan.ext_rows, dtype=torch.int64, device=self.device)
+            setattr(self, key, idx)
+        elif idx is None:
             g = torch.as_tensor(self.plan.own_global if own_only else self.plan.ext_global, dtype=torch.int64, device=self.device)
             idx = (g.view(-1, 1) * self.n_sta + torch.arange(self.n_sta, dtype=torch.int64, device=self.device).view(1, -1)).reshape(-1)
             setattr(self, key, idx)
@@ -469,17 +610,17 @@ class ShardedPath(object):
     def local_rows(self, t, name, cols, own_only=False):
         """This rank's rows of a per-product-node input: a `ShardRows` is taken as it is (its row count is checked), a full
         `[G * S, cols]` tensor (the reference's argument) is cut down by ONE `index_select` on the device it lives on."""
-        n_loc = (self.plan.n_own if own_only else self.plan.n_ext) * self.n_sta
+        n_loc = self.rows_own if own_only else self.rows_ext
         if isinstance(t, ShardRows):
-            if t.own_only != own_only and self.plan.n_halo:
+            if t.own_only != own_only and self.rows_halo:
                 if own_only and not t.own_only:           # owned blocks come first in the local order
-                    return engine._f32(t.t, name, (self.plan.n_ext * self.n_sta, cols))[:n_loc]
+                    return engine._f32(t.t, name, (self.rows_ext, cols))[:n_loc]
                 raise ValueError("%s: rows of the owned source nodes only, the halo rows are needed too" % name)
             return engine._f32(t.t, name, (n_loc, cols))
         t = torch.as_tensor(t)
-        if tuple(t.shape) != (self.n_grid * self.n_sta, cols):
+        if tuple(t.shape) != (self.n_prod, cols):
             raise ValueError("%s: expected shape (%d, %d) (all product nodes) or a ShardRows of %d local rows, got %s"
-                             % (name, self.n_grid * self.n_sta, cols, n_loc, tuple(t.shape)))
+                             % (name, self.n_prod, cols, n_loc, tuple(t.shape)))
         idx = self.row_index(own_only)
         if t.device != idx.device:
             return t.index_select(0, idx.to(t.device)).to(self.device, torch.float32)
@@ -488,28 +629,45 @@ class ShardedPath(object):
     def set_edge_features(self, pos_sta, pos_src_global):
         """`use_updated_model_definition` on the shard (genie_set_edge_features): the mean edge features of the owned source nodes
         come from the local CSR over the EXTENDED node list, so the positions of the halo nodes travel with the plan, not per window."""
+        self._cartesian_only("set_edge_features (use_updated_model_definition)")
         ext = torch.as_tensor(self.plan.ext_global, dtype=torch.long)
         pos = torch.as_tensor(pos_src_global).float()
         self.local.set_edge_features(torch.as_tensor(pos_sta).float().to(self.device), pos[ext].contiguous().to(self.device))
 
     def set_absolute_pos(self, pos_sta, pos_src_global):
         """`use_absolute_pos` on the shard (genie_set_absolute_pos): scaled positions of the stations and of the extended node list."""
+        self._cartesian_only("set_absolute_pos (use_absolute_pos)")
         ext = torch.as_tensor(self.plan.ext_global, dtype=torch.long)
         pos = torch.as_tensor(pos_src_global).float()
         self.local.set_absolute_pos(torch.as_tensor(pos_sta).float().to(self.device), pos[ext].contiguous().to(self.device))
 
+    def _cartesian_only(self, what):
+        if self.irregular:
+            raise NotImplementedError("%s is not available on a source-node shard of an irregular product graph (use_subgraph): it serves "
+                                      "the front and the replicated tail of the default model definition" % what)
+
+    def set_subgraph_stations(self, sta_of_prod):
+        """Station of every product node of the WHOLE irregular graph -> the local context's owned + halo rows (`embed_window`)."""
+        if not self.irregular:
+            raise ValueError("set_subgraph_stations: not an irregular product graph")
+        t = torch.as_tensor(sta_of_prod).reshape(-1)
+        if t.numel() != self.n_prod:
+            raise ValueError("sta_of_prod must have n_prod entries")
+        self.local.set_subgraph_stations(t.cpu()[torch.from_numpy(self.plan.ext_rows)])
+
     def wv_view(self):
-        """Float view [n_ext*S, 16] of the projected operand `wv` inside the local workspace."""
+        """Float view [local rows (owned, then halo), 16] of the projected operand `wv` inside the local workspace."""
         lp = self.local
         ptr = lp.lib.genie_ws_v_ptr(lp.ctx, lp._ws_ptr)
         off = int(ptr) - lp.ws.data_ptr()
-        n = self.plan.n_ext * self.n_sta * self._pitch
-        return lp.ws[off: off + 4 * n].view(torch.float32).view(self.plan.n_ext * self.n_sta, self._pitch)
+        n = self.rows_ext * self._pitch
+        return lp.ws[off: off + 4 * n].view(torch.float32).view(self.rows_ext, self._pitch)
 
     def _exchange(self, wv):
         """Pack the SEND rows, all-to-all, halo rows received in place (the halo part of `wv` is contiguous, grouped by owner). `wv`:
-        any per-product-node operand [n_ext * S, pitch] in the local row space (the workspace's wv rows, the association heads' q2)."""
-        p, S = self.plan, self.n_sta
+        any per-product-node operand [local rows, pitch] in the local row space (the workspace's wv rows, the association heads' q2).
+        A block is the S rows of a source node; on an irregular graph one row (ragged counts: `SubgraphShardPlan`)."""
+        p, S = self.plan, self._unit
         pitch = int(wv.shape[1])
         send_buf = self._send_bufs.get(pitch)
         if send_buf is None:
@@ -518,11 +676,11 @@ class ShardedPath(object):
             return                      # no process group at all. (With one, EVERY rank enters the collective, also a rank with
                                         # nothing to exchange and the single rank of a world-size-1 group: the RCCL code path of the
                                         # 1-GPU tests and of `bench.py --gpus 1 --mode sharded`)
-        blocks = wv[: p.n_own * S].view(p.n_own, S * pitch)
-        recv = wv[p.n_own * S:].view(p.n_halo, S * pitch)
+        blocks = wv[: self.rows_own].view(self.rows_own // S, S * pitch)
+        recv = wv[self.rows_own:].view(self.rows_halo // S, S * pitch)
         if self.halo == "p2p":       # bucketed by destination: pack of peer q + 1 under the transfer of peer q, largest pair first
             if getattr(self, "_send_idx_q", None) is None:
-                self._send_idx_q = [torch.as_tensor(x.astype(np.int64), device=self.device) for x in p.send_local]
+                self._send_idx_q = [torch.as_tensor(x.astype(np.int64), device=self.device) for x in self._send_blocks]
             self.transport.halo_p2p_rows(recv, send_buf, p.recv_counts, p.send_counts, p.rank,
                                          pack=lambda q, view: torch.index_select(blocks, 0, self._send_idx_q[q], out=view))
             return
@@ -537,16 +695,16 @@ class ShardedPath(object):
         p, S = self.plan, self.n_sta
         lp = self.local
         lp.check_input_range()         # (verdicts of the windows that have completed: engine.HipPath.check_input_range)
-        P_ext = p.n_ext * S
+        P_ext = self.rows_ext
         Slice_ext = engine._f32(Slice_ext, "Slice", (P_ext, 4))
         Mask_ext = engine._f32(Mask_ext, "Mask", (P_ext, 4))
-        edge_attr_own = engine._f32(edge_attr_own, "edge_attr", (p.n_own * S, 3))
+        edge_attr_own = engine._f32(edge_attr_own, "edge_attr", (self.rows_own, 3))
         ea = getattr(lp, "_static_ea", None)
         if ea is None or ea.data_ptr() != edge_attr_own.data_ptr() or edge_attr_own._version != lp._static_ea_version:
             # the static edge_attr of the owned rows: registered once, so that stage 2 reads its processing-order copy and runs
             # the straight-line row-layout kernel (k_stage2_ord) as the unsharded path does
             lp.set_static_edge_attr(edge_attr_own)
-        Mask_own = Mask_ext[: p.n_own * S]
+        Mask_own = Mask_ext[: self.rows_own]
         wv = self.wv_view()
         main = torch.cuda.current_stream(self.device)
         (s0, s1), (n0, n1), n = p.r_send, p.r_need, p.n_own
@@ -570,7 +728,7 @@ class ShardedPath(object):
             main.wait_event(halo)
             lp.da_stage2_partials_range(Mask_own, edge_attr_own, n0, n1, x_latent_out)
         bip_own = lp.bipartite_readout()
-        return bip_own
+        return bip_own if self._bip_unproc is None else bip_own.index_select(0, self._bip_unproc)
 
     def gather_and_tail(self, bip_own, pos_global, tail=None):
         """All-gather of the Bipartite output, SpatialAggregation x3 (replicated) and `tail(x_spatial)` (the read-outs)."""
@@ -589,6 +747,7 @@ class ShardedPath(object):
         rank's x_latent / Mask / edge_attr rows -> s [n_own * S, 30]. Two halo exchanges on the current stream, one per layer: the q2
         rows (32 floats) before layer 1, the wv rows before the last pass -- the plan and transport of the DataAggregation window. Call
         after `front` of the same window."""
+        self._cartesian_only("assoc_fwd (the association heads)")
         own = getattr(self, "_own_idx", None)
         if own is None:
             own = self._own_idx = torch.as_tensor(self.plan.own_global, dtype=torch.int64, device=self.device)
@@ -601,6 +760,7 @@ class ShardedPath(object):
         """The time-pointer tables of the whole product graph from this rank's own travel-time rows (`shard_time_pointers`: candidates
         per rank, one all-gather, merge on every rank). tlatent: a `ShardRows` of this rank's rows (owned, or owned + halo), or the whole [G * S, 2] table, of which only the owned rows are
         taken (cut out where the table lives). Returns (A_edges_p, A_edges_s, dt_partition, the owned rows as an own-only `ShardRows`)."""
+        self._cartesian_only("time_pointers")
         tl_own = self.local_rows(tlatent, "tlatent", 2, own_only=True).contiguous()
         edges_p, edges_s, dt_partition = shard_time_pointers(tl_own, self.plan.own_global, self.n_sta, self.n_grid, self.transport,
                                                              max_t=max_t, dt=dt, k=k, win=win)
@@ -612,6 +772,7 @@ class ShardedPath(object):
         its entry number -> table [2 * n_picks * 10, 32] (`HipPath.lslc_fwd_rows` takes it), the same on every rank. tlatent: the
         travel times of the whole product graph [G * S, >= 2], or a `ShardRows` of this rank's rows (tables built by `time_pointers`):
         either way the arrival of a listed row is read by its owner and travels in the row."""
+        self._cartesian_only("pick_rows (the association heads)")
         own = isinstance(tlatent, ShardRows)
         if own:
             tlatent = self.local_rows(tlatent, "tlatent", int(tlatent.shape[1]), own_only=True)

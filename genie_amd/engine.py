@@ -720,7 +720,10 @@ class HipPath(object):
         """`stage_precision`: "auto" (default: two-piece fp16 operands on the 16-bit matrix pipe while the library's fp16 range guard
         holds for the committed weights, fp32 MFMA otherwise), "f16x2" or "f32" (A/B runs); None = `engine.STAGE_PRECISION`.
         `subgraph` = dict(n_prod, sta_csr, src_csr, seg_rowptr): an irregular product graph (`use_subgraph`) given as
-        product-level CSRs + the row range of every source node (genie_ctx_create_subgraph); `sta_csr` is then ignored.
+        product-level CSRs + the row range of every source node (genie_ctx_create_subgraph); `sta_csr` is then ignored. With
+        `n_prod_ext` in the dict: one rank's part of a source-node-sharded irregular graph (genie_ctx_create_subgraph_ext): `n_grid`
+        owned source nodes in processing order, their `n_prod` rows, then the halo rows up to `n_prod_ext`; CSR columns are local
+        row ids, `src_csr` / `grid_order` are not used.
         `grid_order` / `sta_order`: processing orders of the source nodes / stations (e.g. `sfc_order(positions)`);
         internal only, every input and output keeps the caller's order."""
         self.lib = _lib.load()
@@ -730,7 +733,7 @@ class HipPath(object):
         self.n_sta, self.n_grid = int(n_sta), int(n_grid)
         self.n_grid_ext = int(n_grid_ext) if n_grid_ext is not None else self.n_grid
         self.scale_rel = float(scale_rel)
-        self._n_prod = None
+        self._n_prod = self._n_prod_ext = None
         dev = self.device
         order = None
         if grid_order is not None:
@@ -738,10 +741,27 @@ class HipPath(object):
             if order.numel() != self.n_grid:
                 raise ValueError("grid_order must have n_grid entries")
         self.ctx = ctypes.c_void_p(0)
-        if subgraph is not None:
+        if subgraph is not None and subgraph.get("n_prod_ext") is not None:
+            if self.n_grid_ext != self.n_grid or order is not None:
+                raise ValueError("an extended irregular product graph numbers its owned source nodes in processing order: no "
+                                 "n_grid_ext, no grid_order")
+            self._n_prod, self._n_prod_ext = int(subgraph["n_prod"]), int(subgraph["n_prod_ext"])
+            self._keep = [t.to(dev, torch.int32).contiguous() for t in (
+                subgraph["sta_csr"][0], subgraph["sta_csr"][1], subgraph["src_csr"][0], subgraph["src_csr"][1], subgraph["seg_rowptr"])]
+            k = self._keep
+            if k[0].numel() != self._n_prod + 1 or k[2].numel() != self._n_prod + 1 or k[4].numel() != self.n_grid + 1:
+                raise ValueError("subgraph CSR arrays do not match n_prod / n_grid")
+            with torch.cuda.device(dev):
+                torch.cuda.synchronize()
+                rc = self.lib.genie_ctx_create_subgraph_ext(ctypes.byref(self.ctx), self.n_sta, self.n_grid, self._n_prod, self._n_prod_ext,
+                                                            _ptr(k[0]), _ptr(k[1]), _ptr(k[2]), _ptr(k[3]), _ptr(k[4]),
+                                                            ctypes.c_float(self.scale_rel))
+            _lib.check(rc, "genie_ctx_create_subgraph_ext")
+        elif subgraph is not None:
             if self.n_grid_ext != self.n_grid:
-                raise ValueError("an irregular product graph cannot be sharded")
-            self._n_prod = int(subgraph["n_prod"])
+                raise ValueError("an irregular product graph is sharded over an extended row list (subgraph['n_prod_ext']), not over "
+                                 "n_grid_ext")
+            self._n_prod = self._n_prod_ext = int(subgraph["n_prod"])
             self._keep = [t.to(dev, torch.int32).contiguous() for t in (
                 subgraph["sta_csr"][0], subgraph["sta_csr"][1], subgraph["src_csr"][0], subgraph["src_csr"][1],
                 subgraph["seg_rowptr"], src_csr[0], src_csr[1])]
@@ -791,8 +811,8 @@ class HipPath(object):
         if self._n_prod is None:
             raise ValueError("set_subgraph_stations: not an irregular product graph")
         t = torch.as_tensor(sta_of_prod).to(self.device, torch.int32).contiguous()
-        if t.numel() != self._n_prod:
-            raise ValueError("sta_of_prod must have n_prod entries")
+        if t.numel() != self._n_prod_ext:
+            raise ValueError("sta_of_prod must have n_prod entries (owned and halo rows of an extended context)")
         _lib.check(self.lib.genie_set_subgraph_stations(self.ctx, _ptr(t), _stream()), "genie_set_subgraph_stations")
         torch.cuda.current_stream().synchronize()      # (the library keeps its own copy)
 
@@ -852,7 +872,7 @@ class HipPath(object):
 
     @property
     def n_prod_ext(self):
-        return self._n_prod if self._n_prod is not None else self.n_sta * self.n_grid_ext
+        return self._n_prod_ext if self._n_prod is not None else self.n_sta * self.n_grid_ext
 
     # ---- weights -------------------------------------------------------------------------------
     def set_weights(self, named_tensors):

@@ -658,6 +658,9 @@ class GCN_Detection_Network_extended(nn.Module):
         the HipPath `path`, or for the owned (+ halo) source nodes of the ShardedPath `path`; returned on the device (a `ShardRows` when
         sharded)."""
         sharded = isinstance(path, _dist.ShardedPath)
+        if sharded and path.irregular:
+            raise NotImplementedError("a callable over source-node ids (node_rows / edge_attr) is not available on a source-node shard of "
+                                      "an irregular product graph (use_subgraph): pass the table of all product nodes or a ShardRows")
         ids = (path.plan.own_global if own_only else path.plan.ext_global) if sharded else np.arange(path.n_grid, dtype=np.int64)
         parts = []
         for i in range(0, len(ids), block):
@@ -722,7 +725,6 @@ class GCN_Detection_Network_extended(nn.Module):
             except ValueError:
                 cartesian = False
         if not cartesian:
-            self._not_sharded("an irregular product graph (use_subgraph)")
             return self._set_adjacencies_subgraph(A_in_sta, A_in_src, A_src_in_edges, A_src_in_sta, A_src, n_sta, n_grid,
                                                   pos_loc, pos_src)
         src_csr = _engine.csr_from_table(src_nbr)
@@ -773,6 +775,10 @@ class GCN_Detection_Network_extended(nn.Module):
     def _set_adjacencies_subgraph(self, A_in_sta, A_in_src, A_src_in_edges, A_src_in_sta, A_src, n_sta, n_grid, pos_loc, pos_src):
         """`use_subgraph: True` (config.yaml:86, process_utils.py:744-849): the product nodes are the pairs listed in
         A_src_in_sta (grouped by source node) and the edge lists are irregular: product-level CSRs, generic HIP kernels."""
+        if self._shard_cfg is not None and (self.use_updated_model_definition or self.use_absolute_pos):
+            raise NotImplementedError("set_adjacencies with an irregular product graph (use_subgraph) under use_updated_model_definition / "
+                                      "use_absolute_pos is not available on a source-node-sharded model (process_group / shard): an "
+                                      "irregular shard serves the default model definition")
         pairs = torch.as_tensor(A_src_in_sta).long().cpu()
         n_prod = int(pairs.shape[1])
         src_of = pairs[1]
@@ -782,6 +788,14 @@ class GCN_Detection_Network_extended(nn.Module):
         seg[1:] = torch.cumsum(torch.bincount(src_of, minlength=n_grid), 0).to(torch.int32)
         sub = {"n_prod": n_prod, "sta_csr": _engine.csr_from_edges(A_in_sta, n_prod),
                "src_csr": _engine.csr_from_edges(A_in_src, n_prod), "seg_rowptr": seg}
+        if self._shard_cfg is not None:
+            # this rank's rows of the irregular graph (dist.SubgraphShardPlan: ownership by source node, ragged halo of rows) and the
+            # replicated G-sized context over the base source graph, as on a Cartesian shard
+            rank, world, group = self._shard_cfg
+            to_np = lambda t: t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+            new = _dist.ShardedPath(n_sta, n_grid, None, to_np(torch.as_tensor(A_src)), to_np(pos_src), world, rank,
+                                    next(self.parameters()).device, group=group, scale_rel=self.scale_rel, subgraph=sub, **self._shard_opts)
+            return self._install(new, A_src_in_edges.x, pos_loc, pos_src, pairs=pairs)
         order = _engine.sfc_order(pos_src.detach().cpu().numpy())
         new = _engine.HipPath(n_sta, n_grid, None, _engine.csr_from_edges(A_src, n_grid), grid_order=order,
                               scale_rel=self.scale_rel, device=next(self.parameters()).device, subgraph=sub)
@@ -802,7 +816,10 @@ class GCN_Detection_Network_extended(nn.Module):
         `time_pointers=dict(max_t=, dt=, k=, win=)` also builds the time-pointer tables of the 4-output `forward_fixed` on the device
         (`engine.time_pointers_device`, irregular form: a station with fewer than k product nodes cycles through them) and leaves
         A_edges_p / A_edges_s / dt_partition / tlatent on the model."""
-        self._not_sharded("an irregular product graph (use_subgraph)")
+        # (a shard serves the irregular lists themselves: `set_adjacencies`; the device build of the whole graph's pairs and CSRs is the
+        # replication a shard avoids)
+        self._not_sharded("set_adjacencies_subgraph_from_positions (use_subgraph set up on the device; pass the irregular lists to "
+                          "set_adjacencies, which builds this rank's shard of them)")
         if time_pointers is not None and tlatent is None:
             raise ValueError("time_pointers= needs the travel times (tlatent=)")
         dev = next(self.parameters()).device
@@ -1123,6 +1140,10 @@ class GCN_Detection_Network_extended(nn.Module):
         (`ShardedPath.assoc_fwd`); the rows the picks' time-pointer entries list travel in ONE ragged all-gather from their owners, each with its
         travel time (`ShardedPath.pick_rows`, genie_lslc_rows: `self.tlatent` is the whole table or this rank's `ShardRows`), and the
         pick-sized heads run replicated on them. Every rank joins every collective, whatever it owns."""
+        if self._shard is not None and self._shard.irregular:
+            raise NotImplementedError("forward_fixed (the four outputs) on an irregular product graph (use_subgraph) is not available on a "
+                                      "source-node-sharded model (process_group / shard): an irregular shard serves "
+                                      "forward_fixed_source[_pipelined], embed_window, node_rows and apply.apply_windows_device")
         self._sharded_forward_guard(getattr(self, "A_edges_p", None), getattr(self, "A_edges_s", None), getattr(self, "tlatent", None))
         return self._sharded_four_outputs(Slice, Mask, tpick, ipick, phase_label, x_temp_cuda_cart, x_query_cart, x_query_src_cart, t_query,
                                           tq_sample, trv_out_q)
@@ -1182,6 +1203,10 @@ class GCN_Detection_Network_extended(nn.Module):
         are checked up front (no deferred verdicts) and the call ends in the sharded `forward_fixed`."""
         sharded = self._shard_cfg is not None
         if sharded:
+            if int(A_src_in_sta.shape[1]) != int(locs_use_cart.shape[0]) * int(x_temp_cuda_cart.shape[0]):
+                raise NotImplementedError("forward (the four outputs) on an irregular product graph (use_subgraph) is not available on a "
+                                          "source-node-sharded model (process_group / shard): an irregular shard serves set_adjacencies, "
+                                          "forward_fixed_source[_pipelined], embed_window, node_rows and apply.apply_windows_device")
             self._sharded_forward_guard(A_edges_p, A_edges_s, tlatent)
 
         def tk(t):

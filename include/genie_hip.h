@@ -81,6 +81,22 @@ int genie_ctx_create_subgraph(genie_ctx** out, int n_sta, int n_grid, int64_t n_
                               const int32_t* p_sta_rowptr, const int32_t* p_sta_col,
                               const int32_t* p_src_rowptr, const int32_t* p_src_col, const int32_t* seg_rowptr,
                               const int32_t* src_rowptr, const int32_t* src_col, const int32_t* grid_order, float scale_rel);
+/* One rank's part of an irregular product graph sharded over source nodes: an irregular context over an EXTENDED row list. The n_own
+ * owned source nodes are numbered in the order the rank processes them and their product rows come first, node after node
+ * (seg_rowptr [n_own + 1], seg_rowptr[n_own] = n_prod_own); rows [n_prod_own, n_prod_ext) are HALO rows: product nodes of source nodes
+ * owned elsewhere. p_sta_* / p_src_* are the product-level CSRs of the n_prod_own owned rows with columns in this local numbering:
+ * station neighbours are owned rows, source neighbours owned or halo rows, in the edge order of the unsharded lists (every column is
+ * checked against those bounds here; GENIE_ERR_ARG). Slice / Mask (and genie_set_subgraph_stations, genie_embed_window*) have
+ * n_prod_ext rows, every other [P, .] argument and the c / wu rows n_prod_own; the wv rows (genie_ws_v_ptr) have n_prod_ext, the halo
+ * part filled by the caller between the two stages. Because a range of source nodes is a range of rows, genie_da_stage1_range and
+ * genie_da_stage2_partials_range are served on such a context (on genie_ctx_create_subgraph they are not), with genie_da_stage1,
+ * genie_da_stage2_partials and genie_bipartite_readout; every kernel cuts its tiles from the first row of the range or of the source
+ * node, so each row's and each node's result is the unsharded context's, bit for bit. Inference only and the default model
+ * definition: the training calls, genie_assoc_fwd*, genie_set_edge_features and genie_set_absolute_pos return GENIE_ERR_STATE, and
+ * no base source graph is kept (nothing G-sized runs on it). */
+int genie_ctx_create_subgraph_ext(genie_ctx** out, int n_sta, int n_own, int64_t n_prod_own, int64_t n_prod_ext,
+                                  const int32_t* p_sta_rowptr, const int32_t* p_sta_col,
+                                  const int32_t* p_src_rowptr, const int32_t* p_src_col, const int32_t* seg_rowptr, float scale_rel);
 /* Station index of every product node of an irregular product graph (device pointer, n_prod int32 = row 0 of the reference's
  * A_src_in_sta, process_utils.py:790-794; copied): what the device embedding reads where a Cartesian graph has p % n_sta. `trv` of
  * genie_embed_window* is then [n_prod, 2], the travel times of the listed (station, source) pairs
