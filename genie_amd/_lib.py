@@ -49,6 +49,8 @@ SYMBOLS = [
     ("genie_index_check", _c.c_int, [_P, _P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_uint, _P]),
     ("genie_set_static_edge_attr", _c.c_int, [_P, _P, _P]),
     ("genie_tail_batched", _c.c_int, [_P, _c.c_int, _c.c_int, _P, _P, _P, _c.c_int, _c.c_int, _P, _c.c_int, _P, _P, _P, _P, _P]),
+    ("genie_tail_batched_q", _c.c_int, [_P, _c.c_int, _c.c_int, _P, _c.c_int, _P, _P, _P, _c.c_int, _c.c_int, _P, _c.c_int, _P, _P, _P, _P,
+                                        _P]),
     ("genie_readout_grid", _c.c_int, [_P, _P, _P, _c.c_int, _P, _P]),
     ("genie_readout_query", _c.c_int, [_P, _P, _P, _P, _P, _c.c_int, _c.c_int, _P, _c.c_int, _P, _P, _P]),
     ("genie_readouts", _c.c_int, [_P, _P, _P, _P, _P, _c.c_int, _c.c_int, _P, _c.c_int, _P, _P, _P, _P]),
@@ -154,6 +156,8 @@ SYMBOLS = [
     ("genie_refine_select_scratch_bytes", _c.c_size_t, []),
     ("genie_refine_select", _c.c_int, [_P, _c.c_int, _c.c_int64, _c.c_int, _P, _c.c_float, _P, _P, _P]),
     ("genie_refine_cloud", _c.c_int, [_c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int64] + [_c.c_double] * 9 + [_P, _P, _P, _P]),
+    ("genie_refine_select_batch", _c.c_int, [_P, _c.c_int, _c.c_int, _c.c_int64, _c.c_int, _P, _c.c_float, _P, _P, _P]),
+    ("genie_refine_cloud_batch", _c.c_int, [_c.c_uint64, _c.c_uint64, _c.c_uint64, _c.c_int, _c.c_int64, _P] + [_c.c_double] * 6 + [_P, _P, _P]),
     ("genie_adam_step", _c.c_int, [_P, _P, _P, _c.c_int64, _P, _c.c_int, _c.c_int64, _P, _c.c_double, _c.c_double, _c.c_double, _c.c_double,
                                    _c.c_int64, _P]),
     ("genie_ws_export", _c.c_int, [_P, _c.c_int, _P, _P, _P]),

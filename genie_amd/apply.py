@@ -995,7 +995,7 @@ def refined_from_found(found, srcs, tq, ftrns2):
 
 def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offset_range, n_rand_query, ftrns1, ftrns2,
                    lat_range, lon_range, depth_range, kernel_sig_t=synthetic.KERNEL_SIG_T, dt_embed=None, rand=None, ftrns2_device=None,
-                   source_parallel=None, merge_timeout=60.0, source_offset=0):
+                   source_parallel=None, merge_timeout=60.0, source_offset=0, source_batch=1):
     """The refine pass of the caller (process_continuous_days.py:926-980) on the device: for every candidate source `srcs[i]` = (lat, lon,
     depth, origin time, value) a cloud of `n_rand_query` random queries around it (`ftrns1(src) + rand(n, 3) * X_offset_range +
     X_offset_min`, kept where `ftrns2` of it lies strictly inside the three ranges, :929-936), one `forward_fixed_source` per grid
@@ -1031,7 +1031,22 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
 
     `source_offset`: the place of `srcs[0]` in a longer list of which `srcs` is a contiguous part (`OnlineCatalogue` refines a day's
     sources a few at a time): a keyed draw for local source i uses counter `source_offset + i`, so the part draws the clouds the whole
-    list would have drawn for these sources. A plain callable `rand` has no counter and ignores it; 0 is the whole list."""
+    list would have drawn for these sources. A plain callable `rand` has no counter and ignores it; 0 is the whole list.
+
+    `source_batch`: 1 (default) refines one source after the other as described above. B in 2..16 (needs `ftrns2_device`; ValueError
+    otherwise) takes the rank's sources B at a time, the last batch short: one cloud launch per batch (`postproc.refine_cloud_batch_device`;
+    with a plain `rand` the staged draws stacked, `rand` still called once per source in source order), per leg one `push_window` per
+    source whose window holds a pick and ONE G-sized tail with both read-outs for the batch (`flush_windows_clouds`: every window read
+    out at its own cloud, one kNN search for all clouds), and one select launch pair (`postproc.refine_select_batch_device`). The
+    region mask stays one `ftrns2_device` call per source. The rows, and so the results, are those of `source_batch=1` bit for bit.
+    Each leg model's `window_batch` is set to B for the pass and put back afterwards (on an exception too, unless windows are still
+    pending); unsharded models only. Measured at config 2 (112 000 queries, one leg, keyed draw; tools/refine_batch_time.py,
+    profiles/EXPERIMENTS.md): 1.76 ms per source one by one, 1.33 / 1.29 / 1.23 ms in batches of 4 / 8 / 16, run-to-run spread 0.01 to
+    0.1 ms -- 16 is the recommended value where the sources of a call are many; the default stays 1."""
+    source_batch = _check_source_batch(source_batch, ftrns2_device)
+    if source_batch > 1:
+        for leg in legs:       # batched tails exist on unsharded models only: refused before anything touches a device
+            leg.net._not_sharded("refine_sources(source_batch > 1): push_window / flush_windows_clouds")
     sp = _rank_split(source_parallel, "source_parallel", any(getattr(leg.net, "is_sharded", False) for leg in legs))
     keyed = rand if isinstance(rand, PhiloxCloud) else None
     source_offset = int(source_offset)
@@ -1057,7 +1072,40 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
             if em is not None:                                                                                          # :966-967
                 yield leg.net.forward_fixed_source(em[0], em[1], None, None, None, locs_d, leg.x_grid_cart, xq, tq_d)[1]
 
-    cloud = (srcs, readouts, len(legs), tq_host.shape[0], X_offset_min, X_offset_range, ftrns1, (lat_range, lon_range, depth_range), dev)
+    ranges = (lat_range, lon_range, depth_range)
+    if source_batch > 1:
+        def window(leg, i):
+            return leg.embed(picks, srcs[i, 3], max_t, kernel_sig_t, dt)
+
+        def draws():           # (source, its draw) in source order; a plain `rand` is called for every source, the rank's own or not
+            for i in (range(b_lo, b_hi) if keyed is not None else range(srcs.shape[0])):
+                draw = None if keyed is not None else rand(n_rand_query, 3)
+                if b_lo <= i < b_hi:
+                    yield i, draw
+
+        refine_batch = _refine_batches_on_device_cloud(legs, srcs, window, tq_d.reshape(-1), X_offset_min, X_offset_range, ftrns1, ranges,
+                                                       dev, ftrns2_device, n_rand_query, keyed, source_offset)
+        nets = {id(leg.net): leg.net for leg in legs}.values()
+        before = [(net, net.window_batch) for net in nets]
+        found, batch = [], []
+        try:
+            for net in nets:
+                net.window_batch = source_batch
+            with torch.no_grad():
+                for item in draws():
+                    batch.append(item)
+                    if len(batch) == source_batch:
+                        found.append(refine_batch([i for i, _ in batch], [d for _, d in batch]))
+                        batch = []
+                if batch:
+                    found.append(refine_batch([i for i, _ in batch], [d for _, d in batch]))
+        finally:
+            for net, n in before:      # (the setter waits for the tails issued here before it changes the batch size)
+                if net.pending_windows == 0:
+                    net.window_batch = n
+        rows = torch.cat(found) if found else torch.zeros((0, 7), dtype=torch.float64, device=dev)
+        return _refine_ending(rows, sp, blocks if sp is not None else None, merge_timeout, legs, (b_lo, b_hi), srcs, tq_host, ftrns2)
+    cloud = (srcs, readouts, len(legs), tq_host.shape[0], X_offset_min, X_offset_range, ftrns1, ranges, dev)
     if ftrns2_device is not None:
         refine, to_geographic = _refine_on_device_cloud(*cloud, ftrns2_device, n_rand_query, keyed, source_offset), ftrns2
     else:
@@ -1073,6 +1121,11 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
                 if b_lo <= i < b_hi:
                     found.append(refine(i, draw))
     rows = torch.stack(found) if found else torch.zeros((0, 7), dtype=torch.float64, device=dev)
+    return _refine_ending(rows, sp, blocks if sp is not None else None, merge_timeout, legs, (b_lo, b_hi), srcs, tq_host, to_geographic)
+
+
+def _refine_ending(rows, sp, blocks, merge_timeout, legs, block, srcs, tq_host, to_geographic):
+    """The end of `refine_sources`: this rank's device rows [hi - lo, 7] -> what the call returns."""
     if sp is not None and sp.collective:
         found = _gather_blocks(rows, blocks, sp.group, merge_timeout)
     else:
@@ -1080,7 +1133,7 @@ def refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offs
     for leg in legs:       # a copy to the host has waited for the device (after the collective, so that a rank that raises here
         leg.check()        # leaves no other rank waiting): the verdicts of every window of this rank's pass are in
     if sp is not None and not sp.collective:
-        return found, (b_lo, b_hi)
+        return found, block
     return refined_from_found(found, srcs, tq_host, to_geographic)
 
 
@@ -1550,6 +1603,26 @@ def _inside_region(X, ranges):
             & (X[:, 2] > ranges[2][0]) & (X[:, 2] < ranges[2][1]))
 
 
+def _staged_clouds(src_cart, off_rng, off_min, n_rand_query, dev):
+    """`staged_cloud(i, draw)` of the device-cloud refine pass with a host draw: source i's cloud (Xc float64 [n, 3], its float32 rounding)
+    from the host's `draw`, which crosses through one of two pinned buffers taken in turn."""
+    off_rng_d, off_min_d = torch.as_tensor(off_rng, device=dev), torch.as_tensor(off_min, device=dev)
+    src_cart_d = torch.from_numpy(src_cart).to(dev) if src_cart is not None else None
+    stage, stage_ev = _pinned_pair(n_rand_query, dev), [None, None]
+
+    def staged_cloud(i, draw):
+        k = i % 2
+        if stage_ev[k] is not None:
+            stage_ev[k].synchronize()              # the copy that last read this staging buffer (two sources ago) has finished
+        stage[k].numpy()[...] = draw                                                                              # the host's draw, float64
+        r = stage[k].to(dev, non_blocking=True)
+        stage_ev[k] = torch.cuda.Event()
+        stage_ev[k].record(torch.cuda.current_stream(dev))       # the stream of `dev` the copy was issued on
+        Xc_d = src_cart_d[i:i + 1] + (r * off_rng_d + off_min_d)                                                  # :929
+        return Xc_d, Xc_d.float()
+    return staged_cloud
+
+
 def _refine_on_device_cloud(srcs, readouts, n_legs, n_t, X_offset_min, X_offset_range, ftrns1, ranges, dev, ftrns2_device, n_rand_query,
                             keyed=None, source_offset=0):
     """`refine(i, draw)` of `refine_sources(ftrns2_device=...)`: source i's row float64 [7] on the device = (query row, offset index,
@@ -1562,24 +1635,11 @@ def _refine_on_device_cloud(srcs, readouts, n_legs, n_t, X_offset_min, X_offset_
     off_rng = np.asarray(X_offset_range, dtype=np.float64).reshape(1, 3)
     off_min = np.asarray(X_offset_min, dtype=np.float64).reshape(1, 3)
     src_cart = np.ascontiguousarray(ftrns1(srcs[:, 0:3]), dtype=np.float64).reshape(-1, 3) if srcs.shape[0] else None
-    if keyed is None:          # the staged path's device copies and pinned pair; the keyed path passes the same numbers by value
-        off_rng_d, off_min_d = torch.as_tensor(off_rng, device=dev), torch.as_tensor(off_min, device=dev)
-        src_cart_d = torch.from_numpy(src_cart).to(dev) if srcs.shape[0] else None
-        stage, stage_ev = _pinned_pair(n_rand_query, dev), [None, None]
+    # the staged path's device copies and pinned pair; the keyed path passes the same numbers by value
+    staged_cloud = None if keyed is not None else _staged_clouds(src_cart, off_rng, off_min, n_rand_query, dev)
     if n_legs > postproc.REFINE_SELECT_MAX_LEGS:
         raise ValueError("refine_sources: at most %d grid legs with ftrns2_device" % postproc.REFINE_SELECT_MAX_LEGS)
     sel_scratch = postproc.refine_select_scratch(dev)
-
-    def staged_cloud(i, draw):
-        k = i % 2
-        if stage_ev[k] is not None:
-            stage_ev[k].synchronize()              # the copy that last read this staging buffer (two sources ago) has finished
-        stage[k].numpy()[...] = draw                                                                              # the host's draw, float64
-        r = stage[k].to(dev, non_blocking=True)
-        stage_ev[k] = torch.cuda.Event()
-        stage_ev[k].record(torch.cuda.current_stream(dev))       # the stream of `dev` the copy was issued on
-        Xc_d = src_cart_d[i:i + 1] + (r * off_rng_d + off_min_d)                                                  # :929
-        return Xc_d, Xc_d.float()
 
     def refine(i, draw):
         # Nothing here waits for the device (round 5, tools/sync_probe_day.py: eight waits per source before -- pageable copies, the
@@ -1598,6 +1658,71 @@ def _refine_on_device_cloud(srcs, readouts, n_legs, n_t, X_offset_min, X_offset_
         sel = postproc.refine_select_device(xs, (xq.shape[0], n_t), keep, float(n_legs), scratch=sel_scratch)      # :972-978
         return torch.cat((sel, Xc_d.index_select(0, sel[0:1].long()).view(3)))
     return refine
+
+
+REFINE_BATCH_MAX = 16      # sources per batched tail of `refine_sources(source_batch=)`: a tail batch holds at most 16 windows
+
+
+def _check_source_batch(source_batch, ftrns2_device):
+    """`source_batch` of `refine_sources` as an int: 1, or 2..REFINE_BATCH_MAX with `ftrns2_device`; ValueError otherwise."""
+    if isinstance(source_batch, bool) or not isinstance(source_batch, (int, np.integer)) or not 1 <= int(source_batch) <= REFINE_BATCH_MAX:
+        raise ValueError("refine_sources: source_batch must be an integer in [1, %d], got %r" % (REFINE_BATCH_MAX, source_batch))
+    if int(source_batch) > 1 and ftrns2_device is None:
+        raise ValueError("refine_sources: source_batch > 1 needs ftrns2_device (the batch runs on the device branch's clouds)")
+    return int(source_batch)
+
+
+def _refine_batches_on_device_cloud(legs, srcs, window, tq_d, X_offset_min, X_offset_range, ftrns1, ranges, dev, ftrns2_device,
+                                    n_rand_query, keyed, source_offset):
+    """`refine_batch(ids, draws)` of `refine_sources(source_batch=B)`: the rows float64 [len(ids), 7] of the consecutive sources `ids`, each
+    the row `_refine_on_device_cloud` makes of that source alone, from one cloud launch, one batched tail per leg (`push_window` per
+    source whose window holds a pick, `flush_windows_clouds` with every window at its own cloud) and one select launch pair.
+    `window(leg, i)`: (Slice, Mask) of source i's window on `leg`, or None without a pick. `draws`: the sources' `rand` draws (None
+    with `keyed`)."""
+    from . import postproc
+    if int(n_rand_query) < 1:
+        raise ValueError("refine_sources: n_rand_query must be >= 1")
+    n_legs, n_t = len(legs), int(tq_d.shape[0])
+    if n_legs > postproc.REFINE_SELECT_MAX_LEGS:
+        raise ValueError("refine_sources: at most %d grid legs with ftrns2_device" % postproc.REFINE_SELECT_MAX_LEGS)
+    off_rng = np.asarray(X_offset_range, dtype=np.float64).reshape(1, 3)
+    off_min = np.asarray(X_offset_min, dtype=np.float64).reshape(1, 3)
+    src_cart = np.ascontiguousarray(ftrns1(srcs[:, 0:3]), dtype=np.float64).reshape(-1, 3) if srcs.shape[0] else None
+    staged = None if keyed is not None else _staged_clouds(src_cart, off_rng, off_min, n_rand_query, dev)
+    sel_scratch = postproc.refine_select_batch_scratch(dev, REFINE_BATCH_MAX)
+    Q = int(n_rand_query)
+
+    def refine_batch(ids, draws):
+        nb = len(ids)
+        if keyed is not None:                                                                                       # :929, :934
+            Xc, xq = postproc.refine_cloud_batch_device(keyed.key, source_offset + ids[0], nb, Q, src_cart[ids[0]:ids[0] + nb], off_rng,
+                                                        off_min, dev)
+        else:
+            clouds = [staged(i, draw) for i, draw in zip(ids, draws)]
+            Xc, xq = torch.stack([c[0] for c in clouds]), torch.stack([c[1] for c in clouds])
+        # the user's transform per source, on the slice the single form hands it: a batched call need not give the same bits
+        keep = torch.stack([_inside_region(ftrns2_device(Xc[b]), ranges) for b in range(nb)])
+        table = np.zeros((nb, n_legs), dtype=np.int64)
+        held = []                                            # the read-outs the table points into, alive until the select is issued
+        main = torch.cuda.current_stream(dev)
+        for l, leg in enumerate(legs):
+            pushed = []
+            for b, i in enumerate(ids):
+                em = window(leg, i)
+                if em is not None:                                                                                  # :966-967
+                    leg.net.push_window(em[0], em[1])
+                    pushed.append(b)
+            if pushed:
+                _, x, done = leg.net.flush_windows_clouds(leg.x_grid_cart, xq, tq_d, pushed)
+                main.wait_event(done)
+                held.append(x)
+                for k, b in enumerate(pushed):
+                    table[b, l] = x[k].data_ptr()
+        sel = postproc.refine_select_batch_device(torch.from_numpy(table).to(dev), (Q, n_t), keep, float(n_legs),
+                                                  scratch=sel_scratch)                                              # :972-978
+        rows = sel[:, 0].long() + torch.arange(nb, device=dev) * Q
+        return torch.cat((sel, Xc.view(nb * Q, 3).index_select(0, rows)), dim=1)
+    return refine_batch
 
 
 def _refine_on_host_cloud(srcs, readouts, n_legs, n_t, X_offset_min, X_offset_range, ftrns1, ranges, dev, ftrns2):
@@ -1724,7 +1849,8 @@ def retained_after_marching(srcs_refined, ftrns1, tc_win, sp_win, scale_depth_cl
 def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, tq, max_t, ftrns1, ftrns2, lat_range, lon_range,
                             depth_range, X_offset_min, X_offset_range, n_rand_query, thresh, src_t_kernel, dt_win, break_win, tc_win,
                             sp_win, scale_depth_clustering=0.2, kernel_sig_t=synthetic.KERNEL_SIG_T, dt_embed=None, t_win_assoc=10.0,
-                            rand=None, ftrns2_device=None, detect_on_device=False, source_parallel=None, max_unit_cols=None):
+                            rand=None, ftrns2_device=None, detect_on_device=False, source_parallel=None, max_unit_cols=None,
+                            refine_batch=1):
     """Everything the caller does between the apply loop and the competitive assignment, with the network calls on the device
     (process_continuous_days.py:811-1105): peaks of the device-resident `Out_2` -> time groups -> LocalMarching (`postproc.
     detect_sources`, :811-891), the refine pass (`refine_sources`, :926-982), travel times of the refined sources (`trv(locs, srcs)`
@@ -1742,8 +1868,10 @@ def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, 
     the default one, or `(rank, world)` -- which, having no transport, must have world 1 here). Detection, both LocalMarchings and the
     `trv` calls are cheap and deterministic and run replicated on every rank; the returned dict equals the one-GPU dict on every rank.
     `max_unit_cols`: detection in units of at most that many columns (`postproc.detect_sources_device(max_unit_cols=...)`, the offline
-    twin of an `OnlineDetector` with the same argument); device detection on a dense `Out_2` only (ValueError otherwise)."""
+    twin of an `OnlineDetector` with the same argument); device detection on a dense `Out_2` only (ValueError otherwise).
+    `refine_batch`: `refine_sources(source_batch=...)`, the sources one batched tail refines together; the dict does not depend on it."""
     from . import postproc
+    refine_batch = _check_source_batch(refine_batch, ftrns2_device)
     if max_unit_cols is not None:
         if not detect_on_device:
             raise ValueError("detect_refine_associate: max_unit_cols needs detect_on_device=True (the host detection has no unit rule)")
@@ -1776,7 +1904,7 @@ def detect_refine_associate(legs, picks, Out_2, X_query, tsteps_abs, locs, trv, 
     locs_d = torch.as_tensor(locs).float().to(dev)
     srcs_refined, _ = refine_sources(legs, picks, srcs, locs_cart, tq, max_t, X_offset_min, X_offset_range, n_rand_query, ftrns1, ftrns2,
                                      lat_range, lon_range, depth_range, kernel_sig_t, dt_embed, rand, ftrns2_device,
-                                     source_parallel=source_parallel)
+                                     source_parallel=source_parallel, source_batch=refine_batch)
     with torch.no_grad():
         trv_out = trv(locs_d, torch.as_tensor(srcs_refined[:, 0:3]).float().to(dev)).detach()                           # :1004
     x_save = np.array([lat_range[0], lon_range[0], 0.0])                              # xx[0] of the meshgrid of :1008-1014
@@ -1839,7 +1967,8 @@ class OnlineCatalogue(object):
     `rand` must be a `PhiloxCloud` and `ftrns2_device` must be given (ValueError): a stateful draw or the host cloud has no offline twin
     that a sub-list reproduces. `pick_lists`: how the association pass makes its pick lists (`associate_sources`; "device" here, one launch per source: at the
     few hundred picks of a window it takes about half the time of the torch statements, profiles/EXPERIMENTS.md). There is no
-    `source_parallel`: a push carries a few sources. Every block of `day` must go through this object (a `day.feed` of the caller's
+    `source_parallel`: a push carries a few sources. `refine_batch`: `refine_sources(source_batch=...)` for the sources of a push; results
+    and saved state do not depend on it. Every block of `day` must go through this object (a `day.feed` of the caller's
     own loses columns: ValueError at the next call, nothing changed).
 
     A restart: `state_dict()` between any two `push` calls saves the day, the detector and this object in one call,
@@ -1847,13 +1976,14 @@ class OnlineCatalogue(object):
 
     def __init__(self, day, det, locs, trv, tq, ftrns1, ftrns2, lat_range, lon_range, depth_range, X_offset_min, X_offset_range,
                  n_rand_query, tc_win, sp_win, scale_depth_clustering=0.2, t_win_assoc=10.0, rand=None, ftrns2_device=None,
-                 pick_lists="device"):
+                 pick_lists="device", refine_batch=1):
         if not isinstance(rand, PhiloxCloud):
             raise ValueError("OnlineCatalogue: rand must be a PhiloxCloud (a source's draw must not depend on when it runs)")
         if ftrns2_device is None:
             raise ValueError("OnlineCatalogue: ftrns2_device is required (the keyed cloud is drawn on the device)")
         if pick_lists not in ("torch", "device"):
             raise ValueError('OnlineCatalogue: pick_lists must be "torch" or "device"')
+        self.refine_batch = _check_source_batch(refine_batch, ftrns2_device)       # how the sources run, not what comes out: not saved
         if len(det.tsteps_abs) != len(day.tsteps_abs) or not np.array_equal(det.tsteps_abs, day.tsteps_abs):
             raise ValueError("OnlineCatalogue: day and det must share one tsteps_abs")
         self.day, self.det, self.legs = day, det, list(day.lanes)
@@ -1890,7 +2020,8 @@ class OnlineCatalogue(object):
         day, legs = self.day, self.legs
         rows, _ = refine_sources(legs, day.picks, srcs, self.locs_cart, self.tq, day.max_t, self.offsets[0], self.offsets[1],
                                  self.n_rand_query, self.ftrns1, self.ftrns2, *self.ranges, day.kernel_sig_t, day.dt_embed, self.rand,
-                                 self.ftrns2_device, source_offset=self.n_released - self._pending.shape[0])
+                                 self.ftrns2_device, source_offset=self.n_released - self._pending.shape[0],
+                                 source_batch=self.refine_batch)
         dev = self.device
         with torch.no_grad():
             trv_out = self.trv(self.locs_d, torch.as_tensor(rows[:, 0:3]).float().to(dev)).detach()

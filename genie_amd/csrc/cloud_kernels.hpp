@@ -30,9 +30,11 @@ struct RcAxes {                                 // per axis: the source's Cartes
     double mx, my, mz;
 };
 
-__global__ __launch_bounds__(RC_BLOCK) void k_refine_cloud(unsigned long long key0, unsigned long long key1, unsigned long long source,
-                                                            long long n_elem, RcAxes a, double* __restrict__ r, double* __restrict__ xc,
-                                                            float* __restrict__ xq) {
+// One source's cloud around (sx, sy, sz) (a's own position is not read), by the workgroups of grid axis x. `vec`: r, xc and xq are 16-byte aligned, full blocks go out as 16-byte stores
+// (else element by element: the same values).
+__device__ __forceinline__ void rc_cloud(unsigned long long key0, unsigned long long key1, unsigned long long source, long long n_elem,
+                                         const double sx, const double sy, const double sz, const RcAxes& a, double* __restrict__ r, double* __restrict__ xc, float* __restrict__ xq,
+                                         const bool vec) {
 #pragma clang fp contract(off)
     const long long n_blk = (n_elem + 3) >> 2;
     const long long stride = (long long)gridDim.x * RC_BLOCK;
@@ -58,7 +60,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_refine_cloud(unsigned long long ke
             d[k] = (double)(u[k] >> 11) * (1.0 / 9007199254740992.0);
             const double rg = ax == 0 ? a.rx : (ax == 1 ? a.ry : a.rz);
             const double mn = ax == 0 ? a.mx : (ax == 1 ? a.my : a.mz);
-            const double s = ax == 0 ? a.sx : (ax == 1 ? a.sy : a.sz);
+            const double s = ax == 0 ? sx : (ax == 1 ? sy : sz);
             const double p = d[k] * rg;
             const double o = p + mn;
             x[k] = s + o;
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(RC_BLOCK) void k_refine_cloud(unsigned long long ke
             ax = ax == 2 ? 0 : ax + 1;
         }
         const long long j = b << 2;
-        if (j + 4 <= n_elem) {
+        if (vec && j + 4 <= n_elem) {
             if (r) {
                 *(double2*)(r + j) = make_double2(d[0], d[1]);
                 *(double2*)(r + j + 2) = make_double2(d[2], d[3]);
@@ -84,4 +86,22 @@ __global__ __launch_bounds__(RC_BLOCK) void k_refine_cloud(unsigned long long ke
                 }
         }
     }
+}
+
+__global__ __launch_bounds__(RC_BLOCK) void k_refine_cloud(unsigned long long key0, unsigned long long key1, unsigned long long source,
+                                                            long long n_elem, RcAxes a, double* __restrict__ r, double* __restrict__ xc,
+                                                            float* __restrict__ xq) {
+    rc_cloud(key0, key1, source, n_elem, a.sx, a.sy, a.sz, a, r, xc, xq, true);
+}
+
+// The clouds of the sources source0 .. source0 + gridDim.y - 1 in one launch (the refine pass with `source_batch` > 1): blockIdx.y = b draws
+// source0 + b around src[b] (a DEVICE array [n_batch, 3]: the ranges and minima are the batch's and stay in the arguments) into row block b
+// of xc / xq [n_batch, n_elem]. A row block starts n_elem elements after the one before, which is 16-byte aligned for every b only when
+// n_elem is a multiple of 4 (`vec`, said by the host); the values do not depend on it. Row block b = k_refine_cloud of source0 + b.
+__global__ __launch_bounds__(RC_BLOCK) void k_refine_cloud_b(unsigned long long key0, unsigned long long key1, unsigned long long source0,
+                                                              long long n_elem, const double* __restrict__ src, RcAxes a,
+                                                              double* __restrict__ xc, float* __restrict__ xq, int vec) {
+    const long long b = blockIdx.y;
+    rc_cloud(key0, key1, source0 + (unsigned long long)b, n_elem, src[3 * b + 0], src[3 * b + 1], src[3 * b + 2], a, nullptr, xc + b * n_elem,
+             xq + b * n_elem, vec != 0);
 }

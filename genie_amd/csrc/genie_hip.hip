@@ -3034,10 +3034,11 @@ int launch_readout_grid(genie_ctx* c, const StageCall& call, const RoArgs& a, bo
     k<<<tl_blocks(a.N, c->tail_cu_ro), 256, lds, st>>>(a);
     return GENIE_OK;
 }
-// query read-out (k_readout_m<1>), with or without the prefetch of the next tile's gathers
+// query read-out (k_readout_m<1>), with or without the prefetch of the next tile's gathers; with a query-set table (a.qset, batched tails
+// only: no prefetch) the instantiation that reads it
 int launch_readout_query(genie_ctx* c, bool prefetch, const RoArgs& a, hipStream_t st) {
     const int lds = (int)(sizeof(float) * ROM_LDS_FLOATS);
-    const auto k = prefetch ? k_readout_m<1, false, true> : k_readout_m<1>;
+    const auto k = a.qset ? k_readout_m<1, false, false, true> : (prefetch ? k_readout_m<1, false, true> : k_readout_m<1>);
     GENIE_TRY(raise_lds_limit(c, (const void*)k, lds));
     k<<<tl_blocks(a.N, c->tail_cu_ro), 256, lds, st>>>(a);
     return GENIE_OK;
@@ -3148,17 +3149,20 @@ int genie_readout_query_latent(genie_ctx* c, const float* x_spatial, const float
 // advance when those retire workgroups -- every launch costs the P-sized kernels about one of its own durations. Batched, the
 // fixed costs (weight images into LDS, launch, drain) are paid once per nwin windows. Window w uses workspace slot
 // slot0 + w (where genie_da_stage2_partials left its partials); results are bit-identical to the per-window calls.
-int genie_tail_batched(genie_ctx* c, int slot0, int nwin, const float* pos, const float* x_query, const int32_t* knn, int n_query,
-                       int k, const float* t_query, int n_t, float* x_spatial_out, float* y_out, float* x_out, void* ws,
-                       void* stream) {
+namespace {
+// genie_tail_batched (qset null: one query set [n_query, 3] for every window) and genie_tail_batched_q (window w reads set qset[w] of
+// x_query [n_sets, n_query, 3] / knn [n_sets, n_query, 10])
+int tail_batched_impl(genie_ctx* c, const std::string& who, int slot0, int nwin, const float* pos, const int32_t* qset, const float* x_query,
+                      const int32_t* knn, int n_query, int k, const float* t_query, int n_t, float* x_spatial_out, float* y_out,
+                      float* x_out, void* ws, void* stream) {
     int rc = check_ws(c, ws);
     if (rc) return rc;
-    if (!pos || !t_query || !x_spatial_out || !y_out) return fail(GENIE_ERR_ARG, "genie_tail_batched: null argument");
-    if (nwin < 1 || slot0 < 0 || slot0 + nwin > GENIE_NSLOT) return fail(GENIE_ERR_ARG, "genie_tail_batched: windows must fit slots [0, 33)");
-    if (n_t < 1 || n_t > RO_TMAX) return fail(GENIE_ERR_ARG, "genie_tail_batched: 1 <= n_t <= 10 required");
-    if (x_out && (!x_query || !knn || n_query < 1 || k != RO_K)) return fail(GENIE_ERR_ARG, "genie_tail_batched: bad query arguments");
-    if (c->G_ext != c->G) return fail(GENIE_ERR_STATE, "genie_tail_batched needs an unsharded source graph");
-    if ((long long)nwin * std::max(c->G, n_query) > 0x7fffffffLL) return fail(GENIE_ERR_ARG, "genie_tail_batched: batch too large");
+    if (!pos || !t_query || !x_spatial_out || !y_out) return fail(GENIE_ERR_ARG, who + ": null argument");
+    if (nwin < 1 || slot0 < 0 || slot0 + nwin > GENIE_NSLOT) return fail(GENIE_ERR_ARG, who + ": windows must fit slots [0, 33)");
+    if (n_t < 1 || n_t > RO_TMAX) return fail(GENIE_ERR_ARG, who + ": 1 <= n_t <= 10 required");
+    if (x_out && (!x_query || !knn || n_query < 1 || k != RO_K)) return fail(GENIE_ERR_ARG, who + ": bad query arguments");
+    if (c->G_ext != c->G) return fail(GENIE_ERR_STATE, who + " needs an unsharded source graph");
+    if ((long long)nwin * std::max(c->G, n_query) > 0x7fffffffLL) return fail(GENIE_ERR_ARG, who + ": batch too large");
     { int rcp = ensure_packed(c, (hipStream_t)stream); if (rcp) return rcp; }
     hipStream_t st = (hipStream_t)stream;
     float* w = (float*)ws;
@@ -3184,10 +3188,32 @@ int genie_tail_batched(genie_ctx* c, int slot0, int nwin, const float* pos, cons
         RoArgs q = a;
         q.N = nwin * n_query; q.Nw = n_query; q.x_grid = pos; q.x_query = x_query; q.knn = knn; q.out = x_out;
         q.img = c->packed[PL_RO1]; q.cv = w + c->o_cv + so; q.cv_ws = ss;
+        q.qset = qset; q.q_ws = n_query;
         if ((rc = launch_readout_query(c, false, q, st))) return rc;
     }
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
+}
+}  // namespace
+
+int genie_tail_batched(genie_ctx* c, int slot0, int nwin, const float* pos, const float* x_query, const int32_t* knn, int n_query,
+                       int k, const float* t_query, int n_t, float* x_spatial_out, float* y_out, float* x_out, void* ws,
+                       void* stream) {
+    return tail_batched_impl(c, "genie_tail_batched", slot0, nwin, pos, nullptr, x_query, knn, n_query, k, t_query, n_t, x_spatial_out, y_out,
+                             x_out, ws, stream);
+}
+
+// genie_tail_batched with a query set per window: the refine pass's batch of sources, each with its own cloud
+int genie_tail_batched_q(genie_ctx* c, int slot0, int nwin, const float* pos, int n_sets, const int32_t* qset, const float* x_query,
+                         const int32_t* knn, int n_query, int k, const float* t_query, int n_t, float* x_spatial_out, float* y_out,
+                         float* x_out, void* ws, void* stream) {
+    if (!qset) return fail(GENIE_ERR_ARG, "genie_tail_batched_q: null query-set table");
+    if (n_sets < 1) return fail(GENIE_ERR_ARG, "genie_tail_batched_q: n_sets >= 1 required");
+    if (!x_out) return fail(GENIE_ERR_ARG, "genie_tail_batched_q: null argument (the query read-out is what the table is for)");
+    if (n_query >= 1 && ((long long)n_sets * n_query > 0x7fffffffLL || (long long)std::max(nwin, 0) * n_query > 0x7fffffffLL))
+        return fail(GENIE_ERR_ARG, "genie_tail_batched_q: n_sets x n_query and nwin x n_query must fit an int");
+    return tail_batched_impl(c, "genie_tail_batched_q", slot0, nwin, pos, qset, x_query, knn, n_query, k, t_query, n_t, x_spatial_out, y_out,
+                             x_out, ws, stream);
 }
 
 int genie_embed_ntime(double t0, double max_t, double kernel_sig_t, double dt) {
@@ -4592,6 +4618,26 @@ int genie_refine_select(const float* const* x, int n_used, int64_t n_query, int 
     return GENIE_OK;
 }
 
+int genie_refine_select_batch(const float* const* x, int n_batch, int n_legs, int64_t n_query, int n_t, const uint8_t* keep, float n_scale,
+                              void* scratch, double* out, void* stream) {
+    if (n_batch < 1 || n_batch > 65535) return fail(GENIE_ERR_ARG, "genie_refine_select_batch: 1 <= n_batch <= 65535 required");
+    if (n_legs < 0 || n_legs > RS_MAX_LEGS) return fail(GENIE_ERR_ARG, "genie_refine_select_batch: 0 <= n_legs <= 32 required");
+    if (n_query < 0 || n_t < 1) return fail(GENIE_ERR_ARG, "genie_refine_select_batch: n_query >= 0 and n_t >= 1 required");
+    if (!(n_scale > 0.f) || !dbl_finite((double)n_scale)) return fail(GENIE_ERR_ARG, "genie_refine_select_batch: n_scale must be finite and > 0");
+    if (!out || !scratch || (n_legs > 0 && !x)) return fail(GENIE_ERR_ARG, "genie_refine_select_batch: null argument");
+    if ((((uintptr_t)scratch) & 15) != 0 || (((uintptr_t)out) & 7) != 0 || (((uintptr_t)x) & 7) != 0)
+        return fail(GENIE_ERR_ARG, "genie_refine_select_batch: scratch must be 16-byte, out and the table 8-byte aligned");
+    if (n_query > (int64_t)0x7fffffffffffffffLL / n_t / 2 / n_batch) return fail(GENIE_ERR_ARG, "genie_refine_select_batch: n_batch x n_query x n_t too large");
+    hipStream_t st = (hipStream_t)stream;
+    const long long n_elem = (long long)n_query * n_t;
+    const int nb = (int)std::min<long long>((n_elem + RS_SPAN - 1) / RS_SPAN, (long long)RS_MAX_WG);       // per source, as genie_refine_select
+    RsPartial* part = (RsPartial*)scratch;
+    if (nb > 0) k_refine_select_partial_b<<<dim3(nb, n_batch), RS_BLOCK, 0, st>>>(x, n_legs, (long long)n_query, n_t, keep, 1.0f / n_scale, part);
+    k_refine_select_final<<<n_batch, RS_BLOCK, 0, st>>>(part, nb, n_t, out);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
 int genie_refine_cloud(uint64_t key0, uint64_t key1, uint64_t source, int64_t n_query, double sx, double sy, double sz, double rx, double ry,
                        double rz, double mx, double my, double mz, double* r, double* xc, float* xq, void* stream) {
     if (n_query < 0) return fail(GENIE_ERR_ARG, "genie_refine_cloud: n_query >= 0 required");
@@ -4608,6 +4654,29 @@ int genie_refine_cloud(uint64_t key0, uint64_t key1, uint64_t source, int64_t n_
     a.mx = mx; a.my = my; a.mz = mz;
     k_refine_cloud<<<nb, RC_BLOCK, 0, (hipStream_t)stream>>>((unsigned long long)key0, (unsigned long long)key1, (unsigned long long)source, n_elem, a, r,
                                                             xc, xq);
+    HIP_TRY(hipGetLastError());
+    return GENIE_OK;
+}
+
+int genie_refine_cloud_batch(uint64_t key0, uint64_t key1, uint64_t source0, int n_batch, int64_t n_query, const double* src_cart, double rx,
+                             double ry, double rz, double mx, double my, double mz, double* xc, float* xq, void* stream) {
+    if (n_batch < 1 || n_batch > 65535) return fail(GENIE_ERR_ARG, "genie_refine_cloud_batch: 1 <= n_batch <= 65535 required");
+    if (n_query < 0) return fail(GENIE_ERR_ARG, "genie_refine_cloud_batch: n_query >= 0 required");
+    if (n_query == 0) return GENIE_OK;
+    if (!src_cart || !xc || !xq) return fail(GENIE_ERR_ARG, "genie_refine_cloud_batch: null argument");
+    if (n_query > (int64_t)0x7fffffffffffffffLL / 8 / n_batch) return fail(GENIE_ERR_ARG, "genie_refine_cloud_batch: n_batch x n_query too large");
+    if ((((uintptr_t)xc) | ((uintptr_t)xq)) & 15 || ((uintptr_t)src_cart) & 7)
+        return fail(GENIE_ERR_ARG, "genie_refine_cloud_batch: xc and xq must be 16-byte, src_cart 8-byte aligned");
+    const long long n_elem = 3 * (long long)n_query;
+    const long long n_blk = (n_elem + 3) / 4;                              // per source, as genie_refine_cloud
+    const int nb = (int)std::min<long long>((n_blk + RC_BLOCK - 1) / RC_BLOCK, (long long)RC_MAX_WG);
+    RcAxes a;
+    a.sx = a.sy = a.sz = 0.0;                                              // (the kernel takes them from src_cart)
+    a.rx = rx; a.ry = ry; a.rz = rz;
+    a.mx = mx; a.my = my; a.mz = mz;
+    k_refine_cloud_b<<<dim3(nb, n_batch), RC_BLOCK, 0, (hipStream_t)stream>>>((unsigned long long)key0, (unsigned long long)key1,
+                                                                             (unsigned long long)source0, n_elem, src_cart, a, xc, xq,
+                                                                             n_elem % 4 == 0 ? 1 : 0);
     HIP_TRY(hipGetLastError());
     return GENIE_OK;
 }

@@ -59,9 +59,10 @@ __device__ __forceinline__ void rs_block_reduce(float& v, long long& i, float* s
         for (int w = 1; w < RS_BLOCK / 64; ++w) rs_take(v, i, s_v[w], s_i[w]);
 }
 
-__global__ __launch_bounds__(RS_BLOCK) void k_refine_select_partial(RsLegs legs, int n_used, long long n_elem, int n_t,
-                                                                     const uint8_t* __restrict__ keep, float inv,
-                                                                     RsPartial* __restrict__ part) {
+// pass 1 of one source: workgroup blockIdx.x of gridDim.x over the n_elem elements of the read-outs legs.x[0 .. n_used), its pair to `part`
+template <class Legs>
+__device__ __forceinline__ void rs_partial(const Legs& legs, int n_used, long long n_elem, int n_t, const uint8_t* __restrict__ keep,
+                                           float inv, RsPartial* __restrict__ part) {
 #pragma clang fp contract(off)
     __shared__ float s_v[RS_BLOCK / 64];
     __shared__ long long s_i[RS_BLOCK / 64];
@@ -102,10 +103,19 @@ __global__ __launch_bounds__(RS_BLOCK) void k_refine_select_partial(RsLegs legs,
     }
 }
 
+__global__ __launch_bounds__(RS_BLOCK) void k_refine_select_partial(RsLegs legs, int n_used, long long n_elem, int n_t,
+                                                                     const uint8_t* __restrict__ keep, float inv,
+                                                                     RsPartial* __restrict__ part) {
+    rs_partial(legs, n_used, n_elem, n_t, keep, inv, part);
+}
+
+// pass 2: workgroup b (the single form launches one) reduces the n_part partials of source b into row b of out
 __global__ __launch_bounds__(RS_BLOCK) void k_refine_select_final(const RsPartial* __restrict__ part, int n_part, int n_t,
                                                                    double* __restrict__ out) {
     __shared__ float s_v[RS_BLOCK / 64];
     __shared__ long long s_i[RS_BLOCK / 64];
+    part += (long long)blockIdx.x * n_part;
+    out += 4 * (long long)blockIdx.x;
     float bv = 0.f;
     long long bi = RS_NONE;
     for (int k = threadIdx.x; k < n_part; k += RS_BLOCK) rs_take(bv, bi, part[k].v, part[k].i);
@@ -124,4 +134,37 @@ __global__ __launch_bounds__(RS_BLOCK) void k_refine_select_final(const RsPartia
             out[3] = 1.0;
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same selection for a batch of sources in one launch pair (the refine pass with `source_batch` > 1): blockIdx.y = source b, whose
+// read-outs are row b of a DEVICE table [n_batch, n_legs] of pointers (a batch has up to 16 x 32 of them: too many to travel by value),
+// a null entry = that leg produced no window for the source and is skipped, so the sum runs over the source's legs in leg order exactly as
+// the single form's `n_used` pointers do. keep [n_batch, n_query], partials [n_batch, gridDim.x], out [n_batch, 4]. Per source the grid
+// (gridDim.x = the single form's workgroup count), the element walk and the block reduction are the single form's (rs_partial), and
+// pass 2 is k_refine_select_final with one workgroup per source, so row b carries its bits; the reduction is order-independent anyway.
+// A workgroup compacts its source's non-null pointers into LDS once.
+// ------------------------------------------------------------------------------------------------
+struct RsLegsLds {
+    const float* const* x;
+};
+
+__global__ __launch_bounds__(RS_BLOCK) void k_refine_select_partial_b(const float* const* __restrict__ table, int n_legs, long long n_query,
+                                                                       int n_t, const uint8_t* __restrict__ keep, float inv,
+                                                                       RsPartial* __restrict__ part) {
+    __shared__ const float* s_x[RS_MAX_LEGS];
+    __shared__ int s_used;
+    const int b = blockIdx.y;
+    if (threadIdx.x == 0) {
+        int u = 0;
+        for (int l = 0; l < n_legs; ++l) {
+            const float* p = table[(long long)b * n_legs + l];
+            if (p) s_x[u++] = p;
+        }
+        s_used = u;
+    }
+    __syncthreads();
+    RsLegsLds legs;
+    legs.x = s_x;
+    rs_partial(legs, s_used, n_query * n_t, n_t, keep ? keep + (long long)b * n_query : nullptr, inv, part + (long long)b * gridDim.x);
 }

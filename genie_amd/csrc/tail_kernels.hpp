@@ -68,6 +68,8 @@ struct RoArgs {
     int o_q1w, o_q1b, o_q2w, o_q2b, o_c1w, o_c1b, o_c2w, o_c2b, o_v1w, o_v1b, o_v2w, o_v2b, o_p1w, o_p1b, o_p2w, o_p2b;
     int o_a1, o_a2, o_a3, o_a4, o_a5;
     int o_sq_w, o_sq_b, o_sc_w, o_sc_b, o_sv_w, o_sv_b, o_sp_w, o_sp_b, o_sa1, o_sa2;
+    const int32_t* qset;         // MODE 1, the QS form only (else null): [N / Nw] query set of window w -- it reads row qset[w] * q_ws + nl of
+    int q_ws;                    // x_query / knn ([n_sets, q_ws, ..]) where the plain form reads row nl; cv, x_spatial and `out` as ever
 };
 
 // Per-grid-node part of SpatialAttention's edge Linears (module.py:290-291): f_context / f_values act on
@@ -540,9 +542,11 @@ constexpr int RO_SCS = 68;      // floats per node in the score scratch: [5 head
 constexpr int ROM_LDS_FLOATS = GR_IMG_FLOATS + 5 * 256 + 10 * 80 + 4 * 16 * RO_SCS;
 // The body of a read-out workgroup: block `blk` of `nblk` over the 16-node tiles of `a`, LDS from `sm` (k_readout_m runs one head per
 // launch, k_readouts_m both heads in one).
-template <int MODE, bool WIDE, bool PF>      // PF (MODE 1): the gathered rows of head h + 1 requested before head h is worked on
+// QS (MODE 1): a query set per window (RoArgs::qset): the refine pass's batch, every window read out at its own cloud
+template <int MODE, bool WIDE, bool PF, bool QS = false>      // PF (MODE 1): the gathered rows of head h + 1 requested before head h is worked on
 __device__ __forceinline__ void ro_body(const RoArgs& a, const unsigned blk, const unsigned nblk, float* sm) {
     static_assert(!(WIDE && MODE != 0), "the fp64 form exists for the grid read-out (MODE 0)");
+    static_assert(!(QS && (MODE != 1 || PF)), "query sets belong to the query read-out of a batch, which takes no prefetch");
     typedef typename TlV<WIDE>::v V;
     typedef typename std::conditional<WIDE, double, float>::type R;
     constexpr int SCW = WIDE ? 2 : 1;        // the score scratch holds R values
@@ -625,11 +629,19 @@ __device__ __forceinline__ void ro_body(const RoArgs& a, const unsigned blk, con
             const int ncl = n_l < a.N ? n_l : a.N - 1;
             const int wq = ncl / a.Nw, nl = ncl - wq * a.Nw;
             const float* cvw = a.cv + wq * a.cv_ws + 4 * ql;
-            const float xq0 = a.x_query[nl * 3 + 0], xq1 = a.x_query[nl * 3 + 1], xq2 = a.x_query[nl * 3 + 2];
+            // QS: the window's own query set. A 16-query tile straddles two windows when Nw % 16 != 0, so the set is per lane, as wq is
+            const float* xqr = a.x_query;
+            const int32_t* knr = a.knn;
+            if (QS) {
+                const long long qo = (long long)a.qset[wq] * a.q_ws;
+                xqr += qo * 3;
+                knr += qo * RO_K;
+            }
+            const float xq0 = xqr[nl * 3 + 0], xq1 = xqr[nl * 3 + 1], xq2 = xqr[nl * 3 + 2];
             int jn[RO_K];
             float e[RO_K][3];
 #pragma unroll
-            for (int k = 0; k < RO_K; ++k) jn[k] = a.knn[(long long)nl * RO_K + k];
+            for (int k = 0; k < RO_K; ++k) jn[k] = knr[(long long)nl * RO_K + k];
 #pragma unroll
             for (int k = 0; k < RO_K; ++k) {                                            // edge_attr  :283
                 e[k][0] = (xq0 - a.x_grid[jn[k] * 3 + 0]) / a.scale_rel;
@@ -759,10 +771,10 @@ __device__ __forceinline__ void ro_body(const RoArgs& a, const unsigned blk, con
         GSYNC();
     }
 }
-template <int MODE, bool WIDE = false, bool PF = false>
+template <int MODE, bool WIDE = false, bool PF = false, bool QS = false>
 __global__ __launch_bounds__(256) void k_readout_m(RoArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    ro_body<MODE, WIDE, PF>(a, blockIdx.x, gridDim.x, sm);
+    ro_body<MODE, WIDE, PF, QS>(a, blockIdx.x, gridDim.x, sm);
 }
 // Both heads of one window in ONE launch: given x_spatial (and cv) they are independent, and a window's 16-node tiles of both (625 + 625
 // one-wave tiles at 10 000 nodes / queries) fit on the chip together, so they run side by side without a second stream. Workgroups

@@ -1215,28 +1215,51 @@ class HipPath(object):
         """The G-sized tail of all pending windows (genie_tail_batched) on a side stream, where it overlaps the P-sized kernels
         of the following windows. Returns (y [n, G, T, 1], x [n, Q, T, 1], done_event), produced on `self.side_stream`: consume
         them there or after the event. Consecutive tails alternate between two side streams."""
+        x_query = _f32(x_query, "x_query")
+        return self._windows_flush("windows_flush", pos, x_query, self._knn_table(knn_idx, x_query.shape[0]), None, t_query)
+
+    def windows_flush_clouds(self, pos, x_query, knn_idx, qset, t_query):
+        """`windows_flush` with a query set per window (genie_tail_batched_q): `x_query` [n_sets, Q, 3], `knn_idx` int32 [n_sets, Q, 10],
+        `qset` an int32 GPU tensor with one entry in [0, n_sets) per pending window, in push order (the caller has checked the values: the
+        library reads the rows they name). Window w is read out at the queries of set qset[w]; the streams, events and slots are those of
+        `windows_flush`. Returns (y [n, G, T, 1], x [n, Q, T, 1], done_event)."""
+        x_query = _f32(x_query, "x_query")
+        if x_query.dim() != 3 or x_query.shape[0] < 1 or x_query.shape[2] != 3:
+            raise ValueError("x_query must be [n_sets, Q, 3] with n_sets >= 1")
+        n_sets, nq = int(x_query.shape[0]), int(x_query.shape[1])
+        knn_idx = self._knn_table(knn_idx.reshape(-1, 10) if knn_idx.dim() == 3 else knn_idx, n_sets * nq)
+        bt = getattr(self, "_bt", None)
+        if not (torch.is_tensor(qset) and qset.is_cuda and qset.dtype == torch.int32 and qset.dim() == 1
+                and bt is not None and qset.numel() == bt["n"]):
+            raise ValueError("qset must be an int32 GPU tensor with one entry per pending window")
+        return self._windows_flush("windows_flush_clouds", pos, x_query, knn_idx, qset.contiguous(), t_query)
+
+    def _windows_flush(self, who, pos, x_query, knn_idx, qset, t_query):
+        """The body of `windows_flush` (`qset` None: one query set [Q, 3]) and `windows_flush_clouds` (`x_query` [n_sets, Q, 3])."""
         bt = getattr(self, "_bt", None)
         if bt is None or bt["n"] == 0:
-            raise RuntimeError("windows_flush: no pending window")
+            raise RuntimeError("%s: no pending window" % who)
         n = bt["n"]
         pos = _f32(pos, "pos", (self.n_grid, 3))
-        x_query = _f32(x_query, "x_query")
-        nq = x_query.shape[0]
-        knn_idx = self._knn_table(knn_idx, nq)
+        nq = x_query.shape[-2]
         tq = _f32(t_query, "t_query").reshape(-1)
         main = torch.cuda.current_stream(self.device)
         ev = torch.cuda.Event()
         ev.record(main)
         side = self.side_stream = bt["streams"][bt["turn"]]
         side.wait_event(ev)
-        self._crosses_to(side, pos, x_query, knn_idx, tq)
+        self._crosses_to(side, pos, x_query, knn_idx, tq, qset)
         with torch.cuda.stream(side):
             x_spatial = torch.empty((n, self.n_grid, 30), dtype=torch.float32, device=self.device)
             y = torch.empty((n, self.n_grid, tq.numel(), 1), dtype=torch.float32, device=self.device)
             x = torch.empty((n, nq, tq.numel(), 1), dtype=torch.float32, device=self.device)
-            _lib.check(self.lib.genie_tail_batched(self.ctx, bt["group"] * self.window_batch, n, _ptr(pos), _ptr(x_query), _ptr(knn_idx),
-                                                   nq, 10, _ptr(tq), tq.numel(), _ptr(x_spatial), _ptr(y), _ptr(x), self._ws_ptr,
-                                                   ctypes.c_void_p(side.cuda_stream)), "genie_tail_batched")
+            head = (self.ctx, bt["group"] * self.window_batch, n, _ptr(pos))
+            rest = (nq, 10, _ptr(tq), tq.numel(), _ptr(x_spatial), _ptr(y), _ptr(x), self._ws_ptr, ctypes.c_void_p(side.cuda_stream))
+            if qset is None:
+                _lib.check(self.lib.genie_tail_batched(*head, _ptr(x_query), _ptr(knn_idx), *rest), "genie_tail_batched")
+            else:
+                _lib.check(self.lib.genie_tail_batched_q(*head, int(x_query.shape[0]), _ptr(qset), _ptr(x_query), _ptr(knn_idx), *rest),
+                           "genie_tail_batched_q")
             done = torch.cuda.Event()
             done.record(side)
         self._crosses_to(main, y, x)

@@ -349,6 +349,17 @@ def knn_query_edges(x_context, x_query, k, index=None):
     return torch.stack([idx.reshape(-1), row_q], dim=0)
 
 
+def checked_qset(qset, n_pending, n_sets):
+    """The query-set table of `flush_windows_clouds` as int32 [n_pending]: a host list or array of integers, one per pending window, each in
+    [0, n_sets). ValueError otherwise: the library reads the rows the table names, so it is checked here, where its values are known."""
+    q = np.asarray(qset)
+    if q.ndim != 1 or q.shape[0] != int(n_pending) or (q.size and q.dtype.kind not in "iu"):
+        raise ValueError("flush_windows_clouds: qset must hold one integer per pending window (%d pending)" % int(n_pending))
+    if q.size and (int(q.min()) < 0 or int(q.max()) >= int(n_sets)):
+        raise ValueError("flush_windows_clouds: qset entries must lie in [0, %d)" % int(n_sets))
+    return np.ascontiguousarray(q, dtype=np.int32)
+
+
 class SpatialAttention(nn.Module):
     """Parameters of module.py:262-297 (kNN k=10 of the queries into the grid, per-edge q/c/v, segment softmax, mean over heads:
     k_ro_pre_m + k_readout_m<1>) and the cache of the query set's kNN table (genie_knn). `knn_index` (default False; set through the
@@ -1024,6 +1035,27 @@ class GCN_Detection_Network_extended(nn.Module):
         `self._hip.side_stream` (consume them there, or after `done_event.wait()`)."""
         knn = self.SpatialAttention.query_table(x_query_cart, x_temp_cuda_cart, 10)
         return self._hip.windows_flush(x_temp_cuda_cart, x_query_cart, knn, t_query)
+
+    def flush_windows_clouds(self, x_temp_cuda_cart, x_query_sets, t_query, qset):
+        """`flush_windows` with a query set per window (the refine pass: every source has its own cloud): `x_query_sets` [n_sets, Q, 3],
+        `qset` a host list or array with one entry in [0, n_sets) per pending window, in push order -- window w is read out at the queries
+        `x_query_sets[qset[w]]`. A wrong length or value raises ValueError before any launch. The kNN table of all sets is one exact
+        search (the rows of the per-set searches; through the context's cell index where `net.knn_index` asks for it and the sets together
+        reach its threshold). Returns (y [n, G, T, 1], x [n, Q, T, 1], done_event) as `flush_windows` does, bit-identical to the
+        per-window calls."""
+        if self._hip is None:
+            raise RuntimeError("call set_adjacencies(...) before forward_fixed*/forward_fixed_source")
+        if not torch.is_tensor(x_query_sets) or x_query_sets.dim() != 3 or x_query_sets.shape[0] < 1 or x_query_sets.shape[2] != 3:
+            raise ValueError("flush_windows_clouds: x_query_sets must be a tensor [n_sets, Q, 3] with n_sets >= 1")
+        n_sets = int(x_query_sets.shape[0])
+        q = checked_qset(qset, self.pending_windows, n_sets)
+        xq = _engine._f32(x_query_sets, "x_query")
+        flat = xq.view(-1, 3)
+        sa = self.SpatialAttention
+        indexed = sa.knn_index and flat.shape[0] >= _engine.KNN_INDEX_MIN_QUERIES
+        knn = _engine.knn_device(x_temp_cuda_cart, flat, 10, index=sa.context_index(x_temp_cuda_cart) if indexed else None)
+        qset_d = torch.from_numpy(q).to(xq.device)
+        return self._hip.windows_flush_clouds(x_temp_cuda_cart, xq, knn.view(n_sets, -1, 10), qset_d, t_query)
 
     @property
     def window_batch(self):

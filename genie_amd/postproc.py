@@ -955,3 +955,67 @@ def refine_cloud_device(key, source, n_query, src_cart, off_range, off_min, devi
     with torch.cuda.device(dev):
         _lib.check(_lib.load().genie_refine_cloud(k0, k1, source, n, *vec, _ptr(r), _ptr(Xc), _ptr(xq), _stream(dev)), "genie_refine_cloud")
     return (Xc, xq, r) if want_draw else (Xc, xq)
+
+
+# ------------------------------------------------------------------------------------------------
+# The two kernels above for a batch of sources in one launch (pair) each: `apply.refine_sources(source_batch=B)`.
+# ------------------------------------------------------------------------------------------------
+def refine_select_batch_scratch(device, n_batch):
+    """The scratch buffer of `refine_select_batch_device` for up to `n_batch` sources (uint8 GPU tensor, `n_batch` times the single form's)."""
+    return torch.empty(int(n_batch) * int(_lib.load().genie_refine_select_scratch_bytes()), dtype=torch.uint8, device=device)
+
+
+def refine_select_batch_device(table, shape, keep, n_scale, scratch=None):
+    """`refine_select_device` of B sources in one launch pair (genie_refine_select_batch): fp64 GPU tensor [B, 4] whose row b carries the
+    bits the single form gives for source b's read-outs. `table`: int64 GPU tensor [B, n_legs] of device addresses, entry (b, l) = the
+    `data_ptr()` of leg l's contiguous fp32 read-out [Q, n_t] (or [Q, n_t, 1]) of source b, or 0 where that leg produced no window for
+    it; the caller keeps those tensors alive and orders their producers before the current stream. `shape` = (Q, n_t); `keep`: bool /
+    uint8 GPU tensor [B, Q] or None (all kept); `n_scale`: the number of legs of the average. Nothing here waits for the device."""
+    Q, n_t = int(shape[0]), int(shape[1])
+    if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.int64 and table.dim() == 2 and table.is_contiguous()
+            and table.shape[0] >= 1):
+        raise ValueError("refine_select_batch_device: table must be a contiguous int64 GPU tensor [B, n_legs] with B >= 1")
+    B, n_legs = int(table.shape[0]), int(table.shape[1])
+    if n_legs > REFINE_SELECT_MAX_LEGS:
+        raise ValueError("refine_select_batch_device: at most %d read-outs per source" % REFINE_SELECT_MAX_LEGS)
+    dev = table.device
+    if keep is not None:
+        if not (torch.is_tensor(keep) and keep.is_cuda and keep.dtype in (torch.bool, torch.uint8) and tuple(keep.shape) == (B, Q)):
+            raise ValueError("refine_select_batch_device: keep must be a bool or uint8 GPU tensor [%d, %d]" % (B, Q))
+        keep = keep.contiguous()
+    lib = _lib.load()
+    need = B * int(lib.genie_refine_select_scratch_bytes())
+    if scratch is None:
+        scratch = refine_select_batch_scratch(dev, B)
+    elif scratch.numel() < need:
+        raise ValueError("refine_select_batch_device: scratch holds %d bytes, %d sources need %d" % (scratch.numel(), B, need))
+    out = torch.empty((B, 4), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.genie_refine_select_batch(_ptr(table), B, n_legs, Q, n_t, _ptr(keep), float(n_scale), _ptr(scratch), _ptr(out),
+                                                 _stream(dev)), "genie_refine_select_batch")
+    return out
+
+
+def refine_cloud_batch_device(key, source0, n_batch, n_query, src_cart, off_range, off_min, device):
+    """The query clouds of the candidate sources `source0 .. source0 + n_batch - 1` in one launch (genie_refine_cloud_batch): (Xc float64
+    [n_batch, n_query, 3], xq = Xc rounded to float32), row block b bit-equal to `refine_cloud_device(key, source0 + b, n_query,
+    src_cart[b], off_range, off_min, device)`. `src_cart`: host numbers [n_batch, 3] (one small copy to the device, in stream order);
+    `off_range`, `off_min`: three host numbers each."""
+    k0, k1 = philox_key_words(key)
+    source0, B, n = int(source0), int(n_batch), int(n_query)
+    if B < 1:
+        raise ValueError("refine_cloud_batch_device: n_batch must be >= 1")
+    if not (0 <= source0 and source0 + B - 1 < 1 << 64):
+        raise ValueError("refine_cloud_batch_device: sources must lie in [0, 2**64)")
+    if n < 0:
+        raise ValueError("refine_cloud_batch_device: n_query must be >= 0")
+    src = np.ascontiguousarray(np.asarray(src_cart, dtype=np.float64).reshape(B, 3))
+    vec = [float(v) for a in (off_range, off_min) for v in np.asarray(a, dtype=np.float64).reshape(3)]
+    dev = torch.device(device)
+    src_d = torch.from_numpy(src).to(dev)
+    Xc = torch.empty((B, n, 3), dtype=torch.float64, device=dev)
+    xq = torch.empty((B, n, 3), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().genie_refine_cloud_batch(k0, k1, source0, B, n, _ptr(src_d), *vec, _ptr(Xc), _ptr(xq), _stream(dev)),
+                   "genie_refine_cloud_batch")
+    return Xc, xq

@@ -191,6 +191,17 @@ int genie_set_slot(genie_ctx* ctx, int slot);
 int genie_tail_batched(genie_ctx* ctx, int slot0, int nwin, const float* pos, const float* x_query, const int32_t* knn,
                        int n_query, int k, const float* t_query, int n_t, float* x_spatial_out, float* y_out, float* x_out,
                        void* ws, void* stream);
+/* genie_tail_batched with a query set per window (the refine pass: every candidate source has its own query cloud): x_query [n_sets,
+ * n_query, 3], knn [n_sets, n_query, 10] and qset [nwin] int32 on the device; window w is read out at the queries of set qset[w], i.e. its
+ * query nl reads row qset[w] * n_query + nl of x_query and knn, and x_out [nwin, n_query, n_t] row w is genie_tail_batched's for that
+ * set. Everything else (slots, x_spatial_out, y_out, streams) as genie_tail_batched; bit-identical to the per-window calls. CONTRACT:
+ * every qset[w] lies in [0, n_sets). The library does not read the table on the host and the kernel does not check it: a caller that
+ * knows the values checks them (the Python binding does, before any launch). Refused with GENIE_ERR_ARG: a null qset, n_sets < 1, a
+ * null x_out, n_sets * n_query or nwin * n_query above INT_MAX, and what genie_tail_batched refuses (a sharded context:
+ * GENIE_ERR_STATE). */
+int genie_tail_batched_q(genie_ctx* ctx, int slot0, int nwin, const float* pos, int n_sets, const int32_t* qset, const float* x_query,
+                         const int32_t* knn, int n_query, int k, const float* t_query, int n_t, float* x_spatial_out, float* y_out,
+                         float* x_out, void* ws, void* stream);
 /* Temporal scale of TemporalAttention: `scale_t = 3 * kernel_sig_t` (module.py:40); default 9.0. */
 int genie_set_scale_t(genie_ctx* ctx, float scale_t);
 /* `use_absolute_pos: True` (config.yaml:92; module.py:916, :971, :1007): every product node's input gets its station position and
@@ -873,6 +884,14 @@ size_t genie_refine_select_scratch_bytes(void);
 int genie_refine_select(const float* const* x, int n_used, int64_t n_query, int n_t, const uint8_t* keep, float n_scale, void* scratch,
                         double* out, void* stream);
 
+/* genie_refine_select for a batch of sources in one launch pair: row b of out [n_batch, 4] carries the bits genie_refine_select gives for
+ * source b alone. x: DEVICE table [n_batch, n_legs] of device pointers, entry (b, l) = leg l's read-out fp32 [n_query, n_t] of source b,
+ * or NULL where that leg produced no window for the source: source b's sum runs over its non-null legs in leg order (the single form's
+ * n_used pointers); a row of NULLs is an all-zero acc. keep [n_batch, n_query] uint8 on the device or NULL; scratch: n_batch *
+ * genie_refine_select_scratch_bytes() bytes, 16-byte aligned. 1 <= n_batch <= 65535, 0 <= n_legs <= 32; otherwise as the single form. */
+int genie_refine_select_batch(const float* const* x, int n_batch, int n_legs, int64_t n_query, int n_t, const uint8_t* keep, float n_scale,
+                              void* scratch, double* out, void* stream);
+
 /* The query cloud of one candidate source of the refine pass (process_continuous_days.py:929, :934), drawn on the device by a keyed
  * counter-based generator, one launch per source and nothing copied from the host:
  *   r   = np.random.Generator(np.random.Philox(key=[key0, key1], counter=[0, source, 0, 0])).random((n_query, 3))     as bits: flat
@@ -891,6 +910,13 @@ int genie_refine_select(const float* const* x, int n_used, int64_t n_query, int 
  * pointer that is not 16-byte aligned, n_query > 2^60) return GENIE_ERR_ARG before any launch. */
 int genie_refine_cloud(uint64_t key0, uint64_t key1, uint64_t source, int64_t n_query, double sx, double sy, double sz, double rx, double ry,
                        double rz, double mx, double my, double mz, double* r, double* xc, float* xq, void* stream);
+
+/* genie_refine_cloud for the sources source0 .. source0 + n_batch - 1 in one launch: row block b of xc [n_batch, n_query, 3] fp64 and xq
+ * [n_batch, n_query, 3] fp32 carries the bits of genie_refine_cloud(key0, key1, source0 + b, n_query, src_cart[b], ...). src_cart
+ * [n_batch, 3] fp64 ON THE DEVICE (8-byte aligned): the sources' Cartesian positions; the ranges and minima are the batch's. xc and xq
+ * 16-byte aligned. The draw itself is not stored. 1 <= n_batch <= 65535; n_query == 0 returns GENIE_OK without a launch. */
+int genie_refine_cloud_batch(uint64_t key0, uint64_t key1, uint64_t source0, int n_batch, int64_t n_query, const double* src_cart, double rx,
+                             double ry, double rz, double mx, double my, double mz, double* xc, float* xq, void* stream);
 
 /* The optimizer step of a training batch in one launch: the ranks' gradient parts summed in rank order, then torch.optim.Adam's update
  * (defaults: no weight decay, no amsgrad, not maximize; train_GENIE_model.py:1383, :1861) on flat arrays. Needs no context. Per element j:
